@@ -16,11 +16,21 @@ images (one kernel launch; 4.8 GB of distinct input+output per step, so nothing 
 the 256 MiB Infinity Cache).  Every rank owns its own batch (images shard by index, no
 collective on the data path): weak scaling.
 
-Prints ONE JSON line on rank 0:  metric = Mpixels/s decoded (whole job), plus
+Prints ONE JSON line on rank 0:  metric = Mpixels/s decoded (whole job), ms_per_step = wall time of
+one timed step (the K timed steps / K), plus
   roofline     achieved = algorithmic bytes per launch / mean kernel time (HIP events on the
                launch stream around sampled timed steps), against the 8 TB/s HBM3E peak;
                traffic = HBM bytes per launch from the committed PMC passes (profiles/), only
-               when they were taken with THIS jb_kernels.hip (content hash), else null;
+               when they were taken with THIS jb_kernels.hip (content hash), else null.
+A plain run does only that: set up, pre-condition, warm up, time the K steps, print the line.
+
+--dump-outputs DIR  after the timed steps, rank 0 writes what its last timed step handed back (the
+               RGB images of that step's batch) as DIR/<name>.npy (dump_outputs(): exact per-row sums
+               of all of it plus a fixed, seeded sample of its bytes).  The inputs are seeded, so two
+               builds run with the same arguments can be compared output for output.
+
+--full adds the measurements that take runs of their own (--no-configs / --no-e2e /
+--no-cpu-baseline leave single ones out):
   configs      (N=1) the other single-GPU BASELINE.json configurations timed as stated: config 2
                = ONE 1920x1080 4:4:4 image per launch, config 3 = ONE 4096x4096 4:2:0 image per
                launch, both COLD (rotating buffer sets totalling > 512 MiB, twice the Infinity
@@ -127,6 +137,34 @@ def cpu_baseline(width, height, hs, vs, coef, qtabs, budget_s=12.0):
     out["port_allcores_threads"] = nthr
     out["host_cpus"] = ncores
     return out
+
+
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs writes at most this much in all
+DUMP_SAMPLE_BYTES = 1 << 23    # image bytes in the seeded sample (32 MB as float32)
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir, np, torch, res, rgb_t):
+    """--dump-outputs: the images one step of the timed path handed back, rgb_t = uint8 [images, h, pitch]
+    on the device (pixel row y of image i = rgb_t[i, y, :3w]), as float arrays:
+      rgb_row_sums.npy  float64 [images, h]  the sum of every pixel row's 3w bytes (exact): all of the output
+      rgb_sample.npy    float32 [n]          the bytes at n positions drawn with a fixed seed from the
+                                             images' pixel bytes (row-major over [images, h, 3w], ascending)
+    n = min(DUMP_SAMPLE_BYTES, all pixel bytes), less if the row sums would push the total over
+    DUMP_BUDGET_BYTES; the positions depend only on the workload, so equal arguments give equal files."""
+    os.makedirs(out_dir, exist_ok=True)
+    row = 3 * res.w
+    pix = rgb_t[:, :, :row]
+    sums = pix.sum(dim=2, dtype=torch.int64).cpu().numpy().astype(np.float64)
+    np.save(os.path.join(out_dir, "rgb_row_sums.npy"), sums)
+    total = res.nimg * res.h * row
+    n = max(0, min(DUMP_SAMPLE_BYTES, total, (DUMP_BUDGET_BYTES - sums.nbytes) // 4))
+    pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, size=n, dtype=np.int64))
+    img, rest = np.divmod(pos, res.h * row)
+    y, x = np.divmod(rest, row)
+    off = torch.from_numpy(img * (res.h * res.pitch) + y * res.pitch + x).to(rgb_t.device)
+    sample = rgb_t.reshape(-1)[off].to(torch.float32).cpu().numpy()
+    np.save(os.path.join(out_dir, "rgb_sample.npy"), sample)
 
 
 def fan_out(n_gpus, argv):
@@ -343,9 +381,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--precondition", type=int, default=400,
                     help="untimed launches before the warm-up steps (lets clocks/power settle)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the extra per-config measurements (N=1)")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the decode(path) batches over JPEG files (configs 4 and 5 end to end)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run configs (N=1), end_to_end and cpu_baseline (N=1); "
+                         "a plain run measures the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the extra per-config measurements (N=1)")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the decode(path) batches over JPEG files (configs 4 and 5 end to end)")
     ap.add_argument("--images-per-step", type=int, default=IMAGES_PER_STEP)
     ap.add_argument("--sets", type=int, default=1, help="rotating buffer sets (cold single-image runs: > 512 MiB in total)")
     ap.add_argument("--workload", default="4096x4096-444",
@@ -448,6 +491,10 @@ def main():
     nimg = args.images_per_step
     head = Resident(jb, torch, dev, args.workload, nimg, args.sets, seed=rank)
     elapsed, kern_ms = run(head, args.steps, args.warmup, args.precondition, every)
+    if args.dump_outputs and rank == 0:
+        # the last timed launch wrote buffer set (launches - 1) % sets
+        last = (args.precondition + args.warmup + args.steps - 1) % head.sets
+        dump_outputs(args.dump_outputs, np, torch, head, head.tensors[last][1])
     from jpeg_decoder_amd.shard import job_throughput
     total_pixels, elapsed = job_throughput(dist, dev if backend == "nccl" else torch.device("cpu"),
                                            head.pixels * args.steps, elapsed)
@@ -460,7 +507,7 @@ def main():
     torch.cuda.empty_cache()
 
     e2e = None
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         import tempfile
         with tempfile.TemporaryDirectory(dir="/tmp") as tmpdir:
             e2e = end_to_end(jb, np, torch, dist, local_rank, dev if backend == "nccl" else torch.device("cpu"), rank, world, tmpdir)
@@ -497,7 +544,7 @@ def main():
                          "kernel_ms_mean": round(mean_ms, 4), "kernel_ms_median": round(float(np.median(kern_ms)), 4), "kernel_ms_min": round(float(np.min(kern_ms)), 4),
                          "kernel_gpix_s": round(nimg * WIDTH * HEIGHT / (mean_ms * 1e-3) / 1e9, 2)},
         }
-        if n_gpus == 1 and not args.no_configs:
+        if args.full and n_gpus == 1 and not args.no_configs:
             # the other single-GPU configurations of BASELINE.json, timed as stated (events around
             # every launch, median of >= 200 launches; cold entries rotate over > 512 MiB of buffers)
             cfgs = {}
@@ -518,7 +565,7 @@ def main():
             line["configs"] = cfgs
         if e2e is not None:
             line["end_to_end"] = e2e
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(WIDTH, HEIGHT, HS, VS, head_coef, head_q)
         print(json.dumps(line), flush=True)
     ctx.close()

@@ -9,13 +9,19 @@ Fixtures written:
   tests/golden/images/*.jpg      the reference's own sample files (data files, images/)
   tests/golden/<name>.npz        per baseline image: desc, qtabs, coefficient blocks after
                                  decodeHuffman() (int16, decode order), RGB after
-                                 YCbCrToRGB() (cropped), sha256 of the RGB bytes
+                                 YCbCrToRGB() (cropped), sha256 of the RGB bytes; where
+                                 that file would pass 1 MiB, the RGB rows go to bands
+                                 <name>.rgb<k>.npz, k = 0, 1, ... instead
   tests/golden/kat_blocks.npz    known-answer vectors through the reference hot path on
                                  synthetic blocks: DC-only, single-coefficient impulses,
                                  max-magnitude, truncation-stress and full-range random blocks
                                  in 4:4:4 / 4:2:2 / 4:4:0 / 4:2:0 with ragged sizes
   tests/golden/manifest.json     sizes + hashes + reference timings measured here
+  tests/golden/ref_results.json  sha256 digests of what the reference returns in the cases of
+                                 tests/test_oracle.py that compare with it directly (random blocks,
+                                 the build's writer streams through its reader), for runs without it
 """
+import glob
 import hashlib
 import json
 import os
@@ -32,6 +38,7 @@ from jpeg_decoder_amd import synth  # noqa: E402
 REF_IMAGES = "/root/reference/images"
 GOLD = os.path.join(ROOT, "tests", "golden")
 BASELINE = ["img", "img2", "img3", "img4", "img5", "img6"]
+MAX_FIXTURE_BYTES = 1 << 20   # no fixture file above 1 MiB
 
 
 def kat_cases():
@@ -72,6 +79,71 @@ def kat_cases():
     return cases
 
 
+def save_image_fixture(name, desc, q, coef, rgb):
+    """<name>.npz with every array, or, where that file would pass MAX_FIXTURE_BYTES, <name>.npz without the
+    pixels and as few row bands <name>.rgb<k>.npz as keep each file within it (tests/conftest.py load_golden)."""
+    path = os.path.join(GOLD, name + ".npz")
+    for stale in glob.glob(os.path.join(GOLD, name + ".rgb*.npz")):
+        os.remove(stale)
+    np.savez_compressed(path, desc=desc, qtabs=q, coef=coef, rgb=rgb)
+    if os.path.getsize(path) <= MAX_FIXTURE_BYTES:
+        return
+    np.savez_compressed(path, desc=desc, qtabs=q, coef=coef)
+    for bands in range(2, rgb.shape[0] + 1):
+        edges = np.linspace(0, rgb.shape[0], bands + 1).astype(int)
+        parts = [os.path.join(GOLD, f"{name}.rgb{k}.npz") for k in range(bands)]
+        for part, a, b in zip(parts, edges[:-1], edges[1:]):
+            np.savez_compressed(part, rgb=rgb[a:b])
+        if all(os.path.getsize(part) <= MAX_FIXTURE_BYTES for part in parts):
+            return
+        for part in parts:
+            os.remove(part)
+    raise RuntimeError(f"{name}: no split of the pixels keeps every fixture file within {MAX_FIXTURE_BYTES} bytes")
+
+
+# the cases of tests/test_oracle.py that call the reference build itself (keep the two in step)
+RANDOM_BLOCK_SAMPLINGS = [(1, 1), (2, 1), (1, 2), (2, 2)]
+RANDOM_BLOCK_SIZES = [(8, 8, 1), (100, 52, 2), (257, 131, 3)]
+WRITER_CASES = [(679, 451, 2, 2, 0), (333, 211, 1, 1, 0), (100, 60, 2, 1, 0), (64, 80, 1, 2, 0), (640, 360, 1, 1, 2), (512, 256, 2, 2, 1)]
+
+
+def sha256_of(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def write_ref_results(ref):
+    """tests/golden/ref_results.json: the reference's answers in the cases of tests/test_oracle.py that ask it directly."""
+    import tempfile
+    from oracle.pyoracle import Oracle
+    ora = Oracle()
+    out = {"random_blocks": {}, "writer_streams": {}}
+    for hs, vs in RANDOM_BLOCK_SAMPLINGS:
+        q = synth.annex_k_qtabs(75)
+        q[2] = 255
+        q[3] = 1
+        for (w, h, seed) in RANDOM_BLOCK_SIZES:
+            d = make_desc(w, h, hs, vs, (0, 1, 2))
+            n = ora.geometry(d).n_coded_blocks
+            for kind, coef in (("full", synth.random_blocks(n, seed)), ("small", synth.random_blocks(n, seed + 10, -64, 64))):
+                out["random_blocks"][f"{hs}x{vs}/{w}x{h}/seed{seed}/{kind}"] = sha256_of(ref.blocks_to_rgb(d, coef, q))
+    with tempfile.TemporaryDirectory() as tmp:
+        for (w, h, hs, vs, rows) in WRITER_CASES:
+            coef, q = synth.synth_blocks(w, h, hs, vs, 21)
+            data = synth.encode_jpeg(coef, w, h, hs, vs, q, restart_interval=rows * synth.geometry(w, h, hs, vs)[0])
+            path = os.path.join(tmp, "w.jpg")
+            with open(path, "wb") as f:
+                f.write(data)
+            info, rcoef, rq, rrgb = ref.decode_file(path)
+            assert np.array_equal(rcoef.astype(coef.dtype), rcoef) and np.array_equal(rq.astype(q.dtype), rq)
+            out["writer_streams"][f"{w}x{h}/{hs}x{vs}/rows{rows}"] = {
+                "stream_sha256": sha256_of(np.frombuffer(data, np.uint8)),
+                "frame": [info.width, info.height, info.hs, info.vs],
+                "coef_sha256": sha256_of(rcoef.astype(coef.dtype)), "qtabs01_sha256": sha256_of(rq[:2].astype(q.dtype)),
+                "rgb_sha256": sha256_of(rrgb)}
+    with open(os.path.join(GOLD, "ref_results.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+
+
 def main():
     ref = Ref()
     os.makedirs(os.path.join(GOLD, "images"), exist_ok=True)
@@ -85,7 +157,7 @@ def main():
         sha = hashlib.sha256(rgb.tobytes()).hexdigest()
         desc = np.array([info.width, info.height, info.hs, info.vs, *info.qtab_id, info.restart_interval,
                          info.mcu_w_real, info.mcu_h_real], np.int32)
-        np.savez_compressed(os.path.join(GOLD, name + ".npz"), desc=desc, qtabs=q, coef=coef, rgb=rgb)
+        save_image_fixture(name, desc, q, coef, rgb)
         manifest["images"][name] = {
             "file_sha256": hashlib.sha256(open(path, "rb").read()).hexdigest(),
             "width": info.width, "height": info.height, "hs": info.hs, "vs": info.vs,
@@ -107,6 +179,7 @@ def main():
         kat[name + "__rgb"] = rgb
         manifest["kat"][name] = hashlib.sha256(rgb.tobytes()).hexdigest()
     np.savez_compressed(os.path.join(GOLD, "kat_blocks.npz"), **kat)
+    write_ref_results(ref)
     with open(os.path.join(GOLD, "manifest.json"), "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
     print("kat cases:", len(manifest["kat"]))

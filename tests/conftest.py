@@ -1,3 +1,4 @@
+import hashlib
 import json
 import os
 import sys
@@ -29,11 +30,23 @@ def oracle():
 
 
 def load_golden(name):
-    """-> (desc, coef, qtabs, rgb) of one baseline image fixture."""
+    """-> (desc, coef, qtabs, rgb) of one baseline image fixture.  A fixture too large for one file keeps
+    its RGB rows in bands <name>.rgb<k>.npz (oracle/gen_golden.py): joined here, and checked against the
+    digest manifest.json records."""
     from oracle.pyoracle import make_desc
     z = np.load(os.path.join(GOLD, name + ".npz"))
     d = z["desc"]
-    return make_desc(d[0], d[1], d[2], d[3], d[4:7]), z["coef"], z["qtabs"], z["rgb"]
+    if "rgb" in z.files:
+        rgb = z["rgb"]
+    else:
+        bands = []
+        while os.path.exists(os.path.join(GOLD, f"{name}.rgb{len(bands)}.npz")):
+            bands.append(np.load(os.path.join(GOLD, f"{name}.rgb{len(bands)}.npz"))["rgb"])
+        rgb = np.concatenate(bands, axis=0)
+        with open(os.path.join(GOLD, "manifest.json")) as f:
+            want = json.load(f)["images"][name]["rgb_sha256"]
+        assert hashlib.sha256(rgb.tobytes()).hexdigest() == want, f"{name}: the RGB bands do not join to the recorded image"
+    return make_desc(d[0], d[1], d[2], d[3], d[4:7]), z["coef"], z["qtabs"], rgb
 
 
 def load_kat():

@@ -53,13 +53,13 @@ def test_two_child_ranks_real_hip_path(tmp_path, manifest):
 
 
 def test_bench_gpus_2_run_plainly_reports_two_ranks():
-    """`python bench.py --gpus 2` with no launcher: it must start two ranks itself (before any GPU
+    """`python bench.py --gpus 2 --full` with no launcher: it must start two ranks itself (before any GPU
     call) and print n_gpus 2 -- here both on the one GPU of the box, bookkeeping over gloo."""
     env = dict(os.environ, JB_BENCH_SINGLE_DEVICE="1", JB_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-                        "--precondition", "10", "--images-per-step", "2", "--no-cpu-baseline"],
+                        "--precondition", "10", "--images-per-step", "2", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

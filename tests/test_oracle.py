@@ -3,14 +3,17 @@
 (1) against the committed golden vectors generated from the genuine reference build
     (oracle/gen_golden.py) -- runs everywhere;
 (2) directly against oracle/_ref/libjpegref.so (the reference compiled in place) when that
-    build is present.
+    build is present, and always against the digests of its answers recorded in
+    tests/golden/ref_results.json (oracle/gen_golden.py) -- which must agree with it where it is present.
 Parity bar: bit-exact (the task's +-1 LSB allowance is not used)."""
 import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
 
-from conftest import BASELINE_IMAGES, load_golden, load_kat
+from conftest import BASELINE_IMAGES, GOLD, load_golden, load_kat
 from jpeg_decoder_amd import synth
 from oracle.pyoracle import Ref, make_desc
 
@@ -76,44 +79,62 @@ def test_dc_only_block_is_flat(oracle):
     assert (out == out[0]).all() and out[0] == 99
 
 
-needs_ref = pytest.mark.skipif(not Ref.available(), reason="oracle/_ref not built (reference absent)")
+@pytest.fixture(scope="module")
+def ref_results():
+    with open(os.path.join(GOLD, "ref_results.json")) as f:
+        return json.load(f)
 
 
-@needs_ref
-def test_ref_constants(oracle):
-    assert np.array_equal(Ref().constants(), oracle.constants())
+def _sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
-@needs_ref
+def test_ref_constants(oracle, manifest):
+    """The oracle's constants == the reference build's, or, without it, those it gave for tests/golden/."""
+    want = Ref().constants() if Ref.available() else np.array(manifest["constants_f32_bits"], np.uint32)
+    assert np.array_equal(want, oracle.constants())
+
+
 @pytest.mark.parametrize("hs,vs", [(1, 1), (2, 1), (1, 2), (2, 2)])
-def test_oracle_matches_reference_on_random_blocks(oracle, hs, vs):
-    ref = Ref()
+def test_oracle_matches_reference_on_random_blocks(oracle, ref_results, hs, vs):
+    ref = Ref() if Ref.available() else None
     q = synth.annex_k_qtabs(75)
     q[2] = 255
     q[3] = 1
     for (w, h, seed) in [(8, 8, 1), (100, 52, 2), (257, 131, 3)]:
         d = make_desc(w, h, hs, vs, (0, 1, 2))
         n = oracle.geometry(d).n_coded_blocks
-        for coef in (synth.random_blocks(n, seed), synth.random_blocks(n, seed + 10, -64, 64)):
-            assert np.array_equal(oracle.blocks_to_rgb(d, coef, q), ref.blocks_to_rgb(d, coef, q))
+        for kind, coef in (("full", synth.random_blocks(n, seed)), ("small", synth.random_blocks(n, seed + 10, -64, 64))):
+            got = oracle.blocks_to_rgb(d, coef, q)
+            if ref is not None:
+                assert np.array_equal(got, ref.blocks_to_rgb(d, coef, q))
+            assert _sha(got) == ref_results["random_blocks"][f"{hs}x{vs}/{w}x{h}/seed{seed}/{kind}"], (w, h, seed, kind)
 
 
-@needs_ref
 @pytest.mark.parametrize("w,h,hs,vs,rows", [(679, 451, 2, 2, 0), (333, 211, 1, 1, 0), (100, 60, 2, 1, 0),
                                               (64, 80, 1, 2, 0), (640, 360, 1, 1, 2), (512, 256, 2, 2, 1)])
-def test_writer_streams_through_the_reference_reader(oracle, tmp_path, w, h, hs, vs, rows):
+def test_writer_streams_through_the_reference_reader(oracle, ref_results, tmp_path, w, h, hs, vs, rows):
     """Pins the build's baseline writer (tools/jpegwriter) with the genuine reference: the
     reference's own marker parser + Huffman decoder (oracle/_ref) must read back exactly the
     blocks and tables that were written, and its RGB must equal the oracle's on them.  Restart
     intervals only as whole MCU rows -- the reference's restart test (jpeg.cpp:414,419) counts
-    block rows, see INTEGRATION.md section 5."""
+    block rows, see INTEGRATION.md section 5.  Without the reference build: the writer must still
+    produce the very stream whose reading by the reference tests/golden/ref_results.json records."""
     from jpeg_decoder_amd import synth
     from oracle.pyoracle import Ref, make_desc
     coef, q = synth.synth_blocks(w, h, hs, vs, 21)
     ri = rows * synth.geometry(w, h, hs, vs)[0]
-    p = tmp_path / "w.jpg"
-    p.write_bytes(synth.encode_jpeg(coef, w, h, hs, vs, q, restart_interval=ri))
-    info, rcoef, rq, rrgb = Ref().decode_file(str(p))
-    assert (info.width, info.height, info.hs, info.vs) == (w, h, hs, vs)
-    assert np.array_equal(rcoef, coef) and np.array_equal(rq[:2], q[:2])
-    assert np.array_equal(rrgb, oracle.blocks_to_rgb(make_desc(w, h, hs, vs), coef, q))
+    data = synth.encode_jpeg(coef, w, h, hs, vs, q, restart_interval=ri)
+    rgb = oracle.blocks_to_rgb(make_desc(w, h, hs, vs), coef, q)
+    if Ref.available():
+        p = tmp_path / "w.jpg"
+        p.write_bytes(data)
+        info, rcoef, rq, rrgb = Ref().decode_file(str(p))
+        assert (info.width, info.height, info.hs, info.vs) == (w, h, hs, vs)
+        assert np.array_equal(rcoef, coef) and np.array_equal(rq[:2], q[:2])
+        assert np.array_equal(rrgb, rgb)
+    rec = ref_results["writer_streams"][f"{w}x{h}/{hs}x{vs}/rows{rows}"]
+    assert _sha(np.frombuffer(data, np.uint8)) == rec["stream_sha256"], "the writer no longer makes the stream the reference read"
+    assert rec["frame"] == [w, h, hs, vs]
+    assert _sha(coef) == rec["coef_sha256"] and _sha(q[:2]) == rec["qtabs01_sha256"]
+    assert _sha(rgb) == rec["rgb_sha256"]
