@@ -217,6 +217,32 @@ int jb_resolve_qtabs(const jb_image_desc *desc, const uint16_t *qtabs, int32_t *
  * 4:2:0) run as jb_small_kernel_444 / _420 / _16<2,1> / _16<1,2> instead (JPEGBLK_SMALL_GRID). */
 const char *jb_kernel_name(const jb_image_desc *desc);
 
+/* ---- scaled output: decode at 1/2, 1/4 or 1/8 size ---------------------------------------
+ * For denom K in {1, 2, 4, 8} an image of W x H decodes to ceil(W/K) x ceil(H/K) RGB pixels (interleaved
+ * uint8, the layout above), each the rounded mean of its K x K box of the full-size output:
+ *
+ *     out[y][x][c] = floor((S + n/2) / n),  S = sum of full[yy][xx][c] over yy in [K*y, min(K*y+K, H)),
+ *                                               xx in [K*x, min(K*x+K, W)),  n = number of such (yy, xx)
+ *
+ * where `full` is what the entry points above return for the image, bit for bit (so n = K*K inside the image and
+ * fewer in the last column / row; the MCU padding beyond W x H never enters a sum).  This is an AREA (box) filter on
+ * the decoded pixels, computed in the pixel kernel from the very samples it would have stored -- NOT the DCT-domain
+ * reduced IDCT of libjpeg's scale_denom, whose output differs; inside the image it equals PIL's Image.reduce(K).
+ * What is saved is output bytes (HBM writes, and the device-to-host link on the host-output forms): K^2 fewer.
+ * K = 1 is the full-size path, unchanged.  A denom outside {1, 2, 4, 8} is JB_ERR_GEOMETRY everywhere.
+ * The scaled launches use the row-bound tiling and ignore JPEGBLK_SMALL_GRID and JPEGBLK_BYTE_STORE. */
+/* Output size of a W x H image at 1/denom.  Pure host code. */
+int jb_scaled_size(int32_t width, int32_t height, int denom, int32_t *out_w, int32_t *out_h);
+/* jb_blocks_to_rgb_device at 1/denom: d_rgb receives n_images images of jb_scaled_size(desc) pixels,
+ * rgb_row_stride >= 3 * out_w, rgb_image_stride >= rgb_row_stride * out_h (n_images > 1).  denom = 1 is
+ * jb_blocks_to_rgb_device. */
+int jb_blocks_to_rgb_device_scaled(jb_ctx *ctx, const jb_device_batch *batch, int denom, void *stream);
+/* jb_decode_memory / jb_decode_file at 1/denom: *rgb holds out_w x out_h pixels (tight rows), *width / *height
+ * report the OUTPUT size.  Both entropy paths take the scale (the same rule picks the device entropy stage). */
+int jb_decode_memory_scaled(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, int denom, uint8_t **rgb,
+                            int32_t *width, int32_t *height);
+int jb_decode_file_scaled(jb_ctx *ctx, const char *path, int denom, uint8_t **rgb, int32_t *width, int32_t *height);
+
 /* ---- host front end ("next" rows of the scope table; reference jpeg.cpp:67-446, 826-907,
  *      include/file.hpp, include/huffman.hpp) --------------------------------------------- */
 /* Parse a JFIF byte stream and Huffman-decode it into packed int16 blocks in the order
@@ -356,6 +382,12 @@ int jb_batch_decoder_set_device_output(jb_batch_decoder *dec, void *d_base, size
  * jb_batch_decoder_create_multi (d_bases[k] is memory of device_ids[k]); file i lands in the region of
  * device_ids[i % n_devices].  n = 0: host output again. */
 int jb_batch_decoder_set_device_outputs(jb_batch_decoder *dec, void *const *d_bases, const size_t *bytes, int n);
+/* Output scale of the batch decoder's later runs and submissions (1 = full size, the default; 2, 4, 8: see "scaled
+ * output" above).  widths / heights then report the output sizes, and every output form -- malloc'ed, pinned arena,
+ * device regions -- holds ceil(W/denom) x ceil(H/denom) pixels per image with tight rows (an arena or region only
+ * needs room for the reduced images).  Applies to every device of a multi-device decoder and to both sides of
+ * submit / collect.  Refused with JB_ERR_STATE while a batch is in flight. */
+int jb_batch_decoder_set_scale(jb_batch_decoder *dec, int denom);
 /* Output sink replacing the reference's X11 window / unused BMP writer (display.hpp,
  * jpeg.cpp:462-509): binary PPM (P6). */
 int jb_write_ppm(const char *path, const uint8_t *rgb, int32_t width, int32_t height,

@@ -139,6 +139,11 @@ def lib():
     L.jb_batch_decoder_set_device_outputs.restype = ctypes.c_int
     L.jb_free.argtypes = [vp]
     L.jb_free.restype = None
+    L.jb_scaled_size.argtypes = [i32, i32, ctypes.c_int, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.jb_blocks_to_rgb_device_scaled.argtypes = [vp, ctypes.POINTER(DeviceBatch), ctypes.c_int, vp]
+    L.jb_decode_memory_scaled.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.jb_decode_file_scaled.argtypes = [vp, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.jb_batch_decoder_set_scale.argtypes = [vp, ctypes.c_int]
     L.jb_write_ppm.argtypes = [ctypes.c_char_p, vp, i32, i32, i64]
     L.jb_write_bmp.argtypes = [ctypes.c_char_p, vp, i32, i32, i64]
     if L.jb_abi_version() != 1:
@@ -169,6 +174,13 @@ def geometry_of(desc):
     g = Geometry()
     _check(lib().jb_geometry_of(ctypes.byref(desc), ctypes.byref(g)))
     return g
+
+
+def scaled_size(width, height, scale):
+    """jb_scaled_size: (ceil(width / scale), ceil(height / scale)) for scale in {1, 2, 4, 8}."""
+    w, h = ctypes.c_int32(), ctypes.c_int32()
+    _check(lib().jb_scaled_size(int(width), int(height), int(scale), ctypes.byref(w), ctypes.byref(h)))
+    return w.value, h.value
 
 
 def resolve_qtabs(desc, qtabs):
@@ -298,13 +310,23 @@ class Context:
         _check(lib().jb_wait(self._h, ticket), self._h)
 
     # -- the seam, device buffers ------------------------------------------------------------
-    def blocks_to_rgb_device(self, batch, stream=None):
-        _check(lib().jb_blocks_to_rgb_device(self._h, ctypes.byref(batch), stream), self._h)
+    def blocks_to_rgb_device(self, batch, stream=None, scale=1):
+        """scale 2, 4, 8 (jb_blocks_to_rgb_device_scaled): the batch's d_rgb and strides describe images of
+        scaled_size(desc.width, desc.height, scale)."""
+        if scale == 1:
+            _check(lib().jb_blocks_to_rgb_device(self._h, ctypes.byref(batch), stream), self._h)
+        else:
+            _check(lib().jb_blocks_to_rgb_device_scaled(self._h, ctypes.byref(batch), scale, stream), self._h)
 
     # -- decode(path) -> RGB -----------------------------------------------------------------
-    def decode_file(self, path):
+    def decode_file(self, path, scale=1):
+        """-> RGB [H, W, 3]; scale 2, 4, 8: the area-reduced image (jb_decode_file_scaled)."""
         p, w, h = ctypes.c_void_p(), ctypes.c_int32(), ctypes.c_int32()
-        _check(lib().jb_decode_file(self._h, os.fsencode(path), ctypes.byref(p), ctypes.byref(w), ctypes.byref(h)), self._h)
+        if scale == 1:
+            rc = lib().jb_decode_file(self._h, os.fsencode(path), ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
+        else:
+            rc = lib().jb_decode_file_scaled(self._h, os.fsencode(path), scale, ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
+        _check(rc, self._h)
         try:
             n = w.value * h.value * 3
             arr = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)), shape=(n,)).copy()
@@ -312,11 +334,16 @@ class Context:
             lib().jb_free(p)
         return arr.reshape(h.value, w.value, 3)
 
-    def decode_memory(self, jpeg_bytes):
-        """jb_decode_memory: a JFIF byte string -> RGB [H, W, 3] (front end + device seam)."""
+    def decode_memory(self, jpeg_bytes, scale=1):
+        """jb_decode_memory: a JFIF byte string -> RGB [H, W, 3] (front end + device seam); scale 2, 4, 8: the
+        area-reduced image (jb_decode_memory_scaled)."""
         buf = np.frombuffer(jpeg_bytes, dtype=np.uint8)
         p, w, h = ctypes.c_void_p(), ctypes.c_int32(), ctypes.c_int32()
-        _check(lib().jb_decode_memory(self._h, _ptr(buf), buf.size, ctypes.byref(p), ctypes.byref(w), ctypes.byref(h)), self._h)
+        if scale == 1:
+            rc = lib().jb_decode_memory(self._h, _ptr(buf), buf.size, ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
+        else:
+            rc = lib().jb_decode_memory_scaled(self._h, _ptr(buf), buf.size, scale, ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
+        _check(rc, self._h)
         try:
             n = w.value * h.value * 3
             arr = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)), shape=(n,)).copy()
@@ -328,9 +355,10 @@ class Context:
 class BatchDecoder:
     """jb_batch_decoder: n_threads host lanes (pinned buffers each) feeding one shared context per
     device, reusable.  devices=[...] (jb_batch_decoder_create_multi): one decoder over several
-    devices, file i -> devices[i % len(devices)], the host threads split evenly."""
+    devices, file i -> devices[i % len(devices)], the host threads split evenly.  scale 2, 4, 8
+    (jb_batch_decoder_set_scale): every image comes out area-reduced."""
 
-    def __init__(self, n_threads=8, device=0, max_coef_bytes=0, max_rgb_bytes=0, arena_bytes=0, devices=None):
+    def __init__(self, n_threads=8, device=0, max_coef_bytes=0, max_rgb_bytes=0, arena_bytes=0, devices=None, scale=1):
         self._h = ctypes.c_void_p()
         if devices is not None:
             ids = (ctypes.c_int * len(devices))(*devices)
@@ -343,6 +371,13 @@ class BatchDecoder:
         if arena_bytes:
             _check(lib().jb_batch_decoder_set_arena(self._h, arena_bytes))
             self._arena = True
+        if scale != 1:
+            self.set_scale(scale)
+
+    def set_scale(self, scale):
+        """jb_batch_decoder_set_scale: output at 1/scale for later runs and submissions (JbError -7 while a batch
+        is in flight)."""
+        _check(lib().jb_batch_decoder_set_scale(self._h, scale))
 
     @property
     def device_entropy_images(self):
@@ -435,10 +470,16 @@ class BatchDecoder:
         self.close()
 
 
-def decode_batch(paths, n_threads=8, device=0, keep_pixels=True, on_image=None, _decoder=None, _arena=False):
+def decode_batch(paths, n_threads=8, device=0, keep_pixels=True, on_image=None, _decoder=None, _arena=False, scale=1):
     """jb_decode_batch: -> (list of uint8 [H,W,3] arrays or None, statuses, times dict).
     on_image(i, view): called with a no-copy [H,W,3] view of every decoded image before its buffer
-    is released (checks over batches too large to keep)."""
+    is released (checks over batches too large to keep).  scale 2, 4, 8: through a temporary
+    BatchDecoder with set_scale(scale)."""
+    if scale != 1 and _decoder is None:
+        if n_threads > len(paths) > 0:
+            n_threads = len(paths)
+        with BatchDecoder(n_threads=n_threads, device=device, scale=scale) as d:
+            return d.run(paths, keep_pixels=keep_pixels, on_image=on_image)
     n = len(paths)
     arr = (ctypes.c_char_p * n)(*[os.fsencode(p) for p in paths])
     rgb = (ctypes.c_void_p * n)()
@@ -470,9 +511,14 @@ def decode_batch(paths, n_threads=8, device=0, keep_pixels=True, on_image=None, 
     return out, list(st), t
 
 
-def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, shared_qtabs=True):
+def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, shared_qtabs=True, scale=1):
     """DeviceBatch over torch CUDA tensors (plumbing): coef_t int16 [n_images, n_blocks, 64],
-    qtabs_t int32 [3,64] (shared) or [n_images,3,64], rgb_t uint8 [n_images, H, row_stride]."""
+    qtabs_t int32 [3,64] (shared) or [n_images,3,64], rgb_t uint8 [n_images, H, row_stride].
+    scale 2, 4, 8: rgb_t holds the reduced images, [n_images, ceil(H/scale), row_stride], for
+    Context.blocks_to_rgb_device(..., scale=scale)."""
+    if scale != 1:
+        out_w, out_h = scaled_size(desc.width, desc.height, scale)
+        assert rgb_t.shape[1] >= out_h and (rgb_row_stride or rgb_t.stride(1)) >= 3 * out_w, "rgb_t is smaller than the scaled images"
     b = DeviceBatch()
     b.desc = desc
     b.n_images = n_images

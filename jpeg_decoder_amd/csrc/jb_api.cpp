@@ -515,20 +515,30 @@ int jb_ctx_synchronize(jb_ctx *ctx) {
 // 4:2:2 / 4:4:0 (all 64 lanes busy): one 1080p 11.2 -> 10.6 / 11.4 -> 9.6 us, one 4096x4096 25.0 -> 23.4 / 25.7 -> 26.3.
 constexpr int kSmallGridBelowPerCu = 8;
 
-int jb_blocks_to_rgb_device(jb_ctx *ctx, const jb_device_batch *b, void *stream) {
-  if (!ctx) return fail(nullptr, JB_ERR_NULL, "jb_blocks_to_rgb_device: ctx is NULL");
-  if (!b || !b->d_coef || !b->d_qtabs || !b->d_rgb) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device: NULL pointer");
+}  // extern "C"
+
+namespace {
+
+// The tile and launch setup of both seams: jb_blocks_to_rgb_device (scale 1: exactly the launch it has always
+// made) and jb_blocks_to_rgb_device_scaled (scale 2, 4, 8: the row-bound tiling with the area-reduced store stage).
+// The batch's row / image strides describe the output, i.e. the reduced image when scale > 1.
+int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int scale, const char *fn) {
+  if (!ctx) return fail(nullptr, JB_ERR_NULL, "%s: ctx is NULL", fn);
+  if (!b || !b->d_coef || !b->d_qtabs || !b->d_rgb) return fail(ctx, JB_ERR_NULL, "%s: NULL pointer", fn);
   jb_geometry g;
   int rc = check_desc(ctx, &b->desc, &g);
   if (rc) return rc;
+  int32_t out_w = 0, out_h = 0;
+  if (jb_scaled_size(b->desc.width, b->desc.height, scale, &out_w, &out_h) != JB_OK)
+    return fail(ctx, JB_ERR_GEOMETRY, "%s: scale %d is not 1, 2, 4 or 8", fn, scale);
   if (b->n_images < 1) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d", b->n_images);
-  if (b->rgb_row_stride < 3LL * b->desc.width)
+  if (b->rgb_row_stride < 3LL * out_w)
     return fail(ctx, JB_ERR_GEOMETRY, "rgb_row_stride %lld < 3*width", (long long)b->rgb_row_stride);
   if (((uintptr_t)b->d_coef & 15) || (b->coef_image_stride & 15))
     return fail(ctx, JB_ERR_GEOMETRY, "coefficient pointer and image stride must be multiples of 16 bytes");
   if (((uintptr_t)b->d_qtabs & 3) || (b->qtab_image_stride & 3))
     return fail(ctx, JB_ERR_GEOMETRY, "quant-table pointer and stride must be multiples of 4 bytes");
-  if (b->n_images > 1 && (b->coef_image_stride < g.coef_bytes || b->rgb_image_stride < b->rgb_row_stride * (int64_t)b->desc.height))
+  if (b->n_images > 1 && (b->coef_image_stride < g.coef_bytes || b->rgb_image_stride < b->rgb_row_stride * (int64_t)out_h))
     return fail(ctx, JB_ERR_GEOMETRY, "image strides smaller than one image");
   const int per_tile = jbk_mcus_per_tile(b->desc.hs, b->desc.vs);
   JbLaunch p;
@@ -545,8 +555,8 @@ int jb_blocks_to_rgb_device(jb_ctx *ctx, const jb_device_batch *b, void *stream)
   p.mcus_x = g.mcus_x;
   p.mcus_y = g.mcus_y;
   p.tiles_per_row = (g.mcus_x + per_tile - 1) / per_tile;
-  // JPEGBLK_ROW_TILING=1 (debug / A-B knob) forces the row-bound tiling
-  const bool force_row = ctx->knobs.row_tiling;
+  // JPEGBLK_ROW_TILING=1 (debug / A-B knob) forces the row-bound tiling; the scaled stage only exists in it
+  const bool force_row = ctx->knobs.row_tiling || scale > 1;
   // linear tiling only where the row-bound one would leave ragged tiles
   p.linear = (force_row || g.mcus_x % per_tile == 0) ? 0 : jbk_linear_ok(b->desc.hs, b->desc.vs, g.mcus_x);
   const int64_t tiles_per_image = p.linear ? ((int64_t)g.mcus_x * g.mcus_y + per_tile - 1) / per_tile
@@ -558,7 +568,8 @@ int jb_blocks_to_rgb_device(jb_ctx *ctx, const jb_device_batch *b, void *stream)
   p.n_tiles = (int32_t)n_tiles;
   // Small launches (a single 1080p image is 507 / 255 workgroups on 256 CUs): four times as many one-wave
   // workgroups (jb_kernels.hip jb_small_kernel_*), row-bound.  JPEGBLK_SMALL_GRID = 1 / 0 forces / forbids it; so does
-  // JPEGBLK_ROW_TILING=1 (that knob asks for the 192-lane kernel's row-bound instantiation).
+  // JPEGBLK_ROW_TILING=1 (that knob asks for the 192-lane kernel's row-bound instantiation).  (The scaled stage has no
+  // small-grid variant.)
   if (jbk_small_mcus(b->desc.hs, b->desc.vs) > 0 && !force_row && b->rgb_row_stride < (1LL << 26) &&  // (the lane's row offset is 32-bit)
       (ctx->knobs.small_grid == 1 || (ctx->knobs.small_grid < 0 && n_tiles <= (int64_t)kSmallGridBelowPerCu * ctx->n_cus))) {
     const int per = jbk_small_mcus(b->desc.hs, b->desc.vs);
@@ -576,7 +587,7 @@ int jb_blocks_to_rgb_device(jb_ctx *ctx, const jb_device_batch *b, void *stream)
   // 12-byte stores at any byte address: gfx950 under ROCm runs with unaligned global/buffer access
   // enabled, and odd widths with tightly packed rows (row stride 3*W) are the common case --
   // measured 1.67x faster than byte stores on 679x451 (tests/test_gpu_parity.py covers both).
-  // JPEGBLK_BYTE_STORE=1 forces the byte-store path (test / A-B knob).
+  // JPEGBLK_BYTE_STORE=1 forces the byte-store path (test / A-B knob; the scaled stage ignores it).
   p.fast_store = ctx->knobs.byte_store ? 0 : 1;
   // (measurement builds of jb_kernels.hip only -- tools/build_variant.sh -DJB_LAB: the staged store stage of the linear
   // tiling; the product's kernels ignore the field)
@@ -584,8 +595,21 @@ int jb_blocks_to_rgb_device(jb_ctx *ctx, const jb_device_batch *b, void *stream)
   p.chroma_q_equal = (b->desc.qtab_id[1] == b->desc.qtab_id[2]) ? 1 : 0;
   DeviceGuard guard(ctx->device);
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  JB_HIP(ctx, jbk_launch(p, b->desc.hs, b->desc.vs, s));
+  if (scale == 1) JB_HIP(ctx, jbk_launch(p, b->desc.hs, b->desc.vs, s));
+  else JB_HIP(ctx, jbk_launch_scaled(p, b->desc.hs, b->desc.vs, scale, s));
   return JB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int jb_blocks_to_rgb_device(jb_ctx *ctx, const jb_device_batch *b, void *stream) {
+  return seam_launch(ctx, b, stream, 1, "jb_blocks_to_rgb_device");
+}
+
+int jb_blocks_to_rgb_device_scaled(jb_ctx *ctx, const jb_device_batch *b, int denom, void *stream) {
+  return seam_launch(ctx, b, stream, denom, "jb_blocks_to_rgb_device_scaled");
 }
 
 int jb_ctx_device(const jb_ctx *ctx) { return ctx ? ctx->device : -1; }
@@ -705,16 +729,20 @@ constexpr int kMaxBatch = 256;  // images per submission (the slot's table block
 // n_images == 1, any row stride.
 // dst_device: `rgb` is DEVICE memory of ctx's device -- the kernel writes the pixels there and nothing
 // is downloaded (jb_batch_decoder_set_device_output).
+// scale (2, 4, 8): the pixels are the area-reduced image (jb_scaled_size), rgb / rgb_stride describe it.
 int submit_impl(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef, const uint16_t *qtabs,
-                uint8_t *rgb, int64_t rgb_stride, int *ticket, bool dst_device = false) {
+                uint8_t *rgb, int64_t rgb_stride, int *ticket, bool dst_device = false, int scale = 1) {
   if (ctx->n_slots == 0) return fail(ctx, JB_ERR_CAPACITY, "context was created without staging buffers");
   jb_geometry g;
   int rc = check_desc(ctx, desc, &g);
   if (rc) return rc;
   if (n_images < 1 || n_images > kMaxBatch) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d outside 1..%d", n_images, kMaxBatch);
-  const int64_t dev_stride = 3LL * desc->width;  // tight rows on the device (12-byte stores need no alignment)
+  int32_t out_w = 0, out_h = 0;
+  if (jb_scaled_size(desc->width, desc->height, scale, &out_w, &out_h) != JB_OK) return fail(ctx, JB_ERR_GEOMETRY, "scale %d is not 1, 2, 4 or 8", scale);
+  const int64_t out_bytes = 3LL * out_w * out_h;  // g.rgb_bytes when scale == 1
+  const int64_t dev_stride = 3LL * out_w;  // tight rows on the device (12-byte stores need no alignment)
   if (rgb_stride < dev_stride) return fail(ctx, JB_ERR_GEOMETRY, "rgb_stride %lld < 3*width", (long long)rgb_stride);
-  const size_t coef_total = (size_t)g.coef_bytes * (size_t)n_images, rgb_total = (size_t)g.rgb_bytes * (size_t)n_images;
+  const size_t coef_total = (size_t)g.coef_bytes * (size_t)n_images, rgb_total = (size_t)out_bytes * (size_t)n_images;
   if (coef_total > ctx->max_coef || (!dst_device && (rgb_total > ctx->rgb_alloc || rgb_total > ctx->max_rgb)))
     return fail(ctx, JB_ERR_CAPACITY, "%d image(s) of %dx%d exceed the capacity the context was created with", n_images,
                 desc->width, desc->height);
@@ -760,8 +788,8 @@ int submit_impl(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int1
   b.qtab_image_stride = n_images > 1 ? 768 : 0;
   b.d_rgb = dst_device ? rgb : (uint8_t *)s.d_rgb;
   b.rgb_row_stride = dev_stride;
-  b.rgb_image_stride = g.rgb_bytes;
-  rc = jb_blocks_to_rgb_device(ctx, &b, up);
+  b.rgb_image_stride = out_bytes;
+  rc = seam_launch(ctx, &b, up, scale, "submit");
   if (rc) return rc;
   if (dst_device) {
     down = up;  // the pixels stay on the device: done when the kernel is
@@ -774,8 +802,8 @@ int submit_impl(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int1
     if (rgb_stride == dev_stride)
       JB_HIP(ctx, hipMemcpyAsync(rgb, s.d_rgb, rgb_total, hipMemcpyDeviceToHost, down));
     else
-      JB_HIP(ctx, hipMemcpy2DAsync(rgb, (size_t)rgb_stride, s.d_rgb, (size_t)dev_stride, (size_t)desc->width * 3,
-                                   (size_t)desc->height, hipMemcpyDeviceToHost, down));
+      JB_HIP(ctx, hipMemcpy2DAsync(rgb, (size_t)rgb_stride, s.d_rgb, (size_t)dev_stride, (size_t)out_w * 3,
+                                   (size_t)out_h, hipMemcpyDeviceToHost, down));
   }
   JB_HIP(ctx, hipEventRecord(s.done, down));
   s.busy = true;
@@ -867,16 +895,19 @@ int pack_into_slot(jb_ctx *ctx, Slot &s, const JbHuffJob *const *jobs, int n, in
 // and tables (`desc`, `qtabs` = n x 4*64).
 int submit_jobs_impl(jb_ctx *ctx, const JbHuffJob *const *jobs, const uint8_t *packed, const JbHuffLayout *lay_in,
                      const jb_image_desc *desc_in, const uint16_t *qtabs_in, int n_images, uint8_t *rgb, int64_t rgb_stride,
-                     uint32_t *status_out, int *ticket, bool dst_device = false) {
+                     uint32_t *status_out, int *ticket, bool dst_device = false, int scale = 1) {
   if (ctx->n_slots == 0) return fail(ctx, JB_ERR_CAPACITY, "context was created without staging buffers");
   if (n_images < 1 || n_images > kMaxBatch) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d outside 1..%d", n_images, kMaxBatch);
   const jb_image_desc *desc = jobs ? &jobs[0]->desc : desc_in;
   jb_geometry g;
   int rc = check_desc(ctx, desc, &g);
   if (rc) return rc;
-  const int64_t dev_stride = 3LL * desc->width;
+  int32_t out_w = 0, out_h = 0;
+  if (jb_scaled_size(desc->width, desc->height, scale, &out_w, &out_h) != JB_OK) return fail(ctx, JB_ERR_GEOMETRY, "scale %d is not 1, 2, 4 or 8", scale);
+  const int64_t out_bytes = 3LL * out_w * out_h;  // g.rgb_bytes when scale == 1
+  const int64_t dev_stride = 3LL * out_w;
   if (rgb_stride < dev_stride) return fail(ctx, JB_ERR_GEOMETRY, "rgb_stride %lld < 3*width", (long long)rgb_stride);
-  const size_t coef_total = (size_t)g.coef_bytes * (size_t)n_images, rgb_total = (size_t)g.rgb_bytes * (size_t)n_images;
+  const size_t coef_total = (size_t)g.coef_bytes * (size_t)n_images, rgb_total = (size_t)out_bytes * (size_t)n_images;
   if (coef_total > ctx->max_coef || (!dst_device && (rgb_total > ctx->rgb_alloc || rgb_total > ctx->max_rgb)))
     return fail(ctx, JB_ERR_CAPACITY, "%d image(s) of %dx%d exceed the capacity the context was created with", n_images,
                 desc->width, desc->height);
@@ -922,8 +953,8 @@ int submit_jobs_impl(jb_ctx *ctx, const JbHuffJob *const *jobs, const uint8_t *p
   b.qtab_image_stride = n_images > 1 ? 768 : 0;
   b.d_rgb = dst_device ? rgb : (uint8_t *)s.d_rgb;
   b.rgb_row_stride = dev_stride;
-  b.rgb_image_stride = g.rgb_bytes;
-  rc = jb_blocks_to_rgb_device(ctx, &b, up);
+  b.rgb_image_stride = out_bytes;
+  rc = seam_launch(ctx, &b, up, scale, "submit");
   if (rc) return rc;
   // the status words travel with the pixels: into the caller's (pinned) words when it keeps its own
   // -- many threads share this ring, a slot's words may be recycled before their owner looks -- else
@@ -948,7 +979,7 @@ int submit_jobs_impl(jb_ctx *ctx, const JbHuffJob *const *jobs, const uint8_t *p
     it.dst = rgb, it.src = s.d_rgb, it.bytes = rgb_total;
     it.rows = 0, it.dst_pitch = it.src_pitch = it.row_bytes = 0;
     if (rgb_stride != dev_stride)
-      it.rows = (size_t)desc->height, it.dst_pitch = (size_t)rgb_stride, it.src_pitch = (size_t)dev_stride, it.row_bytes = (size_t)desc->width * 3;
+      it.rows = (size_t)out_h, it.dst_pitch = (size_t)rgb_stride, it.src_pitch = (size_t)dev_stride, it.row_bytes = (size_t)out_w * 3;
     it.status_dst = nullptr;
     it.status_src = nullptr;
     it.status_bytes = 0;
@@ -1023,16 +1054,25 @@ int jb_entropy_decode_device(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes
 
 // decode(bytes) with the entropy stage on the device: one prepared image through the ring
 // (used by jb_decode_memory, jb_frontend.cpp); the staging ring follows the frame
+int jb_decode_job_scaled_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride, int scale);
 int jb_decode_job_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride) {
+  return jb_decode_job_scaled_(ctx, job, rgb, rgb_stride, 1);
+}
+
+// the same at 1/scale (jb_decode_memory_scaled): rgb / rgb_stride describe the reduced image
+int jb_decode_job_scaled_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride, int scale) {
   const bool timing = ctx->knobs.timing == 1;
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t0 = timing ? now() : 0;
-  int rc = jb_ctx_reserve(ctx, (size_t)job->geo.coef_bytes, (size_t)job->geo.rgb_bytes);
+  int32_t out_w = 0, out_h = 0;
+  if (jb_scaled_size(job->desc.width, job->desc.height, scale, &out_w, &out_h) != JB_OK)
+    return fail(ctx, JB_ERR_GEOMETRY, "scale %d is not 1, 2, 4 or 8", scale);
+  int rc = jb_ctx_reserve(ctx, (size_t)job->geo.coef_bytes, (size_t)3 * out_w * out_h);
   if (rc) return rc;
   const double t1 = timing ? now() : 0;
   int ticket = -1;
   const JbHuffJob *jobs[1] = {job};
-  rc = submit_jobs_impl(ctx, jobs, nullptr, nullptr, nullptr, nullptr, 1, rgb, rgb_stride, nullptr, &ticket);
+  rc = submit_jobs_impl(ctx, jobs, nullptr, nullptr, nullptr, nullptr, 1, rgb, rgb_stride, nullptr, &ticket, false, scale);
   if (rc) return rc;
   const double t2 = timing ? now() : 0;
   rc = jb_wait(ctx, ticket);
@@ -1041,15 +1081,19 @@ int jb_decode_job_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_
 }
 
 // several prepared images of ONE geometry in one submission (jb_batch.cpp); pixels contiguous, tight rows
+// (scale: the pixels are the area-reduced images, tight rows of 3 * ceil(width / scale) bytes)
 int jb_submit_packed_(jb_ctx *ctx, const jb_image_desc *desc, const uint16_t *qtabs, const uint8_t *packed, const JbHuffLayout *lay,
-                      uint8_t *rgb, uint32_t *status_out, int *ticket, int dst_device) {
-  return submit_jobs_impl(ctx, nullptr, packed, lay, desc, qtabs, lay->n, rgb, 3LL * desc->width, status_out, ticket, dst_device != 0);
+                      uint8_t *rgb, uint32_t *status_out, int *ticket, int dst_device, int scale) {
+  const int64_t out_w = (desc->width + scale - 1) / (scale > 0 ? scale : 1);
+  return submit_jobs_impl(ctx, nullptr, packed, lay, desc, qtabs, lay->n, rgb, 3LL * out_w, status_out, ticket, dst_device != 0, scale);
 }
 
-// jb_submit_batch with the pixels left in DEVICE memory of the context's device (jb_batch.cpp)
-int jb_submit_batch_dev_(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef, const uint16_t *qtabs,
-                         uint8_t *d_rgb, int *ticket) {
-  return submit_impl(ctx, desc, n_images, coef, qtabs, d_rgb, 3LL * desc->width, ticket, true);
+// a group of the batch decoder (jb_batch.cpp): jb_submit_batch, or (dst_device = 1) with the pixels left in DEVICE
+// memory of the context's device; at 1/scale (tight rows of 3 * ceil(width / scale) bytes)
+int jb_submit_group_(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef, const uint16_t *qtabs,
+                     uint8_t *rgb, int *ticket, int dst_device, int scale) {
+  const int64_t out_w = (desc->width + scale - 1) / (scale > 0 ? scale : 1);
+  return submit_impl(ctx, desc, n_images, coef, qtabs, rgb, 3LL * out_w, ticket, dst_device != 0, scale);
 }
 
 int jb_submit(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs,
@@ -1105,6 +1149,17 @@ int jb_blocks_to_rgb(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef
                      uint8_t *rgb, int64_t rgb_stride) {
   int ticket = -1;
   int rc = jb_submit(ctx, desc, coef, qtabs, rgb, rgb_stride, &ticket);
+  if (rc) return rc;
+  return jb_wait(ctx, ticket);
+}
+
+// jb_blocks_to_rgb at 1/scale (jb_decode_memory_scaled's host-entropy path): rgb holds the reduced image
+int jb_blocks_to_rgb_scaled_(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs,
+                             uint8_t *rgb, int64_t rgb_stride, int scale) {
+  if (!ctx) return fail(nullptr, JB_ERR_NULL, "jb_blocks_to_rgb: ctx is NULL");
+  if (!desc || !coef || !qtabs || !rgb) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb: NULL pointer");
+  int ticket = -1;
+  int rc = submit_impl(ctx, desc, 1, coef, qtabs, rgb, rgb_stride, &ticket, false, scale);
   if (rc) return rc;
   return jb_wait(ctx, ticket);
 }

@@ -37,10 +37,12 @@ int jb_fail_(jb_ctx *ctx, int code, const char *msg);
 // device-side entropy decoding: several prepared images of one geometry in one submission; the
 // images' status words (0 = decoded cleanly) are copied to `status_out` (pinned) with the pixels
 // (dst_device: `rgb` is device memory of the context's device, nothing is downloaded)
+// (scale: the pixels are the area-reduced images of jb_batch_decoder_set_scale, tight rows)
 extern "C" int jb_submit_packed_(jb_ctx *ctx, const jb_image_desc *desc, const uint16_t *qtabs, const uint8_t *packed,
-                                 const JbHuffLayout *lay, uint8_t *rgb, uint32_t *status_out, int *ticket, int dst_device);
-extern "C" int jb_submit_batch_dev_(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef, const uint16_t *qtabs,
-                                    uint8_t *d_rgb, int *ticket);
+                                 const JbHuffLayout *lay, uint8_t *rgb, uint32_t *status_out, int *ticket, int dst_device, int scale);
+// jb_submit_batch (dst_device = 0) or its device-output form (1) at 1/scale
+extern "C" int jb_submit_group_(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef, const uint16_t *qtabs,
+                                uint8_t *rgb, int *ticket, int dst_device, int scale);
 // jb_wait in two halves, so that many threads can wait on one shared context (jb_api.cpp):
 // under the caller's lock, the event to block on (nullptr: the submission has completed) ...
 void *jb_wait_begin_(jb_ctx *ctx, int ticket);
@@ -123,7 +125,8 @@ struct Parsed {
   std::vector<uint8_t> bytes;
   bool loaded = false;  // `bytes` is the whole file (pass 1 reads only the head of a large file)
   jb_image_desc desc;
-  jb_geometry geo;
+  jb_geometry geo;         // (geo.rgb_bytes: the bytes of the OUTPUT image, reduced when the run's scale is > 1)
+  int32_t out_w = 0, out_h = 0;  // the output image's size
   uint16_t qtabs[256];
   int status = JB_OK;
   std::string error;
@@ -279,6 +282,7 @@ struct Run {
   bool lazy = false;
   std::vector<std::vector<int>> *deferred = nullptr;
   size_t slot_coef = 0, slot_rgb = 0;  // what a ring slot holds (one image may be larger than a group's bound, not than this)
+  int scale = 1;                       // output at 1/scale (jb_batch_decoder_set_scale)
 };
 
 // pass 1 (per host thread): parse the headers of its files, so that the buffers can be sized once for
@@ -295,9 +299,13 @@ struct Run {
 // thread opening the same inodes -- 59 us per file against 12 us for one thread alone.)
 constexpr size_t kHeadBytes[2] = {(size_t)4 << 10, (size_t)64 << 10};
 
-void parse_one(Parsed &p) {
+// every size of the pixels that this file takes downstream -- staging, arena, ring slots, copies -- is the output's:
+// geo.rgb_bytes is set to the reduced image's bytes at scale > 1
+void parse_one(Parsed &p, int scale) {
   p.status = jb_entropy_decode(p.bytes.data(), p.bytes.size(), &p.desc, p.qtabs, nullptr, 0);
   if (p.status == JB_OK) p.status = jb_geometry_of(&p.desc, &p.geo);
+  if (p.status == JB_OK) p.status = jb_scaled_size(p.desc.width, p.desc.height, scale, &p.out_w, &p.out_h);
+  if (p.status == JB_OK) p.geo.rgb_bytes = 3LL * p.out_w * p.out_h;
   if (p.status != JB_OK) p.error = jb_last_error(nullptr);
 }
 
@@ -314,7 +322,7 @@ void parse_pass(const Run &r, int t, std::vector<Parsed> &parsed, size_t *max_co
       ok = level < 2 ? read_prefix(r.paths[i], kHeadBytes[level], p.bytes, &p.loaded) : read_file(r.paths[i], p.bytes);
       *t_read += now_s() - a;
       if (level == 2) p.loaded = ok;
-      if (ok) parse_one(p);
+      if (ok) parse_one(p, r.scale);
     }
     if (!ok) {
       p.status = JB_ERR_FORMAT;
@@ -373,7 +381,7 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
       p.have = true;
       p.loaded = ok;
       if (ok) {
-        parse_one(p);
+        parse_one(p, r.scale);
       } else {
         p.status = JB_ERR_FORMAT;
         p.error = "cannot read file";
@@ -445,8 +453,7 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
           void *ev2 = nullptr;
           {
             std::lock_guard<std::mutex> lk(r.dev->mu);
-            st_j = to_device ? jb_submit_batch_dev_(r.dev->ctx, &p.desc, 1, cbuf, p.qtabs, staged, &ticket)
-                             : jb_submit_batch(r.dev->ctx, &p.desc, 1, cbuf, p.qtabs, staged, &ticket);
+            st_j = jb_submit_group_(r.dev->ctx, &p.desc, 1, cbuf, p.qtabs, staged, &ticket, to_device, r.scale);
             if (st_j == JB_OK) ev2 = jb_wait_begin_(r.dev->ctx, ticket);
             else text_j = jb_last_error(r.dev->ctx);
           }
@@ -583,8 +590,8 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
       const int i = index_of(k + j);
       Parsed &p = parsed[(size_t)(k + j)];
       memcpy(&qtabs[(size_t)j * 256], p.qtabs, sizeof p.qtabs);
-      r.widths[i] = p.desc.width;
-      r.heights[i] = p.desc.height;
+      r.widths[i] = p.out_w;
+      r.heights[i] = p.out_h;
       r.rgb[i] = nullptr;
       if (st == JB_OK) {
         r.rgb[i] = use_arena ? dst + (size_t)j * rgb_bytes : jb_alloc_pixels_(rgb_bytes);
@@ -614,11 +621,10 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
       // transfers and the kernel run while this thread decodes its next group
       std::lock_guard<std::mutex> lk(r.dev->mu);
       if (on_device) {
-        st = jb_submit_packed_(r.dev->ctx, &head.desc, qtabs.data(), lane->blob[s], &lay, dst, lane->status[s], &grp[s].ticket, to_device);
-      } else if (to_device) {
-        st = jb_submit_batch_dev_(r.dev->ctx, &head.desc, n, lane->coef[s], qtabs.data(), dst, &grp[s].ticket);
+        st = jb_submit_packed_(r.dev->ctx, &head.desc, qtabs.data(), lane->blob[s], &lay, dst, lane->status[s], &grp[s].ticket, to_device,
+                               r.scale);
       } else {
-        st = jb_submit_batch(r.dev->ctx, &head.desc, n, lane->coef[s], qtabs.data(), dst, &grp[s].ticket);
+        st = jb_submit_group_(r.dev->ctx, &head.desc, n, lane->coef[s], qtabs.data(), dst, &grp[s].ticket, to_device, r.scale);
       }
       if (st != JB_OK) text = jb_last_error(r.dev->ctx);
       t_wait += now_s() - a;
@@ -674,6 +680,7 @@ struct jb_batch_decoder {
   bool made_multi = false;
   int made_threads = 0;
   size_t made_coef = 0, made_rgb = 0;
+  int scale = 1;  // output at 1/scale (jb_batch_decoder_set_scale): on this decoder, its parts and its twin alike
   // jb_batch_decoder_submit / _collect: up to two batches in flight, batch k on side k & 1 -- side 0 is this
   // decoder, side 1 its twin (same devices, threads and sizes, its own ring, staging and arena) -- so that the
   // start-up of one batch (headers, first groups) runs under the tail of the other (last kernels, last downloads)
@@ -828,6 +835,7 @@ int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8
           &lists, rgb, widths, heights, statuses, d->arena, &dev, &tot, &d->knobs};
     r.lazy = lazy;
     r.deferred = &deferred;
+    r.scale = d->scale;
     const double tr0 = now_s();
     std::vector<std::vector<Parsed>> parsed((size_t)nt);
     for (int t = 0; t < nt; t++) parsed[(size_t)t].resize(lists[(size_t)t].size());
@@ -1088,6 +1096,14 @@ extern "C" int jb_batch_decoder_set_device_outputs(jb_batch_decoder *d, void *co
 
 namespace {
 
+// the decoder, its parts and its twin (with the twin's parts) decode at 1/scale
+void set_scale_all(jb_batch_decoder *d, int scale) {
+  if (!d) return;
+  d->scale = scale;
+  for (jb_batch_decoder *p : d->parts) set_scale_all(p, scale);
+  set_scale_all(d->twin, scale);
+}
+
 // the single-device decoders a decoder consists of
 std::vector<jb_batch_decoder *> singles_of(jb_batch_decoder *d) {
   if (d->parts.empty()) return std::vector<jb_batch_decoder *>(1, d);
@@ -1231,6 +1247,7 @@ extern "C" int jb_batch_decoder_submit(jb_batch_decoder *d, const char *const *p
     if (rc != JB_OK) return rc;
     d->twin = t;
     d->split_for_sides = false;
+    set_scale_all(t, d->scale);
   }
   if (!d->split_for_sides) {  // (only ever the case with nothing in flight: every call that clears it refuses otherwise)
     int rc = arrange_outputs(d, true);
@@ -1269,6 +1286,15 @@ extern "C" int jb_batch_decoder_collect(jb_batch_decoder *d, int ticket, double 
   if (times)
     for (int j = 0; j < 4; j++) times[j] = f.times[j];
   return f.rc == JB_OK ? JB_OK : jb_fail_(nullptr, f.rc, f.text.c_str());
+}
+
+extern "C" int jb_batch_decoder_set_scale(jb_batch_decoder *d, int denom) {
+  if (!d) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_set_scale: decoder is NULL");
+  if (denom != 1 && denom != 2 && denom != 4 && denom != 8)
+    return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_set_scale: denom is not 1, 2, 4 or 8");
+  if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_scale: batches are in flight (collect them first)");
+  set_scale_all(d, denom);
+  return JB_OK;
 }
 
 extern "C" long long jb_batch_decoder_device_entropy_images(const jb_batch_decoder *d) {

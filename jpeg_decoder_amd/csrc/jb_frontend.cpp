@@ -42,6 +42,10 @@ int jb_fail_(jb_ctx *ctx, int code, const char *msg);
 void jb_ctx_set_last_desc_(jb_ctx *ctx, const jb_image_desc *d);
 const JbKnobs *jb_ctx_knobs_(const jb_ctx *ctx);  // jb_api.cpp
 extern "C" int jb_decode_job_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride);  // jb_api.cpp
+// the same two at 1/scale (jb_api.cpp)
+extern "C" int jb_decode_job_scaled_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride, int scale);
+extern "C" int jb_blocks_to_rgb_scaled_(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs,
+                                        uint8_t *rgb, int64_t rgb_stride, int scale);
 // general front end (jb_frontend_ext.cpp): progressive, grayscale, multi-scan files
 int jb_ext_decode_(const uint8_t *jpeg, size_t n, jb_image_desc *desc, uint16_t *qtabs, int16_t *coef,
                    size_t coef_cap_bytes, std::string *err);
@@ -432,9 +436,17 @@ int jb_entropy_decode_mt(const uint8_t *jpeg, size_t jpeg_bytes, jb_image_desc *
 
 int jb_decode_memory(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, uint8_t **rgb, int32_t *width,
                      int32_t *height) {
+  return jb_decode_memory_scaled(ctx, jpeg, jpeg_bytes, 1, rgb, width, height);
+}
+
+// denom = 1: jb_decode_memory; 2, 4, 8: the same decode with the area-reduced store stage (include/jpegblk.h)
+int jb_decode_memory_scaled(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, int denom, uint8_t **rgb, int32_t *width,
+                            int32_t *height) {
   if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_memory: ctx is NULL");
   if (!jpeg || !rgb || !width || !height) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_memory: NULL pointer");
   *rgb = nullptr;
+  if (denom != 1 && denom != 2 && denom != 4 && denom != 8) return jb_fail_(ctx, JB_ERR_GEOMETRY, "jb_decode_memory_scaled: denom is not 1, 2, 4 or 8");
+  int32_t out_w = 0, out_h = 0;  // (of the frame decoded below)
   // The entropy stage of a baseline file can run on the device too (jb_huff.hip): the host then only
   // parses the headers and removes the byte stuffing.  One image is one latency-bound submission
   // (a dozen and a half launches: about 1 ms whatever the size, then ~0.4 ms per megabyte of scan)
@@ -461,16 +473,18 @@ int jb_decode_memory(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, uint8_
       if (jb_huff_prepare_(jpeg, jpeg_bytes, job.get(), nullptr, knobs.chunk_bytes) == JB_OK && jb_huff_worth_it_(*job, min_int) &&
           (forced || job->scan_len >= kAutoDeviceScan)) {
         const double t1 = timing ? now() : 0;
-        uint8_t *out = jb_alloc_pixels_((size_t)job->geo.rgb_bytes);
+        jb_scaled_size(job->desc.width, job->desc.height, denom, &out_w, &out_h);
+        uint8_t *out = jb_alloc_pixels_((size_t)3 * out_w * out_h);
         if (!out) return jb_fail_(ctx, JB_ERR_CAPACITY, "out of host memory");
-        const int rc = jb_decode_job_(ctx, job.get(), out, 3LL * job->desc.width);
+        const int rc = denom == 1 ? jb_decode_job_(ctx, job.get(), out, 3LL * job->desc.width)
+                                  : jb_decode_job_scaled_(ctx, job.get(), out, 3LL * out_w, denom);
         if (timing)
           fprintf(stderr, "jb_decode_memory(device path): prepare %.3f ms, submit + wait %.3f ms (%u intervals, %u chunks, %zu bytes of scan), rc %d\n",
                   (t1 - t0) * 1e3, (now() - t1) * 1e3, job->img.n_int, job->img.n_chunks, job->scan_len, rc);
         if (rc == JB_OK) {
           *rgb = out;
-          *width = job->desc.width;
-          *height = job->desc.height;
+          *width = out_w;
+          *height = out_h;
           jb_ctx_set_last_desc_(ctx, &job->desc);
           return JB_OK;
         }
@@ -486,8 +500,10 @@ int jb_decode_memory(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, uint8_
   jb_geometry g;
   rc = jb_geometry_of(&desc, &g);
   if (rc) return jb_fail_(ctx, rc, "bad frame geometry");
+  rc = jb_scaled_size(desc.width, desc.height, denom, &out_w, &out_h);
+  if (rc) return jb_fail_(ctx, rc, "bad frame geometry");
   // the staging ring follows the frame (a context sized for another image, or created with (0,0))
-  rc = jb_ctx_reserve(ctx, (size_t)g.coef_bytes, (size_t)g.rgb_bytes);
+  rc = jb_ctx_reserve(ctx, (size_t)g.coef_bytes, (size_t)3 * out_w * out_h);
   if (rc) return rc;
   int16_t *coef = (int16_t *)jb_pinned_alloc_on(jb_ctx_device(ctx), (size_t)g.coef_bytes);
   if (!coef) return jb_fail_(ctx, JB_ERR_HIP, jb_last_error(nullptr));
@@ -495,9 +511,10 @@ int jb_decode_memory(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, uint8_
   uint8_t *out = nullptr;
   if (rc) jb_fail_(ctx, rc, jb_last_error(nullptr));
   else {
-    out = jb_alloc_pixels_((size_t)g.rgb_bytes);
+    out = jb_alloc_pixels_((size_t)3 * out_w * out_h);
     if (!out) rc = jb_fail_(ctx, JB_ERR_CAPACITY, "out of host memory");
-    else rc = jb_blocks_to_rgb(ctx, &desc, coef, qtabs, out, 3LL * desc.width);
+    else if (denom == 1) rc = jb_blocks_to_rgb(ctx, &desc, coef, qtabs, out, 3LL * desc.width);
+    else rc = jb_blocks_to_rgb_scaled_(ctx, &desc, coef, qtabs, out, 3LL * out_w, denom);
   }
   jb_pinned_free(coef);
   if (rc) {
@@ -505,13 +522,17 @@ int jb_decode_memory(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, uint8_
     return rc;
   }
   *rgb = out;
-  *width = desc.width;
-  *height = desc.height;
+  *width = out_w;
+  *height = out_h;
   jb_ctx_set_last_desc_(ctx, &desc);
   return JB_OK;
 }
 
 int jb_decode_file(jb_ctx *ctx, const char *path, uint8_t **rgb, int32_t *width, int32_t *height) {
+  return jb_decode_file_scaled(ctx, path, 1, rgb, width, height);
+}
+
+int jb_decode_file_scaled(jb_ctx *ctx, const char *path, int denom, uint8_t **rgb, int32_t *width, int32_t *height) {
   if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_file: ctx is NULL");
   if (!path) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_file: path is NULL");
   FILE *f = fopen(path, "rb");
@@ -521,7 +542,7 @@ int jb_decode_file(jb_ctx *ctx, const char *path, uint8_t **rgb, int32_t *width,
   size_t got;
   while ((got = fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + got);
   fclose(f);
-  return jb_decode_memory(ctx, buf.data(), buf.size(), rgb, width, height);
+  return jb_decode_memory_scaled(ctx, buf.data(), buf.size(), denom, rgb, width, height);
 }
 
 }  // extern "C"

@@ -29,6 +29,15 @@ int jb_geometry_of(const jb_image_desc *d, jb_geometry *g) {
   return JB_OK;
 }
 
+int jb_scaled_size(int32_t width, int32_t height, int denom, int32_t *out_w, int32_t *out_h) {
+  if (!out_w || !out_h) return JB_ERR_NULL;
+  if (denom != 1 && denom != 2 && denom != 4 && denom != 8) return JB_ERR_GEOMETRY;
+  if (width < 1 || height < 1 || width > 65535 || height > 65535) return JB_ERR_GEOMETRY;
+  *out_w = (width + denom - 1) / denom;
+  *out_h = (height + denom - 1) / denom;
+  return JB_OK;
+}
+
 int jb_resolve_qtabs(const jb_image_desc *d, const uint16_t *qtabs, int32_t *out192) {
   if (!d || !qtabs || !out192) return JB_ERR_NULL;
   for (int c = 0; c < 3; c++) {

@@ -35,6 +35,9 @@ int jbk_linear_ok(int hs, int vs, int mcus_x);
 // Launch the fused kernel for luma sampling (hs, vs): one 192-lane workgroup per tile.
 hipError_t jbk_launch(const JbLaunch &p, int hs, int vs, hipStream_t stream);
 const char *jbk_kernel_name(int hs, int vs);
+// The same kernel with an area-reduced store stage (scale 2, 4 or 8; row-bound tiling: p.linear = p.small_grid = 0):
+// p.width / p.height are the full image's, p.rgb and its strides describe the ceil(W/scale) x ceil(H/scale) output.
+hipError_t jbk_launch_scaled(const JbLaunch &p, int hs, int vs, int scale, hipStream_t stream);
 
 // Device-side entropy decoder (jb_huff.hip); structures in jb_huff.h.
 struct JbHuffLaunch;

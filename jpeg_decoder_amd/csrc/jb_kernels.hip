@@ -203,6 +203,16 @@ __device__ __forceinline__ void pack12_rtz(const float (&r)[4], const float (&g)
         "v"(g[3]), "v"(b[3]), "v"(b[2]), "v"(r[3]));  // %11 (w2 byte 2), %12 (w2 byte 3), %13, %14 -> w2 bytes 0,1
 }
 
+// Area-reduced output (SCALE > 1): the mean of the n u8 samples of a box, rounded half up -- floor((s + n/2) / n).
+// A whole box (n = SCALE^2) divides by a shift; the clipped boxes of the last column / row (n = 1..63) exactly.
+template <int SCALE>
+__device__ __forceinline__ uint32_t box_mean(uint32_t s, int n) {
+  constexpr int KK = SCALE * SCALE, SH = SCALE == 2 ? 2 : SCALE == 4 ? 4 : 6;
+  if (n == KK) return (s + KK / 2) >> SH;
+  const uint32_t d = (uint32_t)max(n, 1);
+  return (s + d / 2) / d;
+}
+
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x3_t __attribute__((ext_vector_type(3)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
@@ -267,11 +277,16 @@ struct LaneMap {
 // it was meant for it is 1-3 % slower than the stores it replaces, and 4-10 % slower on aligned rows
 // (profiles/r03/probe_staged.json): the aligned lines are worth about 5 %, the second trip
 // through LDS and the serial pack-then-copy of a row per wave cost more.
-template <int HS, int VS, bool MIXQ, bool LINEAR, bool STAGED = false>
+// SCALE = 2, 4, 8 (row-bound tiling only): the area-reduced output of jbk_launch_scaled -- stages 1 and 2 and the
+// colour transform and u8 conversion of every pixel are those of SCALE = 1; only what is stored differs (see
+// "scaled" below).  p.width / p.height stay the full image's; p.rgb and its strides describe the reduced image.
+template <int HS, int VS, bool MIXQ, bool LINEAR, bool STAGED = false, int SCALE = 1>
 // (5 waves/SIMD are asked for where that costs no spill: 4:4:4 and 4:4:0; forcing it on 4:2:0 or
-// 4:2:2 spills and measured 9 % slower)
-__global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1) ? 5 : 1) void jb_tile_kernel(const JbLaunch p) {
+// 4:2:2 spills and measured 9 % slower; the scaled 4:4:0 instantiations spill at 5 too)
+__global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS == 1)) ? 5 : 1) void jb_tile_kernel(const JbLaunch p) {
   static_assert(!STAGED || LINEAR, "the staged store stage is an instantiation of the linear tiling");
+  static_assert(SCALE == 1 || (!LINEAR && !STAGED && (SCALE == 2 || SCALE == 4 || SCALE == 8)),
+                "the scaled store stage is an instantiation of the row-bound tiling");
   using LM = LaneMap<HS, VS>;
   constexpr int kTileBlocks = LM::TB;
   constexpr int kStripBytes = kTileBlocks * 128;  // half of the tile's f32 samples: 24 or 32 KiB
@@ -473,6 +488,12 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1) ? 5 : 1) void jb_til
   const int lane_late = tid_late & 63;
   const int lane_y_off = (lane_late ^ ((lane_late >> 3) & 1)) * 16;
   const int lane_c_off = HS == 1 ? lane_y_off : (((lane_late >> 1) ^ ((lane_late >> 4) & 1)) * 16 + (lane_late & 1) * 8);
+  // scaled: strip rows a lane sums per wave-iteration, wave-iterations per phase and per wave; SCALE = 8 carries
+  // the sums of its boxes' upper halves (phase 0) to phase 1 in kSJ x 3 registers
+  constexpr int kSR = SCALE < 4 ? SCALE : 4;
+  constexpr int kSIT = (YROWS / kSR) * (TASKS_PER_ROW / 64);
+  constexpr int kSJ = (kSIT + kTileBlocks / 64 - 1) / (kTileBlocks / 64);
+  uint32_t acc8[kSJ][3] = {};
 
 #pragma unroll
   for (int phase = 0; phase < 2; phase++) {
@@ -561,6 +582,110 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1) ? 5 : 1) void jb_til
           m += cnt;
           mx_k = 0;
           my_k++;
+        }
+      }
+    } else if constexpr (SCALE > 1) {
+      // ---- scaled: area-reduced output, one lane = a column of 4 adjacent pixels ----
+      // A wave-iteration takes kSR strip rows (2 for SCALE = 2, else 4) of one 256-pixel segment: every lane
+      // computes the colour of its 4 pixels in each row exactly as the full-size stage does (the same LDS reads, the
+      // same transform, the same pack12_rtz conversion to u8) and adds the u8 samples up per channel.  SCALE = 2 and 4
+      // boxes lie inside one phase (4:2:0 / 4:4:0 strip rows 0-3 and 4-7 are two block rows): the lane owns 2 / 1
+      // whole boxes and stores them.  SCALE = 8: a box is two lanes wide (x4 even + odd) and both phases high; the
+      // lane keeps its phase-0 sums in acc8 and in phase 1 the even lane adds its neighbour's sums and stores.
+      // Samples past the image (MCU padding, rows below the last) never enter a sum.  Stores are 3- or 6-byte buffer
+      // stores at any byte address; the byte-store knob is not looked at here.
+      constexpr int IPR = TASKS_PER_ROW / 64;
+      constexpr int SEG_MCUS = 256 / (8 * HS);
+      uint8_t *const out_img = p.rgb + (int64_t)img * p.rgb_image_stride;
+#pragma unroll
+      for (int j = 0; j < kSJ; j++) {
+        const int it = wave + j * (kTileBlocks / 64);
+        if (it >= kSIT) break;
+        const int rg = it / IPR, seg = it - rg * IPR;
+        const int r0 = rg * kSR;                                            // first strip row of the group
+        const int y0 = my * 8 * VS + phase * 4 + (r0 >> 2) * 8 + (r0 & 3);  // its image row
+        const int ybox = SCALE == 8 ? y0 - phase * 4 : y0;                  // first image row of the lane's boxes
+        const int xseg = (mx0 + seg * SEG_MCUS) * 8 * HS;                   // image column of the segment
+        if (ybox >= p.height || xseg >= p.width) continue;                  // (wave-uniform)
+        const int x = xseg + lane_late * 4;                                 // the lane's first pixel
+        const int npx = min(4, p.width - x);                                // its pixels inside the image (<= 0: none)
+        const uint32_t keep = npx >= 4 ? 0xffffffffu : npx <= 0 ? 0u : (1u << (8 * npx)) - 1u;
+        // per channel: SCALE = 2 two 16-bit sums (pixels 0+1 | 2+3), else one sum of the 4 pixels
+        uint32_t s[3] = {0, 0, 0};
+#pragma unroll
+        for (int rr = 0; rr < kSR; rr++) {
+          if (y0 + rr >= p.height) break;  // (wave-uniform)
+          const int row = r0 + rr;
+          const float4 Y = *(const float4 *)(lds + lane_y_off + row * (YW * 4) + seg * 1024);
+          float cb[4], cr[4];
+          const int coff = (row / VS) * (CW * 4) + seg * (1024 / HS);
+          if (HS == 1) {
+            const float4 a = *(const float4 *)(lds + CB_OFF + lane_c_off + coff);
+            const float4 b = *(const float4 *)(lds + CR_OFF + lane_c_off + coff);
+            cb[0] = a.x, cb[1] = a.y, cb[2] = a.z, cb[3] = a.w;
+            cr[0] = b.x, cr[1] = b.y, cr[2] = b.z, cr[3] = b.w;
+          } else {
+            const float2 a = *(const float2 *)(lds + CB_OFF + lane_c_off + coff);
+            const float2 b = *(const float2 *)(lds + CR_OFF + lane_c_off + coff);
+            cb[0] = cb[1] = a.x, cb[2] = cb[3] = a.y;
+            cr[0] = cr[1] = b.x, cr[2] = cr[3] = b.y;
+          }
+          const float yy[4] = {Y.x, Y.y, Y.z, Y.w};
+          float r[4], g[4], b[4];
+#pragma unroll
+          for (int i = 0; i < 4; i++) {
+            r[i] = (yy[i] + JB_CR_R * cr[i]) + 128.0f;
+            g[i] = ((yy[i] - JB_CB_G * cb[i]) - JB_CR_G * cr[i]) + 128.0f;
+            b[i] = (yy[i] + JB_CB_B * cb[i]) + 128.0f;
+          }
+          // the full-size conversion with its operands permuted: pack12_rtz writes bytes in the order
+          // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3, so these arguments give one word per channel (pixels 0..3)
+          const float pr[4] = {r[0], r[3], g[2], b[1]}, pg[4] = {r[1], g[0], g[3], b[2]}, pb[4] = {r[2], g[1], b[0], b[3]};
+          uint32_t w[3];
+          pack12_rtz(pr, pg, pb, w[0], w[1], w[2]);
+#pragma unroll
+          for (int c = 0; c < 3; c++) {
+            const uint32_t v8 = w[c] & keep;
+            if (SCALE == 2) s[c] += (v8 & 0x00ff00ffu) + ((v8 >> 8) & 0x00ff00ffu);
+            else s[c] = __builtin_amdgcn_sad_u8(v8, 0u, s[c]);  // + the sum of the 4 bytes
+          }
+        }
+        const int ny = min(SCALE, p.height - ybox);
+        if constexpr (SCALE == 2) {
+          const int nx0 = min(2, p.width - x), nx1 = min(2, p.width - x - 2);
+          uint32_t o0[3], o1[3];
+#pragma unroll
+          for (int c = 0; c < 3; c++) o0[c] = box_mean<2>(s[c] & 0xffffu, nx0 * ny), o1[c] = box_mean<2>(s[c] >> 16, nx1 * ny);
+          const __amdgpu_buffer_rsrc_t rsrc =
+              __builtin_amdgcn_make_buffer_rsrc(out_img + (int64_t)(ybox >> 1) * p.rgb_row_stride, 0, 0x7ffffff0, 0x00020000);
+          const int voff = (x >> 1) * 3;
+          if (nx1 > 0) {
+            __builtin_amdgcn_raw_buffer_store_b32(o0[0] | o0[1] << 8 | o0[2] << 16 | o1[0] << 24, rsrc, voff, 0, JB_STORE_AUX);
+            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)(o1[1] | o1[2] << 8), rsrc, voff + 4, 0, JB_STORE_AUX);
+          } else if (nx0 > 0) {
+            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)(o0[0] | o0[1] << 8), rsrc, voff, 0, JB_STORE_AUX);
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)o0[2], rsrc, voff + 2, 0, JB_STORE_AUX);
+          }
+        } else {
+          int nx = npx;
+          if constexpr (SCALE == 8) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) acc8[j][c] += s[c];
+            if (phase == 0) continue;
+#pragma unroll
+            for (int c = 0; c < 3; c++) s[c] = acc8[j][c] + (uint32_t)__shfl_xor((int)acc8[j][c], 1);
+            nx = min(8, p.width - x);
+          }
+          if ((SCALE == 4 || (lane_late & 1) == 0) && nx > 0) {
+            uint32_t o[3];
+#pragma unroll
+            for (int c = 0; c < 3; c++) o[c] = box_mean<SCALE>(s[c], nx * ny);
+            const __amdgpu_buffer_rsrc_t rsrc =
+                __builtin_amdgcn_make_buffer_rsrc(out_img + (int64_t)(ybox / SCALE) * p.rgb_row_stride, 0, 0x7ffffff0, 0x00020000);
+            const int voff = (x / SCALE) * 3;
+            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)(o[0] | o[1] << 8), rsrc, voff, 0, JB_STORE_AUX);
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)o[2], rsrc, voff + 2, 0, JB_STORE_AUX);
+          }
         }
       }
     } else
@@ -1110,6 +1235,36 @@ static hipError_t launch_t(const JbLaunch &p, hipStream_t stream) {
     else hipLaunchKernelGGL((jb_tile_kernel<HS, VS, false, false>), grid, block, extra_lds, stream, p);
   }
   return hipGetLastError();
+}
+
+// the area-reduced output (jbk_launch_scaled): the row-bound instantiation with the scaled store stage
+template <int HS, int VS, int SCALE>
+static hipError_t launch_scaled_t(const JbLaunch &p, hipStream_t stream) {
+  using LM = LaneMap<HS, VS>;
+  const bool mixq = (LM::MCUS % 64 != 0) && !p.chroma_q_equal;  // as launch_t: 4:2:0 whose Cb and Cr tables differ
+  const dim3 grid(p.n_tiles), block(LM::TB);
+  (void)hipGetLastError();
+  if (mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, true, false, false, SCALE>), grid, block, 0, stream, p);
+  else hipLaunchKernelGGL((jb_tile_kernel<HS, VS, false, false, false, SCALE>), grid, block, 0, stream, p);
+  return hipGetLastError();
+}
+
+template <int SCALE>
+static hipError_t launch_scaled_k(const JbLaunch &p, int hs, int vs, hipStream_t stream) {
+  if (hs == 1 && vs == 1) return launch_scaled_t<1, 1, SCALE>(p, stream);
+  if (hs == 2 && vs == 1) return launch_scaled_t<2, 1, SCALE>(p, stream);
+  if (hs == 1 && vs == 2) return launch_scaled_t<1, 2, SCALE>(p, stream);
+  if (hs == 2 && vs == 2) return launch_scaled_t<2, 2, SCALE>(p, stream);
+  return hipErrorInvalidValue;
+}
+
+hipError_t jbk_launch_scaled(const JbLaunch &p, int hs, int vs, int scale, hipStream_t stream) {
+  if (p.n_tiles <= 0) return hipSuccess;
+  if (p.linear || p.small_grid) return hipErrorInvalidValue;  // (row-bound tiling only)
+  if (scale == 2) return launch_scaled_k<2>(p, hs, vs, stream);
+  if (scale == 4) return launch_scaled_k<4>(p, hs, vs, stream);
+  if (scale == 8) return launch_scaled_k<8>(p, hs, vs, stream);
+  return hipErrorInvalidValue;
 }
 
 int jbk_mcus_per_tile(int hs, int vs) { return tile_blocks(hs, vs) / (hs * vs + 2); }

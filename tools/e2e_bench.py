@@ -15,7 +15,9 @@ Every decode(path) line also carries the device-busy fraction (kernel time of th
 wall time; the kernel time is measured on a resident copy of one image), i.e. how idle the GPU is
 while the host Huffman stage is the bottleneck.
 Usage: python tools/e2e_bench.py [--size 1920x1080] [--sub 444|420] [--n 256] [--threads 1,8,16,64]
-                                 [--source pil|writer]
+                                 [--source pil|writer] [--scale 1,2,4,8]
+  --scale: decode at 1/K (jb_batch_decoder_set_scale); every image of the first timed pass must then equal the
+           area reduction (tests/area_reduce.py) of its file's full-size single-image decode
   --source writer: files from the build's own baseline writer (tools/jpegwriter) on synthetic blocks
 Several GPUs (host-fed scaling): launch one rank per GPU,
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/e2e_bench.py --images <total> ...
@@ -34,7 +36,9 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import jpeg_decoder_amd as jb  # noqa: E402
+from area_reduce import area_reduce  # noqa: E402
 
 
 def make_jpegs(n_distinct, w, h, sub, out_dir, dri_rows=0):
@@ -97,13 +101,15 @@ def pinned_array(nbytes, dtype):
     return p, a
 
 
-def device_output_run(jb, paths, want, threads, device, g0, args, w, h, world):
+def device_output_run(jb, paths, want, threads, device, g0, args, w, h, world, scale=1):
     """The batch with the decoded images left in device memory: no download at all."""
     import torch
     n = len(paths)
-    per = (g0.rgb_bytes + 255) // 256 * 256
+    ow, oh = jb.scaled_size(w, h, scale)
+    out_bytes = ow * oh * 3
+    per = (out_bytes + 255) // 256 * 256
     region = torch.empty(n * per, dtype=torch.uint8, device=f"cuda:{device}")
-    with jb.BatchDecoder(threads, device, g0.coef_bytes, g0.rgb_bytes) as dec:
+    with jb.BatchDecoder(threads, device, g0.coef_bytes, g0.rgb_bytes, scale=scale) as dec:
         dec.set_device_output(region.data_ptr(), region.numel())
         dec.run_to_device(paths[:threads])
         runs = []
@@ -113,12 +119,12 @@ def device_output_run(jb, paths, want, threads, device, g0, args, w, h, world):
             if k == 0:   # every image, copied back after the clock has stopped
                 for i, p in enumerate(paths):
                     off = ptrs[i] - region.data_ptr()
-                    got = region[off:off + g0.rgb_bytes].cpu().numpy().reshape(want[p].shape)
+                    got = region[off:off + out_bytes].cpu().numpy().reshape(want[p].shape)
                     assert np.array_equal(got, want[p]), f"device output: image {i} differs from the single-image decode"
             runs.append(tm)
         on_device = dec.device_entropy_images
     tm = min(runs, key=lambda x: x["wall_s"])
-    return {"output": "device memory (nothing downloaded)", "threads": threads, "images_per_s": round(args.n / tm["wall_s"], 1),
+    return {"output": "device memory (nothing downloaded)", "scale": scale, "threads": threads, "images_per_s": round(args.n / tm["wall_s"], 1),
             "mpix_per_s": round(args.n * w * h / tm["wall_s"] / 1e6, 1), "entropy_cpu_s": round(tm["entropy_s"], 3),
             "submit_wait_s": round(tm["device_s"], 3), "wall_s": round(tm["wall_s"], 3), "walls": [round(x["wall_s"], 3) for x in runs],
             "n_gpus": world, "pixels_checked": n, "entropy_on_device": bool(on_device)}
@@ -188,6 +194,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=2, help="timed runs per configuration (the best is reported, all walls listed)")
     ap.add_argument("--no-pcie", action="store_true", help="skip part (2), so that the last device activity of the run is the last "
                     "timed batch (tools/timeline.py reads that burst out of a rocprofv3 trace)")
+    ap.add_argument("--scale", default="1", help="output at 1/K for every K of this comma-separated list of 1, 2, 4, 8")
     ap.add_argument("--stream", type=int, default=0, help="also stream the files as batches of this many through "
                     "jb_batch_decoder_submit / _collect (two in flight), next to the same batches through run() one after the other")
     args = ap.parse_args()
@@ -223,12 +230,16 @@ def main():
         del c0
         # two output modes: "malloc" = the default ABI (pixels copied from pinned staging into
         # malloc'ed per-image buffers), "arena" = a pinned output arena owned by the decoder
-        for mode, t in [(m, int(x)) for m in args.modes.split(",") for x in args.threads.split(",")]:
-            arena = (n_mine * ((g0.rgb_bytes + 255) // 256 * 256)) if mode == "arena" else 0
+        full = want
+        for scale, mode, t in [(int(k), m, int(x)) for k in args.scale.split(",") for m in args.modes.split(",")
+                               for x in args.threads.split(",")]:
+            want = full if scale == 1 else {p: area_reduce(v, scale) for p, v in full.items()}   # what the batch must decode to
+            ow, oh = jb.scaled_size(w, h, scale)
+            arena = (n_mine * ((ow * oh * 3 + 255) // 256 * 256)) if mode == "arena" else 0
             if mode == "device":   # device-resident output: the pixels stay in HBM (jb_batch_decoder_set_device_output)
-                res.append(device_output_run(jb, paths, want, t, device, g0, args, w, h, world))
+                res.append(device_output_run(jb, paths, want, t, device, g0, args, w, h, world, scale))
                 continue
-            with jb.BatchDecoder(t, device, g0.coef_bytes, g0.rgb_bytes, arena_bytes=arena) as dec:
+            with jb.BatchDecoder(t, device, g0.coef_bytes, g0.rgb_bytes, arena_bytes=arena, scale=scale) as dec:
                 dec.run(paths[:t], keep_pixels=False)          # touch every lane once
                 bad = []
 
@@ -252,7 +263,7 @@ def main():
                 tw = torch.tensor([tm["wall_s"]], dtype=torch.float64)
                 dist.all_reduce(tw, op=dist.ReduceOp.MAX)
                 tm = dict(tm, wall_s=float(tw.item()))
-            res.append({"output": mode, "threads": t, "images_per_s": round(args.n / tm["wall_s"], 1),
+            res.append({"output": mode, "scale": scale, "threads": t, "images_per_s": round(args.n / tm["wall_s"], 1),
                         "mpix_per_s": round(args.n * w * h / tm["wall_s"] / 1e6, 1),
                         "entropy_cpu_s": round(tm["entropy_s"], 3), "submit_wait_s": round(tm["device_s"], 3),
                         "wall_s": round(tm["wall_s"], 3), "walls": walls,

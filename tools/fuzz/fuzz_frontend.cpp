@@ -47,6 +47,8 @@ int jb_decode_job_(jb_ctx *, const JbHuffJob *, uint8_t *, int64_t) { return JB_
 void jb_pinned_free(void *p) { free(p); }
 void jb_free(void *p) { free(p); }
 int jb_blocks_to_rgb(jb_ctx *, const jb_image_desc *, const int16_t *, const uint16_t *, uint8_t *, int64_t) { return JB_OK; }
+int jb_decode_job_scaled_(jb_ctx *, const JbHuffJob *, uint8_t *, int64_t, int) { return JB_OK; }
+int jb_blocks_to_rgb_scaled_(jb_ctx *, const jb_image_desc *, const int16_t *, const uint16_t *, uint8_t *, int64_t, int) { return JB_OK; }
 }
 
 static uint64_t rng_state = 88172645463325252ull;
