@@ -243,6 +243,49 @@ int jb_decode_memory_scaled(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes,
                             int32_t *width, int32_t *height);
 int jb_decode_file_scaled(jb_ctx *ctx, const char *path, int denom, uint8_t **rgb, int32_t *width, int32_t *height);
 
+/* ---- tensor-ready output: planar u8, or normalised f32 / f16, written by the pixel kernel ----
+ * An OUTPUT FORMAT says what the pixel kernel stores.  With `full` = what the entry points above return for the
+ * image, bit for bit (interleaved uint8):
+ *
+ *     JB_FMT_RGB_U8_HWC   uint8    interleaved R,G,B -- the default: this value takes exactly the old code paths
+ *     JB_FMT_RGB_U8_CHW   uint8    three planes R, G, B of `height` rows:  plane[c][y][x] = full[y][x][c]
+ *     JB_FMT_RGB_F32_CHW  float    the same planes:  (float)full[y][x][c] * scale[c] + bias[c]
+ *     JB_FMT_RGB_F16_CHW  half     the f32 value above converted to IEEE binary16, round to nearest even
+ *
+ * i.e. one image is a [3, H, W] tensor, a batch of equal images [N, 3, H, W]: what a model reads, without a
+ * permute / convert / normalise pass over HBM behind the decoder.  The float value is defined operation by
+ * operation -- uint8 -> f32 (exact), ONE f32 multiply, then ONE f32 add (not fused), then for f16 one conversion --
+ * so NumPy's (u.astype(float32) * float32(s) + float32(b)) [.astype(float16)] reproduces it bit for bit.  ImageNet
+ * normalisation is scale[c] = 1 / (255 * std[c]), bias[c] = -mean[c] / std[c].
+ * Not combined with scaled output: a format other than JB_FMT_RGB_U8_HWC together with denom != 1 is
+ * JB_ERR_UNSUPPORTED on every route.  The host-buffer seam (jb_blocks_to_rgb, jb_submit, jb_submit_batch) stays
+ * interleaved.  An unknown format, reserved != 0, a plane_stride smaller than row stride * height, or a scale / bias
+ * that is not finite is JB_ERR_GEOMETRY.  The planar launches use the row-bound tiling and ignore JPEGBLK_SMALL_GRID
+ * and JPEGBLK_BYTE_STORE. */
+enum { JB_FMT_RGB_U8_HWC = 0, JB_FMT_RGB_U8_CHW = 1, JB_FMT_RGB_F32_CHW = 2, JB_FMT_RGB_F16_CHW = 3 };
+typedef struct jb_output_spec {
+  int32_t format;       /* JB_FMT_* */
+  int32_t reserved;     /* 0 */
+  int64_t plane_stride; /* device seam only: bytes between the planes of one image; 0 = rgb_row_stride * height */
+  float scale[3];       /* float formats only (ignored otherwise) */
+  float bias[3];
+} jb_output_spec;
+/* Bytes of one W x H image in `format` with tight rows and planes: 3 * W * H * element size.  Pure host code. */
+int jb_output_bytes(int32_t width, int32_t height, int format, int64_t *bytes);
+/* Validate a spec against planes of `height` rows, `row_stride` bytes apart (the rules above).  Pure host code. */
+int jb_output_spec_check(const jb_output_spec *spec, int32_t height, int64_t row_stride);
+/* jb_blocks_to_rgb_device in spec->format.  For a planar format batch->rgb_row_stride is the bytes between the rows
+ * OF A PLANE (>= width * element size), spec->plane_stride between the planes, batch->rgb_image_stride between the
+ * images (>= 3 planes).  uint8 planes may start anywhere and take any strides; f32 / f16 want d_rgb and all three
+ * strides to be multiples of the element size (else JB_ERR_GEOMETRY).  format 0 is jb_blocks_to_rgb_device. */
+int jb_blocks_to_rgb_device_fmt(jb_ctx *ctx, const jb_device_batch *batch, const jb_output_spec *spec, void *stream);
+/* jb_decode_memory / jb_decode_file in spec->format: *out is malloc'ed (jb_free), tight rows and planes
+ * (jb_output_bytes), elements of the format's type.  Both entropy paths take the format (the same rule picks the
+ * device entropy stage); spec->plane_stride must be 0 here. */
+int jb_decode_memory_fmt(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, const jb_output_spec *spec, void **out,
+                         int32_t *width, int32_t *height);
+int jb_decode_file_fmt(jb_ctx *ctx, const char *path, const jb_output_spec *spec, void **out, int32_t *width, int32_t *height);
+
 /* ---- host front end ("next" rows of the scope table; reference jpeg.cpp:67-446, 826-907,
  *      include/file.hpp, include/huffman.hpp) --------------------------------------------- */
 /* Parse a JFIF byte stream and Huffman-decode it into packed int16 blocks in the order
@@ -388,6 +431,14 @@ int jb_batch_decoder_set_device_outputs(jb_batch_decoder *dec, void *const *d_ba
  * needs room for the reduced images).  Applies to every device of a multi-device decoder and to both sides of
  * submit / collect.  Refused with JB_ERR_STATE while a batch is in flight. */
 int jb_batch_decoder_set_scale(jb_batch_decoder *dec, int denom);
+/* Output format of the batch decoder's later runs and submissions (see "tensor-ready output" above; spec->plane_stride
+ * must be 0: planes are tight).  Every output form -- malloc'ed, pinned arena, device regions -- then holds
+ * jb_output_bytes(width, height, format) per image, rgb[i] pointing at elements of the format's type; with device
+ * regions every rgb[i] is aligned to the element size.  Applies to every device of a multi-device decoder and to
+ * both sides of submit / collect.  Refused with JB_ERR_STATE while a batch is in flight; a format other than
+ * JB_FMT_RGB_U8_HWC while the scale is not 1 (and jb_batch_decoder_set_scale(!= 1) while such a format is set) with
+ * JB_ERR_UNSUPPORTED. */
+int jb_batch_decoder_set_output_format(jb_batch_decoder *dec, const jb_output_spec *spec);
 /* Output sink replacing the reference's X11 window / unused BMP writer (display.hpp,
  * jpeg.cpp:462-509): binary PPM (P6). */
 int jb_write_ppm(const char *path, const uint8_t *rgb, int32_t width, int32_t height,

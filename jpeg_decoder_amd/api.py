@@ -45,6 +45,52 @@ class DeviceBatch(ctypes.Structure):
                 ("rgb_row_stride", ctypes.c_int64)]
 
 
+# output formats (jpegblk.h, "tensor-ready output"): 0 = interleaved uint8 [H, W, 3], the others planar [3, H, W]
+FMT_RGB_U8_HWC, FMT_RGB_U8_CHW, FMT_RGB_F32_CHW, FMT_RGB_F16_CHW = 0, 1, 2, 3
+FMT_DTYPE = {FMT_RGB_U8_HWC: np.uint8, FMT_RGB_U8_CHW: np.uint8, FMT_RGB_F32_CHW: np.float32, FMT_RGB_F16_CHW: np.float16}
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+class OutputSpec(ctypes.Structure):
+    """jb_output_spec.  OutputSpec.make(format, scale=(1, 1, 1), bias=(0, 0, 0)): value = f32(u8) * scale[c] + bias[c]
+    (float formats; scale / bias are rounded to float32 here, as the C struct holds them)."""
+    _fields_ = [("format", ctypes.c_int32), ("reserved", ctypes.c_int32), ("plane_stride", ctypes.c_int64),
+                ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3)]
+
+    @classmethod
+    def make(cls, format, scale=(1.0, 1.0, 1.0), bias=(0.0, 0.0, 0.0), plane_stride=0):
+        s = cls()
+        s.format, s.reserved, s.plane_stride = int(format), 0, int(plane_stride)
+        for c in range(3):
+            s.scale[c], s.bias[c] = float(scale[c]), float(bias[c])
+        return s
+
+    @classmethod
+    def imagenet(cls, format=FMT_RGB_F32_CHW):
+        """(x / 255 - mean) / std as one multiply and one add: scale = 1 / (255 * std), bias = -mean / std."""
+        return cls.make(format, [1.0 / (255.0 * sd) for sd in IMAGENET_STD], [-m / sd for m, sd in zip(IMAGENET_MEAN, IMAGENET_STD)])
+
+    @property
+    def dtype(self):
+        return FMT_DTYPE[self.format]
+
+
+def _as_spec(fmt):
+    """None / an int format / an OutputSpec -> OutputSpec or None (None = the entry points without a format)."""
+    if fmt is None or isinstance(fmt, OutputSpec):
+        return fmt
+    return OutputSpec.make(fmt)
+
+
+def _shape_output(ptr, w, h, spec):
+    """A copy-free view of one decoded image at `ptr`: [H, W, 3] uint8 (no spec / format 0) or [3, H, W] in the format's type."""
+    if spec is None or spec.format == FMT_RGB_U8_HWC:
+        return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_uint8)), shape=(w * h * 3,)).reshape(h, w, 3)
+    dt = np.dtype(FMT_DTYPE[spec.format])
+    raw = np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_uint8)), shape=(w * h * 3 * dt.itemsize,))
+    return raw.view(dt).reshape(3, h, w)
+
+
 def build_library():
     """Compile csrc/ for gfx950 into jpeg_decoder_amd/libjpegblk.so (hipcc cross-compiles
     without a GPU)."""
@@ -144,6 +190,13 @@ def lib():
     L.jb_decode_memory_scaled.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.jb_decode_file_scaled.argtypes = [vp, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.jb_batch_decoder_set_scale.argtypes = [vp, ctypes.c_int]
+    ps = ctypes.POINTER(OutputSpec)
+    L.jb_output_bytes.argtypes = [i32, i32, ctypes.c_int, ctypes.POINTER(i64)]
+    L.jb_output_spec_check.argtypes = [ps, i32, i64]
+    L.jb_blocks_to_rgb_device_fmt.argtypes = [vp, ctypes.POINTER(DeviceBatch), ps, vp]
+    L.jb_decode_memory_fmt.argtypes = [vp, vp, ctypes.c_size_t, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.jb_decode_file_fmt.argtypes = [vp, ctypes.c_char_p, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.jb_batch_decoder_set_output_format.argtypes = [vp, ps]
     L.jb_write_ppm.argtypes = [ctypes.c_char_p, vp, i32, i32, i64]
     L.jb_write_bmp.argtypes = [ctypes.c_char_p, vp, i32, i32, i64]
     if L.jb_abi_version() != 1:
@@ -181,6 +234,13 @@ def scaled_size(width, height, scale):
     w, h = ctypes.c_int32(), ctypes.c_int32()
     _check(lib().jb_scaled_size(int(width), int(height), int(scale), ctypes.byref(w), ctypes.byref(h)))
     return w.value, h.value
+
+
+def output_bytes(width, height, fmt=FMT_RGB_U8_HWC):
+    """jb_output_bytes: bytes of one width x height image in a format (tight rows and planes)."""
+    n = ctypes.c_int64()
+    _check(lib().jb_output_bytes(int(width), int(height), int(fmt.format if isinstance(fmt, OutputSpec) else fmt), ctypes.byref(n)))
+    return n.value
 
 
 def resolve_qtabs(desc, qtabs):
@@ -310,55 +370,73 @@ class Context:
         _check(lib().jb_wait(self._h, ticket), self._h)
 
     # -- the seam, device buffers ------------------------------------------------------------
-    def blocks_to_rgb_device(self, batch, stream=None, scale=1):
+    def blocks_to_rgb_device(self, batch, stream=None, scale=1, fmt=None):
         """scale 2, 4, 8 (jb_blocks_to_rgb_device_scaled): the batch's d_rgb and strides describe images of
-        scaled_size(desc.width, desc.height, scale)."""
+        scaled_size(desc.width, desc.height, scale).  fmt (an OutputSpec or a format number;
+        jb_blocks_to_rgb_device_fmt): planar output -- the batch's rgb_row_stride is then a plane's."""
+        spec = _as_spec(fmt)
+        if spec is not None:
+            if scale != 1 and spec.format != FMT_RGB_U8_HWC:
+                raise JbError(-9, "an output format cannot be combined with a scale")
+            if scale == 1:
+                _check(lib().jb_blocks_to_rgb_device_fmt(self._h, ctypes.byref(batch), ctypes.byref(spec), stream), self._h)
+                return
         if scale == 1:
             _check(lib().jb_blocks_to_rgb_device(self._h, ctypes.byref(batch), stream), self._h)
         else:
             _check(lib().jb_blocks_to_rgb_device_scaled(self._h, ctypes.byref(batch), scale, stream), self._h)
 
     # -- decode(path) -> RGB -----------------------------------------------------------------
-    def decode_file(self, path, scale=1):
-        """-> RGB [H, W, 3]; scale 2, 4, 8: the area-reduced image (jb_decode_file_scaled)."""
+    def decode_file(self, path, scale=1, fmt=None):
+        """-> RGB [H, W, 3]; scale 2, 4, 8: the area-reduced image (jb_decode_file_scaled); fmt (OutputSpec or format
+        number, jb_decode_file_fmt): [3, H, W] in the format's type for the planar formats."""
         p, w, h = ctypes.c_void_p(), ctypes.c_int32(), ctypes.c_int32()
-        if scale == 1:
+        spec = _as_spec(fmt)
+        if spec is not None and scale != 1 and spec.format != FMT_RGB_U8_HWC:
+            raise JbError(-9, "an output format cannot be combined with a scale")
+        if spec is not None and scale == 1:
+            rc = lib().jb_decode_file_fmt(self._h, os.fsencode(path), ctypes.byref(spec), ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
+        elif scale == 1:
             rc = lib().jb_decode_file(self._h, os.fsencode(path), ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
         else:
             rc = lib().jb_decode_file_scaled(self._h, os.fsencode(path), scale, ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
         _check(rc, self._h)
         try:
-            n = w.value * h.value * 3
-            arr = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)), shape=(n,)).copy()
+            arr = _shape_output(p, w.value, h.value, spec if scale == 1 else None).copy()
         finally:
             lib().jb_free(p)
-        return arr.reshape(h.value, w.value, 3)
+        return arr
 
-    def decode_memory(self, jpeg_bytes, scale=1):
+    def decode_memory(self, jpeg_bytes, scale=1, fmt=None):
         """jb_decode_memory: a JFIF byte string -> RGB [H, W, 3] (front end + device seam); scale 2, 4, 8: the
-        area-reduced image (jb_decode_memory_scaled)."""
+        area-reduced image (jb_decode_memory_scaled); fmt: as decode_file (jb_decode_memory_fmt)."""
         buf = np.frombuffer(jpeg_bytes, dtype=np.uint8)
         p, w, h = ctypes.c_void_p(), ctypes.c_int32(), ctypes.c_int32()
-        if scale == 1:
+        spec = _as_spec(fmt)
+        if spec is not None and scale != 1 and spec.format != FMT_RGB_U8_HWC:
+            raise JbError(-9, "an output format cannot be combined with a scale")
+        if spec is not None and scale == 1:
+            rc = lib().jb_decode_memory_fmt(self._h, _ptr(buf), buf.size, ctypes.byref(spec), ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
+        elif scale == 1:
             rc = lib().jb_decode_memory(self._h, _ptr(buf), buf.size, ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
         else:
             rc = lib().jb_decode_memory_scaled(self._h, _ptr(buf), buf.size, scale, ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
         _check(rc, self._h)
         try:
-            n = w.value * h.value * 3
-            arr = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)), shape=(n,)).copy()
+            arr = _shape_output(p, w.value, h.value, spec if scale == 1 else None).copy()
         finally:
             lib().jb_free(p)
-        return arr.reshape(h.value, w.value, 3)
+        return arr
 
 
 class BatchDecoder:
     """jb_batch_decoder: n_threads host lanes (pinned buffers each) feeding one shared context per
     device, reusable.  devices=[...] (jb_batch_decoder_create_multi): one decoder over several
     devices, file i -> devices[i % len(devices)], the host threads split evenly.  scale 2, 4, 8
-    (jb_batch_decoder_set_scale): every image comes out area-reduced."""
+    (jb_batch_decoder_set_scale): every image comes out area-reduced.  fmt (an OutputSpec or a format number;
+    jb_batch_decoder_set_output_format): every image comes out in that format, [3, H, W] for the planar ones."""
 
-    def __init__(self, n_threads=8, device=0, max_coef_bytes=0, max_rgb_bytes=0, arena_bytes=0, devices=None, scale=1):
+    def __init__(self, n_threads=8, device=0, max_coef_bytes=0, max_rgb_bytes=0, arena_bytes=0, devices=None, scale=1, fmt=None):
         self._h = ctypes.c_void_p()
         if devices is not None:
             ids = (ctypes.c_int * len(devices))(*devices)
@@ -368,11 +446,26 @@ class BatchDecoder:
         self._arena = False
         self._device_out = False
         self._flights = {}
+        self._fmt = None
+        self._device = devices[0] if devices else device
         if arena_bytes:
             _check(lib().jb_batch_decoder_set_arena(self._h, arena_bytes))
             self._arena = True
-        if scale != 1:
-            self.set_scale(scale)
+        try:
+            if scale != 1:
+                self.set_scale(scale)
+            if fmt is not None:
+                self.set_output_format(fmt)
+        except JbError:
+            self.close()
+            raise
+
+    def set_output_format(self, fmt):
+        """jb_batch_decoder_set_output_format: the format of later runs and submissions (JbError -7 while a batch is
+        in flight, -9 when the decoder's scale is not 1)."""
+        spec = _as_spec(fmt)
+        _check(lib().jb_batch_decoder_set_output_format(self._h, ctypes.byref(spec)))
+        self._fmt = spec
 
     def set_scale(self, scale):
         """jb_batch_decoder_set_scale: output at 1/scale for later runs and submissions (JbError -7 while a batch
@@ -385,7 +478,7 @@ class BatchDecoder:
 
     def run(self, paths, keep_pixels=True, on_image=None):
         assert not self._device_out, "device output is set: use run_to_device"
-        return decode_batch(paths, keep_pixels=keep_pixels, on_image=on_image, _decoder=self._h, _arena=self._arena)
+        return decode_batch(paths, keep_pixels=keep_pixels, on_image=on_image, _decoder=self._h, _arena=self._arena, _fmt=self._fmt)
 
     def set_device_output(self, d_base, nbytes):
         """jb_batch_decoder_set_device_output: decoded images stay in the caller's DEVICE memory
@@ -418,6 +511,49 @@ class BatchDecoder:
              "error": lib().jb_last_error(None).decode(errors="replace") if rc else ""}
         return [int(rgb[i] or 0) for i in range(n)], [(w[i], h[i]) for i in range(n)], list(st), t
 
+    def run_to_tensor(self, paths, out):
+        """Decode files of ONE size straight into a caller-supplied CUDA tensor through the device-output route:
+        out is [N, 3, H, W] (planar formats; [N, H, W, 3] for format 0), contiguous, of the decoder's format's dtype, on
+        the decoder's device, N = len(paths).  -> (out, statuses, times).  An image whose size does not match out (or
+        that fails to decode) gets a non-zero status (JB_ERR_GEOMETRY = -2 for the size) and its slice of out is left
+        as it was.  The decoder's device-output setting is replaced for the call and cleared afterwards."""
+        import torch
+        spec = self._fmt
+        planar = spec is not None and spec.format != FMT_RGB_U8_HWC
+        dt = {np.uint8: torch.uint8, np.float32: torch.float32, np.float16: torch.float16}[FMT_DTYPE[spec.format] if spec is not None else np.uint8]
+        n = len(paths)
+        if not (out.is_cuda and out.is_contiguous() and out.dtype == dt and out.dim() == 4 and out.shape[0] == n and
+                out.shape[1 if planar else 3] == 3):
+            raise ValueError(f"out must be a contiguous CUDA tensor [{n}, 3, H, W] ([N, H, W, 3] for format 0) of {dt}")
+        if out.device.index != self._device:
+            raise ValueError(f"out is on {out.device}, the decoder on device {self._device}")
+        H, W = (out.shape[2], out.shape[3]) if planar else (out.shape[1], out.shape[2])
+        per = output_bytes(W, H, spec.format if spec is not None else FMT_RGB_U8_HWC)
+        assert per == out[0].numel() * out.element_size()
+        # the decoder places images group by group (a group of one thread's files back to back, groups on 256-byte
+        # steps of the region, in the order the threads get there): they land in a scratch region in their final
+        # format and one device-to-device copy per image puts them in order
+        scratch = torch.empty(n * per + 256 * (n + 1), dtype=torch.uint8, device=out.device)
+        torch.cuda.synchronize(out.device)
+        self.set_device_output(scratch.data_ptr(), scratch.numel())
+        try:
+            ptrs, sizes, st, t = self.run_to_device(paths)
+        finally:
+            self.set_device_output(0, 0)
+        st = list(st)
+        flat = out.view(n, -1).view(torch.uint8) if out.dtype != torch.uint8 else out.view(n, -1)
+        base = scratch.data_ptr()
+        for i in range(n):
+            if st[i] != JB_OK or not ptrs[i]:
+                continue
+            if sizes[i] != (W, H):
+                st[i] = -2   # JB_ERR_GEOMETRY: not the size of `out`
+                continue
+            off = ptrs[i] - base
+            flat[i].copy_(scratch[off:off + per])
+        torch.cuda.synchronize(out.device)
+        return out, st, t
+
     # -- batches in a stream (jb_batch_decoder_submit / _collect): two in flight -----------------
     def submit(self, paths):
         """-> a ticket (keeps the batch's arrays alive); the batch runs while the caller prepares the next one."""
@@ -446,8 +582,7 @@ class BatchDecoder:
         for i in range(n):
             if rgb[i]:
                 if on_image is not None or keep_pixels:
-                    m = w[i] * h[i] * 3
-                    view = np.ctypeslib.as_array(ctypes.cast(rgb[i], ctypes.POINTER(ctypes.c_uint8)), shape=(m,)).reshape(h[i], w[i], 3)
+                    view = _shape_output(rgb[i], w[i], h[i], self._fmt)
                     if on_image is not None:
                         on_image(i, view)
                 out.append(view.copy() if keep_pixels else (w[i], h[i]))
@@ -470,7 +605,7 @@ class BatchDecoder:
         self.close()
 
 
-def decode_batch(paths, n_threads=8, device=0, keep_pixels=True, on_image=None, _decoder=None, _arena=False, scale=1):
+def decode_batch(paths, n_threads=8, device=0, keep_pixels=True, on_image=None, _decoder=None, _arena=False, scale=1, _fmt=None):
     """jb_decode_batch: -> (list of uint8 [H,W,3] arrays or None, statuses, times dict).
     on_image(i, view): called with a no-copy [H,W,3] view of every decoded image before its buffer
     is released (checks over batches too large to keep).  scale 2, 4, 8: through a temporary
@@ -494,12 +629,10 @@ def decode_batch(paths, n_threads=8, device=0, keep_pixels=True, on_image=None, 
     out = []
     for i in range(n):
         if rgb[i]:
-            m = w[i] * h[i] * 3
             if on_image is not None:
-                on_image(i, np.ctypeslib.as_array(ctypes.cast(rgb[i], ctypes.POINTER(ctypes.c_uint8)), shape=(m,)).reshape(h[i], w[i], 3))
+                on_image(i, _shape_output(rgb[i], w[i], h[i], _fmt))
             if keep_pixels:
-                a = np.ctypeslib.as_array(ctypes.cast(rgb[i], ctypes.POINTER(ctypes.c_uint8)), shape=(m,)).copy()
-                out.append(a.reshape(h[i], w[i], 3))
+                out.append(_shape_output(rgb[i], w[i], h[i], _fmt).copy())
             else:
                 out.append((w[i], h[i]))
             if not _arena:  # arena images belong to the decoder
@@ -511,11 +644,32 @@ def decode_batch(paths, n_threads=8, device=0, keep_pixels=True, on_image=None, 
     return out, list(st), t
 
 
-def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, shared_qtabs=True, scale=1):
+def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, shared_qtabs=True, scale=1, fmt=None):
     """DeviceBatch over torch CUDA tensors (plumbing): coef_t int16 [n_images, n_blocks, 64],
     qtabs_t int32 [3,64] (shared) or [n_images,3,64], rgb_t uint8 [n_images, H, row_stride].
     scale 2, 4, 8: rgb_t holds the reduced images, [n_images, ceil(H/scale), row_stride], for
-    Context.blocks_to_rgb_device(..., scale=scale)."""
+    Context.blocks_to_rgb_device(..., scale=scale).
+    fmt (a planar OutputSpec / format number, for Context.blocks_to_rgb_device(..., fmt=)): rgb_t is
+    [n_images, 3, H, W'] in the format's dtype, W' >= W; strides are taken from the tensor (in bytes) and, when fmt is an
+    OutputSpec, its plane_stride is set from rgb_t.stride(1)."""
+    spec = _as_spec(fmt)
+    if spec is not None and spec.format != FMT_RGB_U8_HWC:
+        assert scale == 1, "an output format cannot be combined with a scale"
+        es = rgb_t.element_size()
+        assert rgb_t.dim() == 4 and rgb_t.shape[1] == 3 and rgb_t.shape[2] >= desc.height and rgb_t.shape[3] >= desc.width and rgb_t.stride(3) == 1
+        b = DeviceBatch()
+        b.desc = desc
+        b.n_images = n_images
+        b.d_coef = coef_t.data_ptr()
+        b.coef_image_stride = coef_t.stride(0) * 2 if n_images > 1 else coef_t.numel() * 2
+        b.d_qtabs = qtabs_t.data_ptr()
+        b.qtab_image_stride = 0 if shared_qtabs else 768
+        b.d_rgb = rgb_t.data_ptr()
+        b.rgb_row_stride = rgb_row_stride or rgb_t.stride(2) * es
+        b.rgb_image_stride = rgb_t.stride(0) * es
+        if isinstance(fmt, OutputSpec):
+            fmt.plane_stride = rgb_t.stride(1) * es
+        return b
     if scale != 1:
         out_w, out_h = scaled_size(desc.width, desc.height, scale)
         assert rgb_t.shape[1] >= out_h and (rgb_row_stride or rgb_t.stride(1)) >= 3 * out_w, "rgb_t is smaller than the scaled images"

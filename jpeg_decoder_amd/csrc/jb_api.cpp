@@ -33,6 +33,8 @@
 #include "jb_huff.h"
 #include "jb_knobs.h"
 
+extern "C" int jb_format_esize_(int format);  // jb_geometry.cpp: bytes per element of a JB_FMT_*, 0 = not a format
+
 namespace {
 
 // The staging ring drives up to 8 stream pairs and 16 pool streams per context; the HIP runtime
@@ -522,7 +524,9 @@ namespace {
 // The tile and launch setup of both seams: jb_blocks_to_rgb_device (scale 1: exactly the launch it has always
 // made) and jb_blocks_to_rgb_device_scaled (scale 2, 4, 8: the row-bound tiling with the area-reduced store stage).
 // The batch's row / image strides describe the output, i.e. the reduced image when scale > 1.
-int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int scale, const char *fn) {
+// fmt (null or format 0: the interleaved output, exactly the launches above): a planar format of "tensor-ready output"
+// (jpegblk.h) -- the row-bound tiling with the planar store stage; the batch's row stride is then that of a plane.
+int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int scale, const char *fn, const jb_output_spec *fmt = nullptr) {
   if (!ctx) return fail(nullptr, JB_ERR_NULL, "%s: ctx is NULL", fn);
   if (!b || !b->d_coef || !b->d_qtabs || !b->d_rgb) return fail(ctx, JB_ERR_NULL, "%s: NULL pointer", fn);
   jb_geometry g;
@@ -532,6 +536,25 @@ int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int scale, 
   if (jb_scaled_size(b->desc.width, b->desc.height, scale, &out_w, &out_h) != JB_OK)
     return fail(ctx, JB_ERR_GEOMETRY, "%s: scale %d is not 1, 2, 4 or 8", fn, scale);
   if (b->n_images < 1) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d", b->n_images);
+  if (fmt && fmt->format == JB_FMT_RGB_U8_HWC) {
+    if (fmt->reserved != 0) return fail(ctx, JB_ERR_GEOMETRY, "%s: output spec: reserved must be 0", fn);
+    fmt = nullptr;
+  }
+  int64_t plane_stride = 0;
+  if (fmt) {
+    if (jb_format_esize_(fmt->format) == 0) return fail(ctx, JB_ERR_GEOMETRY, "%s: unknown output format %d", fn, fmt->format);
+    if (scale != 1) return fail(ctx, JB_ERR_UNSUPPORTED, "%s: a planar output format cannot be combined with scale %d", fn, scale);
+    if (jb_output_spec_check(fmt, b->desc.height, b->rgb_row_stride) != JB_OK)
+      return fail(ctx, JB_ERR_GEOMETRY, "%s: bad output spec (reserved, plane_stride < row stride * height, or scale / bias not finite)", fn);
+    const int64_t es = jb_format_esize_(fmt->format);
+    plane_stride = fmt->plane_stride ? fmt->plane_stride : b->rgb_row_stride * (int64_t)b->desc.height;
+    if (b->rgb_row_stride < es * b->desc.width)
+      return fail(ctx, JB_ERR_GEOMETRY, "rgb_row_stride %lld < width * element size", (long long)b->rgb_row_stride);
+    if (((uintptr_t)b->d_rgb | (uint64_t)b->rgb_row_stride | (uint64_t)plane_stride | (uint64_t)(b->n_images > 1 ? b->rgb_image_stride : 0)) & (uint64_t)(es - 1))
+      return fail(ctx, JB_ERR_GEOMETRY, "%s: f32 / f16 output wants the pointer and every stride to be multiples of the element size", fn);
+    if (b->n_images > 1 && b->rgb_image_stride < 2 * plane_stride + b->rgb_row_stride * (int64_t)b->desc.height)
+      return fail(ctx, JB_ERR_GEOMETRY, "image strides smaller than one image");
+  } else
   if (b->rgb_row_stride < 3LL * out_w)
     return fail(ctx, JB_ERR_GEOMETRY, "rgb_row_stride %lld < 3*width", (long long)b->rgb_row_stride);
   if (((uintptr_t)b->d_coef & 15) || (b->coef_image_stride & 15))
@@ -556,7 +579,7 @@ int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int scale, 
   p.mcus_y = g.mcus_y;
   p.tiles_per_row = (g.mcus_x + per_tile - 1) / per_tile;
   // JPEGBLK_ROW_TILING=1 (debug / A-B knob) forces the row-bound tiling; the scaled stage only exists in it
-  const bool force_row = ctx->knobs.row_tiling || scale > 1;
+  const bool force_row = ctx->knobs.row_tiling || scale > 1 || fmt;
   // linear tiling only where the row-bound one would leave ragged tiles
   p.linear = (force_row || g.mcus_x % per_tile == 0) ? 0 : jbk_linear_ok(b->desc.hs, b->desc.vs, g.mcus_x);
   const int64_t tiles_per_image = p.linear ? ((int64_t)g.mcus_x * g.mcus_y + per_tile - 1) / per_tile
@@ -595,7 +618,12 @@ int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int scale, 
   p.chroma_q_equal = (b->desc.qtab_id[1] == b->desc.qtab_id[2]) ? 1 : 0;
   DeviceGuard guard(ctx->device);
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  if (scale == 1) JB_HIP(ctx, jbk_launch(p, b->desc.hs, b->desc.vs, s));
+  if (fmt) {
+    p.format = fmt->format;
+    p.rgb_plane_stride = plane_stride;
+    for (int c = 0; c < 3; c++) p.scale[c] = fmt->scale[c], p.bias[c] = fmt->bias[c];
+    JB_HIP(ctx, jbk_launch_fmt(p, b->desc.hs, b->desc.vs, s));
+  } else if (scale == 1) JB_HIP(ctx, jbk_launch(p, b->desc.hs, b->desc.vs, s));
   else JB_HIP(ctx, jbk_launch_scaled(p, b->desc.hs, b->desc.vs, scale, s));
   return JB_OK;
 }
@@ -610,6 +638,11 @@ int jb_blocks_to_rgb_device(jb_ctx *ctx, const jb_device_batch *b, void *stream)
 
 int jb_blocks_to_rgb_device_scaled(jb_ctx *ctx, const jb_device_batch *b, int denom, void *stream) {
   return seam_launch(ctx, b, stream, denom, "jb_blocks_to_rgb_device_scaled");
+}
+
+int jb_blocks_to_rgb_device_fmt(jb_ctx *ctx, const jb_device_batch *b, const jb_output_spec *spec, void *stream) {
+  if (ctx && !spec) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_fmt: spec is NULL");
+  return seam_launch(ctx, b, stream, 1, "jb_blocks_to_rgb_device_fmt", spec);
 }
 
 int jb_ctx_device(const jb_ctx *ctx) { return ctx ? ctx->device : -1; }
@@ -722,6 +755,10 @@ void jb_pinned_free(void *p) {
 
 namespace {
 
+// element size of a submission's output format (null = interleaved uint8), and whether it is one of the planar ones
+inline int fmt_esize(const jb_output_spec *fmt) { return fmt ? (jb_format_esize_(fmt->format) > 0 ? jb_format_esize_(fmt->format) : 1) : 1; }
+inline bool fmt_planar(const jb_output_spec *fmt) { return fmt && fmt->format != JB_FMT_RGB_U8_HWC; }
+
 constexpr int kMaxBatch = 256;  // images per submission (the slot's table block holds that many)
 
 // One submission of the staging ring: n_images images of one geometry, coefficients contiguous
@@ -731,7 +768,7 @@ constexpr int kMaxBatch = 256;  // images per submission (the slot's table block
 // is downloaded (jb_batch_decoder_set_device_output).
 // scale (2, 4, 8): the pixels are the area-reduced image (jb_scaled_size), rgb / rgb_stride describe it.
 int submit_impl(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef, const uint16_t *qtabs,
-                uint8_t *rgb, int64_t rgb_stride, int *ticket, bool dst_device = false, int scale = 1) {
+                uint8_t *rgb, int64_t rgb_stride, int *ticket, bool dst_device = false, int scale = 1, const jb_output_spec *fmt = nullptr) {
   if (ctx->n_slots == 0) return fail(ctx, JB_ERR_CAPACITY, "context was created without staging buffers");
   jb_geometry g;
   int rc = check_desc(ctx, desc, &g);
@@ -739,8 +776,10 @@ int submit_impl(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int1
   if (n_images < 1 || n_images > kMaxBatch) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d outside 1..%d", n_images, kMaxBatch);
   int32_t out_w = 0, out_h = 0;
   if (jb_scaled_size(desc->width, desc->height, scale, &out_w, &out_h) != JB_OK) return fail(ctx, JB_ERR_GEOMETRY, "scale %d is not 1, 2, 4 or 8", scale);
-  const int64_t out_bytes = 3LL * out_w * out_h;  // g.rgb_bytes when scale == 1
-  const int64_t dev_stride = 3LL * out_w;  // tight rows on the device (12-byte stores need no alignment)
+  const int64_t out_bytes = 3LL * out_w * out_h * fmt_esize(fmt);  // g.rgb_bytes when scale == 1
+  // tight rows on the device (12-byte stores need no alignment); a planar format: tight rows of a plane, tight planes
+  const int64_t dev_stride = fmt_planar(fmt) ? (int64_t)out_w * fmt_esize(fmt) : 3LL * out_w;
+  if (fmt_planar(fmt) && rgb_stride != dev_stride) return fail(ctx, JB_ERR_GEOMETRY, "planar output has tight rows");
   if (rgb_stride < dev_stride) return fail(ctx, JB_ERR_GEOMETRY, "rgb_stride %lld < 3*width", (long long)rgb_stride);
   const size_t coef_total = (size_t)g.coef_bytes * (size_t)n_images, rgb_total = (size_t)out_bytes * (size_t)n_images;
   if (coef_total > ctx->max_coef || (!dst_device && (rgb_total > ctx->rgb_alloc || rgb_total > ctx->max_rgb)))
@@ -789,7 +828,7 @@ int submit_impl(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int1
   b.d_rgb = dst_device ? rgb : (uint8_t *)s.d_rgb;
   b.rgb_row_stride = dev_stride;
   b.rgb_image_stride = out_bytes;
-  rc = seam_launch(ctx, &b, up, scale, "submit");
+  rc = seam_launch(ctx, &b, up, scale, "submit", fmt);
   if (rc) return rc;
   if (dst_device) {
     down = up;  // the pixels stay on the device: done when the kernel is
@@ -895,7 +934,7 @@ int pack_into_slot(jb_ctx *ctx, Slot &s, const JbHuffJob *const *jobs, int n, in
 // and tables (`desc`, `qtabs` = n x 4*64).
 int submit_jobs_impl(jb_ctx *ctx, const JbHuffJob *const *jobs, const uint8_t *packed, const JbHuffLayout *lay_in,
                      const jb_image_desc *desc_in, const uint16_t *qtabs_in, int n_images, uint8_t *rgb, int64_t rgb_stride,
-                     uint32_t *status_out, int *ticket, bool dst_device = false, int scale = 1) {
+                     uint32_t *status_out, int *ticket, bool dst_device = false, int scale = 1, const jb_output_spec *fmt = nullptr) {
   if (ctx->n_slots == 0) return fail(ctx, JB_ERR_CAPACITY, "context was created without staging buffers");
   if (n_images < 1 || n_images > kMaxBatch) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d outside 1..%d", n_images, kMaxBatch);
   const jb_image_desc *desc = jobs ? &jobs[0]->desc : desc_in;
@@ -904,8 +943,9 @@ int submit_jobs_impl(jb_ctx *ctx, const JbHuffJob *const *jobs, const uint8_t *p
   if (rc) return rc;
   int32_t out_w = 0, out_h = 0;
   if (jb_scaled_size(desc->width, desc->height, scale, &out_w, &out_h) != JB_OK) return fail(ctx, JB_ERR_GEOMETRY, "scale %d is not 1, 2, 4 or 8", scale);
-  const int64_t out_bytes = 3LL * out_w * out_h;  // g.rgb_bytes when scale == 1
-  const int64_t dev_stride = 3LL * out_w;
+  const int64_t out_bytes = 3LL * out_w * out_h * fmt_esize(fmt);  // g.rgb_bytes when scale == 1
+  const int64_t dev_stride = fmt_planar(fmt) ? (int64_t)out_w * fmt_esize(fmt) : 3LL * out_w;  // (planar: rows of a plane)
+  if (fmt_planar(fmt) && rgb_stride != dev_stride) return fail(ctx, JB_ERR_GEOMETRY, "planar output has tight rows");
   if (rgb_stride < dev_stride) return fail(ctx, JB_ERR_GEOMETRY, "rgb_stride %lld < 3*width", (long long)rgb_stride);
   const size_t coef_total = (size_t)g.coef_bytes * (size_t)n_images, rgb_total = (size_t)out_bytes * (size_t)n_images;
   if (coef_total > ctx->max_coef || (!dst_device && (rgb_total > ctx->rgb_alloc || rgb_total > ctx->max_rgb)))
@@ -954,7 +994,7 @@ int submit_jobs_impl(jb_ctx *ctx, const JbHuffJob *const *jobs, const uint8_t *p
   b.d_rgb = dst_device ? rgb : (uint8_t *)s.d_rgb;
   b.rgb_row_stride = dev_stride;
   b.rgb_image_stride = out_bytes;
-  rc = seam_launch(ctx, &b, up, scale, "submit");
+  rc = seam_launch(ctx, &b, up, scale, "submit", fmt);
   if (rc) return rc;
   // the status words travel with the pixels: into the caller's (pinned) words when it keeps its own
   // -- many threads share this ring, a slot's words may be recycled before their owner looks -- else
@@ -1055,24 +1095,30 @@ int jb_entropy_decode_device(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes
 // decode(bytes) with the entropy stage on the device: one prepared image through the ring
 // (used by jb_decode_memory, jb_frontend.cpp); the staging ring follows the frame
 int jb_decode_job_scaled_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride, int scale);
+int jb_decode_job_fmt_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride, int scale, const jb_output_spec *fmt);
 int jb_decode_job_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride) {
   return jb_decode_job_scaled_(ctx, job, rgb, rgb_stride, 1);
 }
 
 // the same at 1/scale (jb_decode_memory_scaled): rgb / rgb_stride describe the reduced image
 int jb_decode_job_scaled_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride, int scale) {
+  return jb_decode_job_fmt_(ctx, job, rgb, rgb_stride, scale, nullptr);
+}
+
+// the same in an output format (jb_decode_memory_fmt; null: interleaved): rgb_stride is then a plane's row stride
+int jb_decode_job_fmt_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride, int scale, const jb_output_spec *fmt) {
   const bool timing = ctx->knobs.timing == 1;
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t0 = timing ? now() : 0;
   int32_t out_w = 0, out_h = 0;
   if (jb_scaled_size(job->desc.width, job->desc.height, scale, &out_w, &out_h) != JB_OK)
     return fail(ctx, JB_ERR_GEOMETRY, "scale %d is not 1, 2, 4 or 8", scale);
-  int rc = jb_ctx_reserve(ctx, (size_t)job->geo.coef_bytes, (size_t)3 * out_w * out_h);
+  int rc = jb_ctx_reserve(ctx, (size_t)job->geo.coef_bytes, (size_t)3 * out_w * out_h * fmt_esize(fmt));
   if (rc) return rc;
   const double t1 = timing ? now() : 0;
   int ticket = -1;
   const JbHuffJob *jobs[1] = {job};
-  rc = submit_jobs_impl(ctx, jobs, nullptr, nullptr, nullptr, nullptr, 1, rgb, rgb_stride, nullptr, &ticket, false, scale);
+  rc = submit_jobs_impl(ctx, jobs, nullptr, nullptr, nullptr, nullptr, 1, rgb, rgb_stride, nullptr, &ticket, false, scale, fmt);
   if (rc) return rc;
   const double t2 = timing ? now() : 0;
   rc = jb_wait(ctx, ticket);
@@ -1083,17 +1129,19 @@ int jb_decode_job_scaled_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64
 // several prepared images of ONE geometry in one submission (jb_batch.cpp); pixels contiguous, tight rows
 // (scale: the pixels are the area-reduced images, tight rows of 3 * ceil(width / scale) bytes)
 int jb_submit_packed_(jb_ctx *ctx, const jb_image_desc *desc, const uint16_t *qtabs, const uint8_t *packed, const JbHuffLayout *lay,
-                      uint8_t *rgb, uint32_t *status_out, int *ticket, int dst_device, int scale) {
+                      uint8_t *rgb, uint32_t *status_out, int *ticket, int dst_device, int scale, const jb_output_spec *fmt) {
   const int64_t out_w = (desc->width + scale - 1) / (scale > 0 ? scale : 1);
-  return submit_jobs_impl(ctx, nullptr, packed, lay, desc, qtabs, lay->n, rgb, 3LL * out_w, status_out, ticket, dst_device != 0, scale);
+  const int64_t stride = fmt_planar(fmt) ? out_w * fmt_esize(fmt) : 3LL * out_w;
+  return submit_jobs_impl(ctx, nullptr, packed, lay, desc, qtabs, lay->n, rgb, stride, status_out, ticket, dst_device != 0, scale, fmt);
 }
 
 // a group of the batch decoder (jb_batch.cpp): jb_submit_batch, or (dst_device = 1) with the pixels left in DEVICE
 // memory of the context's device; at 1/scale (tight rows of 3 * ceil(width / scale) bytes)
 int jb_submit_group_(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef, const uint16_t *qtabs,
-                     uint8_t *rgb, int *ticket, int dst_device, int scale) {
+                     uint8_t *rgb, int *ticket, int dst_device, int scale, const jb_output_spec *fmt) {
   const int64_t out_w = (desc->width + scale - 1) / (scale > 0 ? scale : 1);
-  return submit_impl(ctx, desc, n_images, coef, qtabs, rgb, 3LL * out_w, ticket, dst_device != 0, scale);
+  const int64_t stride = fmt_planar(fmt) ? out_w * fmt_esize(fmt) : 3LL * out_w;
+  return submit_impl(ctx, desc, n_images, coef, qtabs, rgb, stride, ticket, dst_device != 0, scale, fmt);
 }
 
 int jb_submit(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs,
@@ -1153,13 +1201,21 @@ int jb_blocks_to_rgb(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef
   return jb_wait(ctx, ticket);
 }
 
+int jb_blocks_to_rgb_fmt_(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs,
+                          uint8_t *rgb, int64_t rgb_stride, int scale, const jb_output_spec *fmt);
 // jb_blocks_to_rgb at 1/scale (jb_decode_memory_scaled's host-entropy path): rgb holds the reduced image
 int jb_blocks_to_rgb_scaled_(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs,
                              uint8_t *rgb, int64_t rgb_stride, int scale) {
+  return jb_blocks_to_rgb_fmt_(ctx, desc, coef, qtabs, rgb, rgb_stride, scale, nullptr);
+}
+
+// the same in an output format (jb_decode_memory_fmt's host-entropy path; null: interleaved)
+int jb_blocks_to_rgb_fmt_(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs,
+                          uint8_t *rgb, int64_t rgb_stride, int scale, const jb_output_spec *fmt) {
   if (!ctx) return fail(nullptr, JB_ERR_NULL, "jb_blocks_to_rgb: ctx is NULL");
   if (!desc || !coef || !qtabs || !rgb) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb: NULL pointer");
   int ticket = -1;
-  int rc = submit_impl(ctx, desc, 1, coef, qtabs, rgb, rgb_stride, &ticket, false, scale);
+  int rc = submit_impl(ctx, desc, 1, coef, qtabs, rgb, rgb_stride, &ticket, false, scale, fmt);
   if (rc) return rc;
   return jb_wait(ctx, ticket);
 }

@@ -39,10 +39,13 @@ int jb_fail_(jb_ctx *ctx, int code, const char *msg);
 // (dst_device: `rgb` is device memory of the context's device, nothing is downloaded)
 // (scale: the pixels are the area-reduced images of jb_batch_decoder_set_scale, tight rows)
 extern "C" int jb_submit_packed_(jb_ctx *ctx, const jb_image_desc *desc, const uint16_t *qtabs, const uint8_t *packed,
-                                 const JbHuffLayout *lay, uint8_t *rgb, uint32_t *status_out, int *ticket, int dst_device, int scale);
+                                 const JbHuffLayout *lay, uint8_t *rgb, uint32_t *status_out, int *ticket, int dst_device, int scale,
+                                 const jb_output_spec *fmt);
 // jb_submit_batch (dst_device = 0) or its device-output form (1) at 1/scale
 extern "C" int jb_submit_group_(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef, const uint16_t *qtabs,
-                                uint8_t *rgb, int *ticket, int dst_device, int scale);
+                                uint8_t *rgb, int *ticket, int dst_device, int scale, const jb_output_spec *fmt);
+// (fmt: null, or the planar output format of jb_batch_decoder_set_output_format -- tight rows and planes)
+extern "C" int jb_format_esize_(int format);  // jb_geometry.cpp: bytes per element of a JB_FMT_*
 // jb_wait in two halves, so that many threads can wait on one shared context (jb_api.cpp):
 // under the caller's lock, the event to block on (nullptr: the submission has completed) ...
 void *jb_wait_begin_(jb_ctx *ctx, int ticket);
@@ -283,6 +286,7 @@ struct Run {
   std::vector<std::vector<int>> *deferred = nullptr;
   size_t slot_coef = 0, slot_rgb = 0;  // what a ring slot holds (one image may be larger than a group's bound, not than this)
   int scale = 1;                       // output at 1/scale (jb_batch_decoder_set_scale)
+  const jb_output_spec *fmt = nullptr; // a planar output format (jb_batch_decoder_set_output_format); null: interleaved uint8
 };
 
 // pass 1 (per host thread): parse the headers of its files, so that the buffers can be sized once for
@@ -300,12 +304,12 @@ struct Run {
 constexpr size_t kHeadBytes[2] = {(size_t)4 << 10, (size_t)64 << 10};
 
 // every size of the pixels that this file takes downstream -- staging, arena, ring slots, copies -- is the output's:
-// geo.rgb_bytes is set to the reduced image's bytes at scale > 1
-void parse_one(Parsed &p, int scale) {
+// geo.rgb_bytes is set to the reduced image's bytes at scale > 1, to the format's bytes (jb_output_bytes) with a planar format
+void parse_one(Parsed &p, int scale, const jb_output_spec *fmt) {
   p.status = jb_entropy_decode(p.bytes.data(), p.bytes.size(), &p.desc, p.qtabs, nullptr, 0);
   if (p.status == JB_OK) p.status = jb_geometry_of(&p.desc, &p.geo);
   if (p.status == JB_OK) p.status = jb_scaled_size(p.desc.width, p.desc.height, scale, &p.out_w, &p.out_h);
-  if (p.status == JB_OK) p.geo.rgb_bytes = 3LL * p.out_w * p.out_h;
+  if (p.status == JB_OK) p.geo.rgb_bytes = 3LL * p.out_w * p.out_h * (fmt ? jb_format_esize_(fmt->format) : 1);
   if (p.status != JB_OK) p.error = jb_last_error(nullptr);
 }
 
@@ -322,7 +326,7 @@ void parse_pass(const Run &r, int t, std::vector<Parsed> &parsed, size_t *max_co
       ok = level < 2 ? read_prefix(r.paths[i], kHeadBytes[level], p.bytes, &p.loaded) : read_file(r.paths[i], p.bytes);
       *t_read += now_s() - a;
       if (level == 2) p.loaded = ok;
-      if (ok) parse_one(p, r.scale);
+      if (ok) parse_one(p, r.scale, r.fmt);
     }
     if (!ok) {
       p.status = JB_ERR_FORMAT;
@@ -381,7 +385,7 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
       p.have = true;
       p.loaded = ok;
       if (ok) {
-        parse_one(p, r.scale);
+        parse_one(p, r.scale, r.fmt);
       } else {
         p.status = JB_ERR_FORMAT;
         p.error = "cannot read file";
@@ -453,7 +457,7 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
           void *ev2 = nullptr;
           {
             std::lock_guard<std::mutex> lk(r.dev->mu);
-            st_j = jb_submit_group_(r.dev->ctx, &p.desc, 1, cbuf, p.qtabs, staged, &ticket, to_device, r.scale);
+            st_j = jb_submit_group_(r.dev->ctx, &p.desc, 1, cbuf, p.qtabs, staged, &ticket, to_device, r.scale, r.fmt);
             if (st_j == JB_OK) ev2 = jb_wait_begin_(r.dev->ctx, ticket);
             else text_j = jb_last_error(r.dev->ctx);
           }
@@ -584,6 +588,11 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
     if (!dst) {
       st = JB_ERR_CAPACITY;
       text = "output arena exhausted";
+    } else if (r.fmt && ((uintptr_t)dst & (uintptr_t)(jb_format_esize_(r.fmt->format) - 1))) {
+      // (groups start on 256-byte steps of the arena / region and an image is a whole number of elements, so every image
+      // is element-aligned unless the region itself is not: checked, not assumed -- the kernel's f32 / f16 stores need it)
+      st = JB_ERR_GEOMETRY;
+      text = "output region is not aligned to the format's element size";
     }
     qtabs.resize((size_t)n * 256);
     for (int j = 0; j < n; j++) {
@@ -622,9 +631,9 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
       std::lock_guard<std::mutex> lk(r.dev->mu);
       if (on_device) {
         st = jb_submit_packed_(r.dev->ctx, &head.desc, qtabs.data(), lane->blob[s], &lay, dst, lane->status[s], &grp[s].ticket, to_device,
-                               r.scale);
+                               r.scale, r.fmt);
       } else {
-        st = jb_submit_group_(r.dev->ctx, &head.desc, n, lane->coef[s], qtabs.data(), dst, &grp[s].ticket, to_device, r.scale);
+        st = jb_submit_group_(r.dev->ctx, &head.desc, n, lane->coef[s], qtabs.data(), dst, &grp[s].ticket, to_device, r.scale, r.fmt);
       }
       if (st != JB_OK) text = jb_last_error(r.dev->ctx);
       t_wait += now_s() - a;
@@ -681,6 +690,9 @@ struct jb_batch_decoder {
   int made_threads = 0;
   size_t made_coef = 0, made_rgb = 0;
   int scale = 1;  // output at 1/scale (jb_batch_decoder_set_scale): on this decoder, its parts and its twin alike
+  // output format (jb_batch_decoder_set_output_format), likewise; has_fmt: it is one of the planar ones
+  jb_output_spec fmt = {};
+  bool has_fmt = false;
   // jb_batch_decoder_submit / _collect: up to two batches in flight, batch k on side k & 1 -- side 0 is this
   // decoder, side 1 its twin (same devices, threads and sizes, its own ring, staging and arena) -- so that the
   // start-up of one batch (headers, first groups) runs under the tail of the other (last kernels, last downloads)
@@ -836,6 +848,7 @@ int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8
     r.lazy = lazy;
     r.deferred = &deferred;
     r.scale = d->scale;
+    r.fmt = d->has_fmt ? &d->fmt : nullptr;
     const double tr0 = now_s();
     std::vector<std::vector<Parsed>> parsed((size_t)nt);
     for (int t = 0; t < nt; t++) parsed[(size_t)t].resize(lists[(size_t)t].size());
@@ -1104,6 +1117,15 @@ void set_scale_all(jb_batch_decoder *d, int scale) {
   set_scale_all(d->twin, scale);
 }
 
+// ... and in one output format
+void set_format_all(jb_batch_decoder *d, const jb_output_spec &spec) {
+  if (!d) return;
+  d->fmt = spec;
+  d->has_fmt = spec.format != JB_FMT_RGB_U8_HWC;
+  for (jb_batch_decoder *p : d->parts) set_format_all(p, spec);
+  set_format_all(d->twin, spec);
+}
+
 // the single-device decoders a decoder consists of
 std::vector<jb_batch_decoder *> singles_of(jb_batch_decoder *d) {
   if (d->parts.empty()) return std::vector<jb_batch_decoder *>(1, d);
@@ -1248,6 +1270,7 @@ extern "C" int jb_batch_decoder_submit(jb_batch_decoder *d, const char *const *p
     d->twin = t;
     d->split_for_sides = false;
     set_scale_all(t, d->scale);
+    set_format_all(t, d->fmt);
   }
   if (!d->split_for_sides) {  // (only ever the case with nothing in flight: every call that clears it refuses otherwise)
     int rc = arrange_outputs(d, true);
@@ -1293,7 +1316,20 @@ extern "C" int jb_batch_decoder_set_scale(jb_batch_decoder *d, int denom) {
   if (denom != 1 && denom != 2 && denom != 4 && denom != 8)
     return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_set_scale: denom is not 1, 2, 4 or 8");
   if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_scale: batches are in flight (collect them first)");
+  if (denom != 1 && d->has_fmt) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_scale: a planar output format is set: it cannot be combined with a scale");
   set_scale_all(d, denom);
+  return JB_OK;
+}
+
+extern "C" int jb_batch_decoder_set_output_format(jb_batch_decoder *d, const jb_output_spec *spec) {
+  if (!d) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_set_output_format: decoder is NULL");
+  if (!spec) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_set_output_format: spec is NULL");
+  if (jb_output_spec_check(spec, 1, 1 << 20) != JB_OK || (spec->format != JB_FMT_RGB_U8_HWC && spec->plane_stride != 0))
+    return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_set_output_format: bad output spec (unknown format, reserved or plane_stride not 0, scale / bias not finite)");
+  if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_output_format: batches are in flight (collect them first)");
+  if (spec->format != JB_FMT_RGB_U8_HWC && d->scale != 1)
+    return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_output_format: the decoder's scale is not 1: a planar output format cannot be combined with it");
+  set_format_all(d, *spec);
   return JB_OK;
 }
 

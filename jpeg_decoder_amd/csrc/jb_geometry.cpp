@@ -38,6 +38,36 @@ int jb_scaled_size(int32_t width, int32_t height, int denom, int32_t *out_w, int
   return JB_OK;
 }
 
+// bytes per element of an output format (0: not a format); internal, shared by jb_api.cpp / jb_frontend.cpp / jb_batch.cpp
+int jb_format_esize_(int format) {
+  return format == JB_FMT_RGB_U8_HWC || format == JB_FMT_RGB_U8_CHW ? 1 : format == JB_FMT_RGB_F32_CHW ? 4 : format == JB_FMT_RGB_F16_CHW ? 2 : 0;
+}
+
+int jb_output_bytes(int32_t width, int32_t height, int format, int64_t *bytes) {
+  if (!bytes) return JB_ERR_NULL;
+  const int es = jb_format_esize_(format);
+  if (es == 0 || width < 1 || height < 1 || width > 65535 || height > 65535) return JB_ERR_GEOMETRY;
+  *bytes = 3LL * width * height * es;  // at most 3 * 65535^2 * 4 < 2^36
+  return JB_OK;
+}
+
+int jb_output_spec_check(const jb_output_spec *s, int32_t height, int64_t row_stride) {
+  if (!s) return JB_ERR_NULL;
+  if (jb_format_esize_(s->format) == 0 || s->reserved != 0) return JB_ERR_GEOMETRY;
+  if (s->format == JB_FMT_RGB_U8_HWC) return JB_OK;  // (the other fields are not looked at)
+  if (height < 1 || height > 65535 || row_stride < 1) return JB_ERR_GEOMETRY;
+  if (s->plane_stride != 0 && s->plane_stride < row_stride * (int64_t)height) return JB_ERR_GEOMETRY;
+  if (s->format != JB_FMT_RGB_U8_CHW)
+    for (int c = 0; c < 3; c++) {
+      // finite: the exponent field is not all ones (tested on the bits)
+      uint32_t a, b;
+      memcpy(&a, &s->scale[c], 4);
+      memcpy(&b, &s->bias[c], 4);
+      if ((a & 0x7f800000u) == 0x7f800000u || (b & 0x7f800000u) == 0x7f800000u) return JB_ERR_GEOMETRY;
+    }
+  return JB_OK;
+}
+
 int jb_resolve_qtabs(const jb_image_desc *d, const uint16_t *qtabs, int32_t *out192) {
   if (!d || !qtabs || !out192) return JB_ERR_NULL;
   for (int c = 0; c < 3; c++) {

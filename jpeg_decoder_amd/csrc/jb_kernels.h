@@ -24,6 +24,11 @@ struct JbLaunch {
   int32_t reserved;           // 0 (777 = skip switch of the timing-experiment builds)
   int32_t staged;             // 1 (linear tiling only): the line-aligned store stage for rows that are not 64-byte aligned
   int32_t small_grid;         // 1: 4:4:4 and 4:2:0 only, one 64-lane workgroup per jbk_small_mcus() MCUs of an MCU row (row-bound)
+  // jbk_launch_fmt only (planar output; every other launch leaves these 0): rgb_row_stride is then the bytes between
+  // the rows of ONE plane, rgb_plane_stride the bytes between the R, G and B planes of an image
+  int32_t format;             // JB_FMT_* of include/jpegblk.h
+  int64_t rgb_plane_stride;   // bytes
+  float scale[3], bias[3];    // float formats: value = (float)u8 * scale[c] + bias[c]
 };
 
 // MCUs covered by one workgroup (a tile is always 192 coded blocks): 64 / 48 / 32.
@@ -38,6 +43,10 @@ const char *jbk_kernel_name(int hs, int vs);
 // The same kernel with an area-reduced store stage (scale 2, 4 or 8; row-bound tiling: p.linear = p.small_grid = 0):
 // p.width / p.height are the full image's, p.rgb and its strides describe the ceil(W/scale) x ceil(H/scale) output.
 hipError_t jbk_launch_scaled(const JbLaunch &p, int hs, int vs, int scale, hipStream_t stream);
+// The same kernel with a planar store stage (p.format = JB_FMT_RGB_U8_CHW / _F32_CHW / _F16_CHW; row-bound tiling:
+// p.linear = p.small_grid = 0): p.rgb, p.rgb_row_stride, p.rgb_plane_stride and p.rgb_image_stride describe three planes
+// of p.height rows of p.width elements per image; p.scale / p.bias the float formats' affine map.
+hipError_t jbk_launch_fmt(const JbLaunch &p, int hs, int vs, hipStream_t stream);
 
 // Device-side entropy decoder (jb_huff.hip); structures in jb_huff.h.
 struct JbHuffLaunch;

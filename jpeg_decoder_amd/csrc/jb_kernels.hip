@@ -280,13 +280,17 @@ struct LaneMap {
 // SCALE = 2, 4, 8 (row-bound tiling only): the area-reduced output of jbk_launch_scaled -- stages 1 and 2 and the
 // colour transform and u8 conversion of every pixel are those of SCALE = 1; only what is stored differs (see
 // "scaled" below).  p.width / p.height stay the full image's; p.rgb and its strides describe the reduced image.
-template <int HS, int VS, bool MIXQ, bool LINEAR, bool STAGED = false, int SCALE = 1>
+// FORMAT = 1, 2, 3 (JB_FMT_RGB_U8_CHW, _F32_CHW, _F16_CHW; row-bound tiling only, SCALE = 1): the planar output of
+// jbk_launch_fmt -- again only what is stored differs (see "planar" below): the u8 values are those of FORMAT = 0.
+template <int HS, int VS, bool MIXQ, bool LINEAR, bool STAGED = false, int SCALE = 1, int FORMAT = 0>
 // (5 waves/SIMD are asked for where that costs no spill: 4:4:4 and 4:4:0; forcing it on 4:2:0 or
 // 4:2:2 spills and measured 9 % slower; the scaled 4:4:0 instantiations spill at 5 too)
 __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS == 1)) ? 5 : 1) void jb_tile_kernel(const JbLaunch p) {
   static_assert(!STAGED || LINEAR, "the staged store stage is an instantiation of the linear tiling");
   static_assert(SCALE == 1 || (!LINEAR && !STAGED && (SCALE == 2 || SCALE == 4 || SCALE == 8)),
                 "the scaled store stage is an instantiation of the row-bound tiling");
+  static_assert(FORMAT == 0 || (!LINEAR && !STAGED && SCALE == 1 && FORMAT >= 1 && FORMAT <= 3),
+                "the planar store stage is an instantiation of the full-size row-bound tiling");
   using LM = LaneMap<HS, VS>;
   constexpr int kTileBlocks = LM::TB;
   constexpr int kStripBytes = kTileBlocks * 128;  // half of the tile's f32 samples: 24 or 32 KiB
@@ -685,6 +689,96 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
             const int voff = (x / SCALE) * 3;
             __builtin_amdgcn_raw_buffer_store_b16((uint16_t)(o[0] | o[1] << 8), rsrc, voff, 0, JB_STORE_AUX);
             __builtin_amdgcn_raw_buffer_store_b8((uint8_t)o[2], rsrc, voff + 2, 0, JB_STORE_AUX);
+          }
+        }
+      }
+    } else if constexpr (FORMAT > 0) {
+      // ---- planar: three planes R, G, B of u8 / f32 / f16, one lane = 4 adjacent pixels of one row ----
+      // The wave-iterations are those of the full-size row-bound stage below: one strip row of one 256-pixel segment,
+      // the same LDS reads and colour transform.  pack12_rtz with its operands permuted (as the scaled stage calls it)
+      // gives ONE word per channel -- the four u8 samples of R, of G, of B, truncated and clamped exactly as FORMAT = 0
+      // stores them -- so a lane stores 4 bytes per plane, or widens them: v_cvt_f32_ubyte0..3 (exact), one f32
+      // multiply, one f32 add (separate instructions: this file is built with -ffp-contract=off), for f16 one
+      // v_cvt_f16_f32.  All of these consume pack12_rtz's outputs, so they issue after it has switched the wave's
+      // rounding mode back to nearest-even.  A wave-instruction writes 256 / 1024 / 512 contiguous bytes of one plane
+      // row; the descriptor's range check drops the lanes past the right edge, and the one lane whose group straddles
+      // it (width % 4 != 0) stores its 1-3 elements with one or two narrower stores.
+      constexpr int IPR = TASKS_PER_ROW / 64;
+      constexpr int SEG_MCUS = 256 / (8 * HS);
+      constexpr int ES = FORMAT == 1 ? 1 : FORMAT == 2 ? 4 : 2;  // bytes per element
+      for (int it = wave; it < TASKS / 64; it += kTileBlocks / 64) {
+        const int row = it / IPR, seg = it - row * IPR;
+        const int y = my * 8 * VS + phase * 4 + (row >> 2) * 8 + (row & 3);  // image row of the strip row
+        const int xseg = (mx0 + seg * SEG_MCUS) * 8 * HS;                    // image column of the segment
+        if (y >= p.height || xseg >= p.width) continue;                      // (wave-uniform; covers MCUs past nvalid)
+        const float4 Y = *(const float4 *)(lds + lane_y_off + row * (YW * 4) + seg * 1024);
+        float cb[4], cr[4];
+        const int coff = (row / VS) * (CW * 4) + seg * (1024 / HS);
+        if (HS == 1) {
+          const float4 a = *(const float4 *)(lds + CB_OFF + lane_c_off + coff);
+          const float4 b = *(const float4 *)(lds + CR_OFF + lane_c_off + coff);
+          cb[0] = a.x, cb[1] = a.y, cb[2] = a.z, cb[3] = a.w;
+          cr[0] = b.x, cr[1] = b.y, cr[2] = b.z, cr[3] = b.w;
+        } else {
+          const float2 a = *(const float2 *)(lds + CB_OFF + lane_c_off + coff);
+          const float2 b = *(const float2 *)(lds + CR_OFF + lane_c_off + coff);
+          cb[0] = cb[1] = a.x, cb[2] = cb[3] = a.y;
+          cr[0] = cr[1] = b.x, cr[2] = cr[3] = b.y;
+        }
+        const float yy[4] = {Y.x, Y.y, Y.z, Y.w};
+        float r[4], g[4], b[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          r[i] = (yy[i] + JB_CR_R * cr[i]) + 128.0f;
+          g[i] = ((yy[i] - JB_CB_G * cb[i]) - JB_CR_G * cr[i]) + 128.0f;
+          b[i] = (yy[i] + JB_CB_B * cb[i]) + 128.0f;
+        }
+        // byte order of pack12_rtz: r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3 -> with these arguments w[c] = channel c, pixels 0..3
+        const float pr[4] = {r[0], r[3], g[2], b[1]}, pg[4] = {r[1], g[0], g[3], b[2]}, pb[4] = {r[2], g[1], b[0], b[3]};
+        uint32_t w[3];
+        pack12_rtz(pr, pg, pb, w[0], w[1], w[2]);
+        const int npx = min(256, p.width - xseg);    // pixels of the segment inside the image (wave-uniform)
+        const int whole = npx >> 2, part = npx & 3;  // whole 4-pixel groups; pixels of the group that straddles the edge
+        uint8_t *const segp = img_rgb + (int64_t)y * p.rgb_row_stride + (int64_t)xseg * ES;
+        const int voff = lane_late * (4 * ES);
+        const bool edge = part != 0 && lane_late == whole;
+        const int voff2 = voff + (part == 3 ? 2 * ES : 0);  // where the edge group's odd element goes
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          uint8_t *const planep = segp + (int64_t)c * p.rgb_plane_stride;
+          const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(planep, 0, whole * (4 * ES), 0x00020000);
+          const __amdgpu_buffer_rsrc_t tail = __builtin_amdgcn_make_buffer_rsrc(planep, 0, 0x7ffffff0, 0x00020000);
+          if constexpr (FORMAT == 1) {
+            __builtin_amdgcn_raw_buffer_store_b32(w[c], rsrc, voff, 0, JB_STORE_AUX);
+            if (edge) {
+              if (part >= 2) __builtin_amdgcn_raw_buffer_store_b16((uint16_t)w[c], tail, voff, 0, JB_STORE_AUX);
+              if (part != 2) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(part == 3 ? w[c] >> 16 : w[c]), tail, voff2, 0, JB_STORE_AUX);
+            }
+          } else {
+            const float sc = p.scale[c], bi = p.bias[c];
+            float f[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) f[i] = (float)((w[c] >> (8 * i)) & 0xffu) * sc + bi;
+            if constexpr (FORMAT == 2) {
+              const uint32_t u[4] = {__builtin_bit_cast(uint32_t, f[0]), __builtin_bit_cast(uint32_t, f[1]),
+                                     __builtin_bit_cast(uint32_t, f[2]), __builtin_bit_cast(uint32_t, f[3])};
+              __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{u[0], u[1], u[2], u[3]}, rsrc, voff, 0, JB_STORE_AUX);
+              if (edge) {
+                if (part >= 2) __builtin_amdgcn_raw_buffer_store_b64(u32x2_t{u[0], u[1]}, tail, voff, 0, JB_STORE_AUX);
+                if (part != 2) __builtin_amdgcn_raw_buffer_store_b32(part == 3 ? u[2] : u[0], tail, voff2, 0, JB_STORE_AUX);
+              }
+            } else {
+              // (_Float16)x is v_cvt_f16_f32: round to nearest even (never the packed round-toward-zero conversion)
+              uint32_t h[4];
+#pragma unroll
+              for (int i = 0; i < 4; i++) h[i] = (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f[i]);
+              const uint32_t h01 = h[0] | h[1] << 16, h23 = h[2] | h[3] << 16;
+              __builtin_amdgcn_raw_buffer_store_b64(u32x2_t{h01, h23}, rsrc, voff, 0, JB_STORE_AUX);
+              if (edge) {
+                if (part >= 2) __builtin_amdgcn_raw_buffer_store_b32(h01, tail, voff, 0, JB_STORE_AUX);
+                if (part != 2) __builtin_amdgcn_raw_buffer_store_b16((uint16_t)(part == 3 ? h[2] : h[0]), tail, voff2, 0, JB_STORE_AUX);
+              }
+            }
           }
         }
       }
@@ -1264,6 +1358,36 @@ hipError_t jbk_launch_scaled(const JbLaunch &p, int hs, int vs, int scale, hipSt
   if (scale == 2) return launch_scaled_k<2>(p, hs, vs, stream);
   if (scale == 4) return launch_scaled_k<4>(p, hs, vs, stream);
   if (scale == 8) return launch_scaled_k<8>(p, hs, vs, stream);
+  return hipErrorInvalidValue;
+}
+
+// the planar output (jbk_launch_fmt): the row-bound instantiation with the planar store stage
+template <int HS, int VS, int FORMAT>
+static hipError_t launch_fmt_t(const JbLaunch &p, hipStream_t stream) {
+  using LM = LaneMap<HS, VS>;
+  const bool mixq = (LM::MCUS % 64 != 0) && !p.chroma_q_equal;  // as launch_t: 4:2:0 whose Cb and Cr tables differ
+  const dim3 grid(p.n_tiles), block(LM::TB);
+  (void)hipGetLastError();
+  if (mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, true, false, false, 1, FORMAT>), grid, block, 0, stream, p);
+  else hipLaunchKernelGGL((jb_tile_kernel<HS, VS, false, false, false, 1, FORMAT>), grid, block, 0, stream, p);
+  return hipGetLastError();
+}
+
+template <int FORMAT>
+static hipError_t launch_fmt_k(const JbLaunch &p, int hs, int vs, hipStream_t stream) {
+  if (hs == 1 && vs == 1) return launch_fmt_t<1, 1, FORMAT>(p, stream);
+  if (hs == 2 && vs == 1) return launch_fmt_t<2, 1, FORMAT>(p, stream);
+  if (hs == 1 && vs == 2) return launch_fmt_t<1, 2, FORMAT>(p, stream);
+  if (hs == 2 && vs == 2) return launch_fmt_t<2, 2, FORMAT>(p, stream);
+  return hipErrorInvalidValue;
+}
+
+hipError_t jbk_launch_fmt(const JbLaunch &p, int hs, int vs, hipStream_t stream) {
+  if (p.n_tiles <= 0) return hipSuccess;
+  if (p.linear || p.small_grid) return hipErrorInvalidValue;  // (row-bound tiling only)
+  if (p.format == 1) return launch_fmt_k<1>(p, hs, vs, stream);
+  if (p.format == 2) return launch_fmt_k<2>(p, hs, vs, stream);
+  if (p.format == 3) return launch_fmt_k<3>(p, hs, vs, stream);
   return hipErrorInvalidValue;
 }
 

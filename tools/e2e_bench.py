@@ -101,15 +101,41 @@ def pinned_array(nbytes, dtype):
     return p, a
 
 
-def device_output_run(jb, paths, want, threads, device, g0, args, w, h, world, scale=1):
-    """The batch with the decoded images left in device memory: no download at all."""
+def in_format(full, spec):
+    """What an image decodes to in an output format (jpegblk.h, "tensor-ready output"): [3, H, W], the float formats as
+    ONE float32 multiply and ONE float32 add per element, then (f16) one conversion -- compared bit for bit."""
+    planes = np.ascontiguousarray(full.transpose(2, 0, 1))
+    if spec.format == 1:
+        return planes
+    v = planes.astype(np.float32) * np.array(list(spec.scale), np.float32).reshape(3, 1, 1) + np.array(list(spec.bias), np.float32).reshape(3, 1, 1)
+    return v if spec.format == 2 else v.astype(np.float16)
+
+
+FORMATS = {"RGB_U8_HWC": 0, "RGB_U8_CHW": 1, "RGB_F32_CHW": 2, "RGB_F16_CHW": 3}
+FORMATS_BY_NUMBER = {v: k for k, v in FORMATS.items()}
+
+
+def device_output_run(jb, paths, want, threads, device, g0, args, w, h, world, scale=1, spec=None):
+    """The batch with the decoded images left in device memory: no download at all.  spec (--format, scale 1): the
+    images in that output format (ImageNet's scale / bias), the ring sized for it."""
     import torch
     n = len(paths)
     ow, oh = jb.scaled_size(w, h, scale)
     out_bytes = ow * oh * 3
+    if spec is not None and spec.format != 0:
+        assert scale == 1, "--format cannot be combined with --scale"
+        out_bytes = jb.output_bytes(w, h, spec.format)
+        want = {p: in_format(v, spec) for p, v in want.items()}
+        return _device_output_run(jb, paths, want, threads, device, g0, args, w, h, world, scale, out_bytes, spec)
+    return _device_output_run(jb, paths, want, threads, device, g0, args, w, h, world, scale, out_bytes, None)
+
+
+def _device_output_run(jb, paths, want, threads, device, g0, args, w, h, world, scale, out_bytes, spec):
+    import torch
+    n = len(paths)
     per = (out_bytes + 255) // 256 * 256
     region = torch.empty(n * per, dtype=torch.uint8, device=f"cuda:{device}")
-    with jb.BatchDecoder(threads, device, g0.coef_bytes, g0.rgb_bytes, scale=scale) as dec:
+    with jb.BatchDecoder(threads, device, g0.coef_bytes, max(g0.rgb_bytes, out_bytes), scale=scale, fmt=spec) as dec:
         dec.set_device_output(region.data_ptr(), region.numel())
         dec.run_to_device(paths[:threads])
         runs = []
@@ -119,12 +145,12 @@ def device_output_run(jb, paths, want, threads, device, g0, args, w, h, world, s
             if k == 0:   # every image, copied back after the clock has stopped
                 for i, p in enumerate(paths):
                     off = ptrs[i] - region.data_ptr()
-                    got = region[off:off + out_bytes].cpu().numpy().reshape(want[p].shape)
-                    assert np.array_equal(got, want[p]), f"device output: image {i} differs from the single-image decode"
+                    got = region[off:off + out_bytes].cpu().numpy().view(want[p].dtype).reshape(want[p].shape)
+                    assert np.array_equal(got.view(np.uint8), want[p].view(np.uint8)), f"device output: image {i} differs from the single-image decode"
             runs.append(tm)
         on_device = dec.device_entropy_images
     tm = min(runs, key=lambda x: x["wall_s"])
-    return {"output": "device memory (nothing downloaded)", "scale": scale, "threads": threads, "images_per_s": round(args.n / tm["wall_s"], 1),
+    return {"output": "device memory (nothing downloaded)", "scale": scale, "format": FORMATS_BY_NUMBER[spec.format if spec is not None else 0], "threads": threads, "images_per_s": round(args.n / tm["wall_s"], 1),
             "mpix_per_s": round(args.n * w * h / tm["wall_s"] / 1e6, 1), "entropy_cpu_s": round(tm["entropy_s"], 3),
             "submit_wait_s": round(tm["device_s"], 3), "wall_s": round(tm["wall_s"], 3), "walls": [round(x["wall_s"], 3) for x in runs],
             "n_gpus": world, "pixels_checked": n, "entropy_on_device": bool(on_device)}
@@ -195,6 +221,8 @@ def main():
     ap.add_argument("--no-pcie", action="store_true", help="skip part (2), so that the last device activity of the run is the last "
                     "timed batch (tools/timeline.py reads that burst out of a rocprofv3 trace)")
     ap.add_argument("--scale", default="1", help="output at 1/K for every K of this comma-separated list of 1, 2, 4, 8")
+    ap.add_argument("--format", default="RGB_U8_HWC", help="output format(s) of the device mode, comma separated: " + " | ".join(FORMATS) +
+                    " (the float formats with ImageNet's scale / bias; scale 1 only)")
     ap.add_argument("--stream", type=int, default=0, help="also stream the files as batches of this many through "
                     "jb_batch_decoder_submit / _collect (two in flight), next to the same batches through run() one after the other")
     args = ap.parse_args()
@@ -237,7 +265,9 @@ def main():
             ow, oh = jb.scaled_size(w, h, scale)
             arena = (n_mine * ((ow * oh * 3 + 255) // 256 * 256)) if mode == "arena" else 0
             if mode == "device":   # device-resident output: the pixels stay in HBM (jb_batch_decoder_set_device_output)
-                res.append(device_output_run(jb, paths, want, t, device, g0, args, w, h, world, scale))
+                for name in args.format.split(","):
+                    spec = jb.OutputSpec.imagenet(FORMATS[name]) if FORMATS[name] else None
+                    res.append(device_output_run(jb, paths, want, t, device, g0, args, w, h, world, scale, spec))
                 continue
             with jb.BatchDecoder(t, device, g0.coef_bytes, g0.rgb_bytes, arena_bytes=arena, scale=scale) as dec:
                 dec.run(paths[:t], keep_pixels=False)          # touch every lane once

@@ -49,6 +49,8 @@ void jb_free(void *p) { free(p); }
 int jb_blocks_to_rgb(jb_ctx *, const jb_image_desc *, const int16_t *, const uint16_t *, uint8_t *, int64_t) { return JB_OK; }
 int jb_decode_job_scaled_(jb_ctx *, const JbHuffJob *, uint8_t *, int64_t, int) { return JB_OK; }
 int jb_blocks_to_rgb_scaled_(jb_ctx *, const jb_image_desc *, const int16_t *, const uint16_t *, uint8_t *, int64_t, int) { return JB_OK; }
+int jb_decode_job_fmt_(jb_ctx *, const JbHuffJob *, uint8_t *, int64_t, int, const jb_output_spec *) { return JB_OK; }
+int jb_blocks_to_rgb_fmt_(jb_ctx *, const jb_image_desc *, const int16_t *, const uint16_t *, uint8_t *, int64_t, int, const jb_output_spec *) { return JB_OK; }
 }
 
 static uint64_t rng_state = 88172645463325252ull;
