@@ -32,8 +32,7 @@
 #include "jb_kernels.h"
 #include "jb_huff.h"
 #include "jb_knobs.h"
-
-extern "C" int jb_format_esize_(int format);  // jb_geometry.cpp: bytes per element of a JB_FMT_*, 0 = not a format
+#include "jb_plan.h"
 
 namespace {
 
@@ -375,6 +374,20 @@ void dl_release(jb_ctx *ctx) {
   delete eng;
 }
 
+// nothing of this context is in flight any more: the downloads handed to the engine, and every stream it has made
+hipError_t sync_all_streams(jb_ctx *ctx) {
+  hipError_t e = dl_wait_copies(ctx);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess && ctx->stream2) e = hipStreamSynchronize(ctx->stream2);
+  for (hipStream_t ps : ctx->pool)
+    if (e == hipSuccess && ps) e = hipStreamSynchronize(ps);
+  for (int k = 1; k < jb_ctx::kMaxPairs; k++) {
+    if (e == hipSuccess && ctx->pair_up[k]) e = hipStreamSynchronize(ctx->pair_up[k]);
+    if (e == hipSuccess && ctx->pair_down[k]) e = hipStreamSynchronize(ctx->pair_down[k]);
+  }
+  return e;
+}
+
 int check_desc(jb_ctx *ctx, const jb_image_desc *d, jb_geometry *g) {
   int rc = jb_geometry_of(d, g);
   if (rc == JB_ERR_NULL) return fail(ctx, rc, "null descriptor");
@@ -496,15 +509,7 @@ void *jb_ctx_stream(jb_ctx *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
 int jb_ctx_synchronize(jb_ctx *ctx) {
   if (!ctx) return fail(nullptr, JB_ERR_NULL, "jb_ctx_synchronize: ctx is NULL");
   DeviceGuard guard(ctx->device);
-  JB_HIP(ctx, dl_wait_copies(ctx));
-  JB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->stream2) JB_HIP(ctx, hipStreamSynchronize(ctx->stream2));
-  for (hipStream_t ps : ctx->pool)
-    if (ps) JB_HIP(ctx, hipStreamSynchronize(ps));
-  for (int k = 1; k < jb_ctx::kMaxPairs; k++) {
-    if (ctx->pair_up[k]) JB_HIP(ctx, hipStreamSynchronize(ctx->pair_up[k]));
-    if (ctx->pair_down[k]) JB_HIP(ctx, hipStreamSynchronize(ctx->pair_down[k]));
-  }
+  JB_HIP(ctx, sync_all_streams(ctx));
   return JB_OK;
 }
 
@@ -521,65 +526,50 @@ constexpr int kSmallGridBelowPerCu = 8;
 
 namespace {
 
-// The tile and launch setup of both seams: jb_blocks_to_rgb_device (scale 1: exactly the launch it has always
-// made) and jb_blocks_to_rgb_device_scaled (scale 2, 4, 8: the row-bound tiling with the area-reduced store stage).
-// The batch's row / image strides describe the output, i.e. the reduced image when scale > 1.
-// fmt (null or format 0: the interleaved output, exactly the launches above): a planar format of "tensor-ready output"
-// (jpegblk.h) -- the row-bound tiling with the planar store stage; the batch's row stride is then that of a plane.
-int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int scale, const char *fn, const jb_output_spec *fmt = nullptr) {
+// The pixel launch of every route -- the public device seams below and the staging ring's submissions -- in three
+// steps: argument validation, tile planning, the launch.  `plan` (jb_plan.h) says what the pixels look like: scale 1,
+// format 0 is exactly the launch jb_blocks_to_rgb_device has always made; scale 2, 4, 8 the row-bound tiling with the
+// area-reduced store stage; a planar format the row-bound tiling with the planar store stage.  The batch's row / image
+// strides describe the output: the reduced image when scale > 1, one plane's rows with a planar format.
+
+// 1. validation: the batch against the plan; g: the frame's geometry; plane_stride: bytes between the planes (0: interleaved)
+int seam_check(jb_ctx *ctx, const jb_device_batch *b, const JbOutPlan &plan, const char *fn, jb_geometry *g, int64_t *plane_stride) {
   if (!ctx) return fail(nullptr, JB_ERR_NULL, "%s: ctx is NULL", fn);
   if (!b || !b->d_coef || !b->d_qtabs || !b->d_rgb) return fail(ctx, JB_ERR_NULL, "%s: NULL pointer", fn);
-  jb_geometry g;
-  int rc = check_desc(ctx, &b->desc, &g);
+  int rc = check_desc(ctx, &b->desc, g);
   if (rc) return rc;
-  int32_t out_w = 0, out_h = 0;
-  if (jb_scaled_size(b->desc.width, b->desc.height, scale, &out_w, &out_h) != JB_OK)
-    return fail(ctx, JB_ERR_GEOMETRY, "%s: scale %d is not 1, 2, 4 or 8", fn, scale);
   if (b->n_images < 1) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d", b->n_images);
-  if (fmt && fmt->format == JB_FMT_RGB_U8_HWC) {
-    if (fmt->reserved != 0) return fail(ctx, JB_ERR_GEOMETRY, "%s: output spec: reserved must be 0", fn);
-    fmt = nullptr;
-  }
-  int64_t plane_stride = 0;
-  if (fmt) {
-    if (jb_format_esize_(fmt->format) == 0) return fail(ctx, JB_ERR_GEOMETRY, "%s: unknown output format %d", fn, fmt->format);
-    if (scale != 1) return fail(ctx, JB_ERR_UNSUPPORTED, "%s: a planar output format cannot be combined with scale %d", fn, scale);
-    if (jb_output_spec_check(fmt, b->desc.height, b->rgb_row_stride) != JB_OK)
+  if (plan.status != JB_OK) return fail(ctx, plan.status, "%s: %s", fn, plan.why);
+  *plane_stride = 0;
+  if (plan.planar) {
+    if (jb_output_spec_check(&plan.spec, b->desc.height, b->rgb_row_stride) != JB_OK)
       return fail(ctx, JB_ERR_GEOMETRY, "%s: bad output spec (reserved, plane_stride < row stride * height, or scale / bias not finite)", fn);
-    const int64_t es = jb_format_esize_(fmt->format);
-    plane_stride = fmt->plane_stride ? fmt->plane_stride : b->rgb_row_stride * (int64_t)b->desc.height;
-    if (b->rgb_row_stride < es * b->desc.width)
-      return fail(ctx, JB_ERR_GEOMETRY, "rgb_row_stride %lld < width * element size", (long long)b->rgb_row_stride);
-    if (((uintptr_t)b->d_rgb | (uint64_t)b->rgb_row_stride | (uint64_t)plane_stride | (uint64_t)(b->n_images > 1 ? b->rgb_image_stride : 0)) & (uint64_t)(es - 1))
+    *plane_stride = plan.spec.plane_stride ? plan.spec.plane_stride : b->rgb_row_stride * (int64_t)b->desc.height;
+  }
+  if (b->rgb_row_stride < plan.row_stride)
+    return fail(ctx, JB_ERR_GEOMETRY, "rgb_row_stride %lld < %s", (long long)b->rgb_row_stride, plan.planar ? "width * element size" : "3*width");
+  if (plan.planar) {
+    if (((uintptr_t)b->d_rgb | (uint64_t)b->rgb_row_stride | (uint64_t)*plane_stride | (uint64_t)(b->n_images > 1 ? b->rgb_image_stride : 0)) & (uint64_t)(plan.esize - 1))
       return fail(ctx, JB_ERR_GEOMETRY, "%s: f32 / f16 output wants the pointer and every stride to be multiples of the element size", fn);
-    if (b->n_images > 1 && b->rgb_image_stride < 2 * plane_stride + b->rgb_row_stride * (int64_t)b->desc.height)
+    if (b->n_images > 1 && b->rgb_image_stride < 2 * *plane_stride + b->rgb_row_stride * (int64_t)b->desc.height)
       return fail(ctx, JB_ERR_GEOMETRY, "image strides smaller than one image");
-  } else
-  if (b->rgb_row_stride < 3LL * out_w)
-    return fail(ctx, JB_ERR_GEOMETRY, "rgb_row_stride %lld < 3*width", (long long)b->rgb_row_stride);
+  }
   if (((uintptr_t)b->d_coef & 15) || (b->coef_image_stride & 15))
     return fail(ctx, JB_ERR_GEOMETRY, "coefficient pointer and image stride must be multiples of 16 bytes");
   if (((uintptr_t)b->d_qtabs & 3) || (b->qtab_image_stride & 3))
     return fail(ctx, JB_ERR_GEOMETRY, "quant-table pointer and stride must be multiples of 4 bytes");
-  if (b->n_images > 1 && (b->coef_image_stride < g.coef_bytes || b->rgb_image_stride < b->rgb_row_stride * (int64_t)out_h))
+  if (b->n_images > 1 && (b->coef_image_stride < g->coef_bytes || b->rgb_image_stride < b->rgb_row_stride * (int64_t)plan.out_h))
     return fail(ctx, JB_ERR_GEOMETRY, "image strides smaller than one image");
+  return JB_OK;
+}
+
+// 2. tile planning: linear, row-bound or small-grid, and the store-stage knobs, into p (its pointers, strides and
+// frame fields are set)
+int seam_tiles(jb_ctx *ctx, const jb_device_batch *b, const jb_geometry &g, const JbOutPlan &plan, JbLaunch &p) {
   const int per_tile = jbk_mcus_per_tile(b->desc.hs, b->desc.vs);
-  JbLaunch p;
-  memset(&p, 0, sizeof p);
-  p.coef = b->d_coef;
-  p.qtabs = b->d_qtabs;
-  p.rgb = b->d_rgb;
-  p.coef_image_stride = b->coef_image_stride;
-  p.qtab_image_stride = b->qtab_image_stride;
-  p.rgb_image_stride = b->rgb_image_stride;
-  p.rgb_row_stride = b->rgb_row_stride;
-  p.width = b->desc.width;
-  p.height = b->desc.height;
-  p.mcus_x = g.mcus_x;
-  p.mcus_y = g.mcus_y;
   p.tiles_per_row = (g.mcus_x + per_tile - 1) / per_tile;
-  // JPEGBLK_ROW_TILING=1 (debug / A-B knob) forces the row-bound tiling; the scaled stage only exists in it
-  const bool force_row = ctx->knobs.row_tiling || scale > 1 || fmt;
+  // JPEGBLK_ROW_TILING=1 (debug / A-B knob) forces the row-bound tiling; the scaled and planar stages only exist in it
+  const bool force_row = ctx->knobs.row_tiling || plan.scale > 1 || plan.planar;
   // linear tiling only where the row-bound one would leave ragged tiles
   p.linear = (force_row || g.mcus_x % per_tile == 0) ? 0 : jbk_linear_ok(b->desc.hs, b->desc.vs, g.mcus_x);
   const int64_t tiles_per_image = p.linear ? ((int64_t)g.mcus_x * g.mcus_y + per_tile - 1) / per_tile
@@ -591,8 +581,8 @@ int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int scale, 
   p.n_tiles = (int32_t)n_tiles;
   // Small launches (a single 1080p image is 507 / 255 workgroups on 256 CUs): four times as many one-wave
   // workgroups (jb_kernels.hip jb_small_kernel_*), row-bound.  JPEGBLK_SMALL_GRID = 1 / 0 forces / forbids it; so does
-  // JPEGBLK_ROW_TILING=1 (that knob asks for the 192-lane kernel's row-bound instantiation).  (The scaled stage has no
-  // small-grid variant.)
+  // JPEGBLK_ROW_TILING=1 (that knob asks for the 192-lane kernel's row-bound instantiation).  (The scaled and planar
+  // stages have no small-grid variant.)
   if (jbk_small_mcus(b->desc.hs, b->desc.vs) > 0 && !force_row && b->rgb_row_stride < (1LL << 26) &&  // (the lane's row offset is 32-bit)
       (ctx->knobs.small_grid == 1 || (ctx->knobs.small_grid < 0 && n_tiles <= (int64_t)kSmallGridBelowPerCu * ctx->n_cus))) {
     const int per = jbk_small_mcus(b->desc.hs, b->desc.vs);
@@ -615,16 +605,38 @@ int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int scale, 
   // (measurement builds of jb_kernels.hip only -- tools/build_variant.sh -DJB_LAB: the staged store stage of the linear
   // tiling; the product's kernels ignore the field)
   p.staged = (p.linear && p.fast_store && !p.small_grid && ctx->knobs.staged_store == 1) ? 1 : 0;
+  return JB_OK;
+}
+
+// 3. the launch, on `stream` or (null) the context's primary stream; fn: the entry point's name, for the error text
+int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn) {
+  jb_geometry g;
+  int64_t plane_stride = 0;
+  int rc = seam_check(ctx, b, plan, fn, &g, &plane_stride);
+  if (rc) return rc;
+  JbLaunch p;
+  memset(&p, 0, sizeof p);
+  p.coef = b->d_coef;
+  p.qtabs = b->d_qtabs;
+  p.rgb = b->d_rgb;
+  p.coef_image_stride = b->coef_image_stride;
+  p.qtab_image_stride = b->qtab_image_stride;
+  p.rgb_image_stride = b->rgb_image_stride;
+  p.rgb_row_stride = b->rgb_row_stride;
+  p.width = b->desc.width;
+  p.height = b->desc.height;
+  p.mcus_x = g.mcus_x;
+  p.mcus_y = g.mcus_y;
   p.chroma_q_equal = (b->desc.qtab_id[1] == b->desc.qtab_id[2]) ? 1 : 0;
-  DeviceGuard guard(ctx->device);
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  if (fmt) {
-    p.format = fmt->format;
+  if (plan.planar) {
+    p.format = plan.format;
     p.rgb_plane_stride = plane_stride;
-    for (int c = 0; c < 3; c++) p.scale[c] = fmt->scale[c], p.bias[c] = fmt->bias[c];
-    JB_HIP(ctx, jbk_launch_fmt(p, b->desc.hs, b->desc.vs, s));
-  } else if (scale == 1) JB_HIP(ctx, jbk_launch(p, b->desc.hs, b->desc.vs, s));
-  else JB_HIP(ctx, jbk_launch_scaled(p, b->desc.hs, b->desc.vs, scale, s));
+    for (int c = 0; c < 3; c++) p.scale[c] = plan.spec.scale[c], p.bias[c] = plan.spec.bias[c];
+  }
+  rc = seam_tiles(ctx, b, g, plan, p);
+  if (rc) return rc;
+  DeviceGuard guard(ctx->device);
+  JB_HIP(ctx, jbk_launch(p, b->desc.hs, b->desc.vs, plan.scale, stream ? (hipStream_t)stream : ctx->stream));
   return JB_OK;
 }
 
@@ -633,16 +645,16 @@ int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int scale, 
 extern "C" {
 
 int jb_blocks_to_rgb_device(jb_ctx *ctx, const jb_device_batch *b, void *stream) {
-  return seam_launch(ctx, b, stream, 1, "jb_blocks_to_rgb_device");
+  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, nullptr), "jb_blocks_to_rgb_device");
 }
 
 int jb_blocks_to_rgb_device_scaled(jb_ctx *ctx, const jb_device_batch *b, int denom, void *stream) {
-  return seam_launch(ctx, b, stream, denom, "jb_blocks_to_rgb_device_scaled");
+  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, denom, nullptr), "jb_blocks_to_rgb_device_scaled");
 }
 
 int jb_blocks_to_rgb_device_fmt(jb_ctx *ctx, const jb_device_batch *b, const jb_output_spec *spec, void *stream) {
   if (ctx && !spec) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_fmt: spec is NULL");
-  return seam_launch(ctx, b, stream, 1, "jb_blocks_to_rgb_device_fmt", spec);
+  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec), "jb_blocks_to_rgb_device_fmt");
 }
 
 int jb_ctx_device(const jb_ctx *ctx) { return ctx ? ctx->device : -1; }
@@ -662,15 +674,7 @@ int jb_ctx_reserve(jb_ctx *ctx, size_t max_coef_bytes, size_t max_rgb_bytes) {
   if (ctx->n_slots > 0 && max_coef_bytes <= ctx->max_coef && max_rgb_bytes <= ctx->max_rgb) return JB_OK;
   DeviceGuard guard(ctx->device);
   // nothing may be in flight while the slots' buffers are replaced
-  JB_HIP(ctx, dl_wait_copies(ctx));
-  JB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->stream2) JB_HIP(ctx, hipStreamSynchronize(ctx->stream2));
-  for (hipStream_t ps : ctx->pool)
-    if (ps) JB_HIP(ctx, hipStreamSynchronize(ps));
-  for (int k = 1; k < jb_ctx::kMaxPairs; k++) {
-    if (ctx->pair_up[k]) JB_HIP(ctx, hipStreamSynchronize(ctx->pair_up[k]));
-    if (ctx->pair_down[k]) JB_HIP(ctx, hipStreamSynchronize(ctx->pair_down[k]));
-  }
+  JB_HIP(ctx, sync_all_streams(ctx));
   if (max_coef_bytes < ctx->max_coef) max_coef_bytes = ctx->max_coef;
   if (max_rgb_bytes < ctx->max_rgb) max_rgb_bytes = ctx->max_rgb;
   const int n = ctx->n_slots > 0 ? ctx->n_slots : ctx->n_slots_req;
@@ -755,42 +759,91 @@ void jb_pinned_free(void *p) {
 
 namespace {
 
-// element size of a submission's output format (null = interleaved uint8), and whether it is one of the planar ones
-inline int fmt_esize(const jb_output_spec *fmt) { return fmt ? (jb_format_esize_(fmt->format) > 0 ? jb_format_esize_(fmt->format) : 1) : 1; }
-inline bool fmt_planar(const jb_output_spec *fmt) { return fmt && fmt->format != JB_FMT_RGB_U8_HWC; }
-
 constexpr int kMaxBatch = 256;  // images per submission (the slot's table block holds that many)
+
+// What submit_impl and submit_jobs_impl have in common.  They differ on purpose in their streams, in how the download
+// is issued and in the status words (see each); everything around that is here.
+struct Submission {
+  DeviceGuard guard;
+  jb_geometry g;
+  size_t coef_total = 0, rgb_total = 0;
+  Slot *slot = nullptr;
+  explicit Submission(jb_ctx *ctx) : guard(ctx->device) {}
+};
+
+// Prologue, first half: validation, capacity, and the ring slot (a full ring blocks here).  n_images images of one
+// geometry; the caller's pixels have rows of rgb_stride bytes; plan: what they look like (rows on the device are tight:
+// plan.row_stride).  dst_device: the pixels stay in DEVICE memory of ctx's device and nothing is downloaded.
+int submit_begin(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const JbOutPlan &plan, int64_t rgb_stride, bool dst_device,
+                 Submission &sub) {
+  if (ctx->n_slots == 0) return fail(ctx, JB_ERR_CAPACITY, "context was created without staging buffers");
+  int rc = check_desc(ctx, desc, &sub.g);
+  if (rc) return rc;
+  if (n_images < 1 || n_images > kMaxBatch) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d outside 1..%d", n_images, kMaxBatch);
+  if (plan.status != JB_OK) return fail(ctx, plan.status, "submit: %s", plan.why);
+  // tight rows on the device (12-byte stores need no alignment); a planar format: tight rows of a plane, tight planes
+  if (plan.planar && rgb_stride != plan.row_stride) return fail(ctx, JB_ERR_GEOMETRY, "planar output has tight rows");
+  if (rgb_stride < plan.row_stride) return fail(ctx, JB_ERR_GEOMETRY, "rgb_stride %lld < 3*width", (long long)rgb_stride);
+  sub.coef_total = (size_t)sub.g.coef_bytes * (size_t)n_images, sub.rgb_total = (size_t)plan.image_bytes * (size_t)n_images;
+  if (sub.coef_total > ctx->max_coef || (!dst_device && (sub.rgb_total > ctx->rgb_alloc || sub.rgb_total > ctx->max_rgb)))
+    return fail(ctx, JB_ERR_CAPACITY, "%d image(s) of %dx%d exceed the capacity the context was created with", n_images,
+                desc->width, desc->height);
+  if (dst_device && rgb_stride != plan.row_stride) return fail(ctx, JB_ERR_GEOMETRY, "device output has tight rows");
+  return take_slot(ctx, &sub.slot);
+}
+
+// Prologue, second half, once the caller has chosen its stream: the images' tables (jobs[i]->qtabs, or qtabs + i * 256)
+// resolved into the slot's pinned block and uploaded
+int submit_tables(jb_ctx *ctx, Slot &s, const jb_image_desc *desc, int n_images, const JbHuffJob *const *jobs, const uint16_t *qtabs,
+                  hipStream_t up) {
+  for (int i = 0; i < n_images; i++) {
+    const int rc = jb_resolve_qtabs(desc, jobs ? jobs[i]->qtabs : qtabs + (size_t)i * 256, s.h_q + (size_t)i * 192);
+    if (rc) return fail(ctx, rc, "bad quantisation table id");
+  }
+  JB_HIP(ctx, hipMemcpyAsync(s.d_q, s.h_q, 768u * (size_t)n_images, hipMemcpyHostToDevice, up));
+  return JB_OK;
+}
+
+// The pixel kernel of a submission whose coefficients are (or will be, in stream order) in the slot: into the slot's
+// pixel buffer, or (dst_device) straight into the caller's device memory
+int submit_launch(jb_ctx *ctx, const Submission &sub, const jb_image_desc *desc, int n_images, const JbOutPlan &plan, uint8_t *rgb,
+                  bool dst_device, hipStream_t up) {
+  const Slot &s = *sub.slot;
+  jb_device_batch b;
+  memset(&b, 0, sizeof b);
+  b.desc = *desc;
+  b.n_images = n_images;
+  b.d_coef = (const int16_t *)s.d_coef;
+  b.coef_image_stride = sub.g.coef_bytes;  // a multiple of 128
+  b.d_qtabs = s.d_q;
+  b.qtab_image_stride = n_images > 1 ? 768 : 0;
+  b.d_rgb = dst_device ? rgb : (uint8_t *)s.d_rgb;
+  b.rgb_row_stride = plan.row_stride;
+  b.rgb_image_stride = plan.image_bytes;
+  return seam_launch(ctx, &b, up, plan, "submit");
+}
+
+// Epilogue: the slot is in flight under the next ticket, and the ring moves on
+void submit_end(jb_ctx *ctx, Slot &s, int *ticket) {
+  s.busy = true;
+  s.ticket = ctx->next_ticket++;
+  if (ctx->next_ticket < 0) ctx->next_ticket = 1;
+  *ticket = s.ticket;
+  ctx->next_slot = (ctx->next_slot + 1) % ctx->n_slots;
+}
 
 // One submission of the staging ring: n_images images of one geometry, coefficients contiguous
 // (image stride = coef_bytes), tables per image, pixels contiguous with tight rows -- or, for
 // n_images == 1, any row stride.
 // dst_device: `rgb` is DEVICE memory of ctx's device -- the kernel writes the pixels there and nothing
 // is downloaded (jb_batch_decoder_set_device_output).
-// scale (2, 4, 8): the pixels are the area-reduced image (jb_scaled_size), rgb / rgb_stride describe it.
+// plan: what the pixels look like (at scale 2, 4, 8 the area-reduced image); rgb / rgb_stride describe that output.
 int submit_impl(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef, const uint16_t *qtabs,
-                uint8_t *rgb, int64_t rgb_stride, int *ticket, bool dst_device = false, int scale = 1, const jb_output_spec *fmt = nullptr) {
-  if (ctx->n_slots == 0) return fail(ctx, JB_ERR_CAPACITY, "context was created without staging buffers");
-  jb_geometry g;
-  int rc = check_desc(ctx, desc, &g);
+                uint8_t *rgb, int64_t rgb_stride, int *ticket, const JbOutPlan &plan, bool dst_device) {
+  Submission sub(ctx);
+  int rc = submit_begin(ctx, desc, n_images, plan, rgb_stride, dst_device, sub);
   if (rc) return rc;
-  if (n_images < 1 || n_images > kMaxBatch) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d outside 1..%d", n_images, kMaxBatch);
-  int32_t out_w = 0, out_h = 0;
-  if (jb_scaled_size(desc->width, desc->height, scale, &out_w, &out_h) != JB_OK) return fail(ctx, JB_ERR_GEOMETRY, "scale %d is not 1, 2, 4 or 8", scale);
-  const int64_t out_bytes = 3LL * out_w * out_h * fmt_esize(fmt);  // g.rgb_bytes when scale == 1
-  // tight rows on the device (12-byte stores need no alignment); a planar format: tight rows of a plane, tight planes
-  const int64_t dev_stride = fmt_planar(fmt) ? (int64_t)out_w * fmt_esize(fmt) : 3LL * out_w;
-  if (fmt_planar(fmt) && rgb_stride != dev_stride) return fail(ctx, JB_ERR_GEOMETRY, "planar output has tight rows");
-  if (rgb_stride < dev_stride) return fail(ctx, JB_ERR_GEOMETRY, "rgb_stride %lld < 3*width", (long long)rgb_stride);
-  const size_t coef_total = (size_t)g.coef_bytes * (size_t)n_images, rgb_total = (size_t)out_bytes * (size_t)n_images;
-  if (coef_total > ctx->max_coef || (!dst_device && (rgb_total > ctx->rgb_alloc || rgb_total > ctx->max_rgb)))
-    return fail(ctx, JB_ERR_CAPACITY, "%d image(s) of %dx%d exceed the capacity the context was created with", n_images,
-                desc->width, desc->height);
-  if (dst_device && rgb_stride != dev_stride) return fail(ctx, JB_ERR_GEOMETRY, "device output has tight rows");
-  DeviceGuard guard(ctx->device);
-  Slot *slot = nullptr;
-  rc = take_slot(ctx, &slot);
-  if (rc) return rc;
-  Slot &s = *slot;
+  Slot &s = *sub.slot;
   // One image: upload + kernel on the primary stream, download on the second (ordered by an
   // event), so the link runs both ways even with a single submitter.  A group of small images
   // runs whole on one stream and consecutive groups alternate between the two streams: with many
@@ -801,7 +854,7 @@ int submit_impl(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int1
   if (n_images > 1) {
     if (ctx->stream2 && (ctx->n_group_submits++ & 1u)) up = ctx->stream2;
     down = up;
-  } else if (ctx->stream2 && ctx->n_pairs > 1 && coef_total + rgb_total < jb_ctx::kLargeSubmission) {
+  } else if (ctx->stream2 && ctx->n_pairs > 1 && sub.coef_total + sub.rgb_total < jb_ctx::kLargeSubmission) {
     // one image: the next of the K (upload + kernel, download) stream pairs
     const int k = (int)(ctx->n_single_submits++ % (unsigned)ctx->n_pairs);
     if (k > 0) {
@@ -811,24 +864,10 @@ int submit_impl(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int1
       down = ctx->pair_down[k];
     }
   }
-  for (int i = 0; i < n_images; i++) {
-    rc = jb_resolve_qtabs(desc, qtabs + (size_t)i * 256, s.h_q + (size_t)i * 192);
-    if (rc) return fail(ctx, rc, "bad quantisation table id");
-  }
-  JB_HIP(ctx, hipMemcpyAsync(s.d_q, s.h_q, 768u * (size_t)n_images, hipMemcpyHostToDevice, up));
-  JB_HIP(ctx, hipMemcpyAsync(s.d_coef, coef, coef_total, hipMemcpyHostToDevice, up));
-  jb_device_batch b;
-  memset(&b, 0, sizeof b);
-  b.desc = *desc;
-  b.n_images = n_images;
-  b.d_coef = (const int16_t *)s.d_coef;
-  b.coef_image_stride = g.coef_bytes;  // a multiple of 128
-  b.d_qtabs = s.d_q;
-  b.qtab_image_stride = n_images > 1 ? 768 : 0;
-  b.d_rgb = dst_device ? rgb : (uint8_t *)s.d_rgb;
-  b.rgb_row_stride = dev_stride;
-  b.rgb_image_stride = out_bytes;
-  rc = seam_launch(ctx, &b, up, scale, "submit", fmt);
+  rc = submit_tables(ctx, s, desc, n_images, nullptr, qtabs, up);
+  if (rc) return rc;
+  JB_HIP(ctx, hipMemcpyAsync(s.d_coef, coef, sub.coef_total, hipMemcpyHostToDevice, up));
+  rc = submit_launch(ctx, sub, desc, n_images, plan, rgb, dst_device, up);
   if (rc) return rc;
   if (dst_device) {
     down = up;  // the pixels stay on the device: done when the kernel is
@@ -838,18 +877,14 @@ int submit_impl(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int1
       JB_HIP(ctx, hipEventRecord(s.computed, up));
       JB_HIP(ctx, hipStreamWaitEvent(down, s.computed, 0));
     }
-    if (rgb_stride == dev_stride)
-      JB_HIP(ctx, hipMemcpyAsync(rgb, s.d_rgb, rgb_total, hipMemcpyDeviceToHost, down));
-    else
-      JB_HIP(ctx, hipMemcpy2DAsync(rgb, (size_t)rgb_stride, s.d_rgb, (size_t)dev_stride, (size_t)out_w * 3,
-                                   (size_t)out_h, hipMemcpyDeviceToHost, down));
+    if (rgb_stride == plan.row_stride)
+      JB_HIP(ctx, hipMemcpyAsync(rgb, s.d_rgb, sub.rgb_total, hipMemcpyDeviceToHost, down));
+    else  // (interleaved only: planar rows are tight)
+      JB_HIP(ctx, hipMemcpy2DAsync(rgb, (size_t)rgb_stride, s.d_rgb, (size_t)plan.row_stride, (size_t)plan.row_stride,
+                                   (size_t)plan.out_h, hipMemcpyDeviceToHost, down));
   }
   JB_HIP(ctx, hipEventRecord(s.done, down));
-  s.busy = true;
-  s.ticket = ctx->next_ticket++;
-  if (ctx->next_ticket < 0) ctx->next_ticket = 1;
-  *ticket = s.ticket;
-  ctx->next_slot = (ctx->next_slot + 1) % ctx->n_slots;
+  submit_end(ctx, s, ticket);
   return JB_OK;
 }
 
@@ -934,67 +969,36 @@ int pack_into_slot(jb_ctx *ctx, Slot &s, const JbHuffJob *const *jobs, int n, in
 // and tables (`desc`, `qtabs` = n x 4*64).
 int submit_jobs_impl(jb_ctx *ctx, const JbHuffJob *const *jobs, const uint8_t *packed, const JbHuffLayout *lay_in,
                      const jb_image_desc *desc_in, const uint16_t *qtabs_in, int n_images, uint8_t *rgb, int64_t rgb_stride,
-                     uint32_t *status_out, int *ticket, bool dst_device = false, int scale = 1, const jb_output_spec *fmt = nullptr) {
-  if (ctx->n_slots == 0) return fail(ctx, JB_ERR_CAPACITY, "context was created without staging buffers");
-  if (n_images < 1 || n_images > kMaxBatch) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d outside 1..%d", n_images, kMaxBatch);
+                     uint32_t *status_out, int *ticket, const JbOutPlan &plan, bool dst_device) {
   const jb_image_desc *desc = jobs ? &jobs[0]->desc : desc_in;
-  jb_geometry g;
-  int rc = check_desc(ctx, desc, &g);
+  Submission sub(ctx);
+  int rc = submit_begin(ctx, desc, n_images, plan, rgb_stride, dst_device, sub);
   if (rc) return rc;
-  int32_t out_w = 0, out_h = 0;
-  if (jb_scaled_size(desc->width, desc->height, scale, &out_w, &out_h) != JB_OK) return fail(ctx, JB_ERR_GEOMETRY, "scale %d is not 1, 2, 4 or 8", scale);
-  const int64_t out_bytes = 3LL * out_w * out_h * fmt_esize(fmt);  // g.rgb_bytes when scale == 1
-  const int64_t dev_stride = fmt_planar(fmt) ? (int64_t)out_w * fmt_esize(fmt) : 3LL * out_w;  // (planar: rows of a plane)
-  if (fmt_planar(fmt) && rgb_stride != dev_stride) return fail(ctx, JB_ERR_GEOMETRY, "planar output has tight rows");
-  if (rgb_stride < dev_stride) return fail(ctx, JB_ERR_GEOMETRY, "rgb_stride %lld < 3*width", (long long)rgb_stride);
-  const size_t coef_total = (size_t)g.coef_bytes * (size_t)n_images, rgb_total = (size_t)out_bytes * (size_t)n_images;
-  if (coef_total > ctx->max_coef || (!dst_device && (rgb_total > ctx->rgb_alloc || rgb_total > ctx->max_rgb)))
-    return fail(ctx, JB_ERR_CAPACITY, "%d image(s) of %dx%d exceed the capacity the context was created with", n_images,
-                desc->width, desc->height);
-  if (dst_device && rgb_stride != dev_stride) return fail(ctx, JB_ERR_GEOMETRY, "device output has tight rows");
-  DeviceGuard guard(ctx->device);
-  Slot *slot = nullptr;
-  rc = take_slot(ctx, &slot);
-  if (rc) return rc;
-  Slot &s = *slot;
+  Slot &s = *sub.slot;
   // the whole submission on one stream of the pool, consecutive submissions on different ones
   hipStream_t &ps = ctx->pool[ctx->n_group_submits++ % jb_ctx::kPool];
   if (!ps) JB_HIP(ctx, hipStreamCreateWithFlags(&ps, hipStreamNonBlocking));
   hipStream_t up = ps;
-  for (int i = 0; i < n_images; i++) {
-    rc = jb_resolve_qtabs(desc, jobs ? jobs[i]->qtabs : qtabs_in + (size_t)i * 256, s.h_q + (size_t)i * 192);
-    if (rc) return fail(ctx, rc, "bad quantisation table id");
-  }
-  JB_HIP(ctx, hipMemcpyAsync(s.d_q, s.h_q, 768u * (size_t)n_images, hipMemcpyHostToDevice, up));
+  rc = submit_tables(ctx, s, desc, n_images, jobs, qtabs_in, up);
+  if (rc) return rc;
   const bool timing = ctx->knobs.timing == 2;
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double tt0 = timing ? now() : 0;
   JbHuffLayout lay_own;
   if (jobs) {
-    rc = pack_into_slot(ctx, s, jobs, n_images, g.coef_bytes, &lay_own);
+    rc = pack_into_slot(ctx, s, jobs, n_images, sub.g.coef_bytes, &lay_own);
     if (rc) return rc;
     packed = s.h_blob;
     lay_in = &lay_own;
   }
-  if (lay_in->n != n_images || lay_in->coef_stride != g.coef_bytes) return fail(ctx, JB_ERR_STATE, "packed submission does not match its descriptor");
+  if (lay_in->n != n_images || lay_in->coef_stride != sub.g.coef_bytes) return fail(ctx, JB_ERR_STATE, "packed submission does not match its descriptor");
   const double tt1 = timing ? now() : 0;
-  rc = huff_stage(ctx, s, packed, *lay_in, coef_total, (int16_t *)s.d_coef, up);
+  rc = huff_stage(ctx, s, packed, *lay_in, sub.coef_total, (int16_t *)s.d_coef, up);
   if (rc) return rc;
   const double tt2 = timing ? now() : 0;
   if (timing) (void)hipStreamSynchronize(up);
   const double tt3 = timing ? now() : 0;
-  jb_device_batch b;
-  memset(&b, 0, sizeof b);
-  b.desc = *desc;
-  b.n_images = n_images;
-  b.d_coef = (const int16_t *)s.d_coef;
-  b.coef_image_stride = g.coef_bytes;
-  b.d_qtabs = s.d_q;
-  b.qtab_image_stride = n_images > 1 ? 768 : 0;
-  b.d_rgb = dst_device ? rgb : (uint8_t *)s.d_rgb;
-  b.rgb_row_stride = dev_stride;
-  b.rgb_image_stride = out_bytes;
-  rc = seam_launch(ctx, &b, up, scale, "submit", fmt);
+  rc = submit_launch(ctx, sub, desc, n_images, plan, rgb, dst_device, up);
   if (rc) return rc;
   // the status words travel with the pixels: into the caller's (pinned) words when it keeps its own
   // -- many threads share this ring, a slot's words may be recycled before their owner looks -- else
@@ -1016,10 +1020,10 @@ int submit_jobs_impl(jb_ctx *ctx, const JbHuffJob *const *jobs, const uint8_t *p
     it.ctx = ctx;
     it.age = ctx->dl_age.load(std::memory_order_relaxed);
     it.slot = &s;
-    it.dst = rgb, it.src = s.d_rgb, it.bytes = rgb_total;
+    it.dst = rgb, it.src = s.d_rgb, it.bytes = sub.rgb_total;
     it.rows = 0, it.dst_pitch = it.src_pitch = it.row_bytes = 0;
-    if (rgb_stride != dev_stride)
-      it.rows = (size_t)out_h, it.dst_pitch = (size_t)rgb_stride, it.src_pitch = (size_t)dev_stride, it.row_bytes = (size_t)out_w * 3;
+    if (rgb_stride != plan.row_stride)  // (interleaved only: planar rows are tight)
+      it.rows = (size_t)plan.out_h, it.dst_pitch = (size_t)rgb_stride, it.src_pitch = it.row_bytes = (size_t)plan.row_stride;
     it.status_dst = nullptr;
     it.status_src = nullptr;
     it.status_bytes = 0;
@@ -1029,13 +1033,9 @@ int submit_jobs_impl(jb_ctx *ctx, const JbHuffJob *const *jobs, const uint8_t *p
   if (timing)
     fprintf(stderr, "submit (device entropy): pack %.3f ms, upload + launches issued %.3f ms, entropy kernels done after %.3f ms more, pixel kernel + download call %.3f ms\n",
             (tt1 - tt0) * 1e3, (tt2 - tt1) * 1e3, (tt3 - tt2) * 1e3, (tt4 - tt3) * 1e3);
-  s.busy = true;
   ctx->n_device_entropy += n_images;
   s.n_status = status_out ? 0 : n_images;
-  s.ticket = ctx->next_ticket++;
-  if (ctx->next_ticket < 0) ctx->next_ticket = 1;
-  *ticket = s.ticket;
-  ctx->next_slot = (ctx->next_slot + 1) % ctx->n_slots;
+  submit_end(ctx, s, ticket);
   return JB_OK;
 }
 
@@ -1092,33 +1092,20 @@ int jb_entropy_decode_device(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes
   return check_status(ctx, s);
 }
 
-// decode(bytes) with the entropy stage on the device: one prepared image through the ring
-// (used by jb_decode_memory, jb_frontend.cpp); the staging ring follows the frame
-int jb_decode_job_scaled_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride, int scale);
-int jb_decode_job_fmt_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride, int scale, const jb_output_spec *fmt);
-int jb_decode_job_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride) {
-  return jb_decode_job_scaled_(ctx, job, rgb, rgb_stride, 1);
-}
-
-// the same at 1/scale (jb_decode_memory_scaled): rgb / rgb_stride describe the reduced image
-int jb_decode_job_scaled_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride, int scale) {
-  return jb_decode_job_fmt_(ctx, job, rgb, rgb_stride, scale, nullptr);
-}
-
-// the same in an output format (jb_decode_memory_fmt; null: interleaved): rgb_stride is then a plane's row stride
-int jb_decode_job_fmt_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride, int scale, const jb_output_spec *fmt) {
+// decode(bytes) with the entropy stage on the device: one prepared image through the ring, in any output plan
+// (jb_decode_memory*, jb_frontend.cpp: the device-entropy route); the staging ring follows the frame; tight rows, rgb
+// holds plan.image_bytes
+int jb_decode_job_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, const JbOutPlan &plan) {
   const bool timing = ctx->knobs.timing == 1;
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t0 = timing ? now() : 0;
-  int32_t out_w = 0, out_h = 0;
-  if (jb_scaled_size(job->desc.width, job->desc.height, scale, &out_w, &out_h) != JB_OK)
-    return fail(ctx, JB_ERR_GEOMETRY, "scale %d is not 1, 2, 4 or 8", scale);
-  int rc = jb_ctx_reserve(ctx, (size_t)job->geo.coef_bytes, (size_t)3 * out_w * out_h * fmt_esize(fmt));
+  if (plan.status != JB_OK) return fail(ctx, plan.status, "%s", plan.why);
+  int rc = jb_ctx_reserve(ctx, (size_t)job->geo.coef_bytes, (size_t)plan.image_bytes);
   if (rc) return rc;
   const double t1 = timing ? now() : 0;
   int ticket = -1;
   const JbHuffJob *jobs[1] = {job};
-  rc = submit_jobs_impl(ctx, jobs, nullptr, nullptr, nullptr, nullptr, 1, rgb, rgb_stride, nullptr, &ticket, false, scale, fmt);
+  rc = submit_jobs_impl(ctx, jobs, nullptr, nullptr, nullptr, nullptr, 1, rgb, plan.row_stride, nullptr, &ticket, plan, false);
   if (rc) return rc;
   const double t2 = timing ? now() : 0;
   rc = jb_wait(ctx, ticket);
@@ -1126,36 +1113,32 @@ int jb_decode_job_fmt_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t 
   return rc;
 }
 
-// several prepared images of ONE geometry in one submission (jb_batch.cpp); pixels contiguous, tight rows
-// (scale: the pixels are the area-reduced images, tight rows of 3 * ceil(width / scale) bytes)
+// several prepared images of ONE geometry in one submission (jb_batch.cpp); pixels contiguous, tight rows of the plan
 int jb_submit_packed_(jb_ctx *ctx, const jb_image_desc *desc, const uint16_t *qtabs, const uint8_t *packed, const JbHuffLayout *lay,
-                      uint8_t *rgb, uint32_t *status_out, int *ticket, int dst_device, int scale, const jb_output_spec *fmt) {
-  const int64_t out_w = (desc->width + scale - 1) / (scale > 0 ? scale : 1);
-  const int64_t stride = fmt_planar(fmt) ? out_w * fmt_esize(fmt) : 3LL * out_w;
-  return submit_jobs_impl(ctx, nullptr, packed, lay, desc, qtabs, lay->n, rgb, stride, status_out, ticket, dst_device != 0, scale, fmt);
+                      uint8_t *rgb, uint32_t *status_out, int *ticket, const JbOutPlan &plan, int dst_device) {
+  return submit_jobs_impl(ctx, nullptr, packed, lay, desc, qtabs, lay->n, rgb, plan.row_stride, status_out, ticket, plan, dst_device != 0);
 }
 
-// a group of the batch decoder (jb_batch.cpp): jb_submit_batch, or (dst_device = 1) with the pixels left in DEVICE
-// memory of the context's device; at 1/scale (tight rows of 3 * ceil(width / scale) bytes)
+// a group of the batch decoder (jb_batch.cpp): jb_submit_batch in the plan's output, or (dst_device = 1) with the
+// pixels left in DEVICE memory of the context's device; tight rows
 int jb_submit_group_(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef, const uint16_t *qtabs,
-                     uint8_t *rgb, int *ticket, int dst_device, int scale, const jb_output_spec *fmt) {
-  const int64_t out_w = (desc->width + scale - 1) / (scale > 0 ? scale : 1);
-  const int64_t stride = fmt_planar(fmt) ? out_w * fmt_esize(fmt) : 3LL * out_w;
-  return submit_impl(ctx, desc, n_images, coef, qtabs, rgb, stride, ticket, dst_device != 0, scale, fmt);
+                     uint8_t *rgb, int *ticket, const JbOutPlan &plan, int dst_device) {
+  return submit_impl(ctx, desc, n_images, coef, qtabs, rgb, plan.row_stride, ticket, plan, dst_device != 0);
 }
 
 int jb_submit(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs,
               uint8_t *rgb, int64_t rgb_stride, int *ticket) {
   if (!ctx) return fail(nullptr, JB_ERR_NULL, "jb_submit: ctx is NULL");
   if (!desc || !coef || !qtabs || !rgb || !ticket) return fail(ctx, JB_ERR_NULL, "jb_submit: NULL pointer");
-  return submit_impl(ctx, desc, 1, coef, qtabs, rgb, rgb_stride, ticket);
+  return submit_impl(ctx, desc, 1, coef, qtabs, rgb, rgb_stride, ticket, jb_out_plan_(desc, 1, nullptr), false);
 }
 
 int jb_submit_batch(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef,
                     const uint16_t *qtabs, uint8_t *rgb, int *ticket) {
   if (!ctx) return fail(nullptr, JB_ERR_NULL, "jb_submit_batch: ctx is NULL");
   if (!desc || !coef || !qtabs || !rgb || !ticket) return fail(ctx, JB_ERR_NULL, "jb_submit_batch: NULL pointer");
-  return submit_impl(ctx, desc, n_images, coef, qtabs, rgb, 3LL * desc->width, ticket);
+  const JbOutPlan plan = jb_out_plan_(desc, 1, nullptr);
+  return submit_impl(ctx, desc, n_images, coef, qtabs, rgb, plan.row_stride, ticket, plan, false);
 }
 
 int jb_wait(jb_ctx *ctx, int ticket) {
@@ -1201,21 +1184,13 @@ int jb_blocks_to_rgb(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef
   return jb_wait(ctx, ticket);
 }
 
-int jb_blocks_to_rgb_fmt_(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs,
-                          uint8_t *rgb, int64_t rgb_stride, int scale, const jb_output_spec *fmt);
-// jb_blocks_to_rgb at 1/scale (jb_decode_memory_scaled's host-entropy path): rgb holds the reduced image
-int jb_blocks_to_rgb_scaled_(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs,
-                             uint8_t *rgb, int64_t rgb_stride, int scale) {
-  return jb_blocks_to_rgb_fmt_(ctx, desc, coef, qtabs, rgb, rgb_stride, scale, nullptr);
-}
-
-// the same in an output format (jb_decode_memory_fmt's host-entropy path; null: interleaved)
-int jb_blocks_to_rgb_fmt_(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs,
-                          uint8_t *rgb, int64_t rgb_stride, int scale, const jb_output_spec *fmt) {
+// jb_blocks_to_rgb with any output plan (jb_decode_memory*'s host-entropy route): tight rows, rgb holds plan.image_bytes
+int jb_blocks_to_rgb_plan_(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs, uint8_t *rgb,
+                           const JbOutPlan &plan) {
   if (!ctx) return fail(nullptr, JB_ERR_NULL, "jb_blocks_to_rgb: ctx is NULL");
   if (!desc || !coef || !qtabs || !rgb) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb: NULL pointer");
   int ticket = -1;
-  int rc = submit_impl(ctx, desc, 1, coef, qtabs, rgb, rgb_stride, &ticket, false, scale, fmt);
+  int rc = submit_impl(ctx, desc, 1, coef, qtabs, rgb, plan.row_stride, &ticket, plan, false);
   if (rc) return rc;
   return jb_wait(ctx, ticket);
 }

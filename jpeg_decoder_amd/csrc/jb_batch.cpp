@@ -31,21 +31,20 @@
 #include "jb_hostmem.h"
 #include "jb_huff.h"
 #include "jb_knobs.h"
+#include "jb_plan.h"
 
 struct jb_ctx;
 int jb_fail_(jb_ctx *ctx, int code, const char *msg);
 // device-side entropy decoding: several prepared images of one geometry in one submission; the
 // images' status words (0 = decoded cleanly) are copied to `status_out` (pinned) with the pixels
+// (plan: what the pixels look like -- jb_plan.h; tight rows, and tight planes with a planar format)
 // (dst_device: `rgb` is device memory of the context's device, nothing is downloaded)
-// (scale: the pixels are the area-reduced images of jb_batch_decoder_set_scale, tight rows)
 extern "C" int jb_submit_packed_(jb_ctx *ctx, const jb_image_desc *desc, const uint16_t *qtabs, const uint8_t *packed,
-                                 const JbHuffLayout *lay, uint8_t *rgb, uint32_t *status_out, int *ticket, int dst_device, int scale,
-                                 const jb_output_spec *fmt);
-// jb_submit_batch (dst_device = 0) or its device-output form (1) at 1/scale
+                                 const JbHuffLayout *lay, uint8_t *rgb, uint32_t *status_out, int *ticket, const JbOutPlan &plan,
+                                 int dst_device);
+// jb_submit_batch (dst_device = 0) or its device-output form (1) in the plan's output
 extern "C" int jb_submit_group_(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef, const uint16_t *qtabs,
-                                uint8_t *rgb, int *ticket, int dst_device, int scale, const jb_output_spec *fmt);
-// (fmt: null, or the planar output format of jb_batch_decoder_set_output_format -- tight rows and planes)
-extern "C" int jb_format_esize_(int format);  // jb_geometry.cpp: bytes per element of a JB_FMT_*
+                                uint8_t *rgb, int *ticket, const JbOutPlan &plan, int dst_device);
 // jb_wait in two halves, so that many threads can wait on one shared context (jb_api.cpp):
 // under the caller's lock, the event to block on (nullptr: the submission has completed) ...
 void *jb_wait_begin_(jb_ctx *ctx, int ticket);
@@ -124,12 +123,24 @@ int available_cpus() {
   return n;
 }
 
+// What a decoder has been asked to deliver (jb_batch_decoder_set_scale, jb_batch_decoder_set_output_format): ONE value on
+// the decoder, copied to its parts, its twin and every run.  Never a format other than 0 with a scale other than 1.
+struct OutputRequest {
+  int scale = 1;
+  jb_output_spec spec = {};  // format 0: interleaved uint8
+  // can it be had at all?  The plan function decides (jb_plan.h), here for an image of one pixel
+  int status() const {
+    const jb_image_desc one = {1, 1, 1, 1, {0, 0, 0}, 0};
+    return jb_out_plan_(&one, scale, &spec).status;
+  }
+};
+
 struct Parsed {
   std::vector<uint8_t> bytes;
   bool loaded = false;  // `bytes` is the whole file (pass 1 reads only the head of a large file)
   jb_image_desc desc;
-  jb_geometry geo;         // (geo.rgb_bytes: the bytes of the OUTPUT image, reduced when the run's scale is > 1)
-  int32_t out_w = 0, out_h = 0;  // the output image's size
+  jb_geometry geo;         // (geo.rgb_bytes: the bytes of the OUTPUT image, plan.image_bytes)
+  JbOutPlan plan = {};     // the output image: size, element size, bytes (jb_plan.h)
   uint16_t qtabs[256];
   int status = JB_OK;
   std::string error;
@@ -285,8 +296,7 @@ struct Run {
   bool lazy = false;
   std::vector<std::vector<int>> *deferred = nullptr;
   size_t slot_coef = 0, slot_rgb = 0;  // what a ring slot holds (one image may be larger than a group's bound, not than this)
-  int scale = 1;                       // output at 1/scale (jb_batch_decoder_set_scale)
-  const jb_output_spec *fmt = nullptr; // a planar output format (jb_batch_decoder_set_output_format); null: interleaved uint8
+  OutputRequest out;  // the decoder's
 };
 
 // pass 1 (per host thread): parse the headers of its files, so that the buffers can be sized once for
@@ -304,13 +314,18 @@ struct Run {
 constexpr size_t kHeadBytes[2] = {(size_t)4 << 10, (size_t)64 << 10};
 
 // every size of the pixels that this file takes downstream -- staging, arena, ring slots, copies -- is the output's:
-// geo.rgb_bytes is set to the reduced image's bytes at scale > 1, to the format's bytes (jb_output_bytes) with a planar format
-void parse_one(Parsed &p, int scale, const jb_output_spec *fmt) {
+// geo.rgb_bytes is set to the bytes of the plan's image: the reduced one at scale > 1, the format's with a planar format
+void parse_one(Parsed &p, const OutputRequest &out) {
   p.status = jb_entropy_decode(p.bytes.data(), p.bytes.size(), &p.desc, p.qtabs, nullptr, 0);
   if (p.status == JB_OK) p.status = jb_geometry_of(&p.desc, &p.geo);
-  if (p.status == JB_OK) p.status = jb_scaled_size(p.desc.width, p.desc.height, scale, &p.out_w, &p.out_h);
-  if (p.status == JB_OK) p.geo.rgb_bytes = 3LL * p.out_w * p.out_h * (fmt ? jb_format_esize_(fmt->format) : 1);
-  if (p.status != JB_OK) p.error = jb_last_error(nullptr);
+  if (p.status != JB_OK) {
+    p.error = jb_last_error(nullptr);
+    return;
+  }
+  p.plan = jb_out_plan_(&p.desc, out.scale, &out.spec);
+  p.status = p.plan.status;
+  if (p.status == JB_OK) p.geo.rgb_bytes = p.plan.image_bytes;
+  else p.error = p.plan.why;
 }
 
 void parse_pass(const Run &r, int t, std::vector<Parsed> &parsed, size_t *max_coef, size_t *max_rgb, double *t_read) {
@@ -326,7 +341,7 @@ void parse_pass(const Run &r, int t, std::vector<Parsed> &parsed, size_t *max_co
       ok = level < 2 ? read_prefix(r.paths[i], kHeadBytes[level], p.bytes, &p.loaded) : read_file(r.paths[i], p.bytes);
       *t_read += now_s() - a;
       if (level == 2) p.loaded = ok;
-      if (ok) parse_one(p, r.scale, r.fmt);
+      if (ok) parse_one(p, r.out);
     }
     if (!ok) {
       p.status = JB_ERR_FORMAT;
@@ -385,7 +400,7 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
       p.have = true;
       p.loaded = ok;
       if (ok) {
-        parse_one(p, r.scale, r.fmt);
+        parse_one(p, r.out);
       } else {
         p.status = JB_ERR_FORMAT;
         p.error = "cannot read file";
@@ -457,7 +472,7 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
           void *ev2 = nullptr;
           {
             std::lock_guard<std::mutex> lk(r.dev->mu);
-            st_j = jb_submit_group_(r.dev->ctx, &p.desc, 1, cbuf, p.qtabs, staged, &ticket, to_device, r.scale, r.fmt);
+            st_j = jb_submit_group_(r.dev->ctx, &p.desc, 1, cbuf, p.qtabs, staged, &ticket, p.plan, to_device);
             if (st_j == JB_OK) ev2 = jb_wait_begin_(r.dev->ctx, ticket);
             else text_j = jb_last_error(r.dev->ctx);
           }
@@ -588,7 +603,7 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
     if (!dst) {
       st = JB_ERR_CAPACITY;
       text = "output arena exhausted";
-    } else if (r.fmt && ((uintptr_t)dst & (uintptr_t)(jb_format_esize_(r.fmt->format) - 1))) {
+    } else if ((uintptr_t)dst & (uintptr_t)(head.plan.esize - 1)) {
       // (groups start on 256-byte steps of the arena / region and an image is a whole number of elements, so every image
       // is element-aligned unless the region itself is not: checked, not assumed -- the kernel's f32 / f16 stores need it)
       st = JB_ERR_GEOMETRY;
@@ -599,8 +614,8 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
       const int i = index_of(k + j);
       Parsed &p = parsed[(size_t)(k + j)];
       memcpy(&qtabs[(size_t)j * 256], p.qtabs, sizeof p.qtabs);
-      r.widths[i] = p.out_w;
-      r.heights[i] = p.out_h;
+      r.widths[i] = p.plan.out_w;
+      r.heights[i] = p.plan.out_h;
       r.rgb[i] = nullptr;
       if (st == JB_OK) {
         r.rgb[i] = use_arena ? dst + (size_t)j * rgb_bytes : jb_alloc_pixels_(rgb_bytes);
@@ -630,10 +645,10 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
       // transfers and the kernel run while this thread decodes its next group
       std::lock_guard<std::mutex> lk(r.dev->mu);
       if (on_device) {
-        st = jb_submit_packed_(r.dev->ctx, &head.desc, qtabs.data(), lane->blob[s], &lay, dst, lane->status[s], &grp[s].ticket, to_device,
-                               r.scale, r.fmt);
+        st = jb_submit_packed_(r.dev->ctx, &head.desc, qtabs.data(), lane->blob[s], &lay, dst, lane->status[s], &grp[s].ticket, head.plan,
+                               to_device);
       } else {
-        st = jb_submit_group_(r.dev->ctx, &head.desc, n, lane->coef[s], qtabs.data(), dst, &grp[s].ticket, to_device, r.scale, r.fmt);
+        st = jb_submit_group_(r.dev->ctx, &head.desc, n, lane->coef[s], qtabs.data(), dst, &grp[s].ticket, head.plan, to_device);
       }
       if (st != JB_OK) text = jb_last_error(r.dev->ctx);
       t_wait += now_s() - a;
@@ -689,10 +704,7 @@ struct jb_batch_decoder {
   bool made_multi = false;
   int made_threads = 0;
   size_t made_coef = 0, made_rgb = 0;
-  int scale = 1;  // output at 1/scale (jb_batch_decoder_set_scale): on this decoder, its parts and its twin alike
-  // output format (jb_batch_decoder_set_output_format), likewise; has_fmt: it is one of the planar ones
-  jb_output_spec fmt = {};
-  bool has_fmt = false;
+  OutputRequest out;  // scale and format of the output: on this decoder, its parts and its twin alike
   // jb_batch_decoder_submit / _collect: up to two batches in flight, batch k on side k & 1 -- side 0 is this
   // decoder, side 1 its twin (same devices, threads and sizes, its own ring, staging and arena) -- so that the
   // start-up of one batch (headers, first groups) runs under the tail of the other (last kernels, last downloads)
@@ -847,8 +859,7 @@ int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8
           &lists, rgb, widths, heights, statuses, d->arena, &dev, &tot, &d->knobs};
     r.lazy = lazy;
     r.deferred = &deferred;
-    r.scale = d->scale;
-    r.fmt = d->has_fmt ? &d->fmt : nullptr;
+    r.out = d->out;
     const double tr0 = now_s();
     std::vector<std::vector<Parsed>> parsed((size_t)nt);
     for (int t = 0; t < nt; t++) parsed[(size_t)t].resize(lists[(size_t)t].size());
@@ -1109,21 +1120,12 @@ extern "C" int jb_batch_decoder_set_device_outputs(jb_batch_decoder *d, void *co
 
 namespace {
 
-// the decoder, its parts and its twin (with the twin's parts) decode at 1/scale
-void set_scale_all(jb_batch_decoder *d, int scale) {
+// the decoder, its parts and its twin (with the twin's parts) deliver the same output
+void set_output_all(jb_batch_decoder *d, const OutputRequest &out) {
   if (!d) return;
-  d->scale = scale;
-  for (jb_batch_decoder *p : d->parts) set_scale_all(p, scale);
-  set_scale_all(d->twin, scale);
-}
-
-// ... and in one output format
-void set_format_all(jb_batch_decoder *d, const jb_output_spec &spec) {
-  if (!d) return;
-  d->fmt = spec;
-  d->has_fmt = spec.format != JB_FMT_RGB_U8_HWC;
-  for (jb_batch_decoder *p : d->parts) set_format_all(p, spec);
-  set_format_all(d->twin, spec);
+  d->out = out;
+  for (jb_batch_decoder *p : d->parts) set_output_all(p, out);
+  set_output_all(d->twin, out);
 }
 
 // the single-device decoders a decoder consists of
@@ -1269,8 +1271,7 @@ extern "C" int jb_batch_decoder_submit(jb_batch_decoder *d, const char *const *p
     if (rc != JB_OK) return rc;
     d->twin = t;
     d->split_for_sides = false;
-    set_scale_all(t, d->scale);
-    set_format_all(t, d->fmt);
+    set_output_all(t, d->out);
   }
   if (!d->split_for_sides) {  // (only ever the case with nothing in flight: every call that clears it refuses otherwise)
     int rc = arrange_outputs(d, true);
@@ -1316,8 +1317,10 @@ extern "C" int jb_batch_decoder_set_scale(jb_batch_decoder *d, int denom) {
   if (denom != 1 && denom != 2 && denom != 4 && denom != 8)
     return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_set_scale: denom is not 1, 2, 4 or 8");
   if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_scale: batches are in flight (collect them first)");
-  if (denom != 1 && d->has_fmt) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_scale: a planar output format is set: it cannot be combined with a scale");
-  set_scale_all(d, denom);
+  OutputRequest out = d->out;
+  out.scale = denom;
+  if (out.status() == JB_ERR_UNSUPPORTED) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_scale: a planar output format is set: it cannot be combined with a scale");
+  set_output_all(d, out);
   return JB_OK;
 }
 
@@ -1327,9 +1330,11 @@ extern "C" int jb_batch_decoder_set_output_format(jb_batch_decoder *d, const jb_
   if (jb_output_spec_check(spec, 1, 1 << 20) != JB_OK || (spec->format != JB_FMT_RGB_U8_HWC && spec->plane_stride != 0))
     return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_set_output_format: bad output spec (unknown format, reserved or plane_stride not 0, scale / bias not finite)");
   if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_output_format: batches are in flight (collect them first)");
-  if (spec->format != JB_FMT_RGB_U8_HWC && d->scale != 1)
+  OutputRequest out = d->out;
+  out.spec = *spec;
+  if (out.status() == JB_ERR_UNSUPPORTED)
     return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_output_format: the decoder's scale is not 1: a planar output format cannot be combined with it");
-  set_format_all(d, *spec);
+  set_output_all(d, out);
   return JB_OK;
 }
 

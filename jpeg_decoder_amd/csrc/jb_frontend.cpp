@@ -36,21 +36,18 @@
 #include "jb_huff.h"
 #include "jb_huff_core.h"
 #include "jb_knobs.h"
+#include "jb_plan.h"
 
 struct jb_ctx;
 int jb_fail_(jb_ctx *ctx, int code, const char *msg);
 void jb_ctx_set_last_desc_(jb_ctx *ctx, const jb_image_desc *d);
 const JbKnobs *jb_ctx_knobs_(const jb_ctx *ctx);  // jb_api.cpp
-extern "C" int jb_decode_job_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride);  // jb_api.cpp
-// the same two at 1/scale (jb_api.cpp)
-extern "C" int jb_decode_job_scaled_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride, int scale);
-extern "C" int jb_blocks_to_rgb_scaled_(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs,
-                                        uint8_t *rgb, int64_t rgb_stride, int scale);
-// the same two in a planar output format (jb_api.cpp; rgb_stride: a plane's row stride), and a format's element size
-extern "C" int jb_decode_job_fmt_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, int64_t rgb_stride, int scale, const jb_output_spec *fmt);
-extern "C" int jb_blocks_to_rgb_fmt_(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs,
-                                     uint8_t *rgb, int64_t rgb_stride, int scale, const jb_output_spec *fmt);
-extern "C" int jb_format_esize_(int format);
+// the two routes of decode(bytes) into the pixel kernel (jb_api.cpp), tight rows, `plan` (jb_plan.h) says which pixels:
+// the entropy stage on the device (a prepared job) ...
+extern "C" int jb_decode_job_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, const JbOutPlan &plan);
+// ... or on the host (its coefficients)
+extern "C" int jb_blocks_to_rgb_plan_(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs, uint8_t *rgb,
+                                      const JbOutPlan &plan);
 // general front end (jb_frontend_ext.cpp): progressive, grayscale, multi-scan files
 int jb_ext_decode_(const uint8_t *jpeg, size_t n, jb_image_desc *desc, uint16_t *qtabs, int16_t *coef,
                    size_t coef_cap_bytes, std::string *err);
@@ -439,40 +436,14 @@ int jb_entropy_decode_mt(const uint8_t *jpeg, size_t jpeg_bytes, jb_image_desc *
   return rc ? report(nullptr, e) : JB_OK;
 }
 
-int jb_decode_memory(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, uint8_t **rgb, int32_t *width,
-                     int32_t *height) {
-  return jb_decode_memory_scaled(ctx, jpeg, jpeg_bytes, 1, rgb, width, height);
-}
-
-static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, int denom, const jb_output_spec *fmt,
-                              uint8_t **rgb, int32_t *width, int32_t *height);
-
-// denom = 1: jb_decode_memory; 2, 4, 8: the same decode with the area-reduced store stage (include/jpegblk.h)
-int jb_decode_memory_scaled(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, int denom, uint8_t **rgb, int32_t *width,
-                            int32_t *height) {
-  return decode_memory_impl(ctx, jpeg, jpeg_bytes, denom, nullptr, rgb, width, height);
-}
-
-// the same decode in an output format ("tensor-ready output", include/jpegblk.h); format 0 is jb_decode_memory
-int jb_decode_memory_fmt(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, const jb_output_spec *spec, void **out,
-                         int32_t *width, int32_t *height) {
-  if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_memory_fmt: ctx is NULL");
-  if (!spec || !out) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_memory_fmt: NULL pointer");
-  *out = nullptr;
-  if (jb_output_spec_check(spec, 1, 1 << 20) != JB_OK || (spec->format != JB_FMT_RGB_U8_HWC && spec->plane_stride != 0))
-    return jb_fail_(ctx, JB_ERR_GEOMETRY, "jb_decode_memory_fmt: bad output spec (unknown format, reserved or plane_stride not 0, scale / bias not finite)");
-  return decode_memory_impl(ctx, jpeg, jpeg_bytes, 1, spec->format == JB_FMT_RGB_U8_HWC ? nullptr : spec, (uint8_t **)out, width, height);
-}
-
-// fmt: null (interleaved uint8: exactly the calls jb_decode_memory[_scaled] has always made) or a checked planar spec (denom = 1)
-static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, int denom, const jb_output_spec *fmt,
+// Every jb_decode_memory* and jb_decode_file*: denom 1, 2, 4, 8 (checked by the caller); spec: null or format 0
+// (interleaved uint8) or a checked planar spec.  The output's sizes come from the plan of the frame (jb_plan.h).
+static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, int denom, const jb_output_spec *spec,
                               uint8_t **rgb, int32_t *width, int32_t *height) {
-  const size_t es = fmt ? (size_t)jb_format_esize_(fmt->format) : 1;  // bytes per element of the output
   if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_memory: ctx is NULL");
   if (!jpeg || !rgb || !width || !height) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_memory: NULL pointer");
   *rgb = nullptr;
   if (denom != 1 && denom != 2 && denom != 4 && denom != 8) return jb_fail_(ctx, JB_ERR_GEOMETRY, "jb_decode_memory_scaled: denom is not 1, 2, 4 or 8");
-  int32_t out_w = 0, out_h = 0;  // (of the frame decoded below)
   // The entropy stage of a baseline file can run on the device too (jb_huff.hip): the host then only
   // parses the headers and removes the byte stuffing.  One image is one latency-bound submission
   // (a dozen and a half launches: about 1 ms whatever the size, then ~0.4 ms per megabyte of scan)
@@ -499,19 +470,18 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
       if (jb_huff_prepare_(jpeg, jpeg_bytes, job.get(), nullptr, knobs.chunk_bytes) == JB_OK && jb_huff_worth_it_(*job, min_int) &&
           (forced || job->scan_len >= kAutoDeviceScan)) {
         const double t1 = timing ? now() : 0;
-        jb_scaled_size(job->desc.width, job->desc.height, denom, &out_w, &out_h);
-        uint8_t *out = jb_alloc_pixels_((size_t)3 * out_w * out_h * es);
+        const JbOutPlan plan = jb_out_plan_(&job->desc, denom, spec);
+        if (plan.status != JB_OK) return jb_fail_(ctx, plan.status, plan.why);
+        uint8_t *out = jb_alloc_pixels_((size_t)plan.image_bytes);
         if (!out) return jb_fail_(ctx, JB_ERR_CAPACITY, "out of host memory");
-        const int rc = fmt        ? jb_decode_job_fmt_(ctx, job.get(), out, (int64_t)es * out_w, 1, fmt)
-                       : denom == 1 ? jb_decode_job_(ctx, job.get(), out, 3LL * job->desc.width)
-                                    : jb_decode_job_scaled_(ctx, job.get(), out, 3LL * out_w, denom);
+        const int rc = jb_decode_job_(ctx, job.get(), out, plan);
         if (timing)
           fprintf(stderr, "jb_decode_memory(device path): prepare %.3f ms, submit + wait %.3f ms (%u intervals, %u chunks, %zu bytes of scan), rc %d\n",
                   (t1 - t0) * 1e3, (now() - t1) * 1e3, job->img.n_int, job->img.n_chunks, job->scan_len, rc);
         if (rc == JB_OK) {
           *rgb = out;
-          *width = out_w;
-          *height = out_h;
+          *width = plan.out_w;
+          *height = plan.out_h;
           jb_ctx_set_last_desc_(ctx, &job->desc);
           return JB_OK;
         }
@@ -527,10 +497,10 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
   jb_geometry g;
   rc = jb_geometry_of(&desc, &g);
   if (rc) return jb_fail_(ctx, rc, "bad frame geometry");
-  rc = jb_scaled_size(desc.width, desc.height, denom, &out_w, &out_h);
-  if (rc) return jb_fail_(ctx, rc, "bad frame geometry");
+  const JbOutPlan plan = jb_out_plan_(&desc, denom, spec);
+  if (plan.status != JB_OK) return jb_fail_(ctx, plan.status, plan.why);
   // the staging ring follows the frame (a context sized for another image, or created with (0,0))
-  rc = jb_ctx_reserve(ctx, (size_t)g.coef_bytes, (size_t)3 * out_w * out_h * es);
+  rc = jb_ctx_reserve(ctx, (size_t)g.coef_bytes, (size_t)plan.image_bytes);
   if (rc) return rc;
   int16_t *coef = (int16_t *)jb_pinned_alloc_on(jb_ctx_device(ctx), (size_t)g.coef_bytes);
   if (!coef) return jb_fail_(ctx, JB_ERR_HIP, jb_last_error(nullptr));
@@ -538,11 +508,9 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
   uint8_t *out = nullptr;
   if (rc) jb_fail_(ctx, rc, jb_last_error(nullptr));
   else {
-    out = jb_alloc_pixels_((size_t)3 * out_w * out_h * es);
+    out = jb_alloc_pixels_((size_t)plan.image_bytes);
     if (!out) rc = jb_fail_(ctx, JB_ERR_CAPACITY, "out of host memory");
-    else if (fmt) rc = jb_blocks_to_rgb_fmt_(ctx, &desc, coef, qtabs, out, (int64_t)es * out_w, 1, fmt);
-    else if (denom == 1) rc = jb_blocks_to_rgb(ctx, &desc, coef, qtabs, out, 3LL * desc.width);
-    else rc = jb_blocks_to_rgb_scaled_(ctx, &desc, coef, qtabs, out, 3LL * out_w, denom);
+    else rc = jb_blocks_to_rgb_plan_(ctx, &desc, coef, qtabs, out, plan);
   }
   jb_pinned_free(coef);
   if (rc) {
@@ -550,9 +518,44 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
     return rc;
   }
   *rgb = out;
-  *width = out_w;
-  *height = out_h;
+  *width = plan.out_w;
+  *height = plan.out_h;
   jb_ctx_set_last_desc_(ctx, &desc);
+  return JB_OK;
+}
+
+int jb_decode_memory(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, uint8_t **rgb, int32_t *width,
+                     int32_t *height) {
+  return decode_memory_impl(ctx, jpeg, jpeg_bytes, 1, nullptr, rgb, width, height);
+}
+
+// denom = 1: jb_decode_memory; 2, 4, 8: the same decode with the area-reduced store stage (include/jpegblk.h)
+int jb_decode_memory_scaled(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, int denom, uint8_t **rgb, int32_t *width,
+                            int32_t *height) {
+  return decode_memory_impl(ctx, jpeg, jpeg_bytes, denom, nullptr, rgb, width, height);
+}
+
+// the same decode in an output format ("tensor-ready output", include/jpegblk.h); format 0 is jb_decode_memory
+int jb_decode_memory_fmt(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, const jb_output_spec *spec, void **out,
+                         int32_t *width, int32_t *height) {
+  if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_memory_fmt: ctx is NULL");
+  if (!spec || !out) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_memory_fmt: NULL pointer");
+  *out = nullptr;
+  if (jb_output_spec_check(spec, 1, 1 << 20) != JB_OK || (spec->format != JB_FMT_RGB_U8_HWC && spec->plane_stride != 0))
+    return jb_fail_(ctx, JB_ERR_GEOMETRY, "jb_decode_memory_fmt: bad output spec (unknown format, reserved or plane_stride not 0, scale / bias not finite)");
+  return decode_memory_impl(ctx, jpeg, jpeg_bytes, 1, spec, (uint8_t **)out, width, height);
+}
+
+// the file's bytes; fn: the entry point's name, for the error text
+static int read_file(jb_ctx *ctx, const char *fn, const char *path, std::vector<uint8_t> &buf) {
+  if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, (std::string(fn) + ": ctx is NULL").c_str());
+  if (!path) return jb_fail_(ctx, JB_ERR_NULL, (std::string(fn) + ": path is NULL").c_str());
+  FILE *f = fopen(path, "rb");
+  if (!f) return jb_fail_(ctx, JB_ERR_FORMAT, (std::string("cannot open ") + path).c_str());
+  uint8_t chunk[1 << 16];
+  size_t got;
+  while ((got = fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + got);
+  fclose(f);
   return JB_OK;
 }
 
@@ -560,37 +563,18 @@ int jb_decode_file(jb_ctx *ctx, const char *path, uint8_t **rgb, int32_t *width,
   return jb_decode_file_scaled(ctx, path, 1, rgb, width, height);
 }
 
-static int read_file(jb_ctx *ctx, const char *path, std::vector<uint8_t> &buf) {
-  FILE *f = fopen(path, "rb");
-  if (!f) return jb_fail_(ctx, JB_ERR_FORMAT, (std::string("cannot open ") + path).c_str());
-  uint8_t chunk[1 << 16];
-  size_t got;
-  while ((got = fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + got);
-  fclose(f);
-  return JB_OK;
+int jb_decode_file_scaled(jb_ctx *ctx, const char *path, int denom, uint8_t **rgb, int32_t *width, int32_t *height) {
+  std::vector<uint8_t> buf;
+  const int rc = read_file(ctx, "jb_decode_file", path, buf);
+  return rc ? rc : decode_memory_impl(ctx, buf.data(), buf.size(), denom, nullptr, rgb, width, height);
 }
 
 int jb_decode_file_fmt(jb_ctx *ctx, const char *path, const jb_output_spec *spec, void **out, int32_t *width, int32_t *height) {
-  if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_file_fmt: ctx is NULL");
-  if (!path || !spec || !out) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_file_fmt: NULL pointer");
-  *out = nullptr;
+  if (ctx && (!spec || !out)) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_file_fmt: NULL pointer");
+  if (ctx) *out = nullptr;
   std::vector<uint8_t> buf;
-  const int rc = read_file(ctx, path, buf);
-  if (rc) return rc;
-  return jb_decode_memory_fmt(ctx, buf.data(), buf.size(), spec, out, width, height);
-}
-
-int jb_decode_file_scaled(jb_ctx *ctx, const char *path, int denom, uint8_t **rgb, int32_t *width, int32_t *height) {
-  if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_file: ctx is NULL");
-  if (!path) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_file: path is NULL");
-  FILE *f = fopen(path, "rb");
-  if (!f) return jb_fail_(ctx, JB_ERR_FORMAT, (std::string("cannot open ") + path).c_str());
-  std::vector<uint8_t> buf;
-  uint8_t chunk[1 << 16];
-  size_t got;
-  while ((got = fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + got);
-  fclose(f);
-  return jb_decode_memory_scaled(ctx, buf.data(), buf.size(), denom, rgb, width, height);
+  const int rc = read_file(ctx, "jb_decode_file_fmt", path, buf);
+  return rc ? rc : jb_decode_memory_fmt(ctx, buf.data(), buf.size(), spec, out, width, height);
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "../../include/jpegblk.h"
+#include "jb_plan.h"
 
 extern "C" {
 
@@ -38,16 +39,22 @@ int jb_scaled_size(int32_t width, int32_t height, int denom, int32_t *out_w, int
   return JB_OK;
 }
 
-// bytes per element of an output format (0: not a format); internal, shared by jb_api.cpp / jb_frontend.cpp / jb_batch.cpp
-int jb_format_esize_(int format) {
+// bytes per element of an output format (0: not a format)
+static int jb_format_esize_(int format) {
   return format == JB_FMT_RGB_U8_HWC || format == JB_FMT_RGB_U8_CHW ? 1 : format == JB_FMT_RGB_F32_CHW ? 4 : format == JB_FMT_RGB_F16_CHW ? 2 : 0;
 }
 
 int jb_output_bytes(int32_t width, int32_t height, int format, int64_t *bytes) {
   if (!bytes) return JB_ERR_NULL;
-  const int es = jb_format_esize_(format);
-  if (es == 0 || width < 1 || height < 1 || width > 65535 || height > 65535) return JB_ERR_GEOMETRY;
-  *bytes = 3LL * width * height * es;  // at most 3 * 65535^2 * 4 < 2^36
+  jb_image_desc d;
+  jb_output_spec s;
+  memset(&d, 0, sizeof d);
+  memset(&s, 0, sizeof s);
+  d.width = width, d.height = height;
+  s.format = format;
+  const JbOutPlan plan = jb_out_plan_(&d, 1, &s);  // an unknown format or a size outside 1..65535: JB_ERR_GEOMETRY
+  if (plan.status != JB_OK) return plan.status;
+  *bytes = plan.image_bytes;
   return JB_OK;
 }
 
@@ -79,3 +86,33 @@ int jb_resolve_qtabs(const jb_image_desc *d, const uint16_t *qtabs, int32_t *out
 }
 
 }  // extern "C"
+
+// jb_plan.h: the only place that turns (frame, scale, spec) into the output's sizes and strides
+JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *spec) {
+  JbOutPlan p;
+  memset(&p, 0, sizeof p);
+  auto refuse = [&p](int status, const char *why) {
+    p.status = status, p.why = why;
+    return p;
+  };
+  if (!d) return refuse(JB_ERR_NULL, "null descriptor");
+  int32_t out_w = 0, out_h = 0;
+  if (jb_scaled_size(d->width, d->height, scale, &out_w, &out_h) != JB_OK)
+    return refuse(JB_ERR_GEOMETRY, "scale is not 1, 2, 4 or 8 (or the image size is outside 1..65535)");
+  if (spec && spec->format == JB_FMT_RGB_U8_HWC) {
+    if (spec->reserved != 0) return refuse(JB_ERR_GEOMETRY, "output spec: reserved must be 0");
+    spec = nullptr;  // (the other fields are not looked at)
+  }
+  const int esize = spec ? jb_format_esize_(spec->format) : 1;
+  if (esize == 0) return refuse(JB_ERR_GEOMETRY, "unknown output format");
+  if (spec && scale != 1) return refuse(JB_ERR_UNSUPPORTED, "a planar output format cannot be combined with a scale");
+  p.why = "";
+  p.scale = scale;
+  p.out_w = out_w, p.out_h = out_h;
+  p.esize = esize;
+  p.planar = spec != nullptr;
+  if (spec) p.format = spec->format, p.spec = *spec;
+  p.row_stride = p.planar ? (int64_t)out_w * esize : 3LL * out_w;
+  p.image_bytes = 3LL * out_w * out_h * esize;  // at most 3 * 65535^2 * 4 < 2^36
+  return p;
+}

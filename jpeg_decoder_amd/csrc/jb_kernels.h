@@ -24,7 +24,7 @@ struct JbLaunch {
   int32_t reserved;           // 0 (777 = skip switch of the timing-experiment builds)
   int32_t staged;             // 1 (linear tiling only): the line-aligned store stage for rows that are not 64-byte aligned
   int32_t small_grid;         // 1: 4:4:4 and 4:2:0 only, one 64-lane workgroup per jbk_small_mcus() MCUs of an MCU row (row-bound)
-  // jbk_launch_fmt only (planar output; every other launch leaves these 0): rgb_row_stride is then the bytes between
+  // planar output only (format != 0; every other launch leaves these 0): rgb_row_stride is then the bytes between
   // the rows of ONE plane, rgb_plane_stride the bytes between the R, G and B planes of an image
   int32_t format;             // JB_FMT_* of include/jpegblk.h
   int64_t rgb_plane_stride;   // bytes
@@ -37,16 +37,15 @@ int jbk_mcus_per_tile(int hs, int vs);
 int jbk_small_mcus(int hs, int vs);
 // Can the layout use the linear (MCU-stream) tiling for an image with mcus_x MCUs per row?
 int jbk_linear_ok(int hs, int vs, int mcus_x);
-// Launch the fused kernel for luma sampling (hs, vs): one 192-lane workgroup per tile.
-hipError_t jbk_launch(const JbLaunch &p, int hs, int vs, hipStream_t stream);
+// Launch the fused kernel for luma sampling (hs, vs): one 192-lane workgroup per tile, or (p.small_grid) one 64-lane
+// workgroup per jbk_small_mcus() MCUs.  scale 2, 4 or 8: the same kernel with an area-reduced store stage -- p.width /
+// p.height are the full image's, p.rgb and its strides describe the ceil(W/scale) x ceil(H/scale) output.  p.format =
+// JB_FMT_RGB_U8_CHW / _F32_CHW / _F16_CHW: the same kernel with a planar store stage -- p.rgb, p.rgb_row_stride,
+// p.rgb_plane_stride and p.rgb_image_stride describe three planes of p.height rows of p.width elements per image,
+// p.scale / p.bias the float formats' affine map.  Either exists in the row-bound tiling only (p.linear = p.small_grid
+// = 0) and not together: anything else is hipErrorInvalidValue.
+hipError_t jbk_launch(const JbLaunch &p, int hs, int vs, int scale, hipStream_t stream);
 const char *jbk_kernel_name(int hs, int vs);
-// The same kernel with an area-reduced store stage (scale 2, 4 or 8; row-bound tiling: p.linear = p.small_grid = 0):
-// p.width / p.height are the full image's, p.rgb and its strides describe the ceil(W/scale) x ceil(H/scale) output.
-hipError_t jbk_launch_scaled(const JbLaunch &p, int hs, int vs, int scale, hipStream_t stream);
-// The same kernel with a planar store stage (p.format = JB_FMT_RGB_U8_CHW / _F32_CHW / _F16_CHW; row-bound tiling:
-// p.linear = p.small_grid = 0): p.rgb, p.rgb_row_stride, p.rgb_plane_stride and p.rgb_image_stride describe three planes
-// of p.height rows of p.width elements per image; p.scale / p.bias the float formats' affine map.
-hipError_t jbk_launch_fmt(const JbLaunch &p, int hs, int vs, hipStream_t stream);
 
 // Device-side entropy decoder (jb_huff.hip); structures in jb_huff.h.
 struct JbHuffLaunch;

@@ -277,11 +277,11 @@ struct LaneMap {
 // it was meant for it is 1-3 % slower than the stores it replaces, and 4-10 % slower on aligned rows
 // (profiles/r03/probe_staged.json): the aligned lines are worth about 5 %, the second trip
 // through LDS and the serial pack-then-copy of a row per wave cost more.
-// SCALE = 2, 4, 8 (row-bound tiling only): the area-reduced output of jbk_launch_scaled -- stages 1 and 2 and the
+// SCALE = 2, 4, 8 (row-bound tiling only): the area-reduced output (jbk_launch with a scale) -- stages 1 and 2 and the
 // colour transform and u8 conversion of every pixel are those of SCALE = 1; only what is stored differs (see
 // "scaled" below).  p.width / p.height stay the full image's; p.rgb and its strides describe the reduced image.
-// FORMAT = 1, 2, 3 (JB_FMT_RGB_U8_CHW, _F32_CHW, _F16_CHW; row-bound tiling only, SCALE = 1): the planar output of
-// jbk_launch_fmt -- again only what is stored differs (see "planar" below): the u8 values are those of FORMAT = 0.
+// FORMAT = 1, 2, 3 (JB_FMT_RGB_U8_CHW, _F32_CHW, _F16_CHW; row-bound tiling only, SCALE = 1): the planar output
+// (jbk_launch with p.format set) -- again only what is stored differs (see "planar" below): the u8 values are those of FORMAT = 0.
 template <int HS, int VS, bool MIXQ, bool LINEAR, bool STAGED = false, int SCALE = 1, int FORMAT = 0>
 // (5 waves/SIMD are asked for where that costs no spill: 4:4:4 and 4:4:0; forcing it on 4:2:0 or
 // 4:2:2 spills and measured 9 % slower; the scaled 4:4:0 instantiations spill at 5 too)
@@ -1299,95 +1299,52 @@ __global__ __launch_bounds__(64) void jb_small_kernel_16(const JbLaunch p) {
   }
 }
 
-template <int HS, int VS>
-static hipError_t launch_t(const JbLaunch &p, hipStream_t stream) {
+// Launches jb_tile_kernel<HS, VS, MIXQ, LINEAR, STAGED, SCALE, FORMAT>: every launch of the 192-lane kernel goes through
+// here.  SCALE != 1 (the area-reduced store stage) and FORMAT != 0 (the planar one) exist in the row-bound tiling only.
+// MIXQ is decided here, and MIXQ = true is only instantiated for a layout that can need it.
+template <int HS, int VS, int SCALE, int FORMAT, bool LINEAR = false, bool STAGED = false>
+static hipError_t launch_tile(const JbLaunch &p, hipStream_t stream) {
   using LM = LaneMap<HS, VS>;
   // does any wave hold two components whose tables may differ?
   constexpr bool kLumaChromaMixed = (LM::NYT % 64 != 0);                      // no layout any more (see tile_blocks)
   constexpr bool kCbCrMixed = (LM::MCUS % 64 != 0);                           // 4:2:0: Cb and Cr share the third wave
-  const bool mixq = kLumaChromaMixed || (kCbCrMixed && !p.chroma_q_equal);
-  // the linear tiling is a separate instantiation: where the row-bound tiling leaves no tile
-  // ragged (mcus_x a multiple of the tile length, e.g. 4096- and 8192-pixel rows) the simpler
-  // row-bound code is 2 % faster
-  constexpr bool kCanLinear = ((LM::MCUS * 8 * HS / 4) % 64 == 0);
   const dim3 grid(p.n_tiles), block(LM::TB);
   // hipGetLastError below must report THIS launch: an error left in the thread's error slot by an
   // unrelated earlier call (a failed attribute query, say) is not this launch's
   (void)hipGetLastError();
-  constexpr unsigned extra_lds = 0;
-#if defined(JB_LAB)
-  if (kCanLinear && p.linear && p.staged) {
-    if (mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, true, kCanLinear, kCanLinear>), grid, block, extra_lds, stream, p);
-    else hipLaunchKernelGGL((jb_tile_kernel<HS, VS, false, kCanLinear, kCanLinear>), grid, block, extra_lds, stream, p);
-  } else
-#endif
-  if (kCanLinear && p.linear) {
-    if (mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, true, kCanLinear>), grid, block, extra_lds, stream, p);
-    else hipLaunchKernelGGL((jb_tile_kernel<HS, VS, false, kCanLinear>), grid, block, extra_lds, stream, p);
-  } else {
-    if (mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, true, false>), grid, block, extra_lds, stream, p);
-    else hipLaunchKernelGGL((jb_tile_kernel<HS, VS, false, false>), grid, block, extra_lds, stream, p);
+  bool mixq = false;
+  if constexpr (kLumaChromaMixed || kCbCrMixed) {
+    mixq = kLumaChromaMixed || !p.chroma_q_equal;
+    if (mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, true, LINEAR, STAGED, SCALE, FORMAT>), grid, block, 0, stream, p);
   }
+  if (!mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, false, LINEAR, STAGED, SCALE, FORMAT>), grid, block, 0, stream, p);
   return hipGetLastError();
 }
 
-// the area-reduced output (jbk_launch_scaled): the row-bound instantiation with the scaled store stage
-template <int HS, int VS, int SCALE>
-static hipError_t launch_scaled_t(const JbLaunch &p, hipStream_t stream) {
-  using LM = LaneMap<HS, VS>;
-  const bool mixq = (LM::MCUS % 64 != 0) && !p.chroma_q_equal;  // as launch_t: 4:2:0 whose Cb and Cr tables differ
-  const dim3 grid(p.n_tiles), block(LM::TB);
-  (void)hipGetLastError();
-  if (mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, true, false, false, SCALE>), grid, block, 0, stream, p);
-  else hipLaunchKernelGGL((jb_tile_kernel<HS, VS, false, false, false, SCALE>), grid, block, 0, stream, p);
-  return hipGetLastError();
-}
-
-template <int SCALE>
-static hipError_t launch_scaled_k(const JbLaunch &p, int hs, int vs, hipStream_t stream) {
-  if (hs == 1 && vs == 1) return launch_scaled_t<1, 1, SCALE>(p, stream);
-  if (hs == 2 && vs == 1) return launch_scaled_t<2, 1, SCALE>(p, stream);
-  if (hs == 1 && vs == 2) return launch_scaled_t<1, 2, SCALE>(p, stream);
-  if (hs == 2 && vs == 2) return launch_scaled_t<2, 2, SCALE>(p, stream);
-  return hipErrorInvalidValue;
-}
-
-hipError_t jbk_launch_scaled(const JbLaunch &p, int hs, int vs, int scale, hipStream_t stream) {
-  if (p.n_tiles <= 0) return hipSuccess;
-  if (p.linear || p.small_grid) return hipErrorInvalidValue;  // (row-bound tiling only)
-  if (scale == 2) return launch_scaled_k<2>(p, hs, vs, stream);
-  if (scale == 4) return launch_scaled_k<4>(p, hs, vs, stream);
-  if (scale == 8) return launch_scaled_k<8>(p, hs, vs, stream);
-  return hipErrorInvalidValue;
-}
-
-// the planar output (jbk_launch_fmt): the row-bound instantiation with the planar store stage
-template <int HS, int VS, int FORMAT>
-static hipError_t launch_fmt_t(const JbLaunch &p, hipStream_t stream) {
-  using LM = LaneMap<HS, VS>;
-  const bool mixq = (LM::MCUS % 64 != 0) && !p.chroma_q_equal;  // as launch_t: 4:2:0 whose Cb and Cr tables differ
-  const dim3 grid(p.n_tiles), block(LM::TB);
-  (void)hipGetLastError();
-  if (mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, true, false, false, 1, FORMAT>), grid, block, 0, stream, p);
-  else hipLaunchKernelGGL((jb_tile_kernel<HS, VS, false, false, false, 1, FORMAT>), grid, block, 0, stream, p);
-  return hipGetLastError();
-}
-
-template <int FORMAT>
-static hipError_t launch_fmt_k(const JbLaunch &p, int hs, int vs, hipStream_t stream) {
-  if (hs == 1 && vs == 1) return launch_fmt_t<1, 1, FORMAT>(p, stream);
-  if (hs == 2 && vs == 1) return launch_fmt_t<2, 1, FORMAT>(p, stream);
-  if (hs == 1 && vs == 2) return launch_fmt_t<1, 2, FORMAT>(p, stream);
-  if (hs == 2 && vs == 2) return launch_fmt_t<2, 2, FORMAT>(p, stream);
-  return hipErrorInvalidValue;
-}
-
-hipError_t jbk_launch_fmt(const JbLaunch &p, int hs, int vs, hipStream_t stream) {
-  if (p.n_tiles <= 0) return hipSuccess;
-  if (p.linear || p.small_grid) return hipErrorInvalidValue;  // (row-bound tiling only)
-  if (p.format == 1) return launch_fmt_k<1>(p, hs, vs, stream);
-  if (p.format == 2) return launch_fmt_k<2>(p, hs, vs, stream);
-  if (p.format == 3) return launch_fmt_k<3>(p, hs, vs, stream);
+// one layout: which store stage (scale, p.format) and which tiling (p.linear, p.staged)
+template <int HS, int VS>
+static hipError_t launch_layout(const JbLaunch &p, int scale, hipStream_t stream) {
+  if (p.format == 0 && scale == 1) {
+    // the linear tiling is a separate instantiation: where the row-bound tiling leaves no tile
+    // ragged (mcus_x a multiple of the tile length, e.g. 4096- and 8192-pixel rows) the simpler
+    // row-bound code is 2 % faster
+    constexpr bool kCanLinear = ((LaneMap<HS, VS>::MCUS * 8 * HS / 4) % 64 == 0);
+#if defined(JB_LAB)
+    if (kCanLinear && p.linear && p.staged) return launch_tile<HS, VS, 1, 0, kCanLinear, kCanLinear>(p, stream);
+#endif
+    if (kCanLinear && p.linear) return launch_tile<HS, VS, 1, 0, kCanLinear>(p, stream);
+    return launch_tile<HS, VS, 1, 0>(p, stream);
+  }
+  if (p.linear) return hipErrorInvalidValue;  // (row-bound tiling only)
+  if (p.format == 0) {  // the area-reduced output
+    if (scale == 2) return launch_tile<HS, VS, 2, 0>(p, stream);
+    if (scale == 4) return launch_tile<HS, VS, 4, 0>(p, stream);
+    if (scale == 8) return launch_tile<HS, VS, 8, 0>(p, stream);
+  } else if (scale == 1) {  // the planar output
+    if (p.format == 1) return launch_tile<HS, VS, 1, 1>(p, stream);
+    if (p.format == 2) return launch_tile<HS, VS, 1, 2>(p, stream);
+    if (p.format == 3) return launch_tile<HS, VS, 1, 3>(p, stream);
+  }
   return hipErrorInvalidValue;
 }
 
@@ -1403,10 +1360,10 @@ int jbk_linear_ok(int hs, int vs, int mcus_x) {
 
 int jbk_small_mcus(int hs, int vs) { return hs == 1 && vs == 1 ? kSmallMcus : hs == 2 && vs == 2 ? kSmallMcus420 : 16; }
 
-hipError_t jbk_launch(const JbLaunch &p, int hs, int vs, hipStream_t stream) {
+hipError_t jbk_launch(const JbLaunch &p, int hs, int vs, int scale, hipStream_t stream) {
   if (p.n_tiles <= 0) return hipSuccess;
   if (p.small_grid) {  // (the host sets it with the tile counts of this tiling)
-    if (jbk_small_mcus(hs, vs) == 0) return hipErrorInvalidValue;
+    if (jbk_small_mcus(hs, vs) == 0 || scale != 1 || p.format != 0) return hipErrorInvalidValue;
     (void)hipGetLastError();
     if (hs == 1 && vs == 1) hipLaunchKernelGGL(jb_small_kernel_444, dim3(p.n_tiles), dim3(64), 0, stream, p);
     else if (hs == 2 && vs == 2) hipLaunchKernelGGL(jb_small_kernel_420, dim3(p.n_tiles), dim3(64), 0, stream, p);
@@ -1414,10 +1371,10 @@ hipError_t jbk_launch(const JbLaunch &p, int hs, int vs, hipStream_t stream) {
     else hipLaunchKernelGGL((jb_small_kernel_16<1, 2>), dim3(p.n_tiles), dim3(64), 0, stream, p);
     return hipGetLastError();
   }
-  if (hs == 1 && vs == 1) return launch_t<1, 1>(p, stream);
-  if (hs == 2 && vs == 1) return launch_t<2, 1>(p, stream);
-  if (hs == 1 && vs == 2) return launch_t<1, 2>(p, stream);
-  if (hs == 2 && vs == 2) return launch_t<2, 2>(p, stream);
+  if (hs == 1 && vs == 1) return launch_layout<1, 1>(p, scale, stream);
+  if (hs == 2 && vs == 1) return launch_layout<2, 1>(p, scale, stream);
+  if (hs == 1 && vs == 2) return launch_layout<1, 2>(p, scale, stream);
+  if (hs == 2 && vs == 2) return launch_layout<2, 2>(p, scale, stream);
   return hipErrorInvalidValue;
 }
 

@@ -4,7 +4,7 @@
 // read or write out of bounds, overflow, loop forever or abort (the reference exit(1)s or reads
 // past its buffers on such input, jpeg.cpp:886-907, file.hpp:59-104).
 //
-//   make -C tools/fuzz && tools/fuzz/fuzz_frontend <seconds> <seed> file.jpg [file.jpg ...]
+//   make -C tools/fuzz && tools/fuzz/fuzz_frontend <CPU seconds> <seed> file.jpg [file.jpg ...]
 //
 // Seeds: the given files plus streams from the build's own writer (all layouts, restart
 // intervals, 16-bit tables).  The device side is stubbed; only the host code is under test.
@@ -13,12 +13,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <ctime>
 #include <string>
 #include <vector>
 
 #include "../../include/jpegblk.h"
 #include "../../jpeg_decoder_amd/csrc/jb_huff.h"
 #include "../../jpeg_decoder_amd/csrc/jb_knobs.h"
+#include "../../jpeg_decoder_amd/csrc/jb_plan.h"
 
 extern "C" long jw_encode_ex(const int16_t *coef, int width, int height, int hs, int vs, const uint16_t *qtabs,
                              const int *qtab_id, const uint8_t *dht, int restart_interval, int dqt16, int scan_mode,
@@ -42,15 +44,11 @@ void *jb_pinned_alloc(size_t n) { return malloc(n); }
 void *jb_pinned_alloc_on(int, size_t n) { return malloc(n); }
 int jb_ctx_reserve(jb_ctx *, size_t, size_t) { return JB_OK; }
 int jb_ctx_device(const jb_ctx *) { return 0; }
-struct JbHuffJob;
-int jb_decode_job_(jb_ctx *, const JbHuffJob *, uint8_t *, int64_t) { return JB_OK; }
 void jb_pinned_free(void *p) { free(p); }
 void jb_free(void *p) { free(p); }
-int jb_blocks_to_rgb(jb_ctx *, const jb_image_desc *, const int16_t *, const uint16_t *, uint8_t *, int64_t) { return JB_OK; }
-int jb_decode_job_scaled_(jb_ctx *, const JbHuffJob *, uint8_t *, int64_t, int) { return JB_OK; }
-int jb_blocks_to_rgb_scaled_(jb_ctx *, const jb_image_desc *, const int16_t *, const uint16_t *, uint8_t *, int64_t, int) { return JB_OK; }
-int jb_decode_job_fmt_(jb_ctx *, const JbHuffJob *, uint8_t *, int64_t, int, const jb_output_spec *) { return JB_OK; }
-int jb_blocks_to_rgb_fmt_(jb_ctx *, const jb_image_desc *, const int16_t *, const uint16_t *, uint8_t *, int64_t, int, const jb_output_spec *) { return JB_OK; }
+// the two routes of decode(bytes) into the pixel kernel
+int jb_decode_job_(jb_ctx *, const JbHuffJob *, uint8_t *, const JbOutPlan &) { return JB_OK; }
+int jb_blocks_to_rgb_plan_(jb_ctx *, const jb_image_desc *, const int16_t *, const uint16_t *, uint8_t *, const JbOutPlan &) { return JB_OK; }
 }
 
 static uint64_t rng_state = 88172645463325252ull;
@@ -199,10 +197,18 @@ int main(int argc, char **argv) {
       return 1;
     }
   }
+  // <seconds> is CPU time of this process, so that a run does the same work on a busy machine as on an idle one (a
+  // wall-clock budget does less work the busier the machine is); eight times that in wall time ends it too
   const auto t0 = std::chrono::steady_clock::now();
+  const auto cpu_s = [] {
+    timespec ts;
+    clock_gettime(CLOCK_PROCESS_CPUTIME_ID, &ts);
+    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+  };
+  const double cpu0 = cpu_s();
   long iters = 0, ok = 0, counts[16] = {0};
   std::vector<int16_t> coef;
-  while (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < budget) {
+  while (cpu_s() - cpu0 < budget && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < 8 * budget) {
     std::vector<uint8_t> d = seeds[rnd() % seeds.size()];
     mutate(d);
     prepare_once(d);
