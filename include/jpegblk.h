@@ -214,7 +214,8 @@ int jb_blocks_to_rgb_device(jb_ctx *ctx, const jb_device_batch *batch, void *str
 int jb_resolve_qtabs(const jb_image_desc *desc, const uint16_t *qtabs, int32_t *out192);
 /* Name of the kernel jb_blocks_to_rgb_device launches for this descriptor (for profilers): the 192 / 256-lane
  * kernel of the layout.  Launches of up to 8 of its workgroups per CU (one to four 1080p images, one 4096x4096
- * 4:2:0) run as jb_small_kernel_444 / _420 / _16<2,1> / _16<1,2> instead (JPEGBLK_SMALL_GRID). */
+ * 4:2:0) run as jb_small_kernel_444 / _420 / _16<2,1> / _16<1,2> instead (JPEGBLK_SMALL_GRID): four entry points
+ * of one kernel body, one per layout. */
 const char *jb_kernel_name(const jb_image_desc *desc);
 
 /* ---- scaled output: decode at 1/2, 1/4 or 1/8 size ---------------------------------------

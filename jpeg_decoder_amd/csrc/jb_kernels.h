@@ -23,7 +23,7 @@ struct JbLaunch {
   int32_t chroma_q_equal;     // 1 when Cb and Cr use the same table (desc.qtab_id[1] == qtab_id[2])
   int32_t reserved;           // 0 (777 = skip switch of the timing-experiment builds)
   int32_t staged;             // 1 (linear tiling only): the line-aligned store stage for rows that are not 64-byte aligned
-  int32_t small_grid;         // 1: 4:4:4 and 4:2:0 only, one 64-lane workgroup per jbk_small_mcus() MCUs of an MCU row (row-bound)
+  int32_t small_grid;         // 1: every layout, one 64-lane workgroup per jbk_small_mcus() MCUs of an MCU row (row-bound)
   // planar output only (format != 0; every other launch leaves these 0): rgb_row_stride is then the bytes between
   // the rows of ONE plane, rgb_plane_stride the bytes between the R, G and B planes of an image
   int32_t format;             // JB_FMT_* of include/jpegblk.h
@@ -31,9 +31,9 @@ struct JbLaunch {
   float scale[3], bias[3];    // float formats: value = (float)u8 * scale[c] + bias[c]
 };
 
-// MCUs covered by one workgroup (a tile is always 192 coded blocks): 64 / 48 / 32.
+// MCUs covered by one workgroup (a tile is 192 coded blocks in 4:4:4 and 4:2:0, 256 in 4:2:2 and 4:4:0): 64 / 32 / 64 / 64.
 int jbk_mcus_per_tile(int hs, int vs);
-// MCUs per workgroup of the small-grid kernels (4:4:4: 16, 4:2:0: 8; 0: the layout has none)
+// MCUs per workgroup of the small-grid kernels (4:2:0: 8, every other layout: 16; never 0)
 int jbk_small_mcus(int hs, int vs);
 // Can the layout use the linear (MCU-stream) tiling for an image with mcus_x MCUs per row?
 int jbk_linear_ok(int hs, int vs, int mcus_x);

@@ -39,6 +39,10 @@
 //     5 workgroups of 4 waves for the 256-lane tiles); the 3
 //     workgroup barriers per tile order LDS traffic only (s_waitcnt lgkmcnt(0); s_barrier).
 //
+// Layout of this file: the stage helpers (dequantise, IDCT passes, chroma read, colour, packs, byte store); LaneMap and
+// jb_tile_kernel, the kernel described above; SmallMap and jb_small_body, the same stages as ONE 64-lane body for small
+// launches, with its four entry points jb_small_kernel_444 / _420 / _16<2,1> / _16<1,2>; the launchers.
+//
 // Arithmetic is bit-exact with the reference: int32 dequantise (v_mul_i32_i24), the AAN graph
 // of jpeg.cpp:598-662 evaluated in the same order with separate IEEE mul/add (this TU is built
 // with -ffp-contract=off), truncation toward zero after each 1-D pass (v_trunc_f32: equal to the
@@ -92,7 +96,6 @@ __device__ __forceinline__ float kf(uint32_t bits) { return __builtin_bit_cast(f
 #undef JB_STORE_AUX
 #define JB_STORE_AUX 2
 #endif
-#define JB_SCHED_FENCE() ((void)0)
 // Coded blocks per tile = lanes per workgroup: the smallest whole number of MCUs that fills whole
 // waves with ONE component each.  4:4:4 (3 blocks per MCU) and 4:2:0 (6): 192 lanes = 64 / 32 MCUs
 // (in 4:2:0 Cb and Cr share the third wave).  4:2:2 and 4:4:0 (4 blocks per MCU): 256 lanes = 64
@@ -218,6 +221,97 @@ typedef uint32_t u32x3_t __attribute__((ext_vector_type(3)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef u32x4_t u32x4_u __attribute__((aligned(1)));  // 16 bytes at any byte address
 
+
+// ---- the stages the kernels below are written with ----
+// jb_tile_kernel's register allocation sits at the edge, and hipcc schedules it differently as soon as one of its
+// arrays (raw, v, yy / r / g / b together) goes through a helper by reference, although every helper is inlined: there
+// it calls the helpers that take values, or the chroma arrays alone, and keeps its loops over raw[] and v[] in place
+// (instruction-identical to the code before the helpers existed: profiles/r07/isa_diff_existing_kernels.txt).  The
+// small-grid body uses all of them.
+
+// One coded block (eight 16-byte chunks at src) -> raw: row k = dwords 4k..4k+3, two int16 (columns 2j, 2j+1) per dword
+__device__ __forceinline__ void load_block(const u32x4_t *src, uint32_t (&raw)[32]) {
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    const u32x4_t t = src[j];
+    raw[j * 4 + 0] = t.x, raw[j * 4 + 1] = t.y, raw[j * 4 + 2] = t.z, raw[j * 4 + 3] = t.w;
+  }
+}
+
+// dequantise (jpeg.cpp:563-569) column i of a row, from the dword w that holds it: int32 product (v_mul_i32_i24),
+// int->float on first use (jpeg.cpp:598)
+__device__ __forceinline__ float dequant1(uint32_t w, int i, int q) {
+  const int c = (i & 1) ? ((int)w >> 16) : (int)(short)(w & 0xffffu);
+  return (float)__mul24(c, q);
+}
+// a whole block with the table at q (a lane of the small-grid kernels reads it from LDS, four entries per ds_read_b128)
+__device__ __forceinline__ void dequantise(const uint32_t (&raw)[32], float (&v)[64], const int32_t *q) {
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+#pragma unroll
+    for (int i = 0; i < 8; i += 4) {
+      const int4 q4 = *(const int4 *)(q + k * 8 + i);
+      const int qq[4] = {q4.x, q4.y, q4.z, q4.w};
+#pragma unroll
+      for (int e = 0; e < 4; e++) v[k * 8 + i + e] = dequant1(raw[k * 4 + ((i + e) >> 1)], i + e, qq[e]);
+    }
+  }
+}
+
+// column pass, jpeg.cpp:596-663.  PERM: output row k goes to register row sigma(k), sigma = (0 1 4 5 2 3 6 7).
+template <bool PERM = false>
+__device__ __forceinline__ void idct_cols(float (&v)[64]) {
+#pragma unroll
+  for (int i = 0; i < 8; i++)
+    aan_1d_io(v[0 * 8 + i], v[1 * 8 + i], v[2 * 8 + i], v[3 * 8 + i], v[4 * 8 + i], v[5 * 8 + i], v[6 * 8 + i], v[7 * 8 + i],
+              v[0 * 8 + i], v[1 * 8 + i], v[(PERM ? 4 : 2) * 8 + i], v[(PERM ? 5 : 3) * 8 + i], v[(PERM ? 2 : 4) * 8 + i],
+              v[(PERM ? 3 : 5) * 8 + i], v[6 * 8 + i], v[7 * 8 + i]);
+}
+// row pass, jpeg.cpp:664-731
+__device__ __forceinline__ void idct_rows(float (&v)[64]) {
+#pragma unroll
+  for (int k = 0; k < 8; k++)
+    aan_1d(v[k * 8 + 0], v[k * 8 + 1], v[k * 8 + 2], v[k * 8 + 3], v[k * 8 + 4], v[k * 8 + 5], v[k * 8 + 6], v[k * 8 + 7]);
+}
+__device__ __forceinline__ void idct_8x8(float (&v)[64]) { idct_cols(v), idct_rows(v); }
+
+// The chroma of four adjacent luma samples from the strips: the chroma sample of luma pixel (row, col) is
+// (row/VS, col/HS) -- reference jpeg.cpp:518-520 -- so HS = 2 reads two samples and gives each to two pixels.
+template <int HS>
+__device__ __forceinline__ void load_chroma4(const char *pb, const char *pr, float (&cb)[4], float (&cr)[4]) {
+  if (HS == 1) {
+    const float4 a = *(const float4 *)pb;
+    const float4 b = *(const float4 *)pr;
+    cb[0] = a.x, cb[1] = a.y, cb[2] = a.z, cb[3] = a.w;
+    cr[0] = b.x, cr[1] = b.y, cr[2] = b.z, cr[3] = b.w;
+  } else {
+    const float2 a = *(const float2 *)pb;
+    const float2 b = *(const float2 *)pr;
+    cb[0] = cb[1] = a.x, cb[2] = cb[3] = a.y;
+    cr[0] = cr[1] = b.x, cr[2] = cr[3] = b.y;
+  }
+}
+
+// colour transform of one pixel, jpeg.cpp:521-535 (floats before truncation)
+__device__ __forceinline__ void ycc_px(float y, float cb, float cr, float &r, float &g, float &b) {
+  r = (y + JB_CR_R * cr) + 128.0f;
+  g = ((y - JB_CB_G * cb) - JB_CR_G * cr) + 128.0f;
+  b = (y + JB_CB_B * cb) + 128.0f;
+}
+
+// The full-size conversion with its operands permuted: pack12_rtz writes bytes in the order r0 g0 b0 r1 | g1 b1 r2 g2 |
+// b2 r3 g3 b3, so these arguments give ONE word per channel -- w[c] = the u8 samples of channel c, pixels 0..3.
+__device__ __forceinline__ void pack_channels(const float (&r)[4], const float (&g)[4], const float (&b)[4], uint32_t (&w)[3]) {
+  const float pr[4] = {r[0], r[3], g[2], b[1]}, pg[4] = {r[1], g[0], g[3], b[2]}, pb[4] = {r[2], g[1], b[0], b[3]};
+  pack12_rtz(pr, pg, pb, w[0], w[1], w[2]);
+}
+
+// one pixel through three byte stores
+__device__ __forceinline__ void store_px_bytes(uint8_t *o, float r, float g, float b) {
+  o[0] = (uint8_t)pack_u8(r, 0, 0);
+  o[1] = (uint8_t)pack_u8(g, 0, 0);
+  o[2] = (uint8_t)pack_u8(b, 0, 0);
+}
 
 // Measurement variants (tools/ablate.sh through tools/build_variant.sh -DJB_LAB -DJB_EXP_NO_...): a stage is
 // skipped at run time through a condition the compiler cannot fold, so the code and its registers stay.  The
@@ -412,9 +506,7 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
       for (int k = 0; k < 8; k++) {
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-          const uint32_t w = raw[k * 4 + (i >> 1)];
-          const int c = (i & 1) ? ((int)w >> 16) : (int)(short)(w & 0xffffu);
-          v[k * 8 + i] = (float)__mul24(c, qa[k * 8 + i]);
+          v[k * 8 + i] = dequant1(raw[k * 4 + (i >> 1)], i, qa[k * 8 + i]);
         }
       }
     } else {
@@ -423,12 +515,10 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
       for (int k = 0; k < 8; k++) {
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-          const uint32_t w = raw[k * 4 + (i >> 1)];
-          const int c = (i & 1) ? ((int)w >> 16) : (int)(short)(w & 0xffffu);
           // both entries through scalar loads, then a per-lane select (v_cndmask)
           const int q0 = __builtin_amdgcn_readfirstlane(qa[k * 8 + i]);
           const int q1 = __builtin_amdgcn_readfirstlane(qb[k * 8 + i]);
-          v[k * 8 + i] = (float)__mul24(c, second ? q1 : q0);
+          v[k * 8 + i] = dequant1(raw[k * 4 + (i >> 1)], i, second ? q1 : q0);
         }
       }
     }
@@ -445,17 +535,17 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
       aan_1d_io(v[0 * 8 + i], v[1 * 8 + i], v[2 * 8 + i], v[3 * 8 + i], v[4 * 8 + i], v[5 * 8 + i],
                 v[6 * 8 + i], v[7 * 8 + i],  //
                 v[0 * 8 + i], v[1 * 8 + i], v[4 * 8 + i], v[5 * 8 + i], v[2 * 8 + i], v[3 * 8 + i],
-                v[6 * 8 + i], v[7 * 8 + i]), JB_SCHED_FENCE();
+                v[6 * 8 + i], v[7 * 8 + i]);
   } else {
 #pragma unroll
     for (int i = 0; i < 8; i++)  // column pass, jpeg.cpp:596-663
       aan_1d(v[0 * 8 + i], v[1 * 8 + i], v[2 * 8 + i], v[3 * 8 + i], v[4 * 8 + i], v[5 * 8 + i],
-             v[6 * 8 + i], v[7 * 8 + i]), JB_SCHED_FENCE();
+             v[6 * 8 + i], v[7 * 8 + i]);
   }
 #pragma unroll
   for (int k = 0; k < 8; k++)  // row pass, jpeg.cpp:664-731
     aan_1d(v[k * 8 + 0], v[k * 8 + 1], v[k * 8 + 2], v[k * 8 + 3], v[k * 8 + 4], v[k * 8 + 5],
-           v[k * 8 + 6], v[k * 8 + 7]), JB_SCHED_FENCE();
+           v[k * 8 + 6], v[k * 8 + 7]);
   }
 
   // ---- stage 3: two phases (upper / lower half of the tile's pixel rows) ----
@@ -529,24 +619,12 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
           const float4 Y = *(const float4 *)(rowp + lane_y_off + seg * 1024);
           float cb[4], cr[4];
           const int coff = (row / VS) * (CW * 4) + seg * (1024 / HS);
-          if (HS == 1) {
-            const float4 a = *(const float4 *)(lds + CB_OFF + lane_c_off + coff);
-            const float4 b = *(const float4 *)(lds + CR_OFF + lane_c_off + coff);
-            cb[0] = a.x, cb[1] = a.y, cb[2] = a.z, cb[3] = a.w;
-            cr[0] = b.x, cr[1] = b.y, cr[2] = b.z, cr[3] = b.w;
-          } else {
-            const float2 a = *(const float2 *)(lds + CB_OFF + lane_c_off + coff);
-            const float2 b = *(const float2 *)(lds + CR_OFF + lane_c_off + coff);
-            cb[0] = cb[1] = a.x, cb[2] = cb[3] = a.y;
-            cr[0] = cr[1] = b.x, cr[2] = cr[3] = b.y;
-          }
+          load_chroma4<HS>(lds + CB_OFF + lane_c_off + coff, lds + CR_OFF + lane_c_off + coff, cb, cr);
           const float yy[4] = {Y.x, Y.y, Y.z, Y.w};
           float r[4], g[4], b[4];
 #pragma unroll
           for (int i = 0; i < 4; i++) {
-            r[i] = (yy[i] + JB_CR_R * cr[i]) + 128.0f;
-            g[i] = ((yy[i] - JB_CB_G * cb[i]) - JB_CR_G * cr[i]) + 128.0f;
-            b[i] = (yy[i] + JB_CB_B * cb[i]) + 128.0f;
+            ycc_px(yy[i], cb[i], cr[i], r[i], g[i], b[i]);
           }
           uint32_t w0, w1, w2;
           pack12_rtz(r, g, b, w0, w1, w2);
@@ -623,30 +701,17 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
           const float4 Y = *(const float4 *)(lds + lane_y_off + row * (YW * 4) + seg * 1024);
           float cb[4], cr[4];
           const int coff = (row / VS) * (CW * 4) + seg * (1024 / HS);
-          if (HS == 1) {
-            const float4 a = *(const float4 *)(lds + CB_OFF + lane_c_off + coff);
-            const float4 b = *(const float4 *)(lds + CR_OFF + lane_c_off + coff);
-            cb[0] = a.x, cb[1] = a.y, cb[2] = a.z, cb[3] = a.w;
-            cr[0] = b.x, cr[1] = b.y, cr[2] = b.z, cr[3] = b.w;
-          } else {
-            const float2 a = *(const float2 *)(lds + CB_OFF + lane_c_off + coff);
-            const float2 b = *(const float2 *)(lds + CR_OFF + lane_c_off + coff);
-            cb[0] = cb[1] = a.x, cb[2] = cb[3] = a.y;
-            cr[0] = cr[1] = b.x, cr[2] = cr[3] = b.y;
-          }
+          load_chroma4<HS>(lds + CB_OFF + lane_c_off + coff, lds + CR_OFF + lane_c_off + coff, cb, cr);
           const float yy[4] = {Y.x, Y.y, Y.z, Y.w};
           float r[4], g[4], b[4];
 #pragma unroll
           for (int i = 0; i < 4; i++) {
-            r[i] = (yy[i] + JB_CR_R * cr[i]) + 128.0f;
-            g[i] = ((yy[i] - JB_CB_G * cb[i]) - JB_CR_G * cr[i]) + 128.0f;
-            b[i] = (yy[i] + JB_CB_B * cb[i]) + 128.0f;
+            ycc_px(yy[i], cb[i], cr[i], r[i], g[i], b[i]);
           }
           // the full-size conversion with its operands permuted: pack12_rtz writes bytes in the order
           // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3, so these arguments give one word per channel (pixels 0..3)
-          const float pr[4] = {r[0], r[3], g[2], b[1]}, pg[4] = {r[1], g[0], g[3], b[2]}, pb[4] = {r[2], g[1], b[0], b[3]};
-          uint32_t w[3];
-          pack12_rtz(pr, pg, pb, w[0], w[1], w[2]);
+        uint32_t w[3];
+        pack_channels(r, g, b, w);
 #pragma unroll
           for (int c = 0; c < 3; c++) {
             const uint32_t v8 = w[c] & keep;
@@ -714,29 +779,16 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
         const float4 Y = *(const float4 *)(lds + lane_y_off + row * (YW * 4) + seg * 1024);
         float cb[4], cr[4];
         const int coff = (row / VS) * (CW * 4) + seg * (1024 / HS);
-        if (HS == 1) {
-          const float4 a = *(const float4 *)(lds + CB_OFF + lane_c_off + coff);
-          const float4 b = *(const float4 *)(lds + CR_OFF + lane_c_off + coff);
-          cb[0] = a.x, cb[1] = a.y, cb[2] = a.z, cb[3] = a.w;
-          cr[0] = b.x, cr[1] = b.y, cr[2] = b.z, cr[3] = b.w;
-        } else {
-          const float2 a = *(const float2 *)(lds + CB_OFF + lane_c_off + coff);
-          const float2 b = *(const float2 *)(lds + CR_OFF + lane_c_off + coff);
-          cb[0] = cb[1] = a.x, cb[2] = cb[3] = a.y;
-          cr[0] = cr[1] = b.x, cr[2] = cr[3] = b.y;
-        }
+        load_chroma4<HS>(lds + CB_OFF + lane_c_off + coff, lds + CR_OFF + lane_c_off + coff, cb, cr);
         const float yy[4] = {Y.x, Y.y, Y.z, Y.w};
         float r[4], g[4], b[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-          r[i] = (yy[i] + JB_CR_R * cr[i]) + 128.0f;
-          g[i] = ((yy[i] - JB_CB_G * cb[i]) - JB_CR_G * cr[i]) + 128.0f;
-          b[i] = (yy[i] + JB_CB_B * cb[i]) + 128.0f;
+          ycc_px(yy[i], cb[i], cr[i], r[i], g[i], b[i]);
         }
         // byte order of pack12_rtz: r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3 -> with these arguments w[c] = channel c, pixels 0..3
-        const float pr[4] = {r[0], r[3], g[2], b[1]}, pg[4] = {r[1], g[0], g[3], b[2]}, pb[4] = {r[2], g[1], b[0], b[3]};
         uint32_t w[3];
-        pack12_rtz(pr, pg, pb, w[0], w[1], w[2]);
+        pack_channels(r, g, b, w);
         const int npx = min(256, p.width - xseg);    // pixels of the segment inside the image (wave-uniform)
         const int whole = npx >> 2, part = npx & 3;  // whole 4-pixel groups; pixels of the group that straddles the edge
         uint8_t *const segp = img_rgb + (int64_t)y * p.rgb_row_stride + (int64_t)xseg * ES;
@@ -813,25 +865,13 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
         float cb[4], cr[4];
         // chroma sample of luma pixel (row, col): (row/VS, col/HS) -- reference jpeg.cpp:518-520
         const int coff = (row / VS) * (CW * 4) + seg * (1024 / HS);
-        if (HS == 1) {
-          const float4 a = *(const float4 *)(lds + CB_OFF + lane_c_off + coff);
-          const float4 b = *(const float4 *)(lds + CR_OFF + lane_c_off + coff);
-          cb[0] = a.x, cb[1] = a.y, cb[2] = a.z, cb[3] = a.w;
-          cr[0] = b.x, cr[1] = b.y, cr[2] = b.z, cr[3] = b.w;
-        } else {
-          const float2 a = *(const float2 *)(lds + CB_OFF + lane_c_off + coff);
-          const float2 b = *(const float2 *)(lds + CR_OFF + lane_c_off + coff);
-          cb[0] = cb[1] = a.x, cb[2] = cb[3] = a.y;
-          cr[0] = cr[1] = b.x, cr[2] = cr[3] = b.y;
-        }
+        load_chroma4<HS>(lds + CB_OFF + lane_c_off + coff, lds + CR_OFF + lane_c_off + coff, cb, cr);
         const float yy[4] = {Y.x, Y.y, Y.z, Y.w};
         float r[4], g[4], b[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
           if (JB_DO_COLOUR(p)) {
-            r[i] = (yy[i] + JB_CR_R * cr[i]) + 128.0f;
-            g[i] = ((yy[i] - JB_CB_G * cb[i]) - JB_CR_G * cr[i]) + 128.0f;
-            b[i] = (yy[i] + JB_CB_B * cb[i]) + 128.0f;
+            ycc_px(yy[i], cb[i], cr[i], r[i], g[i], b[i]);
           } else {
             r[i] = yy[i], g[i] = cb[i], b[i] = cr[i];
           }
@@ -890,12 +930,7 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
 #pragma unroll
               for (int i = 0; i < 4; i++) {
                 const int px = (LINEAR ? tail_src : tail_src * 4) + i;
-                if (px >= first && px < npx) {
-                  uint8_t *o = segp + px * 3;
-                  o[0] = (uint8_t)pack_u8(r[i], 0, 0);
-                  o[1] = (uint8_t)pack_u8(g[i], 0, 0);
-                  o[2] = (uint8_t)pack_u8(b[i], 0, 0);
-                }
+                if (px >= first && px < npx) store_px_bytes(segp + px * 3, r[i], g[i], b[i]);
               }
             }
           }
@@ -906,380 +941,122 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
   }
 }
 
-// ---- small grids (4:4:4): one WAVE per 16 MCUs -------------------------------------------------------------
+// ---- small grids: one WAVE per 16 (4:2:0: 8) MCUs -------------------------------------------------------------
 // A single 1080p 4:4:4 image is 507 tiles of the kernel above on 256 CUs: every CU runs its two workgroups through
 // load -> IDCT -> colour in step, and the launch is bounded by the length of that chain, not by traffic (DESIGN.md
-// section 5.2).  This variant cuts the same work into four times as many independent pieces: a 64-lane workgroup
-// owns 16 MCUs of one MCU row -- lanes 0-15 their Y blocks, 16-31 Cb, 32-47 Cr, 48-63 idle -- with the
-// quantisation tables in LDS (per-lane component), 6 KiB of strips, and no barrier other workgroups wait on, so
-// the phases of the eight or so waves on a CU interleave.  Arithmetic and its order are those of the kernel above.
+// section 5.2).  These kernels cut the same work into four times as many independent pieces: a 64-lane workgroup
+// owns MCUS MCUs of one MCU row, one lane per coded block, with the quantisation tables in LDS (per-lane component),
+// 6-8 KiB of strips, and no barrier other workgroups wait on, so the phases of the eight or so waves on a CU
+// interleave.  Arithmetic and its order are those of the kernel above.
 // Selected by the host for launches of fewer than 3 workgroups per CU (jb_api.cpp; JPEGBLK_SMALL_GRID).
-constexpr int kSmallMcus = 16;
-__global__ __launch_bounds__(64) void jb_small_kernel_444(const JbLaunch p) {
-  constexpr int kStrip = 2048 + 64;  // 4 rows x 128 samples x 4 B, skewed so the three strips start in different banks
-  constexpr int kQPitch = 64 + 4;    // dwords per table in LDS (the three tables start in different banks)
-  __shared__ __attribute__((aligned(16))) char lds[3 * kStrip + 3 * kQPitch * 4];
-  int32_t *const qlds = (int32_t *)(lds + 3 * kStrip);
-  const int lane = threadIdx.x;
-  const int tile = blockIdx.x;
-  const int img = tile / p.tiles_per_image;
-  const int rem = tile - img * p.tiles_per_image;
-  const int my = rem / p.tiles_per_row;
-  const int mx0 = (rem - my * p.tiles_per_row) * kSmallMcus;
-  const int nvalid = min(kSmallMcus, p.mcus_x - mx0);
-  const int comp = min(lane >> 4, 2);  // (lanes 48-63 repeat the Cr lanes' work and write nothing)
-  const bool active = lane < 48;
-  const int m = lane & 15;
-  const uint8_t *tile_coef = (const uint8_t *)p.coef + (int64_t)img * p.coef_image_stride + ((int64_t)my * p.mcus_x + mx0) * 384;
-  const int32_t *qsrc = (const int32_t *)((const uint8_t *)p.qtabs + (int64_t)img * p.qtab_image_stride);
-#pragma unroll
-  for (int i = 0; i < 3; i++) qlds[i * kQPitch + lane] = qsrc[i * 64 + lane];
-  float v[64];
-  {
-    uint32_t raw[32];
-    const u32x4_t *src = (const u32x4_t *)(tile_coef + (uint32_t)(min(m, nvalid - 1) * 3 + comp) * 128u);
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const u32x4_t t = src[j];
-      raw[j * 4 + 0] = t.x, raw[j * 4 + 1] = t.y, raw[j * 4 + 2] = t.z, raw[j * 4 + 3] = t.w;
-    }
-    __syncthreads();  // the tables are in LDS
-    const int32_t *q = qlds + comp * kQPitch;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-#pragma unroll
-      for (int i = 0; i < 8; i += 4) {
-        const int4 q4 = *(const int4 *)(q + k * 8 + i);
-        const int qq[4] = {q4.x, q4.y, q4.z, q4.w};
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          const uint32_t w = raw[k * 4 + ((i + e) >> 1)];
-          const int c = ((i + e) & 1) ? ((int)w >> 16) : (int)(short)(w & 0xffffu);
-          v[k * 8 + i + e] = (float)__mul24(c, qq[e]);  // jpeg.cpp:563-569
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 8; i++)  // column pass, jpeg.cpp:596-663
-    aan_1d(v[0 * 8 + i], v[1 * 8 + i], v[2 * 8 + i], v[3 * 8 + i], v[4 * 8 + i], v[5 * 8 + i], v[6 * 8 + i], v[7 * 8 + i]);
-#pragma unroll
-  for (int k = 0; k < 8; k++)  // row pass, jpeg.cpp:664-731
-    aan_1d(v[k * 8 + 0], v[k * 8 + 1], v[k * 8 + 2], v[k * 8 + 3], v[k * 8 + 4], v[k * 8 + 5], v[k * 8 + 6], v[k * 8 + 7]);
+//
+// Lane -> block, the counterpart of LaneMap: the luma blocks first (MCU l / NY, block l % NY in decode order), then
+// MCUS Cb lanes, then MCUS Cr lanes:
+//   4:4:4  16 MCUs: lanes 0-15 Y, 16-31 Cb, 32-47 Cr, 48-63 idle
+//   4:2:0   8 MCUs: lanes 0-31 Y (top left, top right, bottom left, bottom right), 32-39 Cb, 40-47 Cr, 48-63 idle
+//   4:2:2, 4:4:0  16 MCUs: lanes 0-31 Y (left / right, or top / bottom), 32-47 Cb, 48-63 Cr: the wave is full
+// An idle lane repeats a Cr lane's loads and arithmetic, writes nothing into the strips, and takes part in the colour loop.
+// Strips per phase: YROWS = 4 * VS luma rows (rows 4p..4p+3 of every block row) x YW samples, and the 4 chroma rows
+// they need x CW samples per chroma component (VS = 2: rows 2p, 2p+1, 4+2p, 5+2p of the block, reference
+// jpeg.cpp:518-520 -- a chroma lane picks them with a select per value; the 192-lane kernel permutes them in the
+// column pass, which a wave of mixed lanes cannot).  The strips are skewed by 64 bytes so that they start in different banks.
+template <int HS, int VS>
+struct SmallMap {
+  static_assert((HS == 1 || HS == 2) && (VS == 1 || VS == 2), "the four layouts of the ABI");
+  static constexpr int NY = HS * VS, NB = NY + 2;
+  static constexpr int MCUS = NY == 4 ? 8 : 16;       // MCUs per workgroup
+  static constexpr int NYL = NY * MCUS;               // luma lanes
+  static constexpr bool kFull = NB * MCUS == 64;      // no idle lanes
+  static constexpr int YW = MCUS * 8 * HS, CW = MCUS * 8;   // strip widths in samples
+  static constexpr int YROWS = 4 * VS;                // luma strip rows per phase
+  static constexpr int kYStrip = YROWS * YW * 4 + (NY == 1 ? 64 : 0);  // bytes; 4:4:4 skews the luma strip too
+  static constexpr int kCStrip = 4 * CW * 4 + 64;
+  static constexpr int kQPitch = 64 + 4;              // dwords per table in LDS (the three tables start in different banks)
+  static constexpr int kLds = kYStrip + 2 * kCStrip + 3 * kQPitch * 4;
+  static constexpr int TPR = YW / 4;                  // 4-pixel tasks per row: 32, or 64 (4:2:2)
+  static constexpr int ROWS_PER_IT = 64 / TPR;        // pixel rows per wave-iteration
+  __device__ static __forceinline__ bool active(int l) { return kFull || l < NB * MCUS; }
+  __device__ static __forceinline__ int comp(int l) { return l < NYL ? 0 : (l < NYL + MCUS ? 1 : 2); }
+  __device__ static __forceinline__ int mcu(int l) { return l < NYL ? l / NY : (l & (MCUS - 1)); }
+  __device__ static __forceinline__ int slot(int l) { return l < NYL ? l % NY : NY + comp(l) - 1; }  // block of the MCU in decode order
+};
 
-  // colour stage, rows 0-3 then rows 4-7 of the MCU row: strips of 4 rows x 128 samples per component, 16-B chunk c
-  // of a row stored at c ^ ((c >> 3) & 1) (as above); then one lane = 4 adjacent pixels, a wave-iteration = 2 rows
-  const int sw = (m >> 2) & 1;
-  char *const dst = lds + comp * kStrip + m * 32;
-  const int x4 = lane & 31;
-  const int rd = (x4 ^ ((x4 >> 3) & 1)) * 16;
-  uint8_t *const img_rgb = p.rgb + (int64_t)img * p.rgb_image_stride;
-  const int x = mx0 * 8 + x4 * 4;                 // image column of this lane's first pixel
-  const int npx = min(4, min(nvalid * 8, p.width - mx0 * 8) - x4 * 4);  // its pixels inside the image (<= 0: none)
-#pragma unroll
-  for (int phase = 0; phase < 2; phase++) {
-    if (phase == 1) __syncthreads();
-    if (active) {
-#pragma unroll
-      for (int kk = 0; kk < 4; kk++) {
-        const int k = phase * 4 + kk;
-        *(float4 *)(dst + kk * 512 + sw * 16) = make_float4(v[k * 8 + 0], v[k * 8 + 1], v[k * 8 + 2], v[k * 8 + 3]);
-        *(float4 *)(dst + kk * 512 + (sw ^ 1) * 16) = make_float4(v[k * 8 + 4], v[k * 8 + 5], v[k * 8 + 6], v[k * 8 + 7]);
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < 2; it++) {
-      const int r = it * 2 + (lane >> 5);
-      const int y = my * 8 + phase * 4 + r;
-      const float4 Y = *(const float4 *)(lds + r * 512 + rd);
-      const float4 B = *(const float4 *)(lds + kStrip + r * 512 + rd);
-      const float4 R = *(const float4 *)(lds + 2 * kStrip + r * 512 + rd);
-      const float yy[4] = {Y.x, Y.y, Y.z, Y.w}, cb[4] = {B.x, B.y, B.z, B.w}, cr[4] = {R.x, R.y, R.z, R.w};
-      float rr[4], gg[4], bb[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) {  // jpeg.cpp:521-535
-        rr[i] = (yy[i] + JB_CR_R * cr[i]) + 128.0f;
-        gg[i] = ((yy[i] - JB_CB_G * cb[i]) - JB_CR_G * cr[i]) + 128.0f;
-        bb[i] = (yy[i] + JB_CB_B * cb[i]) + 128.0f;
-      }
-      if (p.fast_store) {
-        uint32_t w0, w1, w2;
-        pack12_rtz(rr, gg, bb, w0, w1, w2);
-        if (y < p.height && npx == 4) {
-          // a wave-uniform descriptor at the first of the iteration's two rows; the lane adds its row and column
-          uint8_t *const rows = img_rgb + (int64_t)(my * 8 + phase * 4 + it * 2) * p.rgb_row_stride + (int64_t)mx0 * 24;
-          const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(rows, 0, 0x7ffffff0, 0x00020000);
-          __builtin_amdgcn_raw_buffer_store_b96(u32x3_t{w0, w1, w2}, rsrc, (lane >> 5) * (int)p.rgb_row_stride + x4 * 12, 0, JB_STORE_AUX);
-        }
-      }
-      uint8_t *const o = img_rgb + (int64_t)y * p.rgb_row_stride + (int64_t)x * 3;
-      if (y < p.height && npx > 0 && (!p.fast_store || npx < 4)) {
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-          if (i < npx) {
-            o[i * 3 + 0] = (uint8_t)pack_u8(rr[i], 0, 0);
-            o[i * 3 + 1] = (uint8_t)pack_u8(gg[i], 0, 0);
-            o[i * 3 + 2] = (uint8_t)pack_u8(bb[i], 0, 0);
-          }
-      }
-    }
-  }
-}
-
-// The same for 4:2:0: a 64-lane workgroup owns 8 MCUs of one MCU row -- lanes 0-31 their luma blocks (MCU l >> 2,
-// block l & 3 in decode order: top left, top right, bottom left, bottom right), 32-39 Cb, 40-47 Cr, 48-63 idle.
-// Strips per phase: 8 luma rows (rows 4p..4p+3 of both block rows) x 128 samples, 4 chroma rows (2p, 2p+1, 4+2p,
-// 5+2p: reference jpeg.cpp:518-520) x 64 samples per chroma component; a chroma lane picks those rows of its block
-// with a select per value (the 192-lane kernel permutes them in the column pass, which a wave of mixed lanes cannot).
-constexpr int kSmallMcus420 = 8;
-__global__ __launch_bounds__(64) void jb_small_kernel_420(const JbLaunch p) {
-  constexpr int kYStrip = 8 * 128 * 4;       // 4 KiB
-  constexpr int kCStrip = 4 * 64 * 4 + 64;   // 1 KiB, skewed
-  constexpr int kQPitch = 64 + 4;
-  __shared__ __attribute__((aligned(16))) char lds[kYStrip + 2 * kCStrip + 3 * kQPitch * 4];
+template <int HS, int VS>
+__device__ __forceinline__ void jb_small_body(const JbLaunch &p) {
+  using SM = SmallMap<HS, VS>;
+  constexpr int MCUS = SM::MCUS, NB = SM::NB, YW = SM::YW, kYStrip = SM::kYStrip, kCStrip = SM::kCStrip, kCPitch = SM::CW * 4;
+  __shared__ __attribute__((aligned(16))) char lds[SM::kLds];
   int32_t *const qlds = (int32_t *)(lds + kYStrip + 2 * kCStrip);
   const int lane = threadIdx.x;
   const int tile = blockIdx.x;
   const int img = tile / p.tiles_per_image;
   const int rem = tile - img * p.tiles_per_image;
   const int my = rem / p.tiles_per_row;
-  const int mx0 = (rem - my * p.tiles_per_row) * kSmallMcus420;
-  const int nvalid = min(kSmallMcus420, p.mcus_x - mx0);
-  const bool active = lane < 48;
-  const int comp = lane < 32 ? 0 : (lane < 40 ? 1 : 2);  // (lanes 48-63 repeat Cr lanes' work and write nothing)
-  const int m = lane < 32 ? lane >> 2 : (lane & 7);
-  const int slot = lane < 32 ? (lane & 3) : 4 + comp - 1;  // block of the MCU in decode order
-  const uint8_t *tile_coef = (const uint8_t *)p.coef + (int64_t)img * p.coef_image_stride + ((int64_t)my * p.mcus_x + mx0) * 768;
+  const int mx0 = (rem - my * p.tiles_per_row) * MCUS;
+  const int nvalid = min(MCUS, p.mcus_x - mx0);
+  const int comp = SM::comp(lane), m = SM::mcu(lane), slot = SM::slot(lane);
+  const uint8_t *tile_coef = (const uint8_t *)p.coef + (int64_t)img * p.coef_image_stride + ((int64_t)my * p.mcus_x + mx0) * (NB * 128);
   const int32_t *qsrc = (const int32_t *)((const uint8_t *)p.qtabs + (int64_t)img * p.qtab_image_stride);
 #pragma unroll
-  for (int i = 0; i < 3; i++) qlds[i * kQPitch + lane] = qsrc[i * 64 + lane];
+  for (int i = 0; i < 3; i++) qlds[i * SM::kQPitch + lane] = qsrc[i * 64 + lane];
   float v[64];
   {
     uint32_t raw[32];
-    const u32x4_t *src = (const u32x4_t *)(tile_coef + (uint32_t)(min(m, nvalid - 1) * 6 + slot) * 128u);
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const u32x4_t t = src[j];
-      raw[j * 4 + 0] = t.x, raw[j * 4 + 1] = t.y, raw[j * 4 + 2] = t.z, raw[j * 4 + 3] = t.w;
-    }
+    load_block((const u32x4_t *)(tile_coef + (uint32_t)(min(m, nvalid - 1) * NB + slot) * 128u), raw);  // ragged: re-read the last MCU
     __syncthreads();  // the tables are in LDS
-    const int32_t *q = qlds + comp * kQPitch;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-#pragma unroll
-      for (int i = 0; i < 8; i += 4) {
-        const int4 q4 = *(const int4 *)(q + k * 8 + i);
-        const int qq[4] = {q4.x, q4.y, q4.z, q4.w};
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          const uint32_t w = raw[k * 4 + ((i + e) >> 1)];
-          const int c = ((i + e) & 1) ? ((int)w >> 16) : (int)(short)(w & 0xffffu);
-          v[k * 8 + i + e] = (float)__mul24(c, qq[e]);  // jpeg.cpp:563-569
-        }
-      }
-    }
+    dequantise(raw, v, qlds + comp * SM::kQPitch);
   }
-#pragma unroll
-  for (int i = 0; i < 8; i++)  // column pass, jpeg.cpp:596-663
-    aan_1d(v[0 * 8 + i], v[1 * 8 + i], v[2 * 8 + i], v[3 * 8 + i], v[4 * 8 + i], v[5 * 8 + i], v[6 * 8 + i], v[7 * 8 + i]);
-#pragma unroll
-  for (int k = 0; k < 8; k++)  // row pass, jpeg.cpp:664-731
-    aan_1d(v[k * 8 + 0], v[k * 8 + 1], v[k * 8 + 2], v[k * 8 + 3], v[k * 8 + 4], v[k * 8 + 5], v[k * 8 + 6], v[k * 8 + 7]);
+  idct_8x8(v);
 
-  // where this lane's block lands: luma block (bv, bh) of MCU m in strip rows 4*bv.., 8-sample column 2*m + bh;
-  // a chroma block in its component's strip, column m.  16-B chunk c of a row is stored at c ^ ((c >> 3) & 1).
+  // where this lane's block lands: luma block (bv, bh) of MCU m in strip rows 4*bv.., 8-sample column HS*m + bh; a
+  // chroma block in its component's strip, column m.  16-B chunk c of a row is stored at c ^ ((c >> 3) & 1) (as above).
   const bool luma = comp == 0;
-  const int bv = luma ? (slot >> 1) : 0, bh = luma ? (slot & 1) : 0;
-  const int col = luma ? m * 2 + bh : m;
+  const int bv = luma ? slot / HS : 0, bh = luma ? slot % HS : 0;
+  const int col = luma ? m * HS + bh : m;
   const int sw = (col >> 2) & 1;
-  const int pitch = luma ? 512 : 256;
-  char *const dst = lds + (luma ? bv * 4 * 512 : kYStrip + (comp - 1) * kCStrip) + col * 32;
-  const int x4 = lane & 31;
+  const int pitch = luma ? YW * 4 : kCPitch;
+  char *const dst = lds + (luma ? bv * 4 * (YW * 4) : kYStrip + (comp - 1) * kCStrip) + col * 32;
+  // colour stage: one lane = 4 adjacent pixels, a wave-iteration = ROWS_PER_IT pixel rows
+  const int x4 = lane & (SM::TPR - 1);
   const int rd_y = (x4 ^ ((x4 >> 3) & 1)) * 16;
-  const int rd_c = ((x4 >> 1) ^ ((x4 >> 4) & 1)) * 16 + (x4 & 1) * 8;  // chroma chunk x4 / 2, its half x4 & 1
+  const int rd_c = HS == 2 ? ((x4 >> 1) ^ ((x4 >> 4) & 1)) * 16 + (x4 & 1) * 8 : rd_y;  // HS = 2: chroma chunk x4 / 2, its half x4 & 1
   uint8_t *const img_rgb = p.rgb + (int64_t)img * p.rgb_image_stride;
-  const int x = mx0 * 16 + x4 * 4;
-  const int npx = min(4, min(nvalid * 16, p.width - mx0 * 16) - x4 * 4);
+  const int x = mx0 * 8 * HS + x4 * 4;  // image column of this lane's first pixel
+  const int npx = min(4, min(nvalid * 8 * HS, p.width - mx0 * 8 * HS) - x4 * 4);  // its pixels inside the image (<= 0: none)
 #pragma unroll
   for (int phase = 0; phase < 2; phase++) {
     if (phase == 1) __syncthreads();
-    if (active) {
+    if (SM::active(lane)) {
 #pragma unroll
       for (int kk = 0; kk < 4; kk++) {
-        const int kl = phase * 4 + kk;                         // luma: rows 4p .. 4p+3 of the block
-        const int kc = phase * 2 + (kk & 1) + (kk >> 1) * 4;   // chroma: rows 2p, 2p+1, 4+2p, 5+2p
+        const int kl = phase * 4 + kk;                                       // rows 4p .. 4p+3 of the block
+        const int kc = VS == 2 ? phase * 2 + (kk & 1) + (kk >> 1) * 4 : kl;  // VS = 2 chroma: rows 2p, 2p+1, 4+2p, 5+2p
         float o[8];
 #pragma unroll
-        for (int e = 0; e < 8; e++) o[e] = luma ? v[kl * 8 + e] : v[kc * 8 + e];
+        for (int e = 0; e < 8; e++) o[e] = (VS == 2 && !luma) ? v[kc * 8 + e] : v[kl * 8 + e];
         *(float4 *)(dst + kk * pitch + sw * 16) = make_float4(o[0], o[1], o[2], o[3]);
         *(float4 *)(dst + kk * pitch + (sw ^ 1) * 16) = make_float4(o[4], o[5], o[6], o[7]);
       }
     }
     __syncthreads();
 #pragma unroll
-    for (int it = 0; it < 4; it++) {
-      const int r = it * 2 + (lane >> 5);                      // luma strip row
-      const int y = my * 16 + phase * 4 + (r >> 2) * 8 + (r & 3);
-      const float4 Y = *(const float4 *)(lds + r * 512 + rd_y);
-      const float2 B = *(const float2 *)(lds + kYStrip + (r >> 1) * 256 + rd_c);
-      const float2 R = *(const float2 *)(lds + kYStrip + kCStrip + (r >> 1) * 256 + rd_c);
-      const float yy[4] = {Y.x, Y.y, Y.z, Y.w}, cb[4] = {B.x, B.x, B.y, B.y}, cr[4] = {R.x, R.x, R.y, R.y};
-      float rr[4], gg[4], bb[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) {  // jpeg.cpp:521-535
-        rr[i] = (yy[i] + JB_CR_R * cr[i]) + 128.0f;
-        gg[i] = ((yy[i] - JB_CB_G * cb[i]) - JB_CR_G * cr[i]) + 128.0f;
-        bb[i] = (yy[i] + JB_CB_B * cb[i]) + 128.0f;
-      }
-      if (p.fast_store) {
-        uint32_t w0, w1, w2;
-        pack12_rtz(rr, gg, bb, w0, w1, w2);
-        if (y < p.height && npx == 4) {
-          // a wave-uniform descriptor at row 0 of the MCU row; the lane adds its row and column
-          uint8_t *const rows = img_rgb + (int64_t)(my * 16) * p.rgb_row_stride + (int64_t)mx0 * 48;
-          const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(rows, 0, 0x7ffffff0, 0x00020000);
-          __builtin_amdgcn_raw_buffer_store_b96(u32x3_t{w0, w1, w2}, rsrc, (y - my * 16) * (int)p.rgb_row_stride + x4 * 12, 0, JB_STORE_AUX);
-        }
-      }
-      uint8_t *const o = img_rgb + (int64_t)y * p.rgb_row_stride + (int64_t)x * 3;
-      if (y < p.height && npx > 0 && (!p.fast_store || npx < 4)) {
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-          if (i < npx) {
-            o[i * 3 + 0] = (uint8_t)pack_u8(rr[i], 0, 0);
-            o[i * 3 + 1] = (uint8_t)pack_u8(gg[i], 0, 0);
-            o[i * 3 + 2] = (uint8_t)pack_u8(bb[i], 0, 0);
-          }
-      }
-    }
-  }
-}
-
-// 4:2:2 (HS = 2, VS = 1) and 4:4:0 (HS = 1, VS = 2): four blocks per MCU, so 16 MCUs fill a wave exactly -- lanes
-// 0-31 the luma blocks (MCU l >> 1, block l & 1: left / right, or top / bottom), 32-47 Cb, 48-63 Cr.  4:2:2: strips of
-// 4 rows x 256 luma / 128 chroma samples, a pixel row per wave-iteration; 4:4:0: 8 luma rows (rows 4p..4p+3 of both
-// block rows) x 128 samples and the 4 chroma rows they need (selected per value, as in the 4:2:0 variant), two pixel
-// rows per wave-iteration.
-template <int HS, int VS>
-__global__ __launch_bounds__(64) void jb_small_kernel_16(const JbLaunch p) {
-  static_assert((HS == 2 && VS == 1) || (HS == 1 && VS == 2), "the four-blocks-per-MCU layouts");
-  constexpr int kMcus = 16;
-  constexpr int YW = kMcus * 8 * HS;            // luma strip width in samples: 256 / 128
-  constexpr int YROWS = 4 * VS;                 // luma strip rows per phase: 4 / 8
-  constexpr int kYStrip = YROWS * YW * 4;       // 4 KiB either way
-  constexpr int kCPitch = kMcus * 8 * 4;        // 512 B: 128 chroma samples per row
-  constexpr int kCStrip = 4 * kCPitch + 64;     // 2 KiB, skewed
-  constexpr int kQPitch = 64 + 4;
-  __shared__ __attribute__((aligned(16))) char lds[kYStrip + 2 * kCStrip + 3 * kQPitch * 4];
-  int32_t *const qlds = (int32_t *)(lds + kYStrip + 2 * kCStrip);
-  const int lane = threadIdx.x;
-  const int tile = blockIdx.x;
-  const int img = tile / p.tiles_per_image;
-  const int rem = tile - img * p.tiles_per_image;
-  const int my = rem / p.tiles_per_row;
-  const int mx0 = (rem - my * p.tiles_per_row) * kMcus;
-  const int nvalid = min(kMcus, p.mcus_x - mx0);
-  const int comp = lane < 32 ? 0 : (lane < 48 ? 1 : 2);
-  const int m = lane < 32 ? lane >> 1 : (lane & 15);
-  const int slot = lane < 32 ? (lane & 1) : 2 + comp - 1;  // block of the MCU in decode order
-  const uint8_t *tile_coef = (const uint8_t *)p.coef + (int64_t)img * p.coef_image_stride + ((int64_t)my * p.mcus_x + mx0) * 512;
-  const int32_t *qsrc = (const int32_t *)((const uint8_t *)p.qtabs + (int64_t)img * p.qtab_image_stride);
-#pragma unroll
-  for (int i = 0; i < 3; i++) qlds[i * kQPitch + lane] = qsrc[i * 64 + lane];
-  float v[64];
-  {
-    uint32_t raw[32];
-    const u32x4_t *src = (const u32x4_t *)(tile_coef + (uint32_t)(min(m, nvalid - 1) * 4 + slot) * 128u);
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const u32x4_t t = src[j];
-      raw[j * 4 + 0] = t.x, raw[j * 4 + 1] = t.y, raw[j * 4 + 2] = t.z, raw[j * 4 + 3] = t.w;
-    }
-    __syncthreads();  // the tables are in LDS
-    const int32_t *q = qlds + comp * kQPitch;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-#pragma unroll
-      for (int i = 0; i < 8; i += 4) {
-        const int4 q4 = *(const int4 *)(q + k * 8 + i);
-        const int qq[4] = {q4.x, q4.y, q4.z, q4.w};
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          const uint32_t w = raw[k * 4 + ((i + e) >> 1)];
-          const int c = ((i + e) & 1) ? ((int)w >> 16) : (int)(short)(w & 0xffffu);
-          v[k * 8 + i + e] = (float)__mul24(c, qq[e]);  // jpeg.cpp:563-569
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 8; i++)  // column pass, jpeg.cpp:596-663
-    aan_1d(v[0 * 8 + i], v[1 * 8 + i], v[2 * 8 + i], v[3 * 8 + i], v[4 * 8 + i], v[5 * 8 + i], v[6 * 8 + i], v[7 * 8 + i]);
-#pragma unroll
-  for (int k = 0; k < 8; k++)  // row pass, jpeg.cpp:664-731
-    aan_1d(v[k * 8 + 0], v[k * 8 + 1], v[k * 8 + 2], v[k * 8 + 3], v[k * 8 + 4], v[k * 8 + 5], v[k * 8 + 6], v[k * 8 + 7]);
-
-  const bool luma = comp == 0;
-  const int bsel = lane & 1;                                     // luma: right (4:2:2) or bottom (4:4:0) block of the MCU
-  const int col = luma ? (HS == 2 ? m * 2 + bsel : m) : m;       // 8-sample column of the block in its strip
-  const int row0 = luma && VS == 2 ? bsel * 4 : 0;               // first strip row of the block
-  const int sw = (col >> 2) & 1;
-  const int pitch = luma ? YW * 4 : kCPitch;
-  char *const dst = lds + (luma ? row0 * (YW * 4) : kYStrip + (comp - 1) * kCStrip) + col * 32;
-  constexpr int TPR = YW / 4;                                    // 4-pixel tasks per row: 64 / 32
-  const int x4 = lane & (TPR - 1);
-  const int rd_y = (x4 ^ ((x4 >> 3) & 1)) * 16;
-  const int rd_c = HS == 2 ? ((x4 >> 1) ^ ((x4 >> 4) & 1)) * 16 + (x4 & 1) * 8 : rd_y;
-  uint8_t *const img_rgb = p.rgb + (int64_t)img * p.rgb_image_stride;
-  const int x = mx0 * 8 * HS + x4 * 4;
-  const int npx = min(4, min(nvalid * 8 * HS, p.width - mx0 * 8 * HS) - x4 * 4);
-#pragma unroll
-  for (int phase = 0; phase < 2; phase++) {
-    if (phase == 1) __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < 4; kk++) {
-      const int kl = phase * 4 + kk;                                            // rows 4p .. 4p+3 of the block
-      const int kc = VS == 2 ? phase * 2 + (kk & 1) + (kk >> 1) * 4 : kl;       // 4:4:0 chroma: rows 2p, 2p+1, 4+2p, 5+2p
-      float o[8];
-#pragma unroll
-      for (int e = 0; e < 8; e++) o[e] = (VS == 2 && !luma) ? v[kc * 8 + e] : v[kl * 8 + e];
-      *(float4 *)(dst + kk * pitch + sw * 16) = make_float4(o[0], o[1], o[2], o[3]);
-      *(float4 *)(dst + kk * pitch + (sw ^ 1) * 16) = make_float4(o[4], o[5], o[6], o[7]);
-    }
-    __syncthreads();
-    constexpr int ROWS_PER_IT = 64 / TPR;  // 1 / 2
-#pragma unroll
-    for (int it = 0; it < YROWS / ROWS_PER_IT; it++) {
-      const int r = it * ROWS_PER_IT + (ROWS_PER_IT == 2 ? lane >> 5 : 0);   // luma strip row
-      const int y_in = phase * 4 + (r >> 2) * 8 + (r & 3);
+    for (int it = 0; it < SM::YROWS / SM::ROWS_PER_IT; it++) {
+      const int r = it * SM::ROWS_PER_IT + (SM::ROWS_PER_IT == 2 ? lane >> 5 : 0);  // luma strip row
+      const int y_in = phase * 4 + (r >> 2) * 8 + (r & 3);                          // pixel row within the MCU row
       const int y = my * 8 * VS + y_in;
       const float4 Y = *(const float4 *)(lds + r * (YW * 4) + rd_y);
-      float cb[4], cr[4];
-      const int crow = (r / VS) * kCPitch;
-      if (HS == 2) {
-        const float2 B = *(const float2 *)(lds + kYStrip + crow + rd_c);
-        const float2 R = *(const float2 *)(lds + kYStrip + kCStrip + crow + rd_c);
-        cb[0] = cb[1] = B.x, cb[2] = cb[3] = B.y;
-        cr[0] = cr[1] = R.x, cr[2] = cr[3] = R.y;
-      } else {
-        const float4 B = *(const float4 *)(lds + kYStrip + crow + rd_c);
-        const float4 R = *(const float4 *)(lds + kYStrip + kCStrip + crow + rd_c);
-        cb[0] = B.x, cb[1] = B.y, cb[2] = B.z, cb[3] = B.w;
-        cr[0] = R.x, cr[1] = R.y, cr[2] = R.z, cr[3] = R.w;
-      }
       const float yy[4] = {Y.x, Y.y, Y.z, Y.w};
-      float rr[4], gg[4], bb[4];
+      float cb[4], cr[4], rr[4], gg[4], bb[4];
+      const int crow = (r / VS) * kCPitch;
+      load_chroma4<HS>(lds + kYStrip + crow + rd_c, lds + kYStrip + kCStrip + crow + rd_c, cb, cr);
 #pragma unroll
-      for (int i = 0; i < 4; i++) {  // jpeg.cpp:521-535
-        rr[i] = (yy[i] + JB_CR_R * cr[i]) + 128.0f;
-        gg[i] = ((yy[i] - JB_CB_G * cb[i]) - JB_CR_G * cr[i]) + 128.0f;
-        bb[i] = (yy[i] + JB_CB_B * cb[i]) + 128.0f;
-      }
+      for (int i = 0; i < 4; i++) ycc_px(yy[i], cb[i], cr[i], rr[i], gg[i], bb[i]);
       if (p.fast_store) {
         uint32_t w0, w1, w2;
         pack12_rtz(rr, gg, bb, w0, w1, w2);
         if (y < p.height && npx == 4) {
+          // a wave-uniform descriptor at row 0 of the MCU row; the lane adds its row (a 32-bit offset: the host keeps
+          // rgb_row_stride below 2^26) and column
           uint8_t *const rows = img_rgb + (int64_t)(my * 8 * VS) * p.rgb_row_stride + (int64_t)mx0 * (24 * HS);
           const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(rows, 0, 0x7ffffff0, 0x00020000);
           __builtin_amdgcn_raw_buffer_store_b96(u32x3_t{w0, w1, w2}, rsrc, y_in * (int)p.rgb_row_stride + x4 * 12, 0, JB_STORE_AUX);
@@ -1289,14 +1066,19 @@ __global__ __launch_bounds__(64) void jb_small_kernel_16(const JbLaunch p) {
       if (y < p.height && npx > 0 && (!p.fast_store || npx < 4)) {
 #pragma unroll
         for (int i = 0; i < 4; i++)
-          if (i < npx) {
-            o[i * 3 + 0] = (uint8_t)pack_u8(rr[i], 0, 0);
-            o[i * 3 + 1] = (uint8_t)pack_u8(gg[i], 0, 0);
-            o[i * 3 + 2] = (uint8_t)pack_u8(bb[i], 0, 0);
-          }
+          if (i < npx) store_px_bytes(o + i * 3, rr[i], gg[i], bb[i]);
       }
     }
   }
+}
+
+// the entry points (bench.py and the committed profiles know the kernels by these names)
+__global__ __launch_bounds__(64) void jb_small_kernel_444(const JbLaunch p) { jb_small_body<1, 1>(p); }
+__global__ __launch_bounds__(64) void jb_small_kernel_420(const JbLaunch p) { jb_small_body<2, 2>(p); }
+template <int HS, int VS>
+__global__ __launch_bounds__(64) void jb_small_kernel_16(const JbLaunch p) {
+  static_assert(HS * VS == 2, "the four-blocks-per-MCU layouts: 4:2:2 and 4:4:0");
+  jb_small_body<HS, VS>(p);
 }
 
 // Launches jb_tile_kernel<HS, VS, MIXQ, LINEAR, STAGED, SCALE, FORMAT>: every launch of the 192-lane kernel goes through
@@ -1305,16 +1087,15 @@ __global__ __launch_bounds__(64) void jb_small_kernel_16(const JbLaunch p) {
 template <int HS, int VS, int SCALE, int FORMAT, bool LINEAR = false, bool STAGED = false>
 static hipError_t launch_tile(const JbLaunch &p, hipStream_t stream) {
   using LM = LaneMap<HS, VS>;
-  // does any wave hold two components whose tables may differ?
-  constexpr bool kLumaChromaMixed = (LM::NYT % 64 != 0);                      // no layout any more (see tile_blocks)
-  constexpr bool kCbCrMixed = (LM::MCUS % 64 != 0);                           // 4:2:0: Cb and Cr share the third wave
+  // does any wave hold two components whose tables may differ?  (never luma and chroma: jb_tile_kernel asserts it)
+  constexpr bool kCbCrMixed = (LM::MCUS % 64 != 0);  // 4:2:0: Cb and Cr share the third wave
   const dim3 grid(p.n_tiles), block(LM::TB);
   // hipGetLastError below must report THIS launch: an error left in the thread's error slot by an
   // unrelated earlier call (a failed attribute query, say) is not this launch's
   (void)hipGetLastError();
   bool mixq = false;
-  if constexpr (kLumaChromaMixed || kCbCrMixed) {
-    mixq = kLumaChromaMixed || !p.chroma_q_equal;
+  if constexpr (kCbCrMixed) {
+    mixq = !p.chroma_q_equal;
     if (mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, true, LINEAR, STAGED, SCALE, FORMAT>), grid, block, 0, stream, p);
   }
   if (!mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, false, LINEAR, STAGED, SCALE, FORMAT>), grid, block, 0, stream, p);
@@ -1358,17 +1139,21 @@ int jbk_linear_ok(int hs, int vs, int mcus_x) {
   return mcus_x >= 256 / (8 * hs);
 }
 
-int jbk_small_mcus(int hs, int vs) { return hs == 1 && vs == 1 ? kSmallMcus : hs == 2 && vs == 2 ? kSmallMcus420 : 16; }
+int jbk_small_mcus(int hs, int vs) {
+  return hs == 2 ? (vs == 2 ? SmallMap<2, 2>::MCUS : SmallMap<2, 1>::MCUS) : (vs == 2 ? SmallMap<1, 2>::MCUS : SmallMap<1, 1>::MCUS);
+}
 
 hipError_t jbk_launch(const JbLaunch &p, int hs, int vs, int scale, hipStream_t stream) {
   if (p.n_tiles <= 0) return hipSuccess;
   if (p.small_grid) {  // (the host sets it with the tile counts of this tiling)
-    if (jbk_small_mcus(hs, vs) == 0 || scale != 1 || p.format != 0) return hipErrorInvalidValue;
+    void (*kernel)(const JbLaunch) = hs == 1 && vs == 1   ? jb_small_kernel_444
+                                     : hs == 2 && vs == 2 ? jb_small_kernel_420
+                                     : hs == 2 && vs == 1 ? jb_small_kernel_16<2, 1>
+                                     : hs == 1 && vs == 2 ? jb_small_kernel_16<1, 2>
+                                                          : nullptr;
+    if (!kernel || scale != 1 || p.format != 0) return hipErrorInvalidValue;
     (void)hipGetLastError();
-    if (hs == 1 && vs == 1) hipLaunchKernelGGL(jb_small_kernel_444, dim3(p.n_tiles), dim3(64), 0, stream, p);
-    else if (hs == 2 && vs == 2) hipLaunchKernelGGL(jb_small_kernel_420, dim3(p.n_tiles), dim3(64), 0, stream, p);
-    else if (hs == 2) hipLaunchKernelGGL((jb_small_kernel_16<2, 1>), dim3(p.n_tiles), dim3(64), 0, stream, p);
-    else hipLaunchKernelGGL((jb_small_kernel_16<1, 2>), dim3(p.n_tiles), dim3(64), 0, stream, p);
+    hipLaunchKernelGGL(kernel, dim3(p.n_tiles), dim3(64), 0, stream, p);
     return hipGetLastError();
   }
   if (hs == 1 && vs == 1) return launch_layout<1, 1>(p, scale, stream);

@@ -617,8 +617,8 @@ def test_reference_with_the_integration_patch(tmp_path, name):
 @pytest.mark.parametrize("byte_store", [False, True])
 @pytest.mark.parametrize("hs,vs", [(1, 1), (2, 2), (2, 1), (1, 2)])
 def test_small_grid_kernels_vs_oracle(jb, oracle, monkeypatch, byte_store, hs, vs):
-    """jb_small_kernel_444 / _420 / _16<2,1> / _16<1,2> (JPEGBLK_SMALL_GRID=1: one wave per 16 / 8 / 16 / 16 MCUs, the
-    variants for launches that do not fill the device) against the oracle: sizes whose last tile of a row is ragged (1..15 MCUs), odd widths with tight rows and
+    """jb_small_kernel_444 / _420 / _16<2,1> / _16<1,2> (JPEGBLK_SMALL_GRID=1: one wave per 16 / 8 / 16 / 16 MCUs, four
+    entry points of one body, jb_small_body<HS, VS>; the variants for launches that do not fill the device) against the oracle: sizes whose last tile of a row is ragged (1..15 MCUs), odd widths with tight rows and
     padded, misaligned rows, one pixel, a batch of images with per-image tables, 16-bit table entries, and the
     1080p frame of BASELINE.json's config 2 -- with guard bytes around every image, both store paths.  The same
     inputs through the default kernel must give the same bytes (JPEGBLK_SMALL_GRID=0)."""
@@ -633,7 +633,8 @@ def test_small_grid_kernels_vs_oracle(jb, oracle, monkeypatch, byte_store, hs, v
     dev = torch.device("cuda:0")
     ts = torch.cuda.Stream(dev)
     cases = [(1, 1, 0, 0, 1), (8, 8, 0, 1, 1), (127, 9, 2, 1, 3), (128, 16, 0, 0, 2), (129, 17, 1, 3, 1), (333, 41, 0, 1, 2),
-             (679, 451, 0, 3, 1), (1921, 37, 5, 2, 1), (1920, 1080, 0, 0, 1), (2048, 24, 0, 0, 4), (1279, 853, 0, 1, 1), (16, 16, 0, 0, 1)]
+             (679, 451, 0, 3, 1), (1921, 37, 5, 2, 1), (1920, 1080, 0, 0, 1), (2048, 24, 0, 0, 4), (1279, 853, 0, 1, 1), (16, 16, 0, 0, 1),
+             (257, 17, 1, 1, 1)]   # 33 / 17 / 17 / 33 MCUs per row: the last workgroup of a row holds ONE MCU in every layout
     for (w, h, pad, off, n) in cases:
         desc = jb.make_desc(w, h, hs, vs)
         stride = 3 * w + pad
