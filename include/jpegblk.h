@@ -287,6 +287,35 @@ int jb_decode_memory_fmt(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, co
                          int32_t *width, int32_t *height);
 int jb_decode_file_fmt(jb_ctx *ctx, const char *path, const jb_output_spec *spec, void **out, int32_t *width, int32_t *height);
 
+/* ---- region of interest: decode a rectangle of the image, cropped by the pixel kernel ----
+ * With `full` = what the entry points above return for the image in the same format, bit for bit, a decode with the
+ * rectangle (x, y, width, height) returns full[y : y + height, x : x + width] (of every plane, for a planar format): the
+ * pixel kernel launches only the MCUs the rectangle touches and stores only the pixels inside it, so the output -- HBM
+ * writes, and the device-to-host link on the host-output forms -- is the rectangle's.  The entropy stage still decodes
+ * the whole image.  Every output format takes a rectangle; a scale other than 1 does not (the seam and jb_decode_*_roi
+ * cannot express the pair; the batch decoder refuses it with JB_ERR_UNSUPPORTED).  The ROI launches use the row-bound
+ * tiling and ignore JPEGBLK_SMALL_GRID and JPEGBLK_BYTE_STORE. */
+typedef struct jb_roi {
+  int32_t x, y, width, height; /* pixels of the full-size image */
+} jb_roi;
+/* JB_OK when x, y >= 0, width, height >= 1, x + width <= desc->width and y + height <= desc->height (sums that do not
+ * wrap); JB_ERR_NULL for a null argument; the descriptor's own errors (jb_geometry_of) first; else JB_ERR_GEOMETRY.
+ * Pure host code. */
+int jb_roi_check(const jb_image_desc *desc, const jb_roi *roi);
+/* jb_blocks_to_rgb_device_fmt for one rectangle shared by the batch's images: d_rgb and the strides describe images of
+ * roi->width x roi->height (every alignment and stride that is legal for a full-size image of that size is legal here;
+ * the spec is checked against the rectangle's height).  spec == NULL: interleaved uint8.  roi == NULL: exactly
+ * jb_blocks_to_rgb_device_fmt (jb_blocks_to_rgb_device when spec is NULL too). */
+int jb_blocks_to_rgb_device_roi(jb_ctx *ctx, const jb_device_batch *batch, const jb_roi *roi, const jb_output_spec *spec,
+                                void *stream);
+/* jb_decode_memory_fmt / jb_decode_file_fmt of a rectangle: *out holds jb_output_bytes(roi->width, roi->height, format)
+ * bytes (jb_free), *width / *height report the rectangle's size.  spec == NULL: interleaved uint8.  A rectangle that does
+ * not fit the file's frame is JB_ERR_GEOMETRY (jb_last_error names both sizes). */
+int jb_decode_memory_roi(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, const jb_roi *roi, const jb_output_spec *spec,
+                         void **out, int32_t *width, int32_t *height);
+int jb_decode_file_roi(jb_ctx *ctx, const char *path, const jb_roi *roi, const jb_output_spec *spec, void **out,
+                       int32_t *width, int32_t *height);
+
 /* ---- host front end ("next" rows of the scope table; reference jpeg.cpp:67-446, 826-907,
  *      include/file.hpp, include/huffman.hpp) --------------------------------------------- */
 /* Parse a JFIF byte stream and Huffman-decode it into packed int16 blocks in the order
@@ -440,6 +469,14 @@ int jb_batch_decoder_set_scale(jb_batch_decoder *dec, int denom);
  * JB_FMT_RGB_U8_HWC while the scale is not 1 (and jb_batch_decoder_set_scale(!= 1) while such a format is set) with
  * JB_ERR_UNSUPPORTED. */
 int jb_batch_decoder_set_output_format(jb_batch_decoder *dec, const jb_output_spec *spec);
+/* One rectangle for every image of the batch decoder's later runs and submissions (see "region of interest" above; NULL:
+ * whole images again).  widths / heights then report the rectangle's size and every output form holds
+ * jb_output_bytes(roi->width, roi->height, format) per image, so files of different sizes give outputs of one size.  A
+ * file the rectangle does not fit in gets the per-image status JB_ERR_GEOMETRY and the batch goes on.  Applies to every
+ * device of a multi-device decoder and to both sides of submit / collect.  Refused with JB_ERR_STATE while a batch is in
+ * flight; with JB_ERR_GEOMETRY when no frame could hold the rectangle; while the scale is not 1 (and
+ * jb_batch_decoder_set_scale(!= 1) while a rectangle is set) with JB_ERR_UNSUPPORTED. */
+int jb_batch_decoder_set_roi(jb_batch_decoder *dec, const jb_roi *roi);
 /* Output sink replacing the reference's X11 window / unused BMP writer (display.hpp,
  * jpeg.cpp:462-509): binary PPM (P6). */
 int jb_write_ppm(const char *path, const uint8_t *rgb, int32_t width, int32_t height,

@@ -75,6 +75,26 @@ class OutputSpec(ctypes.Structure):
         return FMT_DTYPE[self.format]
 
 
+class Roi(ctypes.Structure):
+    """jb_roi: a rectangle (x, y, width, height) in pixels of the full-size image."""
+    _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
+
+
+def _as_roi(roi, scale=1):
+    """None / (x, y, w, h) / a Roi -> Roi or None (None = the entry points without a rectangle).  A rectangle together
+    with a scale other than 1 is JbError(-9), raised here: no C entry point takes the pair."""
+    if roi is None:
+        return None
+    if scale != 1:
+        raise JbError(-9, "a rectangle (roi) cannot be combined with a scale")
+    return roi if isinstance(roi, Roi) else Roi(*[int(v) for v in roi])
+
+
+def roi_check(desc, roi):
+    """jb_roi_check: does the rectangle lie in the descriptor's image?  Raises JbError otherwise."""
+    _check(lib().jb_roi_check(ctypes.byref(desc), ctypes.byref(_as_roi(roi))))
+
+
 def _as_spec(fmt):
     """None / an int format / an OutputSpec -> OutputSpec or None (None = the entry points without a format)."""
     if fmt is None or isinstance(fmt, OutputSpec):
@@ -197,6 +217,12 @@ def lib():
     L.jb_decode_memory_fmt.argtypes = [vp, vp, ctypes.c_size_t, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.jb_decode_file_fmt.argtypes = [vp, ctypes.c_char_p, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.jb_batch_decoder_set_output_format.argtypes = [vp, ps]
+    pr = ctypes.POINTER(Roi)
+    L.jb_roi_check.argtypes = [pd, pr]
+    L.jb_blocks_to_rgb_device_roi.argtypes = [vp, ctypes.POINTER(DeviceBatch), pr, ps, vp]
+    L.jb_decode_memory_roi.argtypes = [vp, vp, ctypes.c_size_t, pr, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.jb_decode_file_roi.argtypes = [vp, ctypes.c_char_p, pr, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.jb_batch_decoder_set_roi.argtypes = [vp, pr]
     L.jb_write_ppm.argtypes = [ctypes.c_char_p, vp, i32, i32, i64]
     L.jb_write_bmp.argtypes = [ctypes.c_char_p, vp, i32, i32, i64]
     if L.jb_abi_version() != 1:
@@ -370,11 +396,18 @@ class Context:
         _check(lib().jb_wait(self._h, ticket), self._h)
 
     # -- the seam, device buffers ------------------------------------------------------------
-    def blocks_to_rgb_device(self, batch, stream=None, scale=1, fmt=None):
+    def blocks_to_rgb_device(self, batch, stream=None, scale=1, fmt=None, roi=None):
         """scale 2, 4, 8 (jb_blocks_to_rgb_device_scaled): the batch's d_rgb and strides describe images of
         scaled_size(desc.width, desc.height, scale).  fmt (an OutputSpec or a format number;
-        jb_blocks_to_rgb_device_fmt): planar output -- the batch's rgb_row_stride is then a plane's."""
+        jb_blocks_to_rgb_device_fmt): planar output -- the batch's rgb_row_stride is then a plane's.
+        roi=(x, y, w, h) (jb_blocks_to_rgb_device_roi, with any fmt, not with a scale): the batch's d_rgb and strides
+        describe images of w x h, the rectangle of every image."""
         spec = _as_spec(fmt)
+        r = _as_roi(roi, scale)
+        if r is not None:
+            _check(lib().jb_blocks_to_rgb_device_roi(self._h, ctypes.byref(batch), ctypes.byref(r),
+                                                     ctypes.byref(spec) if spec is not None else None, stream), self._h)
+            return
         if spec is not None:
             if scale != 1 and spec.format != FMT_RGB_U8_HWC:
                 raise JbError(-9, "an output format cannot be combined with a scale")
@@ -387,11 +420,17 @@ class Context:
             _check(lib().jb_blocks_to_rgb_device_scaled(self._h, ctypes.byref(batch), scale, stream), self._h)
 
     # -- decode(path) -> RGB -----------------------------------------------------------------
-    def decode_file(self, path, scale=1, fmt=None):
+    def decode_file(self, path, scale=1, fmt=None, roi=None):
         """-> RGB [H, W, 3]; scale 2, 4, 8: the area-reduced image (jb_decode_file_scaled); fmt (OutputSpec or format
-        number, jb_decode_file_fmt): [3, H, W] in the format's type for the planar formats."""
+        number, jb_decode_file_fmt): [3, H, W] in the format's type for the planar formats; roi=(x, y, w, h)
+        (jb_decode_file_roi, with any fmt, not with a scale): that rectangle of the image."""
         p, w, h = ctypes.c_void_p(), ctypes.c_int32(), ctypes.c_int32()
         spec = _as_spec(fmt)
+        r = _as_roi(roi, scale)
+        if r is not None:
+            rc = lib().jb_decode_file_roi(self._h, os.fsencode(path), ctypes.byref(r), ctypes.byref(spec) if spec is not None else None,
+                                          ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
+            return self._take_output(rc, p, w, h, spec)
         if spec is not None and scale != 1 and spec.format != FMT_RGB_U8_HWC:
             raise JbError(-9, "an output format cannot be combined with a scale")
         if spec is not None and scale == 1:
@@ -407,12 +446,25 @@ class Context:
             lib().jb_free(p)
         return arr
 
-    def decode_memory(self, jpeg_bytes, scale=1, fmt=None):
+    def _take_output(self, rc, p, w, h, spec):
+        """The array of a decode_*_roi call, its malloc'ed buffer released."""
+        _check(rc, self._h)
+        try:
+            return _shape_output(p, w.value, h.value, spec).copy()
+        finally:
+            lib().jb_free(p)
+
+    def decode_memory(self, jpeg_bytes, scale=1, fmt=None, roi=None):
         """jb_decode_memory: a JFIF byte string -> RGB [H, W, 3] (front end + device seam); scale 2, 4, 8: the
-        area-reduced image (jb_decode_memory_scaled); fmt: as decode_file (jb_decode_memory_fmt)."""
+        area-reduced image (jb_decode_memory_scaled); fmt, roi: as decode_file (jb_decode_memory_fmt, jb_decode_memory_roi)."""
         buf = np.frombuffer(jpeg_bytes, dtype=np.uint8)
         p, w, h = ctypes.c_void_p(), ctypes.c_int32(), ctypes.c_int32()
         spec = _as_spec(fmt)
+        r = _as_roi(roi, scale)
+        if r is not None:
+            rc = lib().jb_decode_memory_roi(self._h, _ptr(buf), buf.size, ctypes.byref(r), ctypes.byref(spec) if spec is not None else None,
+                                            ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
+            return self._take_output(rc, p, w, h, spec)
         if spec is not None and scale != 1 and spec.format != FMT_RGB_U8_HWC:
             raise JbError(-9, "an output format cannot be combined with a scale")
         if spec is not None and scale == 1:
@@ -434,9 +486,13 @@ class BatchDecoder:
     device, reusable.  devices=[...] (jb_batch_decoder_create_multi): one decoder over several
     devices, file i -> devices[i % len(devices)], the host threads split evenly.  scale 2, 4, 8
     (jb_batch_decoder_set_scale): every image comes out area-reduced.  fmt (an OutputSpec or a format number;
-    jb_batch_decoder_set_output_format): every image comes out in that format, [3, H, W] for the planar ones."""
+    jb_batch_decoder_set_output_format): every image comes out in that format, [3, H, W] for the planar ones.
+    roi=(x, y, w, h) (jb_batch_decoder_set_roi; with any fmt, not with a scale): every image comes out as that rectangle of
+    itself, so files of different sizes give outputs of one size."""
 
-    def __init__(self, n_threads=8, device=0, max_coef_bytes=0, max_rgb_bytes=0, arena_bytes=0, devices=None, scale=1, fmt=None):
+    def __init__(self, n_threads=8, device=0, max_coef_bytes=0, max_rgb_bytes=0, arena_bytes=0, devices=None, scale=1, fmt=None,
+                 roi=None):
+        _as_roi(roi, scale)   # (roi with a scale: JbError(-9) before anything is created)
         self._h = ctypes.c_void_p()
         if devices is not None:
             ids = (ctypes.c_int * len(devices))(*devices)
@@ -456,6 +512,8 @@ class BatchDecoder:
                 self.set_scale(scale)
             if fmt is not None:
                 self.set_output_format(fmt)
+            if roi is not None:
+                self.set_roi(roi)
         except JbError:
             self.close()
             raise
@@ -466,6 +524,13 @@ class BatchDecoder:
         spec = _as_spec(fmt)
         _check(lib().jb_batch_decoder_set_output_format(self._h, ctypes.byref(spec)))
         self._fmt = spec
+
+    def set_roi(self, roi):
+        """jb_batch_decoder_set_roi: one rectangle (x, y, w, h) for every image of later runs and submissions; None:
+        whole images again (JbError -7 while a batch is in flight, -9 when the decoder's scale is not 1).  A file the
+        rectangle does not fit in gets status -2 and the batch goes on."""
+        r = _as_roi(roi)
+        _check(lib().jb_batch_decoder_set_roi(self._h, ctypes.byref(r) if r is not None else None))
 
     def set_scale(self, scale):
         """jb_batch_decoder_set_scale: output at 1/scale for later runs and submissions (JbError -7 while a batch
@@ -512,7 +577,8 @@ class BatchDecoder:
         return [int(rgb[i] or 0) for i in range(n)], [(w[i], h[i]) for i in range(n)], list(st), t
 
     def run_to_tensor(self, paths, out):
-        """Decode files of ONE size straight into a caller-supplied CUDA tensor through the device-output route:
+        """Decode files of ONE size (or, with a rectangle set, of any size the rectangle fits in: out is then
+        [N, 3, h, w] of the rectangle) straight into a caller-supplied CUDA tensor through the device-output route:
         out is [N, 3, H, W] (planar formats; [N, H, W, 3] for format 0), contiguous, of the decoder's format's dtype, on
         the decoder's device, N = len(paths).  -> (out, statuses, times).  An image whose size does not match out (or
         that fails to decode) gets a non-zero status (JB_ERR_GEOMETRY = -2 for the size) and its slice of out is left
@@ -644,19 +710,23 @@ def decode_batch(paths, n_threads=8, device=0, keep_pixels=True, on_image=None, 
     return out, list(st), t
 
 
-def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, shared_qtabs=True, scale=1, fmt=None):
+def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, shared_qtabs=True, scale=1, fmt=None, roi=None):
     """DeviceBatch over torch CUDA tensors (plumbing): coef_t int16 [n_images, n_blocks, 64],
     qtabs_t int32 [3,64] (shared) or [n_images,3,64], rgb_t uint8 [n_images, H, row_stride].
     scale 2, 4, 8: rgb_t holds the reduced images, [n_images, ceil(H/scale), row_stride], for
     Context.blocks_to_rgb_device(..., scale=scale).
     fmt (a planar OutputSpec / format number, for Context.blocks_to_rgb_device(..., fmt=)): rgb_t is
     [n_images, 3, H, W'] in the format's dtype, W' >= W; strides are taken from the tensor (in bytes) and, when fmt is an
-    OutputSpec, its plane_stride is set from rgb_t.stride(1)."""
+    OutputSpec, its plane_stride is set from rgb_t.stride(1).
+    roi=(x, y, w, h) (for Context.blocks_to_rgb_device(..., roi=), with any fmt, not with a scale): rgb_t holds images of
+    the rectangle's size, w x h, instead of desc's."""
     spec = _as_spec(fmt)
+    r = _as_roi(roi, scale)
+    out_w, out_h = (r.width, r.height) if r is not None else (desc.width, desc.height)
     if spec is not None and spec.format != FMT_RGB_U8_HWC:
         assert scale == 1, "an output format cannot be combined with a scale"
         es = rgb_t.element_size()
-        assert rgb_t.dim() == 4 and rgb_t.shape[1] == 3 and rgb_t.shape[2] >= desc.height and rgb_t.shape[3] >= desc.width and rgb_t.stride(3) == 1
+        assert rgb_t.dim() == 4 and rgb_t.shape[1] == 3 and rgb_t.shape[2] >= out_h and rgb_t.shape[3] >= out_w and rgb_t.stride(3) == 1
         b = DeviceBatch()
         b.desc = desc
         b.n_images = n_images
@@ -670,8 +740,9 @@ def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, sha
         if isinstance(fmt, OutputSpec):
             fmt.plane_stride = rgb_t.stride(1) * es
         return b
-    if scale != 1:
-        out_w, out_h = scaled_size(desc.width, desc.height, scale)
+    if scale != 1 or r is not None:
+        if r is None:
+            out_w, out_h = scaled_size(desc.width, desc.height, scale)
         assert rgb_t.shape[1] >= out_h and (rgb_row_stride or rgb_t.stride(1)) >= 3 * out_w, "rgb_t is smaller than the scaled images"
     b = DeviceBatch()
     b.desc = desc

@@ -529,8 +529,10 @@ namespace {
 // The pixel launch of every route -- the public device seams below and the staging ring's submissions -- in three
 // steps: argument validation, tile planning, the launch.  `plan` (jb_plan.h) says what the pixels look like: scale 1,
 // format 0 is exactly the launch jb_blocks_to_rgb_device has always made; scale 2, 4, 8 the row-bound tiling with the
-// area-reduced store stage; a planar format the row-bound tiling with the planar store stage.  The batch's row / image
-// strides describe the output: the reduced image when scale > 1, one plane's rows with a planar format.
+// area-reduced store stage; a planar format the row-bound tiling with the planar store stage; a rectangle (plan.has_roi)
+// the row-bound tiling over the MCUs it touches with the ROI store stage, in any format.  The batch's row / image
+// strides describe the output: the reduced image when scale > 1, one plane's rows with a planar format, images of the
+// rectangle's size with a rectangle (plan.out_w x plan.out_h in every case).
 
 // 1. validation: the batch against the plan; g: the frame's geometry; plane_stride: bytes between the planes (0: interleaved)
 int seam_check(jb_ctx *ctx, const jb_device_batch *b, const JbOutPlan &plan, const char *fn, jb_geometry *g, int64_t *plane_stride) {
@@ -542,16 +544,16 @@ int seam_check(jb_ctx *ctx, const jb_device_batch *b, const JbOutPlan &plan, con
   if (plan.status != JB_OK) return fail(ctx, plan.status, "%s: %s", fn, plan.why);
   *plane_stride = 0;
   if (plan.planar) {
-    if (jb_output_spec_check(&plan.spec, b->desc.height, b->rgb_row_stride) != JB_OK)
+    if (jb_output_spec_check(&plan.spec, plan.out_h, b->rgb_row_stride) != JB_OK)
       return fail(ctx, JB_ERR_GEOMETRY, "%s: bad output spec (reserved, plane_stride < row stride * height, or scale / bias not finite)", fn);
-    *plane_stride = plan.spec.plane_stride ? plan.spec.plane_stride : b->rgb_row_stride * (int64_t)b->desc.height;
+    *plane_stride = plan.spec.plane_stride ? plan.spec.plane_stride : b->rgb_row_stride * (int64_t)plan.out_h;
   }
   if (b->rgb_row_stride < plan.row_stride)
     return fail(ctx, JB_ERR_GEOMETRY, "rgb_row_stride %lld < %s", (long long)b->rgb_row_stride, plan.planar ? "width * element size" : "3*width");
   if (plan.planar) {
     if (((uintptr_t)b->d_rgb | (uint64_t)b->rgb_row_stride | (uint64_t)*plane_stride | (uint64_t)(b->n_images > 1 ? b->rgb_image_stride : 0)) & (uint64_t)(plan.esize - 1))
       return fail(ctx, JB_ERR_GEOMETRY, "%s: f32 / f16 output wants the pointer and every stride to be multiples of the element size", fn);
-    if (b->n_images > 1 && b->rgb_image_stride < 2 * *plane_stride + b->rgb_row_stride * (int64_t)b->desc.height)
+    if (b->n_images > 1 && b->rgb_image_stride < 2 * *plane_stride + b->rgb_row_stride * (int64_t)plan.out_h)
       return fail(ctx, JB_ERR_GEOMETRY, "image strides smaller than one image");
   }
   if (((uintptr_t)b->d_coef & 15) || (b->coef_image_stride & 15))
@@ -567,6 +569,23 @@ int seam_check(jb_ctx *ctx, const jb_device_batch *b, const JbOutPlan &plan, con
 // frame fields are set)
 int seam_tiles(jb_ctx *ctx, const jb_device_batch *b, const jb_geometry &g, const JbOutPlan &plan, JbLaunch &p) {
   const int per_tile = jbk_mcus_per_tile(b->desc.hs, b->desc.vs);
+  if (plan.has_roi) {
+    // only the MCUs the rectangle touches: the grid's origin is the MCU that holds its first pixel, one tile row per
+    // touched MCU row, row-bound tiles from the origin's column on (always the 192-lane kernel's ROI instantiation)
+    const int mw = 8 * b->desc.hs, mh = 8 * b->desc.vs;
+    const jb_roi &r = plan.roi;
+    p.roi = 1;
+    p.roi_x = r.x, p.roi_y = r.y, p.roi_w = r.width, p.roi_h = r.height;
+    p.roi_mx = r.x / mw, p.roi_my = r.y / mh;
+    const int roi_mcus_x = (r.x + r.width - 1) / mw - p.roi_mx + 1, roi_mcus_y = (r.y + r.height - 1) / mh - p.roi_my + 1;
+    p.tiles_per_row = (roi_mcus_x + per_tile - 1) / per_tile;
+    p.tiles_per_image = roi_mcus_y * p.tiles_per_row;  // (at most the whole image's: no overflow)
+    const int64_t n_tiles = (int64_t)b->n_images * p.tiles_per_image;
+    if (n_tiles > 0x7fffffffLL) return fail(ctx, JB_ERR_CAPACITY, "batch too large for one launch (%lld tiles)", (long long)n_tiles);
+    p.n_tiles = (int32_t)n_tiles;
+    p.fast_store = 1;  // (the ROI stage does not look at it)
+    return JB_OK;
+  }
   p.tiles_per_row = (g.mcus_x + per_tile - 1) / per_tile;
   // JPEGBLK_ROW_TILING=1 (debug / A-B knob) forces the row-bound tiling; the scaled and planar stages only exist in it
   const bool force_row = ctx->knobs.row_tiling || plan.scale > 1 || plan.planar;
@@ -655,6 +674,10 @@ int jb_blocks_to_rgb_device_scaled(jb_ctx *ctx, const jb_device_batch *b, int de
 int jb_blocks_to_rgb_device_fmt(jb_ctx *ctx, const jb_device_batch *b, const jb_output_spec *spec, void *stream) {
   if (ctx && !spec) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_fmt: spec is NULL");
   return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec), "jb_blocks_to_rgb_device_fmt");
+}
+
+int jb_blocks_to_rgb_device_roi(jb_ctx *ctx, const jb_device_batch *b, const jb_roi *roi, const jb_output_spec *spec, void *stream) {
+  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, roi), "jb_blocks_to_rgb_device_roi");
 }
 
 int jb_ctx_device(const jb_ctx *ctx) { return ctx ? ctx->device : -1; }

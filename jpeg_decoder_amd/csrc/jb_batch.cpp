@@ -123,15 +123,21 @@ int available_cpus() {
   return n;
 }
 
-// What a decoder has been asked to deliver (jb_batch_decoder_set_scale, jb_batch_decoder_set_output_format): ONE value on
-// the decoder, copied to its parts, its twin and every run.  Never a format other than 0 with a scale other than 1.
+// What a decoder has been asked to deliver (jb_batch_decoder_set_scale, jb_batch_decoder_set_output_format,
+// jb_batch_decoder_set_roi): ONE value on the decoder, copied to its parts, its twin and every run.  Never a format other
+// than 0 or a rectangle with a scale other than 1.
 struct OutputRequest {
   int scale = 1;
   jb_output_spec spec = {};  // format 0: interleaved uint8
-  // can it be had at all?  The plan function decides (jb_plan.h), here for an image of one pixel
+  bool has_roi = false;      // one rectangle for every image
+  jb_roi roi = {};
+  const jb_roi *roi_ptr() const { return has_roi ? &roi : nullptr; }
+  // can it be had at all?  The plan function decides (jb_plan.h), here for an image of one pixel -- with a rectangle,
+  // for the largest frame there is (JB_ERR_GEOMETRY: no frame holds the rectangle)
   int status() const {
-    const jb_image_desc one = {1, 1, 1, 1, {0, 0, 0}, 0};
-    return jb_out_plan_(&one, scale, &spec).status;
+    const int32_t n = has_roi ? 65535 : 1;
+    const jb_image_desc one = {n, n, 1, 1, {0, 0, 0}, 0};
+    return jb_out_plan_(&one, scale, &spec, roi_ptr()).status;
   }
 };
 
@@ -322,7 +328,7 @@ void parse_one(Parsed &p, const OutputRequest &out) {
     p.error = jb_last_error(nullptr);
     return;
   }
-  p.plan = jb_out_plan_(&p.desc, out.scale, &out.spec);
+  p.plan = jb_out_plan_(&p.desc, out.scale, &out.spec, out.roi_ptr());
   p.status = p.plan.status;
   if (p.status == JB_OK) p.geo.rgb_bytes = p.plan.image_bytes;
   else p.error = p.plan.why;
@@ -1319,7 +1325,8 @@ extern "C" int jb_batch_decoder_set_scale(jb_batch_decoder *d, int denom) {
   if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_scale: batches are in flight (collect them first)");
   OutputRequest out = d->out;
   out.scale = denom;
-  if (out.status() == JB_ERR_UNSUPPORTED) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_scale: a planar output format is set: it cannot be combined with a scale");
+  if (out.status() == JB_ERR_UNSUPPORTED)
+    return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_scale: a planar output format or a rectangle is set: it cannot be combined with a scale");
   set_output_all(d, out);
   return JB_OK;
 }
@@ -1334,6 +1341,20 @@ extern "C" int jb_batch_decoder_set_output_format(jb_batch_decoder *d, const jb_
   out.spec = *spec;
   if (out.status() == JB_ERR_UNSUPPORTED)
     return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_output_format: the decoder's scale is not 1: a planar output format cannot be combined with it");
+  set_output_all(d, out);
+  return JB_OK;
+}
+
+extern "C" int jb_batch_decoder_set_roi(jb_batch_decoder *d, const jb_roi *roi) {
+  if (!d) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_set_roi: decoder is NULL");
+  if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_roi: batches are in flight (collect them first)");
+  OutputRequest out = d->out;
+  out.has_roi = roi != nullptr;
+  out.roi = roi ? *roi : jb_roi{};
+  const int st = out.status();
+  if (st == JB_ERR_UNSUPPORTED)
+    return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_roi: the decoder's scale is not 1: a rectangle cannot be combined with it");
+  if (st != JB_OK) return jb_fail_(nullptr, st, "jb_batch_decoder_set_roi: no frame can hold this rectangle");
   set_output_all(d, out);
   return JB_OK;
 }

@@ -437,9 +437,10 @@ int jb_entropy_decode_mt(const uint8_t *jpeg, size_t jpeg_bytes, jb_image_desc *
 }
 
 // Every jb_decode_memory* and jb_decode_file*: denom 1, 2, 4, 8 (checked by the caller); spec: null or format 0
-// (interleaved uint8) or a checked planar spec.  The output's sizes come from the plan of the frame (jb_plan.h).
+// (interleaved uint8) or a checked planar spec; roi: null or a rectangle of the frame (denom 1).  The output's sizes come
+// from the plan of the frame (jb_plan.h).
 static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, int denom, const jb_output_spec *spec,
-                              uint8_t **rgb, int32_t *width, int32_t *height) {
+                              uint8_t **rgb, int32_t *width, int32_t *height, const jb_roi *roi = nullptr) {
   if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_memory: ctx is NULL");
   if (!jpeg || !rgb || !width || !height) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_memory: NULL pointer");
   *rgb = nullptr;
@@ -470,7 +471,7 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
       if (jb_huff_prepare_(jpeg, jpeg_bytes, job.get(), nullptr, knobs.chunk_bytes) == JB_OK && jb_huff_worth_it_(*job, min_int) &&
           (forced || job->scan_len >= kAutoDeviceScan)) {
         const double t1 = timing ? now() : 0;
-        const JbOutPlan plan = jb_out_plan_(&job->desc, denom, spec);
+        const JbOutPlan plan = jb_out_plan_(&job->desc, denom, spec, roi);
         if (plan.status != JB_OK) return jb_fail_(ctx, plan.status, plan.why);
         uint8_t *out = jb_alloc_pixels_((size_t)plan.image_bytes);
         if (!out) return jb_fail_(ctx, JB_ERR_CAPACITY, "out of host memory");
@@ -497,7 +498,7 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
   jb_geometry g;
   rc = jb_geometry_of(&desc, &g);
   if (rc) return jb_fail_(ctx, rc, "bad frame geometry");
-  const JbOutPlan plan = jb_out_plan_(&desc, denom, spec);
+  const JbOutPlan plan = jb_out_plan_(&desc, denom, spec, roi);
   if (plan.status != JB_OK) return jb_fail_(ctx, plan.status, plan.why);
   // the staging ring follows the frame (a context sized for another image, or created with (0,0))
   rc = jb_ctx_reserve(ctx, (size_t)g.coef_bytes, (size_t)plan.image_bytes);
@@ -546,6 +547,17 @@ int jb_decode_memory_fmt(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, co
   return decode_memory_impl(ctx, jpeg, jpeg_bytes, 1, spec, (uint8_t **)out, width, height);
 }
 
+// a rectangle of the same decode ("region of interest", include/jpegblk.h); spec: null = interleaved uint8
+int jb_decode_memory_roi(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, const jb_roi *roi, const jb_output_spec *spec,
+                         void **out, int32_t *width, int32_t *height) {
+  if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_memory_roi: ctx is NULL");
+  if (!roi || !out) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_memory_roi: NULL pointer");
+  *out = nullptr;
+  if (spec && (jb_output_spec_check(spec, 1, 1 << 20) != JB_OK || (spec->format != JB_FMT_RGB_U8_HWC && spec->plane_stride != 0)))
+    return jb_fail_(ctx, JB_ERR_GEOMETRY, "jb_decode_memory_roi: bad output spec (unknown format, reserved or plane_stride not 0, scale / bias not finite)");
+  return decode_memory_impl(ctx, jpeg, jpeg_bytes, 1, spec, (uint8_t **)out, width, height, roi);
+}
+
 // the file's bytes; fn: the entry point's name, for the error text
 static int read_file(jb_ctx *ctx, const char *fn, const char *path, std::vector<uint8_t> &buf) {
   if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, (std::string(fn) + ": ctx is NULL").c_str());
@@ -575,6 +587,15 @@ int jb_decode_file_fmt(jb_ctx *ctx, const char *path, const jb_output_spec *spec
   std::vector<uint8_t> buf;
   const int rc = read_file(ctx, "jb_decode_file_fmt", path, buf);
   return rc ? rc : jb_decode_memory_fmt(ctx, buf.data(), buf.size(), spec, out, width, height);
+}
+
+int jb_decode_file_roi(jb_ctx *ctx, const char *path, const jb_roi *roi, const jb_output_spec *spec, void **out, int32_t *width,
+                       int32_t *height) {
+  if (ctx && (!roi || !out)) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_file_roi: NULL pointer");
+  if (ctx) *out = nullptr;
+  std::vector<uint8_t> buf;
+  const int rc = read_file(ctx, "jb_decode_file_roi", path, buf);
+  return rc ? rc : jb_decode_memory_roi(ctx, buf.data(), buf.size(), roi, spec, out, width, height);
 }
 
 }  // extern "C"

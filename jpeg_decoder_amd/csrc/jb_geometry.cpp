@@ -1,6 +1,7 @@
 // jb_geometry.cpp -- the host-only arithmetic of the ABI (include/jpegblk.h): frame geometry and
 // quantisation-table resolution.  No HIP dependency, so the front end can be built and fuzzed on
 // a CPU-only toolchain with sanitizers (tools/fuzz/).
+#include <cstdio>
 #include <cstring>
 
 #include "../../include/jpegblk.h"
@@ -75,6 +76,20 @@ int jb_output_spec_check(const jb_output_spec *s, int32_t height, int64_t row_st
   return JB_OK;
 }
 
+// does the rectangle lie in a W x H image?  (64-bit sums: x = INT32_MAX is refused, not wrapped)
+static bool jb_roi_fits_(const jb_roi *r, int32_t width, int32_t height) {
+  return r->x >= 0 && r->y >= 0 && r->width >= 1 && r->height >= 1 && (int64_t)r->x + r->width <= width &&
+         (int64_t)r->y + r->height <= height;
+}
+
+int jb_roi_check(const jb_image_desc *d, const jb_roi *roi) {
+  if (!d || !roi) return JB_ERR_NULL;
+  jb_geometry g;
+  const int rc = jb_geometry_of(d, &g);
+  if (rc != JB_OK) return rc;
+  return jb_roi_fits_(roi, d->width, d->height) ? JB_OK : JB_ERR_GEOMETRY;
+}
+
 int jb_resolve_qtabs(const jb_image_desc *d, const uint16_t *qtabs, int32_t *out192) {
   if (!d || !qtabs || !out192) return JB_ERR_NULL;
   for (int c = 0; c < 3; c++) {
@@ -87,8 +102,8 @@ int jb_resolve_qtabs(const jb_image_desc *d, const uint16_t *qtabs, int32_t *out
 
 }  // extern "C"
 
-// jb_plan.h: the only place that turns (frame, scale, spec) into the output's sizes and strides
-JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *spec) {
+// jb_plan.h: the only place that turns (frame, scale, spec, rectangle) into the output's sizes and strides
+JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *spec, const jb_roi *roi) {
   JbOutPlan p;
   memset(&p, 0, sizeof p);
   auto refuse = [&p](int status, const char *why) {
@@ -106,6 +121,17 @@ JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *
   const int esize = spec ? jb_format_esize_(spec->format) : 1;
   if (esize == 0) return refuse(JB_ERR_GEOMETRY, "unknown output format");
   if (spec && scale != 1) return refuse(JB_ERR_UNSUPPORTED, "a planar output format cannot be combined with a scale");
+  if (roi) {
+    if (!jb_roi_fits_(roi, d->width, d->height)) {
+      static thread_local char text[160];
+      snprintf(text, sizeof text, "the rectangle %d x %d at (%d, %d) does not lie in the %d x %d image", roi->width, roi->height,
+               roi->x, roi->y, d->width, d->height);
+      return refuse(JB_ERR_GEOMETRY, text);
+    }
+    if (scale != 1) return refuse(JB_ERR_UNSUPPORTED, "a rectangle cannot be combined with a scale");
+    out_w = roi->width, out_h = roi->height;
+    p.has_roi = true, p.roi = *roi;
+  }
   p.why = "";
   p.scale = scale;
   p.out_w = out_w, p.out_h = out_h;

@@ -29,6 +29,13 @@ struct JbLaunch {
   int32_t format;             // JB_FMT_* of include/jpegblk.h
   int64_t rgb_plane_stride;   // bytes
   float scale[3], bias[3];    // float formats: value = (float)u8 * scale[c] + bias[c]
+  // region of interest only (roi = 1; every other launch leaves these 0): the tile grid covers the MCUs the rectangle
+  // touches -- tiles_per_row tiles from MCU column roi_mx on, tiles_per_image / tiles_per_row MCU rows from roi_my on;
+  // mcus_x / mcus_y, width / height stay the full image's -- and p.rgb and its strides describe the roi_w x roi_h output
+  int32_t roi;                // 1: the ROI store stage (row-bound tiling, scale 1, any format)
+  int32_t roi_x, roi_y;       // the rectangle, in pixels of the full-size image
+  int32_t roi_w, roi_h;
+  int32_t roi_mx, roi_my;     // the MCU that holds (roi_x, roi_y): roi_x / (8 * hs), roi_y / (8 * vs)
 };
 
 // MCUs covered by one workgroup (a tile is 192 coded blocks in 4:4:4 and 4:2:0, 256 in 4:2:2 and 4:4:0): 64 / 32 / 64 / 64.
@@ -43,7 +50,8 @@ int jbk_linear_ok(int hs, int vs, int mcus_x);
 // JB_FMT_RGB_U8_CHW / _F32_CHW / _F16_CHW: the same kernel with a planar store stage -- p.rgb, p.rgb_row_stride,
 // p.rgb_plane_stride and p.rgb_image_stride describe three planes of p.height rows of p.width elements per image,
 // p.scale / p.bias the float formats' affine map.  Either exists in the row-bound tiling only (p.linear = p.small_grid
-// = 0) and not together: anything else is hipErrorInvalidValue.
+// = 0) and not together: anything else is hipErrorInvalidValue.  p.roi = 1: the same kernel with the ROI store stage, for
+// scale 1 and any p.format, row-bound tiling only.
 hipError_t jbk_launch(const JbLaunch &p, int hs, int vs, int scale, hipStream_t stream);
 const char *jbk_kernel_name(int hs, int vs);
 

@@ -376,7 +376,10 @@ struct LaneMap {
 // "scaled" below).  p.width / p.height stay the full image's; p.rgb and its strides describe the reduced image.
 // FORMAT = 1, 2, 3 (JB_FMT_RGB_U8_CHW, _F32_CHW, _F16_CHW; row-bound tiling only, SCALE = 1): the planar output
 // (jbk_launch with p.format set) -- again only what is stored differs (see "planar" below): the u8 values are those of FORMAT = 0.
-template <int HS, int VS, bool MIXQ, bool LINEAR, bool STAGED = false, int SCALE = 1, int FORMAT = 0>
+// ROI = true (jbk_launch with p.roi set; row-bound tiling only, SCALE = 1, any FORMAT): the rectangle p.roi_x, p.roi_y,
+// p.roi_w, p.roi_h of the image in that format -- the grid covers only the MCUs the rectangle touches, and the store
+// stage (see "region of interest" below) writes only the pixels inside it.
+template <int HS, int VS, bool MIXQ, bool LINEAR, bool STAGED = false, int SCALE = 1, int FORMAT = 0, bool ROI = false>
 // (5 waves/SIMD are asked for where that costs no spill: 4:4:4 and 4:4:0; forcing it on 4:2:0 or
 // 4:2:2 spills and measured 9 % slower; the scaled 4:4:0 instantiations spill at 5 too)
 __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS == 1)) ? 5 : 1) void jb_tile_kernel(const JbLaunch p) {
@@ -385,6 +388,7 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
                 "the scaled store stage is an instantiation of the row-bound tiling");
   static_assert(FORMAT == 0 || (!LINEAR && !STAGED && SCALE == 1 && FORMAT >= 1 && FORMAT <= 3),
                 "the planar store stage is an instantiation of the full-size row-bound tiling");
+  static_assert(!ROI || (!LINEAR && !STAGED && SCALE == 1), "the ROI store stage is an instantiation of the full-size row-bound tiling");
   using LM = LaneMap<HS, VS>;
   constexpr int kTileBlocks = LM::TB;
   constexpr int kStripBytes = kTileBlocks * 128;  // half of the tile's f32 samples: 24 or 32 KiB
@@ -434,6 +438,9 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
   } else {
     my = rem / p.tiles_per_row;
     mx0 = (rem - my * p.tiles_per_row) * MCUS;
+    // region of interest: the tile grid's origin is the MCU that holds the rectangle's first pixel; the coefficient
+    // address below keeps the full image's mcus_x as its row pitch
+    if constexpr (ROI) my += p.roi_my, mx0 += p.roi_mx;
     nvalid = min(MCUS, p.mcus_x - mx0);
   }
   const int last_block = nvalid * NB - 1;
@@ -754,6 +761,107 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
             const int voff = (x / SCALE) * 3;
             __builtin_amdgcn_raw_buffer_store_b16((uint16_t)(o[0] | o[1] << 8), rsrc, voff, 0, JB_STORE_AUX);
             __builtin_amdgcn_raw_buffer_store_b8((uint8_t)o[2], rsrc, voff + 2, 0, JB_STORE_AUX);
+          }
+        }
+      }
+    } else if constexpr (ROI) {
+      // ---- region of interest: the pixels of [roi_x, roi_x + roi_w) x [roi_y, roi_y + roi_h), in any format ----
+      // The wave-iterations, LDS reads, colour transform and u8 conversion are those of the full-size stage (FORMAT = 0)
+      // or of the planar one; what differs is which of them are stored, and where.  Strip rows above or below the
+      // rectangle and segments left or right of it are skipped wave-uniformly.  Of a segment's 256 pixels the rectangle
+      // holds [a, b): the descriptor is based at pixel a's place in the output row and ends behind the last whole 4-pixel
+      // group, so its range check drops the lanes right of the rectangle; the lanes left of it (a negative offset from
+      // that base) get an offset past any range instead of the wrapped one.  The at most two lanes whose group the
+      // left or the right edge cuts (one lane for both when the rectangle starts and ends in one group) store their
+      // 1-3 inside pixels one by one.  Nothing outside the rectangle is written.  The byte-store knob is not looked at.
+      constexpr int IPR = TASKS_PER_ROW / 64;
+      constexpr int SEG_MCUS = 256 / (8 * HS);
+      constexpr int ES = FORMAT == 0 ? 3 : FORMAT == 1 ? 1 : FORMAT == 2 ? 4 : 2;  // bytes per pixel in a row (of a plane)
+      const int rx1 = p.roi_x + p.roi_w, ry1 = p.roi_y + p.roi_h;
+      for (int it = wave; it < TASKS / 64; it += kTileBlocks / 64) {
+        const int row = it / IPR, seg = it - row * IPR;
+        const int y = my * 8 * VS + phase * 4 + (row >> 2) * 8 + (row & 3);  // image row of the strip row
+        const int xseg = (mx0 + seg * SEG_MCUS) * 8 * HS;                    // image column of the segment
+        if (y < p.roi_y || y >= ry1 || xseg >= rx1 || xseg + 256 <= p.roi_x) continue;  // (wave-uniform)
+        const float4 Y = *(const float4 *)(lds + lane_y_off + row * (YW * 4) + seg * 1024);
+        float cb[4], cr[4];
+        const int coff = (row / VS) * (CW * 4) + seg * (1024 / HS);
+        load_chroma4<HS>(lds + CB_OFF + lane_c_off + coff, lds + CR_OFF + lane_c_off + coff, cb, cr);
+        const float yy[4] = {Y.x, Y.y, Y.z, Y.w};
+        float r[4], g[4], b[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          ycc_px(yy[i], cb[i], cr[i], r[i], g[i], b[i]);
+        }
+        const int a = max(p.roi_x - xseg, 0), e = min(rx1 - xseg, 256);  // segment pixels inside the rectangle: a < e
+        const int nrec = max((e & ~3) - a, 0) * ES;                       // bytes up to the end of the last whole group
+        uint8_t *const segp = img_rgb + (int64_t)(y - p.roi_y) * p.rgb_row_stride + (int64_t)(xseg + a - p.roi_x) * ES;
+        const int rel = lane_late * 4 - a;                    // the lane's first pixel, relative to pixel a
+        const int voff = rel >= 0 ? rel * ES : 0x40000000;    // (left of the rectangle: past any range, never wrapped)
+        // the edge groups: rare, so their lane tests go through an opaque copy and nothing of them is hoisted
+        const bool ragged = ((a | e) & 3) != 0;               // (wave-uniform)
+        int l4 = lane_late * 4;
+        if (ragged) asm volatile("" : "+v"(l4));
+        const bool cut = ragged && l4 < e && l4 + 4 > a && !(l4 >= a && l4 + 4 <= e);
+        if constexpr (FORMAT == 0) {
+          uint32_t w0, w1, w2;
+          pack12_rtz(r, g, b, w0, w1, w2);
+          const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(segp, 0, nrec, 0x00020000);
+          __builtin_amdgcn_raw_buffer_store_b96(u32x3_t{w0, w1, w2}, rsrc, voff, 0, JB_STORE_AUX);
+          if (cut) {
+            const __amdgpu_buffer_rsrc_t edge = __builtin_amdgcn_make_buffer_rsrc(segp, 0, (e - a) * ES, 0x00020000);
+            // the 12 packed bytes are r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3: pixel i is bytes 3i .. 3i+2
+            const uint32_t px[4] = {w0, w0 >> 24 | w1 << 8, w1 >> 16 | w2 << 16, w2 >> 8};
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+              if (l4 + i >= a && l4 + i < e) {
+                __builtin_amdgcn_raw_buffer_store_b16((uint16_t)px[i], edge, (l4 + i - a) * 3, 0, JB_STORE_AUX);
+                __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(px[i] >> 16), edge, (l4 + i - a) * 3 + 2, 0, JB_STORE_AUX);
+              }
+          }
+        } else {
+          uint32_t w[3];
+          pack_channels(r, g, b, w);  // w[c] = the u8 samples of channel c, pixels 0..3 (as the planar stage)
+#pragma unroll
+          for (int c = 0; c < 3; c++) {
+            uint8_t *const planep = segp + (int64_t)c * p.rgb_plane_stride;
+            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(planep, 0, nrec, 0x00020000);
+            const __amdgpu_buffer_rsrc_t edge = __builtin_amdgcn_make_buffer_rsrc(planep, 0, (e - a) * ES, 0x00020000);
+            if constexpr (FORMAT == 1) {
+              __builtin_amdgcn_raw_buffer_store_b32(w[c], rsrc, voff, 0, JB_STORE_AUX);
+              if (cut) {
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                  if (l4 + i >= a && l4 + i < e)
+                    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(w[c] >> (8 * i)), edge, l4 + i - a, 0, JB_STORE_AUX);
+              }
+            } else {
+              const float sc = p.scale[c], bi = p.bias[c];
+              float f[4];
+#pragma unroll
+              for (int i = 0; i < 4; i++) f[i] = (float)((w[c] >> (8 * i)) & 0xffu) * sc + bi;
+              if constexpr (FORMAT == 2) {
+                const uint32_t u[4] = {__builtin_bit_cast(uint32_t, f[0]), __builtin_bit_cast(uint32_t, f[1]),
+                                       __builtin_bit_cast(uint32_t, f[2]), __builtin_bit_cast(uint32_t, f[3])};
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{u[0], u[1], u[2], u[3]}, rsrc, voff, 0, JB_STORE_AUX);
+                if (cut) {
+#pragma unroll
+                  for (int i = 0; i < 4; i++)
+                    if (l4 + i >= a && l4 + i < e) __builtin_amdgcn_raw_buffer_store_b32(u[i], edge, (l4 + i - a) * 4, 0, JB_STORE_AUX);
+                }
+              } else {
+                // (_Float16)x is v_cvt_f16_f32: round to nearest even (never the packed round-toward-zero conversion)
+                uint32_t h[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) h[i] = (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f[i]);
+                __builtin_amdgcn_raw_buffer_store_b64(u32x2_t{h[0] | h[1] << 16, h[2] | h[3] << 16}, rsrc, voff, 0, JB_STORE_AUX);
+                if (cut) {
+#pragma unroll
+                  for (int i = 0; i < 4; i++)
+                    if (l4 + i >= a && l4 + i < e) __builtin_amdgcn_raw_buffer_store_b16((uint16_t)h[i], edge, (l4 + i - a) * 2, 0, JB_STORE_AUX);
+                }
+              }
+            }
           }
         }
       }
@@ -1081,10 +1189,10 @@ __global__ __launch_bounds__(64) void jb_small_kernel_16(const JbLaunch p) {
   jb_small_body<HS, VS>(p);
 }
 
-// Launches jb_tile_kernel<HS, VS, MIXQ, LINEAR, STAGED, SCALE, FORMAT>: every launch of the 192-lane kernel goes through
-// here.  SCALE != 1 (the area-reduced store stage) and FORMAT != 0 (the planar one) exist in the row-bound tiling only.
+// Launches jb_tile_kernel<HS, VS, MIXQ, LINEAR, STAGED, SCALE, FORMAT, ROI>: every launch of the 192-lane kernel goes through
+// here.  SCALE != 1 (the area-reduced store stage), FORMAT != 0 (the planar one) and ROI exist in the row-bound tiling only.
 // MIXQ is decided here, and MIXQ = true is only instantiated for a layout that can need it.
-template <int HS, int VS, int SCALE, int FORMAT, bool LINEAR = false, bool STAGED = false>
+template <int HS, int VS, int SCALE, int FORMAT, bool LINEAR = false, bool STAGED = false, bool ROI = false>
 static hipError_t launch_tile(const JbLaunch &p, hipStream_t stream) {
   using LM = LaneMap<HS, VS>;
   // does any wave hold two components whose tables may differ?  (never luma and chroma: jb_tile_kernel asserts it)
@@ -1096,15 +1204,23 @@ static hipError_t launch_tile(const JbLaunch &p, hipStream_t stream) {
   bool mixq = false;
   if constexpr (kCbCrMixed) {
     mixq = !p.chroma_q_equal;
-    if (mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, true, LINEAR, STAGED, SCALE, FORMAT>), grid, block, 0, stream, p);
+    if (mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, true, LINEAR, STAGED, SCALE, FORMAT, ROI>), grid, block, 0, stream, p);
   }
-  if (!mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, false, LINEAR, STAGED, SCALE, FORMAT>), grid, block, 0, stream, p);
+  if (!mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, false, LINEAR, STAGED, SCALE, FORMAT, ROI>), grid, block, 0, stream, p);
   return hipGetLastError();
 }
 
 // one layout: which store stage (scale, p.format) and which tiling (p.linear, p.staged)
 template <int HS, int VS>
 static hipError_t launch_layout(const JbLaunch &p, int scale, hipStream_t stream) {
+  if (p.roi) {  // the region of interest: its own store stage for every format, even when the rectangle is the whole image
+    if (p.linear || scale != 1) return hipErrorInvalidValue;  // (full-size row-bound tiling only)
+    if (p.format == 0) return launch_tile<HS, VS, 1, 0, false, false, true>(p, stream);
+    if (p.format == 1) return launch_tile<HS, VS, 1, 1, false, false, true>(p, stream);
+    if (p.format == 2) return launch_tile<HS, VS, 1, 2, false, false, true>(p, stream);
+    if (p.format == 3) return launch_tile<HS, VS, 1, 3, false, false, true>(p, stream);
+    return hipErrorInvalidValue;
+  }
   if (p.format == 0 && scale == 1) {
     // the linear tiling is a separate instantiation: where the row-bound tiling leaves no tile
     // ragged (mcus_x a multiple of the tile length, e.g. 4096- and 8192-pixel rows) the simpler
@@ -1151,7 +1267,7 @@ hipError_t jbk_launch(const JbLaunch &p, int hs, int vs, int scale, hipStream_t 
                                      : hs == 2 && vs == 1 ? jb_small_kernel_16<2, 1>
                                      : hs == 1 && vs == 2 ? jb_small_kernel_16<1, 2>
                                                           : nullptr;
-    if (!kernel || scale != 1 || p.format != 0) return hipErrorInvalidValue;
+    if (!kernel || scale != 1 || p.format != 0 || p.roi) return hipErrorInvalidValue;
     (void)hipGetLastError();
     hipLaunchKernelGGL(kernel, dim3(p.n_tiles), dim3(64), 0, stream, p);
     return hipGetLastError();

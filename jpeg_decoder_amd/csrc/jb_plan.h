@@ -8,20 +8,25 @@
 struct JbOutPlan {
   // JB_OK, or why this output cannot be had: JB_ERR_NULL (no descriptor), JB_ERR_GEOMETRY (scale not 1, 2, 4, 8; image
   // size outside 1..65535; unknown format; reserved != 0 on a format-0 spec), JB_ERR_UNSUPPORTED (a format other than 0
-  // with a scale other than 1) -- in that order.  Whoever uses a plan reports it where the old code checked the scale:
-  // behind the descriptor's own errors.  `why` is the text for jb_last_error; the other fields are 0 on failure.
+  // with a scale other than 1), JB_ERR_GEOMETRY (a rectangle that does not lie in the image), JB_ERR_UNSUPPORTED (a
+  // rectangle with a scale other than 1) -- in that order.  Whoever uses a plan reports it where the old code checked the
+  // scale: behind the descriptor's own errors.  `why` is the text for jb_last_error (of the last plan this thread made,
+  // when it names sizes); the other fields are 0 on failure.
   int status;
   const char *why;
   int32_t scale;          // 1, 2, 4, 8
   int32_t format;         // JB_FMT_*
-  int32_t out_w, out_h;   // ceil(W / scale) x ceil(H / scale)
+  int32_t out_w, out_h;   // ceil(W / scale) x ceil(H / scale); with a rectangle, its width x height
   int32_t esize;          // bytes per element
   bool planar;            // format != JB_FMT_RGB_U8_HWC: three planes of out_h rows
   int64_t row_stride;     // tight rows on the device: of a plane (out_w * esize) when planar, else 3 * out_w
   int64_t image_bytes;    // 3 * out_w * out_h * esize
+  bool has_roi;           // the output is the rectangle `roi` of the full-size image (scale 1): the ROI store stage, even
+  jb_roi roi;             // when the rectangle is the whole image; else all 0
   jb_output_spec spec;    // planar: the caller's spec (plane_stride, and scale / bias for the float formats); else zero
 };
 
 // spec: null or format 0 = interleaved uint8.  Beyond `reserved` on a format-0 spec, the spec's own fields (plane_stride
 // against a row stride, finite scale / bias) are jb_output_spec_check's, which needs the caller's strides.
-JbOutPlan jb_out_plan_(const jb_image_desc *desc, int scale, const jb_output_spec *spec);
+// roi: null = the whole image.
+JbOutPlan jb_out_plan_(const jb_image_desc *desc, int scale, const jb_output_spec *spec, const jb_roi *roi = nullptr);
