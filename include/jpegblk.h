@@ -62,6 +62,8 @@
  *   JPEGBLK_SMALL_GRID     1 = always the one-wave kernels (every layout has one), 0 = never (default: launches of
  *                          up to 8 workgroups per CU of the 192-lane kernel, e.g. one to four 1080p images, one 4096x4096 4:2:0)
  *   JPEGBLK_TIMING         1 | 2 | 3 = where one decode(bytes) / one device-entropy submission / one batch run spends its time (stderr)
+ *   JPEGBLK_RESIZE_TMP_BYTES  bytes of full-size intermediates one launch pair of a decode to a fixed output size may
+ *                          hold (default 128 MiB; more runs as sub-batches of whole images, one image at the least)
  *   JPEGBLK_HW_QUEUES      read when the library is LOADED: hardware queues to ask the HIP runtime for
  *                          (GPU_MAX_HW_QUEUES; default 16, 0 = the runtime's default).  Process-wide, and only
  *                          effective before HIP initialises: an application that initialises HIP first sets
@@ -316,6 +318,39 @@ int jb_decode_memory_roi(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, co
 int jb_decode_file_roi(jb_ctx *ctx, const char *path, const jb_roi *roi, const jb_output_spec *spec, void **out,
                        int32_t *width, int32_t *height);
 
+/* ---- fixed output size: decode to out_w x out_h, an exact area resize on the device ----
+ * With `src` = the full-size uint8 decode (iw x ih), or with a rectangle full[y : y + h, x : x + w], the result is defined
+ * on a common grid of iw * out_w units per axis: source column i covers [i * out_w, (i + 1) * out_w), output column j
+ * covers [j * iw, (j + 1) * iw), wx[j][i] is the integer length of their overlap (sum over i = iw); rows the same with
+ * wy, ih, out_h.  Per channel
+ *     S = sum_r sum_i wy[k][r] * wx[j][i] * src[r][i][c]      (an exact integer)
+ *     out_u8[k][j][c] = floor((S + floor(D / 2)) / D),  D = iw * ih
+ * -- one rounding, half up.  The same formula reduces, enlarges (a box filter: blocky) and mixes the two per axis;
+ * out_w = iw, out_h = ih gives src bit for bit; iw = k * out_w, ih = k * out_h with k = 2, 4, 8 gives the scaled output
+ * of scale k bit for bit; a constant image stays constant.  The planar formats apply to out_u8 exactly as they apply
+ * to a full-size decode (value = (float)u8 * scale[c] + bias[c]).  Any format, with or without a rectangle, never with
+ * a scale other than 1 (JB_ERR_UNSUPPORTED); out_w, out_h in 1..65535 (else JB_ERR_GEOMETRY).
+ * Two launches in stream order: the pixel kernel writes src as tight interleaved uint8 into a scratch the context
+ * owns (it grows on demand, which allocates: not inside a graph capture; one per stream that is used, each at most
+ * JPEGBLK_RESIZE_TMP_BYTES or one image), a second kernel reads it and writes the caller's buffer.  A batch whose
+ * intermediates exceed the cap runs as consecutive sub-batches of whole images.  The entropy stage still decodes the
+ * whole image. */
+/* JB_OK when the rectangle (NULL: the whole image) lies in the image and out_w, out_h are in 1..65535; JB_ERR_NULL for
+ * a null descriptor; the descriptor's own errors (jb_geometry_of) first, then the rectangle's, then the target's (both
+ * JB_ERR_GEOMETRY).  Pure host code. */
+int jb_resize_check(const jb_image_desc *desc, const jb_roi *roi, int32_t out_w, int32_t out_h);
+/* jb_blocks_to_rgb_device_roi at a fixed output size: d_rgb and the strides describe images of out_w x out_h (every
+ * alignment and stride that is legal for a full-size image of that size is legal here; nothing outside the out_w x
+ * out_h elements is written).  roi == NULL: the whole image.  spec == NULL: interleaved uint8. */
+int jb_blocks_to_rgb_device_resized(jb_ctx *ctx, const jb_device_batch *batch, const jb_roi *roi, int32_t out_w, int32_t out_h,
+                                    const jb_output_spec *spec, void *stream);
+/* jb_decode_memory_roi / jb_decode_file_roi at a fixed output size: *out holds jb_output_bytes(out_w, out_h, format)
+ * bytes (jb_free), *width / *height report out_w / out_h.  roi == NULL: the whole image.  spec == NULL: interleaved uint8. */
+int jb_decode_memory_resized(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, const jb_roi *roi, int32_t out_w, int32_t out_h,
+                             const jb_output_spec *spec, void **out, int32_t *width, int32_t *height);
+int jb_decode_file_resized(jb_ctx *ctx, const char *path, const jb_roi *roi, int32_t out_w, int32_t out_h,
+                           const jb_output_spec *spec, void **out, int32_t *width, int32_t *height);
+
 /* ---- host front end ("next" rows of the scope table; reference jpeg.cpp:67-446, 826-907,
  *      include/file.hpp, include/huffman.hpp) --------------------------------------------- */
 /* Parse a JFIF byte stream and Huffman-decode it into packed int16 blocks in the order
@@ -477,6 +512,14 @@ int jb_batch_decoder_set_output_format(jb_batch_decoder *dec, const jb_output_sp
  * flight; with JB_ERR_GEOMETRY when no frame could hold the rectangle; while the scale is not 1 (and
  * jb_batch_decoder_set_scale(!= 1) while a rectangle is set) with JB_ERR_UNSUPPORTED. */
 int jb_batch_decoder_set_roi(jb_batch_decoder *dec, const jb_roi *roi);
+/* One output size for every image of the batch decoder's later runs and submissions (see "fixed output size" above;
+ * (0, 0): the images' own sizes again).  widths / heights then report out_w / out_h and every output form holds
+ * jb_output_bytes(out_w, out_h, format) per image, so files of any size and layout give outputs of one size -- with a
+ * rectangle set as well, the rectangle of every file resized (a file it does not fit in gets JB_ERR_GEOMETRY and the
+ * batch goes on).  Applies to every device of a multi-device decoder and to both sides of submit / collect.  Refused
+ * with JB_ERR_STATE while a batch is in flight; with JB_ERR_GEOMETRY for a size outside 1..65535; while the scale is not
+ * 1 (and jb_batch_decoder_set_scale(!= 1) while a target size is set) with JB_ERR_UNSUPPORTED. */
+int jb_batch_decoder_set_resize(jb_batch_decoder *dec, int32_t out_w, int32_t out_h);
 /* Output sink replacing the reference's X11 window / unused BMP writer (display.hpp,
  * jpeg.cpp:462-509): binary PPM (P6). */
 int jb_write_ppm(const char *path, const uint8_t *rgb, int32_t width, int32_t height,

@@ -98,6 +98,28 @@ class Image {
     mcuHeightReal = g.mcu_h_real;
   }
 
+  // Beyond the reference: the picture (or, roi != nullptr, that rectangle of it) at out_w x out_h, an exact area resize
+  // on the device (jb_decode_file_resized).  image_width / image_height and rgb() are then the target's;
+  // mcuWidthReal / mcuHeightReal stay the frame's.
+  void readJPEG(int32_t out_w, int32_t out_h, const jb_roi *roi = nullptr) {
+    jb_free(rgb_);
+    rgb_ = nullptr;
+    int32_t w = 0, h = 0;
+    void *out = nullptr;
+    int rc = jb_decode_file_resized(ctx_->get(), path_.c_str(), roi, out_w, out_h, nullptr, &out, &w, &h);
+    if (rc) throw Error(rc, jb_last_error(ctx_->get()));
+    rgb_ = static_cast<uint8_t *>(out);
+    image_width = w;
+    image_height = h;
+    jb_image_desc d;
+    jb_geometry g;
+    rc = jb_ctx_last_desc(ctx_->get(), &d);
+    if (!rc) rc = jb_geometry_of(&d, &g);
+    if (rc) throw Error(rc, jb_last_error(nullptr));
+    mcuWidthReal = g.mcu_w_real;
+    mcuHeightReal = g.mcu_h_real;
+  }
+
   // The decoded picture: image_height rows of image_width R,G,B byte triples.  Equals
   // mcus[(y/8)*mcuWidthReal + x/8].{r,g,b}[(y%8)*8 + x%8] of the reference (display.hpp:19-34).
   const uint8_t *rgb() const { return rgb_; }

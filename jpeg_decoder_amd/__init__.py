@@ -11,9 +11,9 @@ loudly (ImportError / JbError).
 from .api import (JbError, Context, ImageDesc, Geometry, DeviceBatch, lib, lib_path, make_desc,
                   geometry_of, resolve_qtabs, entropy_decode, decode_batch, BatchDecoder, build_library, scaled_size,
                   OutputSpec, output_bytes, torch_batch, FMT_RGB_U8_HWC, FMT_RGB_U8_CHW, FMT_RGB_F32_CHW, FMT_RGB_F16_CHW,
-                  FMT_DTYPE, Roi, roi_check)
+                  FMT_DTYPE, Roi, roi_check, resize_check)
 
 __all__ = ["JbError", "Context", "ImageDesc", "Geometry", "DeviceBatch", "lib", "lib_path",
            "make_desc", "geometry_of", "resolve_qtabs", "entropy_decode", "decode_batch", "BatchDecoder", "build_library",
            "scaled_size", "OutputSpec", "output_bytes", "torch_batch", "FMT_RGB_U8_HWC", "FMT_RGB_U8_CHW", "FMT_RGB_F32_CHW",
-           "FMT_RGB_F16_CHW", "FMT_DTYPE", "Roi", "roi_check"]
+           "FMT_RGB_F16_CHW", "FMT_DTYPE", "Roi", "roi_check", "resize_check"]

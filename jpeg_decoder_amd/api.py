@@ -95,6 +95,25 @@ def roi_check(desc, roi):
     _check(lib().jb_roi_check(ctypes.byref(desc), ctypes.byref(_as_roi(roi))))
 
 
+def _as_resize(resize, scale=1):
+    """None / (w, h) -> (w, h) or None (None = the entry points without a target size).  A target size together with a
+    scale other than 1 is JbError(-9), raised here: no C entry point takes the pair."""
+    if resize is None:
+        return None
+    if scale != 1:
+        raise JbError(-9, "a target size (resize) cannot be combined with a scale")
+    w, h = resize
+    return int(w), int(h)
+
+
+def resize_check(desc, resize, roi=None):
+    """jb_resize_check: does the rectangle (None: the whole image) lie in the descriptor's image, and is the target
+    size (w, h) in 1..65535?  Raises JbError otherwise."""
+    r = _as_roi(roi)
+    w, h = _as_resize(resize)
+    _check(lib().jb_resize_check(ctypes.byref(desc), ctypes.byref(r) if r is not None else None, w, h))
+
+
 def _as_spec(fmt):
     """None / an int format / an OutputSpec -> OutputSpec or None (None = the entry points without a format)."""
     if fmt is None or isinstance(fmt, OutputSpec):
@@ -223,6 +242,11 @@ def lib():
     L.jb_decode_memory_roi.argtypes = [vp, vp, ctypes.c_size_t, pr, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.jb_decode_file_roi.argtypes = [vp, ctypes.c_char_p, pr, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.jb_batch_decoder_set_roi.argtypes = [vp, pr]
+    L.jb_resize_check.argtypes = [pd, pr, i32, i32]
+    L.jb_blocks_to_rgb_device_resized.argtypes = [vp, ctypes.POINTER(DeviceBatch), pr, i32, i32, ps, vp]
+    L.jb_decode_memory_resized.argtypes = [vp, vp, ctypes.c_size_t, pr, i32, i32, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.jb_decode_file_resized.argtypes = [vp, ctypes.c_char_p, pr, i32, i32, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.jb_batch_decoder_set_resize.argtypes = [vp, i32, i32]
     L.jb_write_ppm.argtypes = [ctypes.c_char_p, vp, i32, i32, i64]
     L.jb_write_bmp.argtypes = [ctypes.c_char_p, vp, i32, i32, i64]
     if L.jb_abi_version() != 1:
@@ -396,14 +420,21 @@ class Context:
         _check(lib().jb_wait(self._h, ticket), self._h)
 
     # -- the seam, device buffers ------------------------------------------------------------
-    def blocks_to_rgb_device(self, batch, stream=None, scale=1, fmt=None, roi=None):
+    def blocks_to_rgb_device(self, batch, stream=None, scale=1, fmt=None, roi=None, resize=None):
         """scale 2, 4, 8 (jb_blocks_to_rgb_device_scaled): the batch's d_rgb and strides describe images of
         scaled_size(desc.width, desc.height, scale).  fmt (an OutputSpec or a format number;
         jb_blocks_to_rgb_device_fmt): planar output -- the batch's rgb_row_stride is then a plane's.
         roi=(x, y, w, h) (jb_blocks_to_rgb_device_roi, with any fmt, not with a scale): the batch's d_rgb and strides
-        describe images of w x h, the rectangle of every image."""
+        describe images of w x h, the rectangle of every image.
+        resize=(w, h) (jb_blocks_to_rgb_device_resized, with any fmt, with or without roi, not with a scale): the batch's
+        d_rgb and strides describe images of w x h, the exact area resize of every image (or of its rectangle)."""
         spec = _as_spec(fmt)
         r = _as_roi(roi, scale)
+        t = _as_resize(resize, scale)
+        if t is not None:
+            _check(lib().jb_blocks_to_rgb_device_resized(self._h, ctypes.byref(batch), ctypes.byref(r) if r is not None else None,
+                                                         t[0], t[1], ctypes.byref(spec) if spec is not None else None, stream), self._h)
+            return
         if r is not None:
             _check(lib().jb_blocks_to_rgb_device_roi(self._h, ctypes.byref(batch), ctypes.byref(r),
                                                      ctypes.byref(spec) if spec is not None else None, stream), self._h)
@@ -420,13 +451,19 @@ class Context:
             _check(lib().jb_blocks_to_rgb_device_scaled(self._h, ctypes.byref(batch), scale, stream), self._h)
 
     # -- decode(path) -> RGB -----------------------------------------------------------------
-    def decode_file(self, path, scale=1, fmt=None, roi=None):
+    def decode_file(self, path, scale=1, fmt=None, roi=None, resize=None):
         """-> RGB [H, W, 3]; scale 2, 4, 8: the area-reduced image (jb_decode_file_scaled); fmt (OutputSpec or format
         number, jb_decode_file_fmt): [3, H, W] in the format's type for the planar formats; roi=(x, y, w, h)
-        (jb_decode_file_roi, with any fmt, not with a scale): that rectangle of the image."""
+        (jb_decode_file_roi, with any fmt, not with a scale): that rectangle of the image; resize=(w, h)
+        (jb_decode_file_resized, with any fmt, with or without roi, not with a scale): the image, or its rectangle, at w x h."""
         p, w, h = ctypes.c_void_p(), ctypes.c_int32(), ctypes.c_int32()
         spec = _as_spec(fmt)
         r = _as_roi(roi, scale)
+        t = _as_resize(resize, scale)
+        if t is not None:
+            rc = lib().jb_decode_file_resized(self._h, os.fsencode(path), ctypes.byref(r) if r is not None else None, t[0], t[1],
+                                              ctypes.byref(spec) if spec is not None else None, ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
+            return self._take_output(rc, p, w, h, spec)
         if r is not None:
             rc = lib().jb_decode_file_roi(self._h, os.fsencode(path), ctypes.byref(r), ctypes.byref(spec) if spec is not None else None,
                                           ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
@@ -447,20 +484,26 @@ class Context:
         return arr
 
     def _take_output(self, rc, p, w, h, spec):
-        """The array of a decode_*_roi call, its malloc'ed buffer released."""
+        """The array of a decode_*_roi / decode_*_resized call, its malloc'ed buffer released."""
         _check(rc, self._h)
         try:
             return _shape_output(p, w.value, h.value, spec).copy()
         finally:
             lib().jb_free(p)
 
-    def decode_memory(self, jpeg_bytes, scale=1, fmt=None, roi=None):
+    def decode_memory(self, jpeg_bytes, scale=1, fmt=None, roi=None, resize=None):
         """jb_decode_memory: a JFIF byte string -> RGB [H, W, 3] (front end + device seam); scale 2, 4, 8: the
-        area-reduced image (jb_decode_memory_scaled); fmt, roi: as decode_file (jb_decode_memory_fmt, jb_decode_memory_roi)."""
+        area-reduced image (jb_decode_memory_scaled); fmt, roi, resize: as decode_file (jb_decode_memory_fmt,
+        jb_decode_memory_roi, jb_decode_memory_resized)."""
         buf = np.frombuffer(jpeg_bytes, dtype=np.uint8)
         p, w, h = ctypes.c_void_p(), ctypes.c_int32(), ctypes.c_int32()
         spec = _as_spec(fmt)
         r = _as_roi(roi, scale)
+        t = _as_resize(resize, scale)
+        if t is not None:
+            rc = lib().jb_decode_memory_resized(self._h, _ptr(buf), buf.size, ctypes.byref(r) if r is not None else None, t[0], t[1],
+                                                ctypes.byref(spec) if spec is not None else None, ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
+            return self._take_output(rc, p, w, h, spec)
         if r is not None:
             rc = lib().jb_decode_memory_roi(self._h, _ptr(buf), buf.size, ctypes.byref(r), ctypes.byref(spec) if spec is not None else None,
                                             ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
@@ -488,11 +531,14 @@ class BatchDecoder:
     (jb_batch_decoder_set_scale): every image comes out area-reduced.  fmt (an OutputSpec or a format number;
     jb_batch_decoder_set_output_format): every image comes out in that format, [3, H, W] for the planar ones.
     roi=(x, y, w, h) (jb_batch_decoder_set_roi; with any fmt, not with a scale): every image comes out as that rectangle of
-    itself, so files of different sizes give outputs of one size."""
+    itself, so files of different sizes give outputs of one size.  resize=(w, h) (jb_batch_decoder_set_resize; with any
+    fmt, with or without roi, not with a scale): every image, or its rectangle, comes out at w x h, an exact area resize
+    on the device, so files of any size and layout give outputs of one size."""
 
     def __init__(self, n_threads=8, device=0, max_coef_bytes=0, max_rgb_bytes=0, arena_bytes=0, devices=None, scale=1, fmt=None,
-                 roi=None):
+                 roi=None, resize=None):
         _as_roi(roi, scale)   # (roi with a scale: JbError(-9) before anything is created)
+        _as_resize(resize, scale)   # (and resize with a scale)
         self._h = ctypes.c_void_p()
         if devices is not None:
             ids = (ctypes.c_int * len(devices))(*devices)
@@ -514,6 +560,8 @@ class BatchDecoder:
                 self.set_output_format(fmt)
             if roi is not None:
                 self.set_roi(roi)
+            if resize is not None:
+                self.set_resize(resize)
         except JbError:
             self.close()
             raise
@@ -532,9 +580,15 @@ class BatchDecoder:
         r = _as_roi(roi)
         _check(lib().jb_batch_decoder_set_roi(self._h, ctypes.byref(r) if r is not None else None))
 
+    def set_resize(self, resize):
+        """jb_batch_decoder_set_resize: one output size (w, h) for every image of later runs and submissions; None or
+        (0, 0): the images' own sizes again (JbError -7 while a batch is in flight, -9 when the decoder's scale is not 1)."""
+        w, h = _as_resize(resize) or (0, 0)
+        _check(lib().jb_batch_decoder_set_resize(self._h, w, h))
+
     def set_scale(self, scale):
         """jb_batch_decoder_set_scale: output at 1/scale for later runs and submissions (JbError -7 while a batch
-        is in flight)."""
+        is in flight, -9 while a planar format, a rectangle or a target size is set)."""
         _check(lib().jb_batch_decoder_set_scale(self._h, scale))
 
     @property
@@ -578,7 +632,7 @@ class BatchDecoder:
 
     def run_to_tensor(self, paths, out):
         """Decode files of ONE size (or, with a rectangle set, of any size the rectangle fits in: out is then
-        [N, 3, h, w] of the rectangle) straight into a caller-supplied CUDA tensor through the device-output route:
+        [N, 3, h, w] of the rectangle; with a target size set, of any size: out is [N, 3, h, w] of the target) straight into a caller-supplied CUDA tensor through the device-output route:
         out is [N, 3, H, W] (planar formats; [N, H, W, 3] for format 0), contiguous, of the decoder's format's dtype, on
         the decoder's device, N = len(paths).  -> (out, statuses, times).  An image whose size does not match out (or
         that fails to decode) gets a non-zero status (JB_ERR_GEOMETRY = -2 for the size) and its slice of out is left
@@ -710,7 +764,8 @@ def decode_batch(paths, n_threads=8, device=0, keep_pixels=True, on_image=None, 
     return out, list(st), t
 
 
-def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, shared_qtabs=True, scale=1, fmt=None, roi=None):
+def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, shared_qtabs=True, scale=1, fmt=None, roi=None,
+                resize=None):
     """DeviceBatch over torch CUDA tensors (plumbing): coef_t int16 [n_images, n_blocks, 64],
     qtabs_t int32 [3,64] (shared) or [n_images,3,64], rgb_t uint8 [n_images, H, row_stride].
     scale 2, 4, 8: rgb_t holds the reduced images, [n_images, ceil(H/scale), row_stride], for
@@ -719,10 +774,13 @@ def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, sha
     [n_images, 3, H, W'] in the format's dtype, W' >= W; strides are taken from the tensor (in bytes) and, when fmt is an
     OutputSpec, its plane_stride is set from rgb_t.stride(1).
     roi=(x, y, w, h) (for Context.blocks_to_rgb_device(..., roi=), with any fmt, not with a scale): rgb_t holds images of
-    the rectangle's size, w x h, instead of desc's."""
+    the rectangle's size, w x h, instead of desc's.
+    resize=(w, h) (for Context.blocks_to_rgb_device(..., resize=), with any fmt and roi, not with a scale): rgb_t holds
+    images of w x h."""
     spec = _as_spec(fmt)
     r = _as_roi(roi, scale)
-    out_w, out_h = (r.width, r.height) if r is not None else (desc.width, desc.height)
+    t = _as_resize(resize, scale)
+    out_w, out_h = t if t is not None else (r.width, r.height) if r is not None else (desc.width, desc.height)
     if spec is not None and spec.format != FMT_RGB_U8_HWC:
         assert scale == 1, "an output format cannot be combined with a scale"
         es = rgb_t.element_size()
@@ -740,8 +798,8 @@ def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, sha
         if isinstance(fmt, OutputSpec):
             fmt.plane_stride = rgb_t.stride(1) * es
         return b
-    if scale != 1 or r is not None:
-        if r is None:
+    if scale != 1 or r is not None or t is not None:
+        if r is None and t is None:
             out_w, out_h = scaled_size(desc.width, desc.height, scale)
         assert rgb_t.shape[1] >= out_h and (rgb_row_stride or rgb_t.stride(1)) >= 3 * out_w, "rgb_t is smaller than the scaled images"
     b = DeviceBatch()

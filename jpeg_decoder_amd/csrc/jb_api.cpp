@@ -155,6 +155,16 @@ struct jb_ctx {
   // next pair then overlaps nothing).
   std::atomic<uint64_t> dl_age{0};
   std::string dl_error;     // (under dl->mu)
+  // "Fixed output size": the tight uint8 intermediates between the pixel kernel and jb_resample_kernel, one scratch per
+  // stream that has carried such a launch (the two launches and the next pair on the same stream are ordered; launches
+  // on different streams of the ring run side by side and must not share one).  Each grows on demand, is reused, and
+  // holds at most knobs.resize_tmp_bytes (or one image, when that is larger) plus the slack the kernel's loads want.
+  struct Tmp {
+    void *d = nullptr;
+    size_t cap = 0;
+  };
+  std::mutex tmp_mu;
+  std::map<hipStream_t, Tmp> tmp;
 };
 
 namespace {
@@ -492,6 +502,8 @@ void jb_ctx_destroy(jb_ctx *ctx) {
     if (s.h_status) (void)hipHostFree(s.h_status);
     if (s.d_status) (void)hipFree(s.d_status);
   }
+  for (auto &kv : ctx->tmp)
+    if (kv.second.d) (void)hipFree(kv.second.d);  // (hipFree waits for the device: launches on a caller's stream included)
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   delete ctx;
@@ -627,8 +639,89 @@ int seam_tiles(jb_ctx *ctx, const jb_device_batch *b, const jb_geometry &g, cons
   return JB_OK;
 }
 
+int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn);
+
+constexpr size_t kTmpSlack = 16;    // bytes behind the last intermediate (jb_resample_kernel reads pixels as 4-byte words)
+constexpr size_t kTmpStreams = 64;  // scratches a context keeps before it lets go of all of them
+
+// the scratch of `stream`, at least `bytes` large
+int tmp_for_stream(jb_ctx *ctx, hipStream_t stream, size_t bytes, void **out) {
+  std::lock_guard<std::mutex> lk(ctx->tmp_mu);
+  if (ctx->tmp.size() >= kTmpStreams && !ctx->tmp.count(stream)) {
+    // a caller that keeps coming with new streams: nothing of the old ones may be in flight when their scratch goes
+    JB_HIP(ctx, hipDeviceSynchronize());
+    for (auto &kv : ctx->tmp)
+      if (kv.second.d) (void)hipFree(kv.second.d);
+    ctx->tmp.clear();
+  }
+  jb_ctx::Tmp &t = ctx->tmp[stream];
+  if (t.cap < bytes) {
+    if (t.d) {
+      JB_HIP(ctx, hipStreamSynchronize(stream));  // the launches that still read the old one
+      (void)hipFree(t.d);
+      t.d = nullptr, t.cap = 0;
+    }
+    JB_HIP(ctx, hipMalloc(&t.d, bytes));
+    t.cap = bytes;
+  }
+  *out = t.d;
+  return JB_OK;
+}
+
+// 3b. a plan with a target size: two launches per sub-batch, in stream order -- the pixel kernel (full size or the
+// rectangle, interleaved uint8, tight) into the stream's scratch, jb_resample_kernel from there into the caller's buffer
+int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn) {
+  jb_geometry g;
+  int64_t plane_stride = 0;
+  int rc = seam_check(ctx, b, plan, fn, &g, &plane_stride);
+  if (rc) return rc;
+  const JbOutPlan inner = jb_out_plan_(&b->desc, 1, nullptr, plan.has_roi ? &plan.roi : nullptr);
+  if (inner.status != JB_OK) return fail(ctx, inner.status, "%s: %s", fn, inner.why);
+  // whole images per sub-batch: as many as the cap holds, one at the least
+  const int64_t cap = (int64_t)ctx->knobs.resize_tmp_bytes;
+  int64_t per = cap / plan.tmp_image_bytes;
+  if (per < 1) per = 1;
+  if (per > b->n_images) per = b->n_images;
+  if (((int64_t)(plan.out_w + 63) / 64) * ((plan.out_h + 3) / 4) * per > 0x7fffffffLL)
+    return fail(ctx, JB_ERR_CAPACITY, "batch too large for one launch");
+  DeviceGuard guard(ctx->device);
+  const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  void *tmp = nullptr;
+  rc = tmp_for_stream(ctx, s, (size_t)(per * plan.tmp_image_bytes) + kTmpSlack, &tmp);
+  if (rc) return rc;
+  // (the strides between images are checked, and meaningful, only when there is more than one)
+  const int64_t coef_step = b->n_images > 1 ? b->coef_image_stride : 0, rgb_step = b->n_images > 1 ? b->rgb_image_stride : 0;
+  for (int64_t i0 = 0; i0 < b->n_images; i0 += per) {
+    const int m = (int)(b->n_images - i0 < per ? b->n_images - i0 : per);
+    jb_device_batch ib = *b;
+    ib.n_images = m;
+    ib.d_coef = (const int16_t *)((const uint8_t *)b->d_coef + i0 * coef_step);
+    ib.coef_image_stride = coef_step;
+    ib.d_qtabs = (const int32_t *)((const uint8_t *)b->d_qtabs + i0 * b->qtab_image_stride);
+    ib.d_rgb = (uint8_t *)tmp;
+    ib.rgb_row_stride = inner.row_stride;
+    ib.rgb_image_stride = plan.tmp_image_bytes;
+    rc = seam_launch(ctx, &ib, s, inner, fn);
+    if (rc) return rc;
+    JbResample q;
+    memset(&q, 0, sizeof q);
+    q.src = (const uint8_t *)tmp;
+    q.src_image_stride = plan.tmp_image_bytes;
+    q.dst = b->d_rgb + i0 * rgb_step;
+    q.dst_image_stride = rgb_step;
+    q.dst_row_stride = b->rgb_row_stride;
+    q.dst_plane_stride = plane_stride;
+    q.iw = plan.src_w, q.ih = plan.src_h, q.ow = plan.out_w, q.oh = plan.out_h;
+    q.n_images = m;
+    for (int c = 0; c < 3; c++) q.scale[c] = plan.spec.scale[c], q.bias[c] = plan.spec.bias[c];
+    JB_HIP(ctx, jbk_resample_launch(q, plan.format, s));
+  }
+  return JB_OK;
+}
+
 // 3. the launch, on `stream` or (null) the context's primary stream; fn: the entry point's name, for the error text
 int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn) {
+  if (plan.has_resize && ctx && b) return seam_launch_resized(ctx, b, stream, plan, fn);
   jb_geometry g;
   int64_t plane_stride = 0;
   int rc = seam_check(ctx, b, plan, fn, &g, &plane_stride);
@@ -678,6 +771,12 @@ int jb_blocks_to_rgb_device_fmt(jb_ctx *ctx, const jb_device_batch *b, const jb_
 
 int jb_blocks_to_rgb_device_roi(jb_ctx *ctx, const jb_device_batch *b, const jb_roi *roi, const jb_output_spec *spec, void *stream) {
   return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, roi), "jb_blocks_to_rgb_device_roi");
+}
+
+int jb_blocks_to_rgb_device_resized(jb_ctx *ctx, const jb_device_batch *b, const jb_roi *roi, int32_t out_w, int32_t out_h,
+                                    const jb_output_spec *spec, void *stream) {
+  const JbTarget t = {out_w, out_h};
+  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, roi, &t), "jb_blocks_to_rgb_device_resized");
 }
 
 int jb_ctx_device(const jb_ctx *ctx) { return ctx ? ctx->device : -1; }

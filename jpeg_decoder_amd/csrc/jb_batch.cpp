@@ -124,20 +124,23 @@ int available_cpus() {
 }
 
 // What a decoder has been asked to deliver (jb_batch_decoder_set_scale, jb_batch_decoder_set_output_format,
-// jb_batch_decoder_set_roi): ONE value on the decoder, copied to its parts, its twin and every run.  Never a format other
-// than 0 or a rectangle with a scale other than 1.
+// jb_batch_decoder_set_roi, jb_batch_decoder_set_resize): ONE value on the decoder, copied to its parts, its twin and every
+// run.  Never a format other than 0, a rectangle or a target size with a scale other than 1.
 struct OutputRequest {
   int scale = 1;
   jb_output_spec spec = {};  // format 0: interleaved uint8
   bool has_roi = false;      // one rectangle for every image
   jb_roi roi = {};
   const jb_roi *roi_ptr() const { return has_roi ? &roi : nullptr; }
+  bool has_resize = false;   // one output size for every image
+  JbTarget target = {};
+  const JbTarget *target_ptr() const { return has_resize ? &target : nullptr; }
   // can it be had at all?  The plan function decides (jb_plan.h), here for an image of one pixel -- with a rectangle,
   // for the largest frame there is (JB_ERR_GEOMETRY: no frame holds the rectangle)
   int status() const {
     const int32_t n = has_roi ? 65535 : 1;
     const jb_image_desc one = {n, n, 1, 1, {0, 0, 0}, 0};
-    return jb_out_plan_(&one, scale, &spec, roi_ptr()).status;
+    return jb_out_plan_(&one, scale, &spec, roi_ptr(), target_ptr()).status;
   }
 };
 
@@ -328,7 +331,7 @@ void parse_one(Parsed &p, const OutputRequest &out) {
     p.error = jb_last_error(nullptr);
     return;
   }
-  p.plan = jb_out_plan_(&p.desc, out.scale, &out.spec, out.roi_ptr());
+  p.plan = jb_out_plan_(&p.desc, out.scale, &out.spec, out.roi_ptr(), out.target_ptr());
   p.status = p.plan.status;
   if (p.status == JB_OK) p.geo.rgb_bytes = p.plan.image_bytes;
   else p.error = p.plan.why;
@@ -1326,7 +1329,7 @@ extern "C" int jb_batch_decoder_set_scale(jb_batch_decoder *d, int denom) {
   OutputRequest out = d->out;
   out.scale = denom;
   if (out.status() == JB_ERR_UNSUPPORTED)
-    return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_scale: a planar output format or a rectangle is set: it cannot be combined with a scale");
+    return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_scale: a planar output format, a rectangle or a target size is set: it cannot be combined with a scale");
   set_output_all(d, out);
   return JB_OK;
 }
@@ -1355,6 +1358,20 @@ extern "C" int jb_batch_decoder_set_roi(jb_batch_decoder *d, const jb_roi *roi) 
   if (st == JB_ERR_UNSUPPORTED)
     return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_roi: the decoder's scale is not 1: a rectangle cannot be combined with it");
   if (st != JB_OK) return jb_fail_(nullptr, st, "jb_batch_decoder_set_roi: no frame can hold this rectangle");
+  set_output_all(d, out);
+  return JB_OK;
+}
+
+extern "C" int jb_batch_decoder_set_resize(jb_batch_decoder *d, int32_t out_w, int32_t out_h) {
+  if (!d) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_set_resize: decoder is NULL");
+  if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_resize: batches are in flight (collect them first)");
+  OutputRequest out = d->out;
+  out.has_resize = !(out_w == 0 && out_h == 0);
+  out.target = out.has_resize ? JbTarget{out_w, out_h} : JbTarget{};
+  const int st = out.status();
+  if (st == JB_ERR_UNSUPPORTED)
+    return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_resize: the decoder's scale is not 1: a target size cannot be combined with it");
+  if (st != JB_OK) return jb_fail_(nullptr, st, "jb_batch_decoder_set_resize: the target size is outside 1..65535");
   set_output_all(d, out);
   return JB_OK;
 }

@@ -437,10 +437,11 @@ int jb_entropy_decode_mt(const uint8_t *jpeg, size_t jpeg_bytes, jb_image_desc *
 }
 
 // Every jb_decode_memory* and jb_decode_file*: denom 1, 2, 4, 8 (checked by the caller); spec: null or format 0
-// (interleaved uint8) or a checked planar spec; roi: null or a rectangle of the frame (denom 1).  The output's sizes come
-// from the plan of the frame (jb_plan.h).
+// (interleaved uint8) or a checked planar spec; roi: null or a rectangle of the frame (denom 1); target: null or the
+// output's size (denom 1).  The output's sizes come from the plan of the frame (jb_plan.h).
 static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, int denom, const jb_output_spec *spec,
-                              uint8_t **rgb, int32_t *width, int32_t *height, const jb_roi *roi = nullptr) {
+                              uint8_t **rgb, int32_t *width, int32_t *height, const jb_roi *roi = nullptr,
+                              const JbTarget *target = nullptr) {
   if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_memory: ctx is NULL");
   if (!jpeg || !rgb || !width || !height) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_memory: NULL pointer");
   *rgb = nullptr;
@@ -471,7 +472,7 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
       if (jb_huff_prepare_(jpeg, jpeg_bytes, job.get(), nullptr, knobs.chunk_bytes) == JB_OK && jb_huff_worth_it_(*job, min_int) &&
           (forced || job->scan_len >= kAutoDeviceScan)) {
         const double t1 = timing ? now() : 0;
-        const JbOutPlan plan = jb_out_plan_(&job->desc, denom, spec, roi);
+        const JbOutPlan plan = jb_out_plan_(&job->desc, denom, spec, roi, target);
         if (plan.status != JB_OK) return jb_fail_(ctx, plan.status, plan.why);
         uint8_t *out = jb_alloc_pixels_((size_t)plan.image_bytes);
         if (!out) return jb_fail_(ctx, JB_ERR_CAPACITY, "out of host memory");
@@ -498,7 +499,7 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
   jb_geometry g;
   rc = jb_geometry_of(&desc, &g);
   if (rc) return jb_fail_(ctx, rc, "bad frame geometry");
-  const JbOutPlan plan = jb_out_plan_(&desc, denom, spec, roi);
+  const JbOutPlan plan = jb_out_plan_(&desc, denom, spec, roi, target);
   if (plan.status != JB_OK) return jb_fail_(ctx, plan.status, plan.why);
   // the staging ring follows the frame (a context sized for another image, or created with (0,0))
   rc = jb_ctx_reserve(ctx, (size_t)g.coef_bytes, (size_t)plan.image_bytes);
@@ -558,6 +559,19 @@ int jb_decode_memory_roi(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, co
   return decode_memory_impl(ctx, jpeg, jpeg_bytes, 1, spec, (uint8_t **)out, width, height, roi);
 }
 
+// the same decode at a fixed output size ("fixed output size", include/jpegblk.h); roi: null = the whole image; spec:
+// null = interleaved uint8
+int jb_decode_memory_resized(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, const jb_roi *roi, int32_t out_w, int32_t out_h,
+                             const jb_output_spec *spec, void **out, int32_t *width, int32_t *height) {
+  if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_memory_resized: ctx is NULL");
+  if (!out) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_memory_resized: NULL pointer");
+  *out = nullptr;
+  if (spec && (jb_output_spec_check(spec, 1, 1 << 20) != JB_OK || (spec->format != JB_FMT_RGB_U8_HWC && spec->plane_stride != 0)))
+    return jb_fail_(ctx, JB_ERR_GEOMETRY, "jb_decode_memory_resized: bad output spec (unknown format, reserved or plane_stride not 0, scale / bias not finite)");
+  const JbTarget t = {out_w, out_h};
+  return decode_memory_impl(ctx, jpeg, jpeg_bytes, 1, spec, (uint8_t **)out, width, height, roi, &t);
+}
+
 // the file's bytes; fn: the entry point's name, for the error text
 static int read_file(jb_ctx *ctx, const char *fn, const char *path, std::vector<uint8_t> &buf) {
   if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, (std::string(fn) + ": ctx is NULL").c_str());
@@ -596,6 +610,15 @@ int jb_decode_file_roi(jb_ctx *ctx, const char *path, const jb_roi *roi, const j
   std::vector<uint8_t> buf;
   const int rc = read_file(ctx, "jb_decode_file_roi", path, buf);
   return rc ? rc : jb_decode_memory_roi(ctx, buf.data(), buf.size(), roi, spec, out, width, height);
+}
+
+int jb_decode_file_resized(jb_ctx *ctx, const char *path, const jb_roi *roi, int32_t out_w, int32_t out_h,
+                           const jb_output_spec *spec, void **out, int32_t *width, int32_t *height) {
+  if (ctx && !out) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_file_resized: NULL pointer");
+  if (ctx) *out = nullptr;
+  std::vector<uint8_t> buf;
+  const int rc = read_file(ctx, "jb_decode_file_resized", path, buf);
+  return rc ? rc : jb_decode_memory_resized(ctx, buf.data(), buf.size(), roi, out_w, out_h, spec, out, width, height);
 }
 
 }  // extern "C"

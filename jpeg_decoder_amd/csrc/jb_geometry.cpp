@@ -90,6 +90,15 @@ int jb_roi_check(const jb_image_desc *d, const jb_roi *roi) {
   return jb_roi_fits_(roi, d->width, d->height) ? JB_OK : JB_ERR_GEOMETRY;
 }
 
+int jb_resize_check(const jb_image_desc *d, const jb_roi *roi, int32_t out_w, int32_t out_h) {
+  if (!d) return JB_ERR_NULL;
+  jb_geometry g;
+  const int rc = jb_geometry_of(d, &g);
+  if (rc != JB_OK) return rc;
+  const JbTarget t = {out_w, out_h};
+  return jb_out_plan_(d, 1, nullptr, roi, &t).status;  // the rectangle first, then the target
+}
+
 int jb_resolve_qtabs(const jb_image_desc *d, const uint16_t *qtabs, int32_t *out192) {
   if (!d || !qtabs || !out192) return JB_ERR_NULL;
   for (int c = 0; c < 3; c++) {
@@ -102,8 +111,8 @@ int jb_resolve_qtabs(const jb_image_desc *d, const uint16_t *qtabs, int32_t *out
 
 }  // extern "C"
 
-// jb_plan.h: the only place that turns (frame, scale, spec, rectangle) into the output's sizes and strides
-JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *spec, const jb_roi *roi) {
+// jb_plan.h: the only place that turns (frame, scale, spec, rectangle, target) into the output's sizes and strides
+JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *spec, const jb_roi *roi, const JbTarget *target) {
   JbOutPlan p;
   memset(&p, 0, sizeof p);
   auto refuse = [&p](int status, const char *why) {
@@ -131,6 +140,20 @@ JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *
     if (scale != 1) return refuse(JB_ERR_UNSUPPORTED, "a rectangle cannot be combined with a scale");
     out_w = roi->width, out_h = roi->height;
     p.has_roi = true, p.roi = *roi;
+  }
+  if (target) {
+    if (target->w < 1 || target->h < 1 || target->w > 65535 || target->h > 65535) {
+      p.has_roi = false, p.roi = jb_roi{};
+      return refuse(JB_ERR_GEOMETRY, "the target size is outside 1..65535");
+    }
+    if (scale != 1) {
+      p.has_roi = false, p.roi = jb_roi{};
+      return refuse(JB_ERR_UNSUPPORTED, "a target size cannot be combined with a scale");
+    }
+    p.has_resize = true;
+    p.src_w = out_w, p.src_h = out_h;
+    p.tmp_image_bytes = 3LL * out_w * out_h;
+    out_w = target->w, out_h = target->h;
   }
   p.why = "";
   p.scale = scale;

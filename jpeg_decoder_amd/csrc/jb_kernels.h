@@ -55,6 +55,23 @@ int jbk_linear_ok(int hs, int vs, int mcus_x);
 hipError_t jbk_launch(const JbLaunch &p, int hs, int vs, int scale, hipStream_t stream);
 const char *jbk_kernel_name(int hs, int vs);
 
+// "Fixed output size" (jb_resample.hip): n_images tight interleaved uint8 images of iw x ih at src (src_image_stride bytes
+// apart, at least 4 readable bytes behind the last one) -> their exact area resize to ow x oh at dst, in `format`
+// (JB_FMT_*): rows dst_row_stride bytes apart (of a plane when planar), planes dst_plane_stride, images
+// dst_image_stride; scale / bias: the float formats' affine map.  Nothing outside the ow x oh elements is written.
+struct JbResample {
+  const uint8_t *src;
+  uint8_t *dst;
+  int64_t src_image_stride;
+  int64_t dst_image_stride, dst_row_stride, dst_plane_stride;
+  int32_t iw, ih, ow, oh;  // each in 1..65535
+  int32_t n_images;
+  int32_t tiles_x, tiles_y;  // (set by jbk_resample_launch: workgroups per output row / column of rows)
+  float scale[3], bias[3];
+};
+// one workgroup per 64 columns x 4 rows of one image's output; more than 2^31 - 1 of them: hipErrorInvalidValue
+hipError_t jbk_resample_launch(const JbResample &p, int format, hipStream_t stream);
+
 // Device-side entropy decoder (jb_huff.hip); structures in jb_huff.h.
 struct JbHuffLaunch;
 hipError_t jbk_huff_launch(const JbHuffLaunch &p, hipStream_t stream);

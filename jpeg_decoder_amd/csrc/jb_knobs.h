@@ -26,11 +26,17 @@
 //                         under a CPU quota (default: bind only when the process owns a node's worth of CPUs)
 //   JPEGBLK_OVERSUBSCRIBE 1: allow more host threads than CPUs the process may use
 //   JPEGBLK_TIMING        1 | 2 | 3: where one decode(bytes) / one device-entropy submission / one batch run spends its time, on stderr
+//   JPEGBLK_RESIZE_TMP_BYTES  bytes of full-size intermediates one launch pair of a decode to a fixed output size may hold
+//                         (default 128 MiB; a batch that needs more runs as sub-batches of whole images, one image at the least)
 //   JPEGBLK_HW_QUEUES     read when the LIBRARY IS LOADED (before HIP initialises, jb_api.cpp): hardware queues to
 //                         ask the runtime for (GPU_MAX_HW_QUEUES; default 16, 0 = leave the runtime's default)
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>
+
+// "fixed output size": the cap of one scratch of tight uint8 intermediates (jb_api.cpp seam_launch_resized): 20 1080p
+// images, so that a device-entropy group (JPEGBLK_DEV_GROUP_MB) of them stays one launch pair
+constexpr size_t kJbResizeTmpBytes = (size_t)128 << 20;
 
 struct JbKnobs {
   int gpu_huffman = -1;      // -1: unset
@@ -46,6 +52,7 @@ struct JbKnobs {
   int numa = -1;             // -1: automatic, 0: off, 1: forced
   bool oversubscribe = false;
   int timing = 0;
+  size_t resize_tmp_bytes = kJbResizeTmpBytes;
 };
 
 inline JbKnobs jb_knobs_read() {
@@ -71,5 +78,7 @@ inline JbKnobs jb_knobs_read() {
   if (const char *e = getenv("JPEGBLK_NUMA")) k.numa = e[0] == '0' ? 0 : e[0] == '1' ? 1 : -1;
   k.oversubscribe = flag("JPEGBLK_OVERSUBSCRIBE");
   if (const char *e = getenv("JPEGBLK_TIMING")) k.timing = e[0] >= '1' && e[0] <= '3' ? e[0] - '0' : 0;
+  if (const char *e = getenv("JPEGBLK_RESIZE_TMP_BYTES"))
+    if (atoll(e) > 0) k.resize_tmp_bytes = (size_t)atoll(e);
   return k;
 }

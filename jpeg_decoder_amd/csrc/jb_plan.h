@@ -9,14 +9,15 @@ struct JbOutPlan {
   // JB_OK, or why this output cannot be had: JB_ERR_NULL (no descriptor), JB_ERR_GEOMETRY (scale not 1, 2, 4, 8; image
   // size outside 1..65535; unknown format; reserved != 0 on a format-0 spec), JB_ERR_UNSUPPORTED (a format other than 0
   // with a scale other than 1), JB_ERR_GEOMETRY (a rectangle that does not lie in the image), JB_ERR_UNSUPPORTED (a
-  // rectangle with a scale other than 1) -- in that order.  Whoever uses a plan reports it where the old code checked the
+  // rectangle with a scale other than 1), JB_ERR_GEOMETRY (a target size outside 1..65535), JB_ERR_UNSUPPORTED (a target
+  // size with a scale other than 1) -- in that order.  Whoever uses a plan reports it where the old code checked the
   // scale: behind the descriptor's own errors.  `why` is the text for jb_last_error (of the last plan this thread made,
   // when it names sizes); the other fields are 0 on failure.
   int status;
   const char *why;
   int32_t scale;          // 1, 2, 4, 8
   int32_t format;         // JB_FMT_*
-  int32_t out_w, out_h;   // ceil(W / scale) x ceil(H / scale); with a rectangle, its width x height
+  int32_t out_w, out_h;   // ceil(W / scale) x ceil(H / scale); with a rectangle, its width x height; with a target, the target
   int32_t esize;          // bytes per element
   bool planar;            // format != JB_FMT_RGB_U8_HWC: three planes of out_h rows
   int64_t row_stride;     // tight rows on the device: of a plane (out_w * esize) when planar, else 3 * out_w
@@ -24,9 +25,21 @@ struct JbOutPlan {
   bool has_roi;           // the output is the rectangle `roi` of the full-size image (scale 1): the ROI store stage, even
   jb_roi roi;             // when the rectangle is the whole image; else all 0
   jb_output_spec spec;    // planar: the caller's spec (plane_stride, and scale / bias for the float formats); else zero
+  // "fixed output size" (include/jpegblk.h): the output is the exact area resize of the src_w x src_h source -- the
+  // full-size image, or the rectangle -- to out_w x out_h.  The pixel kernel writes the source as tight interleaved
+  // uint8 (tmp_image_bytes per image) into a scratch of the context, jb_resample_kernel reads it.  Else all 0.
+  bool has_resize;
+  int32_t src_w, src_h;
+  int64_t tmp_image_bytes;  // 3 * src_w * src_h
+};
+
+// a target size for jb_out_plan_
+struct JbTarget {
+  int32_t w, h;
 };
 
 // spec: null or format 0 = interleaved uint8.  Beyond `reserved` on a format-0 spec, the spec's own fields (plane_stride
 // against a row stride, finite scale / bias) are jb_output_spec_check's, which needs the caller's strides.
-// roi: null = the whole image.
-JbOutPlan jb_out_plan_(const jb_image_desc *desc, int scale, const jb_output_spec *spec, const jb_roi *roi = nullptr);
+// roi: null = the whole image.  target: null = the size of the image (at the scale) or of the rectangle.
+JbOutPlan jb_out_plan_(const jb_image_desc *desc, int scale, const jb_output_spec *spec, const jb_roi *roi = nullptr,
+                       const JbTarget *target = nullptr);
