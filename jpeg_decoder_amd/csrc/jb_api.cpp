@@ -8,31 +8,17 @@
 // the pixels of image i travel device->host while the coefficients of image i+1 travel
 // host->device (the link is full duplex: 57 GB/s one way, 97 GB/s both ways, tools/probe_pcie.hip).  There is deliberately NO CPU
 // fallback here: without a usable HIP device every compute entry point fails with JB_ERR_HIP.
-#include <atomic>
-#include <condition_variable>
-#include <deque>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <thread>
-#include <hip/hip_runtime_api.h>
-
-#include <cstdarg>
 #include <chrono>
-#include <cstdio>
+#include <condition_variable>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
+#include <memory>
 #include <new>
-#include <string>
-#include <vector>
+#include <thread>
 
-#include <sched.h>
-
-#include "../../include/jpegblk.h"
+#include "jb_ctx.h"
 #include "jb_kernels.h"
-#include "jb_huff.h"
-#include "jb_knobs.h"
-#include "jb_plan.h"
 
 namespace {
 
@@ -54,28 +40,7 @@ __attribute__((constructor)) void jb_ask_for_hw_queues() {
 
 thread_local std::string g_tls_error = "";
 
-struct Slot {
-  void *d_coef = nullptr;
-  void *d_rgb = nullptr;
-  int32_t *h_q = nullptr;  // pinned int32[3][64]
-  int32_t *d_q = nullptr;
-  // device-side entropy decoding (jb_huff.hip): the submission's packed scans, interval tables and
-  // Huffman table sets (pinned host copy + device copy), and one status word per image
-  uint8_t *h_blob = nullptr;
-  size_t h_blob_cap = 0;
-  void *d_blob = nullptr;
-  size_t blob_cap = 0;
-  uint32_t *h_status = nullptr;  // pinned, kMaxBatch words
-  uint32_t *d_status = nullptr;
-  int n_status = 0;              // images of the submission in flight whose status words must be checked
-  hipEvent_t computed = nullptr;  // kernel finished (upload stream) -> the download may start
-  hipEvent_t done = nullptr;      // pixels are in the caller's buffer
-  // a download that the context's download thread has not issued yet (see jb_ctx::dl_*): `done` is only recorded
-  // once it has, so whoever waits for the slot waits for this to clear first
-  std::atomic<int> dl_pending{0};
-  bool busy = false;
-  int ticket = -1;
-};
+}  // namespace
 
 // one download handed to the device's download thread
 struct DlItem {
@@ -109,97 +74,7 @@ struct DlEngine {
   hipStream_t stream = nullptr;
 };
 
-}  // namespace
-
-struct jb_ctx {
-  int device = 0;
-  JbKnobs knobs;                  // the environment as it was when the context was created (jb_knobs.h)
-  hipStream_t stream = nullptr;   // primary: uploads + kernels of the ring; device-resident launches with a NULL stream
-  hipStream_t stream2 = nullptr;  // downloads of the staging ring
-  // Submissions whose entropy stage runs on the device: a decoder launch is latency-bound (a lane
-  // walks its interval's blocks one after the other: milliseconds, whatever the group size), so
-  // several of them must be in flight at once; each such submission runs whole on one of these.
-  static constexpr int kPool = 16;
-  hipStream_t pool[kPool] = {};
-  // Single-image submissions of host coefficients: K independent (upload + kernel, download) stream
-  // pairs used in turn -- pair 0 is (stream, stream2).  Within a pair the download of image i
-  // overlaps the upload of image i + K (the link runs both ways); across pairs the chains of
-  // different submitters do not queue behind each other.
-  // Measured with 16 submitting threads (profiles/r02b/ab_stream_pairs.txt): 1080p images (19 MB
-  // per submission) 1,951 images/s with one pair, 2,631 with eight; 8192x8192 images (402 MB) 164
-  // with one pair, 91 with eight -- several large copies in one direction at a time share the link
-  // badly -- so submissions of 64 MB or more all use pair 0.
-  static constexpr int kMaxPairs = 8;
-  static constexpr size_t kLargeSubmission = (size_t)64 << 20;
-  int n_pairs = 8;
-  hipStream_t pair_up[kMaxPairs] = {}, pair_down[kMaxPairs] = {};
-  unsigned n_single_submits = 0;
-  unsigned n_group_submits = 0;
-  size_t max_coef = 0, max_rgb = 0, rgb_alloc = 0;
-  int n_slots = 0;
-  int n_slots_req = 1;  // ring depth asked for at creation (used when jb_ctx_reserve builds the ring later)
-  Slot slots[64];  // n_slots of them are in use
-  Slot huff_aux;   // blob + status of jb_entropy_decode_device (the only fields of it in use)
-  int next_slot = 0;
-  int next_ticket = 1;
-  int n_cus = 256;                 // compute units of the device
-  size_t blob_hint = 0;            // the largest device blob any slot has been given (huff_stage)
-  long long n_device_entropy = 0;  // images whose entropy stage ran on the device (jb_huff.hip)
-  jb_image_desc last_desc = {0, 0, 0, 0, {0, 0, 0}, 0};  // frame of the last jb_decode_file / jb_decode_memory
-  std::string error;
-  DlEngine *dl = nullptr;   // the device's download engine, once this context has handed it a copy
-  int dl_outstanding = 0;   // copies handed over and not issued yet (under dl->mu)
-  // Which of several contexts' ready copies the engine issues first: the smaller number.  The batch decoder gives
-  // every run the next number, so that of two batches in flight the OLDER one gets the link and finishes, instead of
-  // both sharing it and finishing together (two batches that share evenly fall into step, and the start-up of the
-  // next pair then overlaps nothing).
-  std::atomic<uint64_t> dl_age{0};
-  std::string dl_error;     // (under dl->mu)
-  // "Fixed output size": the tight uint8 intermediates between the pixel kernel and jb_resample_kernel, one scratch per
-  // stream that has carried such a launch (the two launches and the next pair on the same stream are ordered; launches
-  // on different streams of the ring run side by side and must not share one).  Each grows on demand, is reused, and
-  // holds at most knobs.resize_tmp_bytes (or one image, when that is larger) plus the slack the kernel's loads want.
-  struct Tmp {
-    void *d = nullptr;
-    size_t cap = 0;
-  };
-  std::mutex tmp_mu;
-  std::map<hipStream_t, Tmp> tmp;
-};
-
 namespace {
-
-int fail(jb_ctx *ctx, int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  if (ctx) ctx->error = buf;
-  g_tls_error = buf;
-  return code;
-}
-
-#define JB_HIP(ctx, call)                                                                      \
-  do {                                                                                         \
-    hipError_t e_ = (call);                                                                    \
-    if (e_ != hipSuccess) return fail(ctx, JB_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
-  } while (0)
-
-int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-
-// Makes the context's device current for the duration of a call and restores the caller's
-// (a jb_ctx may live on any GPU of the node; the calling thread may be using another one).
-struct DeviceGuard {
-  int prev = -1;
-  bool changed = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = (hipSetDevice(dev) == hipSuccess);
-  }
-  ~DeviceGuard() {
-    if (changed) (void)hipSetDevice(prev);
-  }
-};
 
 // The staging ring of a context (device coefficient / pixel buffers, a pinned table block and two
 // events per slot, plus the download stream), sized from ctx->max_coef / ctx->rgb_alloc.  The
@@ -398,15 +273,6 @@ hipError_t sync_all_streams(jb_ctx *ctx) {
   return e;
 }
 
-int check_desc(jb_ctx *ctx, const jb_image_desc *d, jb_geometry *g) {
-  int rc = jb_geometry_of(d, g);
-  if (rc == JB_ERR_NULL) return fail(ctx, rc, "null descriptor");
-  if (rc == JB_ERR_GEOMETRY) return fail(ctx, rc, "image size %dx%d outside 1..65535", d->width, d->height);
-  if (rc == JB_ERR_SAMPLING) return fail(ctx, rc, "luma sampling factors %dx%d not in {1,2}x{1,2}", d->hs, d->vs);
-  if (rc == JB_ERR_QTAB) return fail(ctx, rc, "quantisation table id outside 0..3");
-  return rc;
-}
-
 }  // namespace
 
 extern "C" {
@@ -418,11 +284,6 @@ int jb_device_count(void) {
   hipError_t e = hipGetDeviceCount(&n);
   if (e != hipSuccess) return fail(nullptr, JB_ERR_HIP, "hipGetDeviceCount: %s", hipGetErrorString(e));
   return n;
-}
-
-const char *jb_kernel_name(const jb_image_desc *d) {
-  if (!d) return "";
-  return jbk_kernel_name(d->hs, d->vs);
 }
 
 int jb_ctx_create(int device_id, size_t max_coef_bytes, size_t max_rgb_bytes, int n_slots, jb_ctx **out) {
@@ -509,11 +370,6 @@ void jb_ctx_destroy(jb_ctx *ctx) {
   delete ctx;
 }
 
-// (jb_batch.cpp) the rank of this context's downloads among those of the other contexts on its device
-void jb_ctx_set_download_age_(jb_ctx *ctx, uint64_t age) {
-  if (ctx) ctx->dl_age.store(age, std::memory_order_relaxed);
-}
-
 const char *jb_last_error(const jb_ctx *ctx) { return ctx ? ctx->error.c_str() : g_tls_error.c_str(); }
 
 void *jb_ctx_stream(jb_ctx *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
@@ -523,260 +379,6 @@ int jb_ctx_synchronize(jb_ctx *ctx) {
   DeviceGuard guard(ctx->device);
   JB_HIP(ctx, sync_all_streams(ctx));
   return JB_OK;
-}
-
-// Launches of up to this many 192 / 256-lane workgroups per CU take the small-grid kernels when
-// JPEGBLK_SMALL_GRID is unset.  Measured on one box, cold, events around every launch, the kernels interleaved
-// (profiles/r03/probe_small_grid.json).  4:4:4: one 1080p image (507 workgroups) 12.1 -> 10.2 us, two (1,014)
-// 14.6 -> 13.6, four (2,028) 21.5 -> 20.5, one 1280x720 9.4 -> 8.4, one 640x360 9.4 -> 7.1, one 4096x4096 (4,096)
-// 33.6 = 33.9.  4:2:0: one 640x360 11.3 -> 7.8 us, one 1080p (255 workgroups) 12.2 -> 9.4, four (1,020) 17.3 -> 15.6,
-// eight (2,040) 28.0 -> 25.7, one 4096x4096 (2,048: BASELINE config 3) 27.5 -> 25.6, two (4,096) 44.6 -> 43.1.
-// 4:2:2 / 4:4:0 (all 64 lanes busy): one 1080p 11.2 -> 10.6 / 11.4 -> 9.6 us, one 4096x4096 25.0 -> 23.4 / 25.7 -> 26.3.
-constexpr int kSmallGridBelowPerCu = 8;
-
-}  // extern "C"
-
-namespace {
-
-// The pixel launch of every route -- the public device seams below and the staging ring's submissions -- in three
-// steps: argument validation, tile planning, the launch.  `plan` (jb_plan.h) says what the pixels look like: scale 1,
-// format 0 is exactly the launch jb_blocks_to_rgb_device has always made; scale 2, 4, 8 the row-bound tiling with the
-// area-reduced store stage; a planar format the row-bound tiling with the planar store stage; a rectangle (plan.has_roi)
-// the row-bound tiling over the MCUs it touches with the ROI store stage, in any format.  The batch's row / image
-// strides describe the output: the reduced image when scale > 1, one plane's rows with a planar format, images of the
-// rectangle's size with a rectangle (plan.out_w x plan.out_h in every case).
-
-// 1. validation: the batch against the plan; g: the frame's geometry; plane_stride: bytes between the planes (0: interleaved)
-int seam_check(jb_ctx *ctx, const jb_device_batch *b, const JbOutPlan &plan, const char *fn, jb_geometry *g, int64_t *plane_stride) {
-  if (!ctx) return fail(nullptr, JB_ERR_NULL, "%s: ctx is NULL", fn);
-  if (!b || !b->d_coef || !b->d_qtabs || !b->d_rgb) return fail(ctx, JB_ERR_NULL, "%s: NULL pointer", fn);
-  int rc = check_desc(ctx, &b->desc, g);
-  if (rc) return rc;
-  if (b->n_images < 1) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d", b->n_images);
-  if (plan.status != JB_OK) return fail(ctx, plan.status, "%s: %s", fn, plan.why);
-  *plane_stride = 0;
-  if (plan.planar) {
-    if (jb_output_spec_check(&plan.spec, plan.out_h, b->rgb_row_stride) != JB_OK)
-      return fail(ctx, JB_ERR_GEOMETRY, "%s: bad output spec (reserved, plane_stride < row stride * height, or scale / bias not finite)", fn);
-    *plane_stride = plan.spec.plane_stride ? plan.spec.plane_stride : b->rgb_row_stride * (int64_t)plan.out_h;
-  }
-  if (b->rgb_row_stride < plan.row_stride)
-    return fail(ctx, JB_ERR_GEOMETRY, "rgb_row_stride %lld < %s", (long long)b->rgb_row_stride, plan.planar ? "width * element size" : "3*width");
-  if (plan.planar) {
-    if (((uintptr_t)b->d_rgb | (uint64_t)b->rgb_row_stride | (uint64_t)*plane_stride | (uint64_t)(b->n_images > 1 ? b->rgb_image_stride : 0)) & (uint64_t)(plan.esize - 1))
-      return fail(ctx, JB_ERR_GEOMETRY, "%s: f32 / f16 output wants the pointer and every stride to be multiples of the element size", fn);
-    if (b->n_images > 1 && b->rgb_image_stride < 2 * *plane_stride + b->rgb_row_stride * (int64_t)plan.out_h)
-      return fail(ctx, JB_ERR_GEOMETRY, "image strides smaller than one image");
-  }
-  if (((uintptr_t)b->d_coef & 15) || (b->coef_image_stride & 15))
-    return fail(ctx, JB_ERR_GEOMETRY, "coefficient pointer and image stride must be multiples of 16 bytes");
-  if (((uintptr_t)b->d_qtabs & 3) || (b->qtab_image_stride & 3))
-    return fail(ctx, JB_ERR_GEOMETRY, "quant-table pointer and stride must be multiples of 4 bytes");
-  if (b->n_images > 1 && (b->coef_image_stride < g->coef_bytes || b->rgb_image_stride < b->rgb_row_stride * (int64_t)plan.out_h))
-    return fail(ctx, JB_ERR_GEOMETRY, "image strides smaller than one image");
-  return JB_OK;
-}
-
-// 2. tile planning: linear, row-bound or small-grid, and the store-stage knobs, into p (its pointers, strides and
-// frame fields are set)
-int seam_tiles(jb_ctx *ctx, const jb_device_batch *b, const jb_geometry &g, const JbOutPlan &plan, JbLaunch &p) {
-  const int per_tile = jbk_mcus_per_tile(b->desc.hs, b->desc.vs);
-  if (plan.has_roi) {
-    // only the MCUs the rectangle touches: the grid's origin is the MCU that holds its first pixel, one tile row per
-    // touched MCU row, row-bound tiles from the origin's column on (always the 192-lane kernel's ROI instantiation)
-    const int mw = 8 * b->desc.hs, mh = 8 * b->desc.vs;
-    const jb_roi &r = plan.roi;
-    p.roi = 1;
-    p.roi_x = r.x, p.roi_y = r.y, p.roi_w = r.width, p.roi_h = r.height;
-    p.roi_mx = r.x / mw, p.roi_my = r.y / mh;
-    const int roi_mcus_x = (r.x + r.width - 1) / mw - p.roi_mx + 1, roi_mcus_y = (r.y + r.height - 1) / mh - p.roi_my + 1;
-    p.tiles_per_row = (roi_mcus_x + per_tile - 1) / per_tile;
-    p.tiles_per_image = roi_mcus_y * p.tiles_per_row;  // (at most the whole image's: no overflow)
-    const int64_t n_tiles = (int64_t)b->n_images * p.tiles_per_image;
-    if (n_tiles > 0x7fffffffLL) return fail(ctx, JB_ERR_CAPACITY, "batch too large for one launch (%lld tiles)", (long long)n_tiles);
-    p.n_tiles = (int32_t)n_tiles;
-    p.fast_store = 1;  // (the ROI stage does not look at it)
-    return JB_OK;
-  }
-  p.tiles_per_row = (g.mcus_x + per_tile - 1) / per_tile;
-  // JPEGBLK_ROW_TILING=1 (debug / A-B knob) forces the row-bound tiling; the scaled and planar stages only exist in it
-  const bool force_row = ctx->knobs.row_tiling || plan.scale > 1 || plan.planar;
-  // linear tiling only where the row-bound one would leave ragged tiles
-  p.linear = (force_row || g.mcus_x % per_tile == 0) ? 0 : jbk_linear_ok(b->desc.hs, b->desc.vs, g.mcus_x);
-  const int64_t tiles_per_image = p.linear ? ((int64_t)g.mcus_x * g.mcus_y + per_tile - 1) / per_tile
-                                           : (int64_t)g.mcus_y * p.tiles_per_row;
-  if (tiles_per_image > 0x7fffffffLL) return fail(ctx, JB_ERR_CAPACITY, "image too large");
-  p.tiles_per_image = (int32_t)tiles_per_image;
-  const int64_t n_tiles = (int64_t)b->n_images * tiles_per_image;
-  if (n_tiles > 0x7fffffffLL) return fail(ctx, JB_ERR_CAPACITY, "batch too large for one launch (%lld tiles)", (long long)n_tiles);
-  p.n_tiles = (int32_t)n_tiles;
-  // Small launches (a single 1080p image is 507 / 255 workgroups on 256 CUs): four times as many one-wave
-  // workgroups (jb_kernels.hip jb_small_kernel_*), row-bound.  JPEGBLK_SMALL_GRID = 1 / 0 forces / forbids it; so does
-  // JPEGBLK_ROW_TILING=1 (that knob asks for the 192-lane kernel's row-bound instantiation).  (The scaled and planar
-  // stages have no small-grid variant.)
-  if (jbk_small_mcus(b->desc.hs, b->desc.vs) > 0 && !force_row && b->rgb_row_stride < (1LL << 26) &&  // (the lane's row offset is 32-bit)
-      (ctx->knobs.small_grid == 1 || (ctx->knobs.small_grid < 0 && n_tiles <= (int64_t)kSmallGridBelowPerCu * ctx->n_cus))) {
-    const int per = jbk_small_mcus(b->desc.hs, b->desc.vs);
-    p.tiles_per_row = (g.mcus_x + per - 1) / per;
-    const int64_t small_tiles = (int64_t)b->n_images * g.mcus_y * p.tiles_per_row;
-    if (small_tiles <= 0x7fffffffLL) {
-      p.linear = 0;
-      p.small_grid = 1;
-      p.tiles_per_image = (int32_t)((int64_t)g.mcus_y * p.tiles_per_row);
-      p.n_tiles = (int32_t)small_tiles;
-    } else {
-      p.tiles_per_row = (g.mcus_x + per_tile - 1) / per_tile;
-    }
-  }
-  // 12-byte stores at any byte address: gfx950 under ROCm runs with unaligned global/buffer access
-  // enabled, and odd widths with tightly packed rows (row stride 3*W) are the common case --
-  // measured 1.67x faster than byte stores on 679x451 (tests/test_gpu_parity.py covers both).
-  // JPEGBLK_BYTE_STORE=1 forces the byte-store path (test / A-B knob; the scaled stage ignores it).
-  p.fast_store = ctx->knobs.byte_store ? 0 : 1;
-  // (measurement builds of jb_kernels.hip only -- tools/build_variant.sh -DJB_LAB: the staged store stage of the linear
-  // tiling; the product's kernels ignore the field)
-  p.staged = (p.linear && p.fast_store && !p.small_grid && ctx->knobs.staged_store == 1) ? 1 : 0;
-  return JB_OK;
-}
-
-int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn);
-
-constexpr size_t kTmpSlack = 16;    // bytes behind the last intermediate (jb_resample_kernel reads pixels as 4-byte words)
-constexpr size_t kTmpStreams = 64;  // scratches a context keeps before it lets go of all of them
-
-// the scratch of `stream`, at least `bytes` large
-int tmp_for_stream(jb_ctx *ctx, hipStream_t stream, size_t bytes, void **out) {
-  std::lock_guard<std::mutex> lk(ctx->tmp_mu);
-  if (ctx->tmp.size() >= kTmpStreams && !ctx->tmp.count(stream)) {
-    // a caller that keeps coming with new streams: nothing of the old ones may be in flight when their scratch goes
-    JB_HIP(ctx, hipDeviceSynchronize());
-    for (auto &kv : ctx->tmp)
-      if (kv.second.d) (void)hipFree(kv.second.d);
-    ctx->tmp.clear();
-  }
-  jb_ctx::Tmp &t = ctx->tmp[stream];
-  if (t.cap < bytes) {
-    if (t.d) {
-      JB_HIP(ctx, hipStreamSynchronize(stream));  // the launches that still read the old one
-      (void)hipFree(t.d);
-      t.d = nullptr, t.cap = 0;
-    }
-    JB_HIP(ctx, hipMalloc(&t.d, bytes));
-    t.cap = bytes;
-  }
-  *out = t.d;
-  return JB_OK;
-}
-
-// 3b. a plan with a target size: two launches per sub-batch, in stream order -- the pixel kernel (full size or the
-// rectangle, interleaved uint8, tight) into the stream's scratch, jb_resample_kernel from there into the caller's buffer
-int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn) {
-  jb_geometry g;
-  int64_t plane_stride = 0;
-  int rc = seam_check(ctx, b, plan, fn, &g, &plane_stride);
-  if (rc) return rc;
-  const JbOutPlan inner = jb_out_plan_(&b->desc, 1, nullptr, plan.has_roi ? &plan.roi : nullptr);
-  if (inner.status != JB_OK) return fail(ctx, inner.status, "%s: %s", fn, inner.why);
-  // whole images per sub-batch: as many as the cap holds, one at the least
-  const int64_t cap = (int64_t)ctx->knobs.resize_tmp_bytes;
-  int64_t per = cap / plan.tmp_image_bytes;
-  if (per < 1) per = 1;
-  if (per > b->n_images) per = b->n_images;
-  if (((int64_t)(plan.out_w + 63) / 64) * ((plan.out_h + 3) / 4) * per > 0x7fffffffLL)
-    return fail(ctx, JB_ERR_CAPACITY, "batch too large for one launch");
-  DeviceGuard guard(ctx->device);
-  const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  void *tmp = nullptr;
-  rc = tmp_for_stream(ctx, s, (size_t)(per * plan.tmp_image_bytes) + kTmpSlack, &tmp);
-  if (rc) return rc;
-  // (the strides between images are checked, and meaningful, only when there is more than one)
-  const int64_t coef_step = b->n_images > 1 ? b->coef_image_stride : 0, rgb_step = b->n_images > 1 ? b->rgb_image_stride : 0;
-  for (int64_t i0 = 0; i0 < b->n_images; i0 += per) {
-    const int m = (int)(b->n_images - i0 < per ? b->n_images - i0 : per);
-    jb_device_batch ib = *b;
-    ib.n_images = m;
-    ib.d_coef = (const int16_t *)((const uint8_t *)b->d_coef + i0 * coef_step);
-    ib.coef_image_stride = coef_step;
-    ib.d_qtabs = (const int32_t *)((const uint8_t *)b->d_qtabs + i0 * b->qtab_image_stride);
-    ib.d_rgb = (uint8_t *)tmp;
-    ib.rgb_row_stride = inner.row_stride;
-    ib.rgb_image_stride = plan.tmp_image_bytes;
-    rc = seam_launch(ctx, &ib, s, inner, fn);
-    if (rc) return rc;
-    JbResample q;
-    memset(&q, 0, sizeof q);
-    q.src = (const uint8_t *)tmp;
-    q.src_image_stride = plan.tmp_image_bytes;
-    q.dst = b->d_rgb + i0 * rgb_step;
-    q.dst_image_stride = rgb_step;
-    q.dst_row_stride = b->rgb_row_stride;
-    q.dst_plane_stride = plane_stride;
-    q.iw = plan.src_w, q.ih = plan.src_h, q.ow = plan.out_w, q.oh = plan.out_h;
-    q.n_images = m;
-    for (int c = 0; c < 3; c++) q.scale[c] = plan.spec.scale[c], q.bias[c] = plan.spec.bias[c];
-    JB_HIP(ctx, jbk_resample_launch(q, plan.format, s));
-  }
-  return JB_OK;
-}
-
-// 3. the launch, on `stream` or (null) the context's primary stream; fn: the entry point's name, for the error text
-int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn) {
-  if (plan.has_resize && ctx && b) return seam_launch_resized(ctx, b, stream, plan, fn);
-  jb_geometry g;
-  int64_t plane_stride = 0;
-  int rc = seam_check(ctx, b, plan, fn, &g, &plane_stride);
-  if (rc) return rc;
-  JbLaunch p;
-  memset(&p, 0, sizeof p);
-  p.coef = b->d_coef;
-  p.qtabs = b->d_qtabs;
-  p.rgb = b->d_rgb;
-  p.coef_image_stride = b->coef_image_stride;
-  p.qtab_image_stride = b->qtab_image_stride;
-  p.rgb_image_stride = b->rgb_image_stride;
-  p.rgb_row_stride = b->rgb_row_stride;
-  p.width = b->desc.width;
-  p.height = b->desc.height;
-  p.mcus_x = g.mcus_x;
-  p.mcus_y = g.mcus_y;
-  p.chroma_q_equal = (b->desc.qtab_id[1] == b->desc.qtab_id[2]) ? 1 : 0;
-  if (plan.planar) {
-    p.format = plan.format;
-    p.rgb_plane_stride = plane_stride;
-    for (int c = 0; c < 3; c++) p.scale[c] = plan.spec.scale[c], p.bias[c] = plan.spec.bias[c];
-  }
-  rc = seam_tiles(ctx, b, g, plan, p);
-  if (rc) return rc;
-  DeviceGuard guard(ctx->device);
-  JB_HIP(ctx, jbk_launch(p, b->desc.hs, b->desc.vs, plan.scale, stream ? (hipStream_t)stream : ctx->stream));
-  return JB_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int jb_blocks_to_rgb_device(jb_ctx *ctx, const jb_device_batch *b, void *stream) {
-  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, nullptr), "jb_blocks_to_rgb_device");
-}
-
-int jb_blocks_to_rgb_device_scaled(jb_ctx *ctx, const jb_device_batch *b, int denom, void *stream) {
-  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, denom, nullptr), "jb_blocks_to_rgb_device_scaled");
-}
-
-int jb_blocks_to_rgb_device_fmt(jb_ctx *ctx, const jb_device_batch *b, const jb_output_spec *spec, void *stream) {
-  if (ctx && !spec) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_fmt: spec is NULL");
-  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec), "jb_blocks_to_rgb_device_fmt");
-}
-
-int jb_blocks_to_rgb_device_roi(jb_ctx *ctx, const jb_device_batch *b, const jb_roi *roi, const jb_output_spec *spec, void *stream) {
-  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, roi), "jb_blocks_to_rgb_device_roi");
-}
-
-int jb_blocks_to_rgb_device_resized(jb_ctx *ctx, const jb_device_batch *b, const jb_roi *roi, int32_t out_w, int32_t out_h,
-                                    const jb_output_spec *spec, void *stream) {
-  const JbTarget t = {out_w, out_h};
-  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, roi, &t), "jb_blocks_to_rgb_device_resized");
 }
 
 int jb_ctx_device(const jb_ctx *ctx) { return ctx ? ctx->device : -1; }
@@ -878,6 +480,8 @@ int jb_device_numa_node(int device_id) {
 void jb_pinned_free(void *p) {
   if (p) (void)hipHostFree(p);
 }
+
+}  // extern "C"
 
 namespace {
 
@@ -1011,7 +615,6 @@ int submit_impl(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int1
 }
 
 // ---- device-side entropy decoding (jb_huff.hip) -------------------------------------------------
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 // upload a packed submission (jb_huff_pack_) and launch the decoder: image i's coefficient blocks
 // land at d_out + i * coef_stride bytes, its status word at s.d_status[i]
@@ -1104,8 +707,7 @@ int submit_jobs_impl(jb_ctx *ctx, const JbHuffJob *const *jobs, const uint8_t *p
   rc = submit_tables(ctx, s, desc, n_images, jobs, qtabs_in, up);
   if (rc) return rc;
   const bool timing = ctx->knobs.timing == 2;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double tt0 = timing ? now() : 0;
+  const double tt0 = timing ? jb_now_s_() : 0;
   JbHuffLayout lay_own;
   if (jobs) {
     rc = pack_into_slot(ctx, s, jobs, n_images, sub.g.coef_bytes, &lay_own);
@@ -1114,18 +716,18 @@ int submit_jobs_impl(jb_ctx *ctx, const JbHuffJob *const *jobs, const uint8_t *p
     lay_in = &lay_own;
   }
   if (lay_in->n != n_images || lay_in->coef_stride != sub.g.coef_bytes) return fail(ctx, JB_ERR_STATE, "packed submission does not match its descriptor");
-  const double tt1 = timing ? now() : 0;
+  const double tt1 = timing ? jb_now_s_() : 0;
   rc = huff_stage(ctx, s, packed, *lay_in, sub.coef_total, (int16_t *)s.d_coef, up);
   if (rc) return rc;
-  const double tt2 = timing ? now() : 0;
+  const double tt2 = timing ? jb_now_s_() : 0;
   if (timing) (void)hipStreamSynchronize(up);
-  const double tt3 = timing ? now() : 0;
+  const double tt3 = timing ? jb_now_s_() : 0;
   rc = submit_launch(ctx, sub, desc, n_images, plan, rgb, dst_device, up);
   if (rc) return rc;
   // the status words travel with the pixels: into the caller's (pinned) words when it keeps its own
   // -- many threads share this ring, a slot's words may be recycled before their owner looks -- else
   // into the slot's, which jb_wait / jb_poll check
-  const double tt4 = timing ? now() : 0;
+  const double tt4 = timing ? jb_now_s_() : 0;
   if (dst_device) {
     // the pixels stay on the device; only the status words come back
     JB_HIP(ctx, hipMemcpyAsync(status_out ? status_out : s.h_status, s.d_status, 4 * (size_t)n_images, hipMemcpyDeviceToHost, up));
@@ -1173,6 +775,8 @@ int check_status(jb_ctx *ctx, Slot &s) {
 
 }  // namespace
 
+extern "C" {
+
 int jb_entropy_decode_device(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, jb_image_desc *desc, uint16_t *qtabs,
                              int16_t *d_coef, size_t coef_cap_bytes) {
   if (!ctx) return fail(nullptr, JB_ERR_NULL, "jb_entropy_decode_device: ctx is NULL");
@@ -1212,40 +816,6 @@ int jb_entropy_decode_device(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes
   }
   s.n_status = 1;
   return check_status(ctx, s);
-}
-
-// decode(bytes) with the entropy stage on the device: one prepared image through the ring, in any output plan
-// (jb_decode_memory*, jb_frontend.cpp: the device-entropy route); the staging ring follows the frame; tight rows, rgb
-// holds plan.image_bytes
-int jb_decode_job_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, const JbOutPlan &plan) {
-  const bool timing = ctx->knobs.timing == 1;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t0 = timing ? now() : 0;
-  if (plan.status != JB_OK) return fail(ctx, plan.status, "%s", plan.why);
-  int rc = jb_ctx_reserve(ctx, (size_t)job->geo.coef_bytes, (size_t)plan.image_bytes);
-  if (rc) return rc;
-  const double t1 = timing ? now() : 0;
-  int ticket = -1;
-  const JbHuffJob *jobs[1] = {job};
-  rc = submit_jobs_impl(ctx, jobs, nullptr, nullptr, nullptr, nullptr, 1, rgb, plan.row_stride, nullptr, &ticket, plan, false);
-  if (rc) return rc;
-  const double t2 = timing ? now() : 0;
-  rc = jb_wait(ctx, ticket);
-  if (timing) fprintf(stderr, "jb_decode_job_: reserve %.3f ms, pack + submit %.3f ms, wait %.3f ms\n", (t1 - t0) * 1e3, (t2 - t1) * 1e3, (now() - t2) * 1e3);
-  return rc;
-}
-
-// several prepared images of ONE geometry in one submission (jb_batch.cpp); pixels contiguous, tight rows of the plan
-int jb_submit_packed_(jb_ctx *ctx, const jb_image_desc *desc, const uint16_t *qtabs, const uint8_t *packed, const JbHuffLayout *lay,
-                      uint8_t *rgb, uint32_t *status_out, int *ticket, const JbOutPlan &plan, int dst_device) {
-  return submit_jobs_impl(ctx, nullptr, packed, lay, desc, qtabs, lay->n, rgb, plan.row_stride, status_out, ticket, plan, dst_device != 0);
-}
-
-// a group of the batch decoder (jb_batch.cpp): jb_submit_batch in the plan's output, or (dst_device = 1) with the
-// pixels left in DEVICE memory of the context's device; tight rows
-int jb_submit_group_(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef, const uint16_t *qtabs,
-                     uint8_t *rgb, int *ticket, const JbOutPlan &plan, int dst_device) {
-  return submit_impl(ctx, desc, n_images, coef, qtabs, rgb, plan.row_stride, ticket, plan, dst_device != 0);
 }
 
 int jb_submit(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs,
@@ -1306,7 +876,37 @@ int jb_blocks_to_rgb(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef
   return jb_wait(ctx, ticket);
 }
 
-// jb_blocks_to_rgb with any output plan (jb_decode_memory*'s host-entropy route): tight rows, rgb holds plan.image_bytes
+}  // extern "C"
+
+// ---- what the other files call: each is described where it is declared, jb_internal.h ----
+
+int jb_decode_job_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, const JbOutPlan &plan) {
+  const bool timing = ctx->knobs.timing == 1;
+  const double t0 = timing ? jb_now_s_() : 0;
+  if (plan.status != JB_OK) return fail(ctx, plan.status, "%s", plan.why);
+  int rc = jb_ctx_reserve(ctx, (size_t)job->geo.coef_bytes, (size_t)plan.image_bytes);
+  if (rc) return rc;
+  const double t1 = timing ? jb_now_s_() : 0;
+  int ticket = -1;
+  const JbHuffJob *jobs[1] = {job};
+  rc = submit_jobs_impl(ctx, jobs, nullptr, nullptr, nullptr, nullptr, 1, rgb, plan.row_stride, nullptr, &ticket, plan, false);
+  if (rc) return rc;
+  const double t2 = timing ? jb_now_s_() : 0;
+  rc = jb_wait(ctx, ticket);
+  if (timing) fprintf(stderr, "jb_decode_job_: reserve %.3f ms, pack + submit %.3f ms, wait %.3f ms\n", (t1 - t0) * 1e3, (t2 - t1) * 1e3, (jb_now_s_() - t2) * 1e3);
+  return rc;
+}
+
+int jb_submit_packed_(jb_ctx *ctx, const jb_image_desc *desc, const uint16_t *qtabs, const uint8_t *packed, const JbHuffLayout *lay,
+                      uint8_t *rgb, uint32_t *status_out, int *ticket, const JbOutPlan &plan, int dst_device) {
+  return submit_jobs_impl(ctx, nullptr, packed, lay, desc, qtabs, lay->n, rgb, plan.row_stride, status_out, ticket, plan, dst_device != 0);
+}
+
+int jb_submit_group_(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef, const uint16_t *qtabs,
+                     uint8_t *rgb, int *ticket, const JbOutPlan &plan, int dst_device) {
+  return submit_impl(ctx, desc, n_images, coef, qtabs, rgb, plan.row_stride, ticket, plan, dst_device != 0);
+}
+
 int jb_blocks_to_rgb_plan_(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs, uint8_t *rgb,
                            const JbOutPlan &plan) {
   if (!ctx) return fail(nullptr, JB_ERR_NULL, "jb_blocks_to_rgb: ctx is NULL");
@@ -1316,60 +916,6 @@ int jb_blocks_to_rgb_plan_(jb_ctx *ctx, const jb_image_desc *desc, const int16_t
   if (rc) return rc;
   return jb_wait(ctx, ticket);
 }
-
-void jb_free(void *p) { free(p); }
-
-int jb_write_ppm(const char *path, const uint8_t *rgb, int32_t width, int32_t height, int64_t rgb_stride) {
-  if (!path || !rgb) return fail(nullptr, JB_ERR_NULL, "jb_write_ppm: NULL pointer");
-  if (width < 1 || height < 1 || rgb_stride < 3LL * width) return fail(nullptr, JB_ERR_GEOMETRY, "jb_write_ppm: bad geometry");
-  FILE *f = fopen(path, "wb");
-  if (!f) return fail(nullptr, JB_ERR_FORMAT, "cannot open %s for writing", path);
-  fprintf(f, "P6\n%d %d\n255\n", width, height);
-  for (int y = 0; y < height; y++)
-    if (fwrite(rgb + (int64_t)y * rgb_stride, 1, (size_t)width * 3, f) != (size_t)width * 3) {
-      fclose(f);
-      return fail(nullptr, JB_ERR_FORMAT, "short write to %s", path);
-    }
-  fclose(f);
-  return JB_OK;
-}
-
-int jb_write_bmp(const char *path, const uint8_t *rgb, int32_t width, int32_t height, int64_t rgb_stride) {
-  if (!path || !rgb) return fail(nullptr, JB_ERR_NULL, "jb_write_bmp: NULL pointer");
-  if (width < 1 || height < 1 || rgb_stride < 3LL * width) return fail(nullptr, JB_ERR_GEOMETRY, "jb_write_bmp: bad geometry");
-  const int64_t row_bytes = (3LL * width + 3) & ~3LL;  // rows are padded to 4 bytes
-  const int64_t file_bytes = 54 + row_bytes * height;
-  if (file_bytes > 0xffffffffLL) return fail(nullptr, JB_ERR_CAPACITY, "jb_write_bmp: %dx%d exceeds the 4 GiB BMP limit", width, height);
-  FILE *f = fopen(path, "wb");
-  if (!f) return fail(nullptr, JB_ERR_FORMAT, "cannot open %s for writing", path);
-  uint8_t hdr[54] = {'B', 'M'};
-  auto le32 = [&](int at, uint32_t v) { for (int i = 0; i < 4; i++) hdr[at + i] = (uint8_t)(v >> (8 * i)); };
-  le32(2, (uint32_t)file_bytes);
-  le32(10, 54);                    // offset of the pixel array
-  le32(14, 40);                    // BITMAPINFOHEADER
-  le32(18, (uint32_t)width);
-  le32(22, (uint32_t)height);      // positive: bottom-up
-  hdr[26] = 1;                     // planes
-  hdr[28] = 24;                    // bits per pixel; compression 0 (BI_RGB)
-  le32(34, (uint32_t)(row_bytes * height));
-  le32(38, 2835);                  // 72 dpi
-  le32(42, 2835);
-  bool ok = fwrite(hdr, 1, sizeof hdr, f) == sizeof hdr;
-  std::vector<uint8_t> row((size_t)row_bytes, 0);
-  for (int y = height - 1; ok && y >= 0; y--) {
-    const uint8_t *src = rgb + (int64_t)y * rgb_stride;
-    for (int x = 0; x < width; x++) {
-      row[3 * x + 0] = src[3 * x + 2];
-      row[3 * x + 1] = src[3 * x + 1];
-      row[3 * x + 2] = src[3 * x + 0];
-    }
-    ok = fwrite(row.data(), 1, row.size(), f) == row.size();
-  }
-  if (fclose(f) != 0) ok = false;
-  return ok ? JB_OK : fail(nullptr, JB_ERR_FORMAT, "short write to %s", path);
-}
-
-}  // extern "C"
 
 // jb_wait in two halves for jb_batch.cpp, where many host threads share one context: the lookup
 // runs under the caller's lock, the blocking wait outside it.  The slot stays marked busy; the
@@ -1384,13 +930,6 @@ int jb_wait_block_(jb_ctx *ctx, void *slot) {
   return slot_finish(ctx, *(Slot *)slot);
 }
 
-// Bind the calling host thread to the CPUs of the NUMA node closest to `device` (intersected with
-// the CPUs the thread may already use; nothing changes when the node is unknown, the intersection
-// is empty, or JPEGBLK_NUMA=0).  The entropy threads of one rank then read their files, decode and
-// write their pinned staging on the socket their GPU hangs off.  Returns the CPUs in the new mask,
-// 0 = left as it was.
-// Is [p, p + bytes) device memory of `device`?  (jb_batch_decoder_set_device_output: a host pointer or
-// another GPU's memory would fault in the pixel kernel instead of failing here.)
 int jb_check_device_region_(int device, const void *p, size_t bytes) {
   hipPointerAttribute_t a;
   memset(&a, 0, sizeof a);
@@ -1413,183 +952,17 @@ int jb_check_device_region_(int device, const void *p, size_t bytes) {
   return JB_OK;
 }
 
-// which CPUs the threads of a decoder on `device` are bound to (n = 0: none): worked out once per (device, knob) --
-// sysfs, the cgroup quota and the affinity mask of the first caller, 16 threads of every pass of every run asked for
-// them again -- then only applied
-static int numa_cpus_for_(int device, int numa_knob, cpu_set_t *out) {
-  if (numa_knob == 0) return 0;
-  const bool forced = numa_knob == 1;
-  const int node = jb_device_numa_node(device);
-  if (node < 0) return 0;
-  char path[96];
-  snprintf(path, sizeof path, "/sys/devices/system/node/node%d/cpulist", node);
-  FILE *f = fopen(path, "r");
-  if (!f) return 0;
-  char list[4096] = {0};
-  const bool got = fgets(list, sizeof list, f) != nullptr;
-  fclose(f);
-  if (!got) return 0;
-  cpu_set_t cur, want;
-  if (sched_getaffinity(0, sizeof cur, &cur) != 0) return 0;
-  CPU_ZERO(&want);
-  int n = 0;
-  for (char *p = list; *p;) {  // "0-15,128-143"
-    char *end;
-    long a = strtol(p, &end, 10), b = a;
-    if (end == p) break;
-    if (*end == '-') b = strtol(end + 1, &end, 10);
-    for (long c = a; c <= b && c < CPU_SETSIZE; c++)
-      if (c >= 0 && CPU_ISSET((int)c, &cur)) {
-        CPU_SET((int)c, &want);
-        n++;
-      }
-    p = (*end == ',') ? end + 1 : end;
-    if (*end != ',') break;
-  }
-  if (n == 0 || n == CPU_COUNT(&cur)) return 0;  // nothing to narrow
-  // Only where the process owns at least a node's worth of CPU time (a rank of a dedicated node).
-  // Under a cgroup CPU quota smaller than the node -- a share of a machine other tenants use too --
-  // the scheduler does better unpinned: measured on a 16-CPU share of a 256-CPU box, 16 entropy
-  // threads on 8192x8192 files: 139 images/s free, 114 bound to the GPU's node (JPEGBLK_NUMA=1 forces).
-  if (!forced) {
-    long quota = -1, period = 100000;
-    if (FILE *q = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-      char qs[32] = {0};
-      if (fscanf(q, "%31s %ld", qs, &period) >= 1 && strcmp(qs, "max") != 0) quota = atol(qs);
-      fclose(q);
-    }
-    if (quota > 0 && period > 0 && quota / period < n) return 0;
-  }
-  *out = want;
-  return n;
-}
-
-int jb_bind_thread_near_device_(int device, int numa_knob) {  // numa_knob: JbKnobs::numa of the calling decoder
-  struct Entry {
-    int n;
-    cpu_set_t set;
-  };
-  static std::mutex mu;
-  static std::map<std::pair<int, int>, Entry> cache;
-  Entry e;
-  {
-    std::lock_guard<std::mutex> g(mu);
-    auto it = cache.find({device, numa_knob});
-    if (it == cache.end()) {
-      Entry fresh;
-      CPU_ZERO(&fresh.set);
-      fresh.n = numa_cpus_for_(device, numa_knob, &fresh.set);
-      it = cache.emplace(std::make_pair(device, numa_knob), fresh).first;
-    }
-    e = it->second;
-  }
-  if (e.n <= 0) return 0;
-  if (sched_setaffinity(0, sizeof e.set, &e.set) != 0) return 0;
-  return e.n;
-}
-
 void jb_ctx_set_last_desc_(jb_ctx *ctx, const jb_image_desc *d) { ctx->last_desc = *d; }
 const JbKnobs *jb_ctx_knobs_(const jb_ctx *ctx) { return &ctx->knobs; }
 
-// used by jb_frontend.cpp to report through the same channel
-int jb_fail_(jb_ctx *ctx, int code, const char *msg) { return fail(ctx, code, "%s", msg); }
-
-// ---- packing of device-entropy submissions: pure host code (see jb_huff.h) ----------------------
-size_t jb_huff_pack_size_(const JbHuffJob *const *jobs, int n) {
-  size_t n_wg = 0, n_starts = 0, scan_bytes = 0, n_chunks = 0;
-  for (int i = 0; i < n; i++) {
-    n_wg += (jobs[i]->img.n_chunks + kJbOwnChunks - 1) / kJbOwnChunks;
-    n_chunks += jobs[i]->img.n_chunks;
-    n_starts += jobs[i]->starts.size();
-    scan_bytes += ((jobs[i]->scan.size() + 15) & ~(size_t)15);
-  }
-  // (every workgroup twice: the list of all of them and the list of the ones that synchronise)
-  return (size_t)n * sizeof(JbHuffImage) + 2 * n_wg * sizeof(JbHuffWg) + (size_t)n * sizeof(JbHuffTables) + n_starts * 4 +
-         n_chunks * sizeof(JbChunkDesc) + scan_bytes + 512;
+void jb_ctx_set_download_age_(jb_ctx *ctx, uint64_t age) {
+  if (ctx) ctx->dl_age.store(age, std::memory_order_relaxed);
 }
 
-int jb_huff_pack_(const JbHuffJob *const *jobs, int n, int64_t coef_stride, uint8_t *h, JbHuffLayout *lay) {
-  auto a16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  std::vector<int> set_of((size_t)n, 0);
-  std::vector<int> sets;  // index of the first job that owns each distinct table set
-  size_t n_wg = 0, n_sync_wg = 0, n_starts = 0, scan_bytes = 0, n_chunks = 0;
-  lay->max_chunk_bytes = 0;
-  lay->max_tabs = 0;
-  for (int i = 0; i < n; i++) {
-    int found = -1;
-    for (size_t k = 0; k < sets.size() && found < 0; k++)
-      if (jobs[sets[k]]->n_tabs == jobs[i]->n_tabs && memcmp(&jobs[sets[k]]->tables, &jobs[i]->tables, sizeof(JbHuffTables)) == 0) found = (int)k;
-    if (found < 0) {
-      found = (int)sets.size();
-      sets.push_back(i);
-    }
-    set_of[(size_t)i] = found;
-    const size_t wgs = (jobs[i]->img.n_chunks + kJbOwnChunks - 1) / kJbOwnChunks;
-    n_wg += wgs;
-    if (jobs[i]->img.needs_sync) n_sync_wg += wgs;
-    n_chunks += jobs[i]->img.n_chunks;
-    n_starts += jobs[i]->starts.size();
-    scan_bytes += a16(jobs[i]->scan.size());
-    if (jobs[i]->img.chunk_bytes > lay->max_chunk_bytes) lay->max_chunk_bytes = jobs[i]->img.chunk_bytes;
-    if (jobs[i]->n_tabs > lay->max_tabs) lay->max_tabs = jobs[i]->n_tabs;
-    // (a frame that changed between the passes of a batch decoder must not write beyond its slot)
-    if ((int64_t)jobs[i]->geo.coef_bytes > coef_stride) return JB_ERR_CAPACITY;
-  }
-  lay->off_img = 0;
-  lay->off_wg = a16((size_t)n * sizeof(JbHuffImage));
-  lay->off_sync_wg = a16(lay->off_wg + n_wg * sizeof(JbHuffWg));
-  lay->off_tab = a16(lay->off_sync_wg + n_sync_wg * sizeof(JbHuffWg));
-  lay->off_starts = lay->off_tab + sets.size() * sizeof(JbHuffTables);
-  lay->off_chunks = a16(lay->off_starts + n_starts * 4);
-  lay->off_scan = a16(lay->off_chunks + n_chunks * sizeof(JbChunkDesc));
-  lay->total = lay->off_scan + scan_bytes + 256;  // (a lane reads up to 16 dwords beyond its chunk's last byte)
-  // device-only scratch behind the uploaded bytes
-  lay->off_entry = a16(lay->total);
-  lay->off_exit = a16(lay->off_entry + n_chunks * sizeof(JbChunkState));
-  lay->off_cps = a16(lay->off_exit + n_chunks * sizeof(JbChunkState));
-  lay->off_chunk_dc = (a16(lay->off_cps + n_chunks * kJbCheckpoints * 4) + 31) & ~(size_t)31;
-  lay->off_wgsum = lay->off_chunk_dc + n_chunks * sizeof(JbChunkDc);
-  lay->device_total = a16(lay->off_wgsum + n_wg * sizeof(JbWgSum));
-  lay->n = n;
-  lay->n_wg = (int)n_wg;
-  lay->n_sync_wg = (int)n_sync_wg;
-  lay->n_chunks = (uint32_t)n_chunks;
-  lay->coef_stride = coef_stride;
-  if (lay->device_total > 0xffffff00u || n_wg > 0x7fffffffu || n_chunks > 0x3fffffffu) return JB_ERR_CAPACITY;
-  JbHuffImage *im = (JbHuffImage *)(h + lay->off_img);
-  JbHuffWg *wg = (JbHuffWg *)(h + lay->off_wg);
-  JbHuffWg *swg = (JbHuffWg *)(h + lay->off_sync_wg);
-  uint32_t *st = (uint32_t *)(h + lay->off_starts);
-  size_t w = 0, sw = 0, si = 0, sc = lay->off_scan, chunk0 = 0;
-  for (size_t k = 0; k < sets.size(); k++) memcpy(h + lay->off_tab + k * sizeof(JbHuffTables), &jobs[sets[k]]->tables, sizeof(JbHuffTables));
-  for (int i = 0; i < n; i++) {
-    const JbHuffJob &j = *jobs[i];
-    im[i] = j.img;
-    im[i].scan_off = (uint32_t)(sc - lay->off_scan);
-    im[i].int_off = (uint32_t)si;
-    im[i].table_set = (uint32_t)set_of[(size_t)i];
-    im[i].coef_off = (int64_t)i * coef_stride;
-    im[i].state_off = (uint32_t)chunk0;
-    im[i].wg0 = (uint32_t)w;
-    // the chunks of every restart interval, from the interval's first byte (jb_chunks_of_)
-    JbChunkDesc *cd = (JbChunkDesc *)(h + lay->off_chunks) + chunk0;
-    uint32_t c = 0;
-    for (uint32_t seg = 0; seg + 1 < (uint32_t)j.starts.size(); seg++) {
-      const uint32_t k = jb_chunks_of_(j.starts[seg + 1] - j.starts[seg], j.img.chunk_bytes);
-      if (c + k > j.img.n_chunks) return JB_ERR_STATE;
-      for (uint32_t q = 0; q < k; q++) cd[c++] = JbChunkDesc{j.starts[seg] + q * j.img.chunk_bytes, seg | (q == 0 ? 0x80000000u : 0u)};
-    }
-    if (c != j.img.n_chunks) return JB_ERR_STATE;
-    chunk0 += j.img.n_chunks;
-    for (uint32_t f = 0; f < j.img.n_chunks; f += kJbOwnChunks) {
-      wg[w++] = JbHuffWg{(uint32_t)i, f};
-      if (j.img.needs_sync) swg[sw++] = JbHuffWg{(uint32_t)i, f};
-    }
-    memcpy(st + si, j.starts.data(), j.starts.size() * 4);
-    si += j.starts.size();
-    memcpy(h + sc, j.scan.data(), j.scan.size());
-    sc += a16(j.scan.size());
-  }
-  memset(h + sc, 0, 256);
-  return JB_OK;
+// the one place an error text is kept: every file reports through it (jb_ctx.h fail() formats for it)
+int jb_fail_(jb_ctx *ctx, int code, const char *msg) {
+  if (ctx) ctx->error = msg;
+  g_tls_error = msg;
+  return code;
 }
+

@@ -13,7 +13,6 @@
 // waits for its own images outside the mutex.
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,105 +22,13 @@
 #include <thread>
 #include <vector>
 
-#include <sched.h>
-
 #include <memory>
 
 #include "../../include/jpegblk.h"
 #include "jb_hostmem.h"
-#include "jb_huff.h"
-#include "jb_knobs.h"
-#include "jb_plan.h"
-
-struct jb_ctx;
-int jb_fail_(jb_ctx *ctx, int code, const char *msg);
-// device-side entropy decoding: several prepared images of one geometry in one submission; the
-// images' status words (0 = decoded cleanly) are copied to `status_out` (pinned) with the pixels
-// (plan: what the pixels look like -- jb_plan.h; tight rows, and tight planes with a planar format)
-// (dst_device: `rgb` is device memory of the context's device, nothing is downloaded)
-extern "C" int jb_submit_packed_(jb_ctx *ctx, const jb_image_desc *desc, const uint16_t *qtabs, const uint8_t *packed,
-                                 const JbHuffLayout *lay, uint8_t *rgb, uint32_t *status_out, int *ticket, const JbOutPlan &plan,
-                                 int dst_device);
-// jb_submit_batch (dst_device = 0) or its device-output form (1) in the plan's output
-extern "C" int jb_submit_group_(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef, const uint16_t *qtabs,
-                                uint8_t *rgb, int *ticket, const JbOutPlan &plan, int dst_device);
-// jb_wait in two halves, so that many threads can wait on one shared context (jb_api.cpp):
-// under the caller's lock, the event to block on (nullptr: the submission has completed) ...
-void *jb_wait_begin_(jb_ctx *ctx, int ticket);
-// ... and the blocking part, without the lock
-int jb_wait_block_(jb_ctx *ctx, void *event);
-// binds the calling thread to the CPUs of the NUMA node closest to a device (jb_api.cpp)
-int jb_bind_thread_near_device_(int device, int numa_knob);
-extern "C" void jb_ctx_set_download_age_(jb_ctx *ctx, uint64_t age);
-// JB_OK when [p, p + bytes) is device memory of `device` (jb_api.cpp)
-int jb_check_device_region_(int device, const void *p, size_t bytes);
+#include "jb_internal.h"
 
 namespace {
-
-double now_s() {
-  using namespace std::chrono;
-  return duration<double>(steady_clock::now().time_since_epoch()).count();
-}
-
-bool read_file(const char *path, std::vector<uint8_t> &buf) {
-  FILE *f = fopen(path, "rb");
-  if (!f) return false;
-  fseek(f, 0, SEEK_END);
-  long n = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  if (n < 0) {
-    fclose(f);
-    return false;
-  }
-  buf.resize((size_t)n);
-  size_t got = n ? fread(buf.data(), 1, (size_t)n, f) : 0;
-  fclose(f);
-  return got == (size_t)n;
-}
-
-// The first `limit` bytes of a file (all of it when it is no longer than that); *whole says which.
-bool read_prefix(const char *path, size_t limit, std::vector<uint8_t> &buf, bool *whole) {
-  FILE *f = fopen(path, "rb");
-  if (!f) return false;
-  buf.resize(limit + 1);
-  const size_t got = fread(buf.data(), 1, limit + 1, f);
-  const bool bad = ferror(f) != 0;
-  fclose(f);
-  if (bad) return false;
-  *whole = got <= limit;
-  buf.resize(got < limit ? got : (*whole ? got : limit));
-  return true;
-}
-
-// CPUs this process may actually use: the affinity mask capped by the cgroup CPU quota
-// (cgroup v2 cpu.max, v1 cpu.cfs_quota_us / cpu.cfs_period_us).  More entropy threads than that only
-// time-slice against each other and against the HIP runtime's own threads: measured on a 16-CPU
-// quota, 24-32 threads halved the rate of 16 (8192x8192: 187 -> 98-110 images/s).
-int available_cpus() {
-  int n = 0;
-  cpu_set_t set;
-  if (sched_getaffinity(0, sizeof set, &set) == 0) n = CPU_COUNT(&set);
-  if (n < 1) n = (int)std::thread::hardware_concurrency();
-  if (n < 1) n = 1;
-  long quota = -1, period = 100000;
-  if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-    char q[32] = {0};
-    if (fscanf(f, "%31s %ld", q, &period) >= 1 && strcmp(q, "max") != 0) quota = atol(q);
-    fclose(f);
-  } else if (FILE *g = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) {
-    if (fscanf(g, "%ld", &quota) != 1) quota = -1;
-    fclose(g);
-    if (FILE *h = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) {
-      if (fscanf(h, "%ld", &period) != 1) period = 100000;
-      fclose(h);
-    }
-  }
-  if (quota > 0 && period > 0) {
-    const int by_quota = (int)((quota + period - 1) / period);
-    if (by_quota >= 1 && by_quota < n) n = by_quota;
-  }
-  return n;
-}
 
 // What a decoder has been asked to deliver (jb_batch_decoder_set_scale, jb_batch_decoder_set_output_format,
 // jb_batch_decoder_set_roi, jb_batch_decoder_set_resize): ONE value on the decoder, copied to its parts, its twin and every
@@ -164,7 +71,7 @@ constexpr int kMaxSlots = 4;
 // 41.1-41.9 / 40.4-40.6 k images/s, to the arena 8,250 / 8,180-8,260 / 8,150-8,170 / 8,160-8,200; 32 8192x8192 files
 // left in HBM 2,060-2,170 / 1,730-1,810 / 1,750-1,780 / 1,760-1,770).  (Round 2's kernels wanted four for
 // device-resident output -- +35 % -- because a group's launches took milliseconds: profiles/r02b/ab_pipeline_depth.txt.)
-int lane_slots(bool /*device_output*/) { return 2; }
+constexpr int kLaneSlots = 2;
 
 // what one host thread owns across runs: the pinned buffers its Huffman stage decodes into and,
 // when the caller's pixel buffers are pageable (no arena), pinned pixel staging -- a
@@ -289,7 +196,7 @@ struct Totals {
 struct Run {
   int device;
   size_t dev_cap_coef, dev_cap_rgb;  // ring-slot capacity: bounds a group whose entropy stage runs on the device
-  int n_slots;                       // submissions a host thread keeps in flight (lane_slots)
+  int n_slots;                       // submissions a host thread keeps in flight (kLaneSlots)
   const char *const *paths;
   int n_paths, n_threads, inner_threads;
   const std::vector<std::vector<int>> *lists;  // which files each host thread owns (indices into paths)
@@ -346,9 +253,9 @@ void parse_pass(const Run &r, int t, std::vector<Parsed> &parsed, size_t *max_co
     p.status = JB_ERR_FORMAT;
     p.loaded = false;
     for (int level = 0; level < 3 && ok && p.status != JB_OK && !p.loaded; level++) {  // heads, then the whole file decides
-      const double a = now_s();
-      ok = level < 2 ? read_prefix(r.paths[i], kHeadBytes[level], p.bytes, &p.loaded) : read_file(r.paths[i], p.bytes);
-      *t_read += now_s() - a;
+      const double a = jb_now_s_();
+      ok = level < 2 ? jb_read_prefix_(r.paths[i], kHeadBytes[level], p.bytes, &p.loaded) : jb_read_file_(r.paths[i], p.bytes);
+      *t_read += jb_now_s_() - a;
       if (level == 2) p.loaded = ok;
       if (ok) parse_one(p, r.out);
     }
@@ -375,56 +282,48 @@ void parse_pass(const Run &r, int t, std::vector<Parsed> &parsed, size_t *max_co
 constexpr size_t kGroupBytes = (size_t)16 << 20;  // coefficient bytes per group (and per pinned buffer)
 constexpr int kMaxGroup = 64;
 
+bool same_geometry(const Parsed &a, const Parsed &b) {
+  return a.desc.width == b.desc.width && a.desc.height == b.desc.height && a.desc.hs == b.desc.hs &&
+         a.desc.vs == b.desc.vs && a.desc.qtab_id[0] == b.desc.qtab_id[0] &&
+         a.desc.qtab_id[1] == b.desc.qtab_id[1] && a.desc.qtab_id[2] == b.desc.qtab_id[2];
+}
+
+// a group in flight in one of the thread's slots
+struct Group {
+  int ticket = -1, first = -1, n = 0;  // images first .. first+n-1 of this thread's list
+  bool on_device = false;              // the group's entropy stage ran on the device (jb_huff.hip)
+};
+
+// how many images of the head's geometry a group may hold: decoded on the host, on the device, and on the device
+// without the ramp of the first groups (what the pinned blob is sized for)
+struct Rooms {
+  int host, dev, dev_full;
+};
+
+// the group being formed, from step to step: images k .. k+n-1 of the thread's list, for slot s
+struct Forming {
+  int k, s;
+  int n = 0;
+  bool on_device = false;
+  std::vector<std::unique_ptr<JbHuffJob>> jobs;  // on_device: the prepared images
+  uint8_t *dst = nullptr;                        // where the group's pixels go
+  int st = JB_OK;                                // what place / pack / submit made of it
+  std::string text;
+  JbHuffLayout lay;
+};
+
 // pass 2 (per host thread): decode a group of images into pinned slot g%2 and submit it; before a
 // slot is reused, the group that used it two steps ago is finished (it has long been through the
 // device by then: entropy decoding takes ~10x the transfers)
-void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, int setup_rc, const std::string &setup_text) {
-  jb_bind_thread_near_device_(r.device, r.knobs->numa);
+struct LaneWorker {
+  const Run &r;
+  Lane *lane;
+  int t;
+  std::vector<Parsed> &parsed;
+  int setup_rc;
+  const std::string &setup_text;
   const bool use_arena = r.arena && r.arena->base;
   const bool to_device = use_arena && r.arena->on_device;
-  double t_entropy = 0, t_wait = 0, t_read = 0;
-  double first_submit = 1e30, last_submit = 0, first_back = 1e30;  // (JPEGBLK_TIMING=3)
-  // the rest of a file whose head was parsed in pass 1
-  auto load = [&](Parsed &p, int i) {
-    if (p.loaded || p.status != JB_OK) return;
-    const double a = now_s();
-    if (read_file(r.paths[i], p.bytes)) {
-      p.loaded = true;
-    } else {
-      p.status = JB_ERR_FORMAT;
-      p.error = "cannot read file";
-      p.bytes.clear();
-    }
-    t_read += now_s() - a;
-  };
-  // (a run without pass 1) headers of file k of this thread's list, from the whole file; -> false: the image does
-  // not fit the buffers this decoder has (it waits for the second round)
-  auto ready = [&](int k) {
-    Parsed &p = parsed[(size_t)k];
-    if (!p.have) {
-      const int i = (*r.lists)[(size_t)t][(size_t)k];
-      const double a = now_s();
-      const bool ok = read_file(r.paths[i], p.bytes);
-      t_read += now_s() - a;
-      p.have = true;
-      p.loaded = ok;
-      if (ok) {
-        parse_one(p, r.out);
-      } else {
-        p.status = JB_ERR_FORMAT;
-        p.error = "cannot read file";
-        p.bytes.clear();
-      }
-    }
-    if (!r.lazy || p.status != JB_OK) return true;
-    const size_t c = (size_t)p.geo.coef_bytes, x = (size_t)p.geo.rgb_bytes;
-    return c <= lane->cap_coef && x <= lane->cap_rgb && c <= r.slot_coef && x <= r.slot_rgb;
-  };
-  struct Group {
-    int ticket = -1, first = -1, n = 0;  // images first .. first+n-1 of this thread's list
-    bool on_device = false;              // the group's entropy stage ran on the device (jb_huff.hip)
-  } grp[kMaxSlots];
-  const int kSlots = r.n_slots;
   // Where the entropy stage runs.  The batch decoder's default is the DEVICE for every baseline image
   // the device decoders take (restart intervals: one lane per interval; none: the self-synchronising
   // decoder), 16 intervals / chunks or more: measured against 16 host threads it is 1.06x (8,192 small
@@ -440,9 +339,54 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
   const bool dev_entropy = r.knobs->gpu_huffman != 0;
   const uint32_t min_intervals = r.knobs->gpu_huffman == 2 ? 1u : 16u;
   const int dev_max_group = kMaxGroup;  // images per device-entropy group
+  double t_entropy = 0, t_wait = 0, t_read = 0;
+  double first_submit = 1e30, last_submit = 0, first_back = 1e30;  // (JPEGBLK_TIMING=3)
+  Group grp[kMaxSlots];
+  int slot = 0;
+  int dev_groups = 0;  // device-entropy groups this thread has submitted
   std::vector<uint16_t> qtabs;
-  auto index_of = [&](int k) { return (*r.lists)[(size_t)t][(size_t)k]; };
-  auto report = [&](int i, int st, const std::string &text) {
+
+  // the rest of a file whose head was parsed in pass 1
+  void load(Parsed &p, int i) {
+    if (p.loaded || p.status != JB_OK) return;
+    const double a = jb_now_s_();
+    if (jb_read_file_(r.paths[i], p.bytes)) {
+      p.loaded = true;
+    } else {
+      p.status = JB_ERR_FORMAT;
+      p.error = "cannot read file";
+      p.bytes.clear();
+    }
+    t_read += jb_now_s_() - a;
+  }
+
+  // (a run without pass 1) headers of file k of this thread's list, from the whole file; -> false: the image does
+  // not fit the buffers this decoder has (it waits for the second round)
+  bool ready(int k) {
+    Parsed &p = parsed[(size_t)k];
+    if (!p.have) {
+      const int i = (*r.lists)[(size_t)t][(size_t)k];
+      const double a = jb_now_s_();
+      const bool ok = jb_read_file_(r.paths[i], p.bytes);
+      t_read += jb_now_s_() - a;
+      p.have = true;
+      p.loaded = ok;
+      if (ok) {
+        parse_one(p, r.out);
+      } else {
+        p.status = JB_ERR_FORMAT;
+        p.error = "cannot read file";
+        p.bytes.clear();
+      }
+    }
+    if (!r.lazy || p.status != JB_OK) return true;
+    const size_t c = (size_t)p.geo.coef_bytes, x = (size_t)p.geo.rgb_bytes;
+    return c <= lane->cap_coef && x <= lane->cap_rgb && c <= r.slot_coef && x <= r.slot_rgb;
+  }
+
+  int index_of(int k) const { return (*r.lists)[(size_t)t][(size_t)k]; }
+
+  void report(int i, int st, const std::string &text) {
     r.statuses[i] = st;
     if (st == JB_OK) return;
     if (!use_arena) jb_free(r.rgb[i]);
@@ -452,11 +396,35 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
       r.tot->first_error = st;
       r.tot->first_error_text = std::string(r.paths[i]) + ": " + text;
     }
-  };
-  auto finish_slot = [&](int s) {
+  }
+
+  // the device decoder met data it calls corrupt: the host decoder is the authority -- image j of the group in slot
+  // s again, entropy stage on the host (the slot's coefficient buffer is free: the group is done)
+  int redo_on_host(int s, int j, uint8_t *staged, std::string &text_j) {
+    Parsed &p = parsed[(size_t)(grp[s].first + j)];
+    int16_t *const cbuf = lane->coef_at(s);
+    int st_j = cbuf ? jb_entropy_decode(p.bytes.data(), p.bytes.size(), &p.desc, p.qtabs, cbuf, lane->cap_coef) : (int)JB_ERR_HIP;
+    if (st_j == JB_OK) {
+      int ticket = -1;
+      void *ev2 = nullptr;
+      {
+        std::lock_guard<std::mutex> lk(r.dev->mu);
+        st_j = jb_submit_group_(r.dev->ctx, &p.desc, 1, cbuf, p.qtabs, staged, &ticket, p.plan, to_device);
+        if (st_j == JB_OK) ev2 = jb_wait_begin_(r.dev->ctx, ticket);
+        else text_j = jb_last_error(r.dev->ctx);
+      }
+      if (st_j == JB_OK && ev2) st_j = jb_wait_block_(r.dev->ctx, ev2);
+    } else {
+      text_j = jb_last_error(nullptr);
+    }
+    return st_j;
+  }
+
+  // the group in slot s has come back: its images are reported, the slot is free
+  void finish_slot(int s) {
     Group &g = grp[s];
     if (g.n == 0) return;
-    double a = now_s();
+    double a = jb_now_s_();
     void *ev;
     {
       std::lock_guard<std::mutex> lk(r.dev->mu);
@@ -471,25 +439,7 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
       int st_j = st;
       std::string text_j = text;
       uint8_t *const staged = use_arena ? r.rgb[i] : lane->out[s] + (size_t)j * rgb_bytes;
-      if (st == JB_OK && g.on_device && lane->status[s][j] != 0) {
-        // the device decoder met data it calls corrupt: the host decoder is the authority -- this one
-        // image again, entropy stage on the host (the slot's coefficient buffer is free: the group is done)
-        int16_t *const cbuf = lane->coef_at(s);
-        st_j = cbuf ? jb_entropy_decode(p.bytes.data(), p.bytes.size(), &p.desc, p.qtabs, cbuf, lane->cap_coef) : (int)JB_ERR_HIP;
-        if (st_j == JB_OK) {
-          int ticket = -1;
-          void *ev2 = nullptr;
-          {
-            std::lock_guard<std::mutex> lk(r.dev->mu);
-            st_j = jb_submit_group_(r.dev->ctx, &p.desc, 1, cbuf, p.qtabs, staged, &ticket, p.plan, to_device);
-            if (st_j == JB_OK) ev2 = jb_wait_begin_(r.dev->ctx, ticket);
-            else text_j = jb_last_error(r.dev->ctx);
-          }
-          if (st_j == JB_OK && ev2) st_j = jb_wait_block_(r.dev->ctx, ev2);
-        } else {
-          text_j = jb_last_error(nullptr);
-        }
-      }
+      if (st == JB_OK && g.on_device && lane->status[s][j] != 0) st_j = redo_on_host(s, j, staged, text_j);
       if (g.on_device) {
         p.bytes.clear();
         p.bytes.shrink_to_fit();
@@ -498,39 +448,12 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
         memcpy(r.rgb[i], staged, rgb_bytes);
       report(i, st_j, text_j);
     }
-    t_wait += now_s() - a;
-    if (first_back > 1e29) first_back = now_s();
+    t_wait += jb_now_s_() - a;
+    if (first_back > 1e29) first_back = jb_now_s_();
     g.n = 0;
-  };
-  auto same_geometry = [](const Parsed &a, const Parsed &b) {
-    return a.desc.width == b.desc.width && a.desc.height == b.desc.height && a.desc.hs == b.desc.hs &&
-           a.desc.vs == b.desc.vs && a.desc.qtab_id[0] == b.desc.qtab_id[0] &&
-           a.desc.qtab_id[1] == b.desc.qtab_id[1] && a.desc.qtab_id[2] == b.desc.qtab_id[2];
-  };
-  const int n_mine = (int)parsed.size();
-  int k = 0, slot = 0;
-  int dev_groups = 0;  // device-entropy groups this thread has submitted
-  while (k < n_mine) {
-    Parsed &head = parsed[(size_t)k];
-    if (!ready(k)) {  // (a run without pass 1) larger than anything this decoder is sized for: the second round's
-      (*r.deferred)[(size_t)t].push_back(k);
-      head.bytes.clear();
-      head.bytes.shrink_to_fit();
-      k++;
-      continue;
-    }
-    load(head, index_of(k));
-    r.rgb[index_of(k)] = nullptr;
-    r.widths[index_of(k)] = r.heights[index_of(k)] = 0;
-    if (head.status != JB_OK || setup_rc != JB_OK) {  // rejected in pass 1, or nothing could be set up
-      report(index_of(k), head.status != JB_OK ? head.status : setup_rc, head.status != JB_OK ? head.error : setup_text);
-      head.bytes.clear();
-      head.bytes.shrink_to_fit();
-      k++;
-      continue;
-    }
-    const int s = slot;
-    finish_slot(s);
+  }
+
+  Rooms group_room(const Parsed &head) const {
     const size_t coef_bytes = (size_t)head.geo.coef_bytes, rgb_bytes = (size_t)head.geo.rgb_bytes;
     // a group must fit the coefficient AND the pixel capacity (pinned lane buffers and ring slots are
     // sized from the batch's largest image: rgb/coef is 0.5 for 4:4:4 and 1.0 for 4:2:0, so many
@@ -552,18 +475,25 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
     // arena 6,700 -> 7,240, interleaved on one box.  Off by default.)
     if (dev_groups < 2 && r.knobs->group_ramp) room_dev = room_dev >> (2 - dev_groups);
     if (room_dev < 1) room_dev = 1;
-    // entropy-decode consecutive images of the head's geometry into the slot, back to back -- or,
-    // for files with restart intervals, only ready them for the device decoder
-    int n = 0;
-    bool on_device = false;
-    std::vector<std::unique_ptr<JbHuffJob>> jobs;
-    while (n < (on_device ? room_dev : room) && k + n < n_mine) {
+    return Rooms{room, room_dev, room_dev_full};
+  }
+
+  // entropy-decode consecutive images of the head's geometry into the slot, back to back -- or,
+  // for files with restart intervals, only ready them for the device decoder.  f.n == 0: the head's scan is corrupt
+  // (reported here; nothing else ends a group before its first image)
+  void form_group(Forming &f, const Rooms &rooms) {
+    const int k = f.k, s = f.s, n_mine = (int)parsed.size();
+    Parsed &head = parsed[(size_t)k];
+    const size_t coef_bytes = (size_t)head.geo.coef_bytes;
+    int &n = f.n;
+    bool &on_device = f.on_device;
+    while (n < (on_device ? rooms.dev : rooms.host) && k + n < n_mine) {
       Parsed &p = parsed[(size_t)(k + n)];
       if (n > 0 && !ready(k + n)) break;  // (the next group's head: it is set aside there)
       if (n > 0 && (p.status != JB_OK || !same_geometry(head, p))) break;
       load(p, index_of(k + n));
       if (p.status != JB_OK) break;  // (n > 0: the head was loaded above; the next group reports it)
-      double a = now_s();
+      double a = jb_now_s_();
       std::unique_ptr<JbHuffJob> job;
       bool eligible = false;
       if (dev_entropy) {
@@ -579,8 +509,8 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
       else if (eligible != on_device) break;  // the next group starts with this image
       if (on_device) {
         memcpy(p.qtabs, job->qtabs, sizeof p.qtabs);
-        jobs.push_back(std::move(job));
-        t_entropy += now_s() - a;
+        f.jobs.push_back(std::move(job));
+        t_entropy += jb_now_s_() - a;
         n++;  // (the file bytes stay until the group has come back clean)
         continue;
       }
@@ -589,7 +519,7 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
       int st = cbuf ? jb_entropy_decode_mt(p.bytes.data(), p.bytes.size(), &p.desc, p.qtabs,
                                            cbuf + (size_t)n * (coef_bytes / 2), coef_bytes, r.inner_threads)
                     : (int)JB_ERR_HIP;
-      t_entropy += now_s() - a;
+      t_entropy += jb_now_s_() - a;
       p.bytes.clear();
       p.bytes.shrink_to_fit();
       if (st != JB_OK) {  // a corrupt scan: it leaves the group, the group ends before it
@@ -598,25 +528,27 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
         if (n == 0) {
           r.rgb[index_of(k)] = nullptr;
           report(index_of(k), st, p.error);
-          k++;
         }
         break;
       }
       n++;
     }
-    if (n == 0) continue;
-    // where the pixels go
-    uint8_t *dst = use_arena ? r.arena->take((size_t)n * rgb_bytes) : lane->out[s];
-    int st = JB_OK;
-    std::string text;
-    if (!dst) {
-      st = JB_ERR_CAPACITY;
-      text = "output arena exhausted";
-    } else if ((uintptr_t)dst & (uintptr_t)(head.plan.esize - 1)) {
+  }
+
+  // where the pixels go
+  void place_outputs(Forming &f) {
+    const int k = f.k, n = f.n;
+    const Parsed &head = parsed[(size_t)k];
+    const size_t rgb_bytes = (size_t)head.geo.rgb_bytes;
+    f.dst = use_arena ? r.arena->take((size_t)n * rgb_bytes) : lane->out[f.s];
+    if (!f.dst) {
+      f.st = JB_ERR_CAPACITY;
+      f.text = "output arena exhausted";
+    } else if ((uintptr_t)f.dst & (uintptr_t)(head.plan.esize - 1)) {
       // (groups start on 256-byte steps of the arena / region and an image is a whole number of elements, so every image
       // is element-aligned unless the region itself is not: checked, not assumed -- the kernel's f32 / f16 stores need it)
-      st = JB_ERR_GEOMETRY;
-      text = "output region is not aligned to the format's element size";
+      f.st = JB_ERR_GEOMETRY;
+      f.text = "output region is not aligned to the format's element size";
     }
     qtabs.resize((size_t)n * 256);
     for (int j = 0; j < n; j++) {
@@ -626,66 +558,112 @@ void decode_pass(const Run &r, Lane *lane, int t, std::vector<Parsed> &parsed, i
       r.widths[i] = p.plan.out_w;
       r.heights[i] = p.plan.out_h;
       r.rgb[i] = nullptr;
-      if (st == JB_OK) {
-        r.rgb[i] = use_arena ? dst + (size_t)j * rgb_bytes : jb_alloc_pixels_(rgb_bytes);
+      if (f.st == JB_OK) {
+        r.rgb[i] = use_arena ? f.dst + (size_t)j * rgb_bytes : jb_alloc_pixels_(rgb_bytes);
         if (!r.rgb[i]) {
-          st = JB_ERR_CAPACITY;
-          text = "out of memory";
+          f.st = JB_ERR_CAPACITY;
+          f.text = "out of memory";
         }
       }
     }
-    JbHuffLayout lay;
-    if (st == JB_OK && on_device) {  // pack the group into this thread's pinned blob -- outside the shared lock
-      std::vector<const JbHuffJob *> ptrs;
-      for (auto &j : jobs) ptrs.push_back(j.get());
-      const size_t blob_bytes = jb_huff_pack_size_(ptrs.data(), n);
-      uint8_t *blob = lane->ensure_blob(r.device, s, blob_bytes, blob_bytes / (size_t)n * (size_t)room_dev_full);
-      if (!blob) {
-        st = JB_ERR_HIP;
-        text = "pinned host allocation failed";
-      } else if ((st = jb_huff_pack_(ptrs.data(), n, (int64_t)coef_bytes, blob, &lay)) != JB_OK) {
-        text = "submission too large for the device entropy decoder";
-      }
-      jobs.clear();  // (everything the jobs held is in the blob now)
-    }
-    if (st == JB_OK) {
-      double a = now_s();
-      // every copy of the submission is pinned <-> device, so this returns at once and the
-      // transfers and the kernel run while this thread decodes its next group
-      std::lock_guard<std::mutex> lk(r.dev->mu);
-      if (on_device) {
-        st = jb_submit_packed_(r.dev->ctx, &head.desc, qtabs.data(), lane->blob[s], &lay, dst, lane->status[s], &grp[s].ticket, head.plan,
-                               to_device);
-      } else {
-        st = jb_submit_group_(r.dev->ctx, &head.desc, n, lane->coef[s], qtabs.data(), dst, &grp[s].ticket, head.plan, to_device);
-      }
-      if (st != JB_OK) text = jb_last_error(r.dev->ctx);
-      t_wait += now_s() - a;
-      last_submit = now_s();
-      if (first_submit > 1e29) first_submit = last_submit;
-    }
-    if (st != JB_OK) {
-      for (int j = 0; j < n; j++) report(index_of(k + j), st, text);
-    } else {
-      grp[s].first = k;
-      grp[s].n = n;
-      grp[s].on_device = on_device;
-      if (on_device) dev_groups++;
-      slot = (slot + 1) % kSlots;
-    }
-    k += n;
   }
-  for (int j = 0; j < kSlots; j++) finish_slot((slot + j) % kSlots);  // oldest first
-  std::lock_guard<std::mutex> g(r.tot->mu);
-  r.tot->t_entropy += t_entropy;
-  r.tot->t_device += t_wait;
-  r.tot->t_read += t_read;
-  if (first_submit < r.tot->first_submit) r.tot->first_submit = first_submit;
-  if (last_submit > r.tot->last_submit) r.tot->last_submit = last_submit;
-  if (first_back < r.tot->first_back) r.tot->first_back = first_back;
-  const double done = now_s();
-  if (done < r.tot->first_thread_done) r.tot->first_thread_done = done;
-}
+
+  // pack the group into this thread's pinned blob -- outside the shared lock
+  void pack_group(Forming &f, int room_dev_full) {
+    if (f.st != JB_OK || !f.on_device) return;
+    const int n = f.n;
+    std::vector<const JbHuffJob *> ptrs;
+    for (auto &j : f.jobs) ptrs.push_back(j.get());
+    const size_t blob_bytes = jb_huff_pack_size_(ptrs.data(), n);
+    uint8_t *blob = lane->ensure_blob(r.device, f.s, blob_bytes, blob_bytes / (size_t)n * (size_t)room_dev_full);
+    if (!blob) {
+      f.st = JB_ERR_HIP;
+      f.text = "pinned host allocation failed";
+    } else if ((f.st = jb_huff_pack_(ptrs.data(), n, (int64_t)parsed[(size_t)f.k].geo.coef_bytes, blob, &f.lay)) != JB_OK) {
+      f.text = "submission too large for the device entropy decoder";
+    }
+    f.jobs.clear();  // (everything the jobs held is in the blob now)
+  }
+
+  void submit_group(Forming &f) {
+    if (f.st != JB_OK) return;
+    const int s = f.s;
+    Parsed &head = parsed[(size_t)f.k];
+    double a = jb_now_s_();
+    // every copy of the submission is pinned <-> device, so this returns at once and the
+    // transfers and the kernel run while this thread decodes its next group
+    std::lock_guard<std::mutex> lk(r.dev->mu);
+    if (f.on_device) {
+      f.st = jb_submit_packed_(r.dev->ctx, &head.desc, qtabs.data(), lane->blob[s], &f.lay, f.dst, lane->status[s], &grp[s].ticket, head.plan,
+                               to_device);
+    } else {
+      f.st = jb_submit_group_(r.dev->ctx, &head.desc, f.n, lane->coef[s], qtabs.data(), f.dst, &grp[s].ticket, head.plan, to_device);
+    }
+    if (f.st != JB_OK) f.text = jb_last_error(r.dev->ctx);
+    t_wait += jb_now_s_() - a;
+    last_submit = jb_now_s_();
+    if (first_submit > 1e29) first_submit = last_submit;
+  }
+
+  void run() {
+    jb_bind_thread_near_device_(r.device, r.knobs->numa);
+    const int kSlots = r.n_slots;
+    const int n_mine = (int)parsed.size();
+    int k = 0;
+    while (k < n_mine) {
+      Parsed &head = parsed[(size_t)k];
+      if (!ready(k)) {  // (a run without pass 1) larger than anything this decoder is sized for: the second round's
+        (*r.deferred)[(size_t)t].push_back(k);
+        head.bytes.clear();
+        head.bytes.shrink_to_fit();
+        k++;
+        continue;
+      }
+      load(head, index_of(k));
+      r.rgb[index_of(k)] = nullptr;
+      r.widths[index_of(k)] = r.heights[index_of(k)] = 0;
+      if (head.status != JB_OK || setup_rc != JB_OK) {  // rejected in pass 1, or nothing could be set up
+        report(index_of(k), head.status != JB_OK ? head.status : setup_rc, head.status != JB_OK ? head.error : setup_text);
+        head.bytes.clear();
+        head.bytes.shrink_to_fit();
+        k++;
+        continue;
+      }
+      const int s = slot;
+      finish_slot(s);
+      const Rooms rooms = group_room(head);
+      Forming f{k, s};
+      form_group(f, rooms);
+      if (f.n == 0) {  // (the head left the list)
+        k++;
+        continue;
+      }
+      place_outputs(f);
+      pack_group(f, rooms.dev_full);
+      submit_group(f);
+      if (f.st != JB_OK) {
+        for (int j = 0; j < f.n; j++) report(index_of(k + j), f.st, f.text);
+      } else {
+        grp[s].first = k;
+        grp[s].n = f.n;
+        grp[s].on_device = f.on_device;
+        if (f.on_device) dev_groups++;
+        slot = (slot + 1) % kSlots;
+      }
+      k += f.n;
+    }
+    for (int j = 0; j < kSlots; j++) finish_slot((slot + j) % kSlots);  // oldest first
+    std::lock_guard<std::mutex> g(r.tot->mu);
+    r.tot->t_entropy += t_entropy;
+    r.tot->t_device += t_wait;
+    r.tot->t_read += t_read;
+    if (first_submit < r.tot->first_submit) r.tot->first_submit = first_submit;
+    if (last_submit > r.tot->last_submit) r.tot->last_submit = last_submit;
+    if (first_back < r.tot->first_back) r.tot->first_back = first_back;
+    const double done = jb_now_s_();
+    if (done < r.tot->first_thread_done) r.tot->first_thread_done = done;
+  }
+};
 
 }  // namespace
 
@@ -701,7 +679,7 @@ struct jb_batch_decoder {
   // (never more submissions in flight than the context's ring of 64 slots holds: a thread that found the ring full
   // would wait for the oldest submission while holding the lock every other thread submits under)
   int slots() const {
-    const int want = lane_slots(arena->base && arena->on_device), fit = lanes.empty() ? want : 64 / (int)lanes.size();
+    const int want = kLaneSlots, fit = lanes.empty() ? want : 64 / (int)lanes.size();
     return want < fit ? want : fit < 1 ? 1 : fit;
   }
   // the caller's device region as it was given (jb_batch_decoder_set_device_output[s]); submit / collect
@@ -791,7 +769,7 @@ int clamp_threads(int n_threads, const JbKnobs &knobs) {
   if (n_threads < 1) n_threads = 1;
   if (n_threads > 64) n_threads = 64;  // one ring slot each at least (64 host threads decode 30 Gpixel/s: far beyond the link)
   // no more entropy threads than CPUs this process may use (JPEGBLK_OVERSUBSCRIBE=1 lifts that)
-  if (!knobs.oversubscribe && n_threads > available_cpus()) n_threads = available_cpus();
+  if (!knobs.oversubscribe && n_threads > jb_available_cpus_()) n_threads = jb_available_cpus_();
   return n_threads;
 }
 
@@ -834,7 +812,7 @@ int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8
   Totals tot;
   Shared dev;
   if (top) d->arena->used = 0;  // the previous run's images are released
-  const double t0 = now_s();
+  const double t0 = jb_now_s_();
   // every pinned buffer and ring slot holds one large image or a group of small ones: the group
   // figure bounds the coefficient and the pixel side alike (rgb_bytes <= coef_bytes in every layout)
   size_t group_bytes = kGroupBytes;
@@ -869,7 +847,7 @@ int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8
     r.lazy = lazy;
     r.deferred = &deferred;
     r.out = d->out;
-    const double tr0 = now_s();
+    const double tr0 = jb_now_s_();
     std::vector<std::vector<Parsed>> parsed((size_t)nt);
     for (int t = 0; t < nt; t++) parsed[(size_t)t].resize(lists[(size_t)t].size());
     int setup_rc = JB_OK;
@@ -899,7 +877,7 @@ int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8
         if (share > (size_t)kMaxGroup) share = (size_t)kMaxGroup;
         if (ring_bytes > share * max_coef) ring_bytes = share * max_coef;
       }
-      t_parsed = now_s();
+      t_parsed = jb_now_s_();
       setup_rc = max_coef ? d->ensure_all(max_coef, max_rgb, nt, ring_bytes, ring_bytes) : JB_OK;
       // a device group is bounded by this round's group size (the ring slots may be larger: an earlier run's)
       const size_t group_cap = ring_bytes > max_coef ? ring_bytes : max_coef;
@@ -920,7 +898,7 @@ int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8
     }
     r.slot_coef = d->ctx_coef;
     r.slot_rgb = d->ctx_rgb;
-    const double t_setup = now_s();
+    const double t_setup = jb_now_s_();
     if (setup_rc != JB_OK) setup_text = jb_last_error(nullptr);
     // pass 2: entropy decoding on the host threads, all submitting to the shared context
     dev.ctx = d->ctx;
@@ -934,7 +912,7 @@ int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8
     {
       std::vector<std::thread> th;
       for (int t = 0; t < nt; t++)
-        th.emplace_back([&, t] { decode_pass(r, &d->lanes[(size_t)t], t, parsed[(size_t)t], setup_rc, setup_text); });
+        th.emplace_back([&, t] { LaneWorker{r, &d->lanes[(size_t)t], t, parsed[(size_t)t], setup_rc, setup_text}.run(); });
       for (auto &x : th) x.join();
     }
     if (left_over)
@@ -944,7 +922,7 @@ int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8
       fprintf(stderr, "run_single %zu files%s: headers %.2f ms, setup %.2f, first submit at %.2f, first group back at %.2f, last submit at %.2f, "
               "first thread done at %.2f, all done at %.2f\n", files.size(), lazy ? " (no pass 1)" : "", (t_parsed - tr0) * 1e3, (t_setup - t_parsed) * 1e3,
               (tot.first_submit - tr0) * 1e3, (tot.first_back - tr0) * 1e3, (tot.last_submit - tr0) * 1e3, (tot.first_thread_done - tr0) * 1e3,
-              (now_s() - tr0) * 1e3);
+              (jb_now_s_() - tr0) * 1e3);
   };
   std::vector<int> all((size_t)(n_paths > 0 ? n_paths : 0));
   for (int i = 0; i < n_paths; i++) all[(size_t)i] = i;
@@ -963,7 +941,7 @@ int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8
   }
   if (d->ctx) jb_ctx_synchronize(d->ctx);
   if (times) {
-    times[0] = now_s() - t0;
+    times[0] = jb_now_s_() - t0;
     times[1] = tot.t_entropy;
     times[2] = tot.t_device;
     times[3] = tot.t_read;
@@ -1190,7 +1168,7 @@ int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8_t
   d->own_arena.used = 0;
   for (jb_batch_decoder *part : d->parts)
     if (part->arena == &part->own_arena) part->own_arena.used = 0;  // device regions: recycled by every run
-  const double t0 = now_s();
+  const double t0 = jb_now_s_();
   struct Share {
     std::vector<const char *> paths;
     std::vector<uint8_t *> rgb;
@@ -1234,7 +1212,7 @@ int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8_t
       text = sh[(size_t)k].text;
     }
   if (times) {
-    times[0] = now_s() - t0;
+    times[0] = jb_now_s_() - t0;
     times[1] = times[2] = times[3] = 0;
     for (int k = 0; k < np; k++)
       for (int j = 1; j < 4; j++) times[j] += sh[(size_t)k].times[j];
@@ -1337,8 +1315,7 @@ extern "C" int jb_batch_decoder_set_scale(jb_batch_decoder *d, int denom) {
 extern "C" int jb_batch_decoder_set_output_format(jb_batch_decoder *d, const jb_output_spec *spec) {
   if (!d) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_set_output_format: decoder is NULL");
   if (!spec) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_set_output_format: spec is NULL");
-  if (jb_output_spec_check(spec, 1, 1 << 20) != JB_OK || (spec->format != JB_FMT_RGB_U8_HWC && spec->plane_stride != 0))
-    return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_set_output_format: bad output spec (unknown format, reserved or plane_stride not 0, scale / bias not finite)");
+  if (jb_tight_spec_check_(spec) != JB_OK) return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_set_output_format" JB_TIGHT_SPEC_TEXT);
   if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_output_format: batches are in flight (collect them first)");
   OutputRequest out = d->out;
   out.spec = *spec;

@@ -21,7 +21,6 @@
 //  * restart intervals are counted in MCUs as ITU-T T.81 says; the reference's test
 //    (jpeg.cpp:414,419) agrees with that only when an interval is a whole number of MCU rows
 //    (true for its bundled images/img4.jpg: interval 100 = one row).
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -33,24 +32,8 @@
 #include "../../include/jpegblk.h"
 #include "jb_entropy.h"
 #include "jb_hostmem.h"
-#include "jb_huff.h"
 #include "jb_huff_core.h"
-#include "jb_knobs.h"
-#include "jb_plan.h"
-
-struct jb_ctx;
-int jb_fail_(jb_ctx *ctx, int code, const char *msg);
-void jb_ctx_set_last_desc_(jb_ctx *ctx, const jb_image_desc *d);
-const JbKnobs *jb_ctx_knobs_(const jb_ctx *ctx);  // jb_api.cpp
-// the two routes of decode(bytes) into the pixel kernel (jb_api.cpp), tight rows, `plan` (jb_plan.h) says which pixels:
-// the entropy stage on the device (a prepared job) ...
-extern "C" int jb_decode_job_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, const JbOutPlan &plan);
-// ... or on the host (its coefficients)
-extern "C" int jb_blocks_to_rgb_plan_(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs, uint8_t *rgb,
-                                      const JbOutPlan &plan);
-// general front end (jb_frontend_ext.cpp): progressive, grayscale, multi-scan files
-int jb_ext_decode_(const uint8_t *jpeg, size_t n, jb_image_desc *desc, uint16_t *qtabs, int16_t *coef,
-                   size_t coef_cap_bytes, std::string *err);
+#include "jb_internal.h"
 
 namespace {
 
@@ -466,12 +449,11 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
     if (forced || (automatic && jpeg_bytes >= kAutoDeviceScan)) {
       // JPEGBLK_TIMING=1: where one decode(bytes) through the device path spends its time, on stderr
       const bool timing = knobs.timing == 1;
-      auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-      const double t0 = timing ? now() : 0;
+      const double t0 = timing ? jb_now_s_() : 0;
       std::unique_ptr<JbHuffJob> job(new JbHuffJob());
       if (jb_huff_prepare_(jpeg, jpeg_bytes, job.get(), nullptr, knobs.chunk_bytes) == JB_OK && jb_huff_worth_it_(*job, min_int) &&
           (forced || job->scan_len >= kAutoDeviceScan)) {
-        const double t1 = timing ? now() : 0;
+        const double t1 = timing ? jb_now_s_() : 0;
         const JbOutPlan plan = jb_out_plan_(&job->desc, denom, spec, roi, target);
         if (plan.status != JB_OK) return jb_fail_(ctx, plan.status, plan.why);
         uint8_t *out = jb_alloc_pixels_((size_t)plan.image_bytes);
@@ -479,7 +461,7 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
         const int rc = jb_decode_job_(ctx, job.get(), out, plan);
         if (timing)
           fprintf(stderr, "jb_decode_memory(device path): prepare %.3f ms, submit + wait %.3f ms (%u intervals, %u chunks, %zu bytes of scan), rc %d\n",
-                  (t1 - t0) * 1e3, (now() - t1) * 1e3, job->img.n_int, job->img.n_chunks, job->scan_len, rc);
+                  (t1 - t0) * 1e3, (jb_now_s_() - t1) * 1e3, job->img.n_int, job->img.n_chunks, job->scan_len, rc);
         if (rc == JB_OK) {
           *rgb = out;
           *width = plan.out_w;
@@ -543,8 +525,8 @@ int jb_decode_memory_fmt(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, co
   if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_memory_fmt: ctx is NULL");
   if (!spec || !out) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_memory_fmt: NULL pointer");
   *out = nullptr;
-  if (jb_output_spec_check(spec, 1, 1 << 20) != JB_OK || (spec->format != JB_FMT_RGB_U8_HWC && spec->plane_stride != 0))
-    return jb_fail_(ctx, JB_ERR_GEOMETRY, "jb_decode_memory_fmt: bad output spec (unknown format, reserved or plane_stride not 0, scale / bias not finite)");
+  if (jb_tight_spec_check_(spec) != JB_OK)
+    return jb_fail_(ctx, JB_ERR_GEOMETRY, "jb_decode_memory_fmt" JB_TIGHT_SPEC_TEXT);
   return decode_memory_impl(ctx, jpeg, jpeg_bytes, 1, spec, (uint8_t **)out, width, height);
 }
 
@@ -554,8 +536,8 @@ int jb_decode_memory_roi(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, co
   if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_memory_roi: ctx is NULL");
   if (!roi || !out) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_memory_roi: NULL pointer");
   *out = nullptr;
-  if (spec && (jb_output_spec_check(spec, 1, 1 << 20) != JB_OK || (spec->format != JB_FMT_RGB_U8_HWC && spec->plane_stride != 0)))
-    return jb_fail_(ctx, JB_ERR_GEOMETRY, "jb_decode_memory_roi: bad output spec (unknown format, reserved or plane_stride not 0, scale / bias not finite)");
+  if (spec && jb_tight_spec_check_(spec) != JB_OK)
+    return jb_fail_(ctx, JB_ERR_GEOMETRY, "jb_decode_memory_roi" JB_TIGHT_SPEC_TEXT);
   return decode_memory_impl(ctx, jpeg, jpeg_bytes, 1, spec, (uint8_t **)out, width, height, roi);
 }
 
@@ -566,8 +548,8 @@ int jb_decode_memory_resized(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes
   if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_memory_resized: ctx is NULL");
   if (!out) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_memory_resized: NULL pointer");
   *out = nullptr;
-  if (spec && (jb_output_spec_check(spec, 1, 1 << 20) != JB_OK || (spec->format != JB_FMT_RGB_U8_HWC && spec->plane_stride != 0)))
-    return jb_fail_(ctx, JB_ERR_GEOMETRY, "jb_decode_memory_resized: bad output spec (unknown format, reserved or plane_stride not 0, scale / bias not finite)");
+  if (spec && jb_tight_spec_check_(spec) != JB_OK)
+    return jb_fail_(ctx, JB_ERR_GEOMETRY, "jb_decode_memory_resized" JB_TIGHT_SPEC_TEXT);
   const JbTarget t = {out_w, out_h};
   return decode_memory_impl(ctx, jpeg, jpeg_bytes, 1, spec, (uint8_t **)out, width, height, roi, &t);
 }
@@ -576,12 +558,7 @@ int jb_decode_memory_resized(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes
 static int read_file(jb_ctx *ctx, const char *fn, const char *path, std::vector<uint8_t> &buf) {
   if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, (std::string(fn) + ": ctx is NULL").c_str());
   if (!path) return jb_fail_(ctx, JB_ERR_NULL, (std::string(fn) + ": path is NULL").c_str());
-  FILE *f = fopen(path, "rb");
-  if (!f) return jb_fail_(ctx, JB_ERR_FORMAT, (std::string("cannot open ") + path).c_str());
-  uint8_t chunk[1 << 16];
-  size_t got;
-  while ((got = fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + got);
-  fclose(f);
+  if (!jb_read_file_(path, buf)) return jb_fail_(ctx, JB_ERR_FORMAT, (std::string("cannot open ") + path).c_str());
   return JB_OK;
 }
 

@@ -22,6 +22,7 @@
 
 #include "../../include/jpegblk.h"
 #include "jb_entropy.h"
+#include "jb_internal.h"
 
 namespace {
 

@@ -1,7 +1,7 @@
 // jb_huff.h -- internal interface of the device-side entropy decoder (jb_huff.hip): Huffman
 // decoding of a baseline scan on the GPU, one lane per chunk of at most 128 bytes of every restart
 // interval (self-synchronising, verified).  Not part of the public ABI.  Plain C structs shared by
-// the host code that fills them (jb_frontend.cpp, jb_api.cpp) and the kernels that read them; the
+// the host code that fills them (jb_frontend.cpp, jb_huff_pack.cpp) and the kernels that read them; the
 // per-symbol step both sides agree on is jb_huff_core.h.
 #pragma once
 #include <stdint.h>
@@ -146,7 +146,7 @@ struct JbHuffLaunch {
 // (the launch function is declared in jb_kernels.h: this header stays free of HIP types, the host
 // front end is also built for the CPU alone by tools/fuzz)
 
-// ---- host side (jb_frontend.cpp prepares, jb_api.cpp packs + launches) ----------------------
+// ---- host side (jb_frontend.cpp prepares, jb_huff_pack.cpp packs, jb_api.cpp launches) ----------------------
 #include <string>
 #include <vector>
 

@@ -34,7 +34,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-// "fixed output size": the cap of one scratch of tight uint8 intermediates (jb_api.cpp seam_launch_resized): 20 1080p
+// "fixed output size": the cap of one scratch of tight uint8 intermediates (jb_seam.cpp seam_launch_resized): 20 1080p
 // images, so that a device-entropy group (JPEGBLK_DEV_GROUP_MB) of them stays one launch pair
 constexpr size_t kJbResizeTmpBytes = (size_t)128 << 20;
 

@@ -1,0 +1,264 @@
+// jb_seam.cpp -- the pixel launch of every route: the public device seams (jb_blocks_to_rgb_device*) and, through
+// seam_launch (jb_ctx.h), the staging ring's submissions of jb_api.cpp.
+#include <cstring>
+
+#include "jb_ctx.h"
+#include "jb_kernels.h"
+
+namespace {
+
+// Launches of up to this many 192 / 256-lane workgroups per CU take the small-grid kernels when
+// JPEGBLK_SMALL_GRID is unset.  Measured on one box, cold, events around every launch, the kernels interleaved
+// (profiles/r03/probe_small_grid.json).  4:4:4: one 1080p image (507 workgroups) 12.1 -> 10.2 us, two (1,014)
+// 14.6 -> 13.6, four (2,028) 21.5 -> 20.5, one 1280x720 9.4 -> 8.4, one 640x360 9.4 -> 7.1, one 4096x4096 (4,096)
+// 33.6 = 33.9.  4:2:0: one 640x360 11.3 -> 7.8 us, one 1080p (255 workgroups) 12.2 -> 9.4, four (1,020) 17.3 -> 15.6,
+// eight (2,040) 28.0 -> 25.7, one 4096x4096 (2,048: BASELINE config 3) 27.5 -> 25.6, two (4,096) 44.6 -> 43.1.
+// 4:2:2 / 4:4:0 (all 64 lanes busy): one 1080p 11.2 -> 10.6 / 11.4 -> 9.6 us, one 4096x4096 25.0 -> 23.4 / 25.7 -> 26.3.
+constexpr int kSmallGridBelowPerCu = 8;
+
+// The pixel launch of every route -- the public device seams below and the staging ring's submissions -- in three
+// steps: argument validation, tile planning, the launch.  `plan` (jb_plan.h) says what the pixels look like: scale 1,
+// format 0 is exactly the launch jb_blocks_to_rgb_device has always made; scale 2, 4, 8 the row-bound tiling with the
+// area-reduced store stage; a planar format the row-bound tiling with the planar store stage; a rectangle (plan.has_roi)
+// the row-bound tiling over the MCUs it touches with the ROI store stage, in any format.  The batch's row / image
+// strides describe the output: the reduced image when scale > 1, one plane's rows with a planar format, images of the
+// rectangle's size with a rectangle (plan.out_w x plan.out_h in every case).
+
+// 1. validation: the batch against the plan; g: the frame's geometry; plane_stride: bytes between the planes (0: interleaved)
+int seam_check(jb_ctx *ctx, const jb_device_batch *b, const JbOutPlan &plan, const char *fn, jb_geometry *g, int64_t *plane_stride) {
+  if (!ctx) return fail(nullptr, JB_ERR_NULL, "%s: ctx is NULL", fn);
+  if (!b || !b->d_coef || !b->d_qtabs || !b->d_rgb) return fail(ctx, JB_ERR_NULL, "%s: NULL pointer", fn);
+  int rc = check_desc(ctx, &b->desc, g);
+  if (rc) return rc;
+  if (b->n_images < 1) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d", b->n_images);
+  if (plan.status != JB_OK) return fail(ctx, plan.status, "%s: %s", fn, plan.why);
+  *plane_stride = 0;
+  if (plan.planar) {
+    if (jb_output_spec_check(&plan.spec, plan.out_h, b->rgb_row_stride) != JB_OK)
+      return fail(ctx, JB_ERR_GEOMETRY, "%s: bad output spec (reserved, plane_stride < row stride * height, or scale / bias not finite)", fn);
+    *plane_stride = plan.spec.plane_stride ? plan.spec.plane_stride : b->rgb_row_stride * (int64_t)plan.out_h;
+  }
+  if (b->rgb_row_stride < plan.row_stride)
+    return fail(ctx, JB_ERR_GEOMETRY, "rgb_row_stride %lld < %s", (long long)b->rgb_row_stride, plan.planar ? "width * element size" : "3*width");
+  if (plan.planar) {
+    if (((uintptr_t)b->d_rgb | (uint64_t)b->rgb_row_stride | (uint64_t)*plane_stride | (uint64_t)(b->n_images > 1 ? b->rgb_image_stride : 0)) & (uint64_t)(plan.esize - 1))
+      return fail(ctx, JB_ERR_GEOMETRY, "%s: f32 / f16 output wants the pointer and every stride to be multiples of the element size", fn);
+    if (b->n_images > 1 && b->rgb_image_stride < 2 * *plane_stride + b->rgb_row_stride * (int64_t)plan.out_h)
+      return fail(ctx, JB_ERR_GEOMETRY, "image strides smaller than one image");
+  }
+  if (((uintptr_t)b->d_coef & 15) || (b->coef_image_stride & 15))
+    return fail(ctx, JB_ERR_GEOMETRY, "coefficient pointer and image stride must be multiples of 16 bytes");
+  if (((uintptr_t)b->d_qtabs & 3) || (b->qtab_image_stride & 3))
+    return fail(ctx, JB_ERR_GEOMETRY, "quant-table pointer and stride must be multiples of 4 bytes");
+  if (b->n_images > 1 && (b->coef_image_stride < g->coef_bytes || b->rgb_image_stride < b->rgb_row_stride * (int64_t)plan.out_h))
+    return fail(ctx, JB_ERR_GEOMETRY, "image strides smaller than one image");
+  return JB_OK;
+}
+
+// 2. tile planning: linear, row-bound or small-grid, and the store-stage knobs, into p (its pointers, strides and
+// frame fields are set)
+int seam_tiles(jb_ctx *ctx, const jb_device_batch *b, const jb_geometry &g, const JbOutPlan &plan, JbLaunch &p) {
+  const int per_tile = jbk_mcus_per_tile(b->desc.hs, b->desc.vs);
+  if (plan.has_roi) {
+    // only the MCUs the rectangle touches: the grid's origin is the MCU that holds its first pixel, one tile row per
+    // touched MCU row, row-bound tiles from the origin's column on (always the 192-lane kernel's ROI instantiation)
+    const int mw = 8 * b->desc.hs, mh = 8 * b->desc.vs;
+    const jb_roi &r = plan.roi;
+    p.roi = 1;
+    p.roi_x = r.x, p.roi_y = r.y, p.roi_w = r.width, p.roi_h = r.height;
+    p.roi_mx = r.x / mw, p.roi_my = r.y / mh;
+    const int roi_mcus_x = (r.x + r.width - 1) / mw - p.roi_mx + 1, roi_mcus_y = (r.y + r.height - 1) / mh - p.roi_my + 1;
+    p.tiles_per_row = (roi_mcus_x + per_tile - 1) / per_tile;
+    p.tiles_per_image = roi_mcus_y * p.tiles_per_row;  // (at most the whole image's: no overflow)
+    const int64_t n_tiles = (int64_t)b->n_images * p.tiles_per_image;
+    if (n_tiles > 0x7fffffffLL) return fail(ctx, JB_ERR_CAPACITY, "batch too large for one launch (%lld tiles)", (long long)n_tiles);
+    p.n_tiles = (int32_t)n_tiles;
+    p.fast_store = 1;  // (the ROI stage does not look at it)
+    return JB_OK;
+  }
+  p.tiles_per_row = (g.mcus_x + per_tile - 1) / per_tile;
+  // JPEGBLK_ROW_TILING=1 (debug / A-B knob) forces the row-bound tiling; the scaled and planar stages only exist in it
+  const bool force_row = ctx->knobs.row_tiling || plan.scale > 1 || plan.planar;
+  // linear tiling only where the row-bound one would leave ragged tiles
+  p.linear = (force_row || g.mcus_x % per_tile == 0) ? 0 : jbk_linear_ok(b->desc.hs, b->desc.vs, g.mcus_x);
+  const int64_t tiles_per_image = p.linear ? ((int64_t)g.mcus_x * g.mcus_y + per_tile - 1) / per_tile
+                                           : (int64_t)g.mcus_y * p.tiles_per_row;
+  if (tiles_per_image > 0x7fffffffLL) return fail(ctx, JB_ERR_CAPACITY, "image too large");
+  p.tiles_per_image = (int32_t)tiles_per_image;
+  const int64_t n_tiles = (int64_t)b->n_images * tiles_per_image;
+  if (n_tiles > 0x7fffffffLL) return fail(ctx, JB_ERR_CAPACITY, "batch too large for one launch (%lld tiles)", (long long)n_tiles);
+  p.n_tiles = (int32_t)n_tiles;
+  // Small launches (a single 1080p image is 507 / 255 workgroups on 256 CUs): four times as many one-wave
+  // workgroups (jb_kernels.hip jb_small_kernel_*), row-bound.  JPEGBLK_SMALL_GRID = 1 / 0 forces / forbids it; so does
+  // JPEGBLK_ROW_TILING=1 (that knob asks for the 192-lane kernel's row-bound instantiation).  (The scaled and planar
+  // stages have no small-grid variant.)
+  if (jbk_small_mcus(b->desc.hs, b->desc.vs) > 0 && !force_row && b->rgb_row_stride < (1LL << 26) &&  // (the lane's row offset is 32-bit)
+      (ctx->knobs.small_grid == 1 || (ctx->knobs.small_grid < 0 && n_tiles <= (int64_t)kSmallGridBelowPerCu * ctx->n_cus))) {
+    const int per = jbk_small_mcus(b->desc.hs, b->desc.vs);
+    p.tiles_per_row = (g.mcus_x + per - 1) / per;
+    const int64_t small_tiles = (int64_t)b->n_images * g.mcus_y * p.tiles_per_row;
+    if (small_tiles <= 0x7fffffffLL) {
+      p.linear = 0;
+      p.small_grid = 1;
+      p.tiles_per_image = (int32_t)((int64_t)g.mcus_y * p.tiles_per_row);
+      p.n_tiles = (int32_t)small_tiles;
+    } else {
+      p.tiles_per_row = (g.mcus_x + per_tile - 1) / per_tile;
+    }
+  }
+  // 12-byte stores at any byte address: gfx950 under ROCm runs with unaligned global/buffer access
+  // enabled, and odd widths with tightly packed rows (row stride 3*W) are the common case --
+  // measured 1.67x faster than byte stores on 679x451 (tests/test_gpu_parity.py covers both).
+  // JPEGBLK_BYTE_STORE=1 forces the byte-store path (test / A-B knob; the scaled stage ignores it).
+  p.fast_store = ctx->knobs.byte_store ? 0 : 1;
+  // (measurement builds of jb_kernels.hip only -- tools/build_variant.sh -DJB_LAB: the staged store stage of the linear
+  // tiling; the product's kernels ignore the field)
+  p.staged = (p.linear && p.fast_store && !p.small_grid && ctx->knobs.staged_store == 1) ? 1 : 0;
+  return JB_OK;
+}
+
+constexpr size_t kTmpSlack = 16;    // bytes behind the last intermediate (jb_resample_kernel reads pixels as 4-byte words)
+constexpr size_t kTmpStreams = 64;  // scratches a context keeps before it lets go of all of them
+
+// the scratch of `stream`, at least `bytes` large
+int tmp_for_stream(jb_ctx *ctx, hipStream_t stream, size_t bytes, void **out) {
+  std::lock_guard<std::mutex> lk(ctx->tmp_mu);
+  if (ctx->tmp.size() >= kTmpStreams && !ctx->tmp.count(stream)) {
+    // a caller that keeps coming with new streams: nothing of the old ones may be in flight when their scratch goes
+    JB_HIP(ctx, hipDeviceSynchronize());
+    for (auto &kv : ctx->tmp)
+      if (kv.second.d) (void)hipFree(kv.second.d);
+    ctx->tmp.clear();
+  }
+  jb_ctx::Tmp &t = ctx->tmp[stream];
+  if (t.cap < bytes) {
+    if (t.d) {
+      JB_HIP(ctx, hipStreamSynchronize(stream));  // the launches that still read the old one
+      (void)hipFree(t.d);
+      t.d = nullptr, t.cap = 0;
+    }
+    JB_HIP(ctx, hipMalloc(&t.d, bytes));
+    t.cap = bytes;
+  }
+  *out = t.d;
+  return JB_OK;
+}
+
+// 3b. a plan with a target size: two launches per sub-batch, in stream order -- the pixel kernel (full size or the
+// rectangle, interleaved uint8, tight) into the stream's scratch, jb_resample_kernel from there into the caller's buffer
+int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn) {
+  jb_geometry g;
+  int64_t plane_stride = 0;
+  int rc = seam_check(ctx, b, plan, fn, &g, &plane_stride);
+  if (rc) return rc;
+  const JbOutPlan inner = jb_out_plan_(&b->desc, 1, nullptr, plan.has_roi ? &plan.roi : nullptr);
+  if (inner.status != JB_OK) return fail(ctx, inner.status, "%s: %s", fn, inner.why);
+  // whole images per sub-batch: as many as the cap holds, one at the least
+  const int64_t cap = (int64_t)ctx->knobs.resize_tmp_bytes;
+  int64_t per = cap / plan.tmp_image_bytes;
+  if (per < 1) per = 1;
+  if (per > b->n_images) per = b->n_images;
+  if (((int64_t)(plan.out_w + 63) / 64) * ((plan.out_h + 3) / 4) * per > 0x7fffffffLL)
+    return fail(ctx, JB_ERR_CAPACITY, "batch too large for one launch");
+  DeviceGuard guard(ctx->device);
+  const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  void *tmp = nullptr;
+  rc = tmp_for_stream(ctx, s, (size_t)(per * plan.tmp_image_bytes) + kTmpSlack, &tmp);
+  if (rc) return rc;
+  // (the strides between images are checked, and meaningful, only when there is more than one)
+  const int64_t coef_step = b->n_images > 1 ? b->coef_image_stride : 0, rgb_step = b->n_images > 1 ? b->rgb_image_stride : 0;
+  for (int64_t i0 = 0; i0 < b->n_images; i0 += per) {
+    const int m = (int)(b->n_images - i0 < per ? b->n_images - i0 : per);
+    jb_device_batch ib = *b;
+    ib.n_images = m;
+    ib.d_coef = (const int16_t *)((const uint8_t *)b->d_coef + i0 * coef_step);
+    ib.coef_image_stride = coef_step;
+    ib.d_qtabs = (const int32_t *)((const uint8_t *)b->d_qtabs + i0 * b->qtab_image_stride);
+    ib.d_rgb = (uint8_t *)tmp;
+    ib.rgb_row_stride = inner.row_stride;
+    ib.rgb_image_stride = plan.tmp_image_bytes;
+    rc = seam_launch(ctx, &ib, s, inner, fn);
+    if (rc) return rc;
+    JbResample q;
+    memset(&q, 0, sizeof q);
+    q.src = (const uint8_t *)tmp;
+    q.src_image_stride = plan.tmp_image_bytes;
+    q.dst = b->d_rgb + i0 * rgb_step;
+    q.dst_image_stride = rgb_step;
+    q.dst_row_stride = b->rgb_row_stride;
+    q.dst_plane_stride = plane_stride;
+    q.iw = plan.src_w, q.ih = plan.src_h, q.ow = plan.out_w, q.oh = plan.out_h;
+    q.n_images = m;
+    for (int c = 0; c < 3; c++) q.scale[c] = plan.spec.scale[c], q.bias[c] = plan.spec.bias[c];
+    JB_HIP(ctx, jbk_resample_launch(q, plan.format, s));
+  }
+  return JB_OK;
+}
+
+
+}  // namespace
+
+// 3. the launch, on `stream` or (null) the context's primary stream; fn: the entry point's name, for the error text
+int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn) {
+  if (plan.has_resize && ctx && b) return seam_launch_resized(ctx, b, stream, plan, fn);
+  jb_geometry g;
+  int64_t plane_stride = 0;
+  int rc = seam_check(ctx, b, plan, fn, &g, &plane_stride);
+  if (rc) return rc;
+  JbLaunch p;
+  memset(&p, 0, sizeof p);
+  p.coef = b->d_coef;
+  p.qtabs = b->d_qtabs;
+  p.rgb = b->d_rgb;
+  p.coef_image_stride = b->coef_image_stride;
+  p.qtab_image_stride = b->qtab_image_stride;
+  p.rgb_image_stride = b->rgb_image_stride;
+  p.rgb_row_stride = b->rgb_row_stride;
+  p.width = b->desc.width;
+  p.height = b->desc.height;
+  p.mcus_x = g.mcus_x;
+  p.mcus_y = g.mcus_y;
+  p.chroma_q_equal = (b->desc.qtab_id[1] == b->desc.qtab_id[2]) ? 1 : 0;
+  if (plan.planar) {
+    p.format = plan.format;
+    p.rgb_plane_stride = plane_stride;
+    for (int c = 0; c < 3; c++) p.scale[c] = plan.spec.scale[c], p.bias[c] = plan.spec.bias[c];
+  }
+  rc = seam_tiles(ctx, b, g, plan, p);
+  if (rc) return rc;
+  DeviceGuard guard(ctx->device);
+  JB_HIP(ctx, jbk_launch(p, b->desc.hs, b->desc.vs, plan.scale, stream ? (hipStream_t)stream : ctx->stream));
+  return JB_OK;
+}
+
+extern "C" {
+
+const char *jb_kernel_name(const jb_image_desc *d) {
+  if (!d) return "";
+  return jbk_kernel_name(d->hs, d->vs);
+}
+
+int jb_blocks_to_rgb_device(jb_ctx *ctx, const jb_device_batch *b, void *stream) {
+  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, nullptr), "jb_blocks_to_rgb_device");
+}
+
+int jb_blocks_to_rgb_device_scaled(jb_ctx *ctx, const jb_device_batch *b, int denom, void *stream) {
+  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, denom, nullptr), "jb_blocks_to_rgb_device_scaled");
+}
+
+int jb_blocks_to_rgb_device_fmt(jb_ctx *ctx, const jb_device_batch *b, const jb_output_spec *spec, void *stream) {
+  if (ctx && !spec) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_fmt: spec is NULL");
+  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec), "jb_blocks_to_rgb_device_fmt");
+}
+
+int jb_blocks_to_rgb_device_roi(jb_ctx *ctx, const jb_device_batch *b, const jb_roi *roi, const jb_output_spec *spec, void *stream) {
+  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, roi), "jb_blocks_to_rgb_device_roi");
+}
+
+int jb_blocks_to_rgb_device_resized(jb_ctx *ctx, const jb_device_batch *b, const jb_roi *roi, int32_t out_w, int32_t out_h,
+                                    const jb_output_spec *spec, void *stream) {
+  const JbTarget t = {out_w, out_h};
+  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, roi, &t), "jb_blocks_to_rgb_device_resized");
+}
+
+}  // extern "C"

@@ -7,7 +7,8 @@
 //   make -C tools/fuzz && tools/fuzz/fuzz_frontend <CPU seconds> <seed> file.jpg [file.jpg ...]
 //
 // Seeds: the given files plus streams from the build's own writer (all layouts, restart
-// intervals, 16-bit tables).  The device side is stubbed; only the host code is under test.
+// intervals, 16-bit tables).  The device side is stubbed; only the host code is under test: the front end, the packer
+// of device-entropy submissions (csrc/jb_huff_pack.cpp) and the host helpers (csrc/jb_hostutil.cpp).
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -18,16 +19,13 @@
 #include <vector>
 
 #include "../../include/jpegblk.h"
-#include "../../jpeg_decoder_amd/csrc/jb_huff.h"
-#include "../../jpeg_decoder_amd/csrc/jb_knobs.h"
-#include "../../jpeg_decoder_amd/csrc/jb_plan.h"
+#include "../../jpeg_decoder_amd/csrc/jb_internal.h"
 
 extern "C" long jw_encode_ex(const int16_t *coef, int width, int height, int hs, int vs, const uint16_t *qtabs,
                              const int *qtab_id, const uint8_t *dht, int restart_interval, int dqt16, int scan_mode,
                              uint8_t *out, long cap);
 
-// ---- stubs for the parts of the library that need a device ----
-struct jb_ctx;
+// ---- stubs for the parts of the library that need a device (prototypes: jb_internal.h, include/jpegblk.h) ----
 static std::string g_err;
 int jb_fail_(jb_ctx *, int code, const char *msg) {
   g_err = msg ? msg : "";
@@ -38,6 +36,9 @@ const JbKnobs *jb_ctx_knobs_(const jb_ctx *) {
   static const JbKnobs k;
   return &k;
 }
+// the two routes of decode(bytes) into the pixel kernel
+int jb_decode_job_(jb_ctx *, const JbHuffJob *, uint8_t *, const JbOutPlan &) { return JB_OK; }
+int jb_blocks_to_rgb_plan_(jb_ctx *, const jb_image_desc *, const int16_t *, const uint16_t *, uint8_t *, const JbOutPlan &) { return JB_OK; }
 extern "C" {
 const char *jb_last_error(const jb_ctx *) { return g_err.c_str(); }
 void *jb_pinned_alloc(size_t n) { return malloc(n); }
@@ -45,10 +46,7 @@ void *jb_pinned_alloc_on(int, size_t n) { return malloc(n); }
 int jb_ctx_reserve(jb_ctx *, size_t, size_t) { return JB_OK; }
 int jb_ctx_device(const jb_ctx *) { return 0; }
 void jb_pinned_free(void *p) { free(p); }
-void jb_free(void *p) { free(p); }
-// the two routes of decode(bytes) into the pixel kernel
-int jb_decode_job_(jb_ctx *, const JbHuffJob *, uint8_t *, const JbOutPlan &) { return JB_OK; }
-int jb_blocks_to_rgb_plan_(jb_ctx *, const jb_image_desc *, const int16_t *, const uint16_t *, uint8_t *, const JbOutPlan &) { return JB_OK; }
+int jb_device_numa_node(int) { return JB_ERR_STATE; }
 }
 
 static uint64_t rng_state = 88172645463325252ull;
@@ -136,15 +134,27 @@ static void prepare_once(const std::vector<uint8_t> &in) {
              (uint64_t)im.n_int * im.ri < im.n_mcus || !(im.nb == 1 || im.nb == 3 || im.nb == 4 || im.nb == 6) ||
              (uint64_t)im.n_mcus * im.nb != im.n_blocks || im.n_blocks >= (1u << 24) || im.n_tabs < 2 || im.n_tabs > kJbMaxTabs ||
              im.n_tabs != job.n_tabs || !(im.chunk_bytes == 64 || im.chunk_bytes == 128) || !(im.blk_bytes == 128 || im.blk_bytes == 384);
-  uint64_t chunks = 0;
-  bool multi = false;
+  bool multi = false;  // an interval of more than one chunk: the image needs the synchronisation launches
   for (size_t i = 1; !bad && i < job.starts.size(); i++) {
     bad = job.starts[i] < job.starts[i - 1];
-    const uint32_t k = jb_chunks_of_(job.starts[i] - job.starts[i - 1], im.chunk_bytes);
-    chunks += k;
-    multi |= k > 1;
+    multi |= jb_chunks_of_(job.starts[i] - job.starts[i - 1], im.chunk_bytes) > 1;
   }
-  bad = bad || chunks != im.n_chunks || (multi ? 1u : 0u) != im.needs_sync;
+  bad = bad || (multi ? 1u : 0u) != im.needs_sync;
+  // the real packer (csrc/jb_huff_pack.cpp) on the job, into a heap buffer of exactly the size it asks for (ASan sees
+  // one byte too many): it re-derives the chunks of every interval and refuses a job whose count differs
+  if (!bad) {
+    const JbHuffJob *jobs[1] = {&job};
+    const size_t size = jb_huff_pack_size_(jobs, 1);
+    std::vector<uint8_t> blob(size);
+    JbHuffLayout lay;
+    const int rc = jb_huff_pack_(jobs, 1, job.geo.coef_bytes, blob.data(), &lay);
+    bad = rc != JB_OK || lay.total > size || lay.n_chunks != im.n_chunks || lay.n != 1 ||
+          lay.n_sync_wg != (im.needs_sync ? lay.n_wg : 0) ||
+          !(lay.off_img <= lay.off_wg && lay.off_wg <= lay.off_sync_wg && lay.off_sync_wg <= lay.off_tab && lay.off_tab <= lay.off_starts &&
+            lay.off_starts <= lay.off_chunks && lay.off_chunks <= lay.off_scan && lay.off_scan <= lay.total && lay.total <= lay.off_entry &&
+            lay.off_entry <= lay.off_exit && lay.off_exit <= lay.off_cps && lay.off_cps <= lay.off_chunk_dc && lay.off_chunk_dc <= lay.off_wgsum &&
+            lay.off_wgsum <= lay.device_total);
+  }
   // block-in-MCU -> table / component: indices the kernels use without a check
   for (uint32_t blk = 0; !bad && blk < im.nb; blk++)
     bad = ((im.lut_ac >> (4 * blk)) & 15u) >= im.n_tabs || ((im.lut_dc >> (4 * blk)) & 15u) >= im.n_tabs || ((im.lut_comp >> (4 * blk)) & 15u) > 2;

@@ -25,7 +25,7 @@ static thread_local std::vector<int> tl_pass_no;
 #define JBH_TRACE_PASS_END(pass) (tl_passes.push_back(tl_steps), tl_pass_no.push_back((int)(pass)), tl_steps = 0)
 
 #include "../../jpeg_decoder_amd/csrc/jb_huff.hip"
-#include "../../jpeg_decoder_amd/csrc/jb_knobs.h"
+#include "../../jpeg_decoder_amd/csrc/jb_internal.h"
 
 alignas(16) uint8_t lds[160 * 1024];
 // per launch (in order): lane-steps, and wave-steps = sum over the waves' passes of the longest lane (what a wave pays)
