@@ -80,45 +80,66 @@ class Roi(ctypes.Structure):
     _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
 
-def _as_roi(roi, scale=1):
-    """None / (x, y, w, h) / a Roi -> Roi or None (None = the entry points without a rectangle).  A rectangle together
+def _ref(struct):
+    """byref(struct), or None (a NULL pointer) for None."""
+    return ctypes.byref(struct) if struct is not None else None
+
+
+class _Request:
+    """The output request of one call, normalised in this one place.  (scale, fmt, roi, resize) as the caller gave them
+    (fmt: None / a format number / an OutputSpec; roi: None / (x, y, w, h) / a Roi; resize: None / (w, h)) become .scale,
+    .spec (OutputSpec or None), .roi (Roi or None) and .target ((w, h) or None).  A rectangle or a target size together
     with a scale other than 1 is JbError(-9), raised here: no C entry point takes the pair."""
-    if roi is None:
-        return None
-    if scale != 1:
-        raise JbError(-9, "a rectangle (roi) cannot be combined with a scale")
-    return roi if isinstance(roi, Roi) else Roi(*[int(v) for v in roi])
+
+    def __init__(self, scale=1, fmt=None, roi=None, resize=None):
+        self.scale = scale
+        self.spec = fmt if fmt is None or isinstance(fmt, OutputSpec) else OutputSpec.make(fmt)
+        if roi is not None and scale != 1:
+            raise JbError(-9, "a rectangle (roi) cannot be combined with a scale")
+        if resize is not None and scale != 1:
+            raise JbError(-9, "a target size (resize) cannot be combined with a scale")
+        self.roi = roi if roi is None or isinstance(roi, Roi) else Roi(*[int(v) for v in roi])
+        self.target = None
+        if resize is not None:
+            w, h = resize
+            self.target = int(w), int(h)
+
+    def routed(self):
+        """-> (route, the arguments the route's entry points take between their family's own and their outputs).  The
+        route names the variant of an entry point that takes this request (_ROUTES has the symbols).  A planar format
+        with a scale has none, JbError(-9); format 0 with a scale is the scaled route, which takes no spec."""
+        if self.target is not None:
+            return "resized", (_ref(self.roi), self.target[0], self.target[1], _ref(self.spec))
+        if self.roi is not None:
+            return "roi", (_ref(self.roi), _ref(self.spec))
+        if self.scale == 1:
+            return ("fmt", (_ref(self.spec),)) if self.spec is not None else ("plain", ())
+        if self.spec is not None and self.spec.format != FMT_RGB_U8_HWC:
+            raise JbError(-9, "an output format cannot be combined with a scale")
+        return "scaled", (self.scale,)
+
+
+# route -> its entry point in each family: decode(path), decode(bytes), the seam over device buffers.  The next output
+# option is one more row here and one more return in _Request.routed().
+_FILE, _MEMORY, _DEVICE = 0, 1, 2
+_ROUTES = {"plain": ("jb_decode_file", "jb_decode_memory", "jb_blocks_to_rgb_device"),
+           "scaled": ("jb_decode_file_scaled", "jb_decode_memory_scaled", "jb_blocks_to_rgb_device_scaled"),
+           "fmt": ("jb_decode_file_fmt", "jb_decode_memory_fmt", "jb_blocks_to_rgb_device_fmt"),
+           "roi": ("jb_decode_file_roi", "jb_decode_memory_roi", "jb_blocks_to_rgb_device_roi"),
+           "resized": ("jb_decode_file_resized", "jb_decode_memory_resized", "jb_blocks_to_rgb_device_resized")}
 
 
 def roi_check(desc, roi):
     """jb_roi_check: does the rectangle lie in the descriptor's image?  Raises JbError otherwise."""
-    _check(lib().jb_roi_check(ctypes.byref(desc), ctypes.byref(_as_roi(roi))))
-
-
-def _as_resize(resize, scale=1):
-    """None / (w, h) -> (w, h) or None (None = the entry points without a target size).  A target size together with a
-    scale other than 1 is JbError(-9), raised here: no C entry point takes the pair."""
-    if resize is None:
-        return None
-    if scale != 1:
-        raise JbError(-9, "a target size (resize) cannot be combined with a scale")
-    w, h = resize
-    return int(w), int(h)
+    _check(lib().jb_roi_check(ctypes.byref(desc), ctypes.byref(_Request(roi=roi).roi)))
 
 
 def resize_check(desc, resize, roi=None):
     """jb_resize_check: does the rectangle (None: the whole image) lie in the descriptor's image, and is the target
     size (w, h) in 1..65535?  Raises JbError otherwise."""
-    r = _as_roi(roi)
-    w, h = _as_resize(resize)
-    _check(lib().jb_resize_check(ctypes.byref(desc), ctypes.byref(r) if r is not None else None, w, h))
-
-
-def _as_spec(fmt):
-    """None / an int format / an OutputSpec -> OutputSpec or None (None = the entry points without a format)."""
-    if fmt is None or isinstance(fmt, OutputSpec):
-        return fmt
-    return OutputSpec.make(fmt)
+    q = _Request(roi=roi, resize=resize)
+    w, h = q.target
+    _check(lib().jb_resize_check(ctypes.byref(desc), _ref(q.roi), w, h))
 
 
 def _shape_output(ptr, w, h, spec):
@@ -421,107 +442,79 @@ class Context:
 
     # -- the seam, device buffers ------------------------------------------------------------
     def blocks_to_rgb_device(self, batch, stream=None, scale=1, fmt=None, roi=None, resize=None):
-        """scale 2, 4, 8 (jb_blocks_to_rgb_device_scaled): the batch's d_rgb and strides describe images of
-        scaled_size(desc.width, desc.height, scale).  fmt (an OutputSpec or a format number;
-        jb_blocks_to_rgb_device_fmt): planar output -- the batch's rgb_row_stride is then a plane's.
-        roi=(x, y, w, h) (jb_blocks_to_rgb_device_roi, with any fmt, not with a scale): the batch's d_rgb and strides
-        describe images of w x h, the rectangle of every image.
-        resize=(w, h) (jb_blocks_to_rgb_device_resized, with any fmt, with or without roi, not with a scale): the batch's
-        d_rgb and strides describe images of w x h, the exact area resize of every image (or of its rectangle)."""
-        spec = _as_spec(fmt)
-        r = _as_roi(roi, scale)
-        t = _as_resize(resize, scale)
-        if t is not None:
-            _check(lib().jb_blocks_to_rgb_device_resized(self._h, ctypes.byref(batch), ctypes.byref(r) if r is not None else None,
-                                                         t[0], t[1], ctypes.byref(spec) if spec is not None else None, stream), self._h)
-            return
-        if r is not None:
-            _check(lib().jb_blocks_to_rgb_device_roi(self._h, ctypes.byref(batch), ctypes.byref(r),
-                                                     ctypes.byref(spec) if spec is not None else None, stream), self._h)
-            return
-        if spec is not None:
-            if scale != 1 and spec.format != FMT_RGB_U8_HWC:
-                raise JbError(-9, "an output format cannot be combined with a scale")
-            if scale == 1:
-                _check(lib().jb_blocks_to_rgb_device_fmt(self._h, ctypes.byref(batch), ctypes.byref(spec), stream), self._h)
-                return
-        if scale == 1:
-            _check(lib().jb_blocks_to_rgb_device(self._h, ctypes.byref(batch), stream), self._h)
-        else:
-            _check(lib().jb_blocks_to_rgb_device_scaled(self._h, ctypes.byref(batch), scale, stream), self._h)
+        """scale 2, 4, 8: the batch's d_rgb and strides describe images of scaled_size(desc.width, desc.height, scale).
+        fmt (an OutputSpec or a format number): planar output -- the batch's rgb_row_stride is then a plane's.
+        roi=(x, y, w, h) (with any fmt, not with a scale): the batch's d_rgb and strides describe images of w x h, the
+        rectangle of every image.
+        resize=(w, h) (with any fmt, with or without roi, not with a scale): the batch's d_rgb and strides describe images
+        of w x h, the exact area resize of every image (or of its rectangle).
+        Each is the entry point of that suffix (_ROUTES)."""
+        route, tail = _Request(scale, fmt, roi, resize).routed()
+        _check(getattr(lib(), _ROUTES[route][_DEVICE])(self._h, ctypes.byref(batch), *tail, stream), self._h)
 
     # -- decode(path) -> RGB -----------------------------------------------------------------
-    def decode_file(self, path, scale=1, fmt=None, roi=None, resize=None):
-        """-> RGB [H, W, 3]; scale 2, 4, 8: the area-reduced image (jb_decode_file_scaled); fmt (OutputSpec or format
-        number, jb_decode_file_fmt): [3, H, W] in the format's type for the planar formats; roi=(x, y, w, h)
-        (jb_decode_file_roi, with any fmt, not with a scale): that rectangle of the image; resize=(w, h)
-        (jb_decode_file_resized, with any fmt, with or without roi, not with a scale): the image, or its rectangle, at w x h."""
+    def _decode(self, family, lead, request):
+        """One decode(bytes) call: the family's entry point of the request's route over (context, the family's leading
+        arguments, the route's, the three outputs) -> a copy of the image, its malloc'ed buffer released."""
+        route, tail = request.routed()
         p, w, h = ctypes.c_void_p(), ctypes.c_int32(), ctypes.c_int32()
-        spec = _as_spec(fmt)
-        r = _as_roi(roi, scale)
-        t = _as_resize(resize, scale)
-        if t is not None:
-            rc = lib().jb_decode_file_resized(self._h, os.fsencode(path), ctypes.byref(r) if r is not None else None, t[0], t[1],
-                                              ctypes.byref(spec) if spec is not None else None, ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
-            return self._take_output(rc, p, w, h, spec)
-        if r is not None:
-            rc = lib().jb_decode_file_roi(self._h, os.fsencode(path), ctypes.byref(r), ctypes.byref(spec) if spec is not None else None,
-                                          ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
-            return self._take_output(rc, p, w, h, spec)
-        if spec is not None and scale != 1 and spec.format != FMT_RGB_U8_HWC:
-            raise JbError(-9, "an output format cannot be combined with a scale")
-        if spec is not None and scale == 1:
-            rc = lib().jb_decode_file_fmt(self._h, os.fsencode(path), ctypes.byref(spec), ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
-        elif scale == 1:
-            rc = lib().jb_decode_file(self._h, os.fsencode(path), ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
-        else:
-            rc = lib().jb_decode_file_scaled(self._h, os.fsencode(path), scale, ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
-        _check(rc, self._h)
+        _check(getattr(lib(), _ROUTES[route][family])(self._h, *lead, *tail, ctypes.byref(p), ctypes.byref(w), ctypes.byref(h)), self._h)
         try:
-            arr = _shape_output(p, w.value, h.value, spec if scale == 1 else None).copy()
+            return _shape_output(p, w.value, h.value, request.spec if route != "scaled" else None).copy()
         finally:
             lib().jb_free(p)
-        return arr
 
-    def _take_output(self, rc, p, w, h, spec):
-        """The array of a decode_*_roi / decode_*_resized call, its malloc'ed buffer released."""
-        _check(rc, self._h)
-        try:
-            return _shape_output(p, w.value, h.value, spec).copy()
-        finally:
-            lib().jb_free(p)
+    def decode_file(self, path, scale=1, fmt=None, roi=None, resize=None):
+        """-> RGB [H, W, 3]; scale 2, 4, 8: the area-reduced image; fmt (OutputSpec or format number): [3, H, W] in the
+        format's type for the planar formats; roi=(x, y, w, h) (with any fmt, not with a scale): that rectangle of the
+        image; resize=(w, h) (with any fmt, with or without roi, not with a scale): the image, or its rectangle, at w x h.
+        Each is jb_decode_file's variant of that suffix (_ROUTES)."""
+        request = _Request(scale, fmt, roi, resize)
+        return self._decode(_FILE, (os.fsencode(path),), request)
 
     def decode_memory(self, jpeg_bytes, scale=1, fmt=None, roi=None, resize=None):
-        """jb_decode_memory: a JFIF byte string -> RGB [H, W, 3] (front end + device seam); scale 2, 4, 8: the
-        area-reduced image (jb_decode_memory_scaled); fmt, roi, resize: as decode_file (jb_decode_memory_fmt,
-        jb_decode_memory_roi, jb_decode_memory_resized)."""
+        """jb_decode_memory: a JFIF byte string -> RGB [H, W, 3] (front end + device seam); scale, fmt, roi, resize: as
+        decode_file."""
         buf = np.frombuffer(jpeg_bytes, dtype=np.uint8)
-        p, w, h = ctypes.c_void_p(), ctypes.c_int32(), ctypes.c_int32()
-        spec = _as_spec(fmt)
-        r = _as_roi(roi, scale)
-        t = _as_resize(resize, scale)
-        if t is not None:
-            rc = lib().jb_decode_memory_resized(self._h, _ptr(buf), buf.size, ctypes.byref(r) if r is not None else None, t[0], t[1],
-                                                ctypes.byref(spec) if spec is not None else None, ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
-            return self._take_output(rc, p, w, h, spec)
-        if r is not None:
-            rc = lib().jb_decode_memory_roi(self._h, _ptr(buf), buf.size, ctypes.byref(r), ctypes.byref(spec) if spec is not None else None,
-                                            ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
-            return self._take_output(rc, p, w, h, spec)
-        if spec is not None and scale != 1 and spec.format != FMT_RGB_U8_HWC:
-            raise JbError(-9, "an output format cannot be combined with a scale")
-        if spec is not None and scale == 1:
-            rc = lib().jb_decode_memory_fmt(self._h, _ptr(buf), buf.size, ctypes.byref(spec), ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
-        elif scale == 1:
-            rc = lib().jb_decode_memory(self._h, _ptr(buf), buf.size, ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
-        else:
-            rc = lib().jb_decode_memory_scaled(self._h, _ptr(buf), buf.size, scale, ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
-        _check(rc, self._h)
-        try:
-            arr = _shape_output(p, w.value, h.value, spec if scale == 1 else None).copy()
-        finally:
-            lib().jb_free(p)
-        return arr
+        return self._decode(_MEMORY, (_ptr(buf), buf.size), _Request(scale, fmt, roi, resize))
+
+
+def _batch_args(paths):
+    """The argument arrays of one batch call over `paths`, as the ticket of BatchDecoder.submit holds them."""
+    n = len(paths)
+    return {"n": n, "paths": (ctypes.c_char_p * n)(*[os.fsencode(p) for p in paths]), "rgb": (ctypes.c_void_p * n)(),
+            "w": (ctypes.c_int32 * n)(), "h": (ctypes.c_int32 * n)(), "st": (ctypes.c_int * n)(), "id": ctypes.c_int(-1)}
+
+
+def _batch_times(times, rc):
+    """The times dict of a batch call: its four times, its status and, when that is not 0, the library's error text."""
+    return {"wall_s": times[0], "entropy_s": times[1], "device_s": times[2], "read_s": times[3], "rc": rc,
+            "error": lib().jb_last_error(None).decode(errors="replace") if rc else ""}
+
+
+def _harvest(n, rgb, w, h, st, fmt, keep_pixels, on_image, arena, device_out):
+    """The results of a finished batch, without the times: (device pointers (int, 0 = failed), (width, height) per image,
+    statuses) with device output, else (arrays / (width, height) without keep_pixels / None = failed, statuses).  Host
+    images cost at most one view and one copy each; a malloc'ed one (no arena: arena images belong to the decoder) is
+    released here.  Afterwards rgb[] is all NULL: every pointer was released or handed out, none can be harvested twice."""
+    if device_out:
+        out = ([int(rgb[i] or 0) for i in range(n)], [(w[i], h[i]) for i in range(n)])
+    else:
+        imgs = []
+        for i in range(n):
+            if rgb[i]:
+                if on_image is not None or keep_pixels:
+                    view = _shape_output(rgb[i], w[i], h[i], fmt)
+                    if on_image is not None:
+                        on_image(i, view)
+                imgs.append(view.copy() if keep_pixels else (w[i], h[i]))
+                if not arena:
+                    lib().jb_free(rgb[i])
+            else:
+                imgs.append(None)
+        out = (imgs,)
+    ctypes.memset(rgb, 0, ctypes.sizeof(rgb))
+    return out + (list(st),)
 
 
 class BatchDecoder:
@@ -537,8 +530,7 @@ class BatchDecoder:
 
     def __init__(self, n_threads=8, device=0, max_coef_bytes=0, max_rgb_bytes=0, arena_bytes=0, devices=None, scale=1, fmt=None,
                  roi=None, resize=None):
-        _as_roi(roi, scale)   # (roi with a scale: JbError(-9) before anything is created)
-        _as_resize(resize, scale)   # (and resize with a scale)
+        _Request(scale, fmt, roi, resize)   # (roi or resize with a scale: JbError(-9) before anything is created)
         self._h = ctypes.c_void_p()
         if devices is not None:
             ids = (ctypes.c_int * len(devices))(*devices)
@@ -569,7 +561,7 @@ class BatchDecoder:
     def set_output_format(self, fmt):
         """jb_batch_decoder_set_output_format: the format of later runs and submissions (JbError -7 while a batch is
         in flight, -9 when the decoder's scale is not 1)."""
-        spec = _as_spec(fmt)
+        spec = _Request(fmt=fmt).spec
         _check(lib().jb_batch_decoder_set_output_format(self._h, ctypes.byref(spec)))
         self._fmt = spec
 
@@ -577,13 +569,12 @@ class BatchDecoder:
         """jb_batch_decoder_set_roi: one rectangle (x, y, w, h) for every image of later runs and submissions; None:
         whole images again (JbError -7 while a batch is in flight, -9 when the decoder's scale is not 1).  A file the
         rectangle does not fit in gets status -2 and the batch goes on."""
-        r = _as_roi(roi)
-        _check(lib().jb_batch_decoder_set_roi(self._h, ctypes.byref(r) if r is not None else None))
+        _check(lib().jb_batch_decoder_set_roi(self._h, _ref(_Request(roi=roi).roi)))
 
     def set_resize(self, resize):
         """jb_batch_decoder_set_resize: one output size (w, h) for every image of later runs and submissions; None or
         (0, 0): the images' own sizes again (JbError -7 while a batch is in flight, -9 when the decoder's scale is not 1)."""
-        w, h = _as_resize(resize) or (0, 0)
+        w, h = _Request(resize=resize).target or (0, 0)
         _check(lib().jb_batch_decoder_set_resize(self._h, w, h))
 
     def set_scale(self, scale):
@@ -595,9 +586,19 @@ class BatchDecoder:
     def device_entropy_images(self):
         return lib().jb_batch_decoder_device_entropy_images(self._h)
 
+    def _run(self, paths, keep_pixels, on_image):
+        a = _batch_args(paths)
+        times = (ctypes.c_double * 4)()
+        rc = lib().jb_batch_decoder_run(self._h, a["paths"], a["n"], a["rgb"], a["w"], a["h"], a["st"], times)
+        return self._results(a, _batch_times(times, rc), keep_pixels, on_image)
+
+    def _results(self, a, t, keep_pixels, on_image):
+        return _harvest(a["n"], a["rgb"], a["w"], a["h"], a["st"], self._fmt, keep_pixels, on_image, self._arena, self._device_out) + (t,)
+
     def run(self, paths, keep_pixels=True, on_image=None):
+        """-> what decode_batch returns, in the decoder's format."""
         assert not self._device_out, "device output is set: use run_to_device"
-        return decode_batch(paths, keep_pixels=keep_pixels, on_image=on_image, _decoder=self._h, _arena=self._arena, _fmt=self._fmt)
+        return self._run(paths, keep_pixels, on_image)
 
     def set_device_output(self, d_base, nbytes):
         """jb_batch_decoder_set_device_output: decoded images stay in the caller's DEVICE memory
@@ -617,18 +618,8 @@ class BatchDecoder:
 
     def run_to_device(self, paths):
         """After set_device_output: -> (device pointers (int, 0 = failed), (width, height) per image, statuses, times)."""
-        assert getattr(self, "_device_out", False), "call set_device_output first"
-        n = len(paths)
-        arr = (ctypes.c_char_p * n)(*[os.fsencode(p) for p in paths])
-        rgb = (ctypes.c_void_p * n)()
-        w = (ctypes.c_int32 * n)()
-        h = (ctypes.c_int32 * n)()
-        st = (ctypes.c_int * n)()
-        times = (ctypes.c_double * 4)()
-        rc = lib().jb_batch_decoder_run(self._h, arr, n, rgb, w, h, st, times)
-        t = {"wall_s": times[0], "entropy_s": times[1], "device_s": times[2], "read_s": times[3], "rc": rc,
-             "error": lib().jb_last_error(None).decode(errors="replace") if rc else ""}
-        return [int(rgb[i] or 0) for i in range(n)], [(w[i], h[i]) for i in range(n)], list(st), t
+        assert self._device_out, "call set_device_output first"
+        return self._run(paths, False, None)
 
     def run_to_tensor(self, paths, out):
         """Decode files of ONE size (or, with a rectangle set, of any size the rectangle fits in: out is then
@@ -677,10 +668,8 @@ class BatchDecoder:
     # -- batches in a stream (jb_batch_decoder_submit / _collect): two in flight -----------------
     def submit(self, paths):
         """-> a ticket (keeps the batch's arrays alive); the batch runs while the caller prepares the next one."""
-        n = len(paths)
-        t = {"n": n, "paths": (ctypes.c_char_p * n)(*[os.fsencode(p) for p in paths]), "rgb": (ctypes.c_void_p * n)(),
-             "w": (ctypes.c_int32 * n)(), "h": (ctypes.c_int32 * n)(), "st": (ctypes.c_int * n)(), "id": ctypes.c_int(-1)}
-        _check(lib().jb_batch_decoder_submit(self._h, t["paths"], n, t["rgb"], t["w"], t["h"], t["st"], ctypes.byref(t["id"])))
+        t = _batch_args(paths)
+        _check(lib().jb_batch_decoder_submit(self._h, t["paths"], t["n"], t["rgb"], t["w"], t["h"], t["st"], ctypes.byref(t["id"])))
         # the library writes into these arrays until the batch is collected (or the decoder destroyed): the decoder
         # object holds them as well, so a ticket the caller drops cannot free them under a running batch
         self._flights[t["id"].value] = t
@@ -688,29 +677,15 @@ class BatchDecoder:
 
     def collect(self, ticket, keep_pixels=True, on_image=None):
         """-> what run() returns (host output: arrays / None; with an arena the pixels are views' copies), or, with
-        device output set, what run_to_device() returns."""
+        device output set, what run_to_device() returns.  A ticket that is not in flight (collected before, or unknown)
+        gives rc -7 in the times and no image: its pointers are stale, none is read or released."""
         times = (ctypes.c_double * 4)()
         rc = lib().jb_batch_decoder_collect(self._h, ticket["id"], times)
-        if rc != -7:   # (JB_ERR_STATE: no such batch -- nothing was collected)
+        if rc == -7:   # (JB_ERR_STATE: no such batch -- nothing was collected)
+            ticket = dict(ticket, rgb=(ctypes.c_void_p * ticket["n"])())
+        else:
             self._flights.pop(ticket["id"].value, None)
-        n, rgb, w, h, st = ticket["n"], ticket["rgb"], ticket["w"], ticket["h"], ticket["st"]
-        t = {"wall_s": times[0], "entropy_s": times[1], "device_s": times[2], "read_s": times[3], "rc": rc,
-             "error": lib().jb_last_error(None).decode(errors="replace") if rc else ""}
-        if self._device_out:
-            return [int(rgb[i] or 0) for i in range(n)], [(w[i], h[i]) for i in range(n)], list(st), t
-        out = []
-        for i in range(n):
-            if rgb[i]:
-                if on_image is not None or keep_pixels:
-                    view = _shape_output(rgb[i], w[i], h[i], self._fmt)
-                    if on_image is not None:
-                        on_image(i, view)
-                out.append(view.copy() if keep_pixels else (w[i], h[i]))
-                if not self._arena:
-                    lib().jb_free(rgb[i])
-            else:
-                out.append(None)
-        return out, list(st), t
+        return self._results(ticket, _batch_times(times, rc), keep_pixels, on_image)
 
     def close(self):
         if self._h:
@@ -725,43 +700,20 @@ class BatchDecoder:
         self.close()
 
 
-def decode_batch(paths, n_threads=8, device=0, keep_pixels=True, on_image=None, _decoder=None, _arena=False, scale=1, _fmt=None):
+def decode_batch(paths, n_threads=8, device=0, keep_pixels=True, on_image=None, scale=1):
     """jb_decode_batch: -> (list of uint8 [H,W,3] arrays or None, statuses, times dict).
     on_image(i, view): called with a no-copy [H,W,3] view of every decoded image before its buffer
     is released (checks over batches too large to keep).  scale 2, 4, 8: through a temporary
     BatchDecoder with set_scale(scale)."""
-    if scale != 1 and _decoder is None:
+    if scale != 1:
         if n_threads > len(paths) > 0:
             n_threads = len(paths)
         with BatchDecoder(n_threads=n_threads, device=device, scale=scale) as d:
             return d.run(paths, keep_pixels=keep_pixels, on_image=on_image)
-    n = len(paths)
-    arr = (ctypes.c_char_p * n)(*[os.fsencode(p) for p in paths])
-    rgb = (ctypes.c_void_p * n)()
-    w = (ctypes.c_int32 * n)()
-    h = (ctypes.c_int32 * n)()
-    st = (ctypes.c_int * n)()
+    a = _batch_args(paths)
     times = (ctypes.c_double * 4)()
-    if _decoder is not None:
-        rc = lib().jb_batch_decoder_run(_decoder, arr, n, rgb, w, h, st, times)
-    else:
-        rc = lib().jb_decode_batch(device, arr, n, n_threads, rgb, w, h, st, times)
-    out = []
-    for i in range(n):
-        if rgb[i]:
-            if on_image is not None:
-                on_image(i, _shape_output(rgb[i], w[i], h[i], _fmt))
-            if keep_pixels:
-                out.append(_shape_output(rgb[i], w[i], h[i], _fmt).copy())
-            else:
-                out.append((w[i], h[i]))
-            if not _arena:  # arena images belong to the decoder
-                lib().jb_free(rgb[i])
-        else:
-            out.append(None)
-    t = {"wall_s": times[0], "entropy_s": times[1], "device_s": times[2], "read_s": times[3], "rc": rc,
-         "error": lib().jb_last_error(None).decode(errors="replace") if rc else ""}
-    return out, list(st), t
+    rc = lib().jb_decode_batch(device, a["paths"], a["n"], n_threads, a["rgb"], a["w"], a["h"], a["st"], times)
+    return _harvest(a["n"], a["rgb"], a["w"], a["h"], a["st"], None, keep_pixels, on_image, False, False) + (_batch_times(times, rc),)
 
 
 def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, shared_qtabs=True, scale=1, fmt=None, roi=None,
@@ -777,31 +729,21 @@ def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, sha
     the rectangle's size, w x h, instead of desc's.
     resize=(w, h) (for Context.blocks_to_rgb_device(..., resize=), with any fmt and roi, not with a scale): rgb_t holds
     images of w x h."""
-    spec = _as_spec(fmt)
-    r = _as_roi(roi, scale)
-    t = _as_resize(resize, scale)
-    out_w, out_h = t if t is not None else (r.width, r.height) if r is not None else (desc.width, desc.height)
-    if spec is not None and spec.format != FMT_RGB_U8_HWC:
+    q = _Request(scale, fmt, roi, resize)
+    out_w, out_h = q.target if q.target is not None else (q.roi.width, q.roi.height) if q.roi is not None else (desc.width, desc.height)
+    if q.spec is not None and q.spec.format != FMT_RGB_U8_HWC:
         assert scale == 1, "an output format cannot be combined with a scale"
         es = rgb_t.element_size()
         assert rgb_t.dim() == 4 and rgb_t.shape[1] == 3 and rgb_t.shape[2] >= out_h and rgb_t.shape[3] >= out_w and rgb_t.stride(3) == 1
-        b = DeviceBatch()
-        b.desc = desc
-        b.n_images = n_images
-        b.d_coef = coef_t.data_ptr()
-        b.coef_image_stride = coef_t.stride(0) * 2 if n_images > 1 else coef_t.numel() * 2
-        b.d_qtabs = qtabs_t.data_ptr()
-        b.qtab_image_stride = 0 if shared_qtabs else 768
-        b.d_rgb = rgb_t.data_ptr()
-        b.rgb_row_stride = rgb_row_stride or rgb_t.stride(2) * es
-        b.rgb_image_stride = rgb_t.stride(0) * es
+        row_stride, image_stride = rgb_row_stride or rgb_t.stride(2) * es, rgb_t.stride(0) * es
         if isinstance(fmt, OutputSpec):
             fmt.plane_stride = rgb_t.stride(1) * es
-        return b
-    if scale != 1 or r is not None or t is not None:
-        if r is None and t is None:
-            out_w, out_h = scaled_size(desc.width, desc.height, scale)
-        assert rgb_t.shape[1] >= out_h and (rgb_row_stride or rgb_t.stride(1)) >= 3 * out_w, "rgb_t is smaller than the scaled images"
+    else:
+        if scale != 1 or q.roi is not None or q.target is not None:
+            if q.roi is None and q.target is None:
+                out_w, out_h = scaled_size(desc.width, desc.height, scale)
+            assert rgb_t.shape[1] >= out_h and (rgb_row_stride or rgb_t.stride(1)) >= 3 * out_w, "rgb_t is smaller than the scaled images"
+        row_stride, image_stride = rgb_row_stride or rgb_t.stride(1), rgb_t.stride(0)
     b = DeviceBatch()
     b.desc = desc
     b.n_images = n_images
@@ -810,6 +752,6 @@ def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, sha
     b.d_qtabs = qtabs_t.data_ptr()
     b.qtab_image_stride = 0 if shared_qtabs else 768
     b.d_rgb = rgb_t.data_ptr()
-    b.rgb_row_stride = rgb_row_stride or rgb_t.stride(1)
-    b.rgb_image_stride = rgb_t.stride(0)
+    b.rgb_row_stride = row_stride
+    b.rgb_image_stride = image_stride
     return b

@@ -9,13 +9,11 @@ import pytest
 
 import format_ref as fr
 from conftest import BASELINE_IMAGES, GOLD, load_golden
-from test_gpu_scaled import LAYOUTS, SEAM_SIZES, _oracle_full
+from seam_harness import LAYOUTS, SEAM_SIZES, Seam, _oracle_full
 
 pytestmark = pytest.mark.gpu
 
-SENT = 0xA5
 NEW_FORMATS = (fr.FMT_RGB_U8_CHW, fr.FMT_RGB_F32_CHW, fr.FMT_RGB_F16_CHW)
-DT = {0: np.uint8, 1: np.uint8, 2: np.float32, 3: np.float16}
 SETS = list(fr.PARAM_SETS.items())
 PROGRESSIVE = os.path.join(GOLD, "images", "prograssive-sample-2.jpg")
 
@@ -34,48 +32,6 @@ def ctx(jb):
     c.close()
 
 
-def _seam_fmt(jb, ctx, w, h, hs, vs, coefs, qs, fmt, scale, bias, qtab_id=(0, 1, 1), pad_row=0, pad_plane=0, pad_img=0):
-    """n images through jb_blocks_to_rgb_device_fmt into a sentinel-filled buffer with padded row, plane and image strides
-    (pads in elements) and, for uint8, an odd leading offset; -> list of [3, h, w] outputs, after checking that every byte
-    outside the planes still holds the sentinel."""
-    import torch
-    n = len(coefs)
-    es = np.dtype(DT[fmt]).itemsize
-    desc = jb.make_desc(w, h, hs, vs, qtab_id)
-    row = (w + pad_row) * es
-    plane = row * h + pad_plane * es
-    img_stride = 3 * plane + pad_img * es
-    coef_t = torch.from_numpy(np.stack(coefs)).to("cuda:0")
-    q_t = torch.from_numpy(np.stack([jb.resolve_qtabs(desc, q) for q in qs])).to("cuda:0")
-    lead = 256 + 5 if es == 1 else 256 + 3 * es   # uint8: the output starts at an odd address
-    buf = torch.full((lead + n * img_stride + 256,), SENT, dtype=torch.uint8, device="cuda:0")
-    assert buf.data_ptr() % 256 == 0
-    b = jb.DeviceBatch()
-    b.desc = desc
-    b.n_images = n
-    b.d_coef = coef_t.data_ptr()
-    b.coef_image_stride = coef_t.stride(0) * 2
-    b.d_qtabs = q_t.data_ptr()
-    b.qtab_image_stride = 768
-    b.d_rgb = buf.data_ptr() + lead
-    b.rgb_row_stride = row
-    b.rgb_image_stride = img_stride
-    spec = jb.OutputSpec.make(fmt, scale, bias, plane_stride=plane if (pad_plane or pad_row) else 0)
-    torch.cuda.synchronize()
-    ctx.blocks_to_rgb_device(b, fmt=spec)
-    ctx.synchronize()
-    host = buf.cpu().numpy()
-    mask = np.ones(host.size, bool)
-    outs = []
-    for i in range(n):
-        base = lead + i * img_stride
-        idx = (base + np.arange(3)[:, None, None] * plane + np.arange(h)[None, :, None] * row + np.arange(w * es)[None, None, :])
-        outs.append(np.ascontiguousarray(host[idx]).view(DT[fmt]).reshape(3, h, w))
-        mask[idx.ravel()] = False
-    assert (host[mask] == SENT).all(), "bytes outside the planes were written"
-    return outs
-
-
 @pytest.mark.parametrize("hs,vs", LAYOUTS)
 @pytest.mark.parametrize("w,h", SEAM_SIZES)
 def test_seam_formats_equal_format_ref_of_oracle(jb, ctx, oracle, hs, vs, w, h):
@@ -83,12 +39,11 @@ def test_seam_formats_equal_format_ref_of_oracle(jb, ctx, oracle, hs, vs, w, h):
     coef, q = synth.synth_blocks(w, h, hs, vs, image_index=w + h)
     full = _oracle_full(oracle, w, h, hs, vs, coef, q)
     big = w * h > 4 << 20
+    # padded rows / planes on everything but the largest size (tight: the spec's plane stride is 0, the seam derives it)
+    s = Seam(jb, w, h, hs, vs, [coef], [q], **(dict(pad_row=0, pad_plane=0) if big else dict(pad_row=3, pad_plane=5)))
     for fmt in NEW_FORMATS:
-        # padded rows / planes on everything but the largest size (whose sentinel check is the tight one)
-        pads = dict(pad_row=0, pad_plane=0) if big else dict(pad_row=3, pad_plane=5)
         name, (scale, bias) = SETS[(w + h + fmt) % 3]
-        (got,) = _seam_fmt(jb, ctx, w, h, hs, vs, [coef], [q], fmt, scale, bias, **pads)
-        assert fr.same_bits(got, fr.to_format(full, fmt, scale, bias)), (w, h, hs, vs, fmt, name)
+        s.check(ctx, [fr.to_format(full, fmt, scale, bias)], fmt, (scale, bias), tag=(w, h, hs, vs, name))
 
 
 @pytest.mark.parametrize("hs,vs", LAYOUTS)
@@ -111,10 +66,9 @@ def test_seam_formats_batch_strides_dense_mixed_tables_and_parameter_sets(jb, ct
     assert np.unique(np.concatenate([f.ravel() for f in fulls])).size == 256
     cases = [(fr.FMT_RGB_U8_CHW, "none", ((1, 1, 1), (0, 0, 0)))]
     cases += [(fmt, name, sb) for fmt in (fr.FMT_RGB_F32_CHW, fr.FMT_RGB_F16_CHW) for name, sb in SETS]
+    s = Seam(jb, w, h, hs, vs, coefs, qs, qid, pad_row=13, pad_plane=7, pad_img=77)
     for fmt, name, (scale, bias) in cases:
-        outs = _seam_fmt(jb, ctx, w, h, hs, vs, coefs, qs, fmt, scale, bias, qid, pad_row=13, pad_plane=7, pad_img=77)
-        for i, (got, full) in enumerate(zip(outs, fulls)):
-            assert fr.same_bits(got, fr.to_format(full, fmt, scale, bias)), (hs, vs, fmt, name, i)
+        s.check(ctx, [fr.to_format(full, fmt, scale, bias) for full in fulls], fmt, (scale, bias), tag=(hs, vs, name))
 
 
 def _device_batch(jb, w, h, hs, vs, es=1):

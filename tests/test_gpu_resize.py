@@ -12,12 +12,10 @@ import format_ref as fr
 from area_reduce import area_reduce
 from conftest import GOLD, load_golden
 from resize_ref import area_resize, area_sums
-from test_gpu_scaled import LAYOUTS, _oracle_full, _seam as scaled_seam
+from seam_harness import LAYOUTS, Seam, _oracle_full
 
 pytestmark = pytest.mark.gpu
 
-SENT = 0xA5
-DT = {0: np.uint8, 1: np.uint8, 2: np.float32, 3: np.float16}
 SETS = list(fr.PARAM_SETS.items())
 
 
@@ -39,70 +37,21 @@ def _params(i, fmt):
     return SETS[(i + fmt) % 3][1] if fmt >= 2 else ((1, 1, 1), (0, 0, 0))
 
 
-class Seam:
-    """n images of one geometry on the device (uploaded once).  run() launches into a fresh sentinel-filled buffer with
-    padded row, plane and image strides (pads in elements) and, for uint8, an odd leading offset."""
+def _seam(jb, w, h, hs, vs, coefs, qs, qtab_id=(0, 1, 1), pad_row=3, pad_plane=5, pad_img=7):
+    return Seam(jb, w, h, hs, vs, coefs, qs, qtab_id, pad_row=pad_row, pad_plane=pad_plane, pad_img=pad_img)
 
-    def __init__(self, jb, w, h, hs, vs, coefs, qs, qtab_id=(0, 1, 1), pad_row=3, pad_plane=5, pad_img=7):
-        import torch
-        self.jb, self.n = jb, len(coefs)
-        self.desc = jb.make_desc(w, h, hs, vs, qtab_id)
-        self.pads = (pad_row, pad_plane, pad_img)
-        self.coef_t = torch.from_numpy(np.stack(coefs)).to("cuda:0")
-        self.q_t = torch.from_numpy(np.stack([jb.resolve_qtabs(self.desc, q) for q in qs])).to("cuda:0")
 
-    def run(self, ctx, fmt, size, scale=(1, 1, 1), bias=(0, 0, 0), roi=None, resize=None):
-        """One launch whose output is `size` = (w, h) -> (the whole buffer as host bytes, the index array [n, ...] of the
-        output's bytes in it)."""
-        import torch
-        jb = self.jb
-        pad_row, pad_plane, pad_img = self.pads
-        w, h = size
-        es = np.dtype(DT[fmt]).itemsize
-        b = jb.DeviceBatch()
-        b.desc, b.n_images = self.desc, self.n
-        b.d_coef, b.coef_image_stride = self.coef_t.data_ptr(), self.coef_t.stride(0) * 2
-        b.d_qtabs, b.qtab_image_stride = self.q_t.data_ptr(), 768
-        lead = 256 + 5 if es == 1 else 256 + 3 * es   # uint8: the output starts at an odd address
-        if fmt == 0:
-            row = 3 * w + pad_row
-            img = row * h + pad_img
-            spec = None
-            idx = lead + np.arange(self.n)[:, None, None] * img + np.arange(h)[None, :, None] * row + np.arange(3 * w)[None, None, :]
-        else:
-            row = (w + pad_row) * es
-            plane = row * h + pad_plane * es
-            img = 3 * plane + pad_img * es
-            spec = jb.OutputSpec.make(fmt, scale, bias, plane_stride=plane)
-            idx = (lead + np.arange(self.n)[:, None, None, None] * img + np.arange(3)[None, :, None, None] * plane +
-                   np.arange(h)[None, None, :, None] * row + np.arange(w * es)[None, None, None, :])
-        buf = torch.full((lead + self.n * img + 256,), SENT, dtype=torch.uint8, device="cuda:0")
-        b.d_rgb, b.rgb_row_stride, b.rgb_image_stride = buf.data_ptr() + lead, row, img
-        torch.cuda.synchronize()
-        ctx.blocks_to_rgb_device(b, fmt=spec, roi=roi, resize=resize)
-        ctx.synchronize()
-        return buf.cpu().numpy(), idx
-
-    def check(self, ctx, srcs, resize, fmt, scale=(1, 1, 1), bias=(0, 0, 0), roi=None, tag=None):
-        """The launch with `resize` (and `roi`): every image's output equals the reference of its source pixels `srcs[i]`
-        (the full-size image, or its rectangle), and every other byte of the buffer still holds the sentinel."""
-        host, idx = self.run(ctx, fmt, resize, scale, bias, roi=roi, resize=resize)
-        want = np.full(host.size, SENT, np.uint8)
-        for i, src in enumerate(srcs):
-            ref = fr.to_format(area_resize(src, *resize), fmt, scale, bias)
-            want[idx[i]] = fr.bits(ref).view(np.uint8).reshape(idx[i].shape)
-        if not np.array_equal(host, want):
-            bad = np.flatnonzero(host != want)
-            inside = np.isin(bad, idx.ravel())
-            raise AssertionError(f"{tag} {resize} roi {roi} fmt {fmt}: {bad.size} bytes differ, {int((~inside).sum())} of them "
-                                 f"outside the output; first at buffer byte {bad[0]}")
-        return host, idx
+def _check(s, ctx, srcs, resize, fmt, scale=(1, 1, 1), bias=(0, 0, 0), roi=None, tag=None):
+    """The launch with `resize` (and `roi`): every image's output equals the reference of its source pixels `srcs[i]` (the
+    full-size image, or its rectangle), and every other byte of the buffer still holds the sentinel."""
+    wants = [fr.to_format(area_resize(src, *resize), fmt, scale, bias) for src in srcs]
+    return s.check(ctx, wants, fmt, (scale, bias), roi=roi, resize=resize, tag=tag)
 
 
 def _one(jb, oracle, w, h, hs, vs, seed=None):
     from jpeg_decoder_amd import synth
     coef, q = synth.synth_blocks(w, h, hs, vs, image_index=(w + h) if seed is None else seed)
-    return Seam(jb, w, h, hs, vs, [coef], [q]), _oracle_full(oracle, w, h, hs, vs, coef, q), coef, q
+    return _seam(jb, w, h, hs, vs, [coef], [q]), _oracle_full(oracle, w, h, hs, vs, coef, q), coef, q
 
 
 @pytest.mark.parametrize("hs,vs", LAYOUTS)
@@ -110,8 +59,8 @@ def test_seam_identity_is_the_plain_decode(jb, ctx, oracle, hs, vs):
     s, full, _, _ = _one(jb, oracle, 16, 16, hs, vs)
     for fmt in (0, 1, 2, 3):
         scale, bias = _params(0, fmt)
-        host, _ = s.check(ctx, [full], (16, 16), fmt, scale, bias, tag=(hs, vs))
-        old, _ = s.run(ctx, fmt, (16, 16), scale, bias)       # the entry point without a target: the same bytes
+        host, _ = _check(s, ctx, [full], (16, 16), fmt, scale, bias, tag=(hs, vs))
+        old, _ = s.run(ctx, fmt, (16, 16), (scale, bias))     # the entry point without a target: the same bytes
         assert np.array_equal(host, old), (hs, vs, fmt)
 
 
@@ -121,13 +70,13 @@ def test_seam_divisible_sizes_equal_the_scaled_output(jb, ctx, oracle, hs, vs):
     w, h = 64, 48
     coef, q = synth.synth_blocks(w, h, hs, vs, image_index=w + h)
     full = _oracle_full(oracle, w, h, hs, vs, coef, q)
-    s = Seam(jb, w, h, hs, vs, [coef], [q])
+    s = _seam(jb, w, h, hs, vs, [coef], [q])
+    tight = Seam(jb, w, h, hs, vs, [coef], [q])
     for k in (2, 4, 8):
-        host, idx = s.check(ctx, [full], (w // k, h // k), 0, tag=(hs, vs))
-        (scaled,) = scaled_seam(jb, ctx, w, h, hs, vs, [coef], [q], k)      # the existing scale=k launch, bit for bit
-        assert np.array_equal(host[idx[0]].reshape(h // k, w // k, 3), scaled), (hs, vs, k)
-        assert np.array_equal(scaled, area_reduce(full, k))
-        s.check(ctx, [full], (w // k, h // k), 1 + k % 3, *_params(k, 1 + k % 3), tag=(hs, vs))
+        host, idx = _check(s, ctx, [full], (w // k, h // k), 0, tag=(hs, vs))
+        got, at = tight.check(ctx, [area_reduce(full, k)], 0, scale=k, tag=(hs, vs))   # the existing scale=k launch, bit for bit
+        assert np.array_equal(host[idx[0]], got[at[0]]), (hs, vs, k)
+        _check(s, ctx, [full], (w // k, h // k), 1 + k % 3, *_params(k, 1 + k % 3), tag=(hs, vs))
 
 
 @pytest.mark.parametrize("fmt", [0, 1, 2, 3])
@@ -135,7 +84,7 @@ def test_seam_divisible_sizes_equal_the_scaled_output(jb, ctx, oracle, hs, vs):
 def test_seam_non_integer_ratio_every_layout_every_format(jb, ctx, oracle, hs, vs, fmt):
     """679 x 451 -> 224 x 224: non-integer ratios on both axes, ragged edge MCUs."""
     s, full, _, _ = _one(jb, oracle, 679, 451, hs, vs)
-    s.check(ctx, [full], (224, 224), fmt, *_params(hs + vs, fmt), tag=(hs, vs))
+    _check(s, ctx, [full], (224, 224), fmt, *_params(hs + vs, fmt), tag=(hs, vs))
 
 
 # (source size, targets): tiny with D not a power of two and one output pixel = the image mean; enlargement; enlargement
@@ -150,11 +99,11 @@ def test_seam_small_enlarging_and_mixed_cases(jb, ctx, oracle, hs, vs):
         s, full, _, _ = _one(jb, oracle, w, h, hs, vs)
         for t in targets:
             for fmt in (0, 1 + k % 3):     # format 0 everywhere; the planar ones in turn
-                s.check(ctx, [full], t, fmt, *_params(k, 1 + k % 3), tag=(hs, vs, w, h))
+                _check(s, ctx, [full], t, fmt, *_params(k, 1 + k % 3), tag=(hs, vs, w, h))
                 k += 1
     # one output pixel is the image mean, rounded half up
     s, full, _, _ = _one(jb, oracle, 33, 17, hs, vs)
-    host, idx = s.check(ctx, [full], (1, 1), 0, tag=(hs, vs))
+    host, idx = _check(s, ctx, [full], (1, 1), 0, tag=(hs, vs))
     tot = full.astype(np.int64).sum(axis=(0, 1))
     assert np.array_equal(host[idx[0]].ravel(), (tot + (33 * 17) // 2) // (33 * 17))
 
@@ -165,7 +114,7 @@ def test_seam_rectangle_then_resize(jb, ctx, oracle, hs, vs):
     s, full, _, _ = _one(jb, oracle, 100, 80, hs, vs)
     x, y, w, h = roi = (5, 3, 50, 40)
     for fmt in (0, 1, 2, 3):
-        s.check(ctx, [full[y:y + h, x:x + w]], (13, 11), fmt, *_params(hs, fmt), roi=roi, tag=(hs, vs))
+        _check(s, ctx, [full[y:y + h, x:x + w]], (13, 11), fmt, *_params(hs, fmt), roi=roi, tag=(hs, vs))
 
 
 def test_seam_sums_beyond_32_bits(jb, ctx, oracle):
@@ -182,17 +131,17 @@ def test_seam_sums_beyond_32_bits(jb, ctx, oracle):
     coef[:, 0] = np.where(blk < 4, rng.integers(52, 61, n), rng.integers(-1, 2, n))
     coef[:, 1] = np.where(blk < 4, rng.integers(-2, 3, n), 0)
     full = _oracle_full(oracle, w, h, 2, 2, coef, q)
-    s = Seam(jb, w, h, 2, 2, [coef], [q])
+    s = _seam(jb, w, h, 2, 2, [coef], [q])
     for t in ((1, 1), (2, 3)):
         assert area_sums(full, *t).max() > 2 ** 32
-        s.check(ctx, [full], t, 0)
-    s.check(ctx, [full], (2, 3), 3, *fr.IMAGENET)
+        _check(s, ctx, [full], t, 0)
+    _check(s, ctx, [full], (2, 3), 3, *fr.IMAGENET)
 
 
 def test_seam_refusals(jb, ctx):
     from jpeg_decoder_amd import synth
     coef, q = synth.synth_blocks(64, 48, 1, 1)
-    s = Seam(jb, 64, 48, 1, 1, [coef], [q])
+    s = _seam(jb, 64, 48, 1, 1, [coef], [q])
     for bad in ((0, 8), (8, 0), (65536, 8), (-1, 8)):
         with pytest.raises(jb.JbError) as e:
             s.run(ctx, 0, (8, 8), resize=bad)
@@ -220,7 +169,7 @@ def _batch5(jb, oracle, hs=2, vs=2):
         c = synth.synth_blocks(BW, BH, hs, vs, image_index=20 + i, qtabs=q, qtab_id=qid, dense=(i == 4))[0]
         coefs.append(c), qs.append(q)
         fulls.append(_oracle_full(oracle, BW, BH, hs, vs, c, q, qid))
-    return Seam(jb, BW, BH, hs, vs, coefs, qs, qid, pad_row=13, pad_plane=7, pad_img=77), fulls
+    return _seam(jb, BW, BH, hs, vs, coefs, qs, qid, pad_row=13, pad_plane=7, pad_img=77), fulls
 
 
 def test_seam_batch_of_five_and_its_sub_batches(jb, ctx, oracle, monkeypatch):
@@ -232,13 +181,13 @@ def test_seam_batch_of_five_and_its_sub_batches(jb, ctx, oracle, monkeypatch):
     first = []
     for k, (t, fmt, roi) in enumerate(cases):
         srcs = fulls if roi is None else [f[roi[1]:roi[1] + roi[3], roi[0]:roi[0] + roi[2]] for f in fulls]
-        first.append(s.check(ctx, srcs, t, fmt, *_params(k, fmt), roi=roi)[0])
+        first.append(_check(s, ctx, srcs, t, fmt, *_params(k, fmt), roi=roi)[0])
     tmp = 3 * BW * BH
     for cap in (tmp * 3 // 2, tmp * 5 // 2):
         monkeypatch.setenv("JPEGBLK_RESIZE_TMP_BYTES", str(cap))
         with jb.Context(0) as small:
             for k, (t, fmt, roi) in enumerate(cases):
-                host, _ = s.run(small, fmt, t, *_params(k, fmt), roi=roi, resize=t)
+                host, _ = s.run(small, fmt, t, _params(k, fmt), roi=roi, resize=t)
                 assert np.array_equal(host, first[k]), (cap, t, fmt, roi)
 
 

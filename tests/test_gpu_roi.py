@@ -10,12 +10,10 @@ import pytest
 
 import format_ref as fr
 from conftest import BASELINE_IMAGES, GOLD, load_golden
-from test_gpu_scaled import LAYOUTS, _oracle_full
+from seam_harness import LAYOUTS, Seam, _oracle_full
 
 pytestmark = pytest.mark.gpu
 
-SENT = 0xA5
-DT = {0: np.uint8, 1: np.uint8, 2: np.float32, 3: np.float16}
 SETS = list(fr.PARAM_SETS.items())
 
 
@@ -33,71 +31,15 @@ def ctx(jb):
     c.close()
 
 
-class Seam:
-    """n images of one geometry on the device (uploaded once) and one sentinel-filled output buffer that is refilled on
-    the device before every launch.  The output of a launch is laid out as _seam_fmt of test_gpu_format.py lays it out:
-    padded row, plane and image strides (pads in elements) and, for uint8, an odd leading offset."""
+def _seam(jb, w, h, hs, vs, coefs, qs, qtab_id=(0, 1, 1), pad_row=3, pad_plane=5, pad_img=0):
+    return Seam(jb, w, h, hs, vs, coefs, qs, qtab_id, pad_row=pad_row, pad_plane=pad_plane, pad_img=pad_img)
 
-    def __init__(self, jb, ctx, w, h, hs, vs, coefs, qs, qtab_id=(0, 1, 1), pad_row=3, pad_plane=5, pad_img=0):
-        import torch
-        self.jb, self.ctx, self.n = jb, ctx, len(coefs)
-        self.desc = jb.make_desc(w, h, hs, vs, qtab_id)
-        self.pads = (pad_row, pad_plane, pad_img)
-        self.coef_t = torch.from_numpy(np.stack(coefs)).to("cuda:0")
-        self.q_t = torch.from_numpy(np.stack([jb.resolve_qtabs(self.desc, q) for q in qs])).to("cuda:0")
-        # room for the whole image in float32 with the pads, whatever the rectangle
-        self.cap = 512 + self.n * (3 * ((w + pad_row) * 4 * h + pad_plane * 4) + pad_img * 4) + 256
-        self.buf = torch.empty(self.cap, dtype=torch.uint8, device="cuda:0")
-        assert self.buf.data_ptr() % 256 == 0
 
-    def run(self, fmt, scale=(1, 1, 1), bias=(0, 0, 0), roi=None, size=None):
-        """One launch (roi=None: the entry point without a rectangle, for an output of `size`) -> (the whole buffer
-        as host bytes, the index array [n, ...] of the output's bytes in it)."""
-        import torch
-        jb = self.jb
-        pad_row, pad_plane, pad_img = self.pads
-        w, h = (roi[2], roi[3]) if roi is not None else size
-        es = np.dtype(DT[fmt]).itemsize
-        b = jb.DeviceBatch()
-        b.desc, b.n_images = self.desc, self.n
-        b.d_coef, b.coef_image_stride = self.coef_t.data_ptr(), self.coef_t.stride(0) * 2
-        b.d_qtabs, b.qtab_image_stride = self.q_t.data_ptr(), 768
-        lead = 256 + 5 if es == 1 else 256 + 3 * es   # uint8: the output starts at an odd address
-        if fmt == 0:
-            row = 3 * w + pad_row
-            img = row * h + pad_img
-            spec = None
-            idx = lead + np.arange(self.n)[:, None, None] * img + np.arange(h)[None, :, None] * row + np.arange(3 * w)[None, None, :]
-        else:
-            row = (w + pad_row) * es
-            plane = row * h + pad_plane * es
-            img = 3 * plane + pad_img * es
-            spec = jb.OutputSpec.make(fmt, scale, bias, plane_stride=plane if (pad_plane or pad_row) else 0)
-            idx = (lead + np.arange(self.n)[:, None, None, None] * img + np.arange(3)[None, :, None, None] * plane +
-                   np.arange(h)[None, None, :, None] * row + np.arange(w * es)[None, None, None, :])
-        assert lead + self.n * img <= self.cap
-        b.d_rgb, b.rgb_row_stride, b.rgb_image_stride = self.buf.data_ptr() + lead, row, img
-        self.buf.fill_(SENT)
-        torch.cuda.synchronize()
-        self.ctx.blocks_to_rgb_device(b, fmt=spec, roi=roi)
-        self.ctx.synchronize()
-        return self.buf.cpu().numpy(), idx
-
-    def check(self, fulls, roi, fmt, scale=(1, 1, 1), bias=(0, 0, 0), tag=None):
-        """The launch with `roi`: every image's output equals format_ref of the slice of its full-size pixels, and
-        every other byte of the buffer still holds the sentinel."""
-        x, y, w, h = roi
-        host, idx = self.run(fmt, scale, bias, roi=roi)
-        want = np.full(host.size, SENT, np.uint8)
-        for i, full in enumerate(fulls):
-            ref = fr.to_format(full[y:y + h, x:x + w], fmt, scale, bias)
-            want[idx[i]] = fr.bits(ref).view(np.uint8).reshape(idx[i].shape)
-        if not np.array_equal(host, want):
-            bad = np.flatnonzero(host != want)
-            inside = np.isin(bad, idx.ravel())
-            raise AssertionError(f"{tag} roi {roi} fmt {fmt}: {bad.size} bytes differ, {int((~inside).sum())} of them outside "
-                                 f"the rectangle; first at buffer byte {bad[0]}")
-        return host
+def _check(s, ctx, fulls, roi, fmt, scale=(1, 1, 1), bias=(0, 0, 0), tag=None):
+    """The launch with `roi`: every image's output equals format_ref of the slice of its full-size pixels, and every
+    other byte of the buffer still holds the sentinel.  -> the buffer."""
+    x, y, w, h = roi
+    return s.check(ctx, [fr.to_format(full[y:y + h, x:x + w], fmt, scale, bias) for full in fulls], fmt, (scale, bias), roi=roi, tag=tag)[0]
 
 
 def _rotated(i, fmt):
@@ -120,13 +62,13 @@ def test_seam_chosen_rectangles_every_format(jb, ctx, oracle, hs, vs):
     from jpeg_decoder_amd import synth
     coef, q = synth.synth_blocks(W1, H1, hs, vs, image_index=W1 + H1)
     full = _oracle_full(oracle, W1, H1, hs, vs, coef, q)
-    s = Seam(jb, ctx, W1, H1, hs, vs, [coef], [q])
+    s = _seam(jb, W1, H1, hs, vs, [coef], [q])
     for fmt in (0, 1, 2, 3):
         for i, roi in enumerate(RECTS):
             scale, bias = _rotated(i, fmt)
-            host = s.check([full], roi, fmt, scale, bias, tag=(hs, vs))
+            host = _check(s, ctx, [full], roi, fmt, scale, bias, tag=(hs, vs))
             if i == 0:   # the whole image through the ROI instantiation: the bytes of the entry point without a rectangle
-                old, _ = s.run(fmt, scale, bias, roi=None, size=(W1, H1))
+                old, _ = s.run(ctx, fmt, (W1, H1), (scale, bias))
                 assert np.array_equal(host, old), (hs, vs, fmt)
 
 
@@ -146,7 +88,7 @@ def test_seam_enumerated_rectangles(jb, ctx, oracle, hs, vs, fmt):
     from jpeg_decoder_amd import synth
     coef, q = synth.synth_blocks(W2, H2, hs, vs, image_index=W2 + H2)
     full = _oracle_full(oracle, W2, H2, hs, vs, coef, q)
-    s = Seam(jb, ctx, W2, H2, hs, vs, [coef], [q])
+    s = _seam(jb, W2, H2, hs, vs, [coef], [q])
     k = 0
     for x in ENUM_X:
         for w in ENUM_W:
@@ -154,7 +96,7 @@ def test_seam_enumerated_rectangles(jb, ctx, oracle, hs, vs, fmt):
                 for h in ENUM_H:
                     roi = (x, y, W2 - x if w is None else w, H2 - y if h is None else h)
                     scale, bias = _rotated(k, fmt)
-                    s.check([full], roi, fmt, scale, bias, tag=(hs, vs))
+                    _check(s, ctx, [full], roi, fmt, scale, bias, tag=(hs, vs))
                     k += 1
     assert k == 18 * 6 * 11 * 3
 
@@ -172,20 +114,20 @@ def test_seam_batch_strides_dense_mixed_tables_and_parameter_sets(jb, ctx, oracl
     coefs = [synth.random_blocks(g.n_coded_blocks, 7 + i) for i in range(2)]
     coefs.append(synth.synth_blocks(w, h, hs, vs, image_index=9, qtabs=q, qtab_id=qid, dense=True)[0])
     fulls = [_oracle_full(oracle, w, h, hs, vs, c, q, qid) for c in coefs]
-    s = Seam(jb, ctx, w, h, hs, vs, coefs, [q] * 3, qid, pad_row=13, pad_plane=7, pad_img=77)
+    s = _seam(jb, w, h, hs, vs, coefs, [q] * 3, qid, pad_row=13, pad_plane=7, pad_img=77)
     cases = [(fr.FMT_RGB_U8_HWC, ((1, 1, 1), (0, 0, 0))), (fr.FMT_RGB_U8_CHW, ((1, 1, 1), (0, 0, 0)))]
     cases += [(fmt, sb) for fmt in (fr.FMT_RGB_F32_CHW, fr.FMT_RGB_F16_CHW) for _, sb in SETS]
     for fmt, (scale, bias) in cases:
-        s.check(fulls, (37, 18, 224, 160), fmt, scale, bias, tag=(hs, vs))
+        _check(s, ctx, fulls, (37, 18, 224, 160), fmt, scale, bias, tag=(hs, vs))
 
 
 def test_seam_refusals(jb, ctx):
     from jpeg_decoder_amd import synth
     coef, q = synth.synth_blocks(64, 48, 1, 1)
-    s = Seam(jb, ctx, 64, 48, 1, 1, [coef], [q])
+    s = _seam(jb, 64, 48, 1, 1, [coef], [q])
     for roi in ((0, 0, 65, 48), (0, 0, 64, 49), (-1, 0, 4, 4), (0, 0, 0, 4), (2 ** 31 - 1, 0, 2, 1), (60, 40, 5, 8)):
         with pytest.raises(jb.JbError) as e:
-            s.run(0, roi=roi)
+            s.run(ctx, 0, (roi[2], roi[3]), roi=roi)
         assert e.value.status == -2, roi
     with pytest.raises(jb.JbError) as e:
         ctx.blocks_to_rgb_device(jb.DeviceBatch(), scale=2, roi=(0, 0, 8, 8))

@@ -9,11 +9,9 @@ import pytest
 
 from area_reduce import area_reduce
 from conftest import BASELINE_IMAGES, GOLD, load_golden
+from seam_harness import LAYOUTS, SEAM_SIZES, Seam, _oracle_full
 
 pytestmark = pytest.mark.gpu
-
-LAYOUTS = [(1, 1), (2, 2), (2, 1), (1, 2)]
-SENT = 0xA5
 
 
 @pytest.fixture(scope="module")
@@ -30,62 +28,15 @@ def ctx(jb):
     c.close()
 
 
-def _seam(jb, ctx, w, h, hs, vs, coefs, qs, k, qtab_id=(0, 1, 1), pad_row=0, pad_img=0):
-    """n images through jb_blocks_to_rgb_device(_scaled) with padded strides; -> list of [oh, ow, 3] outputs, after
-    checking that every byte outside them still holds the sentinel."""
-    import torch
-    n = len(coefs)
-    desc = jb.make_desc(w, h, hs, vs, qtab_id)
-    ow, oh = jb.scaled_size(w, h, k)
-    row = 3 * ow + pad_row
-    img_stride = row * oh + pad_img
-    coef_t = torch.from_numpy(np.stack(coefs)).to("cuda:0")
-    q_t = torch.from_numpy(np.stack([jb.resolve_qtabs(desc, q) for q in qs])).to("cuda:0")
-    lead = 256 + 5  # the output starts at an odd address
-    buf = torch.full((lead + n * img_stride + 256,), SENT, dtype=torch.uint8, device="cuda:0")
-    b = jb.DeviceBatch()
-    b.desc = desc
-    b.n_images = n
-    b.d_coef = coef_t.data_ptr()
-    b.coef_image_stride = coef_t.stride(0) * 2
-    b.d_qtabs = q_t.data_ptr()
-    b.qtab_image_stride = 768
-    b.d_rgb = buf.data_ptr() + lead
-    b.rgb_row_stride = row
-    b.rgb_image_stride = img_stride
-    torch.cuda.synchronize()
-    ctx.blocks_to_rgb_device(b, scale=k)
-    ctx.synchronize()
-    host = buf.cpu().numpy()
-    mask = np.ones(host.size, bool)
-    outs = []
-    for i in range(n):
-        base = lead + i * img_stride
-        idx = base + np.arange(oh)[:, None] * row + np.arange(3 * ow)[None, :]
-        outs.append(host[idx].reshape(oh, ow, 3))
-        mask[idx.ravel()] = False
-    assert (host[mask] == SENT).all(), "bytes outside the images were written"
-    return outs
-
-
-def _oracle_full(oracle, w, h, hs, vs, coef, q, qtab_id=(0, 1, 1)):
-    from oracle.pyoracle import make_desc as odesc
-    return oracle.blocks_to_rgb(odesc(w, h, hs, vs, list(qtab_id)), coef, q, nthreads=16)
-
-
-SEAM_SIZES = [(4096, 4096), (1920, 1080), (679, 451), (100, 37), (1, 1), (7, 13)] + \
-             [(64 * 8 + a, 16 * 3 + b) for a, b in zip(range(1, 8), range(7, 0, -1))]
-
-
 @pytest.mark.parametrize("hs,vs", LAYOUTS)
 @pytest.mark.parametrize("w,h", SEAM_SIZES)
 def test_seam_scaled_equals_area_reduced_oracle(jb, ctx, oracle, hs, vs, w, h):
     from jpeg_decoder_amd import synth
     coef, q = synth.synth_blocks(w, h, hs, vs, image_index=w + h)
     full = _oracle_full(oracle, w, h, hs, vs, coef, q)
+    s = Seam(jb, w, h, hs, vs, [coef], [q])
     for k in (2, 4, 8):
-        (got,) = _seam(jb, ctx, w, h, hs, vs, [coef], [q], k)
-        assert np.array_equal(got, area_reduce(full, k)), (w, h, hs, vs, k)
+        s.check(ctx, [area_reduce(full, k)], 0, scale=k, tag=(w, h, hs, vs))
 
 
 @pytest.mark.parametrize("hs,vs", LAYOUTS)
@@ -103,19 +54,17 @@ def test_seam_scaled_batch_strides_dense_and_mixed_tables(jb, ctx, oracle, hs, v
     qs = [q] * 3
     fulls = [_oracle_full(oracle, w, h, hs, vs, c, q, qid) for c in coefs]
     assert any((f == 0).any() and (f == 255).any() for f in fulls)
+    s = Seam(jb, w, h, hs, vs, coefs, qs, qid, pad_row=13, pad_img=77)
     for k in (2, 4, 8):
-        outs = _seam(jb, ctx, w, h, hs, vs, coefs, qs, k, qid, pad_row=13, pad_img=77)
-        for i, (got, full) in enumerate(zip(outs, fulls)):
-            assert np.array_equal(got, area_reduce(full, k)), (hs, vs, k, i)
+        s.check(ctx, [area_reduce(full, k) for full in fulls], 0, scale=k, tag=(hs, vs))
 
 
 def test_seam_scale_one_is_the_full_size_seam(jb, ctx):
     from jpeg_decoder_amd import synth
     for hs, vs in LAYOUTS:
         coef, q = synth.synth_blocks(679, 451, hs, vs, image_index=5)
-        a = _seam(jb, ctx, 679, 451, hs, vs, [coef], [q], 1, pad_row=3)[0]
         b = ctx.blocks_to_rgb(jb.make_desc(679, 451, hs, vs), coef, q)
-        assert np.array_equal(a, b)
+        Seam(jb, 679, 451, hs, vs, [coef], [q], pad_row=3).check(ctx, [b], 0, scale=1, tag=(hs, vs))
 
 
 def test_seam_scaled_refusals(jb, ctx):
