@@ -802,16 +802,16 @@ int jb_entropy_decode_device(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes
   delete job;  // (everything it held is in the pinned blob now)
   if (rc) return rc;
   // The chunks fall into step within the launches of the first attempt on ordinary data; dense adversarial data
-  // (hardly any EOB to meet at) can need a workgroup's state handed on more often -- status bit 2 alone says "not
+  // (hardly any EOB to meet at) can need a workgroup's state handed on more often -- kJbStatusNotInStep alone says "not
   // yet": one retry with more launches, then the caller is told (JB_ERR_FORMAT) and the host decoder
-  // (jb_entropy_decode) is the authority.  Corrupt data (bits 0, 1) is never retried.
+  // (jb_entropy_decode) is the authority.  Corrupt data (the other bits) is never retried.
   int launches = kJbSyncLaunches;
   for (;;) {
     rc = huff_stage(ctx, s, s.h_blob, lay, coef_bytes, d_coef, ctx->stream, launches);
     if (rc) return rc;
     JB_HIP(ctx, hipMemcpyAsync(s.h_status, s.d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
     JB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (s.h_status[0] != 4u || launches >= kJbSyncLaunchesMax) break;
+    if (s.h_status[0] != kJbStatusNotInStep || launches >= kJbSyncLaunchesMax) break;
     launches = kJbSyncLaunchesMax;
   }
   s.n_status = 1;

@@ -361,6 +361,8 @@ int jb_huff_prepare_(const uint8_t *jpeg, size_t jpeg_bytes, JbHuffJob *job, std
   job->img.wg0 = 0;
   if ((uint64_t)n_mcus * job->img.nb >= (1u << 24)) return done(JB_ERR_UNSUPPORTED, "more blocks than the device decoder's 24-bit block index holds: host decoder");
   job->img.n_blocks = (uint32_t)(n_mcus * job->img.nb);
+  // (the kernels address a block by a 32-bit byte offset, jbh_mul24(block, blk_bytes): a large single-component frame wraps it)
+  if ((uint64_t)job->img.n_blocks * job->img.blk_bytes >= (1ull << 32)) return done(JB_ERR_UNSUPPORTED, "more bytes of blocks than the device decoder's 32-bit block offset holds: host decoder");
   // Every restart interval (a scan without DRI is one interval) is cut into chunks from its own first byte, one
   // lane per chunk (jb_huff.h); the caller's knob may force the size (JPEGBLK_CHUNK_BYTES, jb_knobs.h: tests, A/B runs)
   const uint32_t chunk_bytes = (chunk_knob == 64 || chunk_knob == 128) ? chunk_knob : kJbChunkBytes;

@@ -90,7 +90,7 @@ struct JbChunkDesc {
 // State between two symbols: where the next symbol starts and what it is
 struct JbChunkState {
   uint32_t bitpos;  // bit position in the image's clean scan
-  uint32_t meta;    // k (0 = a DC symbol is next, else zig-zag position) | block-in-MCU << 8 | blocks completed in the chunk << 16 (exit states)
+  uint32_t meta;    // k (0 = a DC symbol is next), block-in-MCU, blocks completed (exit states): the layout is jb_huff_core.h's (jbh_exit_meta)
 };
 
 // A re-decode of a chunk can stop as soon as it meets the path of the chunk's previous decode: from
@@ -98,8 +98,8 @@ struct JbChunkState {
 // at the first symbol boundary behind every kJbCheckpointBits bits (counted in the lane's local
 // coordinates, see jb_huff_core.h), with the counts up to there.
 constexpr uint32_t kJbCheckpointBits = 256;
-constexpr uint32_t kJbCheckpoints = 4;  // records per chunk (a 128-byte chunk crosses at most four boundaries), stored [checkpoint][chunk]:
-                                        // local position u | k << 11 | block-in-MCU << 17 | blocks completed before this place << 20 (jbh_pack_state)
+constexpr uint32_t kJbCheckpoints = 4;  // records per chunk (a 128-byte chunk crosses at most four boundaries), stored [checkpoint][chunk];
+                                        // a record's layout: jbh_pack_state and the jbh_cp_* functions of jb_huff_core.h
 
 // What a workgroup's chunks add up to, for the writing pass's bases (segmented sums over the chunks
 // of each interval, restarting at every interval's first chunk)
@@ -119,6 +119,9 @@ struct JbChunkDc {
   uint32_t pad[3];
 };
 
+// An image's status word: 0, or why the host decoder has to take it: impossible bits or a DC predictor out of range | an interval's
+// data and its blocks do not end together | the chunks are not one consistent decode (yet: more launches may do it)
+constexpr uint32_t kJbStatusCorrupt = 1u, kJbStatusOverrun = 2u, kJbStatusNotInStep = 4u;
 struct JbHuffLaunch {
   const uint8_t *scan;         // device: clean entropy-coded bytes of all images
   const uint32_t *starts;      // device: interval start offsets
@@ -127,7 +130,7 @@ struct JbHuffLaunch {
   const JbHuffWg *wgs;         // device: every workgroup of the submission
   const JbHuffWg *sync_wgs;    // device: the workgroups of the images with needs_sync (a sub-list, same order)
   int16_t *coef;               // device: output, decode-order int16 blocks (include/jpegblk.h)
-  uint32_t *status;            // device: one word per image: bit 0 corrupt data, bit 1 overrun, bit 2 the chunks are not in step
+  uint32_t *status;            // device: one word per image, 0 or kJbStatus* bits
   int32_t n_wgs;
   int32_t n_sync_wgs;
   const JbChunkDesc *chunks;   // device: one descriptor per chunk

@@ -9,8 +9,9 @@
 // predictors reset at every restart marker (T.81 F.2.1.3.1; reference jpeg.cpp:419-425), so the
 // restart intervals of a scan are independent streams (a scan without DRI is one interval).  The
 // host removes the byte stuffing and records where each interval starts (jbe::unstuff: memchr
-// speed); every interval is cut into chunks of 128 (small scans: 64) bytes from its own first byte,
-// ONE LANE PER CHUNK, 256 consecutive chunks of one image per workgroup:
+// speed); every interval is cut into chunks of 128 bytes (64 only
+// where the caller's knob says so) from its own first byte, ONE LANE PER CHUNK, 256 consecutive chunks of one image
+// per workgroup:
 //
 //   synchronisation  jb_huff_sync_kernel.  Pass 0: every lane decodes its chunk from the chunk's first
 //                    bit, assuming "the DC symbol of the MCU's first block is next" (true for the first
@@ -54,6 +55,8 @@
 #include "jb_huff_core.h"
 #include "jb_kernels.h"
 
+extern __shared__ __attribute__((aligned(16))) uint8_t lds[];  // a workgroup's LDS: Lay (the DC kernel: Misc alone) says what lies where
+
 namespace {
 
 constexpr uint32_t L = kJbhLanes;
@@ -65,30 +68,59 @@ __constant__ uint8_t kZz2Dev[64] = {0,   2,   16,  32,  18,  4,   6,   20,  34, 
                                     70,  84,  98,  112, 114, 100, 86,  72,  58,  44, 30,  46,  60,  74,  88,  102,
                                     116, 118, 104, 90,  76,  62,  78,  92,  106, 120, 122, 108, 94,  110, 124, 126};
 
+// The 256 bytes of odds and ends in a workgroup's LDS, in words: the zig-zag table (writing pass), seg_scan_wg's
+// scratch (a Seg per wave), fold_left_workgroups' reduction
+struct Misc {
+  uint32_t *w;
+  static constexpr uint32_t kBytes = 256u, kZz2 = 0u, kZz2Words = 64u / 4u, kScan = 16u, kScanWords = L / 64u * 5u, kFold = 40u, kFoldWords = 8u;
+  static_assert(kZz2 + kZz2Words <= kScan && kScan + kScanWords <= kFold && (kFold + kFoldWords) * 4u <= kBytes, "sub-areas: disjoint, inside the 256 bytes");
+  __device__ uint32_t *zz2() const { return w + kZz2; }
+  __device__ uint32_t *scan() const { return w + kScan; }
+  __device__ uint32_t *fold() const { return w + kFold; }
+};
 // LDS of a workgroup: the transposed stream, the checkpoint states, the exit states the lanes hand to their
-// right neighbours, 256 bytes of odds and ends, the table set
+// right neighbours (bit positions, then the state parts of their metas), Misc, the table set
 template <uint32_t kMaxChunk>
 struct Lay {
   static constexpr uint32_t kRows = jbh_rows(kMaxChunk);
   static constexpr uint32_t kNcp = kMaxChunk * 8u / kJbCheckpointBits;  // boundaries a chunk can cross
   static_assert(kNcp <= kJbCheckpoints, "records per chunk");
-  static constexpr uint32_t off_stream = 0;
-  static constexpr uint32_t off_cp = off_stream + kRows * L * 4u;
+  static constexpr uint32_t off_cp = kRows * L * 4u;  // (the stream: from 0)
   static constexpr uint32_t off_xbit = off_cp + kNcp * L * 4u;
   static constexpr uint32_t off_xmeta = off_xbit + L * 4u;
   static constexpr uint32_t off_misc = off_xmeta + L * 4u;
-  static constexpr uint32_t off_tab = off_misc + 256u;
-  static uint32_t bytes(uint32_t n_tabs) { return off_tab + n_tabs * kJbT1Entries * 2u + kJbT2Tables * kJbT2Entries * 2u; }
+  static constexpr uint32_t off_tab = off_misc + Misc::kBytes;
+  static constexpr uint32_t bytes(uint32_t n_tabs) { return off_tab + n_tabs * kJbT1Entries * 2u + kJbT2Tables * kJbT2Entries * 2u; }
+  static __device__ uint32_t *stream() { return (uint32_t *)lds; }
+  static __device__ uint32_t *cp() { return (uint32_t *)(lds + off_cp); }
+  static __device__ uint32_t *xbit() { return (uint32_t *)(lds + off_xbit); }
+  static __device__ uint32_t *xmeta() { return (uint32_t *)(lds + off_xmeta); }
+  static __device__ Misc misc() { return Misc{(uint32_t *)(lds + off_misc)}; }
+  static __device__ uint16_t *tab() { return (uint16_t *)(lds + off_tab); }
 };
+static_assert(Lay<64>::bytes(2) == 30976 && Lay<64>::bytes(3) == 33024 && Lay<64>::bytes(4) == 35072 && Lay<64>::bytes(5) == 37120 && Lay<64>::bytes(6) == 39168, "LDS bytes: 1.1 KiB more per workgroup cost a third of the waves (NOTES.md)");
+static_assert(Lay<128>::bytes(2) == 49408 && Lay<128>::bytes(3) == 51456 && Lay<128>::bytes(4) == 53504 && Lay<128>::bytes(5) == 55552 && Lay<128>::bytes(6) == 57600, "LDS bytes");
 
-struct ChunkGeo {
+// What a lane is in its kernel.  All three kernels cut an image into the same workgroups of kJbOwnChunks chunks, so
+// that the workgroups' sums line up; the synchronisation puts `warm` lanes in front of them, with the chunks in front
+// of the workgroup's own (none in front of an image's first chunk), which decode where `warm_go`.
+struct LaneId {
+  uint32_t ci;          // the lane's chunk in its image (wraps below 0 for the lanes in front of chunk 0)
+  bool owned, active;   // it is one of the workgroup's own chunks; or one in front of them that decodes
+  uint32_t gidx;        // its entry in the per-chunk arrays (a lane without a chunk: a valid one, nothing stored)
   uint32_t start, end;  // the chunk's bytes in the image's clean scan (end: the interval's end at the latest)
   uint32_t seg;         // its restart interval
   bool first, last;     // of its interval
+  uint32_t u0, u_end;   // the chunk's first position and the one behind its last, in the lane's local coordinates
 };
-__device__ __forceinline__ ChunkGeo chunk_geo(const JbHuffLaunch &p, const JbHuffImage &img, uint32_t gidx) {
-  const JbChunkDesc cd = p.chunks[gidx];
-  ChunkGeo x;
+__device__ __forceinline__ LaneId lane_id(const JbHuffLaunch &p, const JbHuffImage &img, const JbHuffWg &wg, uint32_t tid, uint32_t warm, bool warm_go) {
+  LaneId x;
+  x.ci = wg.first_chunk + tid - warm;
+  const bool has = tid < warm + kJbOwnChunks && x.ci < img.n_chunks;
+  x.owned = tid >= warm && has;
+  x.active = has && (x.owned || warm_go);
+  x.gidx = img.state_off + (has ? x.ci : img.n_chunks - 1u);
+  const JbChunkDesc cd = p.chunks[x.gidx];
   x.seg = cd.seg & 0x7fffffffu;
   x.first = (cd.seg >> 31) != 0;
   uint32_t seg_end = p.starts[img.int_off + x.seg + 1];
@@ -96,6 +128,7 @@ __device__ __forceinline__ ChunkGeo chunk_geo(const JbHuffLaunch &p, const JbHuf
   x.start = cd.start < seg_end ? cd.start : seg_end;
   x.end = x.start + img.chunk_bytes < seg_end ? x.start + img.chunk_bytes : seg_end;
   x.last = x.end == seg_end;
+  x.u0 = jbh_u_of_bit(x.start, x.start * 8u), x.u_end = x.u0 + (x.end - x.start) * 8u;
   return x;
 }
 
@@ -148,6 +181,8 @@ __device__ __forceinline__ Seg seg_shfl_up(const Seg &x, int off) {
   r.d2 = __shfl_up(x.d2, off);
   return r;
 }
+__device__ __forceinline__ void seg_store(uint32_t *s, const Seg &x) { s[0] = x.f, s[1] = x.n, s[2] = x.d0, s[3] = x.d1, s[4] = x.d2; }  // (five words of LDS)
+__device__ __forceinline__ Seg seg_load(const uint32_t *s) { return Seg{s[0], s[1], s[2], s[3], s[4]}; }
 // inclusive scan over the 256 lanes of the workgroup (scratch: 4 x 5 words of LDS); *total = all 256
 __device__ __forceinline__ Seg seg_scan_wg(Seg x, uint32_t *scratch, uint32_t tid, Seg *total) {
   const uint32_t lane = tid & 63u, wave = tid >> 6;
@@ -157,17 +192,13 @@ __device__ __forceinline__ Seg seg_scan_wg(Seg x, uint32_t *scratch, uint32_t ti
     if (lane >= (uint32_t)off) x = seg_combine(t, x);
   }
   __syncthreads();  // (the scratch may still be read from an earlier use)
-  if (lane == 63u) {
-    uint32_t *s = scratch + wave * 5u;
-    s[0] = x.f, s[1] = x.n, s[2] = x.d0, s[3] = x.d1, s[4] = x.d2;
-  }
+  if (lane == 63u) seg_store(scratch + wave * 5u, x);
   __syncthreads();
   Seg run{0, 0, 0, 0, 0};
   Seg all{0, 0, 0, 0, 0};
 #pragma unroll
   for (uint32_t w = 0; w < L / 64u; w++) {
-    const uint32_t *s = scratch + w * 5u;
-    const Seg t{s[0], s[1], s[2], s[3], s[4]};
+    const Seg t = seg_load(scratch + w * 5u);
     if (w < wave) run = seg_combine(run, t);
     all = seg_combine(all, t);
   }
@@ -175,10 +206,12 @@ __device__ __forceinline__ Seg seg_scan_wg(Seg x, uint32_t *scratch, uint32_t ti
   return seg_combine(run, x);
 }
 
-// what the workgroups of this image to the left of workgroup w_me add up to, folded in order: the last one that
-// holds an interval start counts from the image's first block (its DC sums from that start), the ones behind it add
-// up.  `red`: 8 words of LDS.
-__device__ __forceinline__ Seg fold_left_workgroups(const JbHuffLaunch &p, uint32_t w_first, uint32_t w_me, uint32_t *red, uint32_t tid) {
+// What lies to the left of a lane in its interval is seg_combine(seg_left_workgroups, seg_left_lanes):
+// what the workgroups of this image to the left of this one add up to, folded in order: the last one that holds an
+// interval start counts from the image's first block (its DC sums from that start), the ones behind it add up
+__device__ __forceinline__ Seg seg_left_workgroups(const JbHuffLaunch &p, const JbHuffImage &img, const JbHuffWg &wg, const Misc &misc, uint32_t tid) {
+  const uint32_t w_first = img.wg0, w_me = img.wg0 + wg.first_chunk / kJbOwnChunks;
+  uint32_t *const red = misc.fold();
   if (tid < 8) red[tid] = 0;
   __syncthreads();
   uint32_t last_f = 0;
@@ -201,98 +234,66 @@ __device__ __forceinline__ Seg fold_left_workgroups(const JbHuffLaunch &p, uint3
   __syncthreads();
   return Seg{from ? 1u : 0u, red[1], red[2], red[3], red[4]};
 }
-// the exclusive scan of the workgroup's lanes behind `carry`: what lies to the left of this lane
-__device__ __forceinline__ Seg scan_left(const Seg &mine, const Seg &carry, uint32_t *scratch, uint32_t tid, Seg *total) {
-  const Seg incl = seg_scan_wg(mine, scratch, tid, total);
+// ... and the exclusive scan of the workgroup's lanes
+__device__ __forceinline__ Seg seg_left_lanes(const Seg &mine, const Misc &misc, uint32_t tid) {
+  Seg total;
+  const Seg incl = seg_scan_wg(mine, misc.scan(), tid, &total);
   Seg left = seg_shfl_up(incl, 1);
   if ((tid & 63u) == 0) {
     // (the wave's first lane: the waves to the left, as seg_scan_wg left them in the scratch)
     left = Seg{0, 0, 0, 0, 0};
-    for (uint32_t w = 0; w < (tid >> 6); w++) {
-      const uint32_t *s = scratch + w * 5u;
-      left = seg_combine(left, Seg{s[0], s[1], s[2], s[3], s[4]});
-    }
+    for (uint32_t w = 0; w < (tid >> 6); w++) left = seg_combine(left, seg_load(misc.scan() + w * 5u));
   }
-  return seg_combine(carry, left);
+  return left;
 }
+// where a workgroup publishes what its lanes add up to, for the workgroups to its right (the scan and the store stay in the
+// kernels: a helper that holds the total costs the writing kernels registers, profiles/r09/isa_diff_huff_kernels.txt)
+__device__ __forceinline__ JbWgSum *wgsum_of(const JbHuffLaunch &p, const JbHuffImage &img, const JbHuffWg &wg) { return p.wgsum + img.wg0 + wg.first_chunk / kJbOwnChunks; }
 
 }  // namespace
 
 // ---- synchronisation ----------------------------------------------------------------------------
-constexpr uint32_t kMet = 0x80000000u;  // a lane's position once it has met its previous path: kMet | checkpoint
-
 template <uint32_t kMaxChunk>
 __global__ __launch_bounds__(kJbHuffLanes) void jb_huff_sync_kernel(const JbHuffLaunch p, const int launch) {
   using Ly = Lay<kMaxChunk>;
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  uint32_t *const stream = (uint32_t *)(lds + Ly::off_stream);
-  uint32_t *const cpst = (uint32_t *)(lds + Ly::off_cp);
-  uint32_t *const xbit = (uint32_t *)(lds + Ly::off_xbit);
-  uint32_t *const xmeta = (uint32_t *)(lds + Ly::off_xmeta);
-  uint32_t *const misc = (uint32_t *)(lds + Ly::off_misc);
-  uint16_t *const tab = (uint16_t *)(lds + Ly::off_tab);
+  uint32_t *const xbit = Ly::xbit(), *const xmeta = Ly::xmeta();
   const uint32_t tid = threadIdx.x;
   const JbHuffWg wg = p.sync_wgs[blockIdx.x];
   const JbHuffImage img = p.images[wg.image];
-  // lanes 0..kJbWarmChunks-1: the chunks in front of the workgroup's own (none in front of an image's first chunk)
-  const uint32_t ci = wg.first_chunk + tid - kJbWarmChunks;  // (wraps below 0 for the lanes in front of chunk 0)
-  const bool owned = tid >= kJbWarmChunks && ci < img.n_chunks;
   // (the warm-up lanes only matter for the first launch: afterwards the own chunks' states come from device memory)
-  const bool active = ci < img.n_chunks && (owned || launch == 0);
-  const uint32_t gidx = img.state_off + (ci < img.n_chunks ? ci : img.n_chunks - 1u);  // (idle lanes: valid addresses, nothing stored)
-  const ChunkGeo g = chunk_geo(p, img, gidx);
-  const uint32_t u0 = jbh_u_of_bit(g.start, g.start * 8u), u_end = u0 + (g.end - g.start) * 8u;
+  const LaneId me = lane_id(p, img, wg, tid, kJbWarmChunks, launch == 0);
   const size_t n_all = p.n_chunks_total;
 
-  JbChunkState entry{g.start * 8u, 0u}, exitst{0u, 0u};
-  bool changed = active;
+  JbChunkState entry{me.start * 8u, 0u}, exitst{0u, 0u};
+  bool changed = me.active;
   if (launch > 0) {
     // nothing but a new state at the workgroup's first chunk can change anything in this launch
     bool c0 = false;
     JbChunkState ne{0u, 0u};
-    if (tid == kJbWarmChunks && owned && !g.first) {
-      ne = p.exit[gidx - 1u];
-      const JbChunkState en = p.entry[gidx];
-      c0 = ne.bitpos != en.bitpos || ((ne.meta ^ en.meta) & 0xffffu) != 0;
+    if (tid == kJbWarmChunks && me.owned && !me.first) {
+      ne = p.exit[me.gidx - 1u];
+      c0 = !jbh_same_state(ne, p.entry[me.gidx]);
     }
     if (!__syncthreads_or(c0)) return;
-    entry = p.entry[gidx];
-    exitst = p.exit[gidx];
+    entry = p.entry[me.gidx];
+    exitst = p.exit[me.gidx];
     changed = c0;
-    if (c0) entry = JbChunkState{ne.bitpos, ne.meta & 0xffffu};
+    if (c0) entry = jbh_entry_from_exit(ne);
   }
-  load_tables(tab, p, img, tid);
-  if (active) load_stream<Ly::kRows>(stream, p.scan + img.scan_off, g.start, tid);
+  load_tables(Ly::tab(), p, img, tid);
+  if (me.active) load_stream<Ly::kRows>(Ly::stream(), p.scan + img.scan_off, me.start, tid);
+  uint32_t *const cpl = Ly::cp() + tid;  // this lane's checkpoints: cpl[i * L]
 #pragma unroll
-  for (uint32_t i = 0; i < Ly::kNcp; i++) cpst[i * L + tid] = launch > 0 ? p.cps[i * n_all + gidx] : 0xffffffffu;
+  for (uint32_t i = 0; i < Ly::kNcp; i++) cpl[i * L] = launch > 0 ? p.cps[i * n_all + me.gidx] : kJbhCpNone;
   __syncthreads();
-
-  JbhCtx cx;
-  cx.scol = stream + tid;
-  cx.tab = tab;
-  cx.zz2 = nullptr;
-  cx.lut_ac = img.lut_ac, cx.lut_dc = img.lut_dc, cx.lut_comp = img.lut_comp;
-  cx.nb4 = img.nb * 4u;
-  cx.blk_bytes = img.blk_bytes;
-  cx.t2_first = img.n_tabs * kJbT1Entries;
-  uint32_t *const cpl = cpst + tid;  // this lane's checkpoints: cpl[i * L]
+  const JbhCtx cx = jbh_ctx(Ly::stream() + tid, Ly::tab(), nullptr, img);
 
   for (int pass = 0; pass < kMaxPasses; pass++) {
     // (wave-uniform entry: a wave none of whose lanes changed goes straight to the barrier)
     if (__builtin_amdgcn_ballot_w64(changed) != 0) {
-      JbhLane st;
-      {
-        const uint32_t bit = entry.bitpos < g.start * 8u ? g.start * 8u : entry.bitpos;
-        const uint32_t u = jbh_u_of_bit(g.start, bit);
-        st.u = (changed && u < u_end) ? u : u_end;
-        st.k = entry.meta & 0xffu;
-        st.blk4 = ((entry.meta >> 8) & 0xffu) * 4u;
-        if (st.k > 63u) st.k = 0;
-        if (st.blk4 >= cx.nb4) st.blk4 = 0;
-        st.nblk = 0;
-      }
+      JbhLane st = jbh_lane_from(entry, me.start, me.u_end, cx.nb4, changed);
       uint32_t none = 0;
-      while (st.u < u_end) {
+      while (st.u < me.u_end) {
         const uint32_t up = st.u;
         (void)jbh_step<false>(cx, st, none, none, none, nullptr, 0u);
         if (((st.u ^ up) >> 8) != 0) {
@@ -300,128 +301,109 @@ __global__ __launch_bounds__(kJbHuffLanes) void jb_huff_sync_kernel(const JbHuff
           // still inside the chunk): the path of this chunk's previous decode -- what follows is known
           uint32_t *rec = cpl + ((st.u >> 8) - 1u) * L;
           const uint32_t s = jbh_pack_state(st), old = *rec;
-          const bool met = (st.u < u_end) & (((old ^ s) & 0xfffffu) == 0);  // (&: no branch)
+          const bool met = (st.u < me.u_end) & jbh_cp_same_place(old, s);  // (&: no branch)
           *rec = met ? old : s;
-          st.u = met ? (kMet | ((st.u >> 8) - 1u)) : st.u;
+          st.u = met ? jbh_met_at((st.u >> 8) - 1u) : st.u;
         }
       }
       JBH_TRACE_PASS_END(pass);
       if (changed) {
-        if (st.u >= kMet) {
+        if (jbh_has_met(st.u)) {
           // the rest of the chunk is what the previous decode found: its exit state, its block count shifted by the
           // difference of the counts at the meeting place; the later checkpoints move by the same amount
-          const uint32_t met_i = st.u & 0xffu;
-          const uint32_t dn = st.nblk - (cpl[met_i * L] >> 20);
-          for (uint32_t i = met_i; i < Ly::kNcp; i++) cpl[i * L] += dn << 20;
-          exitst.meta = (exitst.meta & 0xffffu) | ((((exitst.meta >> 16) + dn) & 0xffffu) << 16);
+          const uint32_t met_i = jbh_met_checkpoint(st.u);
+          const uint32_t dn = st.nblk - jbh_cp_blocks(cpl[met_i * L]);
+          for (uint32_t i = met_i; i < Ly::kNcp; i++) cpl[i * L] = jbh_cp_add_blocks(cpl[i * L], dn);
+          exitst.meta = jbh_meta_add_blocks(exitst.meta, dn);
         } else {
-          exitst.bitpos = jbh_bit_of_u(g.start, st.u);
-          exitst.meta = st.k | (st.blk4 << 6) | ((st.nblk & 0xffffu) << 16);
+          exitst = JbChunkState{jbh_bit_of_u(me.start, st.u), jbh_exit_meta(st)};
         }
       }
     }
     xbit[tid] = exitst.bitpos;
-    xmeta[tid] = exitst.meta & 0xffffu;
+    xmeta[tid] = jbh_meta_state(exitst.meta);
     __syncthreads();
     changed = false;
-    if (active && !g.first && tid > (launch == 0 ? 0u : kJbWarmChunks)) {
+    if (me.active && !me.first && tid > (launch == 0 ? 0u : kJbWarmChunks)) {
       const uint32_t nbit = xbit[tid - 1u], nmeta = xmeta[tid - 1u];
-      if (nbit != entry.bitpos || nmeta != (entry.meta & 0xffffu)) {
+      if (nbit != entry.bitpos || nmeta != jbh_meta_state(entry.meta)) {
         entry = JbChunkState{nbit, nmeta};
         changed = true;
       }
     }
     if (!__syncthreads_or(changed)) break;
   }
-  if (owned) {
-    p.entry[gidx] = entry;
-    p.exit[gidx] = exitst;
+  if (me.owned) {
+    p.entry[me.gidx] = entry;
+    p.exit[me.gidx] = exitst;
 #pragma unroll
-    for (uint32_t i = 0; i < Ly::kNcp; i++) p.cps[i * n_all + gidx] = cpl[i * L];
+    for (uint32_t i = 0; i < Ly::kNcp; i++) p.cps[i * n_all + me.gidx] = cpl[i * L];
   }
   // what the workgroup's own chunks add up to, for the writing pass
   Seg mine{0, 0, 0, 0, 0};
-  if (owned) {
-    mine.f = g.first ? 1u : 0u;
-    mine.n = (exitst.meta >> 16) + (g.first ? g.seg * img.ri * img.nb : 0u);
+  if (me.owned) {
+    mine.f = me.first ? 1u : 0u;
+    mine.n = jbh_meta_blocks(exitst.meta) + (me.first ? me.seg * img.ri * img.nb : 0u);
   }
   Seg total;
-  (void)seg_scan_wg(mine, misc + 16, tid, &total);
-  if (tid == 0) {
-    JbWgSum *o = p.wgsum + img.wg0 + wg.first_chunk / kJbOwnChunks;
-    o->has_first = total.f;
-    o->blocks = total.n;
-  }
+  (void)seg_scan_wg(mine, Ly::misc().scan(), tid, &total);
+  if (tid == 0) wgsum_of(p, img, wg)->has_first = total.f, wgsum_of(p, img, wg)->blocks = total.n;
 }
 
 // ---- the writing pass: decode from the left neighbour's final exit state, store, verify ----------------
 template <uint32_t kMaxChunk>
 __global__ __launch_bounds__(kJbHuffLanes) void jb_huff_write_kernel(const JbHuffLaunch p) {
   using Ly = Lay<kMaxChunk>;
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  uint32_t *const stream = (uint32_t *)(lds + Ly::off_stream);
-  uint32_t *const misc = (uint32_t *)(lds + Ly::off_misc);
-  uint16_t *const tab = (uint16_t *)(lds + Ly::off_tab);
+  const Misc misc = Ly::misc();
   const uint32_t tid = threadIdx.x;
   const JbHuffWg wg = p.wgs[blockIdx.x];
   const JbHuffImage img = p.images[wg.image];
-  const uint32_t ci = wg.first_chunk + tid;
-  const bool active = tid < kJbOwnChunks && ci < img.n_chunks;
-  const uint32_t gidx = img.state_off + (active ? ci : img.n_chunks - 1u);
-  const ChunkGeo g = chunk_geo(p, img, gidx);
-  const uint32_t u0 = jbh_u_of_bit(g.start, g.start * 8u), u_end = u0 + (g.end - g.start) * 8u;
+  const LaneId me = lane_id(p, img, wg, tid, 0u, false);
   const uint32_t bpi = img.ri * img.nb;  // blocks per restart interval
 
-  load_tables(tab, p, img, tid);
-  if (tid < 16) ((uint32_t *)misc)[tid] = ((const uint32_t *)kZz2Dev)[tid];
-  if (active) load_stream<Ly::kRows>(stream, p.scan + img.scan_off, g.start, tid);
+  load_tables(Ly::tab(), p, img, tid);
+  if (tid < Misc::kZz2Words) misc.zz2()[tid] = ((const uint32_t *)kZz2Dev)[tid];
+  if (me.active) load_stream<Ly::kRows>(Ly::stream(), p.scan + img.scan_off, me.start, tid);
 
   // where the chunk starts: the state, and the block
   uint32_t err = 0;
-  JbChunkState entry{g.start * 8u, 0u}, want{0u, 0u};
-  uint32_t block = g.seg * bpi;
+  JbChunkState entry{me.start * 8u, 0u}, want{0u, 0u};
+  uint32_t block = me.seg * bpi;
   if (img.needs_sync) {
     Seg mine{0, 0, 0, 0, 0};
-    if (active) {
-      want = p.exit[gidx];
-      mine.f = g.first ? 1u : 0u;
-      mine.n = (want.meta >> 16) + (g.first ? g.seg * bpi : 0u);
-      if (!g.first) {
+    if (me.active) {
+      want = p.exit[me.gidx];
+      mine.f = me.first ? 1u : 0u;
+      mine.n = jbh_meta_blocks(want.meta) + (me.first ? me.seg * bpi : 0u);
+      if (!me.first) {
         // the state this chunk starts from: its left neighbour's final exit state -- which must be the state the
         // synchronisation decoded this chunk from, or the chunks are not in step
-        const JbChunkState prev = p.exit[gidx - 1u];
-        const JbChunkState en = p.entry[gidx];
-        entry = JbChunkState{prev.bitpos, prev.meta & 0xffffu};
-        if (en.bitpos != prev.bitpos || ((en.meta ^ prev.meta) & 0xffffu) != 0) err |= 4u;
+        // (scalars, not jbh_same_state on the two structs: that form costs this kernel registers)
+        const JbChunkState prev = p.exit[me.gidx - 1u];
+        const JbChunkState en = p.entry[me.gidx];
+        entry = JbChunkState{prev.bitpos, jbh_meta_state(prev.meta)};
+        if (en.bitpos != prev.bitpos || jbh_meta_state(en.meta ^ prev.meta) != 0) err |= kJbStatusNotInStep;
       }
     }
-    const Seg carry = fold_left_workgroups(p, img.wg0, img.wg0 + wg.first_chunk / kJbOwnChunks, misc + 40, tid);
-    Seg total;
-    const Seg left = scan_left(mine, carry, misc + 16, tid, &total);
-    if (!g.first) block = left.n;
+    const Seg left = seg_combine(seg_left_workgroups(p, img, wg, misc, tid), seg_left_lanes(mine, misc, tid));
+    if (!me.first) block = left.n;
   }
   __syncthreads();
-
-  JbhCtx cx;
-  cx.scol = stream + tid;
-  cx.tab = tab;
-  cx.zz2 = (const uint8_t *)misc;
-  cx.lut_ac = img.lut_ac, cx.lut_dc = img.lut_dc, cx.lut_comp = img.lut_comp;
-  cx.nb4 = img.nb * 4u;
-  cx.blk_bytes = img.blk_bytes;
-  cx.t2_first = img.n_tabs * kJbT1Entries;
+  const JbhCtx cx = jbh_ctx(Ly::stream() + tid, Ly::tab(), (const uint8_t *)misc.zz2(), img);
 
   // the blocks of this chunk's interval end here (the padding bits behind them are not symbols)
-  uint32_t block_end = (g.seg + 1u) * img.ri < img.n_mcus ? (g.seg + 1u) * bpi : img.n_mcus * img.nb;
+  uint32_t block_end = (me.seg + 1u) * img.ri < img.n_mcus ? (me.seg + 1u) * bpi : img.n_mcus * img.nb;
   if (block_end > img.n_blocks) block_end = img.n_blocks;  // (the output is sized for n_blocks)
+  // jbh_lane_from(entry, me.start, me.u_end, cx.nb4, true), written out: the call, in any shape tried, adds 5 instructions and 3
+  // VGPRs to jb_huff_write_kernel<128> (profiles/r09/isa_diff_huff_kernels.txt) -- keep the two in step
   JbhLane st;
-  const bool overran = active && entry.bitpos > g.end * 8u;  // the chunk before consumed bits beyond this one's (= the interval's) end
+  const bool overran = me.active && entry.bitpos > me.end * 8u;  // the chunk before consumed bits beyond this one's (= the interval's) end
   {
-    const uint32_t bit = entry.bitpos < g.start * 8u ? g.start * 8u : entry.bitpos;
-    const uint32_t u = jbh_u_of_bit(g.start, bit);
-    st.u = u < u_end ? u : u_end;
-    st.k = entry.meta & 0xffu;
-    st.blk4 = ((entry.meta >> 8) & 0xffu) * 4u;
+    const uint32_t bit = entry.bitpos < me.start * 8u ? me.start * 8u : entry.bitpos;
+    const uint32_t u = jbh_u_of_bit(me.start, bit);
+    st.u = u < me.u_end ? u : me.u_end;
+    st.k = entry.meta & kJbhMetaFieldMask;
+    st.blk4 = ((entry.meta >> kJbhMetaBlkShift) & kJbhMetaFieldMask) * 4u;
     if (st.k > 63u) st.k = 0;
     if (st.blk4 >= cx.nb4) st.blk4 = 0;
     st.nblk = 0;
@@ -429,24 +411,24 @@ __global__ __launch_bounds__(kJbHuffLanes) void jb_huff_write_kernel(const JbHuf
   const uint32_t k_in = st.k;
   uint32_t dc0 = 0, dc1 = 0, dc2 = 0;
   uint8_t *const coef = (uint8_t *)p.coef + img.coef_off;
-  bool live = active && st.u < u_end && block < block_end;
+  bool live = me.active && st.u < me.u_end && block < block_end;
   while (live) {
     if (jbh_step<true>(cx, st, dc0, dc1, dc2, coef, block)) {
-      err |= 1u;  // reference jpeg.cpp:372-385: the stream is corrupt (or the chunks are not in step: bit 2)
+      err |= kJbStatusCorrupt;  // reference jpeg.cpp:372-385: the stream is corrupt (or the chunks are not in step, which is reported as well)
       live = false;
     } else {
-      live = st.u < u_end && block + st.nblk < block_end;
+      live = st.u < me.u_end && block + st.nblk < block_end;
     }
   }
   JBH_TRACE_PASS_END(0);
-  if (active) {
-    if (g.last) {
+  if (me.active) {
+    if (me.last) {
       // the interval's data ends before its blocks do, or its last symbol reaches beyond its last byte
       // (the host decoder's "entropy-coded data ends early": jb_frontend.cpp decode_interval)
-      if (block + st.nblk != block_end || st.k != 0 || st.u > u_end || overran) err |= 2u;
+      if (block + st.nblk != block_end || st.k != 0 || st.u > me.u_end || overran) err |= kJbStatusOverrun;
     } else if (img.needs_sync) {
       // this chunk must end where the synchronisation passes said it would, after as many blocks
-      if (jbh_bit_of_u(g.start, st.u) != want.bitpos || (st.k | (st.blk4 << 6) | ((st.nblk & 0xffffu) << 16)) != want.meta) err |= 4u;
+      if (jbh_bit_of_u(me.start, st.u) != want.bitpos || jbh_exit_meta(st) != want.meta) err |= kJbStatusNotInStep;
     }
     if (err) atomicOr(p.status + wg.image, err);
     // the blocks whose DC symbol lies in this chunk hold DC DIFFERENCES: jb_huff_dc_kernel makes predictors of them
@@ -455,16 +437,16 @@ __global__ __launch_bounds__(kJbHuffLanes) void jb_huff_write_kernel(const JbHuf
     o.first_block = block + (k_in != 0 ? 1u : 0u);
     o.count = err ? 0u : st.nblk + (st.k != 0 ? 1u : 0u) - (k_in != 0 ? 1u : 0u);
     o.pad[0] = o.pad[1] = o.pad[2] = 0;
-    p.chunk_dc[gidx] = o;
+    p.chunk_dc[me.gidx] = o;
   }
   if (img.needs_sync) {
     // what the workgroup's DC differences add up to (behind its last interval start), for the chunks to the right
     Seg mine{0, 0, 0, 0, 0};
-    if (active) mine = Seg{g.first ? 1u : 0u, 0u, dc0, dc1, dc2};
+    if (me.active) mine = Seg{me.first ? 1u : 0u, 0u, dc0, dc1, dc2};
     Seg total;
-    (void)seg_scan_wg(mine, misc + 16, tid, &total);
+    (void)seg_scan_wg(mine, misc.scan(), tid, &total);
     if (tid == 0) {
-      JbWgSum *o = p.wgsum + img.wg0 + wg.first_chunk / kJbOwnChunks;
+      JbWgSum *o = wgsum_of(p, img, wg);
       o->dc[0] = total.d0, o->dc[1] = total.d1, o->dc[2] = total.d2;
     }
   }
@@ -473,27 +455,21 @@ __global__ __launch_bounds__(kJbHuffLanes) void jb_huff_write_kernel(const JbHuf
 // ---- DC differences -> DC predictors (reference jpeg.cpp:335-345: component[0] = coeff + previousDC) --------
 // One lane per chunk again: the predictors at the chunk's start (0 at an interval's start: T.81 F.2.1.3.1,
 // reference jpeg.cpp:419-425) are a segmented prefix sum of the chunks' sums; the lane then walks the blocks whose
-// DC symbol lies in its chunk.  A predictor the coefficient format cannot hold is corrupt data (bit 0).
+// DC symbol lies in its chunk.  A predictor the coefficient format cannot hold is corrupt data.
 __global__ __launch_bounds__(kJbHuffLanes) void jb_huff_dc_kernel(const JbHuffLaunch p) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  uint32_t *const misc = (uint32_t *)lds;  // 256 bytes
+  const Misc misc{(uint32_t *)lds};  // (all the LDS this kernel has)
   const uint32_t tid = threadIdx.x;
   const JbHuffWg wg = p.wgs[blockIdx.x];
   const JbHuffImage img = p.images[wg.image];
-  const uint32_t ci = wg.first_chunk + tid;
-  const bool active = tid < kJbOwnChunks && ci < img.n_chunks;
-  const uint32_t gidx = img.state_off + (active ? ci : img.n_chunks - 1u);
-  const bool first = (p.chunks[gidx].seg >> 31) != 0;
-  JbChunkDc cd = p.chunk_dc[gidx];
-  if (!active) cd.count = 0;
+  const LaneId me = lane_id(p, img, wg, tid, 0u, false);  // (only gidx, active, first are used: the compiler drops the rest, loads included)
+  JbChunkDc cd = p.chunk_dc[me.gidx];
+  if (!me.active) cd.count = 0;
   uint32_t p0 = 0, p1 = 0, p2 = 0;
   if (img.needs_sync) {
     Seg mine{0, 0, 0, 0, 0};
-    if (active) mine = Seg{first ? 1u : 0u, 0u, cd.dc[0], cd.dc[1], cd.dc[2]};
-    const Seg carry = fold_left_workgroups(p, img.wg0, img.wg0 + wg.first_chunk / kJbOwnChunks, misc + 40, tid);
-    Seg total;
-    const Seg left = scan_left(mine, carry, misc + 16, tid, &total);
-    if (!first) p0 = left.d0, p1 = left.d1, p2 = left.d2;
+    if (me.active) mine = Seg{me.first ? 1u : 0u, 0u, cd.dc[0], cd.dc[1], cd.dc[2]};
+    const Seg left = seg_combine(seg_left_workgroups(p, img, wg, misc, tid), seg_left_lanes(mine, misc, tid));
+    if (!me.first) p0 = left.d0, p1 = left.d1, p2 = left.d2;
   }
   uint8_t *const coef = (uint8_t *)p.coef + img.coef_off;
   uint32_t pos4 = (cd.first_block % img.nb) * 4u;  // 4 * place of the block in its MCU
@@ -519,7 +495,7 @@ __global__ __launch_bounds__(kJbHuffLanes) void jb_huff_dc_kernel(const JbHuffLa
       }
     }
   }
-  if (bad) atomicOr(p.status + wg.image, 1u);
+  if (bad) atomicOr(p.status + wg.image, kJbStatusCorrupt);
 }
 
 // A small packed submission (one image) is fetched from the pinned host blob by a kernel instead of a
@@ -556,23 +532,23 @@ hipError_t jbk_huff_fetch(void *d_dst, const void *h_pinned_src, size_t bytes, h
   return hipGetLastError();
 }
 
-hipError_t jbk_huff_launch(const JbHuffLaunch &p, hipStream_t stream) {
-  (void)hipGetLastError();
+template <uint32_t kMaxChunk>
+static void huff_launch(const JbHuffLaunch &p, hipStream_t stream) {
   const dim3 block(kJbHuffLanes);
   const uint32_t n_tabs = p.max_tabs < 2u ? 2u : p.max_tabs > kJbMaxTabs ? kJbMaxTabs : p.max_tabs;
-  const bool small = p.max_chunk_bytes <= 64u;
-  const unsigned lds = small ? Lay<64>::bytes(n_tabs) : Lay<128>::bytes(n_tabs);
+  const unsigned lds_bytes = Lay<kMaxChunk>::bytes(n_tabs);
   if (p.n_sync_wgs > 0) {
     const int launches = p.sync_launches > 0 ? p.sync_launches : kJbSyncLaunches;
-    for (int l = 0; l < launches; l++) {
-      if (small) hipLaunchKernelGGL(jb_huff_sync_kernel<64>, dim3((unsigned)p.n_sync_wgs), block, lds, stream, p, l);
-      else hipLaunchKernelGGL(jb_huff_sync_kernel<128>, dim3((unsigned)p.n_sync_wgs), block, lds, stream, p, l);
-    }
+    for (int l = 0; l < launches; l++) hipLaunchKernelGGL(jb_huff_sync_kernel<kMaxChunk>, dim3((unsigned)p.n_sync_wgs), block, lds_bytes, stream, p, l);
   }
   if (p.n_wgs > 0) {
-    if (small) hipLaunchKernelGGL(jb_huff_write_kernel<64>, dim3((unsigned)p.n_wgs), block, lds, stream, p);
-    else hipLaunchKernelGGL(jb_huff_write_kernel<128>, dim3((unsigned)p.n_wgs), block, lds, stream, p);
-    hipLaunchKernelGGL(jb_huff_dc_kernel, dim3((unsigned)p.n_wgs), block, 256, stream, p);
+    hipLaunchKernelGGL(jb_huff_write_kernel<kMaxChunk>, dim3((unsigned)p.n_wgs), block, lds_bytes, stream, p);
+    hipLaunchKernelGGL(jb_huff_dc_kernel, dim3((unsigned)p.n_wgs), block, Misc::kBytes, stream, p);
   }
+}
+hipError_t jbk_huff_launch(const JbHuffLaunch &p, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (p.max_chunk_bytes <= 64u) huff_launch<64>(p, stream);
+  else huff_launch<128>(p, stream);
   return hipGetLastError();
 }

@@ -83,6 +83,9 @@ struct JbhLane {
   uint32_t blk4;           // 4 * block-in-MCU
   uint32_t nblk;           // blocks completed
 };
+JBH_FN JbhCtx jbh_ctx(const uint32_t *scol, const uint16_t *tab, const uint8_t *zz2, const JbHuffImage &img) {
+  return JbhCtx{scol, tab, zz2, img.lut_ac, img.lut_dc, img.lut_comp, img.nb * 4u, img.blk_bytes, img.n_tabs * kJbT1Entries};
+}
 // (the three DC values of a lane -- synchronisation: sums of the DC differences so far; writing pass: the DC
 // predictors -- are separate variables on purpose: as neighbouring fields of a struct the compiler reads them as
 // an array indexed by the component and puts the struct into scratch memory)
@@ -94,7 +97,8 @@ struct JbhLane {
 // report) move the lane on by one bit, to expect a block's start, at the NEXT place in the MCU: a wrong guess of
 // the block's place (luma tables on a chroma block) is what produces most impossible symbols and does not correct
 // itself.  kStore == true (writing pass): `coef` = the image's coefficient blocks, `block0` = the block the lane's
-// chunk starts in (an image the device decoder takes has fewer than 2^24 blocks, 2^32 bytes of them); a DC symbol
+// chunk starts in (jb_huff_prepare_ takes an image only with fewer than 2^24 blocks AND fewer than 2^32 bytes of them,
+// blk_bytes each: what jbh_mul24 and the 32-bit byte offset below hold); a DC symbol
 // stores its DIFFERENCE (jb_huff_dc_kernel turns the differences into predictors) and adds it to the chunk's sum
 // of its component; after impossible bits the state is not to be used.
 // Returns true for impossible bits.
@@ -137,7 +141,41 @@ JBH_FN bool jbh_step(const JbhCtx &cx, JbhLane &st, uint32_t &dc0, uint32_t &dc1
   return bad;
 }
 
-JBH_FN uint32_t jbh_pack_state(const JbhLane &st) { return st.u | (st.k << 11) | (st.blk4 << 15) | (st.nblk << 20); }  // (blk4 <= 20: bits 15..19)
+// ---- the state between two symbols, as it is stored: the ONE statement of both layouts (change them here) ----------
+// JbChunkState::meta (device memory, and a lane's exit state in LDS):
+//   bits 0..7 k | bits 8..15 block-in-MCU | bits 16..31 blocks the chunk completed, mod 2^16 (exit states only)
+// Bits 0..15 are the STATE PART: with the bit position, all that what follows depends on.
+constexpr uint32_t kJbhMetaBlkShift = 8, kJbhMetaFieldMask = 0xffu;        // (k and block-in-MCU: a byte each)
+constexpr uint32_t kJbhMetaStateMask = 0xffffu, kJbhMetaCountShift = 16, kJbhMetaCountMask = 0xffffu;  // (the count fills the upper half)
+JBH_FN uint32_t jbh_exit_meta(const JbhLane &st) { return st.k | (st.blk4 << (kJbhMetaBlkShift - 2u)) | ((st.nblk & kJbhMetaCountMask) << kJbhMetaCountShift); }  // (blk4 = 4 * block)
+JBH_FN uint32_t jbh_meta_state(uint32_t meta) { return meta & kJbhMetaStateMask; }
+JBH_FN uint32_t jbh_meta_blocks(uint32_t meta) { return meta >> kJbhMetaCountShift; }
+JBH_FN uint32_t jbh_meta_add_blocks(uint32_t meta, uint32_t dn) { return (meta & kJbhMetaStateMask) | ((((meta >> kJbhMetaCountShift) + dn) & kJbhMetaCountMask) << kJbhMetaCountShift); }
+JBH_FN bool jbh_same_state(const JbChunkState &a, const JbChunkState &b) { return a.bitpos == b.bitpos && ((a.meta ^ b.meta) & kJbhMetaStateMask) == 0; }
+JBH_FN JbChunkState jbh_entry_from_exit(const JbChunkState &x) { return JbChunkState{x.bitpos, x.meta & kJbhMetaStateMask}; }  // what an exit state hands to the chunk on its right
+// A lane that starts from `entry` in the chunk at byte `start` whose positions end at u_end (nb4: JbhCtx).  A position
+// outside the chunk, or `go` == false, puts the lane at u_end (it decodes nothing); k and block-in-MCU beyond what
+// the frame has (device scratch starts as garbage) count as a block's start.
+JBH_FN JbhLane jbh_lane_from(const JbChunkState &entry, uint32_t start, uint32_t u_end, uint32_t nb4, bool go) {
+  const uint32_t u = jbh_u_of_bit(start, entry.bitpos < start * 8u ? start * 8u : entry.bitpos);
+  const uint32_t k = entry.meta & kJbhMetaFieldMask, blk4 = ((entry.meta >> kJbhMetaBlkShift) & kJbhMetaFieldMask) * 4u;
+  return JbhLane{(go && u < u_end) ? u : u_end, k > 63u ? 0u : k, blk4 >= nb4 ? 0u : blk4, 0u};
+}
+
+// Checkpoint record (JbHuffLaunch::cps, and the lanes' copies in LDS), of the state at a symbol boundary:
+//   bits 0..10 local position u (u_end <= 32 + 24 + 8 * 128 < 2^11) | bits 11..16 k | bits 17..19 block-in-MCU (blk4 <= 20
+//   from bit 15) | bits 20..31 blocks completed before this place, mod 2^12.  Bits 0..19 are the PLACE; kJbhCpNone (no
+// record yet) is no lane's place: its u lies beyond every chunk's end.
+constexpr uint32_t kJbhCpKShift = 11, kJbhCpBlk4Shift = 15, kJbhCpCountShift = 20, kJbhCpPlaceMask = 0xfffffu, kJbhCpNone = 0xffffffffu;
+JBH_FN uint32_t jbh_pack_state(const JbhLane &st) { return st.u | (st.k << kJbhCpKShift) | (st.blk4 << kJbhCpBlk4Shift) | (st.nblk << kJbhCpCountShift); }
+JBH_FN bool jbh_cp_same_place(uint32_t a, uint32_t b) { return ((a ^ b) & kJbhCpPlaceMask) == 0; }
+JBH_FN uint32_t jbh_cp_blocks(uint32_t rec) { return rec >> kJbhCpCountShift; }
+JBH_FN uint32_t jbh_cp_add_blocks(uint32_t rec, uint32_t dn) { return rec + (dn << kJbhCpCountShift); }
+// A lane that has met the path of its previous decode stops: its position becomes this marker (beyond every u_end) | the checkpoint
+constexpr uint32_t kJbhMet = 0x80000000u, kJbhMetIndexMask = 0xffu;
+JBH_FN uint32_t jbh_met_at(uint32_t checkpoint) { return kJbhMet | checkpoint; }
+JBH_FN bool jbh_has_met(uint32_t u) { return u >= kJbhMet; }
+JBH_FN uint32_t jbh_met_checkpoint(uint32_t u) { return u & kJbhMetIndexMask; }
 
 // ---- host: table construction ---------------------------------------------------------------------
 #include <string.h>

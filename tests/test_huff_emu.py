@@ -110,6 +110,27 @@ def test_grayscale_and_three_tables_per_kind(emu, tmp_path):
         assert r.returncode == 0 and "not taken" not in r.stdout, r.stdout + r.stderr
 
 
+def test_frame_whose_blocks_exceed_32_bit_offsets_goes_to_the_host(emu, tmp_path):
+    """A single-component frame of 28000 x 28000 has 3500 x 3500 blocks -- fewer than 2^24 -- but 384 bytes apart their
+    offsets reach 2^32, which the kernels' 32-bit block offsets cannot hold: jb_huff_prepare_ must leave it to the host
+    decoder (a small grayscale stream with the SOF0 height and width overwritten: only the refusal is looked at)."""
+    pytest.importorskip("PIL")
+    import io
+    from PIL import Image
+    g = np.clip(np.cumsum(np.random.default_rng(4).normal(0, 5, (397, 531)), axis=1) + 128, 0, 255).astype(np.uint8)
+    b = io.BytesIO()
+    Image.fromarray(g).save(b, "JPEG", quality=88)
+    d = bytearray(b.getvalue())
+    sof = d.index(b"\xff\xc0")
+    assert d[sof + 9] == 1  # one component
+    d[sof + 5:sof + 9] = (28000).to_bytes(2, "big") * 2  # height, width
+    p = tmp_path / "gray_28000.jpg"
+    p.write_bytes(bytes(d))
+    r = run(emu, [str(p)], strict=False)
+    line = [ln for ln in r.stdout.splitlines() if "not taken by the device decoder" in ln]
+    assert line and "32-bit block offset" in line[0], r.stdout + r.stderr
+
+
 def test_dense_random_data_needs_the_second_launch_or_flags(emu, tmp_path):
     """Uniform random coefficients in the full baseline alphabet (16-bit codes with 10 magnitude bits, hardly any EOB
     to fall into step at): the second-level tables run for most symbols, and lanes rarely meet their previous paths.
