@@ -63,7 +63,8 @@
  *                          up to 8 workgroups per CU of the 192-lane kernel, e.g. one to four 1080p images, one 4096x4096 4:2:0)
  *   JPEGBLK_TIMING         1 | 2 | 3 = where one decode(bytes) / one device-entropy submission / one batch run spends its time (stderr)
  *   JPEGBLK_RESIZE_TMP_BYTES  bytes of full-size intermediates one launch pair of a decode to a fixed output size may
- *                          hold (default 128 MiB; more runs as sub-batches of whole images, one image at the least)
+ *                          hold (default 128 MiB; more runs as sub-batches of whole images, one image at the least;
+ *                          with per-image rectangles a sub-batch also ends after 32 images)
  *   JPEGBLK_HW_QUEUES      read when the library is LOADED: hardware queues to ask the HIP runtime for
  *                          (GPU_MAX_HW_QUEUES; default 16, 0 = the runtime's default).  Process-wide, and only
  *                          effective before HIP initialises: an application that initialises HIP first sets
@@ -351,6 +352,30 @@ int jb_decode_memory_resized(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes
 int jb_decode_file_resized(jb_ctx *ctx, const char *path, const jb_roi *roi, int32_t out_w, int32_t out_h,
                            const jb_output_spec *spec, void **out, int32_t *width, int32_t *height);
 
+/* ---- per-image rectangles: a different rectangle for every image of a batch, all at one output size ----
+ * The random-resized-crop of a training pipeline in one call.  For image i of the call, with rectangle r_i = (x, y, w, h)
+ * in pixels of that image's full-size decode and ONE target out_w x out_h for the call,
+ *     out_i = format(area_resize(full_i[y : y + h, x : x + w], out_w, out_h))
+ * -- bit for bit what jb_blocks_to_rgb_device_resized writes for a batch of that one image with &r_i, in every format
+ * (no new arithmetic: "fixed output size" above).  out_w = w_i, out_h = h_i gives the slice itself.  A target size is
+ * required (it is what makes the outputs one size); never with a scale other than 1 (JB_ERR_UNSUPPORTED).
+ * Still two launches in stream order per sub-batch: consecutive images share a launch pair while their tight
+ * intermediates (3 * w_i * h_i bytes each, back to back) fit the stream's scratch (JPEGBLK_RESIZE_TMP_BYTES; a larger
+ * image runs alone) and there are at most 32 of them.  The rectangles of a sub-batch travel in the kernels' arguments:
+ * nothing is uploaded, and the caller's array is not needed once the call has returned. */
+/* JB_OK when every one of the n rectangles lies in the image and out_w, out_h are in 1..65535 (n = 0: only the target is
+ * checked); else the status of the first rectangle that fails (JB_ERR_GEOMETRY) with its index in *bad_index (may be
+ * NULL; -1 when no rectangle is to blame: a bad target, a bad descriptor).  JB_ERR_NULL for a null descriptor or array;
+ * the descriptor's own errors first, then the rectangles', then the target's.  Pure host code. */
+int jb_crops_check(const jb_image_desc *desc, const jb_roi *rois, int n, int32_t out_w, int32_t out_h, int *bad_index);
+/* jb_blocks_to_rgb_device_resized with a rectangle per image: rois is a HOST array of batch->n_images rectangles, read
+ * before the call returns (the caller may reuse it at once).  d_rgb and the strides describe images of out_w x out_h,
+ * exactly as for _resized.  rois == NULL: JB_ERR_NULL.  A rectangle outside the frame: JB_ERR_GEOMETRY, jb_last_error
+ * names the image's index and both sizes; nothing is launched and nothing is written.  The target's checks are those
+ * of _resized.  spec == NULL: interleaved uint8. */
+int jb_blocks_to_rgb_device_crops(jb_ctx *ctx, const jb_device_batch *batch, const jb_roi *rois, int32_t out_w, int32_t out_h,
+                                  const jb_output_spec *spec, void *stream);
+
 /* ---- host front end ("next" rows of the scope table; reference jpeg.cpp:67-446, 826-907,
  *      include/file.hpp, include/huffman.hpp) --------------------------------------------- */
 /* Parse a JFIF byte stream and Huffman-decode it into packed int16 blocks in the order
@@ -520,6 +545,18 @@ int jb_batch_decoder_set_roi(jb_batch_decoder *dec, const jb_roi *roi);
  * with JB_ERR_STATE while a batch is in flight; with JB_ERR_GEOMETRY for a size outside 1..65535; while the scale is not
  * 1 (and jb_batch_decoder_set_scale(!= 1) while a target size is set) with JB_ERR_UNSUPPORTED. */
 int jb_batch_decoder_set_resize(jb_batch_decoder *dec, int32_t out_w, int32_t out_h);
+/* jb_batch_decoder_run / _submit with a rectangle per file (see "per-image rectangles" above): rois[i] belongs to
+ * paths[i], in pixels of that file's frame; files of any size and layout may be mixed.  _submit_crops copies the array,
+ * as it copies the path strings.  The target size must have been set (jb_batch_decoder_set_resize): without one the
+ * call is refused with JB_ERR_STATE, and so is a decoder-wide rectangle (jb_batch_decoder_set_roi) set at the same time
+ * -- two rectangles for one image is a mistake, not a composition.  A file its rectangle does not fit in gets the
+ * per-image status JB_ERR_GEOMETRY and the batch goes on.  Every output form works as with set_resize (malloc'ed,
+ * pinned arena, device regions), both sides of submit / collect, and multi-device decoders (file i and rectangle i go
+ * to the same device).  widths / heights report out_w / out_h.  rois == NULL: JB_ERR_NULL. */
+int jb_batch_decoder_run_crops(jb_batch_decoder *dec, const char *const *paths, int n_paths, const jb_roi *rois, uint8_t **rgb,
+                               int32_t *widths, int32_t *heights, int *statuses, double *times);
+int jb_batch_decoder_submit_crops(jb_batch_decoder *dec, const char *const *paths, int n_paths, const jb_roi *rois, uint8_t **rgb,
+                                  int32_t *widths, int32_t *heights, int *statuses, int *ticket);
 /* Output sink replacing the reference's X11 window / unused BMP writer (display.hpp,
  * jpeg.cpp:462-509): binary PPM (P6). */
 int jb_write_ppm(const char *path, const uint8_t *rgb, int32_t width, int32_t height,

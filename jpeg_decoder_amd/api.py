@@ -85,13 +85,25 @@ def _ref(struct):
     return ctypes.byref(struct) if struct is not None else None
 
 
-class _Request:
-    """The output request of one call, normalised in this one place.  (scale, fmt, roi, resize) as the caller gave them
-    (fmt: None / a format number / an OutputSpec; roi: None / (x, y, w, h) / a Roi; resize: None / (w, h)) become .scale,
-    .spec (OutputSpec or None), .roi (Roi or None) and .target ((w, h) or None).  A rectangle or a target size together
-    with a scale other than 1 is JbError(-9), raised here: no C entry point takes the pair."""
+def _crop_array(crops, n=None):
+    """[(x, y, w, h) or Roi, ...] -> a ctypes array of jb_roi (at least one element long, so that it is never NULL);
+    n: the count the call wants (JbError(-2) for another)."""
+    crops = list(crops)
+    if n is not None and len(crops) != n:
+        raise JbError(-2, f"{len(crops)} rectangles (crops) for {n} images")
+    rois = [c if isinstance(c, Roi) else Roi(*[int(v) for v in c]) for c in crops]
+    return (Roi * max(len(rois), 1))(*rois)
 
-    def __init__(self, scale=1, fmt=None, roi=None, resize=None):
+
+class _Request:
+    """The output request of one call, normalised in this one place.  (scale, fmt, roi, resize, crops) as the caller gave
+    them (fmt: None / a format number / an OutputSpec; roi: None / (x, y, w, h) / a Roi; resize: None / (w, h); crops: None
+    / a rectangle per image) become .scale, .spec (OutputSpec or None), .roi (Roi or None), .target ((w, h) or None) and
+    .crops (a ctypes array of Roi or None; .n_crops).  A rectangle or a target size together with a scale other than 1 is
+    JbError(-9), raised here: no C entry point takes the pair.  So are per-image rectangles with a scale or with roi (two
+    rectangles for one image); without a target size they are JbError(-7): only a target makes the outputs one size."""
+
+    def __init__(self, scale=1, fmt=None, roi=None, resize=None, crops=None):
         self.scale = scale
         self.spec = fmt if fmt is None or isinstance(fmt, OutputSpec) else OutputSpec.make(fmt)
         if roi is not None and scale != 1:
@@ -103,11 +115,23 @@ class _Request:
         if resize is not None:
             w, h = resize
             self.target = int(w), int(h)
+        self.crops, self.n_crops = None, 0
+        if crops is not None:
+            if scale != 1:
+                raise JbError(-9, "per-image rectangles (crops) cannot be combined with a scale")
+            if roi is not None:
+                raise JbError(-9, "per-image rectangles (crops) cannot be combined with a rectangle for every image (roi)")
+            if resize is None:
+                raise JbError(-7, "per-image rectangles (crops) want a target size (resize)")
+            self.crops = _crop_array(crops)
+            self.n_crops = len(list(crops))
 
     def routed(self):
         """-> (route, the arguments the route's entry points take between their family's own and their outputs).  The
         route names the variant of an entry point that takes this request (_ROUTES has the symbols).  A planar format
         with a scale has none, JbError(-9); format 0 with a scale is the scaled route, which takes no spec."""
+        if self.crops is not None:
+            return "crops", (self.crops, self.target[0], self.target[1], _ref(self.spec))
         if self.target is not None:
             return "resized", (_ref(self.roi), self.target[0], self.target[1], _ref(self.spec))
         if self.roi is not None:
@@ -126,7 +150,9 @@ _ROUTES = {"plain": ("jb_decode_file", "jb_decode_memory", "jb_blocks_to_rgb_dev
            "scaled": ("jb_decode_file_scaled", "jb_decode_memory_scaled", "jb_blocks_to_rgb_device_scaled"),
            "fmt": ("jb_decode_file_fmt", "jb_decode_memory_fmt", "jb_blocks_to_rgb_device_fmt"),
            "roi": ("jb_decode_file_roi", "jb_decode_memory_roi", "jb_blocks_to_rgb_device_roi"),
-           "resized": ("jb_decode_file_resized", "jb_decode_memory_resized", "jb_blocks_to_rgb_device_resized")}
+           "resized": ("jb_decode_file_resized", "jb_decode_memory_resized", "jb_blocks_to_rgb_device_resized"),
+           # (the device family alone: decode(path) and decode(bytes) handle one image, and have roi=)
+           "crops": (None, None, "jb_blocks_to_rgb_device_crops")}
 
 
 def roi_check(desc, roi):
@@ -140,6 +166,16 @@ def resize_check(desc, resize, roi=None):
     q = _Request(roi=roi, resize=resize)
     w, h = q.target
     _check(lib().jb_resize_check(ctypes.byref(desc), _ref(q.roi), w, h))
+
+
+def crops_check(desc, crops, resize):
+    """jb_crops_check: does every rectangle of `crops` lie in the descriptor's image, and is the target size (w, h) in
+    1..65535?  Raises JbError otherwise, the text naming the index of the first rectangle that does not."""
+    q = _Request(resize=resize, crops=crops)
+    bad = ctypes.c_int(-1)
+    rc = lib().jb_crops_check(ctypes.byref(desc), q.crops, q.n_crops, q.target[0], q.target[1], ctypes.byref(bad))
+    if rc != JB_OK:
+        raise JbError(rc, f"rectangle {bad.value} does not lie in the image" if bad.value >= 0 else "bad target size or descriptor")
 
 
 def _shape_output(ptr, w, h, spec):
@@ -268,6 +304,10 @@ def lib():
     L.jb_decode_memory_resized.argtypes = [vp, vp, ctypes.c_size_t, pr, i32, i32, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.jb_decode_file_resized.argtypes = [vp, ctypes.c_char_p, pr, i32, i32, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.jb_batch_decoder_set_resize.argtypes = [vp, i32, i32]
+    L.jb_crops_check.argtypes = [pd, pr, ctypes.c_int, i32, i32, ctypes.POINTER(ctypes.c_int)]
+    L.jb_blocks_to_rgb_device_crops.argtypes = [vp, ctypes.POINTER(DeviceBatch), pr, i32, i32, ps, vp]
+    L.jb_batch_decoder_run_crops.argtypes = L.jb_batch_decoder_run.argtypes[:3] + [pr] + L.jb_batch_decoder_run.argtypes[3:]
+    L.jb_batch_decoder_submit_crops.argtypes = L.jb_batch_decoder_submit.argtypes[:3] + [pr] + L.jb_batch_decoder_submit.argtypes[3:]
     L.jb_write_ppm.argtypes = [ctypes.c_char_p, vp, i32, i32, i64]
     L.jb_write_bmp.argtypes = [ctypes.c_char_p, vp, i32, i32, i64]
     if L.jb_abi_version() != 1:
@@ -441,15 +481,20 @@ class Context:
         _check(lib().jb_wait(self._h, ticket), self._h)
 
     # -- the seam, device buffers ------------------------------------------------------------
-    def blocks_to_rgb_device(self, batch, stream=None, scale=1, fmt=None, roi=None, resize=None):
+    def blocks_to_rgb_device(self, batch, stream=None, scale=1, fmt=None, roi=None, resize=None, crops=None):
         """scale 2, 4, 8: the batch's d_rgb and strides describe images of scaled_size(desc.width, desc.height, scale).
         fmt (an OutputSpec or a format number): planar output -- the batch's rgb_row_stride is then a plane's.
         roi=(x, y, w, h) (with any fmt, not with a scale): the batch's d_rgb and strides describe images of w x h, the
         rectangle of every image.
         resize=(w, h) (with any fmt, with or without roi, not with a scale): the batch's d_rgb and strides describe images
         of w x h, the exact area resize of every image (or of its rectangle).
+        crops=[(x, y, w, h), ...] with resize=(w, h) (with any fmt, not with roi or a scale): one rectangle per image of the
+        batch, each resized to w x h (jb_blocks_to_rgb_device_crops); the list is read before the call returns.
         Each is the entry point of that suffix (_ROUTES)."""
-        route, tail = _Request(scale, fmt, roi, resize).routed()
+        request = _Request(scale, fmt, roi, resize, crops)
+        if request.crops is not None and request.n_crops != batch.n_images:
+            raise JbError(-2, f"{request.n_crops} rectangles (crops) for {batch.n_images} images")
+        route, tail = request.routed()
         _check(getattr(lib(), _ROUTES[route][_DEVICE])(self._h, ctypes.byref(batch), *tail, stream), self._h)
 
     # -- decode(path) -> RGB -----------------------------------------------------------------
@@ -586,19 +631,26 @@ class BatchDecoder:
     def device_entropy_images(self):
         return lib().jb_batch_decoder_device_entropy_images(self._h)
 
-    def _run(self, paths, keep_pixels, on_image):
+    def _run(self, paths, keep_pixels, on_image, crops=None):
         a = _batch_args(paths)
         times = (ctypes.c_double * 4)()
-        rc = lib().jb_batch_decoder_run(self._h, a["paths"], a["n"], a["rgb"], a["w"], a["h"], a["st"], times)
+        if crops is not None:
+            rc = lib().jb_batch_decoder_run_crops(self._h, a["paths"], a["n"], _crop_array(crops, a["n"]), a["rgb"], a["w"], a["h"],
+                                                  a["st"], times)
+        else:
+            rc = lib().jb_batch_decoder_run(self._h, a["paths"], a["n"], a["rgb"], a["w"], a["h"], a["st"], times)
         return self._results(a, _batch_times(times, rc), keep_pixels, on_image)
 
     def _results(self, a, t, keep_pixels, on_image):
         return _harvest(a["n"], a["rgb"], a["w"], a["h"], a["st"], self._fmt, keep_pixels, on_image, self._arena, self._device_out) + (t,)
 
-    def run(self, paths, keep_pixels=True, on_image=None):
-        """-> what decode_batch returns, in the decoder's format."""
+    def run(self, paths, keep_pixels=True, on_image=None, crops=None):
+        """-> what decode_batch returns, in the decoder's format.  crops=[(x, y, w, h), ...] (jb_batch_decoder_run_crops; a
+        target size must be set, a rectangle for every image must not: rc -7 in the times): crops[i] is the rectangle of
+        paths[i], in pixels of that file, and every image comes out as its rectangle at the target size; a file its
+        rectangle does not fit in gets status -2 and the batch goes on.  JbError(-2) when len(crops) != len(paths)."""
         assert not self._device_out, "device output is set: use run_to_device"
-        return self._run(paths, keep_pixels, on_image)
+        return self._run(paths, keep_pixels, on_image, crops)
 
     def set_device_output(self, d_base, nbytes):
         """jb_batch_decoder_set_device_output: decoded images stay in the caller's DEVICE memory
@@ -616,18 +668,20 @@ class BatchDecoder:
         _check(lib().jb_batch_decoder_set_device_outputs(self._h, ptrs, sizes, n))
         self._arena = self._device_out = n > 0
 
-    def run_to_device(self, paths):
-        """After set_device_output: -> (device pointers (int, 0 = failed), (width, height) per image, statuses, times)."""
+    def run_to_device(self, paths, crops=None):
+        """After set_device_output: -> (device pointers (int, 0 = failed), (width, height) per image, statuses, times).
+        crops: as for run()."""
         assert self._device_out, "call set_device_output first"
-        return self._run(paths, False, None)
+        return self._run(paths, False, None, crops)
 
-    def run_to_tensor(self, paths, out):
+    def run_to_tensor(self, paths, out, crops=None):
         """Decode files of ONE size (or, with a rectangle set, of any size the rectangle fits in: out is then
         [N, 3, h, w] of the rectangle; with a target size set, of any size: out is [N, 3, h, w] of the target) straight into a caller-supplied CUDA tensor through the device-output route:
         out is [N, 3, H, W] (planar formats; [N, H, W, 3] for format 0), contiguous, of the decoder's format's dtype, on
         the decoder's device, N = len(paths).  -> (out, statuses, times).  An image whose size does not match out (or
         that fails to decode) gets a non-zero status (JB_ERR_GEOMETRY = -2 for the size) and its slice of out is left
-        as it was.  The decoder's device-output setting is replaced for the call and cleared afterwards."""
+        as it was.  The decoder's device-output setting is replaced for the call and cleared afterwards.
+        crops: as for run() -- the random-resized-crop of a batch straight into the model's input tensor."""
         import torch
         spec = self._fmt
         planar = spec is not None and spec.format != FMT_RGB_U8_HWC
@@ -648,7 +702,7 @@ class BatchDecoder:
         torch.cuda.synchronize(out.device)
         self.set_device_output(scratch.data_ptr(), scratch.numel())
         try:
-            ptrs, sizes, st, t = self.run_to_device(paths)
+            ptrs, sizes, st, t = self.run_to_device(paths, crops)
         finally:
             self.set_device_output(0, 0)
         st = list(st)
@@ -666,10 +720,15 @@ class BatchDecoder:
         return out, st, t
 
     # -- batches in a stream (jb_batch_decoder_submit / _collect): two in flight -----------------
-    def submit(self, paths):
-        """-> a ticket (keeps the batch's arrays alive); the batch runs while the caller prepares the next one."""
+    def submit(self, paths, crops=None):
+        """-> a ticket (keeps the batch's arrays alive); the batch runs while the caller prepares the next one.
+        crops: as for run() (jb_batch_decoder_submit_crops, which copies them; a refusal is a JbError here)."""
         t = _batch_args(paths)
-        _check(lib().jb_batch_decoder_submit(self._h, t["paths"], t["n"], t["rgb"], t["w"], t["h"], t["st"], ctypes.byref(t["id"])))
+        if crops is not None:
+            _check(lib().jb_batch_decoder_submit_crops(self._h, t["paths"], t["n"], _crop_array(crops, t["n"]), t["rgb"], t["w"], t["h"],
+                                                       t["st"], ctypes.byref(t["id"])))
+        else:
+            _check(lib().jb_batch_decoder_submit(self._h, t["paths"], t["n"], t["rgb"], t["w"], t["h"], t["st"], ctypes.byref(t["id"])))
         # the library writes into these arrays until the batch is collected (or the decoder destroyed): the decoder
         # object holds them as well, so a ticket the caller drops cannot free them under a running batch
         self._flights[t["id"].value] = t

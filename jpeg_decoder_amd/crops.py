@@ -1,0 +1,38 @@
+"""Rectangles for the per-image crops of a batch (Context.blocks_to_rgb_device(..., crops=), BatchDecoder.run(..., crops=)).
+
+Pure Python over a numpy.random.Generator: the rectangles of a batch can be drawn from the sizes that
+entropy_decode(jpeg_bytes, headers_only=True) reports, before anything is decoded.
+"""
+import math
+
+
+def random_resized_crop(width, height, rng, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3)):
+    """The usual random-resized-crop rectangle of a width x height image -> (x, y, w, h), always inside the image (it
+    passes jb_roi_check).  Ten draws of an area (a uniform share `scale` of the image's) and an aspect ratio w / h
+    (log-uniform in `ratio`); the first whose rounded rectangle fits the image is placed uniformly.  When none fits:
+    the centre crop of the whole image, its aspect ratio clamped to the ratio bounds.  rng: a numpy.random.Generator;
+    the same generator state gives the same rectangle."""
+    width, height = int(width), int(height)
+    if width < 1 or height < 1:
+        raise ValueError("an image is at least 1 x 1")
+    area = width * height
+    log_lo, log_hi = math.log(ratio[0]), math.log(ratio[1])
+    for _ in range(10):
+        target = area * float(rng.uniform(scale[0], scale[1]))
+        aspect = math.exp(float(rng.uniform(log_lo, log_hi)))
+        w = int(round(math.sqrt(target * aspect)))
+        h = int(round(math.sqrt(target / aspect)))
+        if 0 < w <= width and 0 < h <= height:
+            y = int(rng.integers(0, height - h + 1))
+            x = int(rng.integers(0, width - w + 1))
+            return x, y, w, h
+    # the fallback: the whole image, cut to the nearest allowed aspect ratio, centred
+    in_ratio = width / height
+    if in_ratio < ratio[0]:
+        w, h = width, int(round(width / ratio[0]))
+    elif in_ratio > ratio[1]:
+        w, h = int(round(height * ratio[1])), height
+    else:
+        w, h = width, height
+    w, h = min(max(w, 1), width), min(max(h, 1), height)
+    return (width - w) // 2, (height - h) // 2, w, h

@@ -213,6 +213,7 @@ struct Run {
   std::vector<std::vector<int>> *deferred = nullptr;
   size_t slot_coef = 0, slot_rgb = 0;  // what a ring slot holds (one image may be larger than a group's bound, not than this)
   OutputRequest out;  // the decoder's
+  const jb_roi *rois = nullptr;  // "per-image rectangles" (jb_batch_decoder_run_crops): rois[i] belongs to paths[i]; else null
 };
 
 // pass 1 (per host thread): parse the headers of its files, so that the buffers can be sized once for
@@ -231,14 +232,15 @@ constexpr size_t kHeadBytes[2] = {(size_t)4 << 10, (size_t)64 << 10};
 
 // every size of the pixels that this file takes downstream -- staging, arena, ring slots, copies -- is the output's:
 // geo.rgb_bytes is set to the bytes of the plan's image: the reduced one at scale > 1, the format's with a planar format
-void parse_one(Parsed &p, const OutputRequest &out) {
+// (crop: this file's rectangle of a run with per-image rectangles, planned as the rectangle of a batch of one; else null)
+void parse_one(Parsed &p, const OutputRequest &out, const jb_roi *crop = nullptr) {
   p.status = jb_entropy_decode(p.bytes.data(), p.bytes.size(), &p.desc, p.qtabs, nullptr, 0);
   if (p.status == JB_OK) p.status = jb_geometry_of(&p.desc, &p.geo);
   if (p.status != JB_OK) {
     p.error = jb_last_error(nullptr);
     return;
   }
-  p.plan = jb_out_plan_(&p.desc, out.scale, &out.spec, out.roi_ptr(), out.target_ptr());
+  p.plan = jb_out_plan_(&p.desc, out.scale, &out.spec, crop ? crop : out.roi_ptr(), out.target_ptr());
   p.status = p.plan.status;
   if (p.status == JB_OK) p.geo.rgb_bytes = p.plan.image_bytes;
   else p.error = p.plan.why;
@@ -257,7 +259,7 @@ void parse_pass(const Run &r, int t, std::vector<Parsed> &parsed, size_t *max_co
       ok = level < 2 ? jb_read_prefix_(r.paths[i], kHeadBytes[level], p.bytes, &p.loaded) : jb_read_file_(r.paths[i], p.bytes);
       *t_read += jb_now_s_() - a;
       if (level == 2) p.loaded = ok;
-      if (ok) parse_one(p, r.out);
+      if (ok) parse_one(p, r.out, r.rois ? &r.rois[i] : nullptr);
     }
     if (!ok) {
       p.status = JB_ERR_FORMAT;
@@ -372,7 +374,7 @@ struct LaneWorker {
       p.have = true;
       p.loaded = ok;
       if (ok) {
-        parse_one(p, r.out);
+        parse_one(p, r.out, r.rois ? &r.rois[i] : nullptr);
       } else {
         p.status = JB_ERR_FORMAT;
         p.error = "cannot read file";
@@ -589,15 +591,23 @@ struct LaneWorker {
     if (f.st != JB_OK) return;
     const int s = f.s;
     Parsed &head = parsed[(size_t)f.k];
+    // per-image rectangles: the group's members have one geometry and one target, and each its own rectangle -- the
+    // head's plan with the members' rectangles next to it (the array is read before the submission returns)
+    JbOutPlan plan = head.plan;
+    std::vector<jb_roi> crops;
+    if (r.rois) {
+      for (int j = 0; j < f.n; j++) crops.push_back(parsed[(size_t)(f.k + j)].plan.roi);
+      plan = jb_out_plan_(&head.desc, r.out.scale, &r.out.spec, nullptr, r.out.target_ptr(), crops.data(), f.n);
+    }
     double a = jb_now_s_();
     // every copy of the submission is pinned <-> device, so this returns at once and the
     // transfers and the kernel run while this thread decodes its next group
     std::lock_guard<std::mutex> lk(r.dev->mu);
     if (f.on_device) {
-      f.st = jb_submit_packed_(r.dev->ctx, &head.desc, qtabs.data(), lane->blob[s], &f.lay, f.dst, lane->status[s], &grp[s].ticket, head.plan,
+      f.st = jb_submit_packed_(r.dev->ctx, &head.desc, qtabs.data(), lane->blob[s], &f.lay, f.dst, lane->status[s], &grp[s].ticket, plan,
                                to_device);
     } else {
-      f.st = jb_submit_group_(r.dev->ctx, &head.desc, f.n, lane->coef[s], qtabs.data(), f.dst, &grp[s].ticket, head.plan, to_device);
+      f.st = jb_submit_group_(r.dev->ctx, &head.desc, f.n, lane->coef[s], qtabs.data(), f.dst, &grp[s].ticket, plan, to_device);
     }
     if (f.st != JB_OK) f.text = jb_last_error(r.dev->ctx);
     t_wait += jb_now_s_() - a;
@@ -704,6 +714,7 @@ struct jb_batch_decoder {
     double times[4] = {0, 0, 0, 0};
     std::vector<std::string> path_text;  // the batch's paths, copied: the caller's array need not outlive submit
     std::vector<const char *> path_ptr;
+    std::vector<jb_roi> rois;  // (jb_batch_decoder_submit_crops) the batch's rectangles, copied like the paths
   };
   Flight flights[2];
   int tickets = 0;
@@ -807,7 +818,8 @@ int create_single(int device_id, int n_threads, size_t max_coef_bytes, size_t ma
 }
 
 // one device's share of a run; `top` = this decoder owns the arena (and recycles it)
-int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8_t **rgb, int32_t *widths,
+// (rois: the files' rectangles of a run with per-image rectangles, or null)
+int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_roi *rois, uint8_t **rgb, int32_t *widths,
                int32_t *heights, int *statuses, double *times, bool top) {
   Totals tot;
   Shared dev;
@@ -847,6 +859,7 @@ int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8
     r.lazy = lazy;
     r.deferred = &deferred;
     r.out = d->out;
+    r.rois = rois;
     const double tr0 = jb_now_s_();
     std::vector<std::vector<Parsed>> parsed((size_t)nt);
     for (int t = 0; t < nt; t++) parsed[(size_t)t].resize(lists[(size_t)t].size());
@@ -1159,9 +1172,9 @@ int arrange_outputs(jb_batch_decoder *d, bool for_sides) {
   return JB_OK;
 }
 
-int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8_t **rgb, int32_t *widths, int32_t *heights,
-             int *statuses, double *times) {
-  if (d->parts.empty()) return run_single(d, paths, n_paths, rgb, widths, heights, statuses, times, d->arena == &d->own_arena);
+int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_roi *rois, uint8_t **rgb, int32_t *widths,
+             int32_t *heights, int *statuses, double *times) {
+  if (d->parts.empty()) return run_single(d, paths, n_paths, rois, rgb, widths, heights, statuses, times, d->arena == &d->own_arena);
   // multi-device: file i -> part i % n_parts (images are independent: nothing crosses devices);
   // every part runs its share on its own host threads, concurrently with the others
   const int np = (int)d->parts.size();
@@ -1171,6 +1184,7 @@ int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8_t
   const double t0 = jb_now_s_();
   struct Share {
     std::vector<const char *> paths;
+    std::vector<jb_roi> rois;  // (per-image rectangles: rectangle i goes where file i goes)
     std::vector<uint8_t *> rgb;
     std::vector<int32_t> w, h;
     std::vector<int> st;
@@ -1179,7 +1193,10 @@ int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8_t
     std::string text;
   };
   std::vector<Share> sh((size_t)np);
-  for (int i = 0; i < n_paths; i++) sh[(size_t)(i % np)].paths.push_back(paths[i]);
+  for (int i = 0; i < n_paths; i++) {
+    sh[(size_t)(i % np)].paths.push_back(paths[i]);
+    if (rois) sh[(size_t)(i % np)].rois.push_back(rois[i]);
+  }
   std::vector<std::thread> th;
   for (int k = 0; k < np; k++) {
     Share &s = sh[(size_t)k];
@@ -1190,8 +1207,8 @@ int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8_t
     s.st.assign(n, JB_OK);
     th.emplace_back([&, k] {
       Share &m = sh[(size_t)k];
-      m.rc = run_single(d->parts[(size_t)k], m.paths.data(), (int)m.paths.size(), m.rgb.data(), m.w.data(), m.h.data(),
-                        m.st.data(), m.times, false);
+      m.rc = run_single(d->parts[(size_t)k], m.paths.data(), (int)m.paths.size(), rois ? m.rois.data() : nullptr, m.rgb.data(),
+                        m.w.data(), m.h.data(), m.st.data(), m.times, false);
       if (m.rc != JB_OK) m.text = jb_last_error(nullptr);  // thread-local text: fetch it on this thread
     });
   }
@@ -1222,22 +1239,53 @@ int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8_t
 
 }  // namespace
 
-extern "C" int jb_batch_decoder_run(jb_batch_decoder *d, const char *const *paths, int n_paths,
-                                    uint8_t **rgb, int32_t *widths, int32_t *heights, int *statuses,
-                                    double *times) {
-  if (!d || !paths || !rgb || !widths || !heights || !statuses)
-    return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_run: NULL pointer");
-  if (n_paths < 0) return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_run: negative count");
-  if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_run: batches are in flight (collect them first)");
+namespace {
+
+// per-image rectangles want a target size and no decoder-wide rectangle (the plan function says so: jb_plan.h)
+int crops_state(const jb_batch_decoder *d, const char *fn) {
+  static const jb_roi one = {0, 0, 1, 1};
+  const jb_image_desc frame = {65535, 65535, 1, 1, {0, 0, 0}, 0};
+  const JbOutPlan plan = jb_out_plan_(&frame, d->out.scale, &d->out.spec, d->out.roi_ptr(), d->out.target_ptr(), &one, 1);
+  if (plan.status == JB_OK) return JB_OK;
+  return jb_fail_(nullptr, plan.status, (std::string(fn) + ": " + plan.why).c_str());
+}
+
+int run_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_roi *rois, uint8_t **rgb, int32_t *widths,
+                int32_t *heights, int *statuses, double *times, const char *fn) {
+  const std::string name = fn;
+  if (!d || !paths || !rgb || !widths || !heights || !statuses) return jb_fail_(nullptr, JB_ERR_NULL, (name + ": NULL pointer").c_str());
+  if (n_paths < 0) return jb_fail_(nullptr, JB_ERR_GEOMETRY, (name + ": negative count").c_str());
+  if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, (name + ": batches are in flight (collect them first)").c_str());
+  if (rois) {
+    const int rc = crops_state(d, fn);
+    if (rc != JB_OK) return rc;
+  }
   if (d->split_for_sides) {
     int rc = arrange_outputs(d, false);
     if (rc != JB_OK) return rc;
   }
-  return run_impl(d, paths, n_paths, rgb, widths, heights, statuses, times);
+  return run_impl(d, paths, n_paths, rois, rgb, widths, heights, statuses, times);
 }
 
-extern "C" int jb_batch_decoder_submit(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8_t **rgb,
-                                       int32_t *widths, int32_t *heights, int *statuses, int *ticket) {
+}  // namespace
+
+extern "C" int jb_batch_decoder_run(jb_batch_decoder *d, const char *const *paths, int n_paths,
+                                    uint8_t **rgb, int32_t *widths, int32_t *heights, int *statuses,
+                                    double *times) {
+  return run_checked(d, paths, n_paths, nullptr, rgb, widths, heights, statuses, times, "jb_batch_decoder_run");
+}
+
+extern "C" int jb_batch_decoder_run_crops(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_roi *rois, uint8_t **rgb,
+                                          int32_t *widths, int32_t *heights, int *statuses, double *times) {
+  if (!rois) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_run_crops: NULL pointer");
+  return run_checked(d, paths, n_paths, rois, rgb, widths, heights, statuses, times, "jb_batch_decoder_run_crops");
+}
+
+namespace {
+
+// jb_batch_decoder_submit, and (rois != null) jb_batch_decoder_submit_crops
+int submit_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_roi *rois, uint8_t **rgb, int32_t *widths,
+                   int32_t *heights, int *statuses, int *ticket) {
   if (!d || !paths || !rgb || !widths || !heights || !statuses || !ticket)
     return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_submit: NULL pointer");
   if (n_paths < 0) return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_submit: negative count");
@@ -1245,6 +1293,10 @@ extern "C" int jb_batch_decoder_submit(jb_batch_decoder *d, const char *const *p
     return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_submit: submit to the multi-device decoder, not to one of its parts");
   for (int i = 0; i < n_paths; i++)
     if (!paths[i]) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_submit: NULL path");
+  if (rois) {
+    const int rc = crops_state(d, "jb_batch_decoder_submit_crops");
+    if (rc != JB_OK) return rc;
+  }
   const int side = d->tickets & 1;
   jb_batch_decoder::Flight &f = d->flights[side];
   if (f.busy) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_submit: two batches are in flight: collect the older one first");
@@ -1267,6 +1319,9 @@ extern "C" int jb_batch_decoder_submit(jb_batch_decoder *d, const char *const *p
   f.path_text.assign(paths, paths + n_paths);
   f.path_ptr.resize((size_t)n_paths);
   for (int i = 0; i < n_paths; i++) f.path_ptr[(size_t)i] = f.path_text[(size_t)i].c_str();
+  f.rois.clear();
+  if (rois) f.rois.assign(rois, rois + n_paths);
+  const bool with_rois = rois != nullptr;
   f.busy = true;
   f.ticket = d->tickets++;
   f.rc = JB_OK;
@@ -1275,7 +1330,7 @@ extern "C" int jb_batch_decoder_submit(jb_batch_decoder *d, const char *const *p
   jb_batch_decoder::Flight *const fp = &f;
   try {
     f.th = std::thread([=] {
-      fp->rc = run_impl(target, fp->path_ptr.data(), n_paths, rgb, widths, heights, statuses, fp->times);
+      fp->rc = run_impl(target, fp->path_ptr.data(), n_paths, with_rois ? fp->rois.data() : nullptr, rgb, widths, heights, statuses, fp->times);
       if (fp->rc != JB_OK) fp->text = jb_last_error(nullptr);  // thread-local text: fetch it on this thread
     });
   } catch (const std::exception &e) {  // no thread to be had: nothing is in flight
@@ -1285,6 +1340,19 @@ extern "C" int jb_batch_decoder_submit(jb_batch_decoder *d, const char *const *p
   }
   *ticket = f.ticket;
   return JB_OK;
+}
+
+}  // namespace
+
+extern "C" int jb_batch_decoder_submit(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8_t **rgb,
+                                       int32_t *widths, int32_t *heights, int *statuses, int *ticket) {
+  return submit_checked(d, paths, n_paths, nullptr, rgb, widths, heights, statuses, ticket);
+}
+
+extern "C" int jb_batch_decoder_submit_crops(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_roi *rois, uint8_t **rgb,
+                                             int32_t *widths, int32_t *heights, int *statuses, int *ticket) {
+  if (!rois) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_submit_crops: NULL pointer");
+  return submit_checked(d, paths, n_paths, rois, rgb, widths, heights, statuses, ticket);
 }
 
 extern "C" int jb_batch_decoder_collect(jb_batch_decoder *d, int ticket, double *times) {

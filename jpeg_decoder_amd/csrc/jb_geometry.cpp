@@ -99,6 +99,20 @@ int jb_resize_check(const jb_image_desc *d, const jb_roi *roi, int32_t out_w, in
   return jb_out_plan_(d, 1, nullptr, roi, &t).status;  // the rectangle first, then the target
 }
 
+int jb_crops_check(const jb_image_desc *d, const jb_roi *rois, int n, int32_t out_w, int32_t out_h, int *bad_index) {
+  if (bad_index) *bad_index = -1;
+  if (!d || (!rois && n > 0)) return JB_ERR_NULL;
+  jb_geometry g;
+  const int rc = jb_geometry_of(d, &g);
+  if (rc != JB_OK) return rc;
+  if (n < 0) return JB_ERR_GEOMETRY;
+  const JbTarget t = {out_w, out_h};
+  static const jb_roi none = {0, 0, 0, 0};
+  const JbOutPlan plan = jb_out_plan_(d, 1, nullptr, nullptr, &t, rois ? rois : &none, n);  // the rectangles first, then the target
+  if (bad_index) *bad_index = plan.bad_crop;
+  return plan.status;
+}
+
 int jb_resolve_qtabs(const jb_image_desc *d, const uint16_t *qtabs, int32_t *out192) {
   if (!d || !qtabs || !out192) return JB_ERR_NULL;
   for (int c = 0; c < 3; c++) {
@@ -112,9 +126,11 @@ int jb_resolve_qtabs(const jb_image_desc *d, const uint16_t *qtabs, int32_t *out
 }  // extern "C"
 
 // jb_plan.h: the only place that turns (frame, scale, spec, rectangle, target) into the output's sizes and strides
-JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *spec, const jb_roi *roi, const JbTarget *target) {
+JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *spec, const jb_roi *roi, const JbTarget *target,
+                       const jb_roi *crops, int n_crops) {
   JbOutPlan p;
   memset(&p, 0, sizeof p);
+  p.bad_crop = -1;
   auto refuse = [&p](int status, const char *why) {
     p.status = status, p.why = why;
     return p;
@@ -141,6 +157,24 @@ JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *
     out_w = roi->width, out_h = roi->height;
     p.has_roi = true, p.roi = *roi;
   }
+  if (crops) {
+    // two rectangles for one image is a mistake, not a composition; and only a target makes the outputs one size
+    if (roi) {
+      p.has_roi = false, p.roi = jb_roi{};
+      return refuse(JB_ERR_STATE, "per-image rectangles cannot be combined with a rectangle for every image");
+    }
+    if (!target) return refuse(JB_ERR_STATE, "per-image rectangles want a target size");
+    for (int i = 0; i < n_crops; i++)
+      if (!jb_roi_fits_(&crops[i], d->width, d->height)) {
+        static thread_local char text[192];
+        snprintf(text, sizeof text, "image %d: the rectangle %d x %d at (%d, %d) does not lie in the %d x %d image", i, crops[i].width,
+                 crops[i].height, crops[i].x, crops[i].y, d->width, d->height);
+        p.bad_crop = i;
+        return refuse(JB_ERR_GEOMETRY, text);
+      }
+    if (scale != 1) return refuse(JB_ERR_UNSUPPORTED, "a rectangle cannot be combined with a scale");
+    out_w = out_h = 0;  // (the source size is per image)
+  }
   if (target) {
     if (target->w < 1 || target->h < 1 || target->w > 65535 || target->h > 65535) {
       p.has_roi = false, p.roi = jb_roi{};
@@ -151,6 +185,7 @@ JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *
       return refuse(JB_ERR_UNSUPPORTED, "a target size cannot be combined with a scale");
     }
     p.has_resize = true;
+    if (crops) p.crops = crops, p.n_crops = n_crops;
     p.src_w = out_w, p.src_h = out_h;
     p.tmp_image_bytes = 3LL * out_w * out_h;
     out_w = target->w, out_h = target->h;

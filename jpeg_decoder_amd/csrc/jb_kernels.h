@@ -4,6 +4,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "jb_knobs.h"
+
 // Kernel arguments of one launch: a batch of images of identical geometry.
 struct JbLaunch {
   const int16_t *coef;        // device; decode-order int16 blocks
@@ -32,10 +34,24 @@ struct JbLaunch {
   // region of interest only (roi = 1; every other launch leaves these 0): the tile grid covers the MCUs the rectangle
   // touches -- tiles_per_row tiles from MCU column roi_mx on, tiles_per_image / tiles_per_row MCU rows from roi_my on;
   // mcus_x / mcus_y, width / height stay the full image's -- and p.rgb and its strides describe the roi_w x roi_h output
-  int32_t roi;                // 1: the ROI store stage (row-bound tiling, scale 1, any format)
+  int32_t roi;                // 1: the ROI store stage (row-bound tiling, scale 1, any format); 2: jbk_launch_crops
   int32_t roi_x, roi_y;       // the rectangle, in pixels of the full-size image
   int32_t roi_w, roi_h;
   int32_t roi_mx, roi_my;     // the MCU that holds (roi_x, roi_y): roi_x / (8 * hs), roi_y / (8 * vs)
+};
+
+// "Per-image rectangles" (jb_blocks_to_rgb_device_crops): what JbLaunch's roi_* fields say once for a launch, said per
+// image, with the image's place in the scratch.  The table is a kernel ARGUMENT, passed by value next to JbLaunch (or
+// JbResample): no upload, no staging to fence, and the caller's array is not needed once the launch call has returned.
+struct JbCrop {
+  int32_t x, y, w, h;      // the rectangle, in pixels of the full-size image
+  int32_t mx, my;          // the MCU that holds (x, y)
+  int32_t tiles_per_row;   // row-bound tiles that cover the MCU columns the rectangle touches
+  int32_t n_tiles;         // tiles_per_row * MCU rows the rectangle touches: the workgroups of this image that do work
+  int64_t tmp_offset;      // bytes from the scratch's base to this image's tight 3 * w * h intermediate
+};
+struct JbCropTable {
+  JbCrop c[kJbCropsPerLaunch];
 };
 
 // MCUs covered by one workgroup (a tile is 192 coded blocks in 4:4:4 and 4:2:0, 256 in 4:2:2 and 4:4:0): 64 / 32 / 64 / 64.
@@ -53,6 +69,11 @@ int jbk_linear_ok(int hs, int vs, int mcus_x);
 // = 0) and not together: anything else is hipErrorInvalidValue.  p.roi = 1: the same kernel with the ROI store stage, for
 // scale 1 and any p.format, row-bound tiling only.
 hipError_t jbk_launch(const JbLaunch &p, int hs, int vs, int scale, hipStream_t stream);
+// p.roi = 2: the ROI store stage with a rectangle per image (format 0, scale 1, row-bound tiling; at most
+// kJbCropsPerLaunch images).  The grid is n_images x p.tiles_per_image, p.tiles_per_image the largest n_tiles of the
+// table; a workgroup beyond its image's n_tiles returns at once.  Image i is written as tight interleaved uint8 rows
+// at p.rgb + table.c[i].tmp_offset; p.rgb_row_stride, p.rgb_image_stride and p.roi_* are not looked at.
+hipError_t jbk_launch_crops(const JbLaunch &p, const JbCropTable &table, int hs, int vs, hipStream_t stream);
 const char *jbk_kernel_name(int hs, int vs);
 
 // "Fixed output size" (jb_resample.hip): n_images tight interleaved uint8 images of iw x ih at src (src_image_stride bytes
@@ -71,6 +92,9 @@ struct JbResample {
 };
 // one workgroup per 64 columns x 4 rows of one image's output; more than 2^31 - 1 of them: hipErrorInvalidValue
 hipError_t jbk_resample_launch(const JbResample &p, int format, hipStream_t stream);
+// the same with a source per image: image i is table.c[i].w x table.c[i].h at p.src + table.c[i].tmp_offset (p.iw,
+// p.ih and p.src_image_stride are not looked at); at most kJbCropsPerLaunch images
+hipError_t jbk_resample_launch_crops(const JbResample &p, const JbCropTable &table, int format, hipStream_t stream);
 
 // Device-side entropy decoder (jb_huff.hip); structures in jb_huff.h.
 struct JbHuffLaunch;

@@ -359,6 +359,9 @@ struct LaneMap {
   }
 };
 
+// the rows of a kernel's by-value table argument
+static __device__ __forceinline__ const JbCrop *crops_of(const JbCropTable &table) { return table.c; }
+
 // One workgroup (192 or 256 lanes) per tile.  See the file header for the three stages.
 // MIXQ = false: every wave dequantises with ONE table (4:4:4 always; 4:2:0 when Cb and Cr name the
 // same table, the usual case).  MIXQ = true: a wave may hold blocks of two components with
@@ -376,19 +379,26 @@ struct LaneMap {
 // "scaled" below).  p.width / p.height stay the full image's; p.rgb and its strides describe the reduced image.
 // FORMAT = 1, 2, 3 (JB_FMT_RGB_U8_CHW, _F32_CHW, _F16_CHW; row-bound tiling only, SCALE = 1): the planar output
 // (jbk_launch with p.format set) -- again only what is stored differs (see "planar" below): the u8 values are those of FORMAT = 0.
-// ROI = true (jbk_launch with p.roi set; row-bound tiling only, SCALE = 1, any FORMAT): the rectangle p.roi_x, p.roi_y,
+// ROI = 1 (jbk_launch with p.roi set; row-bound tiling only, SCALE = 1, any FORMAT): the rectangle p.roi_x, p.roi_y,
 // p.roi_w, p.roi_h of the image in that format -- the grid covers only the MCUs the rectangle touches, and the store
 // stage (see "region of interest" below) writes only the pixels inside it.
-template <int HS, int VS, bool MIXQ, bool LINEAR, bool STAGED = false, int SCALE = 1, int FORMAT = 0, bool ROI = false>
+// ROI = 2 (jbk_launch_crops; FORMAT = 0 only): the same with a rectangle per image, read from `table` (a kernel
+// argument: the index is workgroup-uniform, so the reads are scalar loads from the argument segment).  The grid gives
+// every image p.tiles_per_image workgroups, the most any image of the launch needs; a workgroup beyond its own image's
+// n_tiles returns before its first load and its first barrier.  Image i is written as tight rows at p.rgb + tmp_offset.
+// TABLE is empty but for ROI = 2, where it is JbCropTable: only those instantiations have a second kernel argument.
+template <int HS, int VS, bool MIXQ, bool LINEAR, bool STAGED = false, int SCALE = 1, int FORMAT = 0, int ROI = 0, typename... TABLE>
 // (5 waves/SIMD are asked for where that costs no spill: 4:4:4 and 4:4:0; forcing it on 4:2:0 or
 // 4:2:2 spills and measured 9 % slower; the scaled 4:4:0 instantiations spill at 5 too)
-__global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS == 1)) ? 5 : 1) void jb_tile_kernel(const JbLaunch p) {
+__global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS == 1)) ? 5 : 1) void jb_tile_kernel(const JbLaunch p, const TABLE... table) {
   static_assert(!STAGED || LINEAR, "the staged store stage is an instantiation of the linear tiling");
   static_assert(SCALE == 1 || (!LINEAR && !STAGED && (SCALE == 2 || SCALE == 4 || SCALE == 8)),
                 "the scaled store stage is an instantiation of the row-bound tiling");
   static_assert(FORMAT == 0 || (!LINEAR && !STAGED && SCALE == 1 && FORMAT >= 1 && FORMAT <= 3),
                 "the planar store stage is an instantiation of the full-size row-bound tiling");
   static_assert(!ROI || (!LINEAR && !STAGED && SCALE == 1), "the ROI store stage is an instantiation of the full-size row-bound tiling");
+  static_assert(ROI >= 0 && ROI <= 2 && (ROI != 2 || FORMAT == 0), "the per-image rectangles exist for the interleaved uint8 intermediate only");
+  static_assert(sizeof...(TABLE) == (ROI == 2 ? 1 : 0), "the table is the second argument of the ROI = 2 instantiations alone");
   using LM = LaneMap<HS, VS>;
   constexpr int kTileBlocks = LM::TB;
   constexpr int kStripBytes = kTileBlocks * 128;  // half of the tile's f32 samples: 24 or 32 KiB
@@ -429,6 +439,23 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
   // MCU stream, whatever MCU rows they fall in -- every tile but the image's last is full for any
   // image width.  Row-bound: a tile is a run of MCUs of ONE MCU row (the last run of a row may be
   // short); used where it leaves no tile ragged, and for very narrow images.
+  // the rectangle, its first MCU, its tiles per row, and where and how wide its output is: this image's row of the
+  // table (ROI = 2) or the launch's (ROI = 1: read from p where they are used, as that stage always has)
+  [[maybe_unused]] JbCrop crop = {};
+  int tiles_per_row = p.tiles_per_row;
+  if constexpr (ROI == 2) {
+    crop = crops_of(table...)[img];
+    if (rem >= crop.n_tiles) return;  // (workgroup-uniform, before the first load and the first barrier)
+    tiles_per_row = crop.tiles_per_row;
+  }
+  const auto roi_x = [&] { if constexpr (ROI == 2) return crop.x; else return p.roi_x; };
+  const auto roi_y = [&] { if constexpr (ROI == 2) return crop.y; else return p.roi_y; };
+  const auto roi_w = [&] { if constexpr (ROI == 2) return crop.w; else return p.roi_w; };
+  const auto roi_h = [&] { if constexpr (ROI == 2) return crop.h; else return p.roi_h; };
+  const auto roi_mx = [&] { if constexpr (ROI == 2) return crop.mx; else return p.roi_mx; };
+  const auto roi_my = [&] { if constexpr (ROI == 2) return crop.my; else return p.roi_my; };
+  // the output rows' stride and the image's place: tight rows at the table's offset, or the launch's strides
+  const auto roi_row_stride = [&] { if constexpr (ROI == 2) return 3LL * crop.w; else return p.rgb_row_stride; };
   int my, mx0, nvalid;
   if (LINEAR) {
     const int m0 = rem * MCUS;
@@ -436,11 +463,11 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
     mx0 = m0 - my * p.mcus_x;
     nvalid = min(MCUS, p.mcus_x * p.mcus_y - m0);
   } else {
-    my = rem / p.tiles_per_row;
-    mx0 = (rem - my * p.tiles_per_row) * MCUS;
+    my = rem / tiles_per_row;
+    mx0 = (rem - my * tiles_per_row) * MCUS;
     // region of interest: the tile grid's origin is the MCU that holds the rectangle's first pixel; the coefficient
     // address below keeps the full image's mcus_x as its row pitch
-    if constexpr (ROI) my += p.roi_my, mx0 += p.roi_mx;
+    if constexpr (ROI != 0) my += roi_my(), mx0 += roi_mx();
     nvalid = min(MCUS, p.mcus_x - mx0);
   }
   const int last_block = nvalid * NB - 1;
@@ -580,7 +607,7 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
   constexpr int TASKS = YROWS * TASKS_PER_ROW;
   static_assert(TASKS % 64 == 0, "whole wave-iterations");
   static_assert(TASKS_PER_ROW % 64 == 0, "a wave-iteration stays within one strip row");
-  uint8_t *const img_rgb = p.rgb + (int64_t)img * p.rgb_image_stride;
+  uint8_t *const img_rgb = p.rgb + (ROI == 2 ? crop.tmp_offset : (int64_t)img * p.rgb_image_stride);
   // loop-invariant lane offsets of the colour stage (row-uniform layouts): the lane's 16-B luma
   // chunk within a 64-chunk segment and its chroma chunk, both with the strip swizzle applied
   // (the swizzle bit is bit 3 of the chunk index, which the segment number does not touch)
@@ -764,7 +791,7 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
           }
         }
       }
-    } else if constexpr (ROI) {
+    } else if constexpr (ROI != 0) {
       // ---- region of interest: the pixels of [roi_x, roi_x + roi_w) x [roi_y, roi_y + roi_h), in any format ----
       // The wave-iterations, LDS reads, colour transform and u8 conversion are those of the full-size stage (FORMAT = 0)
       // or of the planar one; what differs is which of them are stored, and where.  Strip rows above or below the
@@ -777,12 +804,12 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
       constexpr int IPR = TASKS_PER_ROW / 64;
       constexpr int SEG_MCUS = 256 / (8 * HS);
       constexpr int ES = FORMAT == 0 ? 3 : FORMAT == 1 ? 1 : FORMAT == 2 ? 4 : 2;  // bytes per pixel in a row (of a plane)
-      const int rx1 = p.roi_x + p.roi_w, ry1 = p.roi_y + p.roi_h;
+      const int rx1 = roi_x() + roi_w(), ry1 = roi_y() + roi_h();
       for (int it = wave; it < TASKS / 64; it += kTileBlocks / 64) {
         const int row = it / IPR, seg = it - row * IPR;
         const int y = my * 8 * VS + phase * 4 + (row >> 2) * 8 + (row & 3);  // image row of the strip row
         const int xseg = (mx0 + seg * SEG_MCUS) * 8 * HS;                    // image column of the segment
-        if (y < p.roi_y || y >= ry1 || xseg >= rx1 || xseg + 256 <= p.roi_x) continue;  // (wave-uniform)
+        if (y < roi_y() || y >= ry1 || xseg >= rx1 || xseg + 256 <= roi_x()) continue;  // (wave-uniform)
         const float4 Y = *(const float4 *)(lds + lane_y_off + row * (YW * 4) + seg * 1024);
         float cb[4], cr[4];
         const int coff = (row / VS) * (CW * 4) + seg * (1024 / HS);
@@ -793,9 +820,9 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
         for (int i = 0; i < 4; i++) {
           ycc_px(yy[i], cb[i], cr[i], r[i], g[i], b[i]);
         }
-        const int a = max(p.roi_x - xseg, 0), e = min(rx1 - xseg, 256);  // segment pixels inside the rectangle: a < e
+        const int a = max(roi_x() - xseg, 0), e = min(rx1 - xseg, 256);  // segment pixels inside the rectangle: a < e
         const int nrec = max((e & ~3) - a, 0) * ES;                       // bytes up to the end of the last whole group
-        uint8_t *const segp = img_rgb + (int64_t)(y - p.roi_y) * p.rgb_row_stride + (int64_t)(xseg + a - p.roi_x) * ES;
+        uint8_t *const segp = img_rgb + (int64_t)(y - roi_y()) * roi_row_stride() + (int64_t)(xseg + a - roi_x()) * ES;
         const int rel = lane_late * 4 - a;                    // the lane's first pixel, relative to pixel a
         const int voff = rel >= 0 ? rel * ES : 0x40000000;    // (left of the rectangle: past any range, never wrapped)
         // the edge groups: rare, so their lane tests go through an opaque copy and nothing of them is hoisted
@@ -1192,7 +1219,7 @@ __global__ __launch_bounds__(64) void jb_small_kernel_16(const JbLaunch p) {
 // Launches jb_tile_kernel<HS, VS, MIXQ, LINEAR, STAGED, SCALE, FORMAT, ROI>: every launch of the 192-lane kernel goes through
 // here.  SCALE != 1 (the area-reduced store stage), FORMAT != 0 (the planar one) and ROI exist in the row-bound tiling only.
 // MIXQ is decided here, and MIXQ = true is only instantiated for a layout that can need it.
-template <int HS, int VS, int SCALE, int FORMAT, bool LINEAR = false, bool STAGED = false, bool ROI = false>
+template <int HS, int VS, int SCALE, int FORMAT, bool LINEAR = false, bool STAGED = false, int ROI = 0>
 static hipError_t launch_tile(const JbLaunch &p, hipStream_t stream) {
   using LM = LaneMap<HS, VS>;
   // does any wave hold two components whose tables may differ?  (never luma and chroma: jb_tile_kernel asserts it)
@@ -1214,11 +1241,11 @@ static hipError_t launch_tile(const JbLaunch &p, hipStream_t stream) {
 template <int HS, int VS>
 static hipError_t launch_layout(const JbLaunch &p, int scale, hipStream_t stream) {
   if (p.roi) {  // the region of interest: its own store stage for every format, even when the rectangle is the whole image
-    if (p.linear || scale != 1) return hipErrorInvalidValue;  // (full-size row-bound tiling only)
-    if (p.format == 0) return launch_tile<HS, VS, 1, 0, false, false, true>(p, stream);
-    if (p.format == 1) return launch_tile<HS, VS, 1, 1, false, false, true>(p, stream);
-    if (p.format == 2) return launch_tile<HS, VS, 1, 2, false, false, true>(p, stream);
-    if (p.format == 3) return launch_tile<HS, VS, 1, 3, false, false, true>(p, stream);
+    if (p.linear || scale != 1 || p.roi != 1) return hipErrorInvalidValue;  // (full-size row-bound tiling only; 2: jbk_launch_crops)
+    if (p.format == 0) return launch_tile<HS, VS, 1, 0, false, false, 1>(p, stream);
+    if (p.format == 1) return launch_tile<HS, VS, 1, 1, false, false, 1>(p, stream);
+    if (p.format == 2) return launch_tile<HS, VS, 1, 2, false, false, 1>(p, stream);
+    if (p.format == 3) return launch_tile<HS, VS, 1, 3, false, false, 1>(p, stream);
     return hipErrorInvalidValue;
   }
   if (p.format == 0 && scale == 1) {
@@ -1242,6 +1269,34 @@ static hipError_t launch_layout(const JbLaunch &p, int scale, hipStream_t stream
     if (p.format == 2) return launch_tile<HS, VS, 1, 2>(p, stream);
     if (p.format == 3) return launch_tile<HS, VS, 1, 3>(p, stream);
   }
+  return hipErrorInvalidValue;
+}
+
+// the per-image rectangles: as launch_tile, with the table as the second kernel argument
+template <int HS, int VS>
+static hipError_t launch_crops(const JbLaunch &p, const JbCropTable &table, hipStream_t stream) {
+  using LM = LaneMap<HS, VS>;
+  constexpr bool kCbCrMixed = (LM::MCUS % 64 != 0);
+  const dim3 grid(p.n_tiles), block(LM::TB);
+  (void)hipGetLastError();
+  bool mixq = false;
+  if constexpr (kCbCrMixed) {
+    mixq = !p.chroma_q_equal;
+    if (mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, true, false, false, 1, 0, 2, JbCropTable>), grid, block, 0, stream, p, table);
+  }
+  if (!mixq) hipLaunchKernelGGL((jb_tile_kernel<HS, VS, false, false, false, 1, 0, 2, JbCropTable>), grid, block, 0, stream, p, table);
+  return hipGetLastError();
+}
+
+hipError_t jbk_launch_crops(const JbLaunch &p, const JbCropTable &table, int hs, int vs, hipStream_t stream) {
+  // every workgroup indexes the table with tile / tiles_per_image: the grid must be whole images, at most a table's worth
+  if (p.roi != 2 || p.linear || p.small_grid || p.format != 0 || p.tiles_per_image < 1 || p.n_tiles < 1 ||
+      p.n_tiles % p.tiles_per_image != 0 || p.n_tiles / p.tiles_per_image > kJbCropsPerLaunch)
+    return hipErrorInvalidValue;
+  if (hs == 1 && vs == 1) return launch_crops<1, 1>(p, table, stream);
+  if (hs == 2 && vs == 1) return launch_crops<2, 1>(p, table, stream);
+  if (hs == 1 && vs == 2) return launch_crops<1, 2>(p, table, stream);
+  if (hs == 2 && vs == 2) return launch_crops<2, 2>(p, table, stream);
   return hipErrorInvalidValue;
 }
 

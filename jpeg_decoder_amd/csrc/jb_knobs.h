@@ -27,7 +27,8 @@
 //   JPEGBLK_OVERSUBSCRIBE 1: allow more host threads than CPUs the process may use
 //   JPEGBLK_TIMING        1 | 2 | 3: where one decode(bytes) / one device-entropy submission / one batch run spends its time, on stderr
 //   JPEGBLK_RESIZE_TMP_BYTES  bytes of full-size intermediates one launch pair of a decode to a fixed output size may hold
-//                         (default 128 MiB; a batch that needs more runs as sub-batches of whole images, one image at the least)
+//                         (default 128 MiB; a batch that needs more runs as sub-batches of whole images, one image at the least;
+//                         with per-image rectangles a sub-batch also ends after kJbCropsPerLaunch images)
 //   JPEGBLK_HW_QUEUES     read when the LIBRARY IS LOADED (before HIP initialises, jb_api.cpp): hardware queues to
 //                         ask the runtime for (GPU_MAX_HW_QUEUES; default 16, 0 = leave the runtime's default)
 #pragma once
@@ -37,6 +38,9 @@
 // "fixed output size": the cap of one scratch of tight uint8 intermediates (jb_seam.cpp seam_launch_resized): 20 1080p
 // images, so that a device-entropy group (JPEGBLK_DEV_GROUP_MB) of them stays one launch pair
 constexpr size_t kJbResizeTmpBytes = (size_t)128 << 20;
+// "per-image rectangles": images per launch pair whose rectangles travel in the kernel arguments (JbCropTable of
+// jb_kernels.h: 32 x 40 bytes, well inside the 4 KB kernel-argument segment); a longer batch runs as sub-batches
+constexpr int kJbCropsPerLaunch = 32;
 
 struct JbKnobs {
   int gpu_huffman = -1;      // -1: unset

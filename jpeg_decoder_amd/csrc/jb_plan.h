@@ -10,7 +10,9 @@ struct JbOutPlan {
   // size outside 1..65535; unknown format; reserved != 0 on a format-0 spec), JB_ERR_UNSUPPORTED (a format other than 0
   // with a scale other than 1), JB_ERR_GEOMETRY (a rectangle that does not lie in the image), JB_ERR_UNSUPPORTED (a
   // rectangle with a scale other than 1), JB_ERR_GEOMETRY (a target size outside 1..65535), JB_ERR_UNSUPPORTED (a target
-  // size with a scale other than 1) -- in that order.  Whoever uses a plan reports it where the old code checked the
+  // size with a scale other than 1) -- in that order; with per-image rectangles, JB_ERR_GEOMETRY for the first of them
+  // that does not lie in the image (bad_crop: its index) in the single rectangle's place, and JB_ERR_STATE for what is
+  // no composition: no target size, or a launch-wide rectangle as well.  Whoever uses a plan reports it where the old code checked the
   // scale: behind the descriptor's own errors.  `why` is the text for jb_last_error (of the last plan this thread made,
   // when it names sizes); the other fields are 0 on failure.
   int status;
@@ -31,6 +33,13 @@ struct JbOutPlan {
   bool has_resize;
   int32_t src_w, src_h;
   int64_t tmp_image_bytes;  // 3 * src_w * src_h
+  // "per-image rectangles" (include/jpegblk.h): image i of the launch is the rectangle crops[i] of its full-size decode,
+  // resized to the target -- has_resize is set, has_roi is not, src_w / src_h / tmp_image_bytes are 0: the intermediate
+  // of image i is 3 * crops[i].width * crops[i].height bytes.  BORROWED: the array is the caller's, and is read before
+  // the call that takes the plan returns.  out_w, out_h, row_stride, image_bytes are the target's, as with one rectangle.
+  const jb_roi *crops;
+  int32_t n_crops;
+  int32_t bad_crop;  // status == JB_ERR_GEOMETRY because of a rectangle: which one; else -1
 };
 
 // a target size for jb_out_plan_
@@ -41,5 +50,7 @@ struct JbTarget {
 // spec: null or format 0 = interleaved uint8.  Beyond `reserved` on a format-0 spec, the spec's own fields (plane_stride
 // against a row stride, finite scale / bias) are jb_output_spec_check's, which needs the caller's strides.
 // roi: null = the whole image.  target: null = the size of the image (at the scale) or of the rectangle.
+// crops: null = none; else n_crops rectangles, one per image of the launch (n_crops < 1: nothing to check); wants a target
+// and no roi.
 JbOutPlan jb_out_plan_(const jb_image_desc *desc, int scale, const jb_output_spec *spec, const jb_roi *roi = nullptr,
-                       const JbTarget *target = nullptr);
+                       const JbTarget *target = nullptr, const jb_roi *crops = nullptr, int n_crops = 0);

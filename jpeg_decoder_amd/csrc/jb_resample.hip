@@ -22,6 +22,9 @@
 
 static constexpr int kResampleRows = 4;  // output rows (= waves) per workgroup
 
+// the rows of a kernel's by-value table argument
+static __device__ __forceinline__ const JbCrop *crops_of(const JbCropTable &table) { return table.c; }
+
 // floor(n / d) for n < 2^41, 1 <= d < 2^32 with a quotient of at most 255: a float estimate (a few units off at the
 // worst) and integer correction steps that make it exact whatever the estimate was
 static __device__ __forceinline__ uint32_t div_to_u8(uint64_t n, uint32_t d, float rcp_d) {
@@ -31,18 +34,29 @@ static __device__ __forceinline__ uint32_t div_to_u8(uint64_t n, uint32_t d, flo
   return q;
 }
 
-template <int FORMAT>
-__global__ __launch_bounds__(64 * kResampleRows) void jb_resample_kernel(const JbResample p) {
+// CROPS ("per-image rectangles"; TABLE is then JbCropTable, a second kernel argument, and empty otherwise): the source of
+// image `img` is table.c[img].w x .h at p.src + .tmp_offset instead of p.iw x p.ih at p.src + img * p.src_image_stride --
+// img comes from blockIdx, so the table reads are scalar loads and everything derived from them stays wave-uniform.
+template <int FORMAT, bool CROPS = false, typename... TABLE>
+__global__ __launch_bounds__(64 * kResampleRows) void jb_resample_kernel(const JbResample p, const TABLE... table) {
+  static_assert(sizeof...(TABLE) == (CROPS ? 1 : 0), "the table is the second argument of the CROPS instantiations alone");
   // (the wave id is wave-uniform, and only readfirstlane tells the compiler so)
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = (int)(threadIdx.x & 63);
   const uint32_t b = blockIdx.x;
   const uint32_t tx = b % (uint32_t)p.tiles_x, t = b / (uint32_t)p.tiles_x;
   const uint32_t ty = t % (uint32_t)p.tiles_y, img = t / (uint32_t)p.tiles_y;
-  const uint32_t iw = (uint32_t)p.iw, ih = (uint32_t)p.ih, ow = (uint32_t)p.ow, oh = (uint32_t)p.oh;
+  uint32_t iw = (uint32_t)p.iw, ih = (uint32_t)p.ih;
+  const uint32_t ow = (uint32_t)p.ow, oh = (uint32_t)p.oh;
   const uint32_t k = ty * kResampleRows + (uint32_t)wave;  // output row (wave-uniform)
   const uint32_t j = tx * 64 + (uint32_t)lane;             // output column
   if (k >= oh || j >= ow || img >= (uint32_t)p.n_images) return;
+  [[maybe_unused]] int64_t src_offset = 0;
+  if constexpr (CROPS) {  // this image's source
+    const JbCrop &c = crops_of(table...)[img];
+    iw = (uint32_t)c.w, ih = (uint32_t)c.h;
+    src_offset = c.tmp_offset;
+  }
 
   // the footprints on the common grid: products below 65535^2 < 2^32
   const uint32_t r0 = k * ih / oh, r1 = ((k + 1) * ih - 1) / oh;  // source rows r0..r1, wave-uniform
@@ -53,7 +67,7 @@ __global__ __launch_bounds__(64 * kResampleRows) void jb_resample_kernel(const J
   const uint32_t wy0 = min((r0 + 1) * oh, (k + 1) * ih) - k * ih;
   const uint32_t wy1 = (k + 1) * ih - r1 * oh;  // (used when r1 > r0)
 
-  const uint8_t *const src = p.src + (int64_t)img * p.src_image_stride;
+  const uint8_t *const src = p.src + (CROPS ? src_offset : (int64_t)img * p.src_image_stride);
   const int64_t src_row_bytes = 3LL * iw;
   uint64_t acc[3] = {0, 0, 0};
   for (uint32_t r = r0; r <= r1; r++) {
@@ -106,16 +120,43 @@ __global__ __launch_bounds__(64 * kResampleRows) void jb_resample_kernel(const J
   }
 }
 
+// the grid of a launch (tiles_x, tiles_y into p); false: more than 2^31 - 1 workgroups
+static bool resample_grid(JbResample &p, dim3 *grid) {
+  p.tiles_x = (p.ow + 63) / 64;
+  p.tiles_y = (p.oh + kResampleRows - 1) / kResampleRows;
+  const int64_t n_wgs = (int64_t)p.tiles_x * p.tiles_y * p.n_images;
+  if (n_wgs > 0x7fffffffLL) return false;
+  *grid = dim3((unsigned)n_wgs);
+  return true;
+}
+
+hipError_t jbk_resample_launch_crops(const JbResample &q, const JbCropTable &table, int format, hipStream_t stream) {
+  if (format < 0 || format > 3 || q.ow < 1 || q.oh < 1 || q.ow > 65535 || q.oh > 65535 || q.n_images < 1 || q.n_images > kJbCropsPerLaunch)
+    return hipErrorInvalidValue;
+  for (int i = 0; i < q.n_images; i++)
+    if (table.c[i].w < 1 || table.c[i].h < 1 || table.c[i].w > 65535 || table.c[i].h > 65535 || table.c[i].tmp_offset < 0)
+      return hipErrorInvalidValue;
+  JbResample p = q;
+  dim3 grid;
+  if (!resample_grid(p, &grid)) return hipErrorInvalidValue;
+  const dim3 block(64 * kResampleRows);
+  switch (format) {
+    case 0: hipLaunchKernelGGL((jb_resample_kernel<0, true, JbCropTable>), grid, block, 0, stream, p, table); break;
+    case 1: hipLaunchKernelGGL((jb_resample_kernel<1, true, JbCropTable>), grid, block, 0, stream, p, table); break;
+    case 2: hipLaunchKernelGGL((jb_resample_kernel<2, true, JbCropTable>), grid, block, 0, stream, p, table); break;
+    default: hipLaunchKernelGGL((jb_resample_kernel<3, true, JbCropTable>), grid, block, 0, stream, p, table); break;
+  }
+  return hipGetLastError();
+}
+
 hipError_t jbk_resample_launch(const JbResample &q, int format, hipStream_t stream) {
   if (format < 0 || format > 3 || q.iw < 1 || q.ih < 1 || q.ow < 1 || q.oh < 1 || q.iw > 65535 || q.ih > 65535 || q.ow > 65535 ||
       q.oh > 65535 || q.n_images < 1)
     return hipErrorInvalidValue;
   JbResample p = q;
-  p.tiles_x = (q.ow + 63) / 64;
-  p.tiles_y = (q.oh + kResampleRows - 1) / kResampleRows;
-  const int64_t n_wgs = (int64_t)p.tiles_x * p.tiles_y * q.n_images;
-  if (n_wgs > 0x7fffffffLL) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)n_wgs), block(64 * kResampleRows);
+  dim3 grid;
+  if (!resample_grid(p, &grid)) return hipErrorInvalidValue;
+  const dim3 block(64 * kResampleRows);
   switch (format) {
     case 0: hipLaunchKernelGGL(jb_resample_kernel<0>, grid, block, 0, stream, p); break;
     case 1: hipLaunchKernelGGL(jb_resample_kernel<1>, grid, block, 0, stream, p); break;

@@ -117,6 +117,25 @@ int seam_tiles(jb_ctx *ctx, const jb_device_batch *b, const jb_geometry &g, cons
   return JB_OK;
 }
 
+// the launch's pointers, strides and frame fields (everything but the tiling and the store-stage knobs)
+JbLaunch launch_base(const jb_device_batch *b, const jb_geometry &g) {
+  JbLaunch p;
+  memset(&p, 0, sizeof p);
+  p.coef = b->d_coef;
+  p.qtabs = b->d_qtabs;
+  p.rgb = b->d_rgb;
+  p.coef_image_stride = b->coef_image_stride;
+  p.qtab_image_stride = b->qtab_image_stride;
+  p.rgb_image_stride = b->rgb_image_stride;
+  p.rgb_row_stride = b->rgb_row_stride;
+  p.width = b->desc.width;
+  p.height = b->desc.height;
+  p.mcus_x = g.mcus_x;
+  p.mcus_y = g.mcus_y;
+  p.chroma_q_equal = (b->desc.qtab_id[1] == b->desc.qtab_id[2]) ? 1 : 0;
+  return p;
+}
+
 constexpr size_t kTmpSlack = 16;    // bytes behind the last intermediate (jb_resample_kernel reads pixels as 4-byte words)
 constexpr size_t kTmpStreams = 64;  // scratches a context keeps before it lets go of all of them
 
@@ -144,6 +163,90 @@ int tmp_for_stream(jb_ctx *ctx, hipStream_t stream, size_t bytes, void **out) {
   return JB_OK;
 }
 
+// the resample launch of a sub-batch of m images from image i0 on; src: the scratch
+JbResample resample_args(const jb_device_batch *b, const JbOutPlan &plan, int64_t plane_stride, const void *src, int64_t i0, int m) {
+  const int64_t rgb_step = b->n_images > 1 ? b->rgb_image_stride : 0;
+  JbResample q;
+  memset(&q, 0, sizeof q);
+  q.src = (const uint8_t *)src;
+  q.src_image_stride = plan.tmp_image_bytes;
+  q.dst = b->d_rgb + i0 * rgb_step;
+  q.dst_image_stride = rgb_step;
+  q.dst_row_stride = b->rgb_row_stride;
+  q.dst_plane_stride = plane_stride;
+  q.iw = plan.src_w, q.ih = plan.src_h, q.ow = plan.out_w, q.oh = plan.out_h;
+  q.n_images = m;
+  for (int c = 0; c < 3; c++) q.scale[c] = plan.spec.scale[c], q.bias[c] = plan.spec.bias[c];
+  return q;
+}
+
+// 3c. a plan with per-image rectangles (plan.crops) and a target size: as 3b, with the rectangles of a sub-batch in a
+// table that travels in the arguments of both kernels.  Consecutive images are packed into a sub-batch while their
+// intermediates -- back to back, tight, at the prefix sums of 3 * w_i * h_i -- fit the cap of the stream's scratch (an
+// image larger than the cap runs alone) and a table holds them.  The pixel kernel's grid gives every image as many
+// workgroups as the sub-batch's largest rectangle needs; those beyond an image's own count return at once.
+int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn, const jb_geometry &g,
+                      int64_t plane_stride) {
+  if (plan.n_crops != b->n_images) return fail(ctx, JB_ERR_GEOMETRY, "%s: %d rectangles for %d images", fn, plan.n_crops, b->n_images);
+  const int64_t cap = (int64_t)ctx->knobs.resize_tmp_bytes;
+  const auto bytes_of = [&](int64_t i) { return 3LL * plan.crops[i].width * plan.crops[i].height; };
+  // the images of the sub-batch that starts at i0; *bytes: their intermediates
+  const auto pack = [&](int64_t i0, int64_t *bytes) {
+    int m = 1;
+    *bytes = bytes_of(i0);
+    while (i0 + m < b->n_images && m < kJbCropsPerLaunch && *bytes + bytes_of(i0 + m) <= cap) *bytes += bytes_of(i0 + m), m++;
+    return m;
+  };
+  int64_t most = 0;  // the largest sub-batch: what the scratch must hold
+  for (int64_t i0 = 0; i0 < b->n_images;) {
+    int64_t bytes;
+    i0 += pack(i0, &bytes);
+    if (bytes > most) most = bytes;
+  }
+  DeviceGuard guard(ctx->device);
+  const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  void *tmp = nullptr;
+  int rc = tmp_for_stream(ctx, s, (size_t)most + kTmpSlack, &tmp);
+  if (rc) return rc;
+  const int per_tile = jbk_mcus_per_tile(b->desc.hs, b->desc.vs), mw = 8 * b->desc.hs, mh = 8 * b->desc.vs;
+  const int64_t coef_step = b->n_images > 1 ? b->coef_image_stride : 0;
+  for (int64_t i0 = 0; i0 < b->n_images;) {
+    int64_t bytes;
+    const int m = pack(i0, &bytes);
+    JbCropTable table;
+    memset(&table, 0, sizeof table);
+    int32_t most_tiles = 0;
+    int64_t at = 0;
+    for (int j = 0; j < m; j++) {
+      const jb_roi &r = plan.crops[i0 + j];
+      JbCrop &c = table.c[j];
+      c.x = r.x, c.y = r.y, c.w = r.width, c.h = r.height;
+      c.mx = r.x / mw, c.my = r.y / mh;
+      const int mcus_x = (r.x + r.width - 1) / mw - c.mx + 1, mcus_y = (r.y + r.height - 1) / mh - c.my + 1;
+      c.tiles_per_row = (mcus_x + per_tile - 1) / per_tile;
+      c.n_tiles = mcus_y * c.tiles_per_row;  // (at most the whole image's: no overflow)
+      c.tmp_offset = at;
+      at += bytes_of(i0 + j);
+      if (c.n_tiles > most_tiles) most_tiles = c.n_tiles;
+    }
+    jb_device_batch ib = *b;
+    ib.d_coef = (const int16_t *)((const uint8_t *)b->d_coef + i0 * coef_step);
+    ib.coef_image_stride = coef_step;
+    ib.d_qtabs = (const int32_t *)((const uint8_t *)b->d_qtabs + i0 * b->qtab_image_stride);
+    ib.d_rgb = (uint8_t *)tmp;
+    ib.rgb_row_stride = ib.rgb_image_stride = 0;  // (per image: the table's)
+    JbLaunch p = launch_base(&ib, g);
+    p.roi = 2;
+    p.tiles_per_image = most_tiles;
+    p.n_tiles = m * most_tiles;  // (at most 32 images' worth of tiles: no overflow)
+    p.fast_store = 1;            // (the ROI stage does not look at it)
+    JB_HIP(ctx, jbk_launch_crops(p, table, b->desc.hs, b->desc.vs, s));
+    JB_HIP(ctx, jbk_resample_launch_crops(resample_args(b, plan, plane_stride, tmp, i0, m), table, plan.format, s));
+    i0 += m;
+  }
+  return JB_OK;
+}
+
 // 3b. a plan with a target size: two launches per sub-batch, in stream order -- the pixel kernel (full size or the
 // rectangle, interleaved uint8, tight) into the stream's scratch, jb_resample_kernel from there into the caller's buffer
 int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn) {
@@ -151,6 +254,7 @@ int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, con
   int64_t plane_stride = 0;
   int rc = seam_check(ctx, b, plan, fn, &g, &plane_stride);
   if (rc) return rc;
+  if (plan.crops) return seam_launch_crops(ctx, b, stream, plan, fn, g, plane_stride);
   const JbOutPlan inner = jb_out_plan_(&b->desc, 1, nullptr, plan.has_roi ? &plan.roi : nullptr);
   if (inner.status != JB_OK) return fail(ctx, inner.status, "%s: %s", fn, inner.why);
   // whole images per sub-batch: as many as the cap holds, one at the least
@@ -166,7 +270,7 @@ int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, con
   rc = tmp_for_stream(ctx, s, (size_t)(per * plan.tmp_image_bytes) + kTmpSlack, &tmp);
   if (rc) return rc;
   // (the strides between images are checked, and meaningful, only when there is more than one)
-  const int64_t coef_step = b->n_images > 1 ? b->coef_image_stride : 0, rgb_step = b->n_images > 1 ? b->rgb_image_stride : 0;
+  const int64_t coef_step = b->n_images > 1 ? b->coef_image_stride : 0;
   for (int64_t i0 = 0; i0 < b->n_images; i0 += per) {
     const int m = (int)(b->n_images - i0 < per ? b->n_images - i0 : per);
     jb_device_batch ib = *b;
@@ -179,18 +283,7 @@ int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, con
     ib.rgb_image_stride = plan.tmp_image_bytes;
     rc = seam_launch(ctx, &ib, s, inner, fn);
     if (rc) return rc;
-    JbResample q;
-    memset(&q, 0, sizeof q);
-    q.src = (const uint8_t *)tmp;
-    q.src_image_stride = plan.tmp_image_bytes;
-    q.dst = b->d_rgb + i0 * rgb_step;
-    q.dst_image_stride = rgb_step;
-    q.dst_row_stride = b->rgb_row_stride;
-    q.dst_plane_stride = plane_stride;
-    q.iw = plan.src_w, q.ih = plan.src_h, q.ow = plan.out_w, q.oh = plan.out_h;
-    q.n_images = m;
-    for (int c = 0; c < 3; c++) q.scale[c] = plan.spec.scale[c], q.bias[c] = plan.spec.bias[c];
-    JB_HIP(ctx, jbk_resample_launch(q, plan.format, s));
+    JB_HIP(ctx, jbk_resample_launch(resample_args(b, plan, plane_stride, tmp, i0, m), plan.format, s));
   }
   return JB_OK;
 }
@@ -205,20 +298,7 @@ int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOut
   int64_t plane_stride = 0;
   int rc = seam_check(ctx, b, plan, fn, &g, &plane_stride);
   if (rc) return rc;
-  JbLaunch p;
-  memset(&p, 0, sizeof p);
-  p.coef = b->d_coef;
-  p.qtabs = b->d_qtabs;
-  p.rgb = b->d_rgb;
-  p.coef_image_stride = b->coef_image_stride;
-  p.qtab_image_stride = b->qtab_image_stride;
-  p.rgb_image_stride = b->rgb_image_stride;
-  p.rgb_row_stride = b->rgb_row_stride;
-  p.width = b->desc.width;
-  p.height = b->desc.height;
-  p.mcus_x = g.mcus_x;
-  p.mcus_y = g.mcus_y;
-  p.chroma_q_equal = (b->desc.qtab_id[1] == b->desc.qtab_id[2]) ? 1 : 0;
+  JbLaunch p = launch_base(b, g);
   if (plan.planar) {
     p.format = plan.format;
     p.rgb_plane_stride = plane_stride;
@@ -259,6 +339,14 @@ int jb_blocks_to_rgb_device_resized(jb_ctx *ctx, const jb_device_batch *b, const
                                     const jb_output_spec *spec, void *stream) {
   const JbTarget t = {out_w, out_h};
   return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, roi, &t), "jb_blocks_to_rgb_device_resized");
+}
+
+int jb_blocks_to_rgb_device_crops(jb_ctx *ctx, const jb_device_batch *b, const jb_roi *rois, int32_t out_w, int32_t out_h,
+                                  const jb_output_spec *spec, void *stream) {
+  if (ctx && !rois) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_crops: rois is NULL");
+  const JbTarget t = {out_w, out_h};
+  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, nullptr, &t, rois, b ? b->n_images : 0),
+                     "jb_blocks_to_rgb_device_crops");
 }
 
 }  // extern "C"
