@@ -376,6 +376,74 @@ int jb_crops_check(const jb_image_desc *desc, const jb_roi *rois, int n, int32_t
 int jb_blocks_to_rgb_device_crops(jb_ctx *ctx, const jb_device_batch *batch, const jb_roi *rois, int32_t out_w, int32_t out_h,
                                   const jb_output_spec *spec, void *stream);
 
+/* ---- resampling filters: Pillow-exact bilinear and bicubic for the fixed output size and the per-image rectangles ----
+ * The two sections above resize with an exact AREA filter.  A `filter` chooses what gets to the target instead:
+ *
+ *     JB_FILTER_AREA      the arithmetic and the code paths of the two sections above, untouched
+ *     JB_FILTER_BILINEAR  support S = 1:  f(x) = 1 - |x| for |x| < 1, else 0
+ *     JB_FILTER_BICUBIC   support S = 2, a = -0.5, with x = |x|:  ((a + 2) x - (a + 3)) x x + 1 for x < 1,
+ *                         (((x - 5) x + 8) x - 4) a for x < 2, else 0
+ *
+ * and the result is, bit for bit, what Pillow's 8-bit resampling gives: Image.resize((out_w, out_h), BILINEAR / BICUBIC,
+ * box=(x, y, x + w, y + h)) of the full-size decode (what torchvision's antialiased Resize computes on PIL images).
+ * The weights of one axis -- frame extent in_size (the WHOLE image, not the rectangle), rectangle [in0, in1), n outputs --
+ * are computed on IEEE doubles, every operation in exactly this order and none fused:
+ *
+ *     scale = (in1 - in0) / n;   fs = scale < 1.0 ? 1.0 : scale;   sup = S * fs;   inv = 1.0 / fs
+ *     for j in 0..n-1:
+ *         center = in0 + (j + 0.5) * scale
+ *         lo = (int)(center - sup + 0.5);  if lo < 0: lo = 0                  ((int) truncates toward zero)
+ *         hi = (int)(center + sup + 0.5);  if hi > in_size: hi = in_size
+ *         for t in 0..hi-lo-1:  w[t] = f((t + lo - center + 0.5) * inv)
+ *         ww = 0.0;  for t in order: ww += w[t]                               (a SEQUENTIAL sum, in tap order)
+ *         if ww != 0.0:  w[t] = w[t] / ww  for every t
+ *         k[t] = (int)(w[t] * 4194304.0 + 0.5)  if w[t] >= 0  else  (int)(w[t] * 4194304.0 - 0.5)
+ *
+ * With `full` the full-size uint8 decode (W x H) and the rectangle (x, y, w, h) (none: the whole image):
+ *     horizontal, for every frame row r:  T[r][j][c] = clip8((2^21 + sum_t kx_j[t] * full[r][lo_j + t][c]) >> 22)
+ *                                         (columns: in_size = W, in0 = x, in1 = x + w, n = out_w)
+ *     vertical:                      out_u8[k][j][c] = clip8((2^21 + sum_t ky_k[t] * T[lo_k + t][j][c]) >> 22)
+ *                                         (rows: in_size = H, in0 = y, in1 = y + h, n = out_h)
+ * `>>` is the arithmetic shift of a signed 32-bit sum, clip8 clamps to 0..255, and T is rounded to uint8 between the
+ * passes.  Formats 1-3 apply to out_u8 exactly as everywhere else.  What follows from the definition:
+ *   - THE FILTER READS PIXELS OUTSIDE THE RECTANGLE: lo and hi are clamped to the frame, not to the rectangle, so a crop's
+ *     edge pixels depend on their neighbours outside it.  That is Pillow's box=, and it is NOT what cropping first and
+ *     resizing the crop (torchvision's RandomResizedCrop on a tensor) computes.
+ *   - out_w = w, out_h = h reproduces the slice bit for bit under both filters (weights 1 and 0).
+ *   - the order of the ww sum is part of the definition.
+ * The cap: an axis counts floor(2 * sup) + 2 taps (an upper bound of hi - lo), and more than 160 on either axis is
+ * JB_ERR_UNSUPPORTED (jb_last_error names the cap): bicubic reduces up to 39x per axis, bilinear up to 79x.
+ * The source window -- per axis the union of [lo, hi) over all outputs: the rectangle grown by the filter's reach and
+ * clamped to the frame -- is what the pixel kernel writes into the stream's scratch in the rectangle's place; the
+ * intermediates, the sub-batches and JPEGBLK_RESIZE_TMP_BYTES work as in the two sections above with the window's size.
+ * A jb_resize names the target and the filter; out_w = out_h = 0 means "no target size", which only filter 0 goes with.
+ * Refusals, behind those of the sections above and in this order: an unknown filter or reserved != 0 JB_ERR_GEOMETRY; a
+ * filter other than JB_FILTER_AREA without a target size JB_ERR_STATE; the cap JB_ERR_UNSUPPORTED. */
+enum { JB_FILTER_AREA = 0, JB_FILTER_BILINEAR = 1, JB_FILTER_BICUBIC = 2 };
+typedef struct jb_resize {
+  int32_t out_w, out_h; /* the target size */
+  int32_t filter;       /* JB_FILTER_* */
+  int32_t reserved;     /* 0 */
+} jb_resize;
+/* jb_resize_check with a filter: JB_ERR_NULL for a null descriptor or jb_resize; the descriptor's own errors first, then
+ * the rectangle's (NULL: the whole image), the target's, the filter's (above).  Pure host code. */
+int jb_filter_check(const jb_image_desc *desc, const jb_roi *roi, const jb_resize *rs);
+/* The source window of the request (jb_filter_check's statuses first): the pixels of the frame the filter reads.  With
+ * JB_FILTER_AREA the rectangle itself.  Pure host code. */
+int jb_filter_window(const jb_image_desc *desc, const jb_roi *roi, const jb_resize *rs, jb_roi *window);
+/* jb_blocks_to_rgb_device_resized / _crops with rs->filter: everything said there about d_rgb, the strides, the spec
+ * and the rectangles holds.  rs->filter = JB_FILTER_AREA gives exactly what those entry points give.  rs == NULL:
+ * JB_ERR_NULL. */
+int jb_blocks_to_rgb_device_filtered(jb_ctx *ctx, const jb_device_batch *batch, const jb_roi *roi, const jb_resize *rs,
+                                     const jb_output_spec *spec, void *stream);
+int jb_blocks_to_rgb_device_crops_filtered(jb_ctx *ctx, const jb_device_batch *batch, const jb_roi *rois, const jb_resize *rs,
+                                           const jb_output_spec *spec, void *stream);
+/* jb_decode_memory_resized / jb_decode_file_resized with rs->filter. */
+int jb_decode_memory_filtered(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, const jb_roi *roi, const jb_resize *rs,
+                              const jb_output_spec *spec, void **out, int32_t *width, int32_t *height);
+int jb_decode_file_filtered(jb_ctx *ctx, const char *path, const jb_roi *roi, const jb_resize *rs, const jb_output_spec *spec,
+                            void **out, int32_t *width, int32_t *height);
+
 /* ---- host front end ("next" rows of the scope table; reference jpeg.cpp:67-446, 826-907,
  *      include/file.hpp, include/huffman.hpp) --------------------------------------------- */
 /* Parse a JFIF byte stream and Huffman-decode it into packed int16 blocks in the order
@@ -557,6 +625,13 @@ int jb_batch_decoder_run_crops(jb_batch_decoder *dec, const char *const *paths, 
                                int32_t *widths, int32_t *heights, int *statuses, double *times);
 int jb_batch_decoder_submit_crops(jb_batch_decoder *dec, const char *const *paths, int n_paths, const jb_roi *rois, uint8_t **rgb,
                                   int32_t *widths, int32_t *heights, int *statuses, int *ticket);
+/* The filter (JB_FILTER_*; see "resampling filters") of the batch decoder's later runs and submissions: it governs the
+ * target size of jb_batch_decoder_set_resize and the per-image rectangles of _run_crops / _submit_crops alike, and is
+ * kept while no target size is set (there is then nothing to resample).  A file whose reduction exceeds the tap cap gets
+ * the per-image status JB_ERR_UNSUPPORTED and the batch goes on.  Applies to every device of a multi-device decoder and
+ * to both sides of submit / collect.  Refused with JB_ERR_STATE while a batch is in flight, with JB_ERR_GEOMETRY for an
+ * unknown filter. */
+int jb_batch_decoder_set_filter(jb_batch_decoder *dec, int filter);
 /* Output sink replacing the reference's X11 window / unused BMP writer (display.hpp,
  * jpeg.cpp:462-509): binary PPM (P6). */
 int jb_write_ppm(const char *path, const uint8_t *rgb, int32_t width, int32_t height,

@@ -80,6 +80,15 @@ class Roi(ctypes.Structure):
     _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
 
+# resampling filters (jpegblk.h, "resampling filters"): 0 = the exact area resize, the others Pillow's 8-bit resampling
+FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC = 0, 1, 2
+
+
+class Resize(ctypes.Structure):
+    """jb_resize: a target size and the filter that gets there."""
+    _fields_ = [("out_w", ctypes.c_int32), ("out_h", ctypes.c_int32), ("filter", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 def _ref(struct):
     """byref(struct), or None (a NULL pointer) for None."""
     return ctypes.byref(struct) if struct is not None else None
@@ -96,15 +105,20 @@ def _crop_array(crops, n=None):
 
 
 class _Request:
-    """The output request of one call, normalised in this one place.  (scale, fmt, roi, resize, crops) as the caller gave
+    """The output request of one call, normalised in this one place.  (scale, fmt, roi, resize, crops, filter) as the caller gave
     them (fmt: None / a format number / an OutputSpec; roi: None / (x, y, w, h) / a Roi; resize: None / (w, h); crops: None
     / a rectangle per image) become .scale, .spec (OutputSpec or None), .roi (Roi or None), .target ((w, h) or None) and
     .crops (a ctypes array of Roi or None; .n_crops).  A rectangle or a target size together with a scale other than 1 is
     JbError(-9), raised here: no C entry point takes the pair.  So are per-image rectangles with a scale or with roi (two
-    rectangles for one image); without a target size they are JbError(-7): only a target makes the outputs one size."""
+    rectangles for one image); without a target size they are JbError(-7): only a target makes the outputs one size.
+    filter (FILTER_*) becomes .filter; FILTER_AREA asks for nothing new, any other filter without a target size is
+    JbError(-7)."""
 
-    def __init__(self, scale=1, fmt=None, roi=None, resize=None, crops=None):
+    def __init__(self, scale=1, fmt=None, roi=None, resize=None, crops=None, filter=FILTER_AREA):
         self.scale = scale
+        self.filter = int(filter)
+        if self.filter != FILTER_AREA and resize is None:
+            raise JbError(-7, "a resampling filter wants a target size (resize)")
         self.spec = fmt if fmt is None or isinstance(fmt, OutputSpec) else OutputSpec.make(fmt)
         if roi is not None and scale != 1:
             raise JbError(-9, "a rectangle (roi) cannot be combined with a scale")
@@ -130,6 +144,11 @@ class _Request:
         """-> (route, the arguments the route's entry points take between their family's own and their outputs).  The
         route names the variant of an entry point that takes this request (_ROUTES has the symbols).  A planar format
         with a scale has none, JbError(-9); format 0 with a scale is the scaled route, which takes no spec."""
+        if self.filter != FILTER_AREA:   # (always with a target size)
+            rs = ctypes.byref(Resize(self.target[0], self.target[1], self.filter, 0))
+            if self.crops is not None:
+                return "crops_filtered", (self.crops, rs, _ref(self.spec))
+            return "filtered", (_ref(self.roi), rs, _ref(self.spec))
         if self.crops is not None:
             return "crops", (self.crops, self.target[0], self.target[1], _ref(self.spec))
         if self.target is not None:
@@ -152,7 +171,10 @@ _ROUTES = {"plain": ("jb_decode_file", "jb_decode_memory", "jb_blocks_to_rgb_dev
            "roi": ("jb_decode_file_roi", "jb_decode_memory_roi", "jb_blocks_to_rgb_device_roi"),
            "resized": ("jb_decode_file_resized", "jb_decode_memory_resized", "jb_blocks_to_rgb_device_resized"),
            # (the device family alone: decode(path) and decode(bytes) handle one image, and have roi=)
-           "crops": (None, None, "jb_blocks_to_rgb_device_crops")}
+           "crops": (None, None, "jb_blocks_to_rgb_device_crops"),
+           # a filter other than FILTER_AREA (FILTER_AREA takes the two routes above)
+           "filtered": ("jb_decode_file_filtered", "jb_decode_memory_filtered", "jb_blocks_to_rgb_device_filtered"),
+           "crops_filtered": (None, None, "jb_blocks_to_rgb_device_crops_filtered")}
 
 
 def roi_check(desc, roi):
@@ -176,6 +198,25 @@ def crops_check(desc, crops, resize):
     rc = lib().jb_crops_check(ctypes.byref(desc), q.crops, q.n_crops, q.target[0], q.target[1], ctypes.byref(bad))
     if rc != JB_OK:
         raise JbError(rc, f"rectangle {bad.value} does not lie in the image" if bad.value >= 0 else "bad target size or descriptor")
+
+
+def _resize_struct(resize, filter):
+    w, h = resize if resize is not None else (0, 0)
+    return Resize(int(w), int(h), int(filter), 0)
+
+
+def filter_check(desc, resize, filter, roi=None):
+    """jb_filter_check: resize_check, and can `filter` take the rectangle (None: the whole image) to the target size
+    (w, h)?  Raises JbError otherwise (-2 unknown filter, -7 no target size, -9 more taps than the kernel's cap)."""
+    _check(lib().jb_filter_check(ctypes.byref(desc), _ref(_Request(roi=roi).roi), ctypes.byref(_resize_struct(resize, filter))))
+
+
+def filter_window(desc, resize, filter, roi=None):
+    """jb_filter_window: -> (x, y, w, h), the pixels of the frame the filter reads for this request: the rectangle grown
+    by the filter's reach, clamped to the frame."""
+    win = Roi()
+    _check(lib().jb_filter_window(ctypes.byref(desc), _ref(_Request(roi=roi).roi), ctypes.byref(_resize_struct(resize, filter)), ctypes.byref(win)))
+    return win.x, win.y, win.width, win.height
 
 
 def _shape_output(ptr, w, h, spec):
@@ -308,6 +349,14 @@ def lib():
     L.jb_blocks_to_rgb_device_crops.argtypes = [vp, ctypes.POINTER(DeviceBatch), pr, i32, i32, ps, vp]
     L.jb_batch_decoder_run_crops.argtypes = L.jb_batch_decoder_run.argtypes[:3] + [pr] + L.jb_batch_decoder_run.argtypes[3:]
     L.jb_batch_decoder_submit_crops.argtypes = L.jb_batch_decoder_submit.argtypes[:3] + [pr] + L.jb_batch_decoder_submit.argtypes[3:]
+    prs = ctypes.POINTER(Resize)
+    L.jb_filter_check.argtypes = [pd, pr, prs]
+    L.jb_filter_window.argtypes = [pd, pr, prs, pr]
+    L.jb_blocks_to_rgb_device_filtered.argtypes = [vp, ctypes.POINTER(DeviceBatch), pr, prs, ps, vp]
+    L.jb_blocks_to_rgb_device_crops_filtered.argtypes = [vp, ctypes.POINTER(DeviceBatch), pr, prs, ps, vp]
+    L.jb_decode_memory_filtered.argtypes = [vp, vp, ctypes.c_size_t, pr, prs, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.jb_decode_file_filtered.argtypes = [vp, ctypes.c_char_p, pr, prs, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.jb_batch_decoder_set_filter.argtypes = [vp, ctypes.c_int]
     L.jb_write_ppm.argtypes = [ctypes.c_char_p, vp, i32, i32, i64]
     L.jb_write_bmp.argtypes = [ctypes.c_char_p, vp, i32, i32, i64]
     if L.jb_abi_version() != 1:
@@ -481,7 +530,7 @@ class Context:
         _check(lib().jb_wait(self._h, ticket), self._h)
 
     # -- the seam, device buffers ------------------------------------------------------------
-    def blocks_to_rgb_device(self, batch, stream=None, scale=1, fmt=None, roi=None, resize=None, crops=None):
+    def blocks_to_rgb_device(self, batch, stream=None, scale=1, fmt=None, roi=None, resize=None, crops=None, filter=FILTER_AREA):
         """scale 2, 4, 8: the batch's d_rgb and strides describe images of scaled_size(desc.width, desc.height, scale).
         fmt (an OutputSpec or a format number): planar output -- the batch's rgb_row_stride is then a plane's.
         roi=(x, y, w, h) (with any fmt, not with a scale): the batch's d_rgb and strides describe images of w x h, the
@@ -490,8 +539,10 @@ class Context:
         of w x h, the exact area resize of every image (or of its rectangle).
         crops=[(x, y, w, h), ...] with resize=(w, h) (with any fmt, not with roi or a scale): one rectangle per image of the
         batch, each resized to w x h (jb_blocks_to_rgb_device_crops); the list is read before the call returns.
+        filter=FILTER_BILINEAR / FILTER_BICUBIC with resize= (with or without roi or crops): Pillow's 8-bit resampling in
+        the area filter's place (jb_blocks_to_rgb_device_filtered / _crops_filtered).
         Each is the entry point of that suffix (_ROUTES)."""
-        request = _Request(scale, fmt, roi, resize, crops)
+        request = _Request(scale, fmt, roi, resize, crops, filter)
         if request.crops is not None and request.n_crops != batch.n_images:
             raise JbError(-2, f"{request.n_crops} rectangles (crops) for {batch.n_images} images")
         route, tail = request.routed()
@@ -509,19 +560,20 @@ class Context:
         finally:
             lib().jb_free(p)
 
-    def decode_file(self, path, scale=1, fmt=None, roi=None, resize=None):
+    def decode_file(self, path, scale=1, fmt=None, roi=None, resize=None, filter=FILTER_AREA):
         """-> RGB [H, W, 3]; scale 2, 4, 8: the area-reduced image; fmt (OutputSpec or format number): [3, H, W] in the
         format's type for the planar formats; roi=(x, y, w, h) (with any fmt, not with a scale): that rectangle of the
-        image; resize=(w, h) (with any fmt, with or without roi, not with a scale): the image, or its rectangle, at w x h.
+        image; resize=(w, h) (with any fmt, with or without roi, not with a scale): the image, or its rectangle, at w x h;
+        filter (with resize): FILTER_AREA, or FILTER_BILINEAR / FILTER_BICUBIC for Pillow's 8-bit resampling.
         Each is jb_decode_file's variant of that suffix (_ROUTES)."""
-        request = _Request(scale, fmt, roi, resize)
+        request = _Request(scale, fmt, roi, resize, filter=filter)
         return self._decode(_FILE, (os.fsencode(path),), request)
 
-    def decode_memory(self, jpeg_bytes, scale=1, fmt=None, roi=None, resize=None):
-        """jb_decode_memory: a JFIF byte string -> RGB [H, W, 3] (front end + device seam); scale, fmt, roi, resize: as
-        decode_file."""
+    def decode_memory(self, jpeg_bytes, scale=1, fmt=None, roi=None, resize=None, filter=FILTER_AREA):
+        """jb_decode_memory: a JFIF byte string -> RGB [H, W, 3] (front end + device seam); scale, fmt, roi, resize,
+        filter: as decode_file."""
         buf = np.frombuffer(jpeg_bytes, dtype=np.uint8)
-        return self._decode(_MEMORY, (_ptr(buf), buf.size), _Request(scale, fmt, roi, resize))
+        return self._decode(_MEMORY, (_ptr(buf), buf.size), _Request(scale, fmt, roi, resize, filter=filter))
 
 
 def _batch_args(paths):
@@ -571,11 +623,13 @@ class BatchDecoder:
     roi=(x, y, w, h) (jb_batch_decoder_set_roi; with any fmt, not with a scale): every image comes out as that rectangle of
     itself, so files of different sizes give outputs of one size.  resize=(w, h) (jb_batch_decoder_set_resize; with any
     fmt, with or without roi, not with a scale): every image, or its rectangle, comes out at w x h, an exact area resize
-    on the device, so files of any size and layout give outputs of one size."""
+    on the device, so files of any size and layout give outputs of one size.  filter (jb_batch_decoder_set_filter; with
+    resize): FILTER_BILINEAR / FILTER_BICUBIC put Pillow's 8-bit resampling in the area filter's place, for the target
+    size and for the per-image rectangles of run(crops=) alike."""
 
     def __init__(self, n_threads=8, device=0, max_coef_bytes=0, max_rgb_bytes=0, arena_bytes=0, devices=None, scale=1, fmt=None,
-                 roi=None, resize=None):
-        _Request(scale, fmt, roi, resize)   # (roi or resize with a scale: JbError(-9) before anything is created)
+                 roi=None, resize=None, filter=FILTER_AREA):
+        _Request(scale, fmt, roi, resize, filter=filter)   # (roi or resize with a scale: JbError(-9) before anything is created)
         self._h = ctypes.c_void_p()
         if devices is not None:
             ids = (ctypes.c_int * len(devices))(*devices)
@@ -599,6 +653,8 @@ class BatchDecoder:
                 self.set_roi(roi)
             if resize is not None:
                 self.set_resize(resize)
+            if filter != FILTER_AREA:
+                self.set_filter(filter)
         except JbError:
             self.close()
             raise
@@ -621,6 +677,12 @@ class BatchDecoder:
         (0, 0): the images' own sizes again (JbError -7 while a batch is in flight, -9 when the decoder's scale is not 1)."""
         w, h = _Request(resize=resize).target or (0, 0)
         _check(lib().jb_batch_decoder_set_resize(self._h, w, h))
+
+    def set_filter(self, filter):
+        """jb_batch_decoder_set_filter: the resampling filter (FILTER_*) of later runs and submissions, for the target size
+        and for per-image rectangles alike; kept, and idle, while no target size is set (JbError -7 while a batch is in
+        flight, -2 for an unknown filter)."""
+        _check(lib().jb_batch_decoder_set_filter(self._h, int(filter)))
 
     def set_scale(self, scale):
         """jb_batch_decoder_set_scale: output at 1/scale for later runs and submissions (JbError -7 while a batch
@@ -776,7 +838,7 @@ def decode_batch(paths, n_threads=8, device=0, keep_pixels=True, on_image=None, 
 
 
 def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, shared_qtabs=True, scale=1, fmt=None, roi=None,
-                resize=None):
+                resize=None, filter=FILTER_AREA):
     """DeviceBatch over torch CUDA tensors (plumbing): coef_t int16 [n_images, n_blocks, 64],
     qtabs_t int32 [3,64] (shared) or [n_images,3,64], rgb_t uint8 [n_images, H, row_stride].
     scale 2, 4, 8: rgb_t holds the reduced images, [n_images, ceil(H/scale), row_stride], for
@@ -787,8 +849,8 @@ def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, sha
     roi=(x, y, w, h) (for Context.blocks_to_rgb_device(..., roi=), with any fmt, not with a scale): rgb_t holds images of
     the rectangle's size, w x h, instead of desc's.
     resize=(w, h) (for Context.blocks_to_rgb_device(..., resize=), with any fmt and roi, not with a scale): rgb_t holds
-    images of w x h."""
-    q = _Request(scale, fmt, roi, resize)
+    images of w x h; filter (for Context.blocks_to_rgb_device(..., filter=)) changes no size."""
+    q = _Request(scale, fmt, roi, resize, filter=filter)
     out_w, out_h = q.target if q.target is not None else (q.roi.width, q.roi.height) if q.roi is not None else (desc.width, desc.height)
     if q.spec is not None and q.spec.format != FMT_RGB_U8_HWC:
         assert scale == 1, "an output format cannot be combined with a scale"

@@ -40,14 +40,16 @@ struct OutputRequest {
   jb_roi roi = {};
   const jb_roi *roi_ptr() const { return has_roi ? &roi : nullptr; }
   bool has_resize = false;   // one output size for every image
-  JbTarget target = {};
+  JbTarget target = {};      // (target.filter: always the decoder's filter, with or without a target size)
   const JbTarget *target_ptr() const { return has_resize ? &target : nullptr; }
   // can it be had at all?  The plan function decides (jb_plan.h), here for an image of one pixel -- with a rectangle,
   // for the largest frame there is (JB_ERR_GEOMETRY: no frame holds the rectangle)
   int status() const {
     const int32_t n = has_roi ? 65535 : 1;
     const jb_image_desc one = {n, n, 1, 1, {0, 0, 0}, 0};
-    return jb_out_plan_(&one, scale, &spec, roi_ptr(), target_ptr()).status;
+    JbTarget sized = target;  // (without the filter: its tap cap is a matter of every file's own frame)
+    sized.filter = 0;
+    return jb_out_plan_(&one, scale, &spec, roi_ptr(), has_resize ? &sized : nullptr).status;
   }
 };
 
@@ -1412,11 +1414,25 @@ extern "C" int jb_batch_decoder_set_resize(jb_batch_decoder *d, int32_t out_w, i
   if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_resize: batches are in flight (collect them first)");
   OutputRequest out = d->out;
   out.has_resize = !(out_w == 0 && out_h == 0);
-  out.target = out.has_resize ? JbTarget{out_w, out_h} : JbTarget{};
+  out.target = out.has_resize ? JbTarget{out_w, out_h, d->out.target.filter, 0} : JbTarget{0, 0, d->out.target.filter, 0};
   const int st = out.status();
   if (st == JB_ERR_UNSUPPORTED)
     return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_resize: the decoder's scale is not 1: a target size cannot be combined with it");
   if (st != JB_OK) return jb_fail_(nullptr, st, "jb_batch_decoder_set_resize: the target size is outside 1..65535");
+  set_output_all(d, out);
+  return JB_OK;
+}
+
+extern "C" int jb_batch_decoder_set_filter(jb_batch_decoder *d, int filter) {
+  if (!d) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_set_filter: decoder is NULL");
+  if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_filter: batches are in flight (collect them first)");
+  // the plan function decides what a filter is: here with a target of one pixel
+  const jb_image_desc one = {1, 1, 1, 1, {0, 0, 0}, 0};
+  const JbTarget probe = {1, 1, filter, 0};
+  if (jb_out_plan_(&one, 1, nullptr, nullptr, &probe).status != JB_OK)
+    return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_set_filter: unknown resampling filter");
+  OutputRequest out = d->out;
+  out.target.filter = filter;
   set_output_all(d, out);
   return JB_OK;
 }

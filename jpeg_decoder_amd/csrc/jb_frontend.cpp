@@ -556,6 +556,18 @@ int jb_decode_memory_resized(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes
   return decode_memory_impl(ctx, jpeg, jpeg_bytes, 1, spec, (uint8_t **)out, width, height, roi, &t);
 }
 
+// the same with a resampling filter ("resampling filters", include/jpegblk.h)
+int jb_decode_memory_filtered(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, const jb_roi *roi, const jb_resize *rs,
+                              const jb_output_spec *spec, void **out, int32_t *width, int32_t *height) {
+  if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_memory_filtered: ctx is NULL");
+  if (!out || !rs) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_memory_filtered: NULL pointer");
+  *out = nullptr;
+  if (spec && jb_tight_spec_check_(spec) != JB_OK)
+    return jb_fail_(ctx, JB_ERR_GEOMETRY, "jb_decode_memory_filtered" JB_TIGHT_SPEC_TEXT);
+  const JbTarget t = {rs->out_w, rs->out_h, rs->filter, rs->reserved};
+  return decode_memory_impl(ctx, jpeg, jpeg_bytes, 1, spec, (uint8_t **)out, width, height, roi, &t);
+}
+
 // the file's bytes; fn: the entry point's name, for the error text
 static int read_file(jb_ctx *ctx, const char *fn, const char *path, std::vector<uint8_t> &buf) {
   if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, (std::string(fn) + ": ctx is NULL").c_str());
@@ -598,6 +610,15 @@ int jb_decode_file_resized(jb_ctx *ctx, const char *path, const jb_roi *roi, int
   std::vector<uint8_t> buf;
   const int rc = read_file(ctx, "jb_decode_file_resized", path, buf);
   return rc ? rc : jb_decode_memory_resized(ctx, buf.data(), buf.size(), roi, out_w, out_h, spec, out, width, height);
+}
+
+int jb_decode_file_filtered(jb_ctx *ctx, const char *path, const jb_roi *roi, const jb_resize *rs, const jb_output_spec *spec,
+                            void **out, int32_t *width, int32_t *height) {
+  if (ctx && (!out || !rs)) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_file_filtered: NULL pointer");
+  if (ctx) *out = nullptr;
+  std::vector<uint8_t> buf;
+  const int rc = read_file(ctx, "jb_decode_file_filtered", path, buf);
+  return rc ? rc : jb_decode_memory_filtered(ctx, buf.data(), buf.size(), roi, rs, spec, out, width, height);
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "../../include/jpegblk.h"
+#include "jb_filter.h"
 #include "jb_plan.h"
 
 extern "C" {
@@ -113,6 +114,24 @@ int jb_crops_check(const jb_image_desc *d, const jb_roi *rois, int n, int32_t ou
   return plan.status;
 }
 
+int jb_filter_check(const jb_image_desc *d, const jb_roi *roi, const jb_resize *rs) {
+  if (!d || !rs) return JB_ERR_NULL;
+  jb_geometry g;
+  const int rc = jb_geometry_of(d, &g);
+  if (rc != JB_OK) return rc;
+  const JbTarget t = {rs->out_w, rs->out_h, rs->filter, rs->reserved};
+  return jb_out_plan_(d, 1, nullptr, roi, &t).status;  // the rectangle, the target, then the filter
+}
+
+int jb_filter_window(const jb_image_desc *d, const jb_roi *roi, const jb_resize *rs, jb_roi *window) {
+  if (!window) return JB_ERR_NULL;
+  const int rc = jb_filter_check(d, roi, rs);
+  if (rc != JB_OK) return rc;
+  const jb_roi whole = {0, 0, d->width, d->height};
+  *window = rs->filter == JB_FILTER_AREA ? (roi ? *roi : whole) : jb_filter_window_of_(d, roi, rs->out_w, rs->out_h, rs->filter);
+  return JB_OK;
+}
+
 int jb_resolve_qtabs(const jb_image_desc *d, const uint16_t *qtabs, int32_t *out192) {
   if (!d || !qtabs || !out192) return JB_ERR_NULL;
   for (int c = 0; c < 3; c++) {
@@ -124,6 +143,15 @@ int jb_resolve_qtabs(const jb_image_desc *d, const uint16_t *qtabs, int32_t *out
 }
 
 }  // extern "C"
+
+jb_roi jb_filter_window_of_(const jb_image_desc *d, const jb_roi *roi, int32_t out_w, int32_t out_h, int filter) {
+  const jb_roi whole = {0, 0, d->width, d->height};
+  const jb_roi &r = roi ? *roi : whole;
+  int x0, x1, y0, y1;
+  jb_filter_span(jb_filter_axis(filter, d->width, r.x, r.x + r.width, out_w), out_w, &x0, &x1);
+  jb_filter_span(jb_filter_axis(filter, d->height, r.y, r.y + r.height, out_h), out_h, &y0, &y1);
+  return jb_roi{x0, y0, x1 - x0, y1 - y0};
+}
 
 // jb_plan.h: the only place that turns (frame, scale, spec, rectangle, target) into the output's sizes and strides
 JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *spec, const jb_roi *roi, const JbTarget *target,
@@ -176,16 +204,42 @@ JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *
     out_w = out_h = 0;  // (the source size is per image)
   }
   if (target) {
-    if (target->w < 1 || target->h < 1 || target->w > 65535 || target->h > 65535) {
+    auto refuse_target = [&](int status, const char *why) {
       p.has_roi = false, p.roi = jb_roi{};
-      return refuse(JB_ERR_GEOMETRY, "the target size is outside 1..65535");
-    }
-    if (scale != 1) {
-      p.has_roi = false, p.roi = jb_roi{};
-      return refuse(JB_ERR_UNSUPPORTED, "a target size cannot be combined with a scale");
+      return refuse(status, why);
+    };
+    const bool no_target = target->w == 0 && target->h == 0 && target->filter != 0;  // "a filter and no target size"
+    if (!no_target && (target->w < 1 || target->h < 1 || target->w > 65535 || target->h > 65535))
+      return refuse_target(JB_ERR_GEOMETRY, "the target size is outside 1..65535");
+    if (scale != 1) return refuse_target(JB_ERR_UNSUPPORTED, "a target size cannot be combined with a scale");
+    if (target->filter < JB_FILTER_AREA || target->filter > JB_FILTER_BICUBIC || target->reserved != 0)
+      return refuse_target(JB_ERR_GEOMETRY, "unknown resampling filter (or reserved is not 0)");
+    if (no_target) return refuse_target(JB_ERR_STATE, "a resampling filter wants a target size");
+    if (target->filter != JB_FILTER_AREA) {
+      // the taps of both axes against the kernel's cap, for the one rectangle or for every image's
+      const jb_roi whole = {0, 0, d->width, d->height};
+      const jb_roi *rects = crops ? crops : roi ? roi : &whole;
+      const int n_rects = crops ? n_crops : 1;
+      for (int i = 0; i < n_rects; i++) {
+        const jb_roi &r = rects[i];
+        const int tx = jb_filter_taps(jb_filter_axis(target->filter, d->width, r.x, r.x + r.width, target->w));
+        const int ty = jb_filter_taps(jb_filter_axis(target->filter, d->height, r.y, r.y + r.height, target->h));
+        if (tx > kJbFilterMaxTaps || ty > kJbFilterMaxTaps) {
+          static thread_local char text[192];
+          snprintf(text, sizeof text, "the reduction of the %d x %d rectangle to %d x %d wants %d x %d filter taps: more than the cap of %d per axis",
+                   r.width, r.height, target->w, target->h, tx, ty, kJbFilterMaxTaps);
+          if (crops) p.bad_crop = i;
+          return refuse_target(JB_ERR_UNSUPPORTED, text);
+        }
+      }
+      p.filter = target->filter;
     }
     p.has_resize = true;
     if (crops) p.crops = crops, p.n_crops = n_crops;
+    if (p.filter != JB_FILTER_AREA && !crops) {
+      p.window = jb_filter_window_of_(d, roi, target->w, target->h, p.filter);
+      out_w = p.window.width, out_h = p.window.height;
+    }
     p.src_w = out_w, p.src_h = out_h;
     p.tmp_image_bytes = 3LL * out_w * out_h;
     out_w = target->w, out_h = target->h;

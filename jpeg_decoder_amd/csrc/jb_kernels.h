@@ -96,6 +96,33 @@ hipError_t jbk_resample_launch(const JbResample &p, int format, hipStream_t stre
 // p.ih and p.src_image_stride are not looked at); at most kJbCropsPerLaunch images
 hipError_t jbk_resample_launch_crops(const JbResample &p, const JbCropTable &table, int format, hipStream_t stream);
 
+// "Resampling filters" (jb_resample.hip jb_filter_kernel): one image's geometry -- the rectangle the outputs map to, and
+// the window of the frame that lies in the scratch (jb_filter_window: tight interleaved uint8, win_w x win_h).  A
+// JbCrop row has no room for both, so the filtered kernels have a table type of their own: 40 bytes a row, 32 rows and
+// JbFilter together 1.4 KB of the 4 KB argument segment.
+struct JbFilterRow {
+  int32_t x, y, w, h;                  // the rectangle, in pixels of the full-size image
+  int32_t win_x, win_y, win_w, win_h;  // the window, in pixels of the full-size image
+  int64_t tmp_offset;                  // bytes from the scratch's base to the window's pixels (the table's rows only)
+};
+struct JbFilterTable {
+  JbFilterRow r[kJbCropsPerLaunch];
+};
+// base: as for jbk_resample_launch (iw, ih are not looked at; without a table image i's window is at base.src + i *
+// base.src_image_stride).  one: the geometry of every image of a launch without a table.
+struct JbFilter {
+  JbResample base;
+  JbFilterRow one;
+  int32_t frame_w, frame_h;  // the full-size image: what the filter's bounds are clamped to
+  int32_t tx_cap, ty_cap;    // (set by the launch) the taps the LDS weight tables hold per column / row
+  int32_t t_rows;            // (set by the launch) the rows of horizontally filtered pixels LDS holds at a time
+};
+// filter: JB_FILTER_BILINEAR / _BICUBIC.  One workgroup per 64 columns x 8 rows of one image's output.  Every window
+// must be jb_filter_window of its rectangle and p.base.ow x oh, and the taps within kJbFilterMaxTaps (the plan's checks).
+hipError_t jbk_filter_launch(const JbFilter &p, int filter, int format, hipStream_t stream);
+// the same with a geometry per image (p.one is not looked at); at most kJbCropsPerLaunch images
+hipError_t jbk_filter_launch_crops(const JbFilter &p, const JbFilterTable &table, int filter, int format, hipStream_t stream);
+
 // Device-side entropy decoder (jb_huff.hip); structures in jb_huff.h.
 struct JbHuffLaunch;
 hipError_t jbk_huff_launch(const JbHuffLaunch &p, hipStream_t stream);

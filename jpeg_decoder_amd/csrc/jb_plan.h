@@ -12,7 +12,9 @@ struct JbOutPlan {
   // rectangle with a scale other than 1), JB_ERR_GEOMETRY (a target size outside 1..65535), JB_ERR_UNSUPPORTED (a target
   // size with a scale other than 1) -- in that order; with per-image rectangles, JB_ERR_GEOMETRY for the first of them
   // that does not lie in the image (bad_crop: its index) in the single rectangle's place, and JB_ERR_STATE for what is
-  // no composition: no target size, or a launch-wide rectangle as well.  Whoever uses a plan reports it where the old code checked the
+  // no composition: no target size, or a launch-wide rectangle as well.  Behind all of these, "resampling filters":
+  // JB_ERR_GEOMETRY (an unknown filter, or the target's reserved != 0), JB_ERR_STATE (a filter other than 0 without a
+  // target size), JB_ERR_UNSUPPORTED (more than kJbFilterMaxTaps taps on an axis; bad_crop with per-image rectangles).  Whoever uses a plan reports it where the old code checked the
   // scale: behind the descriptor's own errors.  `why` is the text for jb_last_error (of the last plan this thread made,
   // when it names sizes); the other fields are 0 on failure.
   int status;
@@ -33,6 +35,13 @@ struct JbOutPlan {
   bool has_resize;
   int32_t src_w, src_h;
   int64_t tmp_image_bytes;  // 3 * src_w * src_h
+  // "resampling filters" (include/jpegblk.h): filter != JB_FILTER_AREA makes the output the Pillow-exact bilinear /
+  // bicubic resize of the rectangle (has_roi: roi; else the whole frame) to out_w x out_h.  The filter reads beyond the
+  // rectangle, so the pixel kernel writes `window` -- jb_filter_window: the rectangle grown by the filter's reach, clamped
+  // to the frame -- and src_w, src_h, tmp_image_bytes are the WINDOW's.  With per-image rectangles the windows are per
+  // image too (jb_filter_window_of_) and all four are 0.  filter 0: window is all 0.
+  int32_t filter;
+  jb_roi window;
   // "per-image rectangles" (include/jpegblk.h): image i of the launch is the rectangle crops[i] of its full-size decode,
   // resized to the target -- has_resize is set, has_roi is not, src_w / src_h / tmp_image_bytes are 0: the intermediate
   // of image i is 3 * crops[i].width * crops[i].height bytes.  BORROWED: the array is the caller's, and is read before
@@ -42,9 +51,12 @@ struct JbOutPlan {
   int32_t bad_crop;  // status == JB_ERR_GEOMETRY because of a rectangle: which one; else -1
 };
 
-// a target size for jb_out_plan_
+// a target size for jb_out_plan_, and the filter that gets there (JB_FILTER_*; 0: the exact area resize).  w = h = 0 with
+// a filter other than 0 says "a filter and no target": what the plan refuses with JB_ERR_STATE.
 struct JbTarget {
   int32_t w, h;
+  int32_t filter;
+  int32_t reserved;
 };
 
 // spec: null or format 0 = interleaved uint8.  Beyond `reserved` on a format-0 spec, the spec's own fields (plane_stride
@@ -52,5 +64,8 @@ struct JbTarget {
 // roi: null = the whole image.  target: null = the size of the image (at the scale) or of the rectangle.
 // crops: null = none; else n_crops rectangles, one per image of the launch (n_crops < 1: nothing to check); wants a target
 // and no roi.
+// the source window of one rectangle (null: the whole frame) under a plan's filter and target: what jb_filter_window
+// returns, without its checks (the plan has made them)
+jb_roi jb_filter_window_of_(const jb_image_desc *desc, const jb_roi *roi, int32_t out_w, int32_t out_h, int filter);
 JbOutPlan jb_out_plan_(const jb_image_desc *desc, int scale, const jb_output_spec *spec, const jb_roi *roi = nullptr,
                        const JbTarget *target = nullptr, const jb_roi *crops = nullptr, int n_crops = 0);

@@ -165,3 +165,251 @@ hipError_t jbk_resample_launch(const JbResample &q, int format, hipStream_t stre
   }
   return hipGetLastError();
 }
+
+// ---- "resampling filters" (include/jpegblk.h): Pillow's 8-bit bilinear / bicubic resampling, bit for bit ----------------
+// Pillow's two passes inside one workgroup.  A workgroup owns 64 output columns x kFilterRows output rows of one image:
+//   1. the integer weights of its 64 columns (wave 0, one lane per column) and of its rows (wave 1, one lane per row), in
+//      fp64 with jb_filter.h's arithmetic -- each lane loops over its taps in order, so the ww sum is the sequential one
+//      -- into LDS.  The column table is tap-major, kx[t][lane]: a wave's read of tap t is 64 consecutive words, no bank
+//      conflict; the row table is read wave-uniformly (a broadcast).
+//   2. the horizontal pass for every source row the rows' vertical footprints span, the rows dealt round-robin to the
+//      four waves: a lane = an output column, a pixel = ONE 4-byte load as in jb_resample_kernel (four in flight), through
+//      a descriptor of the source row whose range keeps every load inside the scratch; T (rounded to uint8, as Pillow
+//      rounds between the passes) goes to LDS as one word per pixel, T[row][lane]: conflict-free again.
+//   3. one barrier, then the vertical pass out of LDS: a wave = output rows wave and wave + 4, so the row, its bounds and
+//      its weights stay wave-uniform; the store is jb_resample_kernel's.
+// kFilterRows = 8: the span of source rows is (8 - 1) * scale + taps, so per output row 1080 -> 224 bilinear filters
+// 5.6 source rows where the ideal (infinitely many rows per workgroup) is 4.8 and 4 rows per workgroup would be 6.4; 16
+// rows would double T and the accumulators for the last 8 %.  When the span is longer than the T rows that fit LDS
+// (q.t_rows; long bicubic reductions only) the passes 2 and 3 run chunk by chunk of t_rows source rows, the vertical sums
+// staying in registers: T[r] is complete after pass 2 whatever the chunking, and integer addition is associative.
+#include "jb_filter.h"
+
+static constexpr int kFilterRows = 8;
+static constexpr int kFilterLdsBytes = 64 << 10;  // what one workgroup may have
+
+static __device__ __forceinline__ const JbFilterRow *rows_of(const JbFilterTable &table) { return table.r; }
+static __device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+
+// one lane's weights of output `i` of axis `a` (i < n: else none) into tab[t * stride], t < taps, zero behind its own
+// taps; -> its first source sample (`none` without an output); *count: its taps
+static __device__ __forceinline__ int filter_weights(const JbFilterAxis &a, int i, int n, int taps, int none, int32_t *tab, int stride,
+                                                     int *count) {
+  double center = 0.0;
+  int lo = none, m = 0;
+  if (i < n) {
+    int hi;
+    jb_filter_bounds(a, i, &center, &lo, &hi);
+    m = min(hi - lo, taps);
+  }
+  double ww = 0.0;
+  for (int t = 0; t < m; t++) ww += jb_filter_weight(a, lo, center, t);
+  for (int t = 0; t < taps; t++) {
+    int32_t k = 0;
+    if (t < m) {
+      double w = jb_filter_weight(a, lo, center, t);
+      if (ww != 0.0) w = w / ww;
+      k = jb_filter_fixed(w);
+    }
+    tab[t * stride] = k;
+  }
+  *count = m;
+  return lo;
+}
+
+template <int FILTER, int FORMAT, bool CROPS = false, typename... TABLE>
+__global__ __launch_bounds__(256) void jb_filter_kernel(const JbFilter q, const TABLE... table) {
+  static_assert(sizeof...(TABLE) == (CROPS ? 1 : 0), "the table is the second argument of the CROPS instantiations alone");
+  extern __shared__ int32_t filter_lds[];
+  const JbResample &p = q.base;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = (int)(threadIdx.x & 63);
+  const uint32_t b = blockIdx.x;
+  const uint32_t tx = b % (uint32_t)p.tiles_x, t = b / (uint32_t)p.tiles_x;
+  const uint32_t ty = t % (uint32_t)p.tiles_y, img = t / (uint32_t)p.tiles_y;
+  if (img >= (uint32_t)p.n_images) return;  // (the whole workgroup)
+  JbFilterRow g = q.one;
+  int64_t src_offset = (int64_t)img * p.src_image_stride;
+  if constexpr (CROPS) {  // this image's geometry: scalar loads, wave-uniform
+    g = rows_of(table...)[img];
+    src_offset = g.tmp_offset;
+  }
+  const int ow = p.ow, oh = p.oh;
+  const JbFilterAxis ax = jb_filter_axis(FILTER, q.frame_w, g.x, g.x + g.w, ow);
+  const JbFilterAxis ay = jb_filter_axis(FILTER, q.frame_h, g.y, g.y + g.h, oh);
+  const int taps_x = min(jb_filter_taps(ax), q.tx_cap), taps_y = min(jb_filter_taps(ay), q.ty_cap);
+
+  int32_t *const kx = filter_lds;                            // [tx_cap][64]
+  int32_t *const lox = kx + q.tx_cap * 64;                   // [64]: first source column, relative to the window
+  int32_t *const ky = lox + 64;                              // [kFilterRows][ty_cap]
+  int32_t *const loy = ky + kFilterRows * q.ty_cap;          // [kFilterRows]: first source row, in the frame
+  int32_t *const ny = loy + kFilterRows;                     // [kFilterRows]: taps
+  uint32_t *const T = (uint32_t *)(ny + kFilterRows);        // [t_rows][64]: r | g << 8 | b << 16
+
+  const int j = (int)tx * 64 + lane;  // output column
+  const int k0 = (int)ty * kFilterRows;
+  if (wave == 0) {
+    int count;
+    lox[lane] = filter_weights(ax, j, ow, taps_x, g.win_x, kx + lane, 64, &count) - g.win_x;
+  } else if (wave == 1 && lane < kFilterRows) {
+    int count;
+    loy[lane] = filter_weights(ay, k0 + lane, oh, taps_y, g.win_y, ky + lane * q.ty_cap, 1, &count);
+    ny[lane] = count;
+  }
+  __syncthreads();
+
+  const int n_rows = min(kFilterRows, oh - k0);  // >= 1
+  const int span_lo = __builtin_amdgcn_readfirstlane(loy[0]);
+  const int span_hi = __builtin_amdgcn_readfirstlane(loy[n_rows - 1] + ny[n_rows - 1]);
+  const int off0 = 3 * lox[lane];
+  const uint8_t *const src = p.src + src_offset;
+  const int64_t src_row_bytes = 3LL * g.win_w;
+  int acc[kFilterRows / 4][3];
+#pragma unroll
+  for (int i = 0; i < kFilterRows / 4; i++) acc[i][0] = acc[i][1] = acc[i][2] = 1 << 21;
+
+  for (int base = span_lo; base < span_hi; base += q.t_rows) {
+    const int end = min(base + q.t_rows, span_hi);
+    // the horizontal pass of source rows base .. end - 1
+    for (int r = base + wave; r < end; r += 4) {
+      const int wr = min(max(r - g.win_y, 0), g.win_h - 1);  // (inside the window by construction)
+      const __amdgpu_buffer_rsrc_t row =
+          __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src + (int64_t)wr * src_row_bytes), 0, (int)(3 * g.win_w + 4), 0x00020000);
+      int h[3] = {1 << 21, 1 << 21, 1 << 21};
+      int tap = 0;
+      for (; tap + 4 <= taps_x; tap += 4) {  // four loads in flight
+        uint32_t v[4];
+        int32_t w[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) v[u] = __builtin_amdgcn_raw_buffer_load_b32(row, off0 + 3 * (tap + u), 0, 0);
+#pragma unroll
+        for (int u = 0; u < 4; u++) w[u] = kx[(tap + u) * 64 + lane];
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+          h[0] += w[u] * (int)(v[u] & 0xffu), h[1] += w[u] * (int)((v[u] >> 8) & 0xffu), h[2] += w[u] * (int)((v[u] >> 16) & 0xffu);
+      }
+      for (; tap < taps_x; tap++) {
+        const uint32_t v = __builtin_amdgcn_raw_buffer_load_b32(row, off0 + 3 * tap, 0, 0);
+        const int32_t w = kx[tap * 64 + lane];
+        h[0] += w * (int)(v & 0xffu), h[1] += w * (int)((v >> 8) & 0xffu), h[2] += w * (int)((v >> 16) & 0xffu);
+      }
+      T[(r - base) * 64 + lane] = (uint32_t)clip8(h[0] >> 22) | (uint32_t)clip8(h[1] >> 22) << 8 | (uint32_t)clip8(h[2] >> 22) << 16;
+    }
+    __syncthreads();
+    // the vertical pass over what of this chunk lies in each row's footprint
+#pragma unroll
+    for (int i = 0; i < kFilterRows / 4; i++) {
+      const int s = wave + 4 * i;
+      if (s < n_rows) {
+        const int lo = __builtin_amdgcn_readfirstlane(loy[s]), n = __builtin_amdgcn_readfirstlane(ny[s]);
+        const int r1 = min(lo + n, end);
+        for (int r = max(lo, base); r < r1; r++) {
+          const int32_t w = ky[s * q.ty_cap + (r - lo)];
+          const uint32_t v = T[(r - base) * 64 + lane];
+          acc[i][0] += w * (int)(v & 0xffu), acc[i][1] += w * (int)((v >> 8) & 0xffu), acc[i][2] += w * (int)((v >> 16) & 0xffu);
+        }
+      }
+    }
+    if (end < span_hi) __syncthreads();  // (T is written again)
+  }
+
+  if (j >= ow) return;
+#pragma unroll
+  for (int i = 0; i < kFilterRows / 4; i++) {
+    const int s = wave + 4 * i;
+    if (s >= n_rows) continue;
+    uint8_t *const dst = p.dst + (int64_t)img * p.dst_image_stride + (int64_t)(k0 + s) * p.dst_row_stride;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      const uint32_t u = (uint32_t)clip8(acc[i][c] >> 22);
+      // (jb_resample_kernel's store, operation for operation)
+      if constexpr (FORMAT == 0) {
+        dst[3 * (int64_t)j + c] = (uint8_t)u;
+      } else if constexpr (FORMAT == 1) {
+        dst[(int64_t)c * p.dst_plane_stride + j] = (uint8_t)u;
+      } else {
+        const float f = (float)u * p.scale[c] + p.bias[c];
+        uint8_t *const at = dst + (int64_t)c * p.dst_plane_stride;
+        if constexpr (FORMAT == 2) ((float *)at)[j] = f;
+        else ((_Float16 *)at)[j] = (_Float16)f;
+      }
+    }
+  }
+}
+
+// the launch's grid and LDS: tx_cap / ty_cap / t_rows from the geometry of its n rows; 0 bytes: not launchable
+static size_t filter_plan(JbFilter &p, const JbFilterRow *rows, int n, int filter, dim3 *grid) {
+  if (filter != 1 && filter != 2) return 0;
+  if (p.base.ow < 1 || p.base.oh < 1 || p.base.ow > 65535 || p.base.oh > 65535 || p.base.n_images < 1 || p.frame_w < 1 || p.frame_h < 1 ||
+      p.frame_w > 65535 || p.frame_h > 65535)
+    return 0;
+  p.tx_cap = p.ty_cap = 1;
+  int span = 1;
+  for (int i = 0; i < n; i++) {
+    const JbFilterRow &r = rows[i];
+    if (r.w < 1 || r.h < 1 || r.x < 0 || r.y < 0 || r.x + (int64_t)r.w > p.frame_w || r.y + (int64_t)r.h > p.frame_h || r.tmp_offset < 0) return 0;
+    // the window must be the one the kernel's bounds stay in: what jb_filter_window gives
+    const JbFilterAxis ax = jb_filter_axis(filter, p.frame_w, r.x, r.x + r.w, p.base.ow), ay = jb_filter_axis(filter, p.frame_h, r.y, r.y + r.h, p.base.oh);
+    int x0, x1, y0, y1;
+    jb_filter_span(ax, p.base.ow, &x0, &x1);
+    jb_filter_span(ay, p.base.oh, &y0, &y1);
+    if (r.win_x != x0 || r.win_y != y0 || r.win_w != x1 - x0 || r.win_h != y1 - y0) return 0;
+    const int tx = jb_filter_taps(ax), ty = jb_filter_taps(ay);
+    if (tx > kJbFilterMaxTaps || ty > kJbFilterMaxTaps) return 0;
+    if (tx > p.tx_cap) p.tx_cap = tx;
+    if (ty > p.ty_cap) p.ty_cap = ty;
+    int s = (int)((kFilterRows - 1) * ay.scale) + ty + 2;  // the source rows kFilterRows footprints span, at the most
+    if (s > r.win_h) s = r.win_h;
+    if (s > span) span = s;
+  }
+  const size_t fixed = ((size_t)p.tx_cap * 64 + 64 + (size_t)kFilterRows * p.ty_cap + 2 * kFilterRows) * 4;
+  const size_t room = ((size_t)kFilterLdsBytes - fixed) / 256;  // (at the cap: 74 rows)
+  p.t_rows = (int)((size_t)span < room ? (size_t)span : room);
+  p.base.tiles_x = (p.base.ow + 63) / 64;
+  p.base.tiles_y = (p.base.oh + kFilterRows - 1) / kFilterRows;
+  const int64_t n_wgs = (int64_t)p.base.tiles_x * p.base.tiles_y * p.base.n_images;
+  if (n_wgs > 0x7fffffffLL) return 0;
+  *grid = dim3((unsigned)n_wgs);
+  return fixed + (size_t)p.t_rows * 256;
+}
+
+#define JB_FILTER_LAUNCH(FILTER, CROPS, ...)                                                                                  \
+  switch (format) {                                                                                                           \
+    case 0: hipLaunchKernelGGL((jb_filter_kernel<FILTER, 0, CROPS JB_FILTER_TABLE>), grid, dim3(256), lds, stream, __VA_ARGS__); break; \
+    case 1: hipLaunchKernelGGL((jb_filter_kernel<FILTER, 1, CROPS JB_FILTER_TABLE>), grid, dim3(256), lds, stream, __VA_ARGS__); break; \
+    case 2: hipLaunchKernelGGL((jb_filter_kernel<FILTER, 2, CROPS JB_FILTER_TABLE>), grid, dim3(256), lds, stream, __VA_ARGS__); break; \
+    default: hipLaunchKernelGGL((jb_filter_kernel<FILTER, 3, CROPS JB_FILTER_TABLE>), grid, dim3(256), lds, stream, __VA_ARGS__); break; \
+  }
+
+hipError_t jbk_filter_launch(const JbFilter &q, int filter, int format, hipStream_t stream) {
+  if (format < 0 || format > 3) return hipErrorInvalidValue;
+  JbFilter p = q;
+  dim3 grid;
+  const size_t lds = filter_plan(p, &p.one, 1, filter, &grid);
+  if (!lds) return hipErrorInvalidValue;
+#define JB_FILTER_TABLE
+  if (filter == 1) {
+    JB_FILTER_LAUNCH(1, false, p)
+  } else {
+    JB_FILTER_LAUNCH(2, false, p)
+  }
+#undef JB_FILTER_TABLE
+  return hipGetLastError();
+}
+
+hipError_t jbk_filter_launch_crops(const JbFilter &q, const JbFilterTable &table, int filter, int format, hipStream_t stream) {
+  if (format < 0 || format > 3 || q.base.n_images < 1 || q.base.n_images > kJbCropsPerLaunch) return hipErrorInvalidValue;
+  JbFilter p = q;
+  dim3 grid;
+  const size_t lds = filter_plan(p, table.r, p.base.n_images, filter, &grid);
+  if (!lds) return hipErrorInvalidValue;
+#define JB_FILTER_TABLE , JbFilterTable
+  if (filter == 1) {
+    JB_FILTER_LAUNCH(1, true, p, table)
+  } else {
+    JB_FILTER_LAUNCH(2, true, p, table)
+  }
+#undef JB_FILTER_TABLE
+  return hipGetLastError();
+}
+#undef JB_FILTER_LAUNCH

@@ -1,6 +1,7 @@
 // jb_seam.cpp -- the pixel launch of every route: the public device seams (jb_blocks_to_rgb_device*) and, through
 // seam_launch (jb_ctx.h), the staging ring's submissions of jb_api.cpp.
 #include <cstring>
+#include <vector>
 
 #include "jb_ctx.h"
 #include "jb_kernels.h"
@@ -180,16 +181,37 @@ JbResample resample_args(const jb_device_batch *b, const JbOutPlan &plan, int64_
   return q;
 }
 
+// the filtered launch's arguments ("resampling filters"): the resample launch's and the frame
+JbFilter filter_args(const jb_device_batch *b, const JbOutPlan &plan, int64_t plane_stride, const void *src, int64_t i0, int m) {
+  JbFilter f;
+  memset(&f, 0, sizeof f);
+  f.base = resample_args(b, plan, plane_stride, src, i0, m);
+  f.frame_w = b->desc.width, f.frame_h = b->desc.height;
+  return f;
+}
+
+// a rectangle and its window as the filtered kernels take them
+JbFilterRow filter_row(const jb_roi &r, const jb_roi &win, int64_t tmp_offset) {
+  return JbFilterRow{r.x, r.y, r.width, r.height, win.x, win.y, win.width, win.height, tmp_offset};
+}
+
 // 3c. a plan with per-image rectangles (plan.crops) and a target size: as 3b, with the rectangles of a sub-batch in a
 // table that travels in the arguments of both kernels.  Consecutive images are packed into a sub-batch while their
 // intermediates -- back to back, tight, at the prefix sums of 3 * w_i * h_i -- fit the cap of the stream's scratch (an
-// image larger than the cap runs alone) and a table holds them.  The pixel kernel's grid gives every image as many
+// image larger than the cap runs alone) and a table holds them.  With a filter other than 0 the pixel kernel writes every
+// image's WINDOW (jb_filter_window) in its rectangle's place -- the window's size decides the packing -- and the filtered
+// kernel gets rectangle and window in a table of its own.  The pixel kernel's grid gives every image as many
 // workgroups as the sub-batch's largest rectangle needs; those beyond an image's own count return at once.
 int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn, const jb_geometry &g,
                       int64_t plane_stride) {
   if (plan.n_crops != b->n_images) return fail(ctx, JB_ERR_GEOMETRY, "%s: %d rectangles for %d images", fn, plan.n_crops, b->n_images);
   const int64_t cap = (int64_t)ctx->knobs.resize_tmp_bytes;
-  const auto bytes_of = [&](int64_t i) { return 3LL * plan.crops[i].width * plan.crops[i].height; };
+  std::vector<jb_roi> windows;  // what the pixel kernel writes of every image: with a filter, not the rectangle
+  if (plan.filter)
+    for (int64_t i = 0; i < b->n_images; i++)
+      windows.push_back(jb_filter_window_of_(&b->desc, &plan.crops[i], plan.out_w, plan.out_h, plan.filter));
+  const jb_roi *const written = plan.filter ? windows.data() : plan.crops;
+  const auto bytes_of = [&](int64_t i) { return 3LL * written[i].width * written[i].height; };
   // the images of the sub-batch that starts at i0; *bytes: their intermediates
   const auto pack = [&](int64_t i0, int64_t *bytes) {
     int m = 1;
@@ -214,11 +236,14 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
     int64_t bytes;
     const int m = pack(i0, &bytes);
     JbCropTable table;
+    JbFilterTable ftable;
     memset(&table, 0, sizeof table);
+    memset(&ftable, 0, sizeof ftable);
     int32_t most_tiles = 0;
     int64_t at = 0;
     for (int j = 0; j < m; j++) {
-      const jb_roi &r = plan.crops[i0 + j];
+      const jb_roi &r = written[i0 + j];
+      if (plan.filter) ftable.r[j] = filter_row(plan.crops[i0 + j], r, at);
       JbCrop &c = table.c[j];
       c.x = r.x, c.y = r.y, c.w = r.width, c.h = r.height;
       c.mx = r.x / mw, c.my = r.y / mh;
@@ -241,7 +266,8 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
     p.n_tiles = m * most_tiles;  // (at most 32 images' worth of tiles: no overflow)
     p.fast_store = 1;            // (the ROI stage does not look at it)
     JB_HIP(ctx, jbk_launch_crops(p, table, b->desc.hs, b->desc.vs, s));
-    JB_HIP(ctx, jbk_resample_launch_crops(resample_args(b, plan, plane_stride, tmp, i0, m), table, plan.format, s));
+    if (plan.filter) JB_HIP(ctx, jbk_filter_launch_crops(filter_args(b, plan, plane_stride, tmp, i0, m), ftable, plan.filter, plan.format, s));
+    else JB_HIP(ctx, jbk_resample_launch_crops(resample_args(b, plan, plane_stride, tmp, i0, m), table, plan.format, s));
     i0 += m;
   }
   return JB_OK;
@@ -255,7 +281,8 @@ int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, con
   int rc = seam_check(ctx, b, plan, fn, &g, &plane_stride);
   if (rc) return rc;
   if (plan.crops) return seam_launch_crops(ctx, b, stream, plan, fn, g, plane_stride);
-  const JbOutPlan inner = jb_out_plan_(&b->desc, 1, nullptr, plan.has_roi ? &plan.roi : nullptr);
+  // (with a filter other than 0 the source is the window: the ROI store stage with the window in the rectangle's place)
+  const JbOutPlan inner = jb_out_plan_(&b->desc, 1, nullptr, plan.filter ? &plan.window : plan.has_roi ? &plan.roi : nullptr);
   if (inner.status != JB_OK) return fail(ctx, inner.status, "%s: %s", fn, inner.why);
   // whole images per sub-batch: as many as the cap holds, one at the least
   const int64_t cap = (int64_t)ctx->knobs.resize_tmp_bytes;
@@ -283,7 +310,14 @@ int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, con
     ib.rgb_image_stride = plan.tmp_image_bytes;
     rc = seam_launch(ctx, &ib, s, inner, fn);
     if (rc) return rc;
-    JB_HIP(ctx, jbk_resample_launch(resample_args(b, plan, plane_stride, tmp, i0, m), plan.format, s));
+    if (plan.filter) {
+      JbFilter f = filter_args(b, plan, plane_stride, tmp, i0, m);
+      const jb_roi whole = {0, 0, b->desc.width, b->desc.height};
+      f.one = filter_row(plan.has_roi ? plan.roi : whole, plan.window, 0);
+      JB_HIP(ctx, jbk_filter_launch(f, plan.filter, plan.format, s));
+    } else {
+      JB_HIP(ctx, jbk_resample_launch(resample_args(b, plan, plane_stride, tmp, i0, m), plan.format, s));
+    }
   }
   return JB_OK;
 }
@@ -347,6 +381,21 @@ int jb_blocks_to_rgb_device_crops(jb_ctx *ctx, const jb_device_batch *b, const j
   const JbTarget t = {out_w, out_h};
   return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, nullptr, &t, rois, b ? b->n_images : 0),
                      "jb_blocks_to_rgb_device_crops");
+}
+
+int jb_blocks_to_rgb_device_filtered(jb_ctx *ctx, const jb_device_batch *b, const jb_roi *roi, const jb_resize *rs,
+                                     const jb_output_spec *spec, void *stream) {
+  if (ctx && !rs) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_filtered: rs is NULL");
+  const JbTarget t = rs ? JbTarget{rs->out_w, rs->out_h, rs->filter, rs->reserved} : JbTarget{};
+  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, roi, &t), "jb_blocks_to_rgb_device_filtered");
+}
+
+int jb_blocks_to_rgb_device_crops_filtered(jb_ctx *ctx, const jb_device_batch *b, const jb_roi *rois, const jb_resize *rs,
+                                           const jb_output_spec *spec, void *stream) {
+  if (ctx && (!rois || !rs)) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_crops_filtered: NULL pointer");
+  const JbTarget t = rs ? JbTarget{rs->out_w, rs->out_h, rs->filter, rs->reserved} : JbTarget{};
+  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, nullptr, &t, rois, b ? b->n_images : 0),
+                     "jb_blocks_to_rgb_device_crops_filtered");
 }
 
 }  // extern "C"
