@@ -63,21 +63,26 @@ def window(filt, W, H, rect, target):
     return x0, y0, x1 - x0, y1 - y0
 
 
-def _pass(src, weights):
-    """src [n_in, ...] -> [len(weights), ...]: clip8((2^21 + sum_t k[t] * src[lo + t]) >> 22) along axis 0, in int64"""
-    out = np.empty((len(weights),) + src.shape[1:], np.uint8)
+def _pass(src, weights, clamp="clip"):
+    """src [n_in, ...] -> [len(weights), ...]: clip8((2^21 + sum_t k[t] * src[lo + t]) >> 22) along axis 0, in int64.
+    clamp (for tests that must tell a missing clamp from a present one; "clip" is the definition): "none" leaves the
+    clamp out and returns the int64 values, "wrap" keeps their low 8 bits as a plain uint8 store would."""
+    out = np.empty((len(weights),) + src.shape[1:], np.uint8 if clamp != "none" else np.int64)
     s64 = src.astype(np.int64)
     for j, (lo, k) in enumerate(weights):
         acc = np.full(src.shape[1:], 1 << 21, np.int64)
         for t, kt in enumerate(k):
             acc += kt * s64[lo + t]
         assert np.all(np.abs(acc) < 2 ** 31)         # the definition's sum is a signed 32-bit one
-        out[j] = np.clip(acc >> 22, 0, 255)
+        out[j] = np.clip(acc >> 22, 0, 255) if clamp == "clip" else (acc >> 22) & 0xff if clamp == "wrap" else acc >> 22
     return out
 
 
-def resize(full, rect, target, filt):
-    """full [H, W, 3] uint8, rect (x, y, w, h) or None (the whole frame), target (ow, oh) -> [oh, ow, 3] uint8"""
+def resize(full, rect, target, filt, mid_clamp="clip", out_clamp="clip"):
+    """full [H, W, 3] uint8, rect (x, y, w, h) or None (the whole frame), target (ow, oh) -> [oh, ow, 3] uint8.
+    mid_clamp / out_clamp: _pass's clamp of the horizontal / the vertical pass -- anything but the default "clip" is
+    the WRONG answer of a kernel that lost that clamp (mid_clamp "none": the unclamped int64 goes into the second
+    pass; out_clamp "wrap": the low byte is stored), for tests to tell from the right one."""
     full = np.asarray(full)
     assert full.dtype == np.uint8 and full.ndim == 3
     H, W = full.shape[:2]
@@ -85,8 +90,8 @@ def resize(full, rect, target, filt):
     ow, oh = target
     kx = axis_weights(filt, W, x, x + w, ow)
     ky = axis_weights(filt, H, y, y + h, oh)
-    t = _pass(np.ascontiguousarray(full.transpose(1, 0, 2)), kx).transpose(1, 0, 2)   # every frame row: [H, ow, 3]
-    return _pass(np.ascontiguousarray(t), ky)
+    t = _pass(np.ascontiguousarray(full.transpose(1, 0, 2)), kx, mid_clamp).transpose(1, 0, 2)   # every frame row: [H, ow, 3]
+    return _pass(np.ascontiguousarray(t), ky, out_clamp)
 
 
 def resize_rect_clamped(full, rect, target, filt):

@@ -74,6 +74,20 @@ def test_restatement_identity_and_margin():
         assert not np.array_equal(pr.resize(full, (20, 12, 30, 20), (11, 9), filt), pr.resize_rect_clamped(full, (20, 12, 30, 20), (11, 9), filt))
 
 
+def test_restatement_without_a_clamp_is_another_image():
+    """mid_clamp / out_clamp restate a kernel that lost a clamp (for the GPU tests' preconditions): on a 0 / 255 image
+    bicubic's overshoot makes each of them another image, bilinear -- no negative weight -- never leaves 0..255, and the
+    defaults are the definition."""
+    full = _frame(67, 45, "binary", 7)
+    for rect, target in (((5, 6, 40, 30), (41, 33)), (None, (100, 70))):
+        for filt in (BILINEAR, BICUBIC):
+            want = pr.resize(full, rect, target, filt)
+            assert np.array_equal(pr.resize(full, rect, target, filt, mid_clamp="clip", out_clamp="clip"), want)
+            lost = [pr.resize(full, rect, target, filt, mid_clamp="none"), pr.resize(full, rect, target, filt, out_clamp="wrap")]
+            assert all(x.dtype == np.uint8 and x.shape == want.shape for x in lost)
+            assert all(np.array_equal(x, want) == (filt == BILINEAR) for x in lost), (rect, target, filt)
+
+
 # ---- jb_filter_window ------------------------------------------------------------------------------------------------
 def _rs(jb, target, filt, reserved=0):
     return jb.Resize(target[0], target[1], filt, reserved)
