@@ -386,6 +386,8 @@ int jb_blocks_to_rgb_device_crops(jb_ctx *ctx, const jb_device_batch *batch, con
  *
  * and the result is, bit for bit, what Pillow's 8-bit resampling gives: Image.resize((out_w, out_h), BILINEAR / BICUBIC,
  * box=(x, y, x + w, y + h)) of the full-size decode (what torchvision's antialiased Resize computes on PIL images).
+ * The RESIZE is Pillow's; the full-size DECODE it is applied to is Pillow's own -- Image.open(f).convert("RGB") -- only
+ * under JB_ARITH_LIBJPEG ("decoder arithmetic" below), and the reference program's otherwise.
  * The weights of one axis -- frame extent in_size (the WHOLE image, not the rectangle), rectangle [in0, in1), n outputs --
  * are computed on IEEE doubles, every operation in exactly this order and none fused:
  *
@@ -443,6 +445,61 @@ int jb_decode_memory_filtered(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
                               const jb_output_spec *spec, void **out, int32_t *width, int32_t *height);
 int jb_decode_file_filtered(jb_ctx *ctx, const char *path, const jb_roi *roi, const jb_resize *rs, const jb_output_spec *spec,
                             void **out, int32_t *width, int32_t *height);
+
+/* ---- decoder arithmetic: the reference program's, or libjpeg's bit for bit ----
+ * What a full-size decode computes between the coefficients and the uint8 pixels.  JB_ARITH_REFERENCE (the default) is
+ * the reference program's: a float AAN IDCT, chroma replicated to the luma grid, float YCbCr -> RGB.  JB_ARITH_LIBJPEG
+ * is libjpeg(-turbo)'s default decode -- jidctint.c ("islow"), jdsample.c's "fancy" upsampling, jdcolor.c -- so that the
+ * full-size output is, bit for bit, Pillow's Image.open(f).convert("RGB") (and torchvision's and OpenCV's decode), and
+ * every output option composes on top of it unchanged: formats 1-3, a rectangle, a target size, per-image rectangles and
+ * the filters then give the bits of open -> convert("RGB") -> resize(box=) from the file to the normalised tensor.
+ * All arithmetic is integer; >> is an arithmetic shift; clamp is to 0..255.
+ *   1. Dequantise and IDCT (CONST_BITS 13, PASS1_BITS 2).  v[k] = coef[k] * q[k], natural order.  A columns pass, then a
+ *      rows pass, run one 1-D network on in0..in7:
+ *        even:  z1 = (in2 + in6) * 4433;  tmp2 = z1 - in6 * 15137;  tmp3 = z1 + in2 * 6270
+ *               tmp0 = (in0 + in4) << 13;  tmp1 = (in0 - in4) << 13
+ *               tmp10 = tmp0 + tmp3;  tmp13 = tmp0 - tmp3;  tmp11 = tmp1 + tmp2;  tmp12 = tmp1 - tmp2
+ *        odd:   t0 = in7, t1 = in5, t2 = in3, t3 = in1;  z1 = t0 + t3;  z2 = t1 + t2;  z3 = t0 + t2;  z4 = t1 + t3
+ *               z5 = (z3 + z4) * 9633;  t0 *= 2446;  t1 *= 16819;  t2 *= 25172;  t3 *= 12299
+ *               z1 *= -7373;  z2 *= -20995;  z3 = z3 * -16069 + z5;  z4 = z4 * -3196 + z5
+ *               t0 += z1 + z3;  t1 += z2 + z4;  t2 += z2 + z3;  t3 += z1 + z4
+ *        out0/7 = tmp10 +- t3;  out1/6 = tmp11 +- t2;  out2/5 = tmp12 +- t1;  out3/4 = tmp13 +- t0,
+ *        each (x + (1 << (n - 1))) >> n with n = 11 after the columns pass and n = 18 after the rows pass.
+ *      Sample = clamp(out + 128).
+ *   2. Chroma upsampling.  The chroma planes are dw = ceil(W / hs) by dh = ceil(H / vs) samples (a coded block's padding
+ *      beyond that is never read), and EVERY neighbour index is clamped to [0, dw - 1] / [0, dh - 1]: that one rule is
+ *      libjpeg's first / last column and top / bottom row cases.
+ *        4:2:2:  out[2x] = (3 c[x] + c[x-1] + 1) >> 2;  out[2x+1] = (3 c[x] + c[x+1] + 2) >> 2
+ *        4:4:0:  row 2y: (3 c[y] + c[y-1] + 1) >> 2;  row 2y+1: (3 c[y] + c[y+1] + 2) >> 2
+ *        4:2:0:  row 2y+v: s[x] = 3 c[y][x] + c[y + (v ? 1 : -1)][x];
+ *                out[2x] = (3 s[x] + s[x-1] + 8) >> 4;  out[2x+1] = (3 s[x] + s[x+1] + 7) >> 4
+ *      As in libjpeg, with hs = 2 and dw <= 2 (width <= 4) chroma is plainly replicated in both directions (4:2:0: no
+ *      vertical filter either); 4:4:0 has no such exception.
+ *   3. Colour, with cb, cr = sample - 128:
+ *        R = clamp(y + ((91881 cr + 32768) >> 16));  G = clamp(y + ((-22554 cb - 46802 cr + 32768) >> 16))
+ *        B = clamp(y + ((116130 cb + 32768) >> 16))
+ *      A grayscale file arrives as 4:4:4 with zero chroma blocks: R = G = B = Y, Pillow's L converted to RGB.
+ *   4. A rectangle is a crop of the full decode: with a rectangle, per-image rectangles or a filter's window every pixel
+ *      has the bits it has in the full-size decode -- the upsampler's neighbours are the true neighbouring samples, also
+ *      in MCUs the rectangle does not touch; clamping happens at the frame's edges only.
+ * Domain: the contract holds where every intermediate above fits int32 and the inputs of both passes fit int16 -- the
+ * range libjpeg-turbo's SIMD code computes in, and the range every file encoded from 8-bit pixels stays in.  Outside it
+ * the output is memory-safe and deterministic and its bits are pinned to nothing (libjpeg's C code, its SIMD code and a
+ * plain clamp disagree there).
+ * The setting belongs to the context -- of a batch decoder, to the decoder: every device, both sides of submit / collect
+ * -- and governs every later call: the device seam in all its variants, jb_blocks_to_rgb / jb_submit / jb_submit_batch,
+ * jb_decode_file* / jb_decode_memory*, batch runs and submissions.  It is no part of the output plan: no entry point
+ * and no status of the sections above changes.  jb_ctx_set_arithmetic: JB_ERR_NULL for a null context, JB_ERR_GEOMETRY
+ * for an unknown value, JB_ERR_STATE while a submission of the context is in flight.  JB_ARITH_LIBJPEG with a scale other
+ * than 1 is JB_ERR_UNSUPPORTED -- at the call for a context, at jb_batch_decoder_set_arithmetic / _set_scale for a
+ * decoder -- and nothing is written: libjpeg's own scaled decode uses reduced IDCTs, not an area mean, so there is
+ * nothing to be exact against.  JPEGBLK_SMALL_GRID, JPEGBLK_ROW_TILING, JPEGBLK_BYTE_STORE and the linear tiling do
+ * not apply under JB_ARITH_LIBJPEG; its launches keep uint8 Y, Cb, Cr planes in a scratch of the context, per stream,
+ * held to JPEGBLK_RESIZE_TMP_BYTES per launch (one image at the least). */
+enum { JB_ARITH_REFERENCE = 0, JB_ARITH_LIBJPEG = 1 };
+int jb_ctx_set_arithmetic(jb_ctx *ctx, int arith);
+/* the context's arithmetic; a null context: JB_ARITH_REFERENCE */
+int jb_ctx_arithmetic(const jb_ctx *ctx);
 
 /* ---- host front end ("next" rows of the scope table; reference jpeg.cpp:67-446, 826-907,
  *      include/file.hpp, include/huffman.hpp) --------------------------------------------- */
@@ -632,6 +689,11 @@ int jb_batch_decoder_submit_crops(jb_batch_decoder *dec, const char *const *path
  * to both sides of submit / collect.  Refused with JB_ERR_STATE while a batch is in flight, with JB_ERR_GEOMETRY for an
  * unknown filter. */
 int jb_batch_decoder_set_filter(jb_batch_decoder *dec, int filter);
+/* The arithmetic (JB_ARITH_*; see "decoder arithmetic") of the batch decoder's later runs and submissions.  Applies to
+ * every device of a multi-device decoder and to both sides of submit / collect.  Refused with JB_ERR_STATE while a batch
+ * is in flight, with JB_ERR_GEOMETRY for an unknown value, and JB_ARITH_LIBJPEG while the scale is not 1 (and
+ * jb_batch_decoder_set_scale(!= 1) under JB_ARITH_LIBJPEG) with JB_ERR_UNSUPPORTED. */
+int jb_batch_decoder_set_arithmetic(jb_batch_decoder *dec, int arith);
 /* Output sink replacing the reference's X11 window / unused BMP writer (display.hpp,
  * jpeg.cpp:462-509): binary PPM (P6). */
 int jb_write_ppm(const char *path, const uint8_t *rgb, int32_t width, int32_t height,

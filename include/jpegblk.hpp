@@ -37,6 +37,12 @@ class Context {
   Context(const Context &) = delete;
   Context &operator=(const Context &) = delete;
   jb_ctx *get() const { return ctx_; }
+  // "decoder arithmetic" (jpegblk.h): JB_ARITH_LIBJPEG makes every later decode libjpeg's, bit for bit
+  void set_arithmetic(int arith) {
+    int rc = jb_ctx_set_arithmetic(ctx_, arith);
+    if (rc) throw Error(rc, jb_last_error(ctx_));
+  }
+  int arithmetic() const { return jb_ctx_arithmetic(ctx_); }
 
  private:
   jb_ctx *ctx_ = nullptr;

@@ -82,6 +82,8 @@ class Roi(ctypes.Structure):
 
 # resampling filters (jpegblk.h, "resampling filters"): 0 = the exact area resize, the others Pillow's 8-bit resampling
 FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC = 0, 1, 2
+# "decoder arithmetic" (include/jpegblk.h): the reference program's, or libjpeg's -- Pillow's decode bit for bit
+ARITH_REFERENCE, ARITH_LIBJPEG = 0, 1
 
 
 class Resize(ctypes.Structure):
@@ -357,6 +359,9 @@ def lib():
     L.jb_decode_memory_filtered.argtypes = [vp, vp, ctypes.c_size_t, pr, prs, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.jb_decode_file_filtered.argtypes = [vp, ctypes.c_char_p, pr, prs, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.jb_batch_decoder_set_filter.argtypes = [vp, ctypes.c_int]
+    L.jb_batch_decoder_set_arithmetic.argtypes = [vp, ctypes.c_int]
+    L.jb_ctx_set_arithmetic.argtypes = [vp, ctypes.c_int]
+    L.jb_ctx_arithmetic.argtypes = [vp]
     L.jb_write_ppm.argtypes = [ctypes.c_char_p, vp, i32, i32, i64]
     L.jb_write_bmp.argtypes = [ctypes.c_char_p, vp, i32, i32, i64]
     if L.jb_abi_version() != 1:
@@ -429,9 +434,26 @@ def entropy_decode(jpeg_bytes, headers_only=False, n_threads=1):
 class Context:
     """jb_ctx: one device, one stream, a ring of staging slots."""
 
-    def __init__(self, device=0, max_coef_bytes=0, max_rgb_bytes=0, n_slots=2):
+    def __init__(self, device=0, max_coef_bytes=0, max_rgb_bytes=0, n_slots=2, arithmetic=ARITH_REFERENCE):
         self._h = ctypes.c_void_p()
         _check(lib().jb_ctx_create(device, max_coef_bytes, max_rgb_bytes, n_slots, ctypes.byref(self._h)))
+        if arithmetic != ARITH_REFERENCE:
+            try:
+                self.set_arithmetic(arithmetic)
+            except JbError:
+                self.close()
+                raise
+
+    def set_arithmetic(self, arithmetic):
+        """jb_ctx_set_arithmetic: ARITH_REFERENCE, or ARITH_LIBJPEG -- every later call of this context then decodes with
+        libjpeg's integer IDCT, fancy upsampling and colour tables: the full-size output is Pillow's
+        Image.open(f).convert("RGB") bit for bit, and fmt, roi, resize, crops and filter compose on top of it.  JbError -2
+        for an unknown value, -7 while a submission is in flight; a scale other than 1 is then JbError -9 at the call."""
+        _check(lib().jb_ctx_set_arithmetic(self._h, int(arithmetic)), self._h)
+
+    @property
+    def arithmetic(self):
+        return lib().jb_ctx_arithmetic(self._h)
 
     @classmethod
     def for_image(cls, desc, device=0, n_slots=2):
@@ -625,10 +647,11 @@ class BatchDecoder:
     fmt, with or without roi, not with a scale): every image, or its rectangle, comes out at w x h, an exact area resize
     on the device, so files of any size and layout give outputs of one size.  filter (jb_batch_decoder_set_filter; with
     resize): FILTER_BILINEAR / FILTER_BICUBIC put Pillow's 8-bit resampling in the area filter's place, for the target
-    size and for the per-image rectangles of run(crops=) alike."""
+    size and for the per-image rectangles of run(crops=) alike.  arithmetic (jb_batch_decoder_set_arithmetic):
+    ARITH_LIBJPEG decodes every file as libjpeg does, bit for bit (not with a scale)."""
 
     def __init__(self, n_threads=8, device=0, max_coef_bytes=0, max_rgb_bytes=0, arena_bytes=0, devices=None, scale=1, fmt=None,
-                 roi=None, resize=None, filter=FILTER_AREA):
+                 roi=None, resize=None, filter=FILTER_AREA, arithmetic=ARITH_REFERENCE):
         _Request(scale, fmt, roi, resize, filter=filter)   # (roi or resize with a scale: JbError(-9) before anything is created)
         self._h = ctypes.c_void_p()
         if devices is not None:
@@ -655,6 +678,8 @@ class BatchDecoder:
                 self.set_resize(resize)
             if filter != FILTER_AREA:
                 self.set_filter(filter)
+            if arithmetic != ARITH_REFERENCE:
+                self.set_arithmetic(arithmetic)
         except JbError:
             self.close()
             raise
@@ -684,9 +709,14 @@ class BatchDecoder:
         flight, -2 for an unknown filter)."""
         _check(lib().jb_batch_decoder_set_filter(self._h, int(filter)))
 
+    def set_arithmetic(self, arithmetic):
+        """jb_batch_decoder_set_arithmetic: ARITH_REFERENCE or ARITH_LIBJPEG for later runs and submissions (JbError -7
+        while a batch is in flight, -2 for an unknown value, -9 for ARITH_LIBJPEG while the decoder's scale is not 1)."""
+        _check(lib().jb_batch_decoder_set_arithmetic(self._h, int(arithmetic)))
+
     def set_scale(self, scale):
         """jb_batch_decoder_set_scale: output at 1/scale for later runs and submissions (JbError -7 while a batch
-        is in flight, -9 while a planar format, a rectangle or a target size is set)."""
+        is in flight, -9 while a planar format, a rectangle or a target size is set, or under ARITH_LIBJPEG)."""
         _check(lib().jb_batch_decoder_set_scale(self._h, scale))
 
     @property

@@ -365,6 +365,8 @@ void jb_ctx_destroy(jb_ctx *ctx) {
   }
   for (auto &kv : ctx->tmp)
     if (kv.second.d) (void)hipFree(kv.second.d);  // (hipFree waits for the device: launches on a caller's stream included)
+  for (auto &kv : ctx->planes)
+    if (kv.second.d) (void)hipFree(kv.second.d);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   delete ctx;
@@ -382,6 +384,23 @@ int jb_ctx_synchronize(jb_ctx *ctx) {
 }
 
 int jb_ctx_device(const jb_ctx *ctx) { return ctx ? ctx->device : -1; }
+
+int jb_ctx_set_arithmetic(jb_ctx *ctx, int arith) {
+  if (!ctx) return fail(nullptr, JB_ERR_NULL, "jb_ctx_set_arithmetic: ctx is NULL");
+  if (arith != JB_ARITH_REFERENCE && arith != JB_ARITH_LIBJPEG) return fail(ctx, JB_ERR_GEOMETRY, "jb_ctx_set_arithmetic: unknown arithmetic %d", arith);
+  // a submission of the ring that has not completed would change its arithmetic between its launches
+  DeviceGuard guard(ctx->device);
+  for (int i = 0; i < ctx->n_slots; i++) {
+    Slot &s = ctx->slots[i];
+    if (!s.busy) continue;
+    if (s.dl_pending.load(std::memory_order_acquire) || hipEventQuery(s.done) == hipErrorNotReady)
+      return fail(ctx, JB_ERR_STATE, "jb_ctx_set_arithmetic: a submission is in flight (wait for it first)");
+  }
+  ctx->arithmetic = arith;
+  return JB_OK;
+}
+
+int jb_ctx_arithmetic(const jb_ctx *ctx) { return ctx ? ctx->arithmetic : JB_ARITH_REFERENCE; }
 
 long long jb_ctx_device_entropy_images(const jb_ctx *ctx) { return ctx ? ctx->n_device_entropy : 0; }
 
@@ -507,6 +526,7 @@ int submit_begin(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const JbO
   if (rc) return rc;
   if (n_images < 1 || n_images > kMaxBatch) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d outside 1..%d", n_images, kMaxBatch);
   if (plan.status != JB_OK) return fail(ctx, plan.status, "submit: %s", plan.why);
+  if (ctx->arithmetic == JB_ARITH_LIBJPEG && plan.scale != 1) return fail(ctx, JB_ERR_UNSUPPORTED, "submit: %s", kJbArithScaleText);
   // tight rows on the device (12-byte stores need no alignment); a planar format: tight rows of a plane, tight planes
   if (plan.planar && rgb_stride != plan.row_stride) return fail(ctx, JB_ERR_GEOMETRY, "planar output has tight rows");
   if (rgb_stride < plan.row_stride) return fail(ctx, JB_ERR_GEOMETRY, "rgb_stride %lld < 3*width", (long long)rgb_stride);
@@ -953,6 +973,9 @@ int jb_check_device_region_(int device, const void *p, size_t bytes) {
 }
 
 void jb_ctx_set_last_desc_(jb_ctx *ctx, const jb_image_desc *d) { ctx->last_desc = *d; }
+void jb_ctx_set_arithmetic_(jb_ctx *ctx, int arith) {
+  if (ctx) ctx->arithmetic = arith;
+}
 const JbKnobs *jb_ctx_knobs_(const jb_ctx *ctx) { return &ctx->knobs; }
 
 void jb_ctx_set_download_age_(jb_ctx *ctx, uint64_t age) {

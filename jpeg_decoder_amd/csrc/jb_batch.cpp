@@ -42,6 +42,7 @@ struct OutputRequest {
   bool has_resize = false;   // one output size for every image
   JbTarget target = {};      // (target.filter: always the decoder's filter, with or without a target size)
   const JbTarget *target_ptr() const { return has_resize ? &target : nullptr; }
+  int arith = JB_ARITH_REFERENCE;  // "decoder arithmetic": what the decoder's contexts compute in (never LIBJPEG with a scale)
   // can it be had at all?  The plan function decides (jb_plan.h), here for an image of one pixel -- with a rectangle,
   // for the largest frame there is (JB_ERR_GEOMETRY: no frame holds the rectangle)
   int status() const {
@@ -917,6 +918,7 @@ int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, const
     if (setup_rc != JB_OK) setup_text = jb_last_error(nullptr);
     // pass 2: entropy decoding on the host threads, all submitting to the shared context
     dev.ctx = d->ctx;
+    jb_ctx_set_arithmetic_(d->ctx, d->out.arith);  // (nothing of this decoder is in flight here)
     {
       // of two batches in flight on one device (submit / collect, or two decoders) the older one's downloads go first
       static std::atomic<uint64_t> run_seq{0};
@@ -1376,6 +1378,7 @@ extern "C" int jb_batch_decoder_set_scale(jb_batch_decoder *d, int denom) {
   if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_scale: batches are in flight (collect them first)");
   OutputRequest out = d->out;
   out.scale = denom;
+  if (denom != 1 && out.arith == JB_ARITH_LIBJPEG) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_scale: " kJbArithScaleText);
   if (out.status() == JB_ERR_UNSUPPORTED)
     return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_scale: a planar output format, a rectangle or a target size is set: it cannot be combined with a scale");
   set_output_all(d, out);
@@ -1433,6 +1436,18 @@ extern "C" int jb_batch_decoder_set_filter(jb_batch_decoder *d, int filter) {
     return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_set_filter: unknown resampling filter");
   OutputRequest out = d->out;
   out.target.filter = filter;
+  set_output_all(d, out);
+  return JB_OK;
+}
+
+extern "C" int jb_batch_decoder_set_arithmetic(jb_batch_decoder *d, int arith) {
+  if (!d) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_set_arithmetic: decoder is NULL");
+  if (arith != JB_ARITH_REFERENCE && arith != JB_ARITH_LIBJPEG)
+    return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_set_arithmetic: unknown arithmetic");
+  if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_arithmetic: batches are in flight (collect them first)");
+  if (arith == JB_ARITH_LIBJPEG && d->out.scale != 1) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_arithmetic: " kJbArithScaleText);
+  OutputRequest out = d->out;
+  out.arith = arith;
   set_output_all(d, out);
   return JB_OK;
 }

@@ -92,6 +92,12 @@ struct jb_ctx {
   };
   std::mutex tmp_mu;
   std::map<hipStream_t, Tmp> tmp;
+  // "Decoder arithmetic" (include/jpegblk.h): JB_ARITH_*, what every later pixel launch of this context computes in.
+  // Under JB_ARITH_LIBJPEG a launch decodes into uint8 Y, Cb, Cr planes first (jb_libjpeg.hip): `planes` holds them, a
+  // scratch per stream like `tmp` and apart from it -- the resized routes keep their intermediate in `tmp` while the
+  // pixel launch that fills it reads the planes.
+  int arithmetic = JB_ARITH_REFERENCE;
+  std::map<hipStream_t, Tmp> planes;
 };
 
 // the error text of a failed call, formatted: into the context (ctx may be null) and the calling thread (jb_fail_)

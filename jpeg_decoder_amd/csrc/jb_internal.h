@@ -23,6 +23,10 @@ const JbKnobs *jb_ctx_knobs_(const jb_ctx *ctx);
 void jb_ctx_set_last_desc_(jb_ctx *ctx, const jb_image_desc *d);
 // (jb_batch.cpp) the rank of this context's downloads among those of the other contexts on its device
 void jb_ctx_set_download_age_(jb_ctx *ctx, uint64_t age);
+// "decoder arithmetic": the context's setting without jb_ctx_set_arithmetic's look at the ring (jb_batch.cpp sets it
+// between its own runs, when the slots' busy marks are stale and nothing is in flight)
+void jb_ctx_set_arithmetic_(jb_ctx *ctx, int arith);
+#define kJbArithScaleText "JB_ARITH_LIBJPEG cannot be combined with a scale other than 1"
 // JB_OK when [p, p + bytes) is device memory of `device` (jb_batch_decoder_set_device_output: a host pointer or
 // another GPU's memory would fault in the pixel kernel instead of failing here)
 int jb_check_device_region_(int device, const void *p, size_t bytes);

@@ -76,6 +76,26 @@ hipError_t jbk_launch(const JbLaunch &p, int hs, int vs, int scale, hipStream_t 
 hipError_t jbk_launch_crops(const JbLaunch &p, const JbCropTable &table, int hs, int vs, hipStream_t stream);
 const char *jbk_kernel_name(int hs, int vs);
 
+// "Decoder arithmetic" (jb_libjpeg.hip): the pixel launches of JB_ARITH_LIBJPEG, the counterparts of jbk_launch and
+// jbk_launch_crops.  Two kernels per launch: the coded blocks of every image's MCU WINDOW -- the MCUs its rectangle
+// touches, grown by one MCU on every side where chroma is subsampled, clamped to the frame -- go through libjpeg's
+// integer IDCT into uint8 Y, Cb, Cr planes at `planes`; the pixel kernel upsamples, converts and stores from there.
+struct JbLjWindow {
+  int32_t mx, my, nx, ny;  // first MCU, MCUs per row and per column
+  int64_t bytes;           // of one image's three planes (a multiple of 256)
+};
+// the window of the rectangle (x, y, w, h) of a frame of mcus_x x mcus_y MCUs
+JbLjWindow jbk_lj_window(int hs, int vs, int mcus_x, int mcus_y, int x, int y, int w, int h);
+// workgroups of the pixel kernel per image of a w x h output (256 pixels x 4 rows each); 0: more than 2^31 - 1
+int jbk_lj_tiles(int w, int h);
+// Formats 0-3, the whole image or (p.roi = 1) the rectangle p.roi_*: p.tiles_per_image = jbk_lj_tiles of the output,
+// p.n_tiles = images * p.tiles_per_image; p.linear, p.small_grid, p.staged, p.fast_store and p.tiles_per_row are not
+// looked at.  planes: device scratch of images * jbk_lj_window(...).bytes, the launch's alone until it has run.
+hipError_t jbk_lj_launch(const JbLaunch &p, int hs, int vs, void *planes, hipStream_t stream);
+// p.roi = 2: a rectangle per image as for jbk_launch_crops (format 0; of a table row x, y, w, h and tmp_offset are
+// looked at); p.tiles_per_image = the largest jbk_lj_tiles of the rectangles.  planes: the sum of the images' windows.
+hipError_t jbk_lj_launch_crops(const JbLaunch &p, const JbCropTable &table, int hs, int vs, void *planes, hipStream_t stream);
+
 // "Fixed output size" (jb_resample.hip): n_images tight interleaved uint8 images of iw x ih at src (src_image_stride bytes
 // apart, at least 4 readable bytes behind the last one) -> their exact area resize to ow x oh at dst, in `format`
 // (JB_FMT_*): rows dst_row_stride bytes apart (of a plane when planar), planes dst_plane_stride, images

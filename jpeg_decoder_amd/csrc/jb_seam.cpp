@@ -33,6 +33,7 @@ int seam_check(jb_ctx *ctx, const jb_device_batch *b, const JbOutPlan &plan, con
   if (rc) return rc;
   if (b->n_images < 1) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d", b->n_images);
   if (plan.status != JB_OK) return fail(ctx, plan.status, "%s: %s", fn, plan.why);
+  if (ctx->arithmetic == JB_ARITH_LIBJPEG && plan.scale != 1) return fail(ctx, JB_ERR_UNSUPPORTED, "%s: %s", fn, kJbArithScaleText);
   *plane_stride = 0;
   if (plan.planar) {
     if (jb_output_spec_check(&plan.spec, plan.out_h, b->rgb_row_stride) != JB_OK)
@@ -140,17 +141,18 @@ JbLaunch launch_base(const jb_device_batch *b, const jb_geometry &g) {
 constexpr size_t kTmpSlack = 16;    // bytes behind the last intermediate (jb_resample_kernel reads pixels as 4-byte words)
 constexpr size_t kTmpStreams = 64;  // scratches a context keeps before it lets go of all of them
 
-// the scratch of `stream`, at least `bytes` large
-int tmp_for_stream(jb_ctx *ctx, hipStream_t stream, size_t bytes, void **out) {
+// the scratch of `stream` in `pool` (ctx->tmp: the resized routes' intermediates; ctx->planes: the planes of
+// JB_ARITH_LIBJPEG), at least `bytes` large
+int scratch_for_stream(jb_ctx *ctx, std::map<hipStream_t, jb_ctx::Tmp> &pool, hipStream_t stream, size_t bytes, void **out) {
   std::lock_guard<std::mutex> lk(ctx->tmp_mu);
-  if (ctx->tmp.size() >= kTmpStreams && !ctx->tmp.count(stream)) {
+  if (pool.size() >= kTmpStreams && !pool.count(stream)) {
     // a caller that keeps coming with new streams: nothing of the old ones may be in flight when their scratch goes
     JB_HIP(ctx, hipDeviceSynchronize());
-    for (auto &kv : ctx->tmp)
+    for (auto &kv : pool)
       if (kv.second.d) (void)hipFree(kv.second.d);
-    ctx->tmp.clear();
+    pool.clear();
   }
-  jb_ctx::Tmp &t = ctx->tmp[stream];
+  jb_ctx::Tmp &t = pool[stream];
   if (t.cap < bytes) {
     if (t.d) {
       JB_HIP(ctx, hipStreamSynchronize(stream));  // the launches that still read the old one
@@ -162,6 +164,12 @@ int tmp_for_stream(jb_ctx *ctx, hipStream_t stream, size_t bytes, void **out) {
   }
   *out = t.d;
   return JB_OK;
+}
+int tmp_for_stream(jb_ctx *ctx, hipStream_t stream, size_t bytes, void **out) { return scratch_for_stream(ctx, ctx->tmp, stream, bytes, out); }
+
+// the MCU window (jb_kernels.h) of a rectangle of the batch's frame under JB_ARITH_LIBJPEG: what its planes take
+JbLjWindow lj_window(const jb_device_batch *b, const jb_geometry &g, const jb_roi &r) {
+  return jbk_lj_window(b->desc.hs, b->desc.vs, g.mcus_x, g.mcus_y, r.x, r.y, r.width, r.height);
 }
 
 // the resample launch of a sub-batch of m images from image i0 on; src: the scratch
@@ -212,34 +220,41 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
       windows.push_back(jb_filter_window_of_(&b->desc, &plan.crops[i], plan.out_w, plan.out_h, plan.filter));
   const jb_roi *const written = plan.filter ? windows.data() : plan.crops;
   const auto bytes_of = [&](int64_t i) { return 3LL * written[i].width * written[i].height; };
-  // the images of the sub-batch that starts at i0; *bytes: their intermediates
-  const auto pack = [&](int64_t i0, int64_t *bytes) {
+  // JB_ARITH_LIBJPEG: the planes of every image's window are held to the same cap, in a scratch of their own
+  const bool lj = ctx->arithmetic == JB_ARITH_LIBJPEG;
+  const auto planes_of = [&](int64_t i) { return lj ? lj_window(b, g, written[i]).bytes : 0; };
+  // the images of the sub-batch that starts at i0; *bytes: their intermediates; *planes: their planes
+  const auto pack = [&](int64_t i0, int64_t *bytes, int64_t *planes) {
     int m = 1;
-    *bytes = bytes_of(i0);
-    while (i0 + m < b->n_images && m < kJbCropsPerLaunch && *bytes + bytes_of(i0 + m) <= cap) *bytes += bytes_of(i0 + m), m++;
+    *bytes = bytes_of(i0), *planes = planes_of(i0);
+    while (i0 + m < b->n_images && m < kJbCropsPerLaunch && *bytes + bytes_of(i0 + m) <= cap && *planes + planes_of(i0 + m) <= cap)
+      *bytes += bytes_of(i0 + m), *planes += planes_of(i0 + m), m++;
     return m;
   };
-  int64_t most = 0;  // the largest sub-batch: what the scratch must hold
+  int64_t most = 0, most_planes = 0;  // the largest sub-batch: what the scratches must hold
   for (int64_t i0 = 0; i0 < b->n_images;) {
-    int64_t bytes;
-    i0 += pack(i0, &bytes);
+    int64_t bytes, planes;
+    i0 += pack(i0, &bytes, &planes);
     if (bytes > most) most = bytes;
+    if (planes > most_planes) most_planes = planes;
   }
   DeviceGuard guard(ctx->device);
   const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  void *tmp = nullptr;
+  void *tmp = nullptr, *planes_d = nullptr;
   int rc = tmp_for_stream(ctx, s, (size_t)most + kTmpSlack, &tmp);
+  if (rc) return rc;
+  if (lj) rc = scratch_for_stream(ctx, ctx->planes, s, (size_t)most_planes, &planes_d);
   if (rc) return rc;
   const int per_tile = jbk_mcus_per_tile(b->desc.hs, b->desc.vs), mw = 8 * b->desc.hs, mh = 8 * b->desc.vs;
   const int64_t coef_step = b->n_images > 1 ? b->coef_image_stride : 0;
   for (int64_t i0 = 0; i0 < b->n_images;) {
-    int64_t bytes;
-    const int m = pack(i0, &bytes);
+    int64_t bytes, planes;
+    const int m = pack(i0, &bytes, &planes);
     JbCropTable table;
     JbFilterTable ftable;
     memset(&table, 0, sizeof table);
     memset(&ftable, 0, sizeof ftable);
-    int32_t most_tiles = 0;
+    int32_t most_tiles = 0, most_lj_tiles = 0;
     int64_t at = 0;
     for (int j = 0; j < m; j++) {
       const jb_roi &r = written[i0 + j];
@@ -253,6 +268,7 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
       c.tmp_offset = at;
       at += bytes_of(i0 + j);
       if (c.n_tiles > most_tiles) most_tiles = c.n_tiles;
+      if (jbk_lj_tiles(c.w, c.h) > most_lj_tiles) most_lj_tiles = jbk_lj_tiles(c.w, c.h);
     }
     jb_device_batch ib = *b;
     ib.d_coef = (const int16_t *)((const uint8_t *)b->d_coef + i0 * coef_step);
@@ -265,7 +281,13 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
     p.tiles_per_image = most_tiles;
     p.n_tiles = m * most_tiles;  // (at most 32 images' worth of tiles: no overflow)
     p.fast_store = 1;            // (the ROI stage does not look at it)
-    JB_HIP(ctx, jbk_launch_crops(p, table, b->desc.hs, b->desc.vs, s));
+    if (lj) {
+      p.tiles_per_image = most_lj_tiles;  // (the tiles of jb_libjpeg.hip's pixel kernel: 256 pixels x 4 rows of the rectangle)
+      p.n_tiles = m * most_lj_tiles;
+      JB_HIP(ctx, jbk_lj_launch_crops(p, table, b->desc.hs, b->desc.vs, planes_d, s));
+    } else {
+      JB_HIP(ctx, jbk_launch_crops(p, table, b->desc.hs, b->desc.vs, s));
+    }
     if (plan.filter) JB_HIP(ctx, jbk_filter_launch_crops(filter_args(b, plan, plane_stride, tmp, i0, m), ftable, plan.filter, plan.format, s));
     else JB_HIP(ctx, jbk_resample_launch_crops(resample_args(b, plan, plane_stride, tmp, i0, m), table, plan.format, s));
     i0 += m;
@@ -323,6 +345,40 @@ int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, con
 }
 
 
+// 3d. JB_ARITH_LIBJPEG: jb_libjpeg.hip's launch pair in the place of jbk_launch -- any format, the whole image or the
+// plan's rectangle, scale 1 (seam_check has refused another).  The planes of a sub-batch of whole images are held to the
+// cap of the resized routes' scratch (one image at the least), in the stream's scratch of their own.  p: launch_base's,
+// with the planar fields set.
+int seam_launch_lj(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const jb_geometry &g, JbLaunch p) {
+  const jb_roi whole = {0, 0, b->desc.width, b->desc.height};
+  const jb_roi &r = plan.has_roi ? plan.roi : whole;
+  if (plan.has_roi) p.roi = 1, p.roi_x = r.x, p.roi_y = r.y, p.roi_w = r.width, p.roi_h = r.height;
+  p.tiles_per_image = jbk_lj_tiles(r.width, r.height);
+  const JbLjWindow win = lj_window(b, g, r);
+  int64_t per = (int64_t)ctx->knobs.resize_tmp_bytes / win.bytes;
+  if (per < 1) per = 1;
+  if (per > b->n_images) per = b->n_images;
+  if (p.tiles_per_image < 1 || per * p.tiles_per_image > 0x7fffffffLL) return fail(ctx, JB_ERR_CAPACITY, "batch too large for one launch");
+  DeviceGuard guard(ctx->device);
+  const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  void *planes = nullptr;
+  int rc = scratch_for_stream(ctx, ctx->planes, s, (size_t)(per * win.bytes), &planes);
+  if (rc) return rc;
+  const int64_t coef_step = b->n_images > 1 ? b->coef_image_stride : 0, rgb_step = b->n_images > 1 ? b->rgb_image_stride : 0;
+  for (int64_t i0 = 0; i0 < b->n_images; i0 += per) {
+    const int64_t m = b->n_images - i0 < per ? b->n_images - i0 : per;
+    JbLaunch q = p;
+    q.coef = (const int16_t *)((const uint8_t *)b->d_coef + i0 * coef_step);
+    q.coef_image_stride = coef_step;
+    q.qtabs = (const int32_t *)((const uint8_t *)b->d_qtabs + i0 * b->qtab_image_stride);
+    q.rgb = b->d_rgb + i0 * rgb_step;
+    q.rgb_image_stride = rgb_step;
+    q.n_tiles = (int32_t)(m * p.tiles_per_image);
+    JB_HIP(ctx, jbk_lj_launch(q, b->desc.hs, b->desc.vs, planes, s));
+  }
+  return JB_OK;
+}
+
 }  // namespace
 
 // 3. the launch, on `stream` or (null) the context's primary stream; fn: the entry point's name, for the error text
@@ -338,6 +394,7 @@ int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOut
     p.rgb_plane_stride = plane_stride;
     for (int c = 0; c < 3; c++) p.scale[c] = plan.spec.scale[c], p.bias[c] = plan.spec.bias[c];
   }
+  if (ctx->arithmetic == JB_ARITH_LIBJPEG) return seam_launch_lj(ctx, b, stream, plan, g, p);
   rc = seam_tiles(ctx, b, g, plan, p);
   if (rc) return rc;
   DeviceGuard guard(ctx->device);
