@@ -501,6 +501,55 @@ int jb_ctx_set_arithmetic(jb_ctx *ctx, int arith);
 /* the context's arithmetic; a null context: JB_ARITH_REFERENCE */
 int jb_ctx_arithmetic(const jb_ctx *ctx);
 
+/* ---- orientation: the Exif Orientation tag applied on the device, in front of every output option ----
+ * Let `full` be the full-size uint8 decode [H, W, 3] of the context's arithmetic and oriented = T_o(full), T_o being
+ * what Pillow's ImageOps.exif_transpose does for the tag value o (numpy on a = full):
+ *   1  a                                  W x H        5  a.transpose(1,0,2)                   H x W
+ *   2  a[:, ::-1]                         W x H        6  a.transpose(1,0,2)[:, ::-1]          H x W
+ *   3  a[::-1, ::-1]                      W x H        7  a[::-1, ::-1].transpose(1,0,2)       H x W
+ *   4  a[::-1]                            W x H        8  a.transpose(1,0,2)[::-1]             H x W
+ * Every output option of the sections above then acts on `oriented` exactly as it is defined there for a full-size
+ * decode of the oriented size: orientation comes FIRST.  Rectangles (roi, per-image rectangles), the filters' frame
+ * extent in_size, the clamping of lo / hi and jb_filter_window are in oriented coordinates; rectangles are checked
+ * against the oriented size; buffers, strides, *width and *height are the oriented output's.  The float formats use
+ * the planar stage's expression, (float)u8 * scale[c] + bias[c], unfused.  Orientation 1 is bit for bit and launch for
+ * launch the behaviour without this section: no scratch, no extra kernel.  Any other value costs one more kernel
+ * (jb_orient.hip) and a pass through a scratch of the context (per stream, counted against JPEGBLK_RESIZE_TMP_BYTES).
+ * A scale other than 1 together with an orientation other than 1 is JB_ERR_UNSUPPORTED wherever JB_ARITH_LIBJPEG with
+ * a scale is, and nothing is uploaded or written: area reduction puts its partial boxes at the right and bottom
+ * edges, and those do not commute with a mirror.
+ * The setting belongs to the context, as the arithmetic does, and governs every later call.  JB_ORIENT_STORED (1, the
+ * default) leaves the pixels as the file stores them; 2..8 are the Exif codes, applied whatever the file says;
+ * JB_ORIENT_EXIF takes the value from the file in jb_decode_file* / jb_decode_memory* and the batch decoder
+ * (jb_exif_orientation) -- the device seam and jb_blocks_to_rgb / jb_submit / jb_submit_batch have no file, and return
+ * JB_ERR_STATE under it with nothing written.  jb_ctx_set_orientation: JB_ERR_NULL for a null context,
+ * JB_ERR_GEOMETRY for a value outside 0..8, JB_ERR_STATE while a submission of the context is in flight.
+ * Out of scope: XMP tiff:Orientation (which Pillow falls back to when Exif has no tag), Exif spread over several
+ * APP1 segments, an orientation per image inside one launch. */
+enum { JB_ORIENT_EXIF = 0, JB_ORIENT_STORED = 1 /* 2..8: the Exif codes */ };
+int jb_ctx_set_orientation(jb_ctx *ctx, int orientation);
+/* the context's orientation; a null context: JB_ORIENT_STORED */
+int jb_ctx_orientation(const jb_ctx *ctx);
+/* The Exif Orientation of a JPEG byte stream.  Walks the marker segments before the first SOS; in the first APP1 whose
+ * payload starts "Exif\0\0" reads the TIFF header (II or MM, 42, the offset of IFD0) and scans IFD0 for tag 0x0112 of
+ * type SHORT, count 1.  A value in 1..8 is returned in *orientation; everything else gives 1 with JB_OK: no such
+ * segment, no tag, another type or count, a value outside 1..8, an offset or length that leaves the segment.
+ * JB_ERR_NULL for a null argument, JB_ERR_FORMAT only when the bytes do not start with SOI.  Never reads outside
+ * [jpeg, jpeg + bytes).  XMP is not looked at.  Pure host code. */
+int jb_exif_orientation(const uint8_t *jpeg, size_t bytes, int *orientation);
+/* The size of T_o(full) for a w x h frame: h x w for 5..8.  JB_ERR_NULL; JB_ERR_GEOMETRY for a size outside 1..65535
+ * or an orientation outside 1..8.  Pure host code. */
+int jb_oriented_size(int32_t w, int32_t h, int orientation, int32_t *ow, int32_t *oh);
+/* The rectangle of the stored w x h frame that the rectangle `oriented` of T_o(full) shows: T_o of that stored
+ * rectangle IS the oriented one.  JB_ERR_NULL; JB_ERR_GEOMETRY as jb_oriented_size, or when `oriented` does not lie
+ * in the oriented frame.  Pure host code. */
+int jb_orient_map_roi(int32_t w, int32_t h, int orientation, const jb_roi *oriented, jb_roi *stored);
+/* What a call under `orientation` (1..8) at `scale` with the rectangle `roi` (NULL: none) of the oriented frame would
+ * answer before it touches a device: JB_ERR_NULL for a null descriptor, the descriptor's own errors, JB_ERR_GEOMETRY
+ * for a scale that is none or an orientation outside 0..8, JB_ERR_UNSUPPORTED for a scale other than 1 with an
+ * orientation 2..8 (JB_ORIENT_EXIF passes here: a file decides, and an entry point without one answers JB_ERR_STATE), JB_ERR_GEOMETRY for a rectangle that does not lie in the ORIENTED frame.  Pure host code. */
+int jb_orient_check(const jb_image_desc *desc, int orientation, int scale, const jb_roi *roi);
+
 /* ---- host front end ("next" rows of the scope table; reference jpeg.cpp:67-446, 826-907,
  *      include/file.hpp, include/huffman.hpp) --------------------------------------------- */
 /* Parse a JFIF byte stream and Huffman-decode it into packed int16 blocks in the order
@@ -694,6 +743,13 @@ int jb_batch_decoder_set_filter(jb_batch_decoder *dec, int filter);
  * is in flight, with JB_ERR_GEOMETRY for an unknown value, and JB_ARITH_LIBJPEG while the scale is not 1 (and
  * jb_batch_decoder_set_scale(!= 1) under JB_ARITH_LIBJPEG) with JB_ERR_UNSUPPORTED. */
 int jb_batch_decoder_set_arithmetic(jb_batch_decoder *dec, int arith);
+/* The orientation (JB_ORIENT_*, 2..8; see "orientation") of the batch decoder's later runs and submissions.  Applies to
+ * every device of a multi-device decoder and to both sides of submit / collect.  Under JB_ORIENT_EXIF every file's tag
+ * is read when its headers are parsed; a group is one geometry and one orientation.  Reported widths and heights, the
+ * decoder's rectangle and the rectangles of run_crops are oriented.  Refused with JB_ERR_STATE while a batch is in
+ * flight, with JB_ERR_GEOMETRY for a value outside 0..8, and any value but JB_ORIENT_STORED while the scale is not 1
+ * (and jb_batch_decoder_set_scale(!= 1) under such a value) with JB_ERR_UNSUPPORTED. */
+int jb_batch_decoder_set_orientation(jb_batch_decoder *dec, int orientation);
 /* Output sink replacing the reference's X11 window / unused BMP writer (display.hpp,
  * jpeg.cpp:462-509): binary PPM (P6). */
 int jb_write_ppm(const char *path, const uint8_t *rgb, int32_t width, int32_t height,

@@ -84,6 +84,8 @@ class Roi(ctypes.Structure):
 FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC = 0, 1, 2
 # "decoder arithmetic" (include/jpegblk.h): the reference program's, or libjpeg's -- Pillow's decode bit for bit
 ARITH_REFERENCE, ARITH_LIBJPEG = 0, 1
+# "orientation" (include/jpegblk.h): the file's Exif tag, or the pixels as stored; 2..8 are the Exif codes themselves
+ORIENT_EXIF, ORIENT_STORED = 0, 1
 
 
 class Resize(ctypes.Structure):
@@ -362,6 +364,13 @@ def lib():
     L.jb_batch_decoder_set_arithmetic.argtypes = [vp, ctypes.c_int]
     L.jb_ctx_set_arithmetic.argtypes = [vp, ctypes.c_int]
     L.jb_ctx_arithmetic.argtypes = [vp]
+    L.jb_ctx_set_orientation.argtypes = [vp, ctypes.c_int]
+    L.jb_ctx_orientation.argtypes = [vp]
+    L.jb_batch_decoder_set_orientation.argtypes = [vp, ctypes.c_int]
+    L.jb_exif_orientation.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
+    L.jb_oriented_size.argtypes = [i32, i32, ctypes.c_int, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.jb_orient_map_roi.argtypes = [i32, i32, ctypes.c_int, pr, pr]
+    L.jb_orient_check.argtypes = [pd, ctypes.c_int, ctypes.c_int, pr]
     L.jb_write_ppm.argtypes = [ctypes.c_char_p, vp, i32, i32, i64]
     L.jb_write_bmp.argtypes = [ctypes.c_char_p, vp, i32, i32, i64]
     if L.jb_abi_version() != 1:
@@ -401,6 +410,32 @@ def scaled_size(width, height, scale):
     return w.value, h.value
 
 
+def exif_orientation(jpeg_bytes):
+    """jb_exif_orientation: the Exif Orientation tag (1..8) of a JFIF byte string; 1 when it has none or the tag is not
+    a SHORT in 1..8.  JbError(-8) when the bytes do not start with SOI."""
+    buf = np.frombuffer(jpeg_bytes, dtype=np.uint8)
+    o = ctypes.c_int(1)
+    if buf.size == 0:
+        raise JbError(-8, "no bytes")
+    _check(lib().jb_exif_orientation(_ptr(buf), buf.size, ctypes.byref(o)))
+    return o.value
+
+
+def oriented_size(width, height, orientation):
+    """jb_oriented_size: (w, h) of the image once the orientation (1..8) is applied: swapped for 5..8."""
+    w, h = ctypes.c_int32(), ctypes.c_int32()
+    _check(lib().jb_oriented_size(int(width), int(height), int(orientation), ctypes.byref(w), ctypes.byref(h)))
+    return w.value, h.value
+
+
+def orient_map_roi(width, height, orientation, roi):
+    """jb_orient_map_roi: the rectangle (x, y, w, h) of the stored width x height frame that shows as `roi` of the
+    oriented one."""
+    out = Roi()
+    _check(lib().jb_orient_map_roi(int(width), int(height), int(orientation), ctypes.byref(_Request(roi=roi).roi), ctypes.byref(out)))
+    return out.x, out.y, out.width, out.height
+
+
 def output_bytes(width, height, fmt=FMT_RGB_U8_HWC):
     """jb_output_bytes: bytes of one width x height image in a format (tight rows and planes)."""
     n = ctypes.c_int64()
@@ -434,15 +469,29 @@ def entropy_decode(jpeg_bytes, headers_only=False, n_threads=1):
 class Context:
     """jb_ctx: one device, one stream, a ring of staging slots."""
 
-    def __init__(self, device=0, max_coef_bytes=0, max_rgb_bytes=0, n_slots=2, arithmetic=ARITH_REFERENCE):
+    def __init__(self, device=0, max_coef_bytes=0, max_rgb_bytes=0, n_slots=2, arithmetic=ARITH_REFERENCE, orientation=ORIENT_STORED):
         self._h = ctypes.c_void_p()
         _check(lib().jb_ctx_create(device, max_coef_bytes, max_rgb_bytes, n_slots, ctypes.byref(self._h)))
-        if arithmetic != ARITH_REFERENCE:
-            try:
+        try:
+            if arithmetic != ARITH_REFERENCE:
                 self.set_arithmetic(arithmetic)
-            except JbError:
-                self.close()
-                raise
+            if orientation != ORIENT_STORED:
+                self.set_orientation(orientation)
+        except JbError:
+            self.close()
+            raise
+
+    def set_orientation(self, orientation):
+        """jb_ctx_set_orientation: ORIENT_STORED (the pixels as the file stores them), 2..8 (that Exif code, whatever the
+        file says) or ORIENT_EXIF (decode_file / decode_memory take the file's own tag; the seam has no file: JbError -7
+        there).  Every later call of this context then applies it on the device BEFORE fmt, roi, resize, crops and
+        filter, whose rectangles and sizes are the oriented image's.  JbError -2 for a value outside 0..8, -7 while a
+        submission is in flight; a scale other than 1 with an orientation other than 1 is JbError -9 at the call."""
+        _check(lib().jb_ctx_set_orientation(self._h, int(orientation)), self._h)
+
+    @property
+    def orientation(self):
+        return lib().jb_ctx_orientation(self._h)
 
     def set_arithmetic(self, arithmetic):
         """jb_ctx_set_arithmetic: ARITH_REFERENCE, or ARITH_LIBJPEG -- every later call of this context then decodes with
@@ -513,29 +562,50 @@ class Context:
         _check(lib().jb_ctx_synchronize(self._h), self._h)
 
     # -- the seam, host buffers --------------------------------------------------------------
+    def _host_output_size(self, desc):
+        """(w, h) of what the host seam writes for `desc` under this context's orientation: the oriented frame's.
+        ORIENT_EXIF has no file here: JbError -7, as the C entry points answer, before any buffer is sized."""
+        o = self.orientation
+        if o == ORIENT_EXIF:
+            raise JbError(-7, "ORIENT_EXIF takes the orientation from a file: the host seam has none (set 1..8)")
+        return oriented_size(desc.width, desc.height, o)
+
     def blocks_to_rgb(self, desc, coef, qtabs, stride=None):
+        """-> RGB [H, W, 3] of the ORIENTED frame (the context's orientation: [W, H, 3]-shaped for 5..8); stride: bytes
+        between the rows of that output, at least 3 * its width."""
         coef = np.ascontiguousarray(coef, dtype=np.int16)
         q = np.ascontiguousarray(qtabs, dtype=np.uint16).reshape(4, 64)
-        stride = stride or 3 * desc.width
-        out = np.zeros((desc.height, stride), np.uint8)
+        w, h = self._host_output_size(desc)
+        stride = stride or 3 * w
+        if stride < 3 * w:
+            raise JbError(-2, f"stride {stride} < 3 * {w}")
+        out = np.zeros((h, stride), np.uint8)
         _check(lib().jb_blocks_to_rgb(self._h, ctypes.byref(desc), _ptr(coef), _ptr(q), _ptr(out), stride), self._h)
-        return out[:, :3 * desc.width].reshape(desc.height, desc.width, 3)
+        return out[:, :3 * w].reshape(h, w, 3)
 
     def submit(self, desc, coef, qtabs, out, stride=None):
-        """coef / out: numpy arrays that stay alive until wait(ticket)."""
+        """coef / out: numpy arrays that stay alive until wait(ticket).  out and stride are the ORIENTED output's (the
+        context's orientation): h rows of `stride` >= 3 * w bytes with (w, h) = oriented_size(desc.width, desc.height,
+        orientation); an `out` smaller than that is JbError -2 here, before anything is written."""
         q = np.ascontiguousarray(qtabs, dtype=np.uint16).reshape(4, 64)
+        w, h = self._host_output_size(desc)
+        stride = stride or 3 * w
+        if stride < 3 * w or out.nbytes < (h - 1) * stride + 3 * w:
+            raise JbError(-2, f"out holds {out.nbytes} bytes, the {w} x {h} output at stride {stride} needs {(h - 1) * stride + 3 * w}")
         t = ctypes.c_int(-1)
-        _check(lib().jb_submit(self._h, ctypes.byref(desc), _ptr(coef), _ptr(q), _ptr(out),
-                               stride or 3 * desc.width, ctypes.byref(t)), self._h)
+        _check(lib().jb_submit(self._h, ctypes.byref(desc), _ptr(coef), _ptr(q), _ptr(out), stride, ctypes.byref(t)), self._h)
         return t.value
 
     def submit_batch(self, desc, coef, qtabs, out):
         """jb_submit_batch: n images of one geometry in one submission.  coef int16 [n, blocks, 64],
-        qtabs uint16 [n, 4, 64], out uint8 [n, H, 3*W] (tight rows); all C-contiguous and alive
-        until wait()."""
+        qtabs uint16 [n, 4, 64], out uint8 [n, H, 3*W] (tight rows) with W x H the ORIENTED frame under the
+        context's orientation (JbError -2 for an `out` smaller than that); all C-contiguous and alive until wait()."""
         n = coef.shape[0]
         assert coef.flags.c_contiguous and qtabs.flags.c_contiguous and out.flags.c_contiguous
         assert qtabs.shape == (n, 4, 64) and out.shape[0] == n
+        w, h = self._host_output_size(desc)
+        if out.nbytes < n * 3 * w * h:
+            raise JbError(-2, f"out holds {out.nbytes} bytes, {n} images of {w} x {h} need {n * 3 * w * h}")
         t = ctypes.c_int()
         _check(lib().jb_submit_batch(self._h, ctypes.byref(desc), n, _ptr(coef), _ptr(qtabs), _ptr(out), ctypes.byref(t)), self._h)
         return t.value
@@ -648,10 +718,12 @@ class BatchDecoder:
     on the device, so files of any size and layout give outputs of one size.  filter (jb_batch_decoder_set_filter; with
     resize): FILTER_BILINEAR / FILTER_BICUBIC put Pillow's 8-bit resampling in the area filter's place, for the target
     size and for the per-image rectangles of run(crops=) alike.  arithmetic (jb_batch_decoder_set_arithmetic):
-    ARITH_LIBJPEG decodes every file as libjpeg does, bit for bit (not with a scale)."""
+    ARITH_LIBJPEG decodes every file as libjpeg does, bit for bit (not with a scale).  orientation
+    (jb_batch_decoder_set_orientation): ORIENT_EXIF applies every file's own Exif tag, 2..8 that code to every file, in
+    front of every other option: sizes, roi and crops are then the oriented image's (not with a scale)."""
 
     def __init__(self, n_threads=8, device=0, max_coef_bytes=0, max_rgb_bytes=0, arena_bytes=0, devices=None, scale=1, fmt=None,
-                 roi=None, resize=None, filter=FILTER_AREA, arithmetic=ARITH_REFERENCE):
+                 roi=None, resize=None, filter=FILTER_AREA, arithmetic=ARITH_REFERENCE, orientation=ORIENT_STORED):
         _Request(scale, fmt, roi, resize, filter=filter)   # (roi or resize with a scale: JbError(-9) before anything is created)
         self._h = ctypes.c_void_p()
         if devices is not None:
@@ -680,9 +752,17 @@ class BatchDecoder:
                 self.set_filter(filter)
             if arithmetic != ARITH_REFERENCE:
                 self.set_arithmetic(arithmetic)
+            if orientation != ORIENT_STORED:
+                self.set_orientation(orientation)
         except JbError:
             self.close()
             raise
+
+    def set_orientation(self, orientation):
+        """jb_batch_decoder_set_orientation: ORIENT_STORED, ORIENT_EXIF or 2..8 for later runs and submissions (JbError
+        -7 while a batch is in flight, -2 for a value outside 0..8, -9 for any value but ORIENT_STORED while the
+        decoder's scale is not 1)."""
+        _check(lib().jb_batch_decoder_set_orientation(self._h, int(orientation)))
 
     def set_output_format(self, fmt):
         """jb_batch_decoder_set_output_format: the format of later runs and submissions (JbError -7 while a batch is

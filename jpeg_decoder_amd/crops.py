@@ -1,7 +1,8 @@
 """Rectangles for the per-image crops of a batch (Context.blocks_to_rgb_device(..., crops=), BatchDecoder.run(..., crops=)).
 
 Pure Python over a numpy.random.Generator: the rectangles of a batch can be drawn from the sizes that
-entropy_decode(jpeg_bytes, headers_only=True) reports, before anything is decoded.
+entropy_decode(jpeg_bytes, headers_only=True) reports, before anything is decoded.  Under an orientation (ORIENT_EXIF or
+2..8) rectangles are in oriented coordinates: draw them from oriented_size(width, height, exif_orientation(jpeg_bytes)).
 """
 import math
 

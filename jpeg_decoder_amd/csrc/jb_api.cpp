@@ -402,6 +402,23 @@ int jb_ctx_set_arithmetic(jb_ctx *ctx, int arith) {
 
 int jb_ctx_arithmetic(const jb_ctx *ctx) { return ctx ? ctx->arithmetic : JB_ARITH_REFERENCE; }
 
+int jb_ctx_set_orientation(jb_ctx *ctx, int orientation) {
+  if (!ctx) return fail(nullptr, JB_ERR_NULL, "jb_ctx_set_orientation: ctx is NULL");
+  if (orientation < 0 || orientation > 8) return fail(ctx, JB_ERR_GEOMETRY, "jb_ctx_set_orientation: %d is outside 0..8", orientation);
+  // (as jb_ctx_set_arithmetic: not while a submission of the ring is in flight)
+  DeviceGuard guard(ctx->device);
+  for (int i = 0; i < ctx->n_slots; i++) {
+    Slot &s = ctx->slots[i];
+    if (!s.busy) continue;
+    if (s.dl_pending.load(std::memory_order_acquire) || hipEventQuery(s.done) == hipErrorNotReady)
+      return fail(ctx, JB_ERR_STATE, "jb_ctx_set_orientation: a submission is in flight (wait for it first)");
+  }
+  ctx->orientation = orientation;
+  return JB_OK;
+}
+
+int jb_ctx_orientation(const jb_ctx *ctx) { return ctx ? ctx->orientation : JB_ORIENT_STORED; }
+
 long long jb_ctx_device_entropy_images(const jb_ctx *ctx) { return ctx ? ctx->n_device_entropy : 0; }
 
 int jb_ctx_last_desc(const jb_ctx *ctx, jb_image_desc *out) {
@@ -527,6 +544,7 @@ int submit_begin(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const JbO
   if (n_images < 1 || n_images > kMaxBatch) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d outside 1..%d", n_images, kMaxBatch);
   if (plan.status != JB_OK) return fail(ctx, plan.status, "submit: %s", plan.why);
   if (ctx->arithmetic == JB_ARITH_LIBJPEG && plan.scale != 1) return fail(ctx, JB_ERR_UNSUPPORTED, "submit: %s", kJbArithScaleText);
+  if (plan.orient == JB_ORIENT_EXIF) return fail(ctx, JB_ERR_STATE, "submit: %s", kJbOrientExifText);
   // tight rows on the device (12-byte stores need no alignment); a planar format: tight rows of a plane, tight planes
   if (plan.planar && rgb_stride != plan.row_stride) return fail(ctx, JB_ERR_GEOMETRY, "planar output has tight rows");
   if (rgb_stride < plan.row_stride) return fail(ctx, JB_ERR_GEOMETRY, "rgb_stride %lld < 3*width", (long long)rgb_stride);
@@ -842,14 +860,14 @@ int jb_submit(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const
               uint8_t *rgb, int64_t rgb_stride, int *ticket) {
   if (!ctx) return fail(nullptr, JB_ERR_NULL, "jb_submit: ctx is NULL");
   if (!desc || !coef || !qtabs || !rgb || !ticket) return fail(ctx, JB_ERR_NULL, "jb_submit: NULL pointer");
-  return submit_impl(ctx, desc, 1, coef, qtabs, rgb, rgb_stride, ticket, jb_out_plan_(desc, 1, nullptr), false);
+  return submit_impl(ctx, desc, 1, coef, qtabs, rgb, rgb_stride, ticket, jb_out_plan_(desc, 1, nullptr, nullptr, nullptr, nullptr, 0, ctx->orientation), false);
 }
 
 int jb_submit_batch(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef,
                     const uint16_t *qtabs, uint8_t *rgb, int *ticket) {
   if (!ctx) return fail(nullptr, JB_ERR_NULL, "jb_submit_batch: ctx is NULL");
   if (!desc || !coef || !qtabs || !rgb || !ticket) return fail(ctx, JB_ERR_NULL, "jb_submit_batch: NULL pointer");
-  const JbOutPlan plan = jb_out_plan_(desc, 1, nullptr);
+  const JbOutPlan plan = jb_out_plan_(desc, 1, nullptr, nullptr, nullptr, nullptr, 0, ctx->orientation);
   return submit_impl(ctx, desc, n_images, coef, qtabs, rgb, plan.row_stride, ticket, plan, false);
 }
 

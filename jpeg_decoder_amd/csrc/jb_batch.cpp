@@ -43,6 +43,7 @@ struct OutputRequest {
   JbTarget target = {};      // (target.filter: always the decoder's filter, with or without a target size)
   const JbTarget *target_ptr() const { return has_resize ? &target : nullptr; }
   int arith = JB_ARITH_REFERENCE;  // "decoder arithmetic": what the decoder's contexts compute in (never LIBJPEG with a scale)
+  int orient = JB_ORIENT_STORED;   // "orientation": JB_ORIENT_* or 2..8 (never another value than 1 with a scale)
   // can it be had at all?  The plan function decides (jb_plan.h), here for an image of one pixel -- with a rectangle,
   // for the largest frame there is (JB_ERR_GEOMETRY: no frame holds the rectangle)
   int status() const {
@@ -243,7 +244,11 @@ void parse_one(Parsed &p, const OutputRequest &out, const jb_roi *crop = nullptr
     p.error = jb_last_error(nullptr);
     return;
   }
-  p.plan = jb_out_plan_(&p.desc, out.scale, &out.spec, crop ? crop : out.roi_ptr(), out.target_ptr());
+  // "orientation": the decoder's, or this file's own tag (the Exif segment lies in front of the frame header that
+  // has just been parsed, so a head that parses holds it)
+  int orient = out.orient;
+  if (orient == JB_ORIENT_EXIF && jb_exif_orientation(p.bytes.data(), p.bytes.size(), &orient) != JB_OK) orient = JB_ORIENT_STORED;
+  p.plan = jb_out_plan_(&p.desc, out.scale, &out.spec, crop ? crop : out.roi_ptr(), out.target_ptr(), nullptr, 0, orient);
   p.status = p.plan.status;
   if (p.status == JB_OK) p.geo.rgb_bytes = p.plan.image_bytes;
   else p.error = p.plan.why;
@@ -290,7 +295,8 @@ constexpr int kMaxGroup = 64;
 bool same_geometry(const Parsed &a, const Parsed &b) {
   return a.desc.width == b.desc.width && a.desc.height == b.desc.height && a.desc.hs == b.desc.hs &&
          a.desc.vs == b.desc.vs && a.desc.qtab_id[0] == b.desc.qtab_id[0] &&
-         a.desc.qtab_id[1] == b.desc.qtab_id[1] && a.desc.qtab_id[2] == b.desc.qtab_id[2];
+         a.desc.qtab_id[1] == b.desc.qtab_id[1] && a.desc.qtab_id[2] == b.desc.qtab_id[2] &&
+         a.plan.orient == b.plan.orient;  // (a group is one launch, a launch one orientation)
 }
 
 // a group in flight in one of the thread's slots
@@ -600,7 +606,7 @@ struct LaneWorker {
     std::vector<jb_roi> crops;
     if (r.rois) {
       for (int j = 0; j < f.n; j++) crops.push_back(parsed[(size_t)(f.k + j)].plan.roi);
-      plan = jb_out_plan_(&head.desc, r.out.scale, &r.out.spec, nullptr, r.out.target_ptr(), crops.data(), f.n);
+      plan = jb_out_plan_(&head.desc, r.out.scale, &r.out.spec, nullptr, r.out.target_ptr(), crops.data(), f.n, head.plan.orient);
     }
     double a = jb_now_s_();
     // every copy of the submission is pinned <-> device, so this returns at once and the
@@ -1379,6 +1385,7 @@ extern "C" int jb_batch_decoder_set_scale(jb_batch_decoder *d, int denom) {
   OutputRequest out = d->out;
   out.scale = denom;
   if (denom != 1 && out.arith == JB_ARITH_LIBJPEG) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_scale: " kJbArithScaleText);
+  if (denom != 1 && out.orient != JB_ORIENT_STORED) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_scale: " kJbOrientScaleText);
   if (out.status() == JB_ERR_UNSUPPORTED)
     return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_scale: a planar output format, a rectangle or a target size is set: it cannot be combined with a scale");
   set_output_all(d, out);
@@ -1448,6 +1455,18 @@ extern "C" int jb_batch_decoder_set_arithmetic(jb_batch_decoder *d, int arith) {
   if (arith == JB_ARITH_LIBJPEG && d->out.scale != 1) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_arithmetic: " kJbArithScaleText);
   OutputRequest out = d->out;
   out.arith = arith;
+  set_output_all(d, out);
+  return JB_OK;
+}
+
+extern "C" int jb_batch_decoder_set_orientation(jb_batch_decoder *d, int orientation) {
+  if (!d) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_set_orientation: decoder is NULL");
+  if (orientation < 0 || orientation > 8) return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_set_orientation: outside 0..8");
+  if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_orientation: batches are in flight (collect them first)");
+  if (orientation != JB_ORIENT_STORED && d->out.scale != 1)
+    return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_orientation: " kJbOrientScaleText);
+  OutputRequest out = d->out;
+  out.orient = orientation;
   set_output_all(d, out);
   return JB_OK;
 }

@@ -98,6 +98,9 @@ struct jb_ctx {
   // pixel launch that fills it reads the planes.
   int arithmetic = JB_ARITH_REFERENCE;
   std::map<hipStream_t, Tmp> planes;
+  // "Orientation" (include/jpegblk.h): JB_ORIENT_* or 2..8, what the plans of this context's later calls are made for
+  // (jb_plan.h: the plan carries the value to the launch).  Its intermediates live in `tmp`.
+  int orientation = JB_ORIENT_STORED;
 };
 
 // the error text of a failed call, formatted: into the context (ctx may be null) and the calling thread (jb_fail_)

@@ -431,6 +431,9 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
   if (!jpeg || !rgb || !width || !height) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_memory: NULL pointer");
   *rgb = nullptr;
   if (denom != 1 && denom != 2 && denom != 4 && denom != 8) return jb_fail_(ctx, JB_ERR_GEOMETRY, "jb_decode_memory_scaled: denom is not 1, 2, 4 or 8");
+  // "orientation" (include/jpegblk.h): the context's, or under JB_ORIENT_EXIF the file's own (1 when it has none)
+  int orient = jb_ctx_orientation(ctx);
+  if (orient == JB_ORIENT_EXIF && jb_exif_orientation(jpeg, jpeg_bytes, &orient) != JB_OK) orient = JB_ORIENT_STORED;
   // The entropy stage of a baseline file can run on the device too (jb_huff.hip): the host then only
   // parses the headers and removes the byte stuffing.  One image is one latency-bound submission
   // (a dozen and a half launches: about 1 ms whatever the size, then ~0.4 ms per megabyte of scan)
@@ -456,7 +459,7 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
       if (jb_huff_prepare_(jpeg, jpeg_bytes, job.get(), nullptr, knobs.chunk_bytes) == JB_OK && jb_huff_worth_it_(*job, min_int) &&
           (forced || job->scan_len >= kAutoDeviceScan)) {
         const double t1 = timing ? jb_now_s_() : 0;
-        const JbOutPlan plan = jb_out_plan_(&job->desc, denom, spec, roi, target);
+        const JbOutPlan plan = jb_out_plan_(&job->desc, denom, spec, roi, target, nullptr, 0, orient);
         if (plan.status != JB_OK) return jb_fail_(ctx, plan.status, plan.why);
         uint8_t *out = jb_alloc_pixels_((size_t)plan.image_bytes);
         if (!out) return jb_fail_(ctx, JB_ERR_CAPACITY, "out of host memory");
@@ -483,7 +486,7 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
   jb_geometry g;
   rc = jb_geometry_of(&desc, &g);
   if (rc) return jb_fail_(ctx, rc, "bad frame geometry");
-  const JbOutPlan plan = jb_out_plan_(&desc, denom, spec, roi, target);
+  const JbOutPlan plan = jb_out_plan_(&desc, denom, spec, roi, target, nullptr, 0, orient);
   if (plan.status != JB_OK) return jb_fail_(ctx, plan.status, plan.why);
   // the staging ring follows the frame (a context sized for another image, or created with (0,0))
   rc = jb_ctx_reserve(ctx, (size_t)g.coef_bytes, (size_t)plan.image_bytes);

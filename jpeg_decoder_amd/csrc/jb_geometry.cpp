@@ -6,6 +6,7 @@
 
 #include "../../include/jpegblk.h"
 #include "jb_filter.h"
+#include "jb_orient.h"
 #include "jb_plan.h"
 
 extern "C" {
@@ -132,6 +133,36 @@ int jb_filter_window(const jb_image_desc *d, const jb_roi *roi, const jb_resize 
   return JB_OK;
 }
 
+int jb_oriented_size(int32_t w, int32_t h, int o, int32_t *ow, int32_t *oh) {
+  if (!ow || !oh) return JB_ERR_NULL;
+  if (w < 1 || h < 1 || w > 65535 || h > 65535 || o < 1 || o > 8) return JB_ERR_GEOMETRY;
+  const bool swap = jb_orient_bits(o).transpose != 0;
+  *ow = swap ? h : w, *oh = swap ? w : h;
+  return JB_OK;
+}
+
+int jb_orient_map_roi(int32_t w, int32_t h, int o, const jb_roi *r, jb_roi *stored) {
+  if (!r || !stored) return JB_ERR_NULL;
+  int32_t ow, oh;
+  const int rc = jb_oriented_size(w, h, o, &ow, &oh);
+  if (rc != JB_OK) return rc;
+  if (!jb_roi_fits_(r, ow, oh)) return JB_ERR_GEOMETRY;
+  // jb_orient.h: u runs along the stored rows' index (y), v along the stored columns' (x)
+  const JbOrientBits b = jb_orient_bits(o);
+  const int32_t u0 = b.transpose ? r->x : r->y, ul = b.transpose ? r->width : r->height;
+  const int32_t v0 = b.transpose ? r->y : r->x, vl = b.transpose ? r->height : r->width;
+  *stored = jb_roi{b.flip_x ? w - v0 - vl : v0, b.flip_y ? h - u0 - ul : u0, vl, ul};
+  return JB_OK;
+}
+
+int jb_orient_check(const jb_image_desc *d, int orientation, int scale, const jb_roi *roi) {
+  if (!d) return JB_ERR_NULL;
+  jb_geometry g;
+  const int rc = jb_geometry_of(d, &g);
+  if (rc != JB_OK) return rc;
+  return jb_out_plan_(d, scale, nullptr, roi, nullptr, nullptr, 0, orientation).status;
+}
+
 int jb_resolve_qtabs(const jb_image_desc *d, const uint16_t *qtabs, int32_t *out192) {
   if (!d || !qtabs || !out192) return JB_ERR_NULL;
   for (int c = 0; c < 3; c++) {
@@ -155,10 +186,11 @@ jb_roi jb_filter_window_of_(const jb_image_desc *d, const jb_roi *roi, int32_t o
 
 // jb_plan.h: the only place that turns (frame, scale, spec, rectangle, target) into the output's sizes and strides
 JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *spec, const jb_roi *roi, const JbTarget *target,
-                       const jb_roi *crops, int n_crops) {
+                       const jb_roi *crops, int n_crops, int orientation) {
   JbOutPlan p;
   memset(&p, 0, sizeof p);
   p.bad_crop = -1;
+  p.orient = 1;
   auto refuse = [&p](int status, const char *why) {
     p.status = status, p.why = why;
     return p;
@@ -167,6 +199,17 @@ JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *
   int32_t out_w = 0, out_h = 0;
   if (jb_scaled_size(d->width, d->height, scale, &out_w, &out_h) != JB_OK)
     return refuse(JB_ERR_GEOMETRY, "scale is not 1, 2, 4 or 8 (or the image size is outside 1..65535)");
+  // "orientation": everything below sees the oriented frame
+  if (orientation < 0 || orientation > 8) return refuse(JB_ERR_GEOMETRY, "orientation is outside 0..8");
+  if (orientation > 1 && scale != 1) return refuse(JB_ERR_UNSUPPORTED, kJbOrientScaleText);  // (0: JB_ERR_STATE at the launch, or the file decides)
+  jb_image_desc oriented;
+  if (jb_orient_bits(orientation).transpose) {
+    oriented = *d;
+    oriented.width = d->height, oriented.height = d->width;
+    d = &oriented;
+    const int32_t t = out_w;
+    out_w = out_h, out_h = t;
+  }
   if (spec && spec->format == JB_FMT_RGB_U8_HWC) {
     if (spec->reserved != 0) return refuse(JB_ERR_GEOMETRY, "output spec: reserved must be 0");
     spec = nullptr;  // (the other fields are not looked at)
@@ -245,6 +288,7 @@ JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *
     out_w = target->w, out_h = target->h;
   }
   p.why = "";
+  p.orient = orientation;
   p.scale = scale;
   p.out_w = out_w, p.out_h = out_h;
   p.esize = esize;

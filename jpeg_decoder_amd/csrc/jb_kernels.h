@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "jb_knobs.h"
+#include "jb_orient.h"
 
 // Kernel arguments of one launch: a batch of images of identical geometry.
 struct JbLaunch {
@@ -142,6 +143,12 @@ struct JbFilter {
 hipError_t jbk_filter_launch(const JbFilter &p, int filter, int format, hipStream_t stream);
 // the same with a geometry per image (p.one is not looked at); at most kJbCropsPerLaunch images
 hipError_t jbk_filter_launch_crops(const JbFilter &p, const JbFilterTable &table, int filter, int format, hipStream_t stream);
+
+// "Orientation" (jb_orient.hip; the arguments are described in jb_orient.h).  One 256-lane workgroup per 64 x 64 tile of
+// source pixels.  More than 2^31 - 1 workgroups, or an argument outside its range: hipErrorInvalidValue.
+hipError_t jbk_orient_launch(const JbOrient &p, int format, hipStream_t stream);
+// format 0, tight, a source and a destination per image (at most kJbCropsPerLaunch images)
+hipError_t jbk_orient_launch_table(const JbOrient &p, const JbOrientTable &table, hipStream_t stream);
 
 // Device-side entropy decoder (jb_huff.hip); structures in jb_huff.h.
 struct JbHuffLaunch;

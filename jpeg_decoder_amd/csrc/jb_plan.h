@@ -16,7 +16,7 @@ struct JbOutPlan {
   // JB_ERR_GEOMETRY (an unknown filter, or the target's reserved != 0), JB_ERR_STATE (a filter other than 0 without a
   // target size), JB_ERR_UNSUPPORTED (more than kJbFilterMaxTaps taps on an axis; bad_crop with per-image rectangles).  Whoever uses a plan reports it where the old code checked the
   // scale: behind the descriptor's own errors.  `why` is the text for jb_last_error (of the last plan this thread made,
-  // when it names sizes); the other fields are 0 on failure.
+  // when it names sizes); the other fields are 0 on failure (orient: 1).
   int status;
   const char *why;
   int32_t scale;          // 1, 2, 4, 8
@@ -49,6 +49,10 @@ struct JbOutPlan {
   const jb_roi *crops;
   int32_t n_crops;
   int32_t bad_crop;  // status == JB_ERR_GEOMETRY because of a rectangle: which one; else -1
+  // "orientation" (include/jpegblk.h): the plan was made for T_o of the frame -- every field above is in oriented
+  // coordinates, of the frame with width and height swapped for 5..8.  1: none.  0 (JB_ORIENT_EXIF, which only a file
+  // resolves): a plan of the stored frame that no launch takes (JB_ERR_STATE where the launch is asked for).
+  int32_t orient;
 };
 
 // a target size for jb_out_plan_, and the filter that gets there (JB_FILTER_*; 0: the exact area resize).  w = h = 0 with
@@ -62,10 +66,15 @@ struct JbTarget {
 // spec: null or format 0 = interleaved uint8.  Beyond `reserved` on a format-0 spec, the spec's own fields (plane_stride
 // against a row stride, finite scale / bias) are jb_output_spec_check's, which needs the caller's strides.
 // roi: null = the whole image.  target: null = the size of the image (at the scale) or of the rectangle.
+// orientation: JB_ORIENT_* or 2..8; desc stays the STORED frame, the plan is that of the oriented one (a value outside
+// 0..8: JB_ERR_GEOMETRY, behind the scale's own check; 2..8 with a scale other than 1: JB_ERR_UNSUPPORTED, behind that).
 // crops: null = none; else n_crops rectangles, one per image of the launch (n_crops < 1: nothing to check); wants a target
 // and no roi.
 // the source window of one rectangle (null: the whole frame) under a plan's filter and target: what jb_filter_window
 // returns, without its checks (the plan has made them)
 jb_roi jb_filter_window_of_(const jb_image_desc *desc, const jb_roi *roi, int32_t out_w, int32_t out_h, int filter);
 JbOutPlan jb_out_plan_(const jb_image_desc *desc, int scale, const jb_output_spec *spec, const jb_roi *roi = nullptr,
-                       const JbTarget *target = nullptr, const jb_roi *crops = nullptr, int n_crops = 0);
+                       const JbTarget *target = nullptr, const jb_roi *crops = nullptr, int n_crops = 0, int orientation = 1);
+// "orientation": the refusal of a plan with orient == 0 at a launch, and of a scale with an orientation
+#define kJbOrientExifText "JB_ORIENT_EXIF takes the orientation from a file: this entry point has none (set 1..8)"
+#define kJbOrientScaleText "an orientation other than 1 cannot be combined with a scale other than 1"

@@ -34,6 +34,7 @@ int seam_check(jb_ctx *ctx, const jb_device_batch *b, const JbOutPlan &plan, con
   if (b->n_images < 1) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d", b->n_images);
   if (plan.status != JB_OK) return fail(ctx, plan.status, "%s: %s", fn, plan.why);
   if (ctx->arithmetic == JB_ARITH_LIBJPEG && plan.scale != 1) return fail(ctx, JB_ERR_UNSUPPORTED, "%s: %s", fn, kJbArithScaleText);
+  if (plan.orient == JB_ORIENT_EXIF) return fail(ctx, JB_ERR_STATE, "%s: %s", fn, kJbOrientExifText);
   *plane_stride = 0;
   if (plan.planar) {
     if (jb_output_spec_check(&plan.spec, plan.out_h, b->rgb_row_stride) != JB_OK)
@@ -203,6 +204,19 @@ JbFilterRow filter_row(const jb_roi &r, const jb_roi &win, int64_t tmp_offset) {
   return JbFilterRow{r.x, r.y, r.width, r.height, win.x, win.y, win.width, win.height, tmp_offset};
 }
 
+// "orientation": the batch as the resample and filter launches see it -- the oriented frame; everything else is b's
+jb_device_batch oriented_batch(const jb_device_batch *b, int orientation) {
+  jb_device_batch ob = *b;
+  if (jb_orient_bits(orientation).transpose) ob.desc.width = b->desc.height, ob.desc.height = b->desc.width;
+  return ob;
+}
+// the rectangle of b's stored frame that shows as `r` of the oriented one (r lies in it: the plan has checked)
+jb_roi stored_rect(const jb_device_batch *b, int orientation, const jb_roi &r) {
+  jb_roi st = r;
+  (void)jb_orient_map_roi(b->desc.width, b->desc.height, orientation, &r, &st);
+  return st;
+}
+
 // 3c. a plan with per-image rectangles (plan.crops) and a target size: as 3b, with the rectangles of a sub-batch in a
 // table that travels in the arguments of both kernels.  Consecutive images are packed into a sub-batch while their
 // intermediates -- back to back, tight, at the prefix sums of 3 * w_i * h_i -- fit the cap of the stream's scratch (an
@@ -214,12 +228,21 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
                       int64_t plane_stride) {
   if (plan.n_crops != b->n_images) return fail(ctx, JB_ERR_GEOMETRY, "%s: %d rectangles for %d images", fn, plan.n_crops, b->n_images);
   const int64_t cap = (int64_t)ctx->knobs.resize_tmp_bytes;
+  // "orientation": the plan's rectangles and windows are the oriented frame's (ob: the batch with that frame); the pixel
+  // kernel writes each one's rectangle of the STORED frame, jb_orient_kernel turns it into a second region of the scratch
+  const bool oriented = plan.orient != JB_ORIENT_STORED;
+  const jb_device_batch ob = oriented_batch(b, plan.orient);
   std::vector<jb_roi> windows;  // what the pixel kernel writes of every image: with a filter, not the rectangle
   if (plan.filter)
     for (int64_t i = 0; i < b->n_images; i++)
-      windows.push_back(jb_filter_window_of_(&b->desc, &plan.crops[i], plan.out_w, plan.out_h, plan.filter));
-  const jb_roi *const written = plan.filter ? windows.data() : plan.crops;
-  const auto bytes_of = [&](int64_t i) { return 3LL * written[i].width * written[i].height; };
+      windows.push_back(jb_filter_window_of_(&ob.desc, &plan.crops[i], plan.out_w, plan.out_h, plan.filter));
+  const jb_roi *const shown = plan.filter ? windows.data() : plan.crops;
+  std::vector<jb_roi> stored;
+  if (oriented)
+    for (int64_t i = 0; i < b->n_images; i++) stored.push_back(stored_rect(b, plan.orient, shown[i]));
+  const jb_roi *const written = oriented ? stored.data() : shown;
+  const auto image_bytes = [&](int64_t i) { return 3LL * written[i].width * written[i].height; };
+  const auto bytes_of = [&](int64_t i) { return image_bytes(i) * (oriented ? 2 : 1); };  // (the cap counts both regions)
   // JB_ARITH_LIBJPEG: the planes of every image's window are held to the same cap, in a scratch of their own
   const bool lj = ctx->arithmetic == JB_ARITH_LIBJPEG;
   const auto planes_of = [&](int64_t i) { return lj ? lj_window(b, g, written[i]).bytes : 0; };
@@ -241,8 +264,11 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
   DeviceGuard guard(ctx->device);
   const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   void *tmp = nullptr, *planes_d = nullptr;
-  int rc = tmp_for_stream(ctx, s, (size_t)most + kTmpSlack, &tmp);
+  // (oriented: `most` counts both regions; the second one starts where the first one and its slack end)
+  const int64_t region = oriented ? round_up(most / 2 + (int64_t)kTmpSlack, 256) : 0;
+  int rc = tmp_for_stream(ctx, s, oriented ? (size_t)(2 * region) : (size_t)most + kTmpSlack, &tmp);
   if (rc) return rc;
+  const void *const resample_src = (const uint8_t *)tmp + region;
   if (lj) rc = scratch_for_stream(ctx, ctx->planes, s, (size_t)most_planes, &planes_d);
   if (rc) return rc;
   const int per_tile = jbk_mcus_per_tile(b->desc.hs, b->desc.vs), mw = 8 * b->desc.hs, mh = 8 * b->desc.vs;
@@ -258,7 +284,7 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
     int64_t at = 0;
     for (int j = 0; j < m; j++) {
       const jb_roi &r = written[i0 + j];
-      if (plan.filter) ftable.r[j] = filter_row(plan.crops[i0 + j], r, at);
+      if (plan.filter) ftable.r[j] = filter_row(plan.crops[i0 + j], shown[i0 + j], at);
       JbCrop &c = table.c[j];
       c.x = r.x, c.y = r.y, c.w = r.width, c.h = r.height;
       c.mx = r.x / mw, c.my = r.y / mh;
@@ -266,7 +292,7 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
       c.tiles_per_row = (mcus_x + per_tile - 1) / per_tile;
       c.n_tiles = mcus_y * c.tiles_per_row;  // (at most the whole image's: no overflow)
       c.tmp_offset = at;
-      at += bytes_of(i0 + j);
+      at += image_bytes(i0 + j);
       if (c.n_tiles > most_tiles) most_tiles = c.n_tiles;
       if (jbk_lj_tiles(c.w, c.h) > most_lj_tiles) most_lj_tiles = jbk_lj_tiles(c.w, c.h);
     }
@@ -288,8 +314,23 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
     } else {
       JB_HIP(ctx, jbk_launch_crops(p, table, b->desc.hs, b->desc.vs, s));
     }
-    if (plan.filter) JB_HIP(ctx, jbk_filter_launch_crops(filter_args(b, plan, plane_stride, tmp, i0, m), ftable, plan.filter, plan.format, s));
-    else JB_HIP(ctx, jbk_resample_launch_crops(resample_args(b, plan, plane_stride, tmp, i0, m), table, plan.format, s));
+    if (oriented) {
+      // every image turned into the second region, at its own offset; `table` then describes the oriented sources as
+      // jb_resample_kernel takes them (of a row it reads w, h and tmp_offset; the pixel launch above has its copy)
+      JbOrient q;
+      JbOrientTable turn;
+      memset(&q, 0, sizeof q);
+      memset(&turn, 0, sizeof turn);
+      q.src = (const uint8_t *)tmp, q.dst = (uint8_t *)tmp + region;
+      q.orientation = plan.orient, q.n_images = m;
+      for (int j = 0; j < m; j++) {
+        turn.r[j] = JbOrientRow{table.c[j].w, table.c[j].h, table.c[j].tmp_offset, table.c[j].tmp_offset};
+        table.c[j].w = shown[i0 + j].width, table.c[j].h = shown[i0 + j].height;
+      }
+      JB_HIP(ctx, jbk_orient_launch_table(q, turn, s));
+    }
+    if (plan.filter) JB_HIP(ctx, jbk_filter_launch_crops(filter_args(&ob, plan, plane_stride, resample_src, i0, m), ftable, plan.filter, plan.format, s));
+    else JB_HIP(ctx, jbk_resample_launch_crops(resample_args(&ob, plan, plane_stride, resample_src, i0, m), table, plan.format, s));
     i0 += m;
   }
   return JB_OK;
@@ -344,6 +385,84 @@ int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, con
   return JB_OK;
 }
 
+// 3e. "orientation": a plan of the oriented frame (plan.orient 2..8).  The pixel launch -- the context's arithmetic,
+// format 0, tight -- writes what the output shows of the STORED frame into the stream's scratch: the whole frame, the
+// rectangle, or with a filter the window, each mapped back (jb_orient_map_roi).  jb_orient_kernel turns it: without a
+// target size into the caller's buffer, in the plan's format; with one into a second tight region of the same scratch,
+// which the resample or filter launch then reads exactly as 3b's reads the first.  Sub-batches of whole images: as
+// many as the cap holds, both regions counted.
+int seam_launch_oriented(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn) {
+  jb_geometry g;
+  int64_t plane_stride = 0;
+  int rc = seam_check(ctx, b, plan, fn, &g, &plane_stride);
+  if (rc) return rc;
+  if (plan.crops) return seam_launch_crops(ctx, b, stream, plan, fn, g, plane_stride);
+  const jb_device_batch ob = oriented_batch(b, plan.orient);
+  const jb_roi whole = {0, 0, ob.desc.width, ob.desc.height};
+  const jb_roi shown = plan.filter ? plan.window : plan.has_roi ? plan.roi : whole;
+  const jb_roi stored = stored_rect(b, plan.orient, shown);
+  const bool all = stored.width == b->desc.width && stored.height == b->desc.height;
+  const JbOutPlan inner = jb_out_plan_(&b->desc, 1, nullptr, all ? nullptr : &stored);
+  if (inner.status != JB_OK) return fail(ctx, inner.status, "%s: %s", fn, inner.why);
+  const int n_regions = plan.has_resize ? 2 : 1;
+  const int64_t image_bytes = inner.image_bytes;  // 3 * stored.width * stored.height, of either region
+  int64_t per = (int64_t)ctx->knobs.resize_tmp_bytes / (n_regions * image_bytes);
+  if (per < 1) per = 1;
+  if (per > b->n_images) per = b->n_images;
+  const int64_t tile = kJbOrientTile;
+  if (((stored.width + tile - 1) / tile) * ((stored.height + tile - 1) / tile) * per > 0x7fffffffLL ||
+      (plan.has_resize && ((int64_t)(plan.out_w + 63) / 64) * ((plan.out_h + 3) / 4) * per > 0x7fffffffLL))
+    return fail(ctx, JB_ERR_CAPACITY, "batch too large for one launch");
+  DeviceGuard guard(ctx->device);
+  const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  const int64_t region = round_up(per * image_bytes + (int64_t)kTmpSlack, 256);
+  void *tmp = nullptr;
+  rc = tmp_for_stream(ctx, s, (size_t)(n_regions * region), &tmp);
+  if (rc) return rc;
+  uint8_t *const turned = (uint8_t *)tmp + region;  // (the second region)
+  const int64_t coef_step = b->n_images > 1 ? b->coef_image_stride : 0, rgb_step = b->n_images > 1 ? b->rgb_image_stride : 0;
+  for (int64_t i0 = 0; i0 < b->n_images; i0 += per) {
+    const int m = (int)(b->n_images - i0 < per ? b->n_images - i0 : per);
+    jb_device_batch ib = *b;
+    ib.n_images = m;
+    ib.d_coef = (const int16_t *)((const uint8_t *)b->d_coef + i0 * coef_step);
+    ib.coef_image_stride = coef_step;
+    ib.d_qtabs = (const int32_t *)((const uint8_t *)b->d_qtabs + i0 * b->qtab_image_stride);
+    ib.d_rgb = (uint8_t *)tmp;
+    ib.rgb_row_stride = inner.row_stride;
+    ib.rgb_image_stride = image_bytes;
+    rc = seam_launch(ctx, &ib, s, inner, fn);
+    if (rc) return rc;
+    JbOrient q;
+    memset(&q, 0, sizeof q);
+    q.src = (const uint8_t *)tmp;
+    q.src_image_stride = image_bytes;
+    q.sw = stored.width, q.sh = stored.height;
+    q.orientation = plan.orient;
+    q.n_images = m;
+    if (!plan.has_resize) {
+      q.dst = b->d_rgb + i0 * rgb_step;
+      q.dst_image_stride = rgb_step;
+      q.dst_row_stride = b->rgb_row_stride;
+      q.dst_plane_stride = plane_stride;
+      for (int c = 0; c < 3; c++) q.scale[c] = plan.spec.scale[c], q.bias[c] = plan.spec.bias[c];
+      JB_HIP(ctx, jbk_orient_launch(q, plan.format, s));
+      continue;
+    }
+    q.dst = turned;
+    q.dst_image_stride = image_bytes;
+    q.dst_row_stride = 3LL * shown.width;
+    JB_HIP(ctx, jbk_orient_launch(q, JB_FMT_RGB_U8_HWC, s));
+    if (plan.filter) {
+      JbFilter f = filter_args(&ob, plan, plane_stride, turned, i0, m);
+      f.one = filter_row(plan.has_roi ? plan.roi : whole, plan.window, 0);
+      JB_HIP(ctx, jbk_filter_launch(f, plan.filter, plan.format, s));
+    } else {
+      JB_HIP(ctx, jbk_resample_launch(resample_args(&ob, plan, plane_stride, turned, i0, m), plan.format, s));
+    }
+  }
+  return JB_OK;
+}
 
 // 3d. JB_ARITH_LIBJPEG: jb_libjpeg.hip's launch pair in the place of jbk_launch -- any format, the whole image or the
 // plan's rectangle, scale 1 (seam_check has refused another).  The planes of a sub-batch of whole images are held to the
@@ -383,6 +502,7 @@ int seam_launch_lj(jb_ctx *ctx, const jb_device_batch *b, void *stream, const Jb
 
 // 3. the launch, on `stream` or (null) the context's primary stream; fn: the entry point's name, for the error text
 int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn) {
+  if (plan.orient != JB_ORIENT_STORED && plan.orient != JB_ORIENT_EXIF && ctx && b) return seam_launch_oriented(ctx, b, stream, plan, fn);
   if (plan.has_resize && ctx && b) return seam_launch_resized(ctx, b, stream, plan, fn);
   jb_geometry g;
   int64_t plane_stride = 0;
@@ -402,6 +522,12 @@ int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOut
   return JB_OK;
 }
 
+// the plan of a seam entry point: of b's frame under the context's orientation
+static JbOutPlan seam_plan(const jb_ctx *ctx, const jb_device_batch *b, int scale, const jb_output_spec *spec, const jb_roi *roi = nullptr,
+                           const JbTarget *target = nullptr, const jb_roi *crops = nullptr, int n_crops = 0) {
+  return jb_out_plan_(b ? &b->desc : nullptr, scale, spec, roi, target, crops, n_crops, ctx ? ctx->orientation : JB_ORIENT_STORED);
+}
+
 extern "C" {
 
 const char *jb_kernel_name(const jb_image_desc *d) {
@@ -410,33 +536,33 @@ const char *jb_kernel_name(const jb_image_desc *d) {
 }
 
 int jb_blocks_to_rgb_device(jb_ctx *ctx, const jb_device_batch *b, void *stream) {
-  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, nullptr), "jb_blocks_to_rgb_device");
+  return seam_launch(ctx, b, stream, seam_plan(ctx, b, 1, nullptr), "jb_blocks_to_rgb_device");
 }
 
 int jb_blocks_to_rgb_device_scaled(jb_ctx *ctx, const jb_device_batch *b, int denom, void *stream) {
-  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, denom, nullptr), "jb_blocks_to_rgb_device_scaled");
+  return seam_launch(ctx, b, stream, seam_plan(ctx, b, denom, nullptr), "jb_blocks_to_rgb_device_scaled");
 }
 
 int jb_blocks_to_rgb_device_fmt(jb_ctx *ctx, const jb_device_batch *b, const jb_output_spec *spec, void *stream) {
   if (ctx && !spec) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_fmt: spec is NULL");
-  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec), "jb_blocks_to_rgb_device_fmt");
+  return seam_launch(ctx, b, stream, seam_plan(ctx, b, 1, spec), "jb_blocks_to_rgb_device_fmt");
 }
 
 int jb_blocks_to_rgb_device_roi(jb_ctx *ctx, const jb_device_batch *b, const jb_roi *roi, const jb_output_spec *spec, void *stream) {
-  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, roi), "jb_blocks_to_rgb_device_roi");
+  return seam_launch(ctx, b, stream, seam_plan(ctx, b, 1, spec, roi), "jb_blocks_to_rgb_device_roi");
 }
 
 int jb_blocks_to_rgb_device_resized(jb_ctx *ctx, const jb_device_batch *b, const jb_roi *roi, int32_t out_w, int32_t out_h,
                                     const jb_output_spec *spec, void *stream) {
   const JbTarget t = {out_w, out_h};
-  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, roi, &t), "jb_blocks_to_rgb_device_resized");
+  return seam_launch(ctx, b, stream, seam_plan(ctx, b, 1, spec, roi, &t), "jb_blocks_to_rgb_device_resized");
 }
 
 int jb_blocks_to_rgb_device_crops(jb_ctx *ctx, const jb_device_batch *b, const jb_roi *rois, int32_t out_w, int32_t out_h,
                                   const jb_output_spec *spec, void *stream) {
   if (ctx && !rois) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_crops: rois is NULL");
   const JbTarget t = {out_w, out_h};
-  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, nullptr, &t, rois, b ? b->n_images : 0),
+  return seam_launch(ctx, b, stream, seam_plan(ctx, b, 1, spec, nullptr, &t, rois, b ? b->n_images : 0),
                      "jb_blocks_to_rgb_device_crops");
 }
 
@@ -444,14 +570,14 @@ int jb_blocks_to_rgb_device_filtered(jb_ctx *ctx, const jb_device_batch *b, cons
                                      const jb_output_spec *spec, void *stream) {
   if (ctx && !rs) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_filtered: rs is NULL");
   const JbTarget t = rs ? JbTarget{rs->out_w, rs->out_h, rs->filter, rs->reserved} : JbTarget{};
-  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, roi, &t), "jb_blocks_to_rgb_device_filtered");
+  return seam_launch(ctx, b, stream, seam_plan(ctx, b, 1, spec, roi, &t), "jb_blocks_to_rgb_device_filtered");
 }
 
 int jb_blocks_to_rgb_device_crops_filtered(jb_ctx *ctx, const jb_device_batch *b, const jb_roi *rois, const jb_resize *rs,
                                            const jb_output_spec *spec, void *stream) {
   if (ctx && (!rois || !rs)) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_crops_filtered: NULL pointer");
   const JbTarget t = rs ? JbTarget{rs->out_w, rs->out_h, rs->filter, rs->reserved} : JbTarget{};
-  return seam_launch(ctx, b, stream, jb_out_plan_(b ? &b->desc : nullptr, 1, spec, nullptr, &t, rois, b ? b->n_images : 0),
+  return seam_launch(ctx, b, stream, seam_plan(ctx, b, 1, spec, nullptr, &t, rois, b ? b->n_images : 0),
                      "jb_blocks_to_rgb_device_crops_filtered");
 }
 
