@@ -446,6 +446,48 @@ int jb_decode_memory_filtered(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
 int jb_decode_file_filtered(jb_ctx *ctx, const char *path, const jb_roi *roi, const jb_resize *rs, const jb_output_spec *spec,
                             void **out, int32_t *width, int32_t *height);
 
+/* ---- views: several rectangles per image, each optionally mirrored, from one decode ----
+ * The K random crops of a multi-view training pipeline, and the random horizontal flip, in one call.  A call has
+ * views_per_image = K in 1..16 and a HOST array of n_images * K views; view v of image i is views[i * K + v].  One
+ * jb_resize holds the target and the filter (JB_FILTER_AREA is allowed).  Output number i * K + v is
+ *     u   = what "per-image rectangles" gives for image i with the rectangle views[i * K + v] and the same jb_resize
+ *     out = format(flags & JB_VIEW_MIRROR ? u[:, ::-1, :] : u)
+ * -- no new arithmetic: the definitions, the refusals, the tap cap and the frame-clamped filter bounds are those of "fixed
+ * output size", "per-image rectangles" and "resampling filters".  THE MIRROR IS APPLIED LAST, on the uint8 result
+ * (torchvision's order: RandomResizedCrop, then RandomHorizontalFlip): Pillow's normalised weights are not mirror-
+ * symmetric in general, so mirroring the source first gives other bits.  Formats 0-3, the context's arithmetic and its
+ * orientation compose unchanged: rectangles are in oriented coordinates, and the mirror is still last.
+ * The entropy stage and the pixel kernel run ONCE per image: the pixel kernel writes the image's UNION -- the bounding
+ * rectangle of its K rectangles, with a filter of their K source windows -- into the stream's scratch, and the resample
+ * or filter kernel reads K sub-rectangles of it; a mirrored view differs in the store address alone.  A union can be
+ * larger than the sum of its views (two small rectangles in opposite corners: nearly the frame); that is accepted, the
+ * pixel kernel is cheap next to the entropy stage.  Sub-batches pack images while their unions fit
+ * JPEGBLK_RESIZE_TMP_BYTES (a larger one runs alone), at most 32 images each.
+ * Refusals: K outside 1..16, unknown flag bits or reserved != 0 JB_ERR_GEOMETRY; a rectangle outside the frame
+ * JB_ERR_GEOMETRY (jb_last_error names the image's and the view's index); no target size (out_w = out_h = 0)
+ * JB_ERR_STATE; then the target's and the filter's own.  The batch decoder refuses views together with a scale other
+ * than 1 or a decoder-wide rectangle with JB_ERR_UNSUPPORTED.  In every refusal nothing is launched or written. */
+enum { JB_VIEW_MIRROR = 1 }; /* flags bit 0: mirror the OUTPUT left-right */
+typedef struct jb_view {
+  int32_t x, y, width, height; /* as jb_roi */
+  int32_t flags;               /* JB_VIEW_* */
+  int32_t reserved;            /* 0 */
+} jb_view;
+enum { JB_VIEWS_MAX = 16 };
+/* JB_OK when the call can be had.  JB_ERR_NULL for a null descriptor, jb_resize or (n_images * views_per_image > 0)
+ * array; the descriptor's own errors; JB_ERR_GEOMETRY for n_images < 0 or views_per_image outside 1..16; then the
+ * first view that fails -- flags or reserved, else its rectangle: JB_ERR_GEOMETRY -- with its index in the FLAT array in
+ * *bad_index (may be NULL; -1 when no view is to blame); then JB_ERR_STATE without a target size, the target's and the
+ * filter's statuses as jb_filter_check gives them (the tap cap: *bad_index names the view).  Pure host code. */
+int jb_views_check(const jb_image_desc *desc, const jb_view *views, int n_images, int views_per_image, const jb_resize *rs,
+                   int *bad_index);
+/* d_rgb and its strides describe batch->n_images * views_per_image outputs of out_w x out_h, rgb_image_stride apart
+ * (checked whenever there is more than one output); output i * K + v is at index i * K + v.  Everything else about the
+ * batch is as for jb_blocks_to_rgb_device_crops_filtered.  The array is read before the call returns.  views or rs ==
+ * NULL: JB_ERR_NULL.  spec == NULL: interleaved uint8. */
+int jb_blocks_to_rgb_device_views(jb_ctx *ctx, const jb_device_batch *batch, const jb_view *views, int views_per_image,
+                                  const jb_resize *rs, const jb_output_spec *spec, void *stream);
+
 /* ---- decoder arithmetic: the reference program's, or libjpeg's bit for bit ----
  * What a full-size decode computes between the coefficients and the uint8 pixels.  JB_ARITH_REFERENCE (the default) is
  * the reference program's: a float AAN IDCT, chroma replicated to the luma grid, float YCbCr -> RGB.  JB_ARITH_LIBJPEG
@@ -731,6 +773,19 @@ int jb_batch_decoder_run_crops(jb_batch_decoder *dec, const char *const *paths, 
                                int32_t *widths, int32_t *heights, int *statuses, double *times);
 int jb_batch_decoder_submit_crops(jb_batch_decoder *dec, const char *const *paths, int n_paths, const jb_roi *rois, uint8_t **rgb,
                                   int32_t *widths, int32_t *heights, int *statuses, int *ticket);
+/* _run_crops / _submit_crops with K = views_per_image views per file (see "views" above): views[i * K + v] is view v of
+ * paths[i], in pixels of that file's (oriented) frame.  The output arrays keep ONE entry per file: rgb[i] is one buffer
+ * holding file i's K outputs back to back, each jb_output_bytes(out_w, out_h, format), tight; widths[i] / heights[i]
+ * are a view's size, statuses[i] the file's.  The file stays the unit of everything the decoder does with an output --
+ * arena, device region, jb_free, failure -- K times larger: every size check counts K outputs and answers
+ * JB_ERR_CAPACITY where it answers today.  A file one of whose views does not fit gets JB_ERR_GEOMETRY and the batch
+ * goes on.  The entropy stage runs once per file.  Refused with JB_ERR_UNSUPPORTED while the scale is not 1 or a
+ * decoder-wide rectangle is set, with JB_ERR_STATE without a target size, with JB_ERR_GEOMETRY for views_per_image
+ * outside 1..16; views == NULL: JB_ERR_NULL.  _submit_views copies the array. */
+int jb_batch_decoder_run_views(jb_batch_decoder *dec, const char *const *paths, int n_paths, const jb_view *views, int views_per_image,
+                               uint8_t **rgb, int32_t *widths, int32_t *heights, int *statuses, double *times);
+int jb_batch_decoder_submit_views(jb_batch_decoder *dec, const char *const *paths, int n_paths, const jb_view *views, int views_per_image,
+                                  uint8_t **rgb, int32_t *widths, int32_t *heights, int *statuses, int *ticket);
 /* The filter (JB_FILTER_*; see "resampling filters") of the batch decoder's later runs and submissions: it governs the
  * target size of jb_batch_decoder_set_resize and the per-image rectangles of _run_crops / _submit_crops alike, and is
  * kept while no target size is set (there is then nothing to resample).  A file whose reduction exceeds the tap cap gets

@@ -13,8 +13,9 @@ from .api import (JbError, Context, ImageDesc, Geometry, DeviceBatch, lib, lib_p
                   OutputSpec, output_bytes, torch_batch, FMT_RGB_U8_HWC, FMT_RGB_U8_CHW, FMT_RGB_F32_CHW, FMT_RGB_F16_CHW,
                   FMT_DTYPE, Roi, roi_check, resize_check, crops_check, Resize, filter_check, filter_window,
                   FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC, ARITH_REFERENCE, ARITH_LIBJPEG,
-                  ORIENT_EXIF, ORIENT_STORED, exif_orientation, oriented_size, orient_map_roi)
-from .crops import random_resized_crop
+                  ORIENT_EXIF, ORIENT_STORED, exif_orientation, oriented_size, orient_map_roi,
+                  View, VIEW_MIRROR, VIEWS_MAX, views_check)
+from .crops import random_resized_crop, random_views
 
 __all__ = ["JbError", "Context", "ImageDesc", "Geometry", "DeviceBatch", "lib", "lib_path",
            "make_desc", "geometry_of", "resolve_qtabs", "entropy_decode", "decode_batch", "BatchDecoder", "build_library",
@@ -22,4 +23,4 @@ __all__ = ["JbError", "Context", "ImageDesc", "Geometry", "DeviceBatch", "lib", 
            "FMT_RGB_F16_CHW", "FMT_DTYPE", "Roi", "roi_check", "resize_check", "crops_check",
            "random_resized_crop", "Resize", "filter_check", "filter_window", "FILTER_AREA", "FILTER_BILINEAR", "FILTER_BICUBIC",
            "ARITH_REFERENCE", "ARITH_LIBJPEG", "ORIENT_EXIF", "ORIENT_STORED", "exif_orientation", "oriented_size",
-           "orient_map_roi"]
+           "orient_map_roi", "View", "VIEW_MIRROR", "VIEWS_MAX", "views_check", "random_views"]

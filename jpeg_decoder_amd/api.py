@@ -93,6 +93,16 @@ class Resize(ctypes.Structure):
     _fields_ = [("out_w", ctypes.c_int32), ("out_h", ctypes.c_int32), ("filter", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+VIEW_MIRROR = 1   # jb_view.flags bit 0 (jpegblk.h, "views"): mirror the OUTPUT left-right
+VIEWS_MAX = 16
+
+
+class View(ctypes.Structure):
+    """jb_view: a rectangle as jb_roi, and flags (VIEW_MIRROR)."""
+    _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 def _ref(struct):
     """byref(struct), or None (a NULL pointer) for None."""
     return ctypes.byref(struct) if struct is not None else None
@@ -108,6 +118,26 @@ def _crop_array(crops, n=None):
     return (Roi * max(len(rois), 1))(*rois)
 
 
+def _view_array(views, n=None):
+    """[[(x, y, w, h[, mirror]) or View, ... K], ... N] -> (a ctypes array of N * K jb_view, image-major and at least one
+    element long, K).  Rows of unequal length, or (n given) another count of rows than n: JbError(-2)."""
+    rows = [list(r) for r in views]
+    if n is not None and len(rows) != n:
+        raise JbError(-2, f"{len(rows)} rows of views for {n} images")
+    k = len(rows[0]) if rows else 1
+    if any(len(r) != k for r in rows):
+        raise JbError(-2, "views: every image wants the same number of views")
+    flat = []
+    for r in rows:
+        for v in r:
+            if isinstance(v, View):
+                flat.append(v)
+            else:
+                v = tuple(v)
+                flat.append(View(int(v[0]), int(v[1]), int(v[2]), int(v[3]), VIEW_MIRROR if len(v) > 4 and v[4] else 0, 0))
+    return (View * max(len(flat), 1))(*flat), k
+
+
 class _Request:
     """The output request of one call, normalised in this one place.  (scale, fmt, roi, resize, crops, filter) as the caller gave
     them (fmt: None / a format number / an OutputSpec; roi: None / (x, y, w, h) / a Roi; resize: None / (w, h); crops: None
@@ -116,9 +146,11 @@ class _Request:
     JbError(-9), raised here: no C entry point takes the pair.  So are per-image rectangles with a scale or with roi (two
     rectangles for one image); without a target size they are JbError(-7): only a target makes the outputs one size.
     filter (FILTER_*) becomes .filter; FILTER_AREA asks for nothing new, any other filter without a target size is
-    JbError(-7)."""
+    JbError(-7).  views (K views per image, [[(x, y, w, h[, mirror]), ...], ...]) become .views (a ctypes array of View or
+    None; .n_view_rows images of .views_per_image each): with a scale, roi or crops JbError(-9), without a target size
+    JbError(-7), rows of unequal length JbError(-2)."""
 
-    def __init__(self, scale=1, fmt=None, roi=None, resize=None, crops=None, filter=FILTER_AREA):
+    def __init__(self, scale=1, fmt=None, roi=None, resize=None, crops=None, filter=FILTER_AREA, views=None):
         self.scale = scale
         self.filter = int(filter)
         if self.filter != FILTER_AREA and resize is None:
@@ -143,11 +175,27 @@ class _Request:
                 raise JbError(-7, "per-image rectangles (crops) want a target size (resize)")
             self.crops = _crop_array(crops)
             self.n_crops = len(list(crops))
+        self.views, self.views_per_image, self.n_view_rows = None, 0, 0
+        if views is not None:
+            if scale != 1:
+                raise JbError(-9, "views cannot be combined with a scale")
+            if roi is not None:
+                raise JbError(-9, "views cannot be combined with a rectangle for every image (roi)")
+            if crops is not None:
+                raise JbError(-9, "views cannot be combined with per-image rectangles (crops)")
+            if resize is None:
+                raise JbError(-7, "views want a target size (resize)")
+            views = [list(r) for r in views]
+            self.views, self.views_per_image = _view_array(views)
+            self.n_view_rows = len(views)
 
     def routed(self):
         """-> (route, the arguments the route's entry points take between their family's own and their outputs).  The
         route names the variant of an entry point that takes this request (_ROUTES has the symbols).  A planar format
         with a scale has none, JbError(-9); format 0 with a scale is the scaled route, which takes no spec."""
+        if self.views is not None:       # (takes a jb_resize: the filter needs no route of its own)
+            rs = ctypes.byref(Resize(self.target[0], self.target[1], self.filter, 0))
+            return "views", (self.views, self.views_per_image, rs, _ref(self.spec))
         if self.filter != FILTER_AREA:   # (always with a target size)
             rs = ctypes.byref(Resize(self.target[0], self.target[1], self.filter, 0))
             if self.crops is not None:
@@ -178,7 +226,9 @@ _ROUTES = {"plain": ("jb_decode_file", "jb_decode_memory", "jb_blocks_to_rgb_dev
            "crops": (None, None, "jb_blocks_to_rgb_device_crops"),
            # a filter other than FILTER_AREA (FILTER_AREA takes the two routes above)
            "filtered": ("jb_decode_file_filtered", "jb_decode_memory_filtered", "jb_blocks_to_rgb_device_filtered"),
-           "crops_filtered": (None, None, "jb_blocks_to_rgb_device_crops_filtered")}
+           "crops_filtered": (None, None, "jb_blocks_to_rgb_device_crops_filtered"),
+           # K views per image, each optionally mirrored, any filter
+           "views": (None, None, "jb_blocks_to_rgb_device_views")}
 
 
 def roi_check(desc, roi):
@@ -204,6 +254,18 @@ def crops_check(desc, crops, resize):
         raise JbError(rc, f"rectangle {bad.value} does not lie in the image" if bad.value >= 0 else "bad target size or descriptor")
 
 
+def views_check(desc, views, resize, filter=FILTER_AREA):
+    """jb_views_check: can the K views per image of `views` ([[(x, y, w, h[, mirror]), ...], ...]) of the descriptor's
+    image be had at the target size (w, h) under `filter`?  Raises JbError otherwise, the text naming the image and the
+    view that is to blame when one is."""
+    arr, k = _view_array(views)
+    n = len(list(views))
+    bad = ctypes.c_int(-1)
+    rc = lib().jb_views_check(ctypes.byref(desc), arr, n, k, ctypes.byref(_resize_struct(resize, filter)), ctypes.byref(bad))
+    if rc != JB_OK:
+        raise JbError(rc, f"image {bad.value // k}, view {bad.value % k} cannot be had" if bad.value >= 0 else "bad target size, filter, count or descriptor")
+
+
 def _resize_struct(resize, filter):
     w, h = resize if resize is not None else (0, 0)
     return Resize(int(w), int(h), int(filter), 0)
@@ -223,13 +285,15 @@ def filter_window(desc, resize, filter, roi=None):
     return win.x, win.y, win.width, win.height
 
 
-def _shape_output(ptr, w, h, spec):
-    """A copy-free view of one decoded image at `ptr`: [H, W, 3] uint8 (no spec / format 0) or [3, H, W] in the format's type."""
+def _shape_output(ptr, w, h, spec, k=0):
+    """A copy-free view of one decoded image at `ptr`: [H, W, 3] uint8 (no spec / format 0) or [3, H, W] in the format's
+    type.  k > 0 ("views"): the file's k outputs back to back, [k, H, W, 3] or [k, 3, H, W]."""
+    lead = (k,) if k else ()
     if spec is None or spec.format == FMT_RGB_U8_HWC:
-        return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_uint8)), shape=(w * h * 3,)).reshape(h, w, 3)
+        return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_uint8)), shape=(max(k, 1) * w * h * 3,)).reshape(lead + (h, w, 3))
     dt = np.dtype(FMT_DTYPE[spec.format])
-    raw = np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_uint8)), shape=(w * h * 3 * dt.itemsize,))
-    return raw.view(dt).reshape(3, h, w)
+    raw = np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_uint8)), shape=(max(k, 1) * w * h * 3 * dt.itemsize,))
+    return raw.view(dt).reshape(lead + (3, h, w))
 
 
 def build_library():
@@ -354,6 +418,11 @@ def lib():
     L.jb_batch_decoder_run_crops.argtypes = L.jb_batch_decoder_run.argtypes[:3] + [pr] + L.jb_batch_decoder_run.argtypes[3:]
     L.jb_batch_decoder_submit_crops.argtypes = L.jb_batch_decoder_submit.argtypes[:3] + [pr] + L.jb_batch_decoder_submit.argtypes[3:]
     prs = ctypes.POINTER(Resize)
+    pv = ctypes.POINTER(View)
+    L.jb_views_check.argtypes = [pd, pv, ctypes.c_int, ctypes.c_int, prs, ctypes.POINTER(ctypes.c_int)]
+    L.jb_blocks_to_rgb_device_views.argtypes = [vp, ctypes.POINTER(DeviceBatch), pv, ctypes.c_int, prs, ps, vp]
+    L.jb_batch_decoder_run_views.argtypes = L.jb_batch_decoder_run.argtypes[:3] + [pv, ctypes.c_int] + L.jb_batch_decoder_run.argtypes[3:]
+    L.jb_batch_decoder_submit_views.argtypes = L.jb_batch_decoder_submit.argtypes[:3] + [pv, ctypes.c_int] + L.jb_batch_decoder_submit.argtypes[3:]
     L.jb_filter_check.argtypes = [pd, pr, prs]
     L.jb_filter_window.argtypes = [pd, pr, prs, pr]
     L.jb_blocks_to_rgb_device_filtered.argtypes = [vp, ctypes.POINTER(DeviceBatch), pr, prs, ps, vp]
@@ -622,7 +691,7 @@ class Context:
         _check(lib().jb_wait(self._h, ticket), self._h)
 
     # -- the seam, device buffers ------------------------------------------------------------
-    def blocks_to_rgb_device(self, batch, stream=None, scale=1, fmt=None, roi=None, resize=None, crops=None, filter=FILTER_AREA):
+    def blocks_to_rgb_device(self, batch, stream=None, scale=1, fmt=None, roi=None, resize=None, crops=None, filter=FILTER_AREA, views=None):
         """scale 2, 4, 8: the batch's d_rgb and strides describe images of scaled_size(desc.width, desc.height, scale).
         fmt (an OutputSpec or a format number): planar output -- the batch's rgb_row_stride is then a plane's.
         roi=(x, y, w, h) (with any fmt, not with a scale): the batch's d_rgb and strides describe images of w x h, the
@@ -633,10 +702,16 @@ class Context:
         batch, each resized to w x h (jb_blocks_to_rgb_device_crops); the list is read before the call returns.
         filter=FILTER_BILINEAR / FILTER_BICUBIC with resize= (with or without roi or crops): Pillow's 8-bit resampling in
         the area filter's place (jb_blocks_to_rgb_device_filtered / _crops_filtered).
+        views=[[(x, y, w, h[, mirror]), ... K], ... N] with resize=(w, h) (any fmt and filter; not with roi, crops or a scale): K
+        rectangles per image, each resized to w x h and then mirrored left-right when its fifth field is true, from ONE
+        pixel launch per image (jb_blocks_to_rgb_device_views).  batch.d_rgb and its strides describe n_images * K
+        outputs; output i * K + v is view v of image i.
         Each is the entry point of that suffix (_ROUTES)."""
-        request = _Request(scale, fmt, roi, resize, crops, filter)
+        request = _Request(scale, fmt, roi, resize, crops, filter, views)
         if request.crops is not None and request.n_crops != batch.n_images:
             raise JbError(-2, f"{request.n_crops} rectangles (crops) for {batch.n_images} images")
+        if request.views is not None and request.n_view_rows != batch.n_images:
+            raise JbError(-2, f"{request.n_view_rows} rows of views for {batch.n_images} images")
         route, tail = request.routed()
         _check(getattr(lib(), _ROUTES[route][_DEVICE])(self._h, ctypes.byref(batch), *tail, stream), self._h)
 
@@ -672,7 +747,7 @@ def _batch_args(paths):
     """The argument arrays of one batch call over `paths`, as the ticket of BatchDecoder.submit holds them."""
     n = len(paths)
     return {"n": n, "paths": (ctypes.c_char_p * n)(*[os.fsencode(p) for p in paths]), "rgb": (ctypes.c_void_p * n)(),
-            "w": (ctypes.c_int32 * n)(), "h": (ctypes.c_int32 * n)(), "st": (ctypes.c_int * n)(), "id": ctypes.c_int(-1)}
+            "w": (ctypes.c_int32 * n)(), "h": (ctypes.c_int32 * n)(), "st": (ctypes.c_int * n)(), "id": ctypes.c_int(-1), "k": 0}
 
 
 def _batch_times(times, rc):
@@ -681,7 +756,7 @@ def _batch_times(times, rc):
             "error": lib().jb_last_error(None).decode(errors="replace") if rc else ""}
 
 
-def _harvest(n, rgb, w, h, st, fmt, keep_pixels, on_image, arena, device_out):
+def _harvest(n, rgb, w, h, st, fmt, keep_pixels, on_image, arena, device_out, k=0):
     """The results of a finished batch, without the times: (device pointers (int, 0 = failed), (width, height) per image,
     statuses) with device output, else (arrays / (width, height) without keep_pixels / None = failed, statuses).  Host
     images cost at most one view and one copy each; a malloc'ed one (no arena: arena images belong to the decoder) is
@@ -693,7 +768,7 @@ def _harvest(n, rgb, w, h, st, fmt, keep_pixels, on_image, arena, device_out):
         for i in range(n):
             if rgb[i]:
                 if on_image is not None or keep_pixels:
-                    view = _shape_output(rgb[i], w[i], h[i], fmt)
+                    view = _shape_output(rgb[i], w[i], h[i], fmt, k)
                     if on_image is not None:
                         on_image(i, view)
                 imgs.append(view.copy() if keep_pixels else (w[i], h[i]))
@@ -803,10 +878,15 @@ class BatchDecoder:
     def device_entropy_images(self):
         return lib().jb_batch_decoder_device_entropy_images(self._h)
 
-    def _run(self, paths, keep_pixels, on_image, crops=None):
+    def _run(self, paths, keep_pixels, on_image, crops=None, views=None):
         a = _batch_args(paths)
         times = (ctypes.c_double * 4)()
-        if crops is not None:
+        if views is not None:
+            if crops is not None:
+                raise JbError(-9, "views cannot be combined with per-image rectangles (crops)")
+            arr, a["k"] = _view_array(views, a["n"])
+            rc = lib().jb_batch_decoder_run_views(self._h, a["paths"], a["n"], arr, a["k"], a["rgb"], a["w"], a["h"], a["st"], times)
+        elif crops is not None:
             rc = lib().jb_batch_decoder_run_crops(self._h, a["paths"], a["n"], _crop_array(crops, a["n"]), a["rgb"], a["w"], a["h"],
                                                   a["st"], times)
         else:
@@ -814,15 +894,20 @@ class BatchDecoder:
         return self._results(a, _batch_times(times, rc), keep_pixels, on_image)
 
     def _results(self, a, t, keep_pixels, on_image):
-        return _harvest(a["n"], a["rgb"], a["w"], a["h"], a["st"], self._fmt, keep_pixels, on_image, self._arena, self._device_out) + (t,)
+        return _harvest(a["n"], a["rgb"], a["w"], a["h"], a["st"], self._fmt, keep_pixels, on_image, self._arena, self._device_out,
+                        a.get("k", 0)) + (t,)
 
-    def run(self, paths, keep_pixels=True, on_image=None, crops=None):
+    def run(self, paths, keep_pixels=True, on_image=None, crops=None, views=None):
         """-> what decode_batch returns, in the decoder's format.  crops=[(x, y, w, h), ...] (jb_batch_decoder_run_crops; a
         target size must be set, a rectangle for every image must not: rc -7 in the times): crops[i] is the rectangle of
         paths[i], in pixels of that file, and every image comes out as its rectangle at the target size; a file its
-        rectangle does not fit in gets status -2 and the batch goes on.  JbError(-2) when len(crops) != len(paths)."""
+        rectangle does not fit in gets status -2 and the batch goes on.  JbError(-2) when len(crops) != len(paths).
+        views=[[(x, y, w, h[, mirror]), ... K], ...] (jb_batch_decoder_run_views; a target size must be set, rc -7, a scale or
+        a rectangle for every image must not, rc -9): views[i] are the K views of paths[i], and the file's entry is ONE
+        array [K, ...] in the decoder's format -- the file is decoded once.  A file one of whose views does not fit gets
+        status -2.  JbError(-2) for rows of unequal length or len(views) != len(paths)."""
         assert not self._device_out, "device output is set: use run_to_device"
-        return self._run(paths, keep_pixels, on_image, crops)
+        return self._run(paths, keep_pixels, on_image, crops, views)
 
     def set_device_output(self, d_base, nbytes):
         """jb_batch_decoder_set_device_output: decoded images stay in the caller's DEVICE memory
@@ -840,33 +925,47 @@ class BatchDecoder:
         _check(lib().jb_batch_decoder_set_device_outputs(self._h, ptrs, sizes, n))
         self._arena = self._device_out = n > 0
 
-    def run_to_device(self, paths, crops=None):
+    def run_to_device(self, paths, crops=None, views=None):
         """After set_device_output: -> (device pointers (int, 0 = failed), (width, height) per image, statuses, times).
-        crops: as for run()."""
+        crops: as for run().  views: as for run() -- a file's pointer is that of its K outputs, back to back, tight."""
         assert self._device_out, "call set_device_output first"
-        return self._run(paths, False, None, crops)
+        return self._run(paths, False, None, crops, views)
 
-    def run_to_tensor(self, paths, out, crops=None):
+    def run_to_tensor(self, paths, out, crops=None, views=None):
         """Decode files of ONE size (or, with a rectangle set, of any size the rectangle fits in: out is then
         [N, 3, h, w] of the rectangle; with a target size set, of any size: out is [N, 3, h, w] of the target) straight into a caller-supplied CUDA tensor through the device-output route:
         out is [N, 3, H, W] (planar formats; [N, H, W, 3] for format 0), contiguous, of the decoder's format's dtype, on
         the decoder's device, N = len(paths).  -> (out, statuses, times).  An image whose size does not match out (or
         that fails to decode) gets a non-zero status (JB_ERR_GEOMETRY = -2 for the size) and its slice of out is left
         as it was.  The decoder's device-output setting is replaced for the call and cleared afterwards.
-        crops: as for run() -- the random-resized-crop of a batch straight into the model's input tensor."""
+        crops: as for run() -- the random-resized-crop of a batch straight into the model's input tensor.
+        views: as for run(); out is then [N, K, 3, h, w] ([N, K, h, w, 3] for format 0)."""
+        import torch
+        if views is not None:
+            views = [list(r) for r in views]
+            k = _view_array(views, len(paths))[1]
+            lead = (len(paths), k)
+            if out.dim() != 5 or tuple(out.shape[:2]) != lead or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous CUDA tensor [{lead[0]}, {lead[1]}, 3, H, W] ([N, K, H, W, 3] for format 0)")
+            flat, st, t = self._run_to_tensor(paths, out.view((-1,) + tuple(out.shape[2:])), None, views, k)
+            return out, st, t
+        return self._run_to_tensor(paths, out, crops, None, 1)
+
+    def _run_to_tensor(self, paths, out, crops, views, k):
+        """run_to_tensor over out = [N * k, ...]: file i's k outputs are out[i * k : (i + 1) * k]."""
         import torch
         spec = self._fmt
         planar = spec is not None and spec.format != FMT_RGB_U8_HWC
         dt = {np.uint8: torch.uint8, np.float32: torch.float32, np.float16: torch.float16}[FMT_DTYPE[spec.format] if spec is not None else np.uint8]
         n = len(paths)
-        if not (out.is_cuda and out.is_contiguous() and out.dtype == dt and out.dim() == 4 and out.shape[0] == n and
+        if not (out.is_cuda and out.is_contiguous() and out.dtype == dt and out.dim() == 4 and out.shape[0] == n * k and
                 out.shape[1 if planar else 3] == 3):
             raise ValueError(f"out must be a contiguous CUDA tensor [{n}, 3, H, W] ([N, H, W, 3] for format 0) of {dt}")
         if out.device.index != self._device:
             raise ValueError(f"out is on {out.device}, the decoder on device {self._device}")
         H, W = (out.shape[2], out.shape[3]) if planar else (out.shape[1], out.shape[2])
-        per = output_bytes(W, H, spec.format if spec is not None else FMT_RGB_U8_HWC)
-        assert per == out[0].numel() * out.element_size()
+        per = output_bytes(W, H, spec.format if spec is not None else FMT_RGB_U8_HWC) * k   # (a file's k outputs)
+        assert per == out[0].numel() * out.element_size() * k
         # the decoder places images group by group (a group of one thread's files back to back, groups on 256-byte
         # steps of the region, in the order the threads get there): they land in a scratch region in their final
         # format and one device-to-device copy per image puts them in order
@@ -874,11 +973,11 @@ class BatchDecoder:
         torch.cuda.synchronize(out.device)
         self.set_device_output(scratch.data_ptr(), scratch.numel())
         try:
-            ptrs, sizes, st, t = self.run_to_device(paths, crops)
+            ptrs, sizes, st, t = self.run_to_device(paths, crops, views)
         finally:
             self.set_device_output(0, 0)
         st = list(st)
-        flat = out.view(n, -1).view(torch.uint8) if out.dtype != torch.uint8 else out.view(n, -1)
+        flat = out.view(n, -1).view(torch.uint8) if out.dtype != torch.uint8 else out.view(n, -1)   # (a row per FILE)
         base = scratch.data_ptr()
         for i in range(n):
             if st[i] != JB_OK or not ptrs[i]:
@@ -892,11 +991,18 @@ class BatchDecoder:
         return out, st, t
 
     # -- batches in a stream (jb_batch_decoder_submit / _collect): two in flight -----------------
-    def submit(self, paths, crops=None):
+    def submit(self, paths, crops=None, views=None):
         """-> a ticket (keeps the batch's arrays alive); the batch runs while the caller prepares the next one.
-        crops: as for run() (jb_batch_decoder_submit_crops, which copies them; a refusal is a JbError here)."""
+        crops: as for run() (jb_batch_decoder_submit_crops, which copies them; a refusal is a JbError here).
+        views: as for run() (jb_batch_decoder_submit_views, which copies them)."""
         t = _batch_args(paths)
-        if crops is not None:
+        if views is not None:
+            if crops is not None:
+                raise JbError(-9, "views cannot be combined with per-image rectangles (crops)")
+            arr, t["k"] = _view_array(views, t["n"])
+            _check(lib().jb_batch_decoder_submit_views(self._h, t["paths"], t["n"], arr, t["k"], t["rgb"], t["w"], t["h"], t["st"],
+                                                       ctypes.byref(t["id"])))
+        elif crops is not None:
             _check(lib().jb_batch_decoder_submit_crops(self._h, t["paths"], t["n"], _crop_array(crops, t["n"]), t["rgb"], t["w"], t["h"],
                                                        t["st"], ctypes.byref(t["id"])))
         else:

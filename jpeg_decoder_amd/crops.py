@@ -1,4 +1,5 @@
-"""Rectangles for the per-image crops of a batch (Context.blocks_to_rgb_device(..., crops=), BatchDecoder.run(..., crops=)).
+"""Rectangles for the per-image crops of a batch (Context.blocks_to_rgb_device(..., crops=), BatchDecoder.run(..., crops=)),
+and the K views per image of views=.
 
 Pure Python over a numpy.random.Generator: the rectangles of a batch can be drawn from the sizes that
 entropy_decode(jpeg_bytes, headers_only=True) reports, before anything is decoded.  Under an orientation (ORIENT_EXIF or
@@ -37,3 +38,14 @@ def random_resized_crop(width, height, rng, scale=(0.08, 1.0), ratio=(3 / 4, 4 /
         w, h = width, height
     w, h = min(max(w, 1), width), min(max(h, 1), height)
     return (width - w) // 2, (height - h) // 2, w, h
+
+
+def random_views(width, height, rng, k, p_mirror=0.5, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3)):
+    """k views of a width x height image for views= -> [(x, y, w, h, mirror)] * k: RandomResizedCrop followed by
+    RandomHorizontalFlip, k times.  Per view the draws of random_resized_crop in its order, then one
+    rng.random() < p_mirror; the same generator state gives the same views."""
+    views = []
+    for _ in range(int(k)):
+        x, y, w, h = random_resized_crop(width, height, rng, scale, ratio)
+        views.append((x, y, w, h, bool(float(rng.random()) < p_mirror)))
+    return views

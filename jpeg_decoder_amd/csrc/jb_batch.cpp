@@ -55,6 +55,16 @@ struct OutputRequest {
   }
 };
 
+// what a run has per FILE next to its path: a rectangle ("per-image rectangles": rois[i]), or k views ("views":
+// views[i * k + v]); neither: a plain run
+struct PerFile {
+  const jb_roi *rois = nullptr;
+  const jb_view *views = nullptr;
+  int k = 0;
+  const jb_roi *roi_of(int i) const { return rois ? &rois[i] : nullptr; }
+  const jb_view *views_of(int i) const { return views ? &views[(size_t)i * (size_t)k] : nullptr; }
+};
+
 struct Parsed {
   std::vector<uint8_t> bytes;
   bool loaded = false;  // `bytes` is the whole file (pass 1 reads only the head of a large file)
@@ -217,7 +227,7 @@ struct Run {
   std::vector<std::vector<int>> *deferred = nullptr;
   size_t slot_coef = 0, slot_rgb = 0;  // what a ring slot holds (one image may be larger than a group's bound, not than this)
   OutputRequest out;  // the decoder's
-  const jb_roi *rois = nullptr;  // "per-image rectangles" (jb_batch_decoder_run_crops): rois[i] belongs to paths[i]; else null
+  PerFile per;  // "per-image rectangles" (jb_batch_decoder_run_crops) and "views" (_run_views): what belongs to paths[i]
 };
 
 // pass 1 (per host thread): parse the headers of its files, so that the buffers can be sized once for
@@ -237,7 +247,9 @@ constexpr size_t kHeadBytes[2] = {(size_t)4 << 10, (size_t)64 << 10};
 // every size of the pixels that this file takes downstream -- staging, arena, ring slots, copies -- is the output's:
 // geo.rgb_bytes is set to the bytes of the plan's image: the reduced one at scale > 1, the format's with a planar format
 // (crop: this file's rectangle of a run with per-image rectangles, planned as the rectangle of a batch of one; else null)
-void parse_one(Parsed &p, const OutputRequest &out, const jb_roi *crop = nullptr) {
+// (views: this file's k views of a run with views, planned as a batch of one -- plan.image_bytes is then that of the k
+// outputs, so the FILE stays the unit of every size downstream; the array is the run's and outlives the plan)
+void parse_one(Parsed &p, const OutputRequest &out, const jb_roi *crop = nullptr, const jb_view *views = nullptr, int k = 0) {
   p.status = jb_entropy_decode(p.bytes.data(), p.bytes.size(), &p.desc, p.qtabs, nullptr, 0);
   if (p.status == JB_OK) p.status = jb_geometry_of(&p.desc, &p.geo);
   if (p.status != JB_OK) {
@@ -248,7 +260,12 @@ void parse_one(Parsed &p, const OutputRequest &out, const jb_roi *crop = nullptr
   // has just been parsed, so a head that parses holds it)
   int orient = out.orient;
   if (orient == JB_ORIENT_EXIF && jb_exif_orientation(p.bytes.data(), p.bytes.size(), &orient) != JB_OK) orient = JB_ORIENT_STORED;
-  p.plan = jb_out_plan_(&p.desc, out.scale, &out.spec, crop ? crop : out.roi_ptr(), out.target_ptr(), nullptr, 0, orient);
+  if (views) {
+    const jb_resize rs = {out.target.w, out.target.h, out.target.filter, out.target.reserved};
+    p.plan = jb_views_plan_(&p.desc, &out.spec, views, 1, k, &rs, orient);
+  } else {
+    p.plan = jb_out_plan_(&p.desc, out.scale, &out.spec, crop ? crop : out.roi_ptr(), out.target_ptr(), nullptr, 0, orient);
+  }
   p.status = p.plan.status;
   if (p.status == JB_OK) p.geo.rgb_bytes = p.plan.image_bytes;
   else p.error = p.plan.why;
@@ -267,7 +284,7 @@ void parse_pass(const Run &r, int t, std::vector<Parsed> &parsed, size_t *max_co
       ok = level < 2 ? jb_read_prefix_(r.paths[i], kHeadBytes[level], p.bytes, &p.loaded) : jb_read_file_(r.paths[i], p.bytes);
       *t_read += jb_now_s_() - a;
       if (level == 2) p.loaded = ok;
-      if (ok) parse_one(p, r.out, r.rois ? &r.rois[i] : nullptr);
+      if (ok) parse_one(p, r.out, r.per.roi_of(i), r.per.views_of(i), r.per.k);
     }
     if (!ok) {
       p.status = JB_ERR_FORMAT;
@@ -383,7 +400,7 @@ struct LaneWorker {
       p.have = true;
       p.loaded = ok;
       if (ok) {
-        parse_one(p, r.out, r.rois ? &r.rois[i] : nullptr);
+        parse_one(p, r.out, r.per.roi_of(i), r.per.views_of(i), r.per.k);
       } else {
         p.status = JB_ERR_FORMAT;
         p.error = "cannot read file";
@@ -604,7 +621,13 @@ struct LaneWorker {
     // head's plan with the members' rectangles next to it (the array is read before the submission returns)
     JbOutPlan plan = head.plan;
     std::vector<jb_roi> crops;
-    if (r.rois) {
+    std::vector<jb_view> views;  // "views": the members' views, k each, in the group's order
+    if (r.per.views) {
+      const jb_resize rs = {r.out.target.w, r.out.target.h, r.out.target.filter, r.out.target.reserved};
+      for (int j = 0; j < f.n; j++) views.insert(views.end(), parsed[(size_t)(f.k + j)].plan.views, parsed[(size_t)(f.k + j)].plan.views + r.per.k);
+      plan = jb_views_plan_(&head.desc, &r.out.spec, views.data(), f.n, r.per.k, &rs, head.plan.orient);
+    }
+    if (r.per.rois) {
       for (int j = 0; j < f.n; j++) crops.push_back(parsed[(size_t)(f.k + j)].plan.roi);
       plan = jb_out_plan_(&head.desc, r.out.scale, &r.out.spec, nullptr, r.out.target_ptr(), crops.data(), f.n, head.plan.orient);
     }
@@ -724,6 +747,7 @@ struct jb_batch_decoder {
     std::vector<std::string> path_text;  // the batch's paths, copied: the caller's array need not outlive submit
     std::vector<const char *> path_ptr;
     std::vector<jb_roi> rois;  // (jb_batch_decoder_submit_crops) the batch's rectangles, copied like the paths
+    std::vector<jb_view> views;  // (jb_batch_decoder_submit_views) the batch's views, copied too
   };
   Flight flights[2];
   int tickets = 0;
@@ -828,7 +852,7 @@ int create_single(int device_id, int n_threads, size_t max_coef_bytes, size_t ma
 
 // one device's share of a run; `top` = this decoder owns the arena (and recycles it)
 // (rois: the files' rectangles of a run with per-image rectangles, or null)
-int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_roi *rois, uint8_t **rgb, int32_t *widths,
+int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, const PerFile &per, uint8_t **rgb, int32_t *widths,
                int32_t *heights, int *statuses, double *times, bool top) {
   Totals tot;
   Shared dev;
@@ -868,7 +892,7 @@ int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, const
     r.lazy = lazy;
     r.deferred = &deferred;
     r.out = d->out;
-    r.rois = rois;
+    r.per = per;
     const double tr0 = jb_now_s_();
     std::vector<std::vector<Parsed>> parsed((size_t)nt);
     for (int t = 0; t < nt; t++) parsed[(size_t)t].resize(lists[(size_t)t].size());
@@ -1182,9 +1206,10 @@ int arrange_outputs(jb_batch_decoder *d, bool for_sides) {
   return JB_OK;
 }
 
-int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_roi *rois, uint8_t **rgb, int32_t *widths,
+int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, const PerFile &per, uint8_t **rgb, int32_t *widths,
              int32_t *heights, int *statuses, double *times) {
-  if (d->parts.empty()) return run_single(d, paths, n_paths, rois, rgb, widths, heights, statuses, times, d->arena == &d->own_arena);
+  const jb_roi *const rois = per.rois;
+  if (d->parts.empty()) return run_single(d, paths, n_paths, per, rgb, widths, heights, statuses, times, d->arena == &d->own_arena);
   // multi-device: file i -> part i % n_parts (images are independent: nothing crosses devices);
   // every part runs its share on its own host threads, concurrently with the others
   const int np = (int)d->parts.size();
@@ -1195,6 +1220,7 @@ int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, const j
   struct Share {
     std::vector<const char *> paths;
     std::vector<jb_roi> rois;  // (per-image rectangles: rectangle i goes where file i goes)
+    std::vector<jb_view> views;  // (views: and so do file i's k views)
     std::vector<uint8_t *> rgb;
     std::vector<int32_t> w, h;
     std::vector<int> st;
@@ -1206,6 +1232,7 @@ int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, const j
   for (int i = 0; i < n_paths; i++) {
     sh[(size_t)(i % np)].paths.push_back(paths[i]);
     if (rois) sh[(size_t)(i % np)].rois.push_back(rois[i]);
+    if (per.views) sh[(size_t)(i % np)].views.insert(sh[(size_t)(i % np)].views.end(), per.views_of(i), per.views_of(i) + per.k);
   }
   std::vector<std::thread> th;
   for (int k = 0; k < np; k++) {
@@ -1217,7 +1244,9 @@ int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, const j
     s.st.assign(n, JB_OK);
     th.emplace_back([&, k] {
       Share &m = sh[(size_t)k];
-      m.rc = run_single(d->parts[(size_t)k], m.paths.data(), (int)m.paths.size(), rois ? m.rois.data() : nullptr, m.rgb.data(),
+      PerFile mine;
+      mine.rois = rois ? m.rois.data() : nullptr, mine.views = per.views ? m.views.data() : nullptr, mine.k = per.k;
+      m.rc = run_single(d->parts[(size_t)k], m.paths.data(), (int)m.paths.size(), mine, m.rgb.data(),
                         m.w.data(), m.h.data(), m.st.data(), m.times, false);
       if (m.rc != JB_OK) m.text = jb_last_error(nullptr);  // thread-local text: fetch it on this thread
     });
@@ -1260,8 +1289,19 @@ int crops_state(const jb_batch_decoder *d, const char *fn) {
   return jb_fail_(nullptr, plan.status, (std::string(fn) + ": " + plan.why).c_str());
 }
 
-int run_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_roi *rois, uint8_t **rgb, int32_t *widths,
+// "views": no scale, no decoder-wide rectangle (JB_ERR_UNSUPPORTED), a target size (JB_ERR_STATE), k in 1..16
+int views_state(const jb_batch_decoder *d, int k, const char *fn) {
+  const std::string name = fn;
+  if (d->out.scale != 1) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, (name + ": views cannot be combined with a scale other than 1").c_str());
+  if (d->out.has_roi) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, (name + ": views cannot be combined with a rectangle for every image").c_str());
+  if (!d->out.has_resize) return jb_fail_(nullptr, JB_ERR_STATE, (name + ": views want a target size").c_str());
+  if (k < 1 || k > JB_VIEWS_MAX) return jb_fail_(nullptr, JB_ERR_GEOMETRY, (name + ": views_per_image is outside 1..16").c_str());
+  return JB_OK;
+}
+
+int run_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, const PerFile &per, uint8_t **rgb, int32_t *widths,
                 int32_t *heights, int *statuses, double *times, const char *fn) {
+  const jb_roi *const rois = per.rois;
   const std::string name = fn;
   if (!d || !paths || !rgb || !widths || !heights || !statuses) return jb_fail_(nullptr, JB_ERR_NULL, (name + ": NULL pointer").c_str());
   if (n_paths < 0) return jb_fail_(nullptr, JB_ERR_GEOMETRY, (name + ": negative count").c_str());
@@ -1270,11 +1310,15 @@ int run_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, cons
     const int rc = crops_state(d, fn);
     if (rc != JB_OK) return rc;
   }
+  if (per.views) {
+    const int rc = views_state(d, per.k, fn);
+    if (rc != JB_OK) return rc;
+  }
   if (d->split_for_sides) {
     int rc = arrange_outputs(d, false);
     if (rc != JB_OK) return rc;
   }
-  return run_impl(d, paths, n_paths, rois, rgb, widths, heights, statuses, times);
+  return run_impl(d, paths, n_paths, per, rgb, widths, heights, statuses, times);
 }
 
 }  // namespace
@@ -1282,20 +1326,31 @@ int run_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, cons
 extern "C" int jb_batch_decoder_run(jb_batch_decoder *d, const char *const *paths, int n_paths,
                                     uint8_t **rgb, int32_t *widths, int32_t *heights, int *statuses,
                                     double *times) {
-  return run_checked(d, paths, n_paths, nullptr, rgb, widths, heights, statuses, times, "jb_batch_decoder_run");
+  return run_checked(d, paths, n_paths, PerFile{}, rgb, widths, heights, statuses, times, "jb_batch_decoder_run");
 }
 
 extern "C" int jb_batch_decoder_run_crops(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_roi *rois, uint8_t **rgb,
                                           int32_t *widths, int32_t *heights, int *statuses, double *times) {
   if (!rois) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_run_crops: NULL pointer");
-  return run_checked(d, paths, n_paths, rois, rgb, widths, heights, statuses, times, "jb_batch_decoder_run_crops");
+  PerFile per;
+  per.rois = rois;
+  return run_checked(d, paths, n_paths, per, rgb, widths, heights, statuses, times, "jb_batch_decoder_run_crops");
+}
+
+extern "C" int jb_batch_decoder_run_views(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_view *views, int views_per_image,
+                                          uint8_t **rgb, int32_t *widths, int32_t *heights, int *statuses, double *times) {
+  if (!views) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_run_views: NULL pointer");
+  PerFile per;
+  per.views = views, per.k = views_per_image;
+  return run_checked(d, paths, n_paths, per, rgb, widths, heights, statuses, times, "jb_batch_decoder_run_views");
 }
 
 namespace {
 
 // jb_batch_decoder_submit, and (rois != null) jb_batch_decoder_submit_crops
-int submit_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_roi *rois, uint8_t **rgb, int32_t *widths,
+int submit_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, const PerFile &per, uint8_t **rgb, int32_t *widths,
                    int32_t *heights, int *statuses, int *ticket) {
+  const jb_roi *const rois = per.rois;
   if (!d || !paths || !rgb || !widths || !heights || !statuses || !ticket)
     return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_submit: NULL pointer");
   if (n_paths < 0) return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_submit: negative count");
@@ -1305,6 +1360,10 @@ int submit_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, c
     if (!paths[i]) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_submit: NULL path");
   if (rois) {
     const int rc = crops_state(d, "jb_batch_decoder_submit_crops");
+    if (rc != JB_OK) return rc;
+  }
+  if (per.views) {
+    const int rc = views_state(d, per.k, "jb_batch_decoder_submit_views");
     if (rc != JB_OK) return rc;
   }
   const int side = d->tickets & 1;
@@ -1331,7 +1390,10 @@ int submit_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, c
   for (int i = 0; i < n_paths; i++) f.path_ptr[(size_t)i] = f.path_text[(size_t)i].c_str();
   f.rois.clear();
   if (rois) f.rois.assign(rois, rois + n_paths);
-  const bool with_rois = rois != nullptr;
+  f.views.clear();
+  if (per.views) f.views.assign(per.views, per.views + (size_t)n_paths * (size_t)per.k);
+  const bool with_rois = rois != nullptr, with_views = per.views != nullptr;
+  const int views_k = per.k;
   f.busy = true;
   f.ticket = d->tickets++;
   f.rc = JB_OK;
@@ -1340,7 +1402,9 @@ int submit_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, c
   jb_batch_decoder::Flight *const fp = &f;
   try {
     f.th = std::thread([=] {
-      fp->rc = run_impl(target, fp->path_ptr.data(), n_paths, with_rois ? fp->rois.data() : nullptr, rgb, widths, heights, statuses, fp->times);
+      PerFile mine;
+      mine.rois = with_rois ? fp->rois.data() : nullptr, mine.views = with_views ? fp->views.data() : nullptr, mine.k = views_k;
+      fp->rc = run_impl(target, fp->path_ptr.data(), n_paths, mine, rgb, widths, heights, statuses, fp->times);
       if (fp->rc != JB_OK) fp->text = jb_last_error(nullptr);  // thread-local text: fetch it on this thread
     });
   } catch (const std::exception &e) {  // no thread to be had: nothing is in flight
@@ -1356,13 +1420,23 @@ int submit_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, c
 
 extern "C" int jb_batch_decoder_submit(jb_batch_decoder *d, const char *const *paths, int n_paths, uint8_t **rgb,
                                        int32_t *widths, int32_t *heights, int *statuses, int *ticket) {
-  return submit_checked(d, paths, n_paths, nullptr, rgb, widths, heights, statuses, ticket);
+  return submit_checked(d, paths, n_paths, PerFile{}, rgb, widths, heights, statuses, ticket);
 }
 
 extern "C" int jb_batch_decoder_submit_crops(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_roi *rois, uint8_t **rgb,
                                              int32_t *widths, int32_t *heights, int *statuses, int *ticket) {
   if (!rois) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_submit_crops: NULL pointer");
-  return submit_checked(d, paths, n_paths, rois, rgb, widths, heights, statuses, ticket);
+  PerFile per;
+  per.rois = rois;
+  return submit_checked(d, paths, n_paths, per, rgb, widths, heights, statuses, ticket);
+}
+
+extern "C" int jb_batch_decoder_submit_views(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_view *views, int views_per_image,
+                                             uint8_t **rgb, int32_t *widths, int32_t *heights, int *statuses, int *ticket) {
+  if (!views) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_submit_views: NULL pointer");
+  PerFile per;
+  per.views = views, per.k = views_per_image;
+  return submit_checked(d, paths, n_paths, per, rgb, widths, heights, statuses, ticket);
 }
 
 extern "C" int jb_batch_decoder_collect(jb_batch_decoder *d, int ticket, double *times) {

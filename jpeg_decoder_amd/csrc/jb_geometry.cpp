@@ -3,6 +3,7 @@
 // a CPU-only toolchain with sanitizers (tools/fuzz/).
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "../../include/jpegblk.h"
 #include "jb_filter.h"
@@ -115,6 +116,17 @@ int jb_crops_check(const jb_image_desc *d, const jb_roi *rois, int n, int32_t ou
   return plan.status;
 }
 
+int jb_views_check(const jb_image_desc *d, const jb_view *views, int n_images, int views_per_image, const jb_resize *rs, int *bad_index) {
+  if (bad_index) *bad_index = -1;
+  if (!d || !rs || (!views && n_images > 0 && views_per_image > 0)) return JB_ERR_NULL;
+  jb_geometry g;
+  const int rc = jb_geometry_of(d, &g);
+  if (rc != JB_OK) return rc;
+  const JbOutPlan plan = jb_views_plan_(d, nullptr, views, n_images, views_per_image, rs);
+  if (bad_index) *bad_index = plan.bad_crop;
+  return plan.status;
+}
+
 int jb_filter_check(const jb_image_desc *d, const jb_roi *roi, const jb_resize *rs) {
   if (!d || !rs) return JB_ERR_NULL;
   jb_geometry g;
@@ -182,6 +194,58 @@ jb_roi jb_filter_window_of_(const jb_image_desc *d, const jb_roi *roi, int32_t o
   jb_filter_span(jb_filter_axis(filter, d->width, r.x, r.x + r.width, out_w), out_w, &x0, &x1);
   jb_filter_span(jb_filter_axis(filter, d->height, r.y, r.y + r.height, out_h), out_h, &y0, &y1);
   return jb_roi{x0, y0, x1 - x0, y1 - y0};
+}
+
+JbOutPlan jb_views_plan_(const jb_image_desc *d, const jb_output_spec *spec, const jb_view *views, int n_images, int k, const jb_resize *rs,
+                         int orientation) {
+  JbOutPlan p;
+  memset(&p, 0, sizeof p);
+  p.bad_crop = -1;
+  p.orient = 1;
+  auto refuse = [&p](int status, const char *why, int bad = -1) {
+    memset(&p, 0, sizeof p);
+    p.orient = 1;
+    p.status = status, p.why = why, p.bad_crop = bad;
+    return p;
+  };
+  if (!d || !rs) return refuse(JB_ERR_NULL, "null descriptor or jb_resize");
+  if (n_images < 0) return refuse(JB_ERR_GEOMETRY, "negative count");
+  if (k < 1 || k > JB_VIEWS_MAX) return refuse(JB_ERR_GEOMETRY, "views_per_image is outside 1..16");
+  const int64_t n = (int64_t)n_images * k;
+  if (n > 0 && !views) return refuse(JB_ERR_NULL, "views is NULL");
+  if (n > 0x7fffffffLL) return refuse(JB_ERR_CAPACITY, "too many views");
+  static thread_local char text[224];
+  std::vector<jb_roi> rects((size_t)n);
+  for (int64_t i = 0; i < n; i++) {
+    const jb_view &v = views[i];
+    if ((v.flags & ~JB_VIEW_MIRROR) != 0 || v.reserved != 0) {
+      snprintf(text, sizeof text, "image %d, view %d: unknown flag bits (or reserved is not 0)", (int)(i / k), (int)(i % k));
+      return refuse(JB_ERR_GEOMETRY, text, (int)i);
+    }
+    rects[(size_t)i] = jb_roi{v.x, v.y, v.width, v.height};
+  }
+  // the rectangles, the target and the filter: exactly the checks of per-image rectangles, in their order
+  static const jb_roi none = {0, 0, 0, 0};
+  const bool no_target = rs->out_w == 0 && rs->out_h == 0;
+  // ("no target size" is JB_ERR_STATE whatever the filter: a filter of 1 makes the plan say so where the target is checked)
+  const JbTarget t = {rs->out_w, rs->out_h, no_target && rs->filter == JB_FILTER_AREA ? JB_FILTER_BILINEAR : rs->filter, rs->reserved};
+  p = jb_out_plan_(d, 1, spec, nullptr, &t, n > 0 ? rects.data() : &none, (int)n, orientation);
+  if (p.status != JB_OK) {
+    const int bad = p.bad_crop;
+    if (bad >= 0 && p.status == JB_ERR_GEOMETRY) {
+      const jb_view &v = views[bad];
+      const bool swap = jb_orient_bits(orientation).transpose != 0;
+      snprintf(text, sizeof text, "image %d, view %d: the rectangle %d x %d at (%d, %d) does not lie in the %d x %d image", bad / k, bad % k,
+               v.width, v.height, v.x, v.y, swap ? d->height : d->width, swap ? d->width : d->height);
+      return refuse(JB_ERR_GEOMETRY, text, bad);
+    }
+    return refuse(p.status, p.why, bad);
+  }
+  p.crops = nullptr, p.n_crops = 0;  // (rects ends here: the launch reads the views)
+  p.views = views, p.views_per_image = k, p.n_views = (int32_t)n;
+  p.view_bytes = p.image_bytes;
+  p.image_bytes = p.view_bytes * k;
+  return p;
 }
 
 // jb_plan.h: the only place that turns (frame, scale, spec, rectangle, target) into the output's sizes and strides

@@ -1,8 +1,13 @@
 // jb_kernels.h -- internal interface between the C-ABI layer (jb_api.cpp) and the HIP
 // kernels (jb_kernels.hip).  Not part of the public ABI (include/jpegblk.h).
 #pragma once
-#include <hip/hip_runtime_api.h>
 #include <stdint.h>
+#ifdef JB_KERNELS_HOST  // (tools/fuzz/views_kernel_check.cpp: kernel bodies compiled for the CPU, no HIP headers)
+typedef int hipError_t;
+typedef void *hipStream_t;
+#else
+#include <hip/hip_runtime_api.h>
+#endif
 
 #include "jb_knobs.h"
 #include "jb_orient.h"
@@ -143,6 +148,34 @@ struct JbFilter {
 hipError_t jbk_filter_launch(const JbFilter &p, int filter, int format, hipStream_t stream);
 // the same with a geometry per image (p.one is not looked at); at most kJbCropsPerLaunch images
 hipError_t jbk_filter_launch_crops(const JbFilter &p, const JbFilterTable &table, int filter, int format, hipStream_t stream);
+
+// "Views" (jb_resample.hip): the K outputs of an image read K sub-rectangles of its UNION, which the pixel kernel wrote
+// once -- tight interleaved uint8 rows of src_row_bytes = 3 * union_w at src_offset in the scratch.  A launch takes up to
+// kJbCropsPerLaunch ROWS (outputs, not images): row n is output n of p.dst (the caller has moved p.dst to the launch's
+// first output), so one pixel launch may be followed by several of these.  Lane j computes output column j exactly as
+// without a mirror and stores it at column ow - 1 - j.  32 bytes a row: 32 rows and JbResample are 1.1 KB of the 4 KB
+// argument segment.
+struct JbViewRow {
+  int64_t src_offset;     // bytes from the scratch's base to the union's first pixel
+  int32_t src_row_bytes;  // 3 * union_w: at most 3 * 65535
+  int32_t dx, dy, w, h;   // the view's rectangle inside the union: dx + w <= union_w, dy + h <= union_h
+  int32_t mirror;         // 1: store column j at ow - 1 - j
+};
+struct JbViewTable {
+  JbViewRow r[kJbCropsPerLaunch];
+};
+// jbk_resample_launch_crops with a view per row: p.n_images = the rows of the launch (p.iw, p.ih and p.src_image_stride
+// are not looked at).  A source row is read through a descriptor of the UNION's row + 4 bytes: the scratch's slack
+// covers the last row of the last union, as it covers the last image's without views.
+hipError_t jbk_resample_launch_views(const JbResample &p, const JbViewTable &table, int format, hipStream_t stream);
+// The filtered counterpart: a JbFilterRow already separates rectangle, window and offset -- the window is the union (it
+// must CONTAIN jb_filter_window of the row's rectangle, where jbk_filter_launch_crops wants exactly that window), and bit
+// n of `mirror` is row n's flag.  40 bytes a row and 4 for the flags: 1.4 KB with JbFilter.
+struct JbViewFilterTable {
+  JbFilterRow r[kJbCropsPerLaunch];
+  uint32_t mirror;
+};
+hipError_t jbk_filter_launch_views(const JbFilter &p, const JbViewFilterTable &table, int filter, int format, hipStream_t stream);
 
 // "Orientation" (jb_orient.hip; the arguments are described in jb_orient.h).  One 256-lane workgroup per 64 x 64 tile of
 // source pixels.  More than 2^31 - 1 workgroups, or an argument outside its range: hipErrorInvalidValue.

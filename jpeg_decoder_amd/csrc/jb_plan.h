@@ -49,6 +49,15 @@ struct JbOutPlan {
   const jb_roi *crops;
   int32_t n_crops;
   int32_t bad_crop;  // status == JB_ERR_GEOMETRY because of a rectangle: which one; else -1
+  // "views" (include/jpegblk.h; jb_views_plan_ alone sets these): output i * views_per_image + v of the launch is the
+  // rectangle views[i * views_per_image + v] of image i, resized to the target and then mirrored when its flag says so.
+  // has_resize is set, crops is not, src_w / src_h / tmp_image_bytes are 0.  BORROWED like crops.  THE IMAGE STAYS THE
+  // UNIT: image_bytes is that of an image's views_per_image outputs back to back (view_bytes each); out_w, out_h and
+  // row_stride are one output's.  bad_crop indexes the flat array.
+  const jb_view *views;
+  int32_t views_per_image;  // 0: no views
+  int32_t n_views;          // images * views_per_image
+  int64_t view_bytes;       // 3 * out_w * out_h * esize
   // "orientation" (include/jpegblk.h): the plan was made for T_o of the frame -- every field above is in oriented
   // coordinates, of the frame with width and height swapped for 5..8.  1: none.  0 (JB_ORIENT_EXIF, which only a file
   // resolves): a plan of the stored frame that no launch takes (JB_ERR_STATE where the launch is asked for).
@@ -75,6 +84,11 @@ struct JbTarget {
 jb_roi jb_filter_window_of_(const jb_image_desc *desc, const jb_roi *roi, int32_t out_w, int32_t out_h, int filter);
 JbOutPlan jb_out_plan_(const jb_image_desc *desc, int scale, const jb_output_spec *spec, const jb_roi *roi = nullptr,
                        const JbTarget *target = nullptr, const jb_roi *crops = nullptr, int n_crops = 0, int orientation = 1);
+// "views": the plan of n_images * views_per_image views under `rs` (null: JB_ERR_NULL) -- views_per_image, then every view's
+// flags and reserved, then the rectangles, the target ("no target size": JB_ERR_STATE) and the filter, as jb_out_plan_
+// checks per-image rectangles.  views may be null when there are none.
+JbOutPlan jb_views_plan_(const jb_image_desc *desc, const jb_output_spec *spec, const jb_view *views, int n_images, int views_per_image,
+                         const jb_resize *rs, int orientation = 1);
 // "orientation": the refusal of a plan with orient == 0 at a launch, and of a scale with an orientation
 #define kJbOrientExifText "JB_ORIENT_EXIF takes the orientation from a file: this entry point has none (set 1..8)"
 #define kJbOrientScaleText "an orientation other than 1 cannot be combined with a scale other than 1"

@@ -16,14 +16,27 @@
 // the fourth byte is the next pixel's red, or one byte of the slack behind the scratch, and is not looked at).  The
 // descriptor's range (the row + 4 bytes) keeps every load inside the scratch whatever the arithmetic above it does.
 // The two divisions per lane that bound the column footprint, and the two per wave for the rows, are outside the loops.
+//
+// "Views" (include/jpegblk.h; MODE = kViews of both kernels): an output's source is a w x h sub-rectangle at (dx, dy) of
+// a UNION the pixel kernel wrote once for all the views of an image, and a mirrored view stores column j at ow - 1 - j.
+// The footprint, the weights and the sums are those of column j -- the bits are defined by the unmirrored output -- so a
+// wave's 64 stores are still one contiguous run, walked backwards.  The bodies also compile for the CPU
+// (JB_KERNELS_HOST: tools/fuzz/views_kernel_check.cpp stubs the built-ins and runs a workgroup as 256 threads).
+#ifndef JB_KERNELS_HOST
 #include <hip/hip_runtime.h>
+#define JB_DYNAMIC_LDS(name) extern __shared__ int32_t name[]
+#endif
 
 #include "jb_kernels.h"
+
+// what a kernel's table argument is: none (one geometry for the launch), a rectangle per image, a view per output
+enum { kNoTable = 0, kCrops = 1, kViews = 2 };
 
 static constexpr int kResampleRows = 4;  // output rows (= waves) per workgroup
 
 // the rows of a kernel's by-value table argument
 static __device__ __forceinline__ const JbCrop *crops_of(const JbCropTable &table) { return table.c; }
+static __device__ __forceinline__ const JbViewRow *views_of(const JbViewTable &table) { return table.r; }
 
 // floor(n / d) for n < 2^41, 1 <= d < 2^32 with a quotient of at most 255: a float estimate (a few units off at the
 // worst) and integer correction steps that make it exact whatever the estimate was
@@ -37,9 +50,12 @@ static __device__ __forceinline__ uint32_t div_to_u8(uint64_t n, uint32_t d, flo
 // CROPS ("per-image rectangles"; TABLE is then JbCropTable, a second kernel argument, and empty otherwise): the source of
 // image `img` is table.c[img].w x .h at p.src + .tmp_offset instead of p.iw x p.ih at p.src + img * p.src_image_stride --
 // img comes from blockIdx, so the table reads are scalar loads and everything derived from them stays wave-uniform.
-template <int FORMAT, bool CROPS = false, typename... TABLE>
+// VIEWS (TABLE is JbViewTable): `img` is the launch's row = the output's index behind p.dst; its source is the row's
+// w x h at (dx, dy) of the union at p.src + .src_offset, rows .src_row_bytes apart, and .mirror reverses the store.
+template <int FORMAT, int MODE = kNoTable, typename... TABLE>
 __global__ __launch_bounds__(64 * kResampleRows) void jb_resample_kernel(const JbResample p, const TABLE... table) {
-  static_assert(sizeof...(TABLE) == (CROPS ? 1 : 0), "the table is the second argument of the CROPS instantiations alone");
+  constexpr bool CROPS = MODE == kCrops, VIEWS = MODE == kViews;
+  static_assert(sizeof...(TABLE) == (MODE != kNoTable ? 1 : 0), "the table is the second argument of the CROPS and VIEWS instantiations alone");
   // (the wave id is wave-uniform, and only readfirstlane tells the compiler so)
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = (int)(threadIdx.x & 63);
@@ -57,6 +73,15 @@ __global__ __launch_bounds__(64 * kResampleRows) void jb_resample_kernel(const J
     iw = (uint32_t)c.w, ih = (uint32_t)c.h;
     src_offset = c.tmp_offset;
   }
+  // VIEWS: the union's row length, the view's first column in it, and the column this lane stores (else: constants)
+  [[maybe_unused]] uint32_t union_row_bytes = 0, dx = 0, js = j;
+  if constexpr (VIEWS) {
+    const JbViewRow &v = views_of(table...)[img];
+    iw = (uint32_t)v.w, ih = (uint32_t)v.h;
+    union_row_bytes = (uint32_t)v.src_row_bytes, dx = (uint32_t)v.dx;
+    src_offset = v.src_offset + (int64_t)v.dy * v.src_row_bytes;
+    if (v.mirror) js = ow - 1 - j;
+  }
 
   // the footprints on the common grid: products below 65535^2 < 2^32
   const uint32_t r0 = k * ih / oh, r1 = ((k + 1) * ih - 1) / oh;  // source rows r0..r1, wave-uniform
@@ -67,14 +92,16 @@ __global__ __launch_bounds__(64 * kResampleRows) void jb_resample_kernel(const J
   const uint32_t wy0 = min((r0 + 1) * oh, (k + 1) * ih) - k * ih;
   const uint32_t wy1 = (k + 1) * ih - r1 * oh;  // (used when r1 > r0)
 
-  const uint8_t *const src = p.src + (CROPS ? src_offset : (int64_t)img * p.src_image_stride);
-  const int64_t src_row_bytes = 3LL * iw;
+  const uint8_t *const src = p.src + (CROPS || VIEWS ? src_offset : (int64_t)img * p.src_image_stride);
+  // (VIEWS: the descriptor is the UNION's row + 4 bytes, the view's columns start 3 * dx into it)
+  const int64_t src_row_bytes = VIEWS ? (int64_t)union_row_bytes : 3LL * iw;
+  const uint32_t i_dx = VIEWS ? dx : 0;
   uint64_t acc[3] = {0, 0, 0};
   for (uint32_t r = r0; r <= r1; r++) {
     const __amdgpu_buffer_rsrc_t row =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src + (int64_t)r * src_row_bytes), 0, (int)(3 * iw + 4), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src + (int64_t)r * src_row_bytes), 0, (int)((VIEWS ? union_row_bytes : 3 * iw) + 4), 0x00020000);
     // the horizontal partial sum: sum of wx * sample <= 255 * iw < 2^24
-    uint32_t px = __builtin_amdgcn_raw_buffer_load_b32(row, (int)(3 * i0), 0, 0);
+    uint32_t px = __builtin_amdgcn_raw_buffer_load_b32(row, (int)(3 * (i0 + i_dx)), 0, 0);
     uint32_t h[3] = {wx0 * (px & 0xffu), wx0 * ((px >> 8) & 0xffu), wx0 * ((px >> 16) & 0xffu)};
     if (i1 > i0) {
       uint32_t m[3] = {0, 0, 0};  // the samples of weight ow
@@ -82,15 +109,15 @@ __global__ __launch_bounds__(64 * kResampleRows) void jb_resample_kernel(const J
       for (; i + 8 <= i1; i += 8) {  // eight loads in flight: a long footprint is bound by their latency
         uint32_t v[8];
 #pragma unroll
-        for (int u = 0; u < 8; u++) v[u] = __builtin_amdgcn_raw_buffer_load_b32(row, (int)(3 * (i + u)), 0, 0);
+        for (int u = 0; u < 8; u++) v[u] = __builtin_amdgcn_raw_buffer_load_b32(row, (int)(3 * (i + i_dx + u)), 0, 0);
 #pragma unroll
         for (int u = 0; u < 8; u++) m[0] += v[u] & 0xffu, m[1] += (v[u] >> 8) & 0xffu, m[2] += (v[u] >> 16) & 0xffu;
       }
       for (; i < i1; i++) {
-        px = __builtin_amdgcn_raw_buffer_load_b32(row, (int)(3 * i), 0, 0);
+        px = __builtin_amdgcn_raw_buffer_load_b32(row, (int)(3 * (i + i_dx)), 0, 0);
         m[0] += px & 0xffu, m[1] += (px >> 8) & 0xffu, m[2] += (px >> 16) & 0xffu;
       }
-      px = __builtin_amdgcn_raw_buffer_load_b32(row, (int)(3 * i1), 0, 0);
+      px = __builtin_amdgcn_raw_buffer_load_b32(row, (int)(3 * (i1 + i_dx)), 0, 0);
 #pragma unroll
       for (int c = 0; c < 3; c++) h[c] += ow * m[c] + wx1 * ((px >> (8 * c)) & 0xffu);
     }
@@ -106,16 +133,16 @@ __global__ __launch_bounds__(64 * kResampleRows) void jb_resample_kernel(const J
   for (int c = 0; c < 3; c++) {
     const uint32_t u = div_to_u8(acc[c] + (d >> 1), d, rcp_d);
     if constexpr (FORMAT == 0) {
-      dst[3 * (int64_t)j + c] = (uint8_t)u;
+      dst[3 * (int64_t)js + c] = (uint8_t)u;
     } else if constexpr (FORMAT == 1) {
-      dst[(int64_t)c * p.dst_plane_stride + j] = (uint8_t)u;
+      dst[(int64_t)c * p.dst_plane_stride + js] = (uint8_t)u;
     } else {
       // the planar store stage's expression, operation for operation: u8 -> f32 (exact), one f32 multiply, one f32 add
       // (separate instructions: built with -ffp-contract=off), for f16 one v_cvt_f16_f32 (round to nearest even)
       const float f = (float)u * p.scale[c] + p.bias[c];
       uint8_t *const at = dst + (int64_t)c * p.dst_plane_stride;
-      if constexpr (FORMAT == 2) ((float *)at)[j] = f;
-      else ((_Float16 *)at)[j] = (_Float16)f;
+      if constexpr (FORMAT == 2) ((float *)at)[js] = f;
+      else ((_Float16 *)at)[js] = (_Float16)f;
     }
   }
 }
@@ -130,6 +157,29 @@ static bool resample_grid(JbResample &p, dim3 *grid) {
   return true;
 }
 
+#ifndef JB_KERNELS_HOST
+hipError_t jbk_resample_launch_views(const JbResample &q, const JbViewTable &table, int format, hipStream_t stream) {
+  if (format < 0 || format > 3 || q.ow < 1 || q.oh < 1 || q.ow > 65535 || q.oh > 65535 || q.n_images < 1 || q.n_images > kJbCropsPerLaunch)
+    return hipErrorInvalidValue;
+  for (int i = 0; i < q.n_images; i++) {
+    const JbViewRow &v = table.r[i];
+    if (v.w < 1 || v.h < 1 || v.w > 65535 || v.h > 65535 || v.dx < 0 || v.dy < 0 || v.dy > 65535 || v.src_offset < 0 || v.src_row_bytes > 3 * 65535 ||
+        3 * ((int64_t)v.dx + v.w) > v.src_row_bytes || (v.mirror & ~1))
+      return hipErrorInvalidValue;
+  }
+  JbResample p = q;
+  dim3 grid;
+  if (!resample_grid(p, &grid)) return hipErrorInvalidValue;
+  const dim3 block(64 * kResampleRows);
+  switch (format) {
+    case 0: hipLaunchKernelGGL((jb_resample_kernel<0, kViews, JbViewTable>), grid, block, 0, stream, p, table); break;
+    case 1: hipLaunchKernelGGL((jb_resample_kernel<1, kViews, JbViewTable>), grid, block, 0, stream, p, table); break;
+    case 2: hipLaunchKernelGGL((jb_resample_kernel<2, kViews, JbViewTable>), grid, block, 0, stream, p, table); break;
+    default: hipLaunchKernelGGL((jb_resample_kernel<3, kViews, JbViewTable>), grid, block, 0, stream, p, table); break;
+  }
+  return hipGetLastError();
+}
+
 hipError_t jbk_resample_launch_crops(const JbResample &q, const JbCropTable &table, int format, hipStream_t stream) {
   if (format < 0 || format > 3 || q.ow < 1 || q.oh < 1 || q.ow > 65535 || q.oh > 65535 || q.n_images < 1 || q.n_images > kJbCropsPerLaunch)
     return hipErrorInvalidValue;
@@ -141,10 +191,10 @@ hipError_t jbk_resample_launch_crops(const JbResample &q, const JbCropTable &tab
   if (!resample_grid(p, &grid)) return hipErrorInvalidValue;
   const dim3 block(64 * kResampleRows);
   switch (format) {
-    case 0: hipLaunchKernelGGL((jb_resample_kernel<0, true, JbCropTable>), grid, block, 0, stream, p, table); break;
-    case 1: hipLaunchKernelGGL((jb_resample_kernel<1, true, JbCropTable>), grid, block, 0, stream, p, table); break;
-    case 2: hipLaunchKernelGGL((jb_resample_kernel<2, true, JbCropTable>), grid, block, 0, stream, p, table); break;
-    default: hipLaunchKernelGGL((jb_resample_kernel<3, true, JbCropTable>), grid, block, 0, stream, p, table); break;
+    case 0: hipLaunchKernelGGL((jb_resample_kernel<0, kCrops, JbCropTable>), grid, block, 0, stream, p, table); break;
+    case 1: hipLaunchKernelGGL((jb_resample_kernel<1, kCrops, JbCropTable>), grid, block, 0, stream, p, table); break;
+    case 2: hipLaunchKernelGGL((jb_resample_kernel<2, kCrops, JbCropTable>), grid, block, 0, stream, p, table); break;
+    default: hipLaunchKernelGGL((jb_resample_kernel<3, kCrops, JbCropTable>), grid, block, 0, stream, p, table); break;
   }
   return hipGetLastError();
 }
@@ -165,6 +215,7 @@ hipError_t jbk_resample_launch(const JbResample &q, int format, hipStream_t stre
   }
   return hipGetLastError();
 }
+#endif  // JB_KERNELS_HOST
 
 // ---- "resampling filters" (include/jpegblk.h): Pillow's 8-bit bilinear / bicubic resampling, bit for bit ----------------
 // Pillow's two passes inside one workgroup.  A workgroup owns 64 output columns x kFilterRows output rows of one image:
@@ -189,6 +240,8 @@ static constexpr int kFilterRows = 8;
 static constexpr int kFilterLdsBytes = 64 << 10;  // what one workgroup may have
 
 static __device__ __forceinline__ const JbFilterRow *rows_of(const JbFilterTable &table) { return table.r; }
+static __device__ __forceinline__ const JbFilterRow *rows_of(const JbViewFilterTable &table) { return table.r; }
+static __device__ __forceinline__ bool mirror_of(const JbViewFilterTable &table, uint32_t row) { return (table.mirror >> row) & 1u; }
 static __device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
 
 // one lane's weights of output `i` of axis `a` (i < n: else none) into tab[t * stride], t < taps, zero behind its own
@@ -217,10 +270,13 @@ static __device__ __forceinline__ int filter_weights(const JbFilterAxis &a, int 
   return lo;
 }
 
-template <int FILTER, int FORMAT, bool CROPS = false, typename... TABLE>
+// VIEWS (TABLE is JbViewFilterTable): `img` is the launch's row = the output's index behind p.dst; the row's window is its
+// image's union, which holds the rectangle's own window, and its bit of table.mirror reverses the store.
+template <int FILTER, int FORMAT, int MODE = kNoTable, typename... TABLE>
 __global__ __launch_bounds__(256) void jb_filter_kernel(const JbFilter q, const TABLE... table) {
-  static_assert(sizeof...(TABLE) == (CROPS ? 1 : 0), "the table is the second argument of the CROPS instantiations alone");
-  extern __shared__ int32_t filter_lds[];
+  constexpr bool CROPS = MODE != kNoTable, VIEWS = MODE == kViews;
+  static_assert(sizeof...(TABLE) == (CROPS ? 1 : 0), "the table is the second argument of the CROPS and VIEWS instantiations alone");
+  JB_DYNAMIC_LDS(filter_lds);
   const JbResample &p = q.base;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = (int)(threadIdx.x & 63);
@@ -247,6 +303,9 @@ __global__ __launch_bounds__(256) void jb_filter_kernel(const JbFilter q, const 
   uint32_t *const T = (uint32_t *)(ny + kFilterRows);        // [t_rows][64]: r | g << 8 | b << 16
 
   const int j = (int)tx * 64 + lane;  // output column
+  [[maybe_unused]] int js = j;        // the column this lane stores
+  if constexpr (VIEWS)
+    if (mirror_of(table..., img)) js = ow - 1 - j;
   const int k0 = (int)ty * kFilterRows;
   if (wave == 0) {
     int count;
@@ -324,21 +383,22 @@ __global__ __launch_bounds__(256) void jb_filter_kernel(const JbFilter q, const 
       const uint32_t u = (uint32_t)clip8(acc[i][c] >> 22);
       // (jb_resample_kernel's store, operation for operation)
       if constexpr (FORMAT == 0) {
-        dst[3 * (int64_t)j + c] = (uint8_t)u;
+        dst[3 * (int64_t)js + c] = (uint8_t)u;
       } else if constexpr (FORMAT == 1) {
-        dst[(int64_t)c * p.dst_plane_stride + j] = (uint8_t)u;
+        dst[(int64_t)c * p.dst_plane_stride + js] = (uint8_t)u;
       } else {
         const float f = (float)u * p.scale[c] + p.bias[c];
         uint8_t *const at = dst + (int64_t)c * p.dst_plane_stride;
-        if constexpr (FORMAT == 2) ((float *)at)[j] = f;
-        else ((_Float16 *)at)[j] = (_Float16)f;
+        if constexpr (FORMAT == 2) ((float *)at)[js] = f;
+        else ((_Float16 *)at)[js] = (_Float16)f;
       }
     }
   }
 }
 
 // the launch's grid and LDS: tx_cap / ty_cap / t_rows from the geometry of its n rows; 0 bytes: not launchable
-static size_t filter_plan(JbFilter &p, const JbFilterRow *rows, int n, int filter, dim3 *grid) {
+// (contains: a window may be larger than jb_filter_window of its rectangle -- the views' unions)
+static size_t filter_plan(JbFilter &p, const JbFilterRow *rows, int n, int filter, dim3 *grid, bool contains = false) {
   if (filter != 1 && filter != 2) return 0;
   if (p.base.ow < 1 || p.base.oh < 1 || p.base.ow > 65535 || p.base.oh > 65535 || p.base.n_images < 1 || p.frame_w < 1 || p.frame_h < 1 ||
       p.frame_w > 65535 || p.frame_h > 65535)
@@ -353,7 +413,13 @@ static size_t filter_plan(JbFilter &p, const JbFilterRow *rows, int n, int filte
     int x0, x1, y0, y1;
     jb_filter_span(ax, p.base.ow, &x0, &x1);
     jb_filter_span(ay, p.base.oh, &y0, &y1);
-    if (r.win_x != x0 || r.win_y != y0 || r.win_w != x1 - x0 || r.win_h != y1 - y0) return 0;
+    if (contains) {
+      if (r.win_x < 0 || r.win_y < 0 || r.win_w < 1 || r.win_h < 1 || r.win_x > x0 || r.win_y > y0 || r.win_x + (int64_t)r.win_w < x1 ||
+          r.win_y + (int64_t)r.win_h < y1 || r.win_x + (int64_t)r.win_w > p.frame_w || r.win_y + (int64_t)r.win_h > p.frame_h)
+        return 0;
+    } else if (r.win_x != x0 || r.win_y != y0 || r.win_w != x1 - x0 || r.win_h != y1 - y0) {
+      return 0;
+    }
     const int tx = jb_filter_taps(ax), ty = jb_filter_taps(ay);
     if (tx > kJbFilterMaxTaps || ty > kJbFilterMaxTaps) return 0;
     if (tx > p.tx_cap) p.tx_cap = tx;
@@ -373,6 +439,7 @@ static size_t filter_plan(JbFilter &p, const JbFilterRow *rows, int n, int filte
   return fixed + (size_t)p.t_rows * 256;
 }
 
+#ifndef JB_KERNELS_HOST
 #define JB_FILTER_LAUNCH(FILTER, CROPS, ...)                                                                                  \
   switch (format) {                                                                                                           \
     case 0: hipLaunchKernelGGL((jb_filter_kernel<FILTER, 0, CROPS JB_FILTER_TABLE>), grid, dim3(256), lds, stream, __VA_ARGS__); break; \
@@ -389,9 +456,9 @@ hipError_t jbk_filter_launch(const JbFilter &q, int filter, int format, hipStrea
   if (!lds) return hipErrorInvalidValue;
 #define JB_FILTER_TABLE
   if (filter == 1) {
-    JB_FILTER_LAUNCH(1, false, p)
+    JB_FILTER_LAUNCH(1, kNoTable, p)
   } else {
-    JB_FILTER_LAUNCH(2, false, p)
+    JB_FILTER_LAUNCH(2, kNoTable, p)
   }
 #undef JB_FILTER_TABLE
   return hipGetLastError();
@@ -405,11 +472,28 @@ hipError_t jbk_filter_launch_crops(const JbFilter &q, const JbFilterTable &table
   if (!lds) return hipErrorInvalidValue;
 #define JB_FILTER_TABLE , JbFilterTable
   if (filter == 1) {
-    JB_FILTER_LAUNCH(1, true, p, table)
+    JB_FILTER_LAUNCH(1, kCrops, p, table)
   } else {
-    JB_FILTER_LAUNCH(2, true, p, table)
+    JB_FILTER_LAUNCH(2, kCrops, p, table)
+  }
+#undef JB_FILTER_TABLE
+  return hipGetLastError();
+}
+
+hipError_t jbk_filter_launch_views(const JbFilter &q, const JbViewFilterTable &table, int filter, int format, hipStream_t stream) {
+  if (format < 0 || format > 3 || q.base.n_images < 1 || q.base.n_images > kJbCropsPerLaunch) return hipErrorInvalidValue;
+  JbFilter p = q;
+  dim3 grid;
+  const size_t lds = filter_plan(p, table.r, p.base.n_images, filter, &grid, true);
+  if (!lds) return hipErrorInvalidValue;
+#define JB_FILTER_TABLE , JbViewFilterTable
+  if (filter == 1) {
+    JB_FILTER_LAUNCH(1, kViews, p, table)
+  } else {
+    JB_FILTER_LAUNCH(2, kViews, p, table)
   }
 #undef JB_FILTER_TABLE
   return hipGetLastError();
 }
 #undef JB_FILTER_LAUNCH
+#endif  // JB_KERNELS_HOST

@@ -224,22 +224,20 @@ jb_roi stored_rect(const jb_device_batch *b, int orientation, const jb_roi &r) {
 // image's WINDOW (jb_filter_window) in its rectangle's place -- the window's size decides the packing -- and the filtered
 // kernel gets rectangle and window in a table of its own.  The pixel kernel's grid gives every image as many
 // workgroups as the sub-batch's largest rectangle needs; those beyond an image's own count return at once.
-int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn, const jb_geometry &g,
-                      int64_t plane_stride) {
-  if (plan.n_crops != b->n_images) return fail(ctx, JB_ERR_GEOMETRY, "%s: %d rectangles for %d images", fn, plan.n_crops, b->n_images);
+//
+// The first half, shared with "views" (3f): the rectangle shown[i] of every image i -- in ORIENTED coordinates -- into the
+// stream's scratch, sub-batch by sub-batch, under the context's arithmetic and the plan's orientation.  After the pixel
+// (and orient) launches of a sub-batch, tail(i0, m, table, src) makes the launches that read it: images i0 .. i0 + m - 1,
+// image i0 + j's shown[] rectangle as tight rows of table.c[j].w x .h at src + table.c[j].tmp_offset.
+template <class Tail>
+int rects_into_scratch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int orient, const jb_roi *shown, const jb_geometry &g, Tail tail) {
   const int64_t cap = (int64_t)ctx->knobs.resize_tmp_bytes;
-  // "orientation": the plan's rectangles and windows are the oriented frame's (ob: the batch with that frame); the pixel
-  // kernel writes each one's rectangle of the STORED frame, jb_orient_kernel turns it into a second region of the scratch
-  const bool oriented = plan.orient != JB_ORIENT_STORED;
-  const jb_device_batch ob = oriented_batch(b, plan.orient);
-  std::vector<jb_roi> windows;  // what the pixel kernel writes of every image: with a filter, not the rectangle
-  if (plan.filter)
-    for (int64_t i = 0; i < b->n_images; i++)
-      windows.push_back(jb_filter_window_of_(&ob.desc, &plan.crops[i], plan.out_w, plan.out_h, plan.filter));
-  const jb_roi *const shown = plan.filter ? windows.data() : plan.crops;
+  // "orientation": the rectangles are the oriented frame's; the pixel kernel writes each one's rectangle of the STORED
+  // frame, jb_orient_kernel turns it into a second region of the scratch
+  const bool oriented = orient != JB_ORIENT_STORED;
   std::vector<jb_roi> stored;
   if (oriented)
-    for (int64_t i = 0; i < b->n_images; i++) stored.push_back(stored_rect(b, plan.orient, shown[i]));
+    for (int64_t i = 0; i < b->n_images; i++) stored.push_back(stored_rect(b, orient, shown[i]));
   const jb_roi *const written = oriented ? stored.data() : shown;
   const auto image_bytes = [&](int64_t i) { return 3LL * written[i].width * written[i].height; };
   const auto bytes_of = [&](int64_t i) { return image_bytes(i) * (oriented ? 2 : 1); };  // (the cap counts both regions)
@@ -277,14 +275,11 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
     int64_t bytes, planes;
     const int m = pack(i0, &bytes, &planes);
     JbCropTable table;
-    JbFilterTable ftable;
     memset(&table, 0, sizeof table);
-    memset(&ftable, 0, sizeof ftable);
     int32_t most_tiles = 0, most_lj_tiles = 0;
     int64_t at = 0;
     for (int j = 0; j < m; j++) {
       const jb_roi &r = written[i0 + j];
-      if (plan.filter) ftable.r[j] = filter_row(plan.crops[i0 + j], shown[i0 + j], at);
       JbCrop &c = table.c[j];
       c.x = r.x, c.y = r.y, c.w = r.width, c.h = r.height;
       c.mx = r.x / mw, c.my = r.y / mh;
@@ -316,24 +311,113 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
     }
     if (oriented) {
       // every image turned into the second region, at its own offset; `table` then describes the oriented sources as
-      // jb_resample_kernel takes them (of a row it reads w, h and tmp_offset; the pixel launch above has its copy)
+      // the launches of the tail take them (of a row they read w, h and tmp_offset; the pixel launch above has its copy)
       JbOrient q;
       JbOrientTable turn;
       memset(&q, 0, sizeof q);
       memset(&turn, 0, sizeof turn);
       q.src = (const uint8_t *)tmp, q.dst = (uint8_t *)tmp + region;
-      q.orientation = plan.orient, q.n_images = m;
+      q.orientation = orient, q.n_images = m;
       for (int j = 0; j < m; j++) {
         turn.r[j] = JbOrientRow{table.c[j].w, table.c[j].h, table.c[j].tmp_offset, table.c[j].tmp_offset};
         table.c[j].w = shown[i0 + j].width, table.c[j].h = shown[i0 + j].height;
       }
       JB_HIP(ctx, jbk_orient_launch_table(q, turn, s));
     }
-    if (plan.filter) JB_HIP(ctx, jbk_filter_launch_crops(filter_args(&ob, plan, plane_stride, resample_src, i0, m), ftable, plan.filter, plan.format, s));
-    else JB_HIP(ctx, jbk_resample_launch_crops(resample_args(&ob, plan, plane_stride, resample_src, i0, m), table, plan.format, s));
+    rc = tail(i0, m, table, resample_src, s);
+    if (rc) return rc;
     i0 += m;
   }
   return JB_OK;
+}
+
+int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn, const jb_geometry &g,
+                      int64_t plane_stride) {
+  if (plan.n_crops != b->n_images) return fail(ctx, JB_ERR_GEOMETRY, "%s: %d rectangles for %d images", fn, plan.n_crops, b->n_images);
+  // the plan's rectangles and windows are the oriented frame's (ob: the batch with that frame)
+  const jb_device_batch ob = oriented_batch(b, plan.orient);
+  std::vector<jb_roi> windows;  // what the pixel kernel writes of every image: with a filter, not the rectangle
+  if (plan.filter)
+    for (int64_t i = 0; i < b->n_images; i++)
+      windows.push_back(jb_filter_window_of_(&ob.desc, &plan.crops[i], plan.out_w, plan.out_h, plan.filter));
+  const jb_roi *const shown = plan.filter ? windows.data() : plan.crops;
+  return rects_into_scratch(ctx, b, stream, plan.orient, shown, g, [&](int64_t i0, int m, const JbCropTable &table, const void *src, hipStream_t s) {
+    if (plan.filter) {
+      JbFilterTable ftable;
+      memset(&ftable, 0, sizeof ftable);
+      for (int j = 0; j < m; j++) ftable.r[j] = filter_row(plan.crops[i0 + j], shown[i0 + j], table.c[j].tmp_offset);
+      JB_HIP(ctx, jbk_filter_launch_crops(filter_args(&ob, plan, plane_stride, src, i0, m), ftable, plan.filter, plan.format, s));
+    } else {
+      JB_HIP(ctx, jbk_resample_launch_crops(resample_args(&ob, plan, plane_stride, src, i0, m), table, plan.format, s));
+    }
+    return (int)JB_OK;
+  });
+}
+
+// 3f. "views" (plan.views): K outputs per image from ONE pixel launch.  Per image the UNION -- the bounding rectangle of
+// its K rectangles, with a filter of their K windows -- goes through 3c's first half; the view kernels then read K
+// sub-rectangles of each union, kJbCropsPerLaunch outputs a launch, so one pixel launch may be followed by several.
+// (A union may be much larger than its views: accepted, see include/jpegblk.h.)
+int seam_launch_views(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn) {
+  jb_geometry g;
+  int64_t plane_stride = 0;
+  int rc = seam_check(ctx, b, plan, fn, &g, &plane_stride);
+  if (rc) return rc;
+  const int k = plan.views_per_image;
+  if (plan.n_views != (int64_t)b->n_images * k) return fail(ctx, JB_ERR_GEOMETRY, "%s: %d views for %d images", fn, plan.n_views, b->n_images);
+  if (b->n_images == 1 && k > 1) {
+    // one image, several outputs: the strides between OUTPUTS count all the same (seam_check looks at them for a batch)
+    jb_device_batch outputs = *b;
+    outputs.n_images = k;
+    outputs.coef_image_stride = g.coef_bytes;
+    rc = seam_check(ctx, &outputs, plan, fn, &g, &plane_stride);
+    if (rc) return rc;
+  }
+  const jb_device_batch ob = oriented_batch(b, plan.orient);
+  // every image's union of its views' sources -- a view's rectangle, with a filter its window
+  std::vector<jb_roi> unions;
+  for (int64_t i = 0; i < b->n_images; i++) {
+    int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+    for (int v = 0; v < k; v++) {
+      const jb_view &w = plan.views[i * k + v];
+      const jb_roi r = {w.x, w.y, w.width, w.height};
+      const jb_roi src = plan.filter ? jb_filter_window_of_(&ob.desc, &r, plan.out_w, plan.out_h, plan.filter) : r;
+      if (v == 0 || src.x < x0) x0 = src.x;
+      if (v == 0 || src.y < y0) y0 = src.y;
+      if (v == 0 || src.x + src.width > x1) x1 = src.x + src.width;
+      if (v == 0 || src.y + src.height > y1) y1 = src.y + src.height;
+    }
+    unions.push_back(jb_roi{x0, y0, x1 - x0, y1 - y0});
+  }
+  // the outputs are b's "images": one d_rgb index per view
+  jb_device_batch vb = ob;
+  vb.n_images = 2;  // (resample_args: the image stride counts)
+  return rects_into_scratch(ctx, b, stream, plan.orient, unions.data(), g, [&](int64_t i0, int m, const JbCropTable &table, const void *src, hipStream_t s) {
+    const int64_t n_rows = (int64_t)m * k;
+    for (int64_t n0 = 0; n0 < n_rows; n0 += kJbCropsPerLaunch) {
+      const int n = (int)(n_rows - n0 < kJbCropsPerLaunch ? n_rows - n0 : kJbCropsPerLaunch);
+      const int64_t first = i0 * k + n0;  // the launch's first output
+      JbViewTable vt;
+      JbViewFilterTable ft;
+      memset(&vt, 0, sizeof vt);
+      memset(&ft, 0, sizeof ft);
+      for (int t = 0; t < n; t++) {
+        const int j = (int)((n0 + t) / k);  // the image of the sub-batch
+        const jb_view &w = plan.views[first + t];
+        const jb_roi &u = unions[i0 + j];
+        const int mirror = (w.flags & JB_VIEW_MIRROR) ? 1 : 0;
+        if (plan.filter) {
+          ft.r[t] = filter_row(jb_roi{w.x, w.y, w.width, w.height}, u, table.c[j].tmp_offset);
+          ft.mirror |= (uint32_t)mirror << t;
+        } else {
+          vt.r[t] = JbViewRow{table.c[j].tmp_offset, 3 * u.width, w.x - u.x, w.y - u.y, w.width, w.height, mirror};
+        }
+      }
+      if (plan.filter) JB_HIP(ctx, jbk_filter_launch_views(filter_args(&vb, plan, plane_stride, src, first, n), ft, plan.filter, plan.format, s));
+      else JB_HIP(ctx, jbk_resample_launch_views(resample_args(&vb, plan, plane_stride, src, first, n), vt, plan.format, s));
+    }
+    return (int)JB_OK;
+  });
 }
 
 // 3b. a plan with a target size: two launches per sub-batch, in stream order -- the pixel kernel (full size or the
@@ -502,6 +586,7 @@ int seam_launch_lj(jb_ctx *ctx, const jb_device_batch *b, void *stream, const Jb
 
 // 3. the launch, on `stream` or (null) the context's primary stream; fn: the entry point's name, for the error text
 int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn) {
+  if (plan.views && plan.orient != JB_ORIENT_EXIF && ctx && b) return seam_launch_views(ctx, b, stream, plan, fn);
   if (plan.orient != JB_ORIENT_STORED && plan.orient != JB_ORIENT_EXIF && ctx && b) return seam_launch_oriented(ctx, b, stream, plan, fn);
   if (plan.has_resize && ctx && b) return seam_launch_resized(ctx, b, stream, plan, fn);
   jb_geometry g;
@@ -579,6 +664,14 @@ int jb_blocks_to_rgb_device_crops_filtered(jb_ctx *ctx, const jb_device_batch *b
   const JbTarget t = rs ? JbTarget{rs->out_w, rs->out_h, rs->filter, rs->reserved} : JbTarget{};
   return seam_launch(ctx, b, stream, seam_plan(ctx, b, 1, spec, nullptr, &t, rois, b ? b->n_images : 0),
                      "jb_blocks_to_rgb_device_crops_filtered");
+}
+
+int jb_blocks_to_rgb_device_views(jb_ctx *ctx, const jb_device_batch *b, const jb_view *views, int views_per_image, const jb_resize *rs,
+                                  const jb_output_spec *spec, void *stream) {
+  if (ctx && (!views || !rs)) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_views: NULL pointer");
+  if (!ctx || !b) return seam_launch(ctx, b, stream, seam_plan(ctx, b, 1, spec), "jb_blocks_to_rgb_device_views");  // (JB_ERR_NULL)
+  return seam_launch(ctx, b, stream, jb_views_plan_(&b->desc, spec, views, b->n_images < 0 ? 0 : b->n_images, views_per_image, rs, ctx->orientation),
+                     "jb_blocks_to_rgb_device_views");
 }
 
 }  // extern "C"
