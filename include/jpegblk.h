@@ -488,6 +488,59 @@ int jb_views_check(const jb_image_desc *desc, const jb_view *views, int n_images
 int jb_blocks_to_rgb_device_views(jb_ctx *ctx, const jb_device_batch *batch, const jb_view *views, int views_per_image,
                                   const jb_resize *rs, const jb_output_spec *spec, void *stream);
 
+/* ---- fit: aspect-preserving targets -- letterbox (pad) and centred crop (cover) ----
+ * Every route above that gives a batch one output size STRETCHES its source to the target.  A jb_fit next to the
+ * jb_resize says what else to do with a source whose aspect ratio is not the target's.  The SOURCE is the launch's
+ * rectangle, or the whole frame when roi == NULL -- under an orientation the oriented frame's, as for every other option:
+ * sw x sh at (sx, sy).  The target W x H and the filter are the jb_resize's.  A jb_fit_geometry says what happens:
+ * `src` is the rectangle of the frame that is resampled, `inner` the rectangle of the target it lands in.
+ * NULL or JB_FIT_STRETCH: src = source, inner = (0, 0, W, H) -- exactly the code paths and bits of the sections above.
+ * JB_FIT_PAD (letterbox): Pillow's ImageOps.pad, operation for operation on IEEE doubles without contraction.  With
+ * ir = (double)sw / (double)sh and dr = (double)W / (double)H: ir == dr gives the inner size W x H; ir > dr gives dw = W,
+ * dh = rint((double)sh / (double)sw * (double)W); else dh = H, dw = rint((double)sw / (double)sh * (double)H); rint rounds
+ * halves to even (Python's round).  An extent below 1 is raised to 1 (Pillow raises an error there), one above the
+ * target's is cut to it.  Only one axis pads; with d = W - dw (or H - dh) the inner offset on it is rint(d * 0.5) for
+ * JB_FIT_CENTER, 0 for JB_FIT_START, d for JB_FIT_END.  src is the source.  The inner rectangle holds what the ordinary
+ * route gives for the source at the target dw x dh with the same filter (other than JB_FILTER_AREA:
+ * Image.resize((dw, dh), method, box=source)); every other element of the target holds `fill`, converted as the store
+ * stage converts a uint8: the byte itself in formats 0 and 1, (float)fill[c] * scale[c] + bias[c] -- two rounded
+ * operations, and one conversion to binary16 for f16 -- in formats 2 and 3.
+ * JB_FIT_COVER (the evaluation transform's centred crop): integers only, in int64.  sw * H == sh * W: src = source.
+ * sw * H > sh * W: the crop is cw x sh, cw = clamp((2 * sh * W + H) / (2 * H), 1, sw), at x offset (sw - cw) / 2 for
+ * JB_FIT_CENTER, 0 for JB_FIT_START, sw - cw for JB_FIT_END inside the source; else the same with the axes exchanged.
+ * inner = (0, 0, W, H); `fill` is not looked at.  The result is what the ordinary route gives for roi = src.
+ * Refusals, behind every one of the sections above and in this order, with nothing launched or written: an unknown
+ * mode or anchor, reserved8 or reserved not 0 JB_ERR_GEOMETRY; a mode other than JB_FIT_STRETCH without a target size
+ * JB_ERR_STATE; such a mode together with per-image rectangles or views JB_ERR_UNSUPPORTED.  The tap cap and the filter's
+ * source window are those of the pair that is resampled -- src to the inner size -- not of the source against W x H.
+ * Out of scope: a fit per image under per-image rectangles or views, fractional source boxes (ImageOps.fit's own
+ * crop), the inner rectangle of every file of a batch run (ask jb_fit_check with the file's size). */
+enum { JB_FIT_STRETCH = 0, JB_FIT_PAD = 1, JB_FIT_COVER = 2 };
+enum { JB_FIT_CENTER = 0, JB_FIT_START = 1, JB_FIT_END = 2 };
+typedef struct jb_fit {
+  int32_t mode, anchor; /* JB_FIT_* */
+  uint8_t fill[3];      /* JB_FIT_PAD: R, G, B of the border */
+  uint8_t reserved8;    /* 0 */
+  int32_t reserved;     /* 0 */
+} jb_fit;
+typedef struct jb_fit_geometry {
+  jb_roi src;   /* what is resampled, in pixels of the (oriented) frame */
+  jb_roi inner; /* where it lands, in pixels of the target */
+} jb_fit_geometry;
+/* jb_filter_check with a fit (NULL: stretch): JB_ERR_NULL for a null descriptor or jb_resize, the descriptor's own
+ * errors, the rectangle's, the target's and the filter's, then the fit's (above; no target size is rs->out_w =
+ * rs->out_h = 0).  desc is the frame whose coordinates `roi` is in (under an orientation: the oriented frame).  On JB_OK
+ * *out (may be NULL) is the geometry.  Pure host code. */
+int jb_fit_check(const jb_image_desc *desc, const jb_roi *roi, const jb_resize *rs, const jb_fit *fit, jb_fit_geometry *out);
+/* jb_blocks_to_rgb_device_filtered with a fit: d_rgb and its strides describe outputs of out_w x out_h, as there. */
+int jb_blocks_to_rgb_device_fit(jb_ctx *ctx, const jb_device_batch *batch, const jb_roi *roi, const jb_resize *rs, const jb_fit *fit,
+                                const jb_output_spec *spec, void *stream);
+/* jb_decode_memory_filtered / jb_decode_file_filtered with a fit; *width and *height are the target's. */
+int jb_decode_memory_fit(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, const jb_roi *roi, const jb_resize *rs, const jb_fit *fit,
+                         const jb_output_spec *spec, void **out, int32_t *width, int32_t *height);
+int jb_decode_file_fit(jb_ctx *ctx, const char *path, const jb_roi *roi, const jb_resize *rs, const jb_fit *fit,
+                       const jb_output_spec *spec, void **out, int32_t *width, int32_t *height);
+
 /* ---- decoder arithmetic: the reference program's, or libjpeg's bit for bit ----
  * What a full-size decode computes between the coefficients and the uint8 pixels.  JB_ARITH_REFERENCE (the default) is
  * the reference program's: a float AAN IDCT, chroma replicated to the luma grid, float YCbCr -> RGB.  JB_ARITH_LIBJPEG
@@ -793,6 +846,14 @@ int jb_batch_decoder_submit_views(jb_batch_decoder *dec, const char *const *path
  * to both sides of submit / collect.  Refused with JB_ERR_STATE while a batch is in flight, with JB_ERR_GEOMETRY for an
  * unknown filter. */
 int jb_batch_decoder_set_filter(jb_batch_decoder *dec, int filter);
+/* The fit (see "fit"; NULL: stretch again) of the batch decoder's later runs and submissions: what every file does with
+ * the target size of jb_batch_decoder_set_resize.  Like the filter it is kept while no target size is set -- a run of
+ * files with a mode other than JB_FIT_STRETCH and no target size gives every file the status JB_ERR_STATE.  widths /
+ * heights report the target's size; a group is one geometry and so has one inner rectangle.  Applies to every device
+ * of a multi-device decoder and to both sides of submit / collect.  Refused with JB_ERR_STATE while a batch is in
+ * flight, with JB_ERR_GEOMETRY for an unknown mode or anchor or a reserved field that is not 0; while a mode other than
+ * JB_FIT_STRETCH is set, _run_crops / _submit_crops and _run_views / _submit_views are refused with JB_ERR_UNSUPPORTED. */
+int jb_batch_decoder_set_fit(jb_batch_decoder *dec, const jb_fit *fit);
 /* The arithmetic (JB_ARITH_*; see "decoder arithmetic") of the batch decoder's later runs and submissions.  Applies to
  * every device of a multi-device decoder and to both sides of submit / collect.  Refused with JB_ERR_STATE while a batch
  * is in flight, with JB_ERR_GEOMETRY for an unknown value, and JB_ARITH_LIBJPEG while the scale is not 1 (and

@@ -14,7 +14,8 @@ from .api import (JbError, Context, ImageDesc, Geometry, DeviceBatch, lib, lib_p
                   FMT_DTYPE, Roi, roi_check, resize_check, crops_check, Resize, filter_check, filter_window,
                   FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC, ARITH_REFERENCE, ARITH_LIBJPEG,
                   ORIENT_EXIF, ORIENT_STORED, exif_orientation, oriented_size, orient_map_roi,
-                  View, VIEW_MIRROR, VIEWS_MAX, views_check)
+                  View, VIEW_MIRROR, VIEWS_MAX, views_check,
+                  Fit, FitGeometry, fit_geometry, FIT_STRETCH, FIT_PAD, FIT_COVER, FIT_CENTER, FIT_START, FIT_END)
 from .crops import random_resized_crop, random_views
 
 __all__ = ["JbError", "Context", "ImageDesc", "Geometry", "DeviceBatch", "lib", "lib_path",
@@ -23,4 +24,5 @@ __all__ = ["JbError", "Context", "ImageDesc", "Geometry", "DeviceBatch", "lib", 
            "FMT_RGB_F16_CHW", "FMT_DTYPE", "Roi", "roi_check", "resize_check", "crops_check",
            "random_resized_crop", "Resize", "filter_check", "filter_window", "FILTER_AREA", "FILTER_BILINEAR", "FILTER_BICUBIC",
            "ARITH_REFERENCE", "ARITH_LIBJPEG", "ORIENT_EXIF", "ORIENT_STORED", "exif_orientation", "oriented_size",
-           "orient_map_roi", "View", "VIEW_MIRROR", "VIEWS_MAX", "views_check", "random_views"]
+           "orient_map_roi", "View", "VIEW_MIRROR", "VIEWS_MAX", "views_check", "random_views",
+           "Fit", "FitGeometry", "fit_geometry", "FIT_STRETCH", "FIT_PAD", "FIT_COVER", "FIT_CENTER", "FIT_START", "FIT_END"]

@@ -103,6 +103,45 @@ class View(ctypes.Structure):
                 ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+# "fit" (include/jpegblk.h): what a target size does with a source of another aspect ratio -- stretch it (the default), scale
+# it to fit inside and fill the rest (letterbox), or cut the largest centred rectangle of the target's aspect ratio
+FIT_STRETCH, FIT_PAD, FIT_COVER = 0, 1, 2
+FIT_CENTER, FIT_START, FIT_END = 0, 1, 2
+
+
+class Fit(ctypes.Structure):
+    """jb_fit: a mode (FIT_*), an anchor (FIT_CENTER / FIT_START / FIT_END) and, for FIT_PAD, the border's colour."""
+    _fields_ = [("mode", ctypes.c_int32), ("anchor", ctypes.c_int32), ("fill", ctypes.c_uint8 * 3), ("reserved8", ctypes.c_uint8),
+                ("reserved", ctypes.c_int32)]
+
+    @classmethod
+    def pad(cls, fill=(0, 0, 0), anchor=FIT_CENTER):
+        """Letterbox: the source scaled to fit inside the target (Pillow's ImageOps.pad), the rest filled with `fill`."""
+        r, g, b = [int(v) for v in fill]
+        return cls(FIT_PAD, int(anchor), (ctypes.c_uint8 * 3)(r, g, b), 0, 0)
+
+    @classmethod
+    def cover(cls, anchor=FIT_CENTER):
+        """The largest rectangle of the target's aspect ratio, centred (or anchored), resized to the target."""
+        return cls(FIT_COVER, int(anchor), (ctypes.c_uint8 * 3)(0, 0, 0), 0, 0)
+
+
+def _fit_struct(fit):
+    """None / a mode number / a Fit -> a Fit, or None for what asks for nothing new (None, FIT_STRETCH with nothing else set)."""
+    if fit is None:
+        return None
+    if not isinstance(fit, Fit):
+        fit = Fit(int(fit), FIT_CENTER, (ctypes.c_uint8 * 3)(0, 0, 0), 0, 0)
+    if fit.mode == FIT_STRETCH and fit.anchor == 0 and fit.reserved8 == 0 and fit.reserved == 0:
+        return None
+    return fit
+
+
+class FitGeometry(ctypes.Structure):
+    """jb_fit_geometry: what is resampled (src, in the frame) and where it lands (inner, in the target)."""
+    _fields_ = [("src", Roi), ("inner", Roi)]
+
+
 def _ref(struct):
     """byref(struct), or None (a NULL pointer) for None."""
     return ctypes.byref(struct) if struct is not None else None
@@ -148,9 +187,11 @@ class _Request:
     filter (FILTER_*) becomes .filter; FILTER_AREA asks for nothing new, any other filter without a target size is
     JbError(-7).  views (K views per image, [[(x, y, w, h[, mirror]), ...], ...]) become .views (a ctypes array of View or
     None; .n_view_rows images of .views_per_image each): with a scale, roi or crops JbError(-9), without a target size
-    JbError(-7), rows of unequal length JbError(-2)."""
+    JbError(-7), rows of unequal length JbError(-2).  fit (None / a mode number / a Fit) becomes .fit (a Fit, or None for
+    FIT_STRETCH, which asks for nothing new): a mode other than FIT_STRETCH without a target size is JbError(-7), with
+    crops or views JbError(-9), behind every refusal above."""
 
-    def __init__(self, scale=1, fmt=None, roi=None, resize=None, crops=None, filter=FILTER_AREA, views=None):
+    def __init__(self, scale=1, fmt=None, roi=None, resize=None, crops=None, filter=FILTER_AREA, views=None, fit=None):
         self.scale = scale
         self.filter = int(filter)
         if self.filter != FILTER_AREA and resize is None:
@@ -188,11 +229,23 @@ class _Request:
             views = [list(r) for r in views]
             self.views, self.views_per_image = _view_array(views)
             self.n_view_rows = len(views)
+        self.fit = _fit_struct(fit)
+        if self.fit is not None and self.fit.mode != FIT_STRETCH:
+            if resize is None:
+                raise JbError(-7, "a fit other than FIT_STRETCH wants a target size (resize)")
+            if crops is not None or views is not None:
+                raise JbError(-9, "a fit other than FIT_STRETCH cannot be combined with per-image rectangles (crops) or views")
 
     def routed(self):
         """-> (route, the arguments the route's entry points take between their family's own and their outputs).  The
         route names the variant of an entry point that takes this request (_ROUTES has the symbols).  A planar format
         with a scale has none, JbError(-9); format 0 with a scale is the scaled route, which takes no spec."""
+        # (a mode other than FIT_STRETCH, which __init__ has refused together with crops or views and without a target size;
+        # or a Fit that is none -- a bad mode, anchor or reserved field -- which C refuses whatever else the request holds:
+        # crops and views are not passed on, no route takes them next to a fit)
+        if self.fit is not None:
+            rs = ctypes.byref(_resize_struct(self.target, self.filter))
+            return "fit", (_ref(self.roi), rs, ctypes.byref(self.fit), _ref(self.spec))
         if self.views is not None:       # (takes a jb_resize: the filter needs no route of its own)
             rs = ctypes.byref(Resize(self.target[0], self.target[1], self.filter, 0))
             return "views", (self.views, self.views_per_image, rs, _ref(self.spec))
@@ -228,7 +281,9 @@ _ROUTES = {"plain": ("jb_decode_file", "jb_decode_memory", "jb_blocks_to_rgb_dev
            "filtered": ("jb_decode_file_filtered", "jb_decode_memory_filtered", "jb_blocks_to_rgb_device_filtered"),
            "crops_filtered": (None, None, "jb_blocks_to_rgb_device_crops_filtered"),
            # K views per image, each optionally mirrored, any filter
-           "views": (None, None, "jb_blocks_to_rgb_device_views")}
+           "views": (None, None, "jb_blocks_to_rgb_device_views"),
+           # a fit other than FIT_STRETCH: letterbox or centred crop to the target, any filter
+           "fit": ("jb_decode_file_fit", "jb_decode_memory_fit", "jb_blocks_to_rgb_device_fit")}
 
 
 def roi_check(desc, roi):
@@ -283,6 +338,20 @@ def filter_window(desc, resize, filter, roi=None):
     win = Roi()
     _check(lib().jb_filter_window(ctypes.byref(desc), _ref(_Request(roi=roi).roi), ctypes.byref(_resize_struct(resize, filter)), ctypes.byref(win)))
     return win.x, win.y, win.width, win.height
+
+
+def fit_geometry(width, height, resize, fit, roi=None, filter=FILTER_AREA):
+    """jb_fit_check: -> ((sx, sy, sw, sh), (ix, iy, iw, ih)) -- the rectangle of the width x height frame that `fit` (None / a
+    mode number / a Fit) resamples, and the rectangle of the target resize=(w, h) it lands in; roi: the source (None: the
+    whole frame).  What maps a box between a file and its tensor: x_out = ix + (x - sx) * iw / sw.  width, height: of the
+    frame the coordinates are in -- entropy_decode(..., headers_only=True) gives a file's, oriented_size the oriented
+    one's.  Raises JbError as a decode with these arguments would (-2, -7, -9)."""
+    q = _Request(roi=roi)
+    f = _fit_struct(fit)
+    g = FitGeometry()
+    _check(lib().jb_fit_check(ctypes.byref(make_desc(int(width), int(height), 1, 1)), _ref(q.roi), ctypes.byref(_resize_struct(resize, filter)),
+                              _ref(f), ctypes.byref(g)))
+    return (g.src.x, g.src.y, g.src.width, g.src.height), (g.inner.x, g.inner.y, g.inner.width, g.inner.height)
 
 
 def _shape_output(ptr, w, h, spec, k=0):
@@ -430,6 +499,12 @@ def lib():
     L.jb_decode_memory_filtered.argtypes = [vp, vp, ctypes.c_size_t, pr, prs, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.jb_decode_file_filtered.argtypes = [vp, ctypes.c_char_p, pr, prs, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.jb_batch_decoder_set_filter.argtypes = [vp, ctypes.c_int]
+    pf = ctypes.POINTER(Fit)
+    L.jb_fit_check.argtypes = [pd, pr, prs, pf, ctypes.POINTER(FitGeometry)]
+    L.jb_blocks_to_rgb_device_fit.argtypes = [vp, ctypes.POINTER(DeviceBatch), pr, prs, pf, ps, vp]
+    L.jb_decode_memory_fit.argtypes = [vp, vp, ctypes.c_size_t, pr, prs, pf, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.jb_decode_file_fit.argtypes = [vp, ctypes.c_char_p, pr, prs, pf, ps, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.jb_batch_decoder_set_fit.argtypes = [vp, pf]
     L.jb_batch_decoder_set_arithmetic.argtypes = [vp, ctypes.c_int]
     L.jb_ctx_set_arithmetic.argtypes = [vp, ctypes.c_int]
     L.jb_ctx_arithmetic.argtypes = [vp]
@@ -691,7 +766,8 @@ class Context:
         _check(lib().jb_wait(self._h, ticket), self._h)
 
     # -- the seam, device buffers ------------------------------------------------------------
-    def blocks_to_rgb_device(self, batch, stream=None, scale=1, fmt=None, roi=None, resize=None, crops=None, filter=FILTER_AREA, views=None):
+    def blocks_to_rgb_device(self, batch, stream=None, scale=1, fmt=None, roi=None, resize=None, crops=None, filter=FILTER_AREA, views=None,
+                             fit=None):
         """scale 2, 4, 8: the batch's d_rgb and strides describe images of scaled_size(desc.width, desc.height, scale).
         fmt (an OutputSpec or a format number): planar output -- the batch's rgb_row_stride is then a plane's.
         roi=(x, y, w, h) (with any fmt, not with a scale): the batch's d_rgb and strides describe images of w x h, the
@@ -706,8 +782,11 @@ class Context:
         rectangles per image, each resized to w x h and then mirrored left-right when its fifth field is true, from ONE
         pixel launch per image (jb_blocks_to_rgb_device_views).  batch.d_rgb and its strides describe n_images * K
         outputs; output i * K + v is view v of image i.
+        fit=Fit.pad(fill, anchor) / Fit.cover(anchor) / a mode number with resize=(w, h) (any fmt, roi and filter; not with crops
+        or views): the source keeps its aspect ratio -- scaled to fit inside the target with the rest filled, or the largest
+        centred rectangle of the target's aspect ratio resized (jb_blocks_to_rgb_device_fit).  None / FIT_STRETCH: as before.
         Each is the entry point of that suffix (_ROUTES)."""
-        request = _Request(scale, fmt, roi, resize, crops, filter, views)
+        request = _Request(scale, fmt, roi, resize, crops, filter, views, fit)
         if request.crops is not None and request.n_crops != batch.n_images:
             raise JbError(-2, f"{request.n_crops} rectangles (crops) for {batch.n_images} images")
         if request.views is not None and request.n_view_rows != batch.n_images:
@@ -727,20 +806,21 @@ class Context:
         finally:
             lib().jb_free(p)
 
-    def decode_file(self, path, scale=1, fmt=None, roi=None, resize=None, filter=FILTER_AREA):
+    def decode_file(self, path, scale=1, fmt=None, roi=None, resize=None, filter=FILTER_AREA, fit=None):
         """-> RGB [H, W, 3]; scale 2, 4, 8: the area-reduced image; fmt (OutputSpec or format number): [3, H, W] in the
         format's type for the planar formats; roi=(x, y, w, h) (with any fmt, not with a scale): that rectangle of the
         image; resize=(w, h) (with any fmt, with or without roi, not with a scale): the image, or its rectangle, at w x h;
-        filter (with resize): FILTER_AREA, or FILTER_BILINEAR / FILTER_BICUBIC for Pillow's 8-bit resampling.
+        filter (with resize): FILTER_AREA, or FILTER_BILINEAR / FILTER_BICUBIC for Pillow's 8-bit resampling;
+        fit (with resize): Fit.pad(...) / Fit.cover(...) keep the aspect ratio, the output is still w x h.
         Each is jb_decode_file's variant of that suffix (_ROUTES)."""
-        request = _Request(scale, fmt, roi, resize, filter=filter)
+        request = _Request(scale, fmt, roi, resize, filter=filter, fit=fit)
         return self._decode(_FILE, (os.fsencode(path),), request)
 
-    def decode_memory(self, jpeg_bytes, scale=1, fmt=None, roi=None, resize=None, filter=FILTER_AREA):
+    def decode_memory(self, jpeg_bytes, scale=1, fmt=None, roi=None, resize=None, filter=FILTER_AREA, fit=None):
         """jb_decode_memory: a JFIF byte string -> RGB [H, W, 3] (front end + device seam); scale, fmt, roi, resize,
-        filter: as decode_file."""
+        filter, fit: as decode_file."""
         buf = np.frombuffer(jpeg_bytes, dtype=np.uint8)
-        return self._decode(_MEMORY, (_ptr(buf), buf.size), _Request(scale, fmt, roi, resize, filter=filter))
+        return self._decode(_MEMORY, (_ptr(buf), buf.size), _Request(scale, fmt, roi, resize, filter=filter, fit=fit))
 
 
 def _batch_args(paths):
@@ -795,11 +875,13 @@ class BatchDecoder:
     size and for the per-image rectangles of run(crops=) alike.  arithmetic (jb_batch_decoder_set_arithmetic):
     ARITH_LIBJPEG decodes every file as libjpeg does, bit for bit (not with a scale).  orientation
     (jb_batch_decoder_set_orientation): ORIENT_EXIF applies every file's own Exif tag, 2..8 that code to every file, in
-    front of every other option: sizes, roi and crops are then the oriented image's (not with a scale)."""
+    front of every other option: sizes, roi and crops are then the oriented image's (not with a scale).  fit
+    (jb_batch_decoder_set_fit; with resize): Fit.pad(...) letterboxes every file into the target, Fit.cover(...) cuts the
+    largest centred rectangle of the target's aspect ratio; not with run(crops=) or run(views=)."""
 
     def __init__(self, n_threads=8, device=0, max_coef_bytes=0, max_rgb_bytes=0, arena_bytes=0, devices=None, scale=1, fmt=None,
-                 roi=None, resize=None, filter=FILTER_AREA, arithmetic=ARITH_REFERENCE, orientation=ORIENT_STORED):
-        _Request(scale, fmt, roi, resize, filter=filter)   # (roi or resize with a scale: JbError(-9) before anything is created)
+                 roi=None, resize=None, filter=FILTER_AREA, arithmetic=ARITH_REFERENCE, orientation=ORIENT_STORED, fit=None):
+        _Request(scale, fmt, roi, resize, filter=filter, fit=fit)   # (roi or resize with a scale: JbError(-9) before anything is created)
         self._h = ctypes.c_void_p()
         if devices is not None:
             ids = (ctypes.c_int * len(devices))(*devices)
@@ -829,6 +911,8 @@ class BatchDecoder:
                 self.set_arithmetic(arithmetic)
             if orientation != ORIENT_STORED:
                 self.set_orientation(orientation)
+            if fit is not None:
+                self.set_fit(fit)
         except JbError:
             self.close()
             raise
@@ -863,6 +947,15 @@ class BatchDecoder:
         and for per-image rectangles alike; kept, and idle, while no target size is set (JbError -7 while a batch is in
         flight, -2 for an unknown filter)."""
         _check(lib().jb_batch_decoder_set_filter(self._h, int(filter)))
+
+    def set_fit(self, fit):
+        """jb_batch_decoder_set_fit: the fit (None / a mode number / a Fit) of later runs and submissions, for the target
+        size; None or FIT_STRETCH: stretch again.  Kept while no target size is set: the files of such a run get status
+        -7 (JbError -7 while a batch is in flight, -2 for an unknown mode or anchor).  While a mode other than FIT_STRETCH
+        is set, run(crops=) and run(views=) are refused with -9."""
+        if fit is not None and not isinstance(fit, Fit):
+            fit = Fit(int(fit), FIT_CENTER, (ctypes.c_uint8 * 3)(0, 0, 0), 0, 0)
+        _check(lib().jb_batch_decoder_set_fit(self._h, _ref(fit)))
 
     def set_arithmetic(self, arithmetic):
         """jb_batch_decoder_set_arithmetic: ARITH_REFERENCE or ARITH_LIBJPEG for later runs and submissions (JbError -7
@@ -1054,7 +1147,7 @@ def decode_batch(paths, n_threads=8, device=0, keep_pixels=True, on_image=None, 
 
 
 def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, shared_qtabs=True, scale=1, fmt=None, roi=None,
-                resize=None, filter=FILTER_AREA):
+                resize=None, filter=FILTER_AREA, fit=None):
     """DeviceBatch over torch CUDA tensors (plumbing): coef_t int16 [n_images, n_blocks, 64],
     qtabs_t int32 [3,64] (shared) or [n_images,3,64], rgb_t uint8 [n_images, H, row_stride].
     scale 2, 4, 8: rgb_t holds the reduced images, [n_images, ceil(H/scale), row_stride], for
@@ -1065,8 +1158,8 @@ def torch_batch(desc, n_images, coef_t, qtabs_t, rgb_t, rgb_row_stride=None, sha
     roi=(x, y, w, h) (for Context.blocks_to_rgb_device(..., roi=), with any fmt, not with a scale): rgb_t holds images of
     the rectangle's size, w x h, instead of desc's.
     resize=(w, h) (for Context.blocks_to_rgb_device(..., resize=), with any fmt and roi, not with a scale): rgb_t holds
-    images of w x h; filter (for Context.blocks_to_rgb_device(..., filter=)) changes no size."""
-    q = _Request(scale, fmt, roi, resize, filter=filter)
+    images of w x h; filter and fit (for Context.blocks_to_rgb_device(..., filter=, fit=)) change no size."""
+    q = _Request(scale, fmt, roi, resize, filter=filter, fit=fit)
     out_w, out_h = q.target if q.target is not None else (q.roi.width, q.roi.height) if q.roi is not None else (desc.width, desc.height)
     if q.spec is not None and q.spec.format != FMT_RGB_U8_HWC:
         assert scale == 1, "an output format cannot be combined with a scale"

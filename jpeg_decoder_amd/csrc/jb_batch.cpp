@@ -44,6 +44,8 @@ struct OutputRequest {
   const JbTarget *target_ptr() const { return has_resize ? &target : nullptr; }
   int arith = JB_ARITH_REFERENCE;  // "decoder arithmetic": what the decoder's contexts compute in (never LIBJPEG with a scale)
   int orient = JB_ORIENT_STORED;   // "orientation": JB_ORIENT_* or 2..8 (never another value than 1 with a scale)
+  jb_fit fit = {};                 // "fit": a valid one; JB_FIT_STRETCH: none.  Kept, like the filter, while no target size is set
+  const jb_fit *fit_ptr() const { return fit.mode != JB_FIT_STRETCH ? &fit : nullptr; }
   // can it be had at all?  The plan function decides (jb_plan.h), here for an image of one pixel -- with a rectangle,
   // for the largest frame there is (JB_ERR_GEOMETRY: no frame holds the rectangle)
   int status() const {
@@ -264,7 +266,7 @@ void parse_one(Parsed &p, const OutputRequest &out, const jb_roi *crop = nullptr
     const jb_resize rs = {out.target.w, out.target.h, out.target.filter, out.target.reserved};
     p.plan = jb_views_plan_(&p.desc, &out.spec, views, 1, k, &rs, orient);
   } else {
-    p.plan = jb_out_plan_(&p.desc, out.scale, &out.spec, crop ? crop : out.roi_ptr(), out.target_ptr(), nullptr, 0, orient);
+    p.plan = jb_out_plan_(&p.desc, out.scale, &out.spec, crop ? crop : out.roi_ptr(), out.target_ptr(), nullptr, 0, orient, out.fit_ptr());
   }
   p.status = p.plan.status;
   if (p.status == JB_OK) p.geo.rgb_bytes = p.plan.image_bytes;
@@ -1284,7 +1286,7 @@ namespace {
 int crops_state(const jb_batch_decoder *d, const char *fn) {
   static const jb_roi one = {0, 0, 1, 1};
   const jb_image_desc frame = {65535, 65535, 1, 1, {0, 0, 0}, 0};
-  const JbOutPlan plan = jb_out_plan_(&frame, d->out.scale, &d->out.spec, d->out.roi_ptr(), d->out.target_ptr(), &one, 1);
+  const JbOutPlan plan = jb_out_plan_(&frame, d->out.scale, &d->out.spec, d->out.roi_ptr(), d->out.target_ptr(), &one, 1, 1, d->out.fit_ptr());
   if (plan.status == JB_OK) return JB_OK;
   return jb_fail_(nullptr, plan.status, (std::string(fn) + ": " + plan.why).c_str());
 }
@@ -1296,6 +1298,7 @@ int views_state(const jb_batch_decoder *d, int k, const char *fn) {
   if (d->out.has_roi) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, (name + ": views cannot be combined with a rectangle for every image").c_str());
   if (!d->out.has_resize) return jb_fail_(nullptr, JB_ERR_STATE, (name + ": views want a target size").c_str());
   if (k < 1 || k > JB_VIEWS_MAX) return jb_fail_(nullptr, JB_ERR_GEOMETRY, (name + ": views_per_image is outside 1..16").c_str());
+  if (d->out.fit_ptr()) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, (name + ": a fit other than JB_FIT_STRETCH is set: views cannot be combined with it").c_str());
   return JB_OK;
 }
 
@@ -1517,6 +1520,20 @@ extern "C" int jb_batch_decoder_set_filter(jb_batch_decoder *d, int filter) {
     return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_set_filter: unknown resampling filter");
   OutputRequest out = d->out;
   out.target.filter = filter;
+  set_output_all(d, out);
+  return JB_OK;
+}
+
+extern "C" int jb_batch_decoder_set_fit(jb_batch_decoder *d, const jb_fit *fit) {
+  if (!d) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_set_fit: decoder is NULL");
+  if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_fit: batches are in flight (collect them first)");
+  // the plan function decides what a fit is: here with a target of one pixel
+  const jb_image_desc one = {1, 1, 1, 1, {0, 0, 0}, 0};
+  const JbTarget probe = {1, 1, 0, 0};
+  if (jb_out_plan_(&one, 1, nullptr, nullptr, &probe, nullptr, 0, 1, fit).status != JB_OK)
+    return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_set_fit: unknown mode or anchor (or a reserved field is not 0)");
+  OutputRequest out = d->out;
+  out.fit = fit ? *fit : jb_fit{};
   set_output_all(d, out);
   return JB_OK;
 }

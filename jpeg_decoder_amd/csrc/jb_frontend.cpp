@@ -426,7 +426,7 @@ int jb_entropy_decode_mt(const uint8_t *jpeg, size_t jpeg_bytes, jb_image_desc *
 // output's size (denom 1).  The output's sizes come from the plan of the frame (jb_plan.h).
 static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, int denom, const jb_output_spec *spec,
                               uint8_t **rgb, int32_t *width, int32_t *height, const jb_roi *roi = nullptr,
-                              const JbTarget *target = nullptr) {
+                              const JbTarget *target = nullptr, const jb_fit *fit = nullptr) {
   if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_memory: ctx is NULL");
   if (!jpeg || !rgb || !width || !height) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_memory: NULL pointer");
   *rgb = nullptr;
@@ -459,7 +459,7 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
       if (jb_huff_prepare_(jpeg, jpeg_bytes, job.get(), nullptr, knobs.chunk_bytes) == JB_OK && jb_huff_worth_it_(*job, min_int) &&
           (forced || job->scan_len >= kAutoDeviceScan)) {
         const double t1 = timing ? jb_now_s_() : 0;
-        const JbOutPlan plan = jb_out_plan_(&job->desc, denom, spec, roi, target, nullptr, 0, orient);
+        const JbOutPlan plan = jb_out_plan_(&job->desc, denom, spec, roi, target, nullptr, 0, orient, fit);
         if (plan.status != JB_OK) return jb_fail_(ctx, plan.status, plan.why);
         uint8_t *out = jb_alloc_pixels_((size_t)plan.image_bytes);
         if (!out) return jb_fail_(ctx, JB_ERR_CAPACITY, "out of host memory");
@@ -486,7 +486,7 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
   jb_geometry g;
   rc = jb_geometry_of(&desc, &g);
   if (rc) return jb_fail_(ctx, rc, "bad frame geometry");
-  const JbOutPlan plan = jb_out_plan_(&desc, denom, spec, roi, target, nullptr, 0, orient);
+  const JbOutPlan plan = jb_out_plan_(&desc, denom, spec, roi, target, nullptr, 0, orient, fit);
   if (plan.status != JB_OK) return jb_fail_(ctx, plan.status, plan.why);
   // the staging ring follows the frame (a context sized for another image, or created with (0,0))
   rc = jb_ctx_reserve(ctx, (size_t)g.coef_bytes, (size_t)plan.image_bytes);
@@ -571,6 +571,18 @@ int jb_decode_memory_filtered(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
   return decode_memory_impl(ctx, jpeg, jpeg_bytes, 1, spec, (uint8_t **)out, width, height, roi, &t);
 }
 
+// the same with a fit ("fit", include/jpegblk.h)
+int jb_decode_memory_fit(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes, const jb_roi *roi, const jb_resize *rs, const jb_fit *fit,
+                         const jb_output_spec *spec, void **out, int32_t *width, int32_t *height) {
+  if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, "jb_decode_memory_fit: ctx is NULL");
+  if (!out || !rs) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_memory_fit: NULL pointer");
+  *out = nullptr;
+  if (spec && jb_tight_spec_check_(spec) != JB_OK)
+    return jb_fail_(ctx, JB_ERR_GEOMETRY, "jb_decode_memory_fit" JB_TIGHT_SPEC_TEXT);
+  const JbTarget t = {rs->out_w, rs->out_h, rs->filter, rs->reserved};
+  return decode_memory_impl(ctx, jpeg, jpeg_bytes, 1, spec, (uint8_t **)out, width, height, roi, &t, fit);
+}
+
 // the file's bytes; fn: the entry point's name, for the error text
 static int read_file(jb_ctx *ctx, const char *fn, const char *path, std::vector<uint8_t> &buf) {
   if (!ctx) return jb_fail_(nullptr, JB_ERR_NULL, (std::string(fn) + ": ctx is NULL").c_str());
@@ -622,6 +634,15 @@ int jb_decode_file_filtered(jb_ctx *ctx, const char *path, const jb_roi *roi, co
   std::vector<uint8_t> buf;
   const int rc = read_file(ctx, "jb_decode_file_filtered", path, buf);
   return rc ? rc : jb_decode_memory_filtered(ctx, buf.data(), buf.size(), roi, rs, spec, out, width, height);
+}
+
+int jb_decode_file_fit(jb_ctx *ctx, const char *path, const jb_roi *roi, const jb_resize *rs, const jb_fit *fit, const jb_output_spec *spec,
+                       void **out, int32_t *width, int32_t *height) {
+  if (ctx && (!out || !rs)) return jb_fail_(ctx, JB_ERR_NULL, "jb_decode_file_fit: NULL pointer");
+  if (ctx) *out = nullptr;
+  std::vector<uint8_t> buf;
+  const int rc = read_file(ctx, "jb_decode_file_fit", path, buf);
+  return rc ? rc : jb_decode_memory_fit(ctx, buf.data(), buf.size(), roi, rs, fit, spec, out, width, height);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // jb_geometry.cpp -- the host-only arithmetic of the ABI (include/jpegblk.h): frame geometry and
 // quantisation-table resolution.  No HIP dependency, so the front end can be built and fuzzed on
 // a CPU-only toolchain with sanitizers (tools/fuzz/).
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -145,6 +146,22 @@ int jb_filter_window(const jb_image_desc *d, const jb_roi *roi, const jb_resize 
   return JB_OK;
 }
 
+int jb_fit_check(const jb_image_desc *d, const jb_roi *roi, const jb_resize *rs, const jb_fit *fit, jb_fit_geometry *out) {
+  if (!d || !rs) return JB_ERR_NULL;
+  jb_geometry g;
+  const int rc = jb_geometry_of(d, &g);
+  if (rc != JB_OK) return rc;
+  const JbTarget t = {rs->out_w, rs->out_h, rs->filter, rs->reserved};
+  const JbOutPlan plan = jb_out_plan_(d, 1, nullptr, roi, &t, nullptr, 0, 1, fit);  // the rectangle, the target, the filter, then the fit
+  if (plan.status != JB_OK) return plan.status;
+  if (out) {
+    const jb_roi whole = {0, 0, d->width, d->height};
+    out->src = plan.has_roi ? plan.roi : whole;
+    out->inner = plan.inner;
+  }
+  return JB_OK;
+}
+
 int jb_oriented_size(int32_t w, int32_t h, int o, int32_t *ow, int32_t *oh) {
   if (!ow || !oh) return JB_ERR_NULL;
   if (w < 1 || h < 1 || w > 65535 || h > 65535 || o < 1 || o > 8) return JB_ERR_GEOMETRY;
@@ -194,6 +211,41 @@ jb_roi jb_filter_window_of_(const jb_image_desc *d, const jb_roi *roi, int32_t o
   jb_filter_span(jb_filter_axis(filter, d->width, r.x, r.x + r.width, out_w), out_w, &x0, &x1);
   jb_filter_span(jb_filter_axis(filter, d->height, r.y, r.y + r.height, out_h), out_h, &y0, &y1);
   return jb_roi{x0, y0, x1 - x0, y1 - y0};
+}
+
+// "fit" (include/jpegblk.h): PAD is Pillow's ImageOps.pad / contain on doubles, operation for operation (the build keeps
+// every operation separate: -ffp-contract=off; rint rounds halves to even, as Python's round); COVER is integers only
+jb_fit_geometry jb_fit_geometry_of_(const jb_roi &s, int32_t w, int32_t h, const jb_fit *fit) {
+  jb_fit_geometry g = {s, jb_roi{0, 0, w, h}};
+  const int mode = fit ? fit->mode : JB_FIT_STRETCH, anchor = fit ? fit->anchor : JB_FIT_CENTER;
+  const auto offset = [anchor](int64_t d, bool halves_even) -> int32_t {
+    if (anchor == JB_FIT_START) return 0;
+    if (anchor == JB_FIT_END) return (int32_t)d;
+    return halves_even ? (int32_t)std::rint((double)d * 0.5) : (int32_t)(d / 2);
+  };
+  const auto clamp = [](int64_t v, int64_t hi) { return (int32_t)(v < 1 ? 1 : v > hi ? hi : v); };
+  if (mode == JB_FIT_PAD) {
+    const double sw = (double)s.width, sh = (double)s.height;
+    const double ir = sw / sh, dr = (double)w / (double)h;
+    if (ir == dr) return g;
+    if (ir > dr) {
+      const int32_t dh = clamp((int64_t)std::rint(sh / sw * (double)w), h);
+      g.inner = jb_roi{0, offset(h - dh, true), w, dh};
+    } else {
+      const int32_t dw = clamp((int64_t)std::rint(sw / sh * (double)h), w);
+      g.inner = jb_roi{offset(w - dw, true), 0, dw, h};
+    }
+  } else if (mode == JB_FIT_COVER) {
+    const int64_t sw = s.width, sh = s.height, a = sw * h, b = sh * w;
+    if (a > b) {
+      const int32_t cw = clamp((2 * sh * w + h) / (2 * (int64_t)h), sw);
+      g.src = jb_roi{s.x + offset(sw - cw, false), s.y, cw, s.height};
+    } else if (a < b) {
+      const int32_t ch = clamp((2 * sw * h + w) / (2 * (int64_t)w), sh);
+      g.src = jb_roi{s.x, s.y + offset(sh - ch, false), s.width, ch};
+    }
+  }
+  return g;
 }
 
 JbOutPlan jb_views_plan_(const jb_image_desc *d, const jb_output_spec *spec, const jb_view *views, int n_images, int k, const jb_resize *rs,
@@ -250,7 +302,7 @@ JbOutPlan jb_views_plan_(const jb_image_desc *d, const jb_output_spec *spec, con
 
 // jb_plan.h: the only place that turns (frame, scale, spec, rectangle, target) into the output's sizes and strides
 JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *spec, const jb_roi *roi, const JbTarget *target,
-                       const jb_roi *crops, int n_crops, int orientation) {
+                       const jb_roi *crops, int n_crops, int orientation, const jb_fit *fit) {
   JbOutPlan p;
   memset(&p, 0, sizeof p);
   p.bad_crop = -1;
@@ -260,6 +312,11 @@ JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *
     return p;
   };
   if (!d) return refuse(JB_ERR_NULL, "null descriptor");
+  // "fit": a fit that is none is refused behind everything else, and is a stretch until then
+  const bool fit_bad = fit && (fit->mode < JB_FIT_STRETCH || fit->mode > JB_FIT_COVER || fit->anchor < JB_FIT_CENTER || fit->anchor > JB_FIT_END ||
+                               fit->reserved8 != 0 || fit->reserved != 0);
+  const int fit_mode = fit && !fit_bad ? fit->mode : JB_FIT_STRETCH;
+  jb_roi inner = {0, 0, 0, 0}, cover = {0, 0, 0, 0};
   int32_t out_w = 0, out_h = 0;
   if (jb_scaled_size(d->width, d->height, scale, &out_w, &out_h) != JB_OK)
     return refuse(JB_ERR_GEOMETRY, "scale is not 1, 2, 4 or 8 (or the image size is outside 1..65535)");
@@ -315,13 +372,28 @@ JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *
       p.has_roi = false, p.roi = jb_roi{};
       return refuse(status, why);
     };
-    const bool no_target = target->w == 0 && target->h == 0 && target->filter != 0;  // "a filter and no target size"
+    // "a filter and no target size", "a fit and no target size"
+    const bool no_target = target->w == 0 && target->h == 0 && (target->filter != 0 || fit_mode != JB_FIT_STRETCH);
     if (!no_target && (target->w < 1 || target->h < 1 || target->w > 65535 || target->h > 65535))
       return refuse_target(JB_ERR_GEOMETRY, "the target size is outside 1..65535");
     if (scale != 1) return refuse_target(JB_ERR_UNSUPPORTED, "a target size cannot be combined with a scale");
     if (target->filter < JB_FILTER_AREA || target->filter > JB_FILTER_BICUBIC || target->reserved != 0)
       return refuse_target(JB_ERR_GEOMETRY, "unknown resampling filter (or reserved is not 0)");
-    if (no_target) return refuse_target(JB_ERR_STATE, "a resampling filter wants a target size");
+    if (no_target)
+      return refuse_target(JB_ERR_STATE, target->filter != 0 ? "a resampling filter wants a target size" : "a fit other than JB_FIT_STRETCH wants a target size");
+    // "fit": what is resampled is src -> the inner size (with per-image rectangles the fit is refused below)
+    inner = jb_roi{0, 0, target->w, target->h};
+    if (fit_mode != JB_FIT_STRETCH && !crops) {
+      const jb_roi whole = {0, 0, d->width, d->height};
+      const jb_fit_geometry fg = jb_fit_geometry_of_(roi ? *roi : whole, target->w, target->h, fit);
+      inner = fg.inner;
+      if (fit_mode == JB_FIT_COVER) {  // an ordinary plan of the derived rectangle
+        cover = fg.src;
+        roi = &cover;
+        p.has_roi = true, p.roi = cover;
+        out_w = cover.width, out_h = cover.height;
+      }
+    }
     if (target->filter != JB_FILTER_AREA) {
       // the taps of both axes against the kernel's cap, for the one rectangle or for every image's
       const jb_roi whole = {0, 0, d->width, d->height};
@@ -329,12 +401,12 @@ JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *
       const int n_rects = crops ? n_crops : 1;
       for (int i = 0; i < n_rects; i++) {
         const jb_roi &r = rects[i];
-        const int tx = jb_filter_taps(jb_filter_axis(target->filter, d->width, r.x, r.x + r.width, target->w));
-        const int ty = jb_filter_taps(jb_filter_axis(target->filter, d->height, r.y, r.y + r.height, target->h));
+        const int tx = jb_filter_taps(jb_filter_axis(target->filter, d->width, r.x, r.x + r.width, inner.width));
+        const int ty = jb_filter_taps(jb_filter_axis(target->filter, d->height, r.y, r.y + r.height, inner.height));
         if (tx > kJbFilterMaxTaps || ty > kJbFilterMaxTaps) {
           static thread_local char text[192];
           snprintf(text, sizeof text, "the reduction of the %d x %d rectangle to %d x %d wants %d x %d filter taps: more than the cap of %d per axis",
-                   r.width, r.height, target->w, target->h, tx, ty, kJbFilterMaxTaps);
+                   r.width, r.height, inner.width, inner.height, tx, ty, kJbFilterMaxTaps);
           if (crops) p.bad_crop = i;
           return refuse_target(JB_ERR_UNSUPPORTED, text);
         }
@@ -344,13 +416,24 @@ JbOutPlan jb_out_plan_(const jb_image_desc *d, int scale, const jb_output_spec *
     p.has_resize = true;
     if (crops) p.crops = crops, p.n_crops = n_crops;
     if (p.filter != JB_FILTER_AREA && !crops) {
-      p.window = jb_filter_window_of_(d, roi, target->w, target->h, p.filter);
+      p.window = jb_filter_window_of_(d, roi, inner.width, inner.height, p.filter);
       out_w = p.window.width, out_h = p.window.height;
     }
     p.src_w = out_w, p.src_h = out_h;
     p.tmp_image_bytes = 3LL * out_w * out_h;
     out_w = target->w, out_h = target->h;
   }
+  if (fit_bad || (fit_mode != JB_FIT_STRETCH && (!target || crops))) {
+    memset(&p, 0, sizeof p);
+    p.bad_crop = -1;
+    p.orient = 1;
+    if (fit_bad) return refuse(JB_ERR_GEOMETRY, "fit: unknown mode or anchor (or a reserved field is not 0)");
+    if (!target) return refuse(JB_ERR_STATE, "a fit other than JB_FIT_STRETCH wants a target size");
+    return refuse(JB_ERR_UNSUPPORTED, "a fit other than JB_FIT_STRETCH cannot be combined with per-image rectangles or views");
+  }
+  p.fit_mode = fit_mode;
+  p.inner = target ? inner : jb_roi{0, 0, out_w, out_h};
+  if (fit_mode == JB_FIT_PAD) memcpy(p.fill, fit->fill, 3);
   p.why = "";
   p.orient = orientation;
   p.scale = scale;

@@ -177,6 +177,24 @@ struct JbViewFilterTable {
 };
 hipError_t jbk_filter_launch_views(const JbFilter &p, const JbViewFilterTable &table, int filter, int format, hipStream_t stream);
 
+// "Fit" (jb_fit.hip jb_fit_fill_kernel): the border of n_images letterboxed outputs of ow x oh at dst, addressed as
+// JbResample addresses them (rows dst_row_stride bytes apart -- of a plane when planar --, planes dst_plane_stride, images
+// dst_image_stride).  A band is the rectangle bw x bh at (bx, by) of every output, in elements; bw or bh = 0: no such band.
+// Every element of a band gets fill[c] in `format` (scale / bias: the float formats' affine map); nothing else is written.
+struct JbFitFill {
+  uint8_t *dst;
+  int64_t dst_image_stride, dst_row_stride, dst_plane_stride;
+  int32_t ow, oh;  // each in 1..65535: what the bands must lie in
+  int32_t n_images;
+  int32_t bx[2], by[2], bw[2], bh[2];
+  int32_t wgs[2];  // (set by the launch: workgroups per band and image)
+  float scale[3], bias[3];
+  uint8_t fill[3];
+};
+// one workgroup per 256 elements of a band of one image; no band at all: nothing is launched.  More than 2^31 - 1
+// workgroups, or an argument outside its range (a band that leaves the output): hipErrorInvalidValue.
+hipError_t jbk_fit_fill_launch(const JbFitFill &p, int format, hipStream_t stream);
+
 // "Orientation" (jb_orient.hip; the arguments are described in jb_orient.h).  One 256-lane workgroup per 64 x 64 tile of
 // source pixels.  More than 2^31 - 1 workgroups, or an argument outside its range: hipErrorInvalidValue.
 hipError_t jbk_orient_launch(const JbOrient &p, int format, hipStream_t stream);

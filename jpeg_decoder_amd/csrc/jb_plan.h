@@ -14,7 +14,10 @@ struct JbOutPlan {
   // that does not lie in the image (bad_crop: its index) in the single rectangle's place, and JB_ERR_STATE for what is
   // no composition: no target size, or a launch-wide rectangle as well.  Behind all of these, "resampling filters":
   // JB_ERR_GEOMETRY (an unknown filter, or the target's reserved != 0), JB_ERR_STATE (a filter other than 0 without a
-  // target size), JB_ERR_UNSUPPORTED (more than kJbFilterMaxTaps taps on an axis; bad_crop with per-image rectangles).  Whoever uses a plan reports it where the old code checked the
+  // target size), JB_ERR_UNSUPPORTED (more than kJbFilterMaxTaps taps on an axis; bad_crop with per-image rectangles).
+  // Behind all of these, "fit": JB_ERR_GEOMETRY (an unknown mode or anchor, a reserved field not 0), JB_ERR_STATE (a mode other than
+  // JB_FIT_STRETCH without a target size), JB_ERR_UNSUPPORTED (such a mode with per-image rectangles); under such a mode the tap cap
+  // above is that of src -> the inner size.  Whoever uses a plan reports it where the old code checked the
   // scale: behind the descriptor's own errors.  `why` is the text for jb_last_error (of the last plan this thread made,
   // when it names sizes); the other fields are 0 on failure (orient: 1).
   int status;
@@ -62,6 +65,16 @@ struct JbOutPlan {
   // coordinates, of the frame with width and height swapped for 5..8.  1: none.  0 (JB_ORIENT_EXIF, which only a file
   // resolves): a plan of the stored frame that no launch takes (JB_ERR_STATE where the launch is asked for).
   int32_t orient;
+  // "fit" (include/jpegblk.h): out_w, out_h, row_stride and image_bytes are the TARGET's whatever the mode -- buffers,
+  // arena, ring slots and copies are sized from them -- and `inner` is the rectangle of the target that the resample or
+  // filter kernel produces: what a launch reads as "the size the kernel writes" is inner.width x inner.height, at
+  // (inner.x, inner.y) of every output.  Without a target size, and for every mode but JB_FIT_PAD, (0, 0, out_w, out_h).
+  // JB_FIT_PAD: the filter's taps, `window`, src_w, src_h and tmp_image_bytes are those of source -> inner size, and every
+  // element of the target outside `inner` gets `fill` (jb_fit_fill_kernel).  JB_FIT_COVER: has_roi / roi are the derived
+  // rectangle, and the plan is otherwise that of a caller who had asked for it.
+  int32_t fit_mode;  // JB_FIT_*
+  jb_roi inner;
+  uint8_t fill[3];
 };
 
 // a target size for jb_out_plan_, and the filter that gets there (JB_FILTER_*; 0: the exact area resize).  w = h = 0 with
@@ -79,11 +92,15 @@ struct JbTarget {
 // 0..8: JB_ERR_GEOMETRY, behind the scale's own check; 2..8 with a scale other than 1: JB_ERR_UNSUPPORTED, behind that).
 // crops: null = none; else n_crops rectangles, one per image of the launch (n_crops < 1: nothing to check); wants a target
 // and no roi.
+// fit: null = JB_FIT_STRETCH; its refusals come behind every other one ("fit", include/jpegblk.h).
 // the source window of one rectangle (null: the whole frame) under a plan's filter and target: what jb_filter_window
 // returns, without its checks (the plan has made them)
 jb_roi jb_filter_window_of_(const jb_image_desc *desc, const jb_roi *roi, int32_t out_w, int32_t out_h, int filter);
 JbOutPlan jb_out_plan_(const jb_image_desc *desc, int scale, const jb_output_spec *spec, const jb_roi *roi = nullptr,
-                       const JbTarget *target = nullptr, const jb_roi *crops = nullptr, int n_crops = 0, int orientation = 1);
+                       const JbTarget *target = nullptr, const jb_roi *crops = nullptr, int n_crops = 0, int orientation = 1,
+                       const jb_fit *fit = nullptr);
+// "fit": src and inner of a sw x sh source at (sx, sy) under a VALID fit (null: stretch) and the target w x h
+jb_fit_geometry jb_fit_geometry_of_(const jb_roi &source, int32_t w, int32_t h, const jb_fit *fit);
 // "views": the plan of n_images * views_per_image views under `rs` (null: JB_ERR_NULL) -- views_per_image, then every view's
 // flags and reserved, then the rectangles, the target ("no target size": JB_ERR_STATE) and the filter, as jb_out_plan_
 // checks per-image rectangles.  views may be null when there are none.

@@ -173,6 +173,43 @@ JbLjWindow lj_window(const jb_device_batch *b, const jb_geometry &g, const jb_ro
   return jbk_lj_window(b->desc.hs, b->desc.vs, g.mcus_x, g.mcus_y, r.x, r.y, r.width, r.height);
 }
 
+// "fit": the resample and filter kernels produce plan.inner of every output -- its size is their ow x oh, and dst is moved
+// to its first element (their stores address element-wise through the strides, which stay the output's).  Without a
+// JB_FIT_PAD the inner rectangle is the whole output.
+int64_t inner_offset(const jb_device_batch *b, const JbOutPlan &plan) {
+  return (int64_t)plan.inner.y * b->rgb_row_stride + (int64_t)plan.inner.x * (plan.planar ? plan.esize : 3);
+}
+
+// JB_FIT_PAD: the border of images i0 .. i0 + m - 1 (a call's launch: all of them) -- every element of the outputs outside plan.inner -- in one launch
+// (jb_fit.hip).  Only one axis pads, so there are at most two bands.
+JbFitFill fill_args(const jb_device_batch *b, const JbOutPlan &plan, int64_t plane_stride, int64_t i0, int m) {
+  const int64_t rgb_step = b->n_images > 1 ? b->rgb_image_stride : 0;
+  const jb_roi &in = plan.inner;
+  JbFitFill f;
+  memset(&f, 0, sizeof f);
+  f.dst = b->d_rgb + i0 * rgb_step;
+  f.dst_image_stride = rgb_step;
+  f.dst_row_stride = b->rgb_row_stride;
+  f.dst_plane_stride = plane_stride;
+  f.ow = plan.out_w, f.oh = plan.out_h;
+  f.n_images = m;
+  if (in.width < plan.out_w) {  // left and right, the full height
+    f.bx[0] = 0, f.bw[0] = in.x, f.bx[1] = in.x + in.width, f.bw[1] = plan.out_w - in.x - in.width;
+    f.by[0] = f.by[1] = 0, f.bh[0] = f.bh[1] = plan.out_h;
+  } else {  // top and bottom, the full width (none when the inner rectangle is the output)
+    f.by[0] = 0, f.bh[0] = in.y, f.by[1] = in.y + in.height, f.bh[1] = plan.out_h - in.y - in.height;
+    f.bx[0] = f.bx[1] = 0, f.bw[0] = f.bw[1] = plan.out_w;
+  }
+  for (int c = 0; c < 3; c++) f.scale[c] = plan.spec.scale[c], f.bias[c] = plan.spec.bias[c], f.fill[c] = plan.fill[c];
+  return f;
+}
+// false: the border of n_images outputs wants more workgroups than a launch takes
+bool fill_fits(const JbOutPlan &plan, int64_t n_images) {
+  if (plan.fit_mode != JB_FIT_PAD) return true;
+  const int64_t border = (int64_t)plan.out_w * plan.out_h - (int64_t)plan.inner.width * plan.inner.height;
+  return (border / 256 + 2) * n_images <= 0x7fffffffLL;  // (two bands, each rounded up to whole workgroups)
+}
+
 // the resample launch of a sub-batch of m images from image i0 on; src: the scratch
 JbResample resample_args(const jb_device_batch *b, const JbOutPlan &plan, int64_t plane_stride, const void *src, int64_t i0, int m) {
   const int64_t rgb_step = b->n_images > 1 ? b->rgb_image_stride : 0;
@@ -180,11 +217,11 @@ JbResample resample_args(const jb_device_batch *b, const JbOutPlan &plan, int64_
   memset(&q, 0, sizeof q);
   q.src = (const uint8_t *)src;
   q.src_image_stride = plan.tmp_image_bytes;
-  q.dst = b->d_rgb + i0 * rgb_step;
+  q.dst = b->d_rgb + i0 * rgb_step + inner_offset(b, plan);
   q.dst_image_stride = rgb_step;
   q.dst_row_stride = b->rgb_row_stride;
   q.dst_plane_stride = plane_stride;
-  q.iw = plan.src_w, q.ih = plan.src_h, q.ow = plan.out_w, q.oh = plan.out_h;
+  q.iw = plan.src_w, q.ih = plan.src_h, q.ow = plan.inner.width, q.oh = plan.inner.height;
   q.n_images = m;
   for (int c = 0; c < 3; c++) q.scale[c] = plan.spec.scale[c], q.bias[c] = plan.spec.bias[c];
   return q;
@@ -339,7 +376,7 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
   std::vector<jb_roi> windows;  // what the pixel kernel writes of every image: with a filter, not the rectangle
   if (plan.filter)
     for (int64_t i = 0; i < b->n_images; i++)
-      windows.push_back(jb_filter_window_of_(&ob.desc, &plan.crops[i], plan.out_w, plan.out_h, plan.filter));
+      windows.push_back(jb_filter_window_of_(&ob.desc, &plan.crops[i], plan.inner.width, plan.inner.height, plan.filter));
   const jb_roi *const shown = plan.filter ? windows.data() : plan.crops;
   return rects_into_scratch(ctx, b, stream, plan.orient, shown, g, [&](int64_t i0, int m, const JbCropTable &table, const void *src, hipStream_t s) {
     if (plan.filter) {
@@ -381,7 +418,7 @@ int seam_launch_views(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
     for (int v = 0; v < k; v++) {
       const jb_view &w = plan.views[i * k + v];
       const jb_roi r = {w.x, w.y, w.width, w.height};
-      const jb_roi src = plan.filter ? jb_filter_window_of_(&ob.desc, &r, plan.out_w, plan.out_h, plan.filter) : r;
+      const jb_roi src = plan.filter ? jb_filter_window_of_(&ob.desc, &r, plan.inner.width, plan.inner.height, plan.filter) : r;
       if (v == 0 || src.x < x0) x0 = src.x;
       if (v == 0 || src.y < y0) y0 = src.y;
       if (v == 0 || src.x + src.width > x1) x1 = src.x + src.width;
@@ -436,7 +473,7 @@ int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, con
   int64_t per = cap / plan.tmp_image_bytes;
   if (per < 1) per = 1;
   if (per > b->n_images) per = b->n_images;
-  if (((int64_t)(plan.out_w + 63) / 64) * ((plan.out_h + 3) / 4) * per > 0x7fffffffLL)
+  if (((int64_t)(plan.inner.width + 63) / 64) * ((plan.inner.height + 3) / 4) * per > 0x7fffffffLL || !fill_fits(plan, b->n_images))
     return fail(ctx, JB_ERR_CAPACITY, "batch too large for one launch");
   DeviceGuard guard(ctx->device);
   const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
@@ -466,6 +503,9 @@ int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, con
       JB_HIP(ctx, jbk_resample_launch(resample_args(b, plan, plane_stride, tmp, i0, m), plan.format, s));
     }
   }
+  // JB_FIT_PAD: the border of every image of the call in one launch.  Bands and inner rectangles are disjoint, so its place
+  // on the stream is free: behind the last sub-batch, so that a sub-batch that fails leaves the bands alone
+  if (plan.fit_mode == JB_FIT_PAD) JB_HIP(ctx, jbk_fit_fill_launch(fill_args(b, plan, plane_stride, 0, b->n_images), plan.format, s));
   return JB_OK;
 }
 
@@ -495,7 +535,7 @@ int seam_launch_oriented(jb_ctx *ctx, const jb_device_batch *b, void *stream, co
   if (per > b->n_images) per = b->n_images;
   const int64_t tile = kJbOrientTile;
   if (((stored.width + tile - 1) / tile) * ((stored.height + tile - 1) / tile) * per > 0x7fffffffLL ||
-      (plan.has_resize && ((int64_t)(plan.out_w + 63) / 64) * ((plan.out_h + 3) / 4) * per > 0x7fffffffLL))
+      (plan.has_resize && (((int64_t)(plan.inner.width + 63) / 64) * ((plan.inner.height + 3) / 4) * per > 0x7fffffffLL || !fill_fits(plan, b->n_images))))
     return fail(ctx, JB_ERR_CAPACITY, "batch too large for one launch");
   DeviceGuard guard(ctx->device);
   const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
@@ -545,6 +585,7 @@ int seam_launch_oriented(jb_ctx *ctx, const jb_device_batch *b, void *stream, co
       JB_HIP(ctx, jbk_resample_launch(resample_args(&ob, plan, plane_stride, turned, i0, m), plan.format, s));
     }
   }
+  if (plan.fit_mode == JB_FIT_PAD) JB_HIP(ctx, jbk_fit_fill_launch(fill_args(b, plan, plane_stride, 0, b->n_images), plan.format, s));  // (as in 3b: last)
   return JB_OK;
 }
 
@@ -609,8 +650,8 @@ int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOut
 
 // the plan of a seam entry point: of b's frame under the context's orientation
 static JbOutPlan seam_plan(const jb_ctx *ctx, const jb_device_batch *b, int scale, const jb_output_spec *spec, const jb_roi *roi = nullptr,
-                           const JbTarget *target = nullptr, const jb_roi *crops = nullptr, int n_crops = 0) {
-  return jb_out_plan_(b ? &b->desc : nullptr, scale, spec, roi, target, crops, n_crops, ctx ? ctx->orientation : JB_ORIENT_STORED);
+                           const JbTarget *target = nullptr, const jb_roi *crops = nullptr, int n_crops = 0, const jb_fit *fit = nullptr) {
+  return jb_out_plan_(b ? &b->desc : nullptr, scale, spec, roi, target, crops, n_crops, ctx ? ctx->orientation : JB_ORIENT_STORED, fit);
 }
 
 extern "C" {
@@ -656,6 +697,13 @@ int jb_blocks_to_rgb_device_filtered(jb_ctx *ctx, const jb_device_batch *b, cons
   if (ctx && !rs) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_filtered: rs is NULL");
   const JbTarget t = rs ? JbTarget{rs->out_w, rs->out_h, rs->filter, rs->reserved} : JbTarget{};
   return seam_launch(ctx, b, stream, seam_plan(ctx, b, 1, spec, roi, &t), "jb_blocks_to_rgb_device_filtered");
+}
+
+int jb_blocks_to_rgb_device_fit(jb_ctx *ctx, const jb_device_batch *b, const jb_roi *roi, const jb_resize *rs, const jb_fit *fit,
+                                const jb_output_spec *spec, void *stream) {
+  if (ctx && !rs) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_fit: rs is NULL");
+  const JbTarget t = rs ? JbTarget{rs->out_w, rs->out_h, rs->filter, rs->reserved} : JbTarget{};
+  return seam_launch(ctx, b, stream, seam_plan(ctx, b, 1, spec, roi, &t, nullptr, 0, fit), "jb_blocks_to_rgb_device_fit");
 }
 
 int jb_blocks_to_rgb_device_crops_filtered(jb_ctx *ctx, const jb_device_batch *b, const jb_roi *rois, const jb_resize *rs,
