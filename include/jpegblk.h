@@ -645,6 +645,64 @@ int jb_orient_map_roi(int32_t w, int32_t h, int orientation, const jb_roi *orien
  * orientation 2..8 (JB_ORIENT_EXIF passes here: a file decides, and an entry point without one answers JB_ERR_STATE), JB_ERR_GEOMETRY for a rectangle that does not lie in the ORIENTED frame.  Pure host code. */
 int jb_orient_check(const jb_image_desc *desc, int orientation, int scale, const jb_roi *roi);
 
+/* ---- draft decode: libjpeg's 1/2, 1/4 and 1/8 reduced decode (scale_denom; Pillow's Image.draft) ----
+ * Under JB_ARITH_LIBJPEG a context with draft K in {2, 4, 8} decodes what libjpeg gives with scale_num / scale_denom =
+ * 1 / K -- Pillow's im.draft(), which Image.thumbnail() uses too -- bit for bit.  This is NOT scale= (an area mean of
+ * the full-size decode): every component gets a reduced IDCT of its own, and in subsampled files chroma is enlarged by
+ * the IDCT where libjpeg does so, not by the upsampler.  For a frame W x H with luma factors hs, vs (chroma 1 x 1):
+ *   The DRAFT FRAME is ow = ceil(W / K) by oh = ceil(H / K).
+ *   Block sizes (jdmaster.c).  A luma block gives S = 8 / K samples per axis.  A chroma block gives Sc: Sc starts at S
+ *     and doubles while Sc < 8 and (hs * S) % (2 * Sc) == 0 and (vs * S) % (2 * Sc) == 0.  4:2:0 therefore gets Sc = 2 S
+ *     and no upsampling at all; 4:2:2, 4:4:0 and 4:4:4 get Sc = S and keep their upsampler.  What the upsampler still
+ *     does is eh = hs * S / Sc, ev = vs * S / Sc (1 or 2).  Grayscale arrives as 4:4:4.
+ *   Reduced IDCTs (jidctred.c; CONST_BITS 13, PASS1_BITS 2).  v = coef * q; D(x, n) = (x + (1 << (n - 1))) >> n, an
+ *     arithmetic shift; sample = clamp(out + 128).  Size 8 is the islow IDCT of "decoder arithmetic".
+ *     Size 4: one 1-D network on in0, in1, in2, in3, in5, in6, in7 (index 4 is never read):
+ *         t0 = in0 << 14;  t2 = in2 * 15137 - in6 * 6270;  t10 = t0 + t2;  t12 = t0 - t2
+ *         a = -in7 * 1730 + in5 * 11893 - in3 * 17799 + in1 * 8697
+ *         b = -in7 * 4176 - in5 * 4926 + in3 * 7373 + in1 * 20995
+ *         out0..3 = D(t10 + b, n), D(t12 + a, n), D(t12 - a, n), D(t10 - b, n)
+ *       Columns pass over columns 0-3 and 5-7 with n = 12, giving 4 rows; rows pass over those rows with n = 19.
+ *     Size 2: the network reads in0, in1, in3, in5, in7:
+ *         t10 = in0 << 15;  t = -in7 * 5906 + in5 * 6967 - in3 * 10426 + in1 * 29692
+ *         out0, out1 = D(t10 + t, n), D(t10 - t, n)
+ *       Columns pass over columns 0, 1, 3, 5, 7 with n = 13; rows pass with n = 20.
+ *     Size 1: out = D(v[0], 3).
+ *   Planes.  Component c is a plane of its S- (luma) or Sc-sized (chroma) blocks.
+ *   Upsampling.  Rule 2 of "decoder arithmetic" with (eh, ev) in the place of (hs, vs) and the draft frame in the place
+ *     of W x H: dw = ceil(ow / eh), dh = ceil(oh / ev); the dw <= 2 exception stays.  At K = 8 libjpeg switches fancy
+ *     upsampling off (jdsample.c: min_DCT_scaled_size > 1 fails) and chroma is plainly replicated: c[y / ev][x / eh].
+ *   Colour.  Rule 3, unchanged.
+ *   Domain.  As in "decoder arithmetic": every intermediate in int32, both passes' inputs in int16.
+ * Draft comes FIRST: the draft image is "the full-size decode" for everything behind it.  Formats 0-3, a rectangle, a
+ * target size with every filter and fit, per-image rectangles and views act on it exactly as their sections define for
+ * a frame of ow x oh: rectangles, the filters' in_size, the tap cap, jb_fit_check and jb_filter_window take draft
+ * coordinates (hand the pure-host checkers a descriptor with the draft frame's size), and buffers, *width / *height
+ * and the batch decoder's widths / heights report the draft frame or the target.  Draft 1 (the default) is bit for bit
+ * and launch for launch the behaviour without this section.
+ * The setting belongs to the context (of a batch decoder: to the decoder), as the arithmetic and the orientation do,
+ * and is no part of the output plan.  jb_ctx_set_draft: JB_ERR_NULL for a null context, JB_ERR_GEOMETRY for a value
+ * outside {1, 2, 4, 8}, JB_ERR_STATE while a submission of the context is in flight.  A draft other than 1 under
+ * JB_ARITH_REFERENCE, with a scale other than 1, or with an orientation other than JB_ORIENT_STORED (JB_ORIENT_EXIF
+ * included) is JB_ERR_UNSUPPORTED -- at the call for a context, at the setters for a decoder (see
+ * jb_batch_decoder_set_draft) -- and nothing is launched, uploaded or written.
+ * Out of scope: scales M / 8 other than 1/2, 1/4, 1/8; JDCT_IFAST; choosing K from a requested size (Pillow's rule is
+ * one line for the caller, and jb_draft_geometry_of gives the sizes). */
+int jb_ctx_set_draft(jb_ctx *ctx, int denom);
+/* the context's draft; a null context: 1 */
+int jb_ctx_draft(const jb_ctx *ctx);
+typedef struct jb_draft_geometry {
+  int32_t width, height; /* ceil(W / K), ceil(H / K): the DRAFT FRAME */
+  int32_t luma_block;    /* S = 8 / K: samples per axis of a luma block */
+  int32_t chroma_block;  /* Sc, above */
+  int32_t up_h, up_v;    /* eh = hs * S / Sc, ev = vs * S / Sc: what the upsampler still does (1 or 2) */
+  int32_t fancy;         /* 1: the triangle filter; 0: plain replication (K = 8) */
+  int32_t reserved;
+} jb_draft_geometry;
+/* The draft geometry of a frame at draft `denom` (1: the frame itself, S = Sc = 8, eh = hs, ev = vs).  JB_ERR_NULL; the
+ * descriptor's own errors; JB_ERR_GEOMETRY for a denom outside {1, 2, 4, 8}.  Pure host code. */
+int jb_draft_geometry_of(const jb_image_desc *desc, int denom, jb_draft_geometry *out);
+
 /* ---- host front end ("next" rows of the scope table; reference jpeg.cpp:67-446, 826-907,
  *      include/file.hpp, include/huffman.hpp) --------------------------------------------- */
 /* Parse a JFIF byte stream and Huffman-decode it into packed int16 blocks in the order
@@ -866,6 +924,14 @@ int jb_batch_decoder_set_arithmetic(jb_batch_decoder *dec, int arith);
  * flight, with JB_ERR_GEOMETRY for a value outside 0..8, and any value but JB_ORIENT_STORED while the scale is not 1
  * (and jb_batch_decoder_set_scale(!= 1) under such a value) with JB_ERR_UNSUPPORTED. */
 int jb_batch_decoder_set_orientation(jb_batch_decoder *dec, int orientation);
+/* The draft (1, 2, 4, 8; see "draft decode") of the batch decoder's later runs and submissions.  Applies to every
+ * device of a multi-device decoder and to both sides of submit / collect.  Reported widths and heights, the decoder's
+ * rectangle and the rectangles and views of run_crops / run_views are the draft frame's.  Refused with JB_ERR_STATE
+ * while a batch is in flight, with JB_ERR_GEOMETRY for another value, and a value other than 1 with JB_ERR_UNSUPPORTED
+ * under JB_ARITH_REFERENCE, while the scale is not 1 or while the orientation is not JB_ORIENT_STORED -- as
+ * jb_batch_decoder_set_arithmetic(JB_ARITH_REFERENCE), _set_scale(!= 1) and _set_orientation(!= JB_ORIENT_STORED) are
+ * while the draft is not 1. */
+int jb_batch_decoder_set_draft(jb_batch_decoder *dec, int denom);
 /* Output sink replacing the reference's X11 window / unused BMP writer (display.hpp,
  * jpeg.cpp:462-509): binary PPM (P6). */
 int jb_write_ppm(const char *path, const uint8_t *rgb, int32_t width, int32_t height,

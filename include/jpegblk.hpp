@@ -43,6 +43,12 @@ class Context {
     if (rc) throw Error(rc, jb_last_error(ctx_));
   }
   int arithmetic() const { return jb_ctx_arithmetic(ctx_); }
+  // "draft decode" (jpegblk.h): under JB_ARITH_LIBJPEG, libjpeg's 1/2, 1/4 or 1/8 reduced decode (Pillow's draft)
+  void set_draft(int denom) {
+    int rc = jb_ctx_set_draft(ctx_, denom);
+    if (rc) throw Error(rc, jb_last_error(ctx_));
+  }
+  int draft() const { return jb_ctx_draft(ctx_); }
 
  private:
   jb_ctx *ctx_ = nullptr;

@@ -15,7 +15,8 @@ from .api import (JbError, Context, ImageDesc, Geometry, DeviceBatch, lib, lib_p
                   FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC, ARITH_REFERENCE, ARITH_LIBJPEG,
                   ORIENT_EXIF, ORIENT_STORED, exif_orientation, oriented_size, orient_map_roi,
                   View, VIEW_MIRROR, VIEWS_MAX, views_check,
-                  Fit, FitGeometry, fit_geometry, FIT_STRETCH, FIT_PAD, FIT_COVER, FIT_CENTER, FIT_START, FIT_END)
+                  Fit, FitGeometry, fit_geometry, FIT_STRETCH, FIT_PAD, FIT_COVER, FIT_CENTER, FIT_START, FIT_END,
+                  DraftGeometry, draft_geometry)
 from .crops import random_resized_crop, random_views
 
 __all__ = ["JbError", "Context", "ImageDesc", "Geometry", "DeviceBatch", "lib", "lib_path",
@@ -25,4 +26,5 @@ __all__ = ["JbError", "Context", "ImageDesc", "Geometry", "DeviceBatch", "lib", 
            "random_resized_crop", "Resize", "filter_check", "filter_window", "FILTER_AREA", "FILTER_BILINEAR", "FILTER_BICUBIC",
            "ARITH_REFERENCE", "ARITH_LIBJPEG", "ORIENT_EXIF", "ORIENT_STORED", "exif_orientation", "oriented_size",
            "orient_map_roi", "View", "VIEW_MIRROR", "VIEWS_MAX", "views_check", "random_views",
-           "Fit", "FitGeometry", "fit_geometry", "FIT_STRETCH", "FIT_PAD", "FIT_COVER", "FIT_CENTER", "FIT_START", "FIT_END"]
+           "Fit", "FitGeometry", "fit_geometry", "FIT_STRETCH", "FIT_PAD", "FIT_COVER", "FIT_CENTER", "FIT_START", "FIT_END",
+           "DraftGeometry", "draft_geometry"]

@@ -142,6 +142,12 @@ class FitGeometry(ctypes.Structure):
     _fields_ = [("src", Roi), ("inner", Roi)]
 
 
+class DraftGeometry(ctypes.Structure):
+    """jb_draft_geometry: the draft frame, the luma and chroma block sizes and what the upsampler still does."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("luma_block", ctypes.c_int32), ("chroma_block", ctypes.c_int32),
+                ("up_h", ctypes.c_int32), ("up_v", ctypes.c_int32), ("fancy", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 def _ref(struct):
     """byref(struct), or None (a NULL pointer) for None."""
     return ctypes.byref(struct) if struct is not None else None
@@ -511,6 +517,10 @@ def lib():
     L.jb_ctx_set_orientation.argtypes = [vp, ctypes.c_int]
     L.jb_ctx_orientation.argtypes = [vp]
     L.jb_batch_decoder_set_orientation.argtypes = [vp, ctypes.c_int]
+    L.jb_ctx_set_draft.argtypes = [vp, ctypes.c_int]
+    L.jb_ctx_draft.argtypes = [vp]
+    L.jb_batch_decoder_set_draft.argtypes = [vp, ctypes.c_int]
+    L.jb_draft_geometry_of.argtypes = [pd, ctypes.c_int, ctypes.POINTER(DraftGeometry)]
     L.jb_exif_orientation.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
     L.jb_oriented_size.argtypes = [i32, i32, ctypes.c_int, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.jb_orient_map_roi.argtypes = [i32, i32, ctypes.c_int, pr, pr]
@@ -580,6 +590,14 @@ def orient_map_roi(width, height, orientation, roi):
     return out.x, out.y, out.width, out.height
 
 
+def draft_geometry(desc, denom):
+    """jb_draft_geometry_of: the DraftGeometry of `desc` at draft `denom` (1, 2, 4, 8) -- width x height is the draft
+    frame that every output option of a context with that draft then acts on."""
+    g = DraftGeometry()
+    _check(lib().jb_draft_geometry_of(ctypes.byref(desc), int(denom), ctypes.byref(g)))
+    return g
+
+
 def output_bytes(width, height, fmt=FMT_RGB_U8_HWC):
     """jb_output_bytes: bytes of one width x height image in a format (tight rows and planes)."""
     n = ctypes.c_int64()
@@ -613,7 +631,8 @@ def entropy_decode(jpeg_bytes, headers_only=False, n_threads=1):
 class Context:
     """jb_ctx: one device, one stream, a ring of staging slots."""
 
-    def __init__(self, device=0, max_coef_bytes=0, max_rgb_bytes=0, n_slots=2, arithmetic=ARITH_REFERENCE, orientation=ORIENT_STORED):
+    def __init__(self, device=0, max_coef_bytes=0, max_rgb_bytes=0, n_slots=2, arithmetic=ARITH_REFERENCE, orientation=ORIENT_STORED,
+                 draft=1):
         self._h = ctypes.c_void_p()
         _check(lib().jb_ctx_create(device, max_coef_bytes, max_rgb_bytes, n_slots, ctypes.byref(self._h)))
         try:
@@ -621,9 +640,23 @@ class Context:
                 self.set_arithmetic(arithmetic)
             if orientation != ORIENT_STORED:
                 self.set_orientation(orientation)
+            if draft != 1:
+                self.set_draft(draft)
         except JbError:
             self.close()
             raise
+
+    def set_draft(self, draft):
+        """jb_ctx_set_draft: 1, or under ARITH_LIBJPEG 2, 4, 8 -- every later call of this context then decodes libjpeg's
+        1/2, 1/4 or 1/8 reduced image (Pillow's im.draft(); NOT scale=) and fmt, roi, resize, crops, views, filter and
+        fit act on that draft frame: rectangles and sizes are in its coordinates (draft_geometry).  JbError -2 for another
+        value, -7 while a submission is in flight; with ARITH_REFERENCE, a scale other than 1 or an orientation other than
+        ORIENT_STORED a draft other than 1 is JbError -9 at the call."""
+        _check(lib().jb_ctx_set_draft(self._h, int(draft)), self._h)
+
+    @property
+    def draft(self):
+        return lib().jb_ctx_draft(self._h)
 
     def set_orientation(self, orientation):
         """jb_ctx_set_orientation: ORIENT_STORED (the pixels as the file stores them), 2..8 (that Exif code, whatever the
@@ -707,9 +740,14 @@ class Context:
 
     # -- the seam, host buffers --------------------------------------------------------------
     def _host_output_size(self, desc):
-        """(w, h) of what the host seam writes for `desc` under this context's orientation: the oriented frame's.
+        """(w, h) of what the host seam writes for `desc` under this context's orientation and draft: the oriented
+        frame's, or the draft frame's (the two do not combine: the call answers JbError -9).
         ORIENT_EXIF has no file here: JbError -7, as the C entry points answer, before any buffer is sized."""
         o = self.orientation
+        k = self.draft
+        if k != 1:
+            g = draft_geometry(desc, k)
+            return g.width, g.height
         if o == ORIENT_EXIF:
             raise JbError(-7, "ORIENT_EXIF takes the orientation from a file: the host seam has none (set 1..8)")
         return oriented_size(desc.width, desc.height, o)
@@ -877,10 +915,12 @@ class BatchDecoder:
     (jb_batch_decoder_set_orientation): ORIENT_EXIF applies every file's own Exif tag, 2..8 that code to every file, in
     front of every other option: sizes, roi and crops are then the oriented image's (not with a scale).  fit
     (jb_batch_decoder_set_fit; with resize): Fit.pad(...) letterboxes every file into the target, Fit.cover(...) cuts the
-    largest centred rectangle of the target's aspect ratio; not with run(crops=) or run(views=)."""
+    largest centred rectangle of the target's aspect ratio; not with run(crops=) or run(views=).  draft
+    (jb_batch_decoder_set_draft; with ARITH_LIBJPEG): 2, 4, 8 decode every file to libjpeg's reduced image, Pillow's draft,
+    in front of every other option."""
 
     def __init__(self, n_threads=8, device=0, max_coef_bytes=0, max_rgb_bytes=0, arena_bytes=0, devices=None, scale=1, fmt=None,
-                 roi=None, resize=None, filter=FILTER_AREA, arithmetic=ARITH_REFERENCE, orientation=ORIENT_STORED, fit=None):
+                 roi=None, resize=None, filter=FILTER_AREA, arithmetic=ARITH_REFERENCE, orientation=ORIENT_STORED, fit=None, draft=1):
         _Request(scale, fmt, roi, resize, filter=filter, fit=fit)   # (roi or resize with a scale: JbError(-9) before anything is created)
         self._h = ctypes.c_void_p()
         if devices is not None:
@@ -913,6 +953,8 @@ class BatchDecoder:
                 self.set_orientation(orientation)
             if fit is not None:
                 self.set_fit(fit)
+            if draft != 1:
+                self.set_draft(draft)
         except JbError:
             self.close()
             raise
@@ -956,6 +998,13 @@ class BatchDecoder:
         if fit is not None and not isinstance(fit, Fit):
             fit = Fit(int(fit), FIT_CENTER, (ctypes.c_uint8 * 3)(0, 0, 0), 0, 0)
         _check(lib().jb_batch_decoder_set_fit(self._h, _ref(fit)))
+
+    def set_draft(self, draft):
+        """jb_batch_decoder_set_draft: 1, 2, 4 or 8 for later runs and submissions -- under ARITH_LIBJPEG every file then
+        decodes to libjpeg's reduced image (Pillow's draft), and sizes, roi, crops and views are that draft frame's
+        (JbError -7 while a batch is in flight, -2 for another value, -9 for a value other than 1 without ARITH_LIBJPEG,
+        with a scale other than 1 or an orientation other than ORIENT_STORED)."""
+        _check(lib().jb_batch_decoder_set_draft(self._h, int(draft)))
 
     def set_arithmetic(self, arithmetic):
         """jb_batch_decoder_set_arithmetic: ARITH_REFERENCE or ARITH_LIBJPEG for later runs and submissions (JbError -7

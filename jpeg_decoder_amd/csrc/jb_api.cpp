@@ -419,6 +419,23 @@ int jb_ctx_set_orientation(jb_ctx *ctx, int orientation) {
 
 int jb_ctx_orientation(const jb_ctx *ctx) { return ctx ? ctx->orientation : JB_ORIENT_STORED; }
 
+int jb_ctx_set_draft(jb_ctx *ctx, int denom) {
+  if (!ctx) return fail(nullptr, JB_ERR_NULL, "jb_ctx_set_draft: ctx is NULL");
+  if (denom != 1 && denom != 2 && denom != 4 && denom != 8) return fail(ctx, JB_ERR_GEOMETRY, "jb_ctx_set_draft: %d is not 1, 2, 4 or 8", denom);
+  // (as jb_ctx_set_arithmetic: not while a submission of the ring is in flight)
+  DeviceGuard guard(ctx->device);
+  for (int i = 0; i < ctx->n_slots; i++) {
+    Slot &s = ctx->slots[i];
+    if (!s.busy) continue;
+    if (s.dl_pending.load(std::memory_order_acquire) || hipEventQuery(s.done) == hipErrorNotReady)
+      return fail(ctx, JB_ERR_STATE, "jb_ctx_set_draft: a submission is in flight (wait for it first)");
+  }
+  ctx->draft = denom;
+  return JB_OK;
+}
+
+int jb_ctx_draft(const jb_ctx *ctx) { return ctx ? ctx->draft : 1; }
+
 long long jb_ctx_device_entropy_images(const jb_ctx *ctx) { return ctx ? ctx->n_device_entropy : 0; }
 
 int jb_ctx_last_desc(const jb_ctx *ctx, jb_image_desc *out) {
@@ -542,6 +559,9 @@ int submit_begin(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const JbO
   int rc = check_desc(ctx, desc, &sub.g);
   if (rc) return rc;
   if (n_images < 1 || n_images > kMaxBatch) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d outside 1..%d", n_images, kMaxBatch);
+  // "draft decode": the plan is the draft frame's, which exists only where the draft goes with everything else
+  if (const char *why = jb_draft_refusal_(ctx->draft, ctx->arithmetic, plan.scale ? plan.scale : 1, plan.orient == JB_ORIENT_STORED ? ctx->orientation : plan.orient))
+    return fail(ctx, JB_ERR_UNSUPPORTED, "submit: %s", why);
   if (plan.status != JB_OK) return fail(ctx, plan.status, "submit: %s", plan.why);
   if (ctx->arithmetic == JB_ARITH_LIBJPEG && plan.scale != 1) return fail(ctx, JB_ERR_UNSUPPORTED, "submit: %s", kJbArithScaleText);
   if (plan.orient == JB_ORIENT_EXIF) return fail(ctx, JB_ERR_STATE, "submit: %s", kJbOrientExifText);
@@ -860,14 +880,16 @@ int jb_submit(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const
               uint8_t *rgb, int64_t rgb_stride, int *ticket) {
   if (!ctx) return fail(nullptr, JB_ERR_NULL, "jb_submit: ctx is NULL");
   if (!desc || !coef || !qtabs || !rgb || !ticket) return fail(ctx, JB_ERR_NULL, "jb_submit: NULL pointer");
-  return submit_impl(ctx, desc, 1, coef, qtabs, rgb, rgb_stride, ticket, jb_out_plan_(desc, 1, nullptr, nullptr, nullptr, nullptr, 0, ctx->orientation), false);
+  const jb_image_desc frame = jb_draft_desc_(desc, ctx->draft);  // ("draft decode": the output is the draft frame)
+  return submit_impl(ctx, desc, 1, coef, qtabs, rgb, rgb_stride, ticket, jb_out_plan_(&frame, 1, nullptr, nullptr, nullptr, nullptr, 0, ctx->orientation), false);
 }
 
 int jb_submit_batch(jb_ctx *ctx, const jb_image_desc *desc, int n_images, const int16_t *coef,
                     const uint16_t *qtabs, uint8_t *rgb, int *ticket) {
   if (!ctx) return fail(nullptr, JB_ERR_NULL, "jb_submit_batch: ctx is NULL");
   if (!desc || !coef || !qtabs || !rgb || !ticket) return fail(ctx, JB_ERR_NULL, "jb_submit_batch: NULL pointer");
-  const JbOutPlan plan = jb_out_plan_(desc, 1, nullptr, nullptr, nullptr, nullptr, 0, ctx->orientation);
+  const jb_image_desc frame = jb_draft_desc_(desc, ctx->draft);
+  const JbOutPlan plan = jb_out_plan_(&frame, 1, nullptr, nullptr, nullptr, nullptr, 0, ctx->orientation);
   return submit_impl(ctx, desc, n_images, coef, qtabs, rgb, plan.row_stride, ticket, plan, false);
 }
 
@@ -993,6 +1015,9 @@ int jb_check_device_region_(int device, const void *p, size_t bytes) {
 void jb_ctx_set_last_desc_(jb_ctx *ctx, const jb_image_desc *d) { ctx->last_desc = *d; }
 void jb_ctx_set_arithmetic_(jb_ctx *ctx, int arith) {
   if (ctx) ctx->arithmetic = arith;
+}
+void jb_ctx_set_draft_(jb_ctx *ctx, int denom) {
+  if (ctx) ctx->draft = denom;
 }
 const JbKnobs *jb_ctx_knobs_(const jb_ctx *ctx) { return &ctx->knobs; }
 

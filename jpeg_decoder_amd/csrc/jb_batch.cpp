@@ -44,6 +44,7 @@ struct OutputRequest {
   const JbTarget *target_ptr() const { return has_resize ? &target : nullptr; }
   int arith = JB_ARITH_REFERENCE;  // "decoder arithmetic": what the decoder's contexts compute in (never LIBJPEG with a scale)
   int orient = JB_ORIENT_STORED;   // "orientation": JB_ORIENT_* or 2..8 (never another value than 1 with a scale)
+  int draft = 1;                   // "draft decode": 1, 2, 4, 8 (never another value than 1 without LIBJPEG, with a scale or an orientation)
   jb_fit fit = {};                 // "fit": a valid one; JB_FIT_STRETCH: none.  Kept, like the filter, while no target size is set
   const jb_fit *fit_ptr() const { return fit.mode != JB_FIT_STRETCH ? &fit : nullptr; }
   // can it be had at all?  The plan function decides (jb_plan.h), here for an image of one pixel -- with a rectangle,
@@ -262,11 +263,12 @@ void parse_one(Parsed &p, const OutputRequest &out, const jb_roi *crop = nullptr
   // has just been parsed, so a head that parses holds it)
   int orient = out.orient;
   if (orient == JB_ORIENT_EXIF && jb_exif_orientation(p.bytes.data(), p.bytes.size(), &orient) != JB_OK) orient = JB_ORIENT_STORED;
+  const jb_image_desc frame = jb_draft_desc_(&p.desc, out.draft);  // ("draft decode": every size downstream is the draft frame's)
   if (views) {
     const jb_resize rs = {out.target.w, out.target.h, out.target.filter, out.target.reserved};
-    p.plan = jb_views_plan_(&p.desc, &out.spec, views, 1, k, &rs, orient);
+    p.plan = jb_views_plan_(&frame, &out.spec, views, 1, k, &rs, orient);
   } else {
-    p.plan = jb_out_plan_(&p.desc, out.scale, &out.spec, crop ? crop : out.roi_ptr(), out.target_ptr(), nullptr, 0, orient, out.fit_ptr());
+    p.plan = jb_out_plan_(&frame, out.scale, &out.spec, crop ? crop : out.roi_ptr(), out.target_ptr(), nullptr, 0, orient, out.fit_ptr());
   }
   p.status = p.plan.status;
   if (p.status == JB_OK) p.geo.rgb_bytes = p.plan.image_bytes;
@@ -624,14 +626,15 @@ struct LaneWorker {
     JbOutPlan plan = head.plan;
     std::vector<jb_roi> crops;
     std::vector<jb_view> views;  // "views": the members' views, k each, in the group's order
+    const jb_image_desc frame = jb_draft_desc_(&head.desc, r.out.draft);
     if (r.per.views) {
       const jb_resize rs = {r.out.target.w, r.out.target.h, r.out.target.filter, r.out.target.reserved};
       for (int j = 0; j < f.n; j++) views.insert(views.end(), parsed[(size_t)(f.k + j)].plan.views, parsed[(size_t)(f.k + j)].plan.views + r.per.k);
-      plan = jb_views_plan_(&head.desc, &r.out.spec, views.data(), f.n, r.per.k, &rs, head.plan.orient);
+      plan = jb_views_plan_(&frame, &r.out.spec, views.data(), f.n, r.per.k, &rs, head.plan.orient);
     }
     if (r.per.rois) {
       for (int j = 0; j < f.n; j++) crops.push_back(parsed[(size_t)(f.k + j)].plan.roi);
-      plan = jb_out_plan_(&head.desc, r.out.scale, &r.out.spec, nullptr, r.out.target_ptr(), crops.data(), f.n, head.plan.orient);
+      plan = jb_out_plan_(&frame, r.out.scale, &r.out.spec, nullptr, r.out.target_ptr(), crops.data(), f.n, head.plan.orient);
     }
     double a = jb_now_s_();
     // every copy of the submission is pinned <-> device, so this returns at once and the
@@ -951,6 +954,7 @@ int run_single(jb_batch_decoder *d, const char *const *paths, int n_paths, const
     // pass 2: entropy decoding on the host threads, all submitting to the shared context
     dev.ctx = d->ctx;
     jb_ctx_set_arithmetic_(d->ctx, d->out.arith);  // (nothing of this decoder is in flight here)
+    jb_ctx_set_draft_(d->ctx, d->out.draft);
     {
       // of two batches in flight on one device (submit / collect, or two decoders) the older one's downloads go first
       static std::atomic<uint64_t> run_seq{0};
@@ -1463,6 +1467,7 @@ extern "C" int jb_batch_decoder_set_scale(jb_batch_decoder *d, int denom) {
   out.scale = denom;
   if (denom != 1 && out.arith == JB_ARITH_LIBJPEG) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_scale: " kJbArithScaleText);
   if (denom != 1 && out.orient != JB_ORIENT_STORED) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_scale: " kJbOrientScaleText);
+  if (denom != 1 && out.draft != 1) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_scale: " kJbDraftScaleText);
   if (out.status() == JB_ERR_UNSUPPORTED)
     return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_scale: a planar output format, a rectangle or a target size is set: it cannot be combined with a scale");
   set_output_all(d, out);
@@ -1544,6 +1549,7 @@ extern "C" int jb_batch_decoder_set_arithmetic(jb_batch_decoder *d, int arith) {
     return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_set_arithmetic: unknown arithmetic");
   if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_arithmetic: batches are in flight (collect them first)");
   if (arith == JB_ARITH_LIBJPEG && d->out.scale != 1) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_arithmetic: " kJbArithScaleText);
+  if (arith != JB_ARITH_LIBJPEG && d->out.draft != 1) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_arithmetic: " kJbDraftArithText);
   OutputRequest out = d->out;
   out.arith = arith;
   set_output_all(d, out);
@@ -1556,8 +1562,22 @@ extern "C" int jb_batch_decoder_set_orientation(jb_batch_decoder *d, int orienta
   if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_orientation: batches are in flight (collect them first)");
   if (orientation != JB_ORIENT_STORED && d->out.scale != 1)
     return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_orientation: " kJbOrientScaleText);
+  if (orientation != JB_ORIENT_STORED && d->out.draft != 1)
+    return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_batch_decoder_set_orientation: " kJbDraftOrientText);
   OutputRequest out = d->out;
   out.orient = orientation;
+  set_output_all(d, out);
+  return JB_OK;
+}
+
+extern "C" int jb_batch_decoder_set_draft(jb_batch_decoder *d, int denom) {
+  if (!d) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_set_draft: decoder is NULL");
+  if (denom != 1 && denom != 2 && denom != 4 && denom != 8) return jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_batch_decoder_set_draft: denom is not 1, 2, 4 or 8");
+  if (d->in_flight()) return jb_fail_(nullptr, JB_ERR_STATE, "jb_batch_decoder_set_draft: batches are in flight (collect them first)");
+  if (const char *why = jb_draft_refusal_(denom, d->out.arith, d->out.scale, d->out.orient))
+    return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, (std::string("jb_batch_decoder_set_draft: ") + why).c_str());
+  OutputRequest out = d->out;
+  out.draft = denom;
   set_output_all(d, out);
   return JB_OK;
 }

@@ -101,6 +101,9 @@ struct jb_ctx {
   // "Orientation" (include/jpegblk.h): JB_ORIENT_* or 2..8, what the plans of this context's later calls are made for
   // (jb_plan.h: the plan carries the value to the launch).  Its intermediates live in `tmp`.
   int orientation = JB_ORIENT_STORED;
+  // "Draft decode" (include/jpegblk.h): 1, 2, 4, 8.  Not 1: the plans of this context's later calls are made for the
+  // draft frame (jb_draft_desc_) and its pixel launches (JB_ARITH_LIBJPEG's alone) decode that frame.
+  int draft = 1;
 };
 
 // the error text of a failed call, formatted: into the context (ctx may be null) and the calling thread (jb_fail_)

@@ -433,6 +433,10 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
   if (denom != 1 && denom != 2 && denom != 4 && denom != 8) return jb_fail_(ctx, JB_ERR_GEOMETRY, "jb_decode_memory_scaled: denom is not 1, 2, 4 or 8");
   // "orientation" (include/jpegblk.h): the context's, or under JB_ORIENT_EXIF the file's own (1 when it has none)
   int orient = jb_ctx_orientation(ctx);
+  // "draft decode": the plan is that of the context's draft frame; what does not go with a draft is refused before
+  // anything is decoded
+  const int draft = jb_ctx_draft(ctx);
+  if (const char *why = jb_draft_refusal_(draft, jb_ctx_arithmetic(ctx), denom, orient)) return jb_fail_(ctx, JB_ERR_UNSUPPORTED, why);
   if (orient == JB_ORIENT_EXIF && jb_exif_orientation(jpeg, jpeg_bytes, &orient) != JB_OK) orient = JB_ORIENT_STORED;
   // The entropy stage of a baseline file can run on the device too (jb_huff.hip): the host then only
   // parses the headers and removes the byte stuffing.  One image is one latency-bound submission
@@ -459,7 +463,8 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
       if (jb_huff_prepare_(jpeg, jpeg_bytes, job.get(), nullptr, knobs.chunk_bytes) == JB_OK && jb_huff_worth_it_(*job, min_int) &&
           (forced || job->scan_len >= kAutoDeviceScan)) {
         const double t1 = timing ? jb_now_s_() : 0;
-        const JbOutPlan plan = jb_out_plan_(&job->desc, denom, spec, roi, target, nullptr, 0, orient, fit);
+        const jb_image_desc frame = jb_draft_desc_(&job->desc, draft);
+        const JbOutPlan plan = jb_out_plan_(&frame, denom, spec, roi, target, nullptr, 0, orient, fit);
         if (plan.status != JB_OK) return jb_fail_(ctx, plan.status, plan.why);
         uint8_t *out = jb_alloc_pixels_((size_t)plan.image_bytes);
         if (!out) return jb_fail_(ctx, JB_ERR_CAPACITY, "out of host memory");
@@ -486,7 +491,8 @@ static int decode_memory_impl(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_byte
   jb_geometry g;
   rc = jb_geometry_of(&desc, &g);
   if (rc) return jb_fail_(ctx, rc, "bad frame geometry");
-  const JbOutPlan plan = jb_out_plan_(&desc, denom, spec, roi, target, nullptr, 0, orient, fit);
+  const jb_image_desc frame = jb_draft_desc_(&desc, draft);
+  const JbOutPlan plan = jb_out_plan_(&frame, denom, spec, roi, target, nullptr, 0, orient, fit);
   if (plan.status != JB_OK) return jb_fail_(ctx, plan.status, plan.why);
   // the staging ring follows the frame (a context sized for another image, or created with (0,0))
   rc = jb_ctx_reserve(ctx, (size_t)g.coef_bytes, (size_t)plan.image_bytes);

@@ -44,6 +44,25 @@ int jb_scaled_size(int32_t width, int32_t height, int denom, int32_t *out_w, int
   return JB_OK;
 }
 
+// "draft decode": jdmaster.c's block sizes and what is left to jdsample.c
+int jb_draft_geometry_of(const jb_image_desc *d, int denom, jb_draft_geometry *out) {
+  if (!d || !out) return JB_ERR_NULL;
+  jb_geometry g;
+  const int rc = jb_geometry_of(d, &g);
+  if (rc) return rc;
+  if (denom != 1 && denom != 2 && denom != 4 && denom != 8) return JB_ERR_GEOMETRY;
+  memset(out, 0, sizeof *out);
+  const int s = 8 / denom;
+  int sc = s;
+  while (sc < 8 && (d->hs * s) % (2 * sc) == 0 && (d->vs * s) % (2 * sc) == 0) sc *= 2;
+  out->width = (d->width + denom - 1) / denom;
+  out->height = (d->height + denom - 1) / denom;
+  out->luma_block = s, out->chroma_block = sc;
+  out->up_h = d->hs * s / sc, out->up_v = d->vs * s / sc;
+  out->fancy = s > 1 ? 1 : 0;
+  return JB_OK;
+}
+
 // bytes per element of an output format (0: not a format)
 static int jb_format_esize_(int format) {
   return format == JB_FMT_RGB_U8_HWC || format == JB_FMT_RGB_U8_CHW ? 1 : format == JB_FMT_RGB_F32_CHW ? 4 : format == JB_FMT_RGB_F16_CHW ? 2 : 0;
@@ -203,6 +222,23 @@ int jb_resolve_qtabs(const jb_image_desc *d, const uint16_t *qtabs, int32_t *out
 }
 
 }  // extern "C"
+
+jb_image_desc jb_draft_desc_(const jb_image_desc *d, int denom) {
+  jb_image_desc draft = *d;
+  if (denom == 2 || denom == 4 || denom == 8) {
+    draft.width = (d->width + denom - 1) / denom;
+    draft.height = (d->height + denom - 1) / denom;
+  }
+  return draft;
+}
+
+const char *jb_draft_refusal_(int draft, int arith, int scale, int orientation) {
+  if (draft == 1) return nullptr;
+  if (arith != JB_ARITH_LIBJPEG) return kJbDraftArithText;
+  if (scale != 1) return kJbDraftScaleText;
+  if (orientation != JB_ORIENT_STORED) return kJbDraftOrientText;
+  return nullptr;
+}
 
 jb_roi jb_filter_window_of_(const jb_image_desc *d, const jb_roi *roi, int32_t out_w, int32_t out_h, int filter) {
   const jb_roi whole = {0, 0, d->width, d->height};

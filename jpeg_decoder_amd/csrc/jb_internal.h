@@ -26,6 +26,8 @@ void jb_ctx_set_download_age_(jb_ctx *ctx, uint64_t age);
 // "decoder arithmetic": the context's setting without jb_ctx_set_arithmetic's look at the ring (jb_batch.cpp sets it
 // between its own runs, when the slots' busy marks are stale and nothing is in flight)
 void jb_ctx_set_arithmetic_(jb_ctx *ctx, int arith);
+// "draft decode": the same for the context's draft
+void jb_ctx_set_draft_(jb_ctx *ctx, int denom);
 #define kJbArithScaleText "JB_ARITH_LIBJPEG cannot be combined with a scale other than 1"
 // JB_OK when [p, p + bytes) is device memory of `device` (jb_batch_decoder_set_device_output: a host pointer or
 // another GPU's memory would fault in the pixel kernel instead of failing here)

@@ -90,17 +90,20 @@ struct JbLjWindow {
   int32_t mx, my, nx, ny;  // first MCU, MCUs per row and per column
   int64_t bytes;           // of one image's three planes (a multiple of 256)
 };
+// "Draft decode" (include/jpegblk.h): `draft` (1, 2, 4, 8) makes p.width x p.height, the rectangles and the windows those
+// of the DRAFT FRAME -- an MCU is 8 hs / draft by 8 vs / draft of its pixels, the planes hold the reduced IDCTs' blocks, and
+// the halo is kept only where the upsampler still filters; p.mcus_x, p.mcus_y, hs and vs stay the coded frame's.
 // the window of the rectangle (x, y, w, h) of a frame of mcus_x x mcus_y MCUs
-JbLjWindow jbk_lj_window(int hs, int vs, int mcus_x, int mcus_y, int x, int y, int w, int h);
+JbLjWindow jbk_lj_window(int hs, int vs, int draft, int mcus_x, int mcus_y, int x, int y, int w, int h);
 // workgroups of the pixel kernel per image of a w x h output (256 pixels x 4 rows each); 0: more than 2^31 - 1
 int jbk_lj_tiles(int w, int h);
 // Formats 0-3, the whole image or (p.roi = 1) the rectangle p.roi_*: p.tiles_per_image = jbk_lj_tiles of the output,
 // p.n_tiles = images * p.tiles_per_image; p.linear, p.small_grid, p.staged, p.fast_store and p.tiles_per_row are not
 // looked at.  planes: device scratch of images * jbk_lj_window(...).bytes, the launch's alone until it has run.
-hipError_t jbk_lj_launch(const JbLaunch &p, int hs, int vs, void *planes, hipStream_t stream);
+hipError_t jbk_lj_launch(const JbLaunch &p, int hs, int vs, int draft, void *planes, hipStream_t stream);
 // p.roi = 2: a rectangle per image as for jbk_launch_crops (format 0; of a table row x, y, w, h and tmp_offset are
 // looked at); p.tiles_per_image = the largest jbk_lj_tiles of the rectangles.  planes: the sum of the images' windows.
-hipError_t jbk_lj_launch_crops(const JbLaunch &p, const JbCropTable &table, int hs, int vs, void *planes, hipStream_t stream);
+hipError_t jbk_lj_launch_crops(const JbLaunch &p, const JbCropTable &table, int hs, int vs, int draft, void *planes, hipStream_t stream);
 
 // "Fixed output size" (jb_resample.hip): n_images tight interleaved uint8 images of iw x ih at src (src_image_stride bytes
 // apart, at least 4 readable bytes behind the last one) -> their exact area resize to ow x oh at dst, in `format`

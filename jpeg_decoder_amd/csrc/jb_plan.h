@@ -106,6 +106,15 @@ jb_fit_geometry jb_fit_geometry_of_(const jb_roi &source, int32_t w, int32_t h, 
 // checks per-image rectangles.  views may be null when there are none.
 JbOutPlan jb_views_plan_(const jb_image_desc *desc, const jb_output_spec *spec, const jb_view *views, int n_images, int views_per_image,
                          const jb_resize *rs, int orientation = 1);
+// "draft decode" (include/jpegblk.h): the descriptor a plan under draft `denom` (1, 2, 4, 8) is made from -- desc with
+// the DRAFT FRAME's width and height; everything that addresses coefficients keeps the true descriptor.  denom 1: desc.
+jb_image_desc jb_draft_desc_(const jb_image_desc *desc, int denom);
+// why a draft other than 1 does not go with this arithmetic (JB_ARITH_*), scale and orientation: the text of the
+// JB_ERR_UNSUPPORTED refusal, or null when it does (draft 1: always)
+const char *jb_draft_refusal_(int draft, int arith, int scale, int orientation);
+#define kJbDraftArithText "a draft other than 1 needs JB_ARITH_LIBJPEG"
+#define kJbDraftScaleText "a draft other than 1 cannot be combined with a scale other than 1"
+#define kJbDraftOrientText "a draft other than 1 cannot be combined with an orientation other than JB_ORIENT_STORED"
 // "orientation": the refusal of a plan with orient == 0 at a launch, and of a scale with an orientation
 #define kJbOrientExifText "JB_ORIENT_EXIF takes the orientation from a file: this entry point has none (set 1..8)"
 #define kJbOrientScaleText "an orientation other than 1 cannot be combined with a scale other than 1"

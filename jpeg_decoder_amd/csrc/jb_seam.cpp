@@ -32,6 +32,9 @@ int seam_check(jb_ctx *ctx, const jb_device_batch *b, const JbOutPlan &plan, con
   int rc = check_desc(ctx, &b->desc, g);
   if (rc) return rc;
   if (b->n_images < 1) return fail(ctx, JB_ERR_GEOMETRY, "n_images = %d", b->n_images);
+  // "draft decode": the plan is the draft frame's, which exists only where the draft goes with everything else
+  if (const char *why = jb_draft_refusal_(ctx->draft, ctx->arithmetic, plan.scale ? plan.scale : 1, plan.orient == JB_ORIENT_STORED ? ctx->orientation : plan.orient))
+    return fail(ctx, JB_ERR_UNSUPPORTED, "%s: %s", fn, why);
   if (plan.status != JB_OK) return fail(ctx, plan.status, "%s: %s", fn, plan.why);
   if (ctx->arithmetic == JB_ARITH_LIBJPEG && plan.scale != 1) return fail(ctx, JB_ERR_UNSUPPORTED, "%s: %s", fn, kJbArithScaleText);
   if (plan.orient == JB_ORIENT_EXIF) return fail(ctx, JB_ERR_STATE, "%s: %s", fn, kJbOrientExifText);
@@ -120,7 +123,16 @@ int seam_tiles(jb_ctx *ctx, const jb_device_batch *b, const jb_geometry &g, cons
   return JB_OK;
 }
 
-// the launch's pointers, strides and frame fields (everything but the tiling and the store-stage knobs)
+// "draft decode": the batch as plans, windows, the resample and filter launches and the pixel kernel's frame fields see
+// it -- with the context's DRAFT FRAME; the coefficients keep b's own descriptor and geometry.  Draft 1: b.
+jb_device_batch frame_batch(const jb_ctx *ctx, const jb_device_batch *b) {
+  jb_device_batch fb = *b;
+  fb.desc = jb_draft_desc_(&b->desc, ctx->draft);
+  return fb;
+}
+
+// the launch's pointers, strides and frame fields (everything but the tiling and the store-stage knobs); b: with the
+// frame the pixels are those of (frame_batch)
 JbLaunch launch_base(const jb_device_batch *b, const jb_geometry &g) {
   JbLaunch p;
   memset(&p, 0, sizeof p);
@@ -169,8 +181,8 @@ int scratch_for_stream(jb_ctx *ctx, std::map<hipStream_t, jb_ctx::Tmp> &pool, hi
 int tmp_for_stream(jb_ctx *ctx, hipStream_t stream, size_t bytes, void **out) { return scratch_for_stream(ctx, ctx->tmp, stream, bytes, out); }
 
 // the MCU window (jb_kernels.h) of a rectangle of the batch's frame under JB_ARITH_LIBJPEG: what its planes take
-JbLjWindow lj_window(const jb_device_batch *b, const jb_geometry &g, const jb_roi &r) {
-  return jbk_lj_window(b->desc.hs, b->desc.vs, g.mcus_x, g.mcus_y, r.x, r.y, r.width, r.height);
+JbLjWindow lj_window(const jb_ctx *ctx, const jb_device_batch *b, const jb_geometry &g, const jb_roi &r) {
+  return jbk_lj_window(b->desc.hs, b->desc.vs, ctx->draft, g.mcus_x, g.mcus_y, r.x, r.y, r.width, r.height);
 }
 
 // "fit": the resample and filter kernels produce plan.inner of every output -- its size is their ow x oh, and dst is moved
@@ -241,9 +253,10 @@ JbFilterRow filter_row(const jb_roi &r, const jb_roi &win, int64_t tmp_offset) {
   return JbFilterRow{r.x, r.y, r.width, r.height, win.x, win.y, win.width, win.height, tmp_offset};
 }
 
-// "orientation": the batch as the resample and filter launches see it -- the oriented frame; everything else is b's
-jb_device_batch oriented_batch(const jb_device_batch *b, int orientation) {
-  jb_device_batch ob = *b;
+// "orientation": the batch as the resample and filter launches see it -- the oriented frame (of the draft frame: the two
+// never come together, seam_check has refused); everything else is b's
+jb_device_batch oriented_batch(const jb_ctx *ctx, const jb_device_batch *b, int orientation) {
+  jb_device_batch ob = frame_batch(ctx, b);
   if (jb_orient_bits(orientation).transpose) ob.desc.width = b->desc.height, ob.desc.height = b->desc.width;
   return ob;
 }
@@ -280,7 +293,7 @@ int rects_into_scratch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int 
   const auto bytes_of = [&](int64_t i) { return image_bytes(i) * (oriented ? 2 : 1); };  // (the cap counts both regions)
   // JB_ARITH_LIBJPEG: the planes of every image's window are held to the same cap, in a scratch of their own
   const bool lj = ctx->arithmetic == JB_ARITH_LIBJPEG;
-  const auto planes_of = [&](int64_t i) { return lj ? lj_window(b, g, written[i]).bytes : 0; };
+  const auto planes_of = [&](int64_t i) { return lj ? lj_window(ctx, b, g, written[i]).bytes : 0; };
   // the images of the sub-batch that starts at i0; *bytes: their intermediates; *planes: their planes
   const auto pack = [&](int64_t i0, int64_t *bytes, int64_t *planes) {
     int m = 1;
@@ -328,7 +341,7 @@ int rects_into_scratch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int 
       if (c.n_tiles > most_tiles) most_tiles = c.n_tiles;
       if (jbk_lj_tiles(c.w, c.h) > most_lj_tiles) most_lj_tiles = jbk_lj_tiles(c.w, c.h);
     }
-    jb_device_batch ib = *b;
+    jb_device_batch ib = frame_batch(ctx, b);
     ib.d_coef = (const int16_t *)((const uint8_t *)b->d_coef + i0 * coef_step);
     ib.coef_image_stride = coef_step;
     ib.d_qtabs = (const int32_t *)((const uint8_t *)b->d_qtabs + i0 * b->qtab_image_stride);
@@ -342,7 +355,7 @@ int rects_into_scratch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int 
     if (lj) {
       p.tiles_per_image = most_lj_tiles;  // (the tiles of jb_libjpeg.hip's pixel kernel: 256 pixels x 4 rows of the rectangle)
       p.n_tiles = m * most_lj_tiles;
-      JB_HIP(ctx, jbk_lj_launch_crops(p, table, b->desc.hs, b->desc.vs, planes_d, s));
+      JB_HIP(ctx, jbk_lj_launch_crops(p, table, b->desc.hs, b->desc.vs, ctx->draft, planes_d, s));
     } else {
       JB_HIP(ctx, jbk_launch_crops(p, table, b->desc.hs, b->desc.vs, s));
     }
@@ -372,7 +385,7 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
                       int64_t plane_stride) {
   if (plan.n_crops != b->n_images) return fail(ctx, JB_ERR_GEOMETRY, "%s: %d rectangles for %d images", fn, plan.n_crops, b->n_images);
   // the plan's rectangles and windows are the oriented frame's (ob: the batch with that frame)
-  const jb_device_batch ob = oriented_batch(b, plan.orient);
+  const jb_device_batch ob = oriented_batch(ctx, b, plan.orient);
   std::vector<jb_roi> windows;  // what the pixel kernel writes of every image: with a filter, not the rectangle
   if (plan.filter)
     for (int64_t i = 0; i < b->n_images; i++)
@@ -410,7 +423,7 @@ int seam_launch_views(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
     rc = seam_check(ctx, &outputs, plan, fn, &g, &plane_stride);
     if (rc) return rc;
   }
-  const jb_device_batch ob = oriented_batch(b, plan.orient);
+  const jb_device_batch ob = oriented_batch(ctx, b, plan.orient);
   // every image's union of its views' sources -- a view's rectangle, with a filter its window
   std::vector<jb_roi> unions;
   for (int64_t i = 0; i < b->n_images; i++) {
@@ -466,7 +479,8 @@ int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, con
   if (rc) return rc;
   if (plan.crops) return seam_launch_crops(ctx, b, stream, plan, fn, g, plane_stride);
   // (with a filter other than 0 the source is the window: the ROI store stage with the window in the rectangle's place)
-  const JbOutPlan inner = jb_out_plan_(&b->desc, 1, nullptr, plan.filter ? &plan.window : plan.has_roi ? &plan.roi : nullptr);
+  const jb_device_batch fb = frame_batch(ctx, b);  // ("draft decode": the source is the draft frame)
+  const JbOutPlan inner = jb_out_plan_(&fb.desc, 1, nullptr, plan.filter ? &plan.window : plan.has_roi ? &plan.roi : nullptr);
   if (inner.status != JB_OK) return fail(ctx, inner.status, "%s: %s", fn, inner.why);
   // whole images per sub-batch: as many as the cap holds, one at the least
   const int64_t cap = (int64_t)ctx->knobs.resize_tmp_bytes;
@@ -495,8 +509,8 @@ int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, con
     rc = seam_launch(ctx, &ib, s, inner, fn);
     if (rc) return rc;
     if (plan.filter) {
-      JbFilter f = filter_args(b, plan, plane_stride, tmp, i0, m);
-      const jb_roi whole = {0, 0, b->desc.width, b->desc.height};
+      JbFilter f = filter_args(&fb, plan, plane_stride, tmp, i0, m);
+      const jb_roi whole = {0, 0, fb.desc.width, fb.desc.height};
       f.one = filter_row(plan.has_roi ? plan.roi : whole, plan.window, 0);
       JB_HIP(ctx, jbk_filter_launch(f, plan.filter, plan.format, s));
     } else {
@@ -521,7 +535,7 @@ int seam_launch_oriented(jb_ctx *ctx, const jb_device_batch *b, void *stream, co
   int rc = seam_check(ctx, b, plan, fn, &g, &plane_stride);
   if (rc) return rc;
   if (plan.crops) return seam_launch_crops(ctx, b, stream, plan, fn, g, plane_stride);
-  const jb_device_batch ob = oriented_batch(b, plan.orient);
+  const jb_device_batch ob = oriented_batch(ctx, b, plan.orient);
   const jb_roi whole = {0, 0, ob.desc.width, ob.desc.height};
   const jb_roi shown = plan.filter ? plan.window : plan.has_roi ? plan.roi : whole;
   const jb_roi stored = stored_rect(b, plan.orient, shown);
@@ -594,11 +608,11 @@ int seam_launch_oriented(jb_ctx *ctx, const jb_device_batch *b, void *stream, co
 // cap of the resized routes' scratch (one image at the least), in the stream's scratch of their own.  p: launch_base's,
 // with the planar fields set.
 int seam_launch_lj(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const jb_geometry &g, JbLaunch p) {
-  const jb_roi whole = {0, 0, b->desc.width, b->desc.height};
+  const jb_roi whole = {0, 0, p.width, p.height};  // (launch_base: the draft frame)
   const jb_roi &r = plan.has_roi ? plan.roi : whole;
   if (plan.has_roi) p.roi = 1, p.roi_x = r.x, p.roi_y = r.y, p.roi_w = r.width, p.roi_h = r.height;
   p.tiles_per_image = jbk_lj_tiles(r.width, r.height);
-  const JbLjWindow win = lj_window(b, g, r);
+  const JbLjWindow win = lj_window(ctx, b, g, r);
   int64_t per = (int64_t)ctx->knobs.resize_tmp_bytes / win.bytes;
   if (per < 1) per = 1;
   if (per > b->n_images) per = b->n_images;
@@ -618,7 +632,7 @@ int seam_launch_lj(jb_ctx *ctx, const jb_device_batch *b, void *stream, const Jb
     q.rgb = b->d_rgb + i0 * rgb_step;
     q.rgb_image_stride = rgb_step;
     q.n_tiles = (int32_t)(m * p.tiles_per_image);
-    JB_HIP(ctx, jbk_lj_launch(q, b->desc.hs, b->desc.vs, planes, s));
+    JB_HIP(ctx, jbk_lj_launch(q, b->desc.hs, b->desc.vs, ctx->draft, planes, s));
   }
   return JB_OK;
 }
@@ -634,7 +648,8 @@ int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOut
   int64_t plane_stride = 0;
   int rc = seam_check(ctx, b, plan, fn, &g, &plane_stride);
   if (rc) return rc;
-  JbLaunch p = launch_base(b, g);
+  const jb_device_batch fb = frame_batch(ctx, b);
+  JbLaunch p = launch_base(&fb, g);
   if (plan.planar) {
     p.format = plan.format;
     p.rgb_plane_stride = plane_stride;
@@ -651,7 +666,10 @@ int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOut
 // the plan of a seam entry point: of b's frame under the context's orientation
 static JbOutPlan seam_plan(const jb_ctx *ctx, const jb_device_batch *b, int scale, const jb_output_spec *spec, const jb_roi *roi = nullptr,
                            const JbTarget *target = nullptr, const jb_roi *crops = nullptr, int n_crops = 0, const jb_fit *fit = nullptr) {
-  return jb_out_plan_(b ? &b->desc : nullptr, scale, spec, roi, target, crops, n_crops, ctx ? ctx->orientation : JB_ORIENT_STORED, fit);
+  // ("draft decode": of the context's draft frame)
+  jb_image_desc frame = {};
+  if (b) frame = jb_draft_desc_(&b->desc, ctx ? ctx->draft : 1);
+  return jb_out_plan_(b ? &frame : nullptr, scale, spec, roi, target, crops, n_crops, ctx ? ctx->orientation : JB_ORIENT_STORED, fit);
 }
 
 extern "C" {
@@ -718,7 +736,8 @@ int jb_blocks_to_rgb_device_views(jb_ctx *ctx, const jb_device_batch *b, const j
                                   const jb_output_spec *spec, void *stream) {
   if (ctx && (!views || !rs)) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_views: NULL pointer");
   if (!ctx || !b) return seam_launch(ctx, b, stream, seam_plan(ctx, b, 1, spec), "jb_blocks_to_rgb_device_views");  // (JB_ERR_NULL)
-  return seam_launch(ctx, b, stream, jb_views_plan_(&b->desc, spec, views, b->n_images < 0 ? 0 : b->n_images, views_per_image, rs, ctx->orientation),
+  const jb_image_desc frame = jb_draft_desc_(&b->desc, ctx->draft);
+  return seam_launch(ctx, b, stream, jb_views_plan_(&frame, spec, views, b->n_images < 0 ? 0 : b->n_images, views_per_image, rs, ctx->orientation),
                      "jb_blocks_to_rgb_device_views");
 }
 

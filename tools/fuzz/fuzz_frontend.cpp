@@ -46,6 +46,8 @@ void *jb_pinned_alloc_on(int, size_t n) { return malloc(n); }
 int jb_ctx_reserve(jb_ctx *, size_t, size_t) { return JB_OK; }
 int jb_ctx_device(const jb_ctx *) { return 0; }
 int jb_ctx_orientation(const jb_ctx *) { return JB_ORIENT_EXIF; }  // (every mutant goes through the Exif parser too)
+int jb_ctx_arithmetic(const jb_ctx *) { return JB_ARITH_REFERENCE; }
+int jb_ctx_draft(const jb_ctx *) { return 1; }
 void jb_pinned_free(void *p) { free(p); }
 int jb_device_numa_node(int) { return JB_ERR_STATE; }
 }
