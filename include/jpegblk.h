@@ -488,6 +488,57 @@ int jb_views_check(const jb_image_desc *desc, const jb_view *views, int n_images
 int jb_blocks_to_rgb_device_views(jb_ctx *ctx, const jb_device_batch *batch, const jb_view *views, int views_per_image,
                                   const jb_resize *rs, const jb_output_spec *spec, void *stream);
 
+/* ---- view groups: several output sizes per image from one decode ----
+ * The multi-crop pipelines (DINO, DINOv2, iBOT, SwAV: 2 "global" crops at 224 x 224 and 6-10 "local" crops at 96 x 96 of the
+ * same file), "the training crop and a thumbnail" and "one crop at three resolutions" in one call.  A call has G = n_groups
+ * in 1..4 (JB_VIEW_GROUPS_MAX).  Group g has its own jb_resize -- target and filter; the filters of the groups may differ --
+ * and a count K_g >= 1; K = the sum of the K_g lies in 1..JB_VIEWS_MAX.  The HOST array holds n_images * K views,
+ * image-major, and within an image group-major: with s_g = the sum of K_h over h < g, the views [i * K + s_g, i * K + s_g +
+ * K_g) are group g's of image i.
+ * DEFINITION: group g's outputs are what jb_blocks_to_rgb_device_views writes for the same batch with group g's views
+ * alone (views_per_image = K_g) and groups[g].rs -- bit for bit, in every format 0-3, under either arithmetic, any
+ * orientation of the context and any draft.  No new arithmetic; the mirror stays last; G = 1 is "views".
+ * ONE DECODE: per image the pixel kernel writes ONE union -- the bounding rectangle of all K source rectangles, each taken
+ * under its own group's resize (with a filter: jb_filter_window at that group's target).  Sub-batches pack images while
+ * their unions fit JPEGBLK_RESIZE_TMP_BYTES, at most 32 images each, as for views; per sub-batch every group then takes
+ * ceil(images * K_g / 32) resample or filter launches.
+ * A jb_view_output says where group g's outputs go: output (i, v) of the group -- v in 0..K_g-1 -- lies at d_out +
+ * i * image_stride + v * view_stride, its rows row_stride apart and, for the planar formats, its planes plane_stride apart
+ * (0: tight, row_stride * out_h).  The groups' buffers may be one allocation (the batch decoder's layout below) or
+ * separate ones; overlap between different groups' outputs is the caller's business. */
+enum { JB_VIEW_GROUPS_MAX = 4 };
+typedef struct jb_view_group {
+  jb_resize rs;     /* the group's target and filter */
+  int32_t n_views;  /* K_g >= 1 */
+  int32_t reserved; /* 0 */
+} jb_view_group;    /* 24 bytes */
+typedef struct jb_view_output {
+  void *d_out;      /* device */
+  int64_t image_stride, view_stride, row_stride, plane_stride; /* bytes */
+} jb_view_output;   /* 40 bytes */
+/* Can the call be had?  The first failing check in this order decides: NULLs (descriptor, groups, the array when n_images
+ * > 0) JB_ERR_NULL; the descriptor's own errors; JB_ERR_GEOMETRY with *bad_index = -1 for n_images < 0, n_groups outside
+ * 1..4, a group with n_views < 1 or reserved != 0, K > 16; every view in flat order -- flags and reserved, then the
+ * rectangles -- JB_ERR_GEOMETRY with the flat index i * K + v in *bad_index (may be NULL); then every group in order what
+ * jb_views_check answers for that group's views with its rs: no target JB_ERR_STATE, the target's and the filter's
+ * statuses (the tap cap: *bad_index names the view's flat index in the caller's array).  With G = 1 status and
+ * *bad_index are jb_views_check's.  Pure host code. */
+int jb_view_groups_check(const jb_image_desc *desc, const jb_view *views, int n_images, const jb_view_group *groups, int n_groups,
+                         int *bad_index);
+/* The tight layout of one image's block: group 0's K_0 outputs, then group 1's, ..., each output jb_output_bytes of its
+ * target in `format`.  group_offsets (may be NULL; n_groups entries): where group g starts; *image_bytes: the block.
+ * JB_ERR_NULL, JB_ERR_GEOMETRY for the counts as above, a target outside 1..65535 or an unknown format.  Pure host code. */
+int jb_view_groups_bytes(const jb_view_group *groups, int n_groups, int format, int64_t *group_offsets, int64_t *image_bytes);
+/* jb_blocks_to_rgb_device_views with groups: outputs[g] describes group g's buffer; batch->d_rgb and its three rgb
+ * strides are NOT READ, and spec->plane_stride must be 0 (the planes' stride is the output's own; anything else is
+ * JB_ERR_GEOMETRY).  Per group the strides are checked as those of a batch are: row_stride against the width,
+ * plane_stride against the rows, view_stride when K_g > 1 against one output, image_stride when n_images > 1 against the
+ * image's K_g outputs; the float formats want pointer and strides to be multiples of the element size.  Any refusal
+ * launches nothing and writes nothing.  JB_ORIENT_EXIF on the context: JB_ERR_STATE.  The arrays are read before the call
+ * returns.  views, groups or outputs == NULL: JB_ERR_NULL.  spec == NULL: interleaved uint8. */
+int jb_blocks_to_rgb_device_view_groups(jb_ctx *ctx, const jb_device_batch *batch, const jb_view *views, const jb_view_group *groups,
+                                        const jb_view_output *outputs, int n_groups, const jb_output_spec *spec, void *stream);
+
 /* ---- fit: aspect-preserving targets -- letterbox (pad) and centred crop (cover) ----
  * Every route above that gives a batch one output size STRETCHES its source to the target.  A jb_fit next to the
  * jb_resize says what else to do with a source whose aspect ratio is not the target's.  The SOURCE is the launch's
@@ -897,6 +948,20 @@ int jb_batch_decoder_run_views(jb_batch_decoder *dec, const char *const *paths, 
                                uint8_t **rgb, int32_t *widths, int32_t *heights, int *statuses, double *times);
 int jb_batch_decoder_submit_views(jb_batch_decoder *dec, const char *const *paths, int n_paths, const jb_view *views, int views_per_image,
                                   uint8_t **rgb, int32_t *widths, int32_t *heights, int *statuses, int *ticket);
+/* _run_views / _submit_views with groups (see "view groups" above): views[i * K + s_g + v] is view v of group g of
+ * paths[i].  rgb[i] is the file's BLOCK in the jb_view_groups_bytes layout -- a malloc'ed block, a piece of the arena or a
+ * device region alike --, widths[i] / heights[i] report group 0's target, statuses[i] the file's.  The decoder's own target
+ * size and filter are not read (none need be set).  The file stays the unit as for views, with the block as its size.
+ * A file one of whose views does not fit gets JB_ERR_GEOMETRY and the batch goes on.  The entropy stage runs once per
+ * file.  Refused with JB_ERR_UNSUPPORTED while the scale is not 1, a decoder-wide rectangle or a fit other than
+ * JB_FIT_STRETCH is set; with JB_ERR_GEOMETRY for counts jb_view_groups_check refuses; views or groups == NULL:
+ * JB_ERR_NULL.  _submit_view_groups copies both arrays. */
+int jb_batch_decoder_run_view_groups(jb_batch_decoder *dec, const char *const *paths, int n_paths, const jb_view *views,
+                                     const jb_view_group *groups, int n_groups, uint8_t **rgb, int32_t *widths, int32_t *heights,
+                                     int *statuses, double *times);
+int jb_batch_decoder_submit_view_groups(jb_batch_decoder *dec, const char *const *paths, int n_paths, const jb_view *views,
+                                        const jb_view_group *groups, int n_groups, uint8_t **rgb, int32_t *widths, int32_t *heights,
+                                        int *statuses, int *ticket);
 /* The filter (JB_FILTER_*; see "resampling filters") of the batch decoder's later runs and submissions: it governs the
  * target size of jb_batch_decoder_set_resize and the per-image rectangles of _run_crops / _submit_crops alike, and is
  * kept while no target size is set (there is then nothing to resample).  A file whose reduction exceeds the tap cap gets

@@ -14,10 +14,10 @@ from .api import (JbError, Context, ImageDesc, Geometry, DeviceBatch, lib, lib_p
                   FMT_DTYPE, Roi, roi_check, resize_check, crops_check, Resize, filter_check, filter_window,
                   FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC, ARITH_REFERENCE, ARITH_LIBJPEG,
                   ORIENT_EXIF, ORIENT_STORED, exif_orientation, oriented_size, orient_map_roi,
-                  View, VIEW_MIRROR, VIEWS_MAX, views_check,
+                  View, VIEW_MIRROR, VIEWS_MAX, views_check, ViewGroup, ViewOutput, VIEW_GROUPS_MAX, view_groups_check, view_groups_bytes,
                   Fit, FitGeometry, fit_geometry, FIT_STRETCH, FIT_PAD, FIT_COVER, FIT_CENTER, FIT_START, FIT_END,
                   DraftGeometry, draft_geometry)
-from .crops import random_resized_crop, random_views
+from .crops import random_resized_crop, random_views, random_multicrop
 
 __all__ = ["JbError", "Context", "ImageDesc", "Geometry", "DeviceBatch", "lib", "lib_path",
            "make_desc", "geometry_of", "resolve_qtabs", "entropy_decode", "decode_batch", "BatchDecoder", "build_library",
@@ -25,6 +25,7 @@ __all__ = ["JbError", "Context", "ImageDesc", "Geometry", "DeviceBatch", "lib", 
            "FMT_RGB_F16_CHW", "FMT_DTYPE", "Roi", "roi_check", "resize_check", "crops_check",
            "random_resized_crop", "Resize", "filter_check", "filter_window", "FILTER_AREA", "FILTER_BILINEAR", "FILTER_BICUBIC",
            "ARITH_REFERENCE", "ARITH_LIBJPEG", "ORIENT_EXIF", "ORIENT_STORED", "exif_orientation", "oriented_size",
-           "orient_map_roi", "View", "VIEW_MIRROR", "VIEWS_MAX", "views_check", "random_views",
+           "orient_map_roi", "View", "VIEW_MIRROR", "VIEWS_MAX", "views_check", "random_views", "ViewGroup", "ViewOutput", "VIEW_GROUPS_MAX", "view_groups_check", "view_groups_bytes",
+           "random_multicrop",
            "Fit", "FitGeometry", "fit_geometry", "FIT_STRETCH", "FIT_PAD", "FIT_COVER", "FIT_CENTER", "FIT_START", "FIT_END",
            "DraftGeometry", "draft_geometry"]

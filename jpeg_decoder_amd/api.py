@@ -103,6 +103,41 @@ class View(ctypes.Structure):
                 ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+VIEW_GROUPS_MAX = 4
+
+
+class ViewGroup(ctypes.Structure):
+    """jb_view_group ("view groups"): n_views views per image under one target size and filter."""
+    _fields_ = [("rs", Resize), ("n_views", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class ViewOutput(ctypes.Structure):
+    """jb_view_output: where a group's outputs go -- output (i, v) at d_out + i * image_stride + v * view_stride, rows
+    row_stride apart, the planes of a planar format plane_stride apart (0: tight)."""
+    _fields_ = [("d_out", ctypes.c_void_p), ("image_stride", ctypes.c_int64), ("view_stride", ctypes.c_int64),
+                ("row_stride", ctypes.c_int64), ("plane_stride", ctypes.c_int64)]
+
+
+def _group_array(view_groups):
+    """[(k, (w, h)[, filter]) or ViewGroup, ... G] -> (a ctypes array of G jb_view_group, at least one element long, G)."""
+    gs = []
+    for g in view_groups:
+        if not isinstance(g, ViewGroup):
+            g = tuple(g)
+            g = ViewGroup(Resize(int(g[1][0]), int(g[1][1]), int(g[2]) if len(g) > 2 else FILTER_AREA, 0), int(g[0]), 0)
+        gs.append(g)
+    return (ViewGroup * max(len(gs), 1))(*gs), len(gs)
+
+
+def _output_array(view_outputs, n_groups):
+    """[(d_out, image_stride, view_stride, row_stride[, plane_stride]) or ViewOutput, ... G] -> a ctypes array of jb_view_output;
+    another count than the groups': JbError(-2)."""
+    outs = [o if isinstance(o, ViewOutput) else ViewOutput(*([int(v) for v in o] + [0] * (5 - len(o)))) for o in view_outputs]
+    if len(outs) != n_groups:
+        raise JbError(-2, f"{len(outs)} view outputs for {n_groups} groups")
+    return (ViewOutput * max(len(outs), 1))(*outs)
+
+
 # "fit" (include/jpegblk.h): what a target size does with a source of another aspect ratio -- stretch it (the default), scale
 # it to fit inside and fill the rest (letterbox), or cut the largest centred rectangle of the target's aspect ratio
 FIT_STRETCH, FIT_PAD, FIT_COVER = 0, 1, 2
@@ -195,9 +230,22 @@ class _Request:
     None; .n_view_rows images of .views_per_image each): with a scale, roi or crops JbError(-9), without a target size
     JbError(-7), rows of unequal length JbError(-2).  fit (None / a mode number / a Fit) becomes .fit (a Fit, or None for
     FIT_STRETCH, which asks for nothing new): a mode other than FIT_STRETCH without a target size is JbError(-7), with
-    crops or views JbError(-9), behind every refusal above."""
+    crops or views JbError(-9), behind every refusal above.  view_groups ([(k, (w, h)[, filter]), ...]: "view groups") become
+    .groups (a ctypes array of ViewGroup; .n_groups) and bring their own targets and filters: with resize, a filter other
+    than FILTER_AREA, roi, crops, a scale or a fit JbError(-9), without views JbError(-7), a row of views whose length is
+    not the groups' K JbError(-2); view_outputs (the seam's jb_view_output per group) become .outputs."""
 
-    def __init__(self, scale=1, fmt=None, roi=None, resize=None, crops=None, filter=FILTER_AREA, views=None, fit=None):
+    def __init__(self, scale=1, fmt=None, roi=None, resize=None, crops=None, filter=FILTER_AREA, views=None, fit=None, view_groups=None,
+                 view_outputs=None):
+        self.groups, self.n_groups, self.outputs = None, 0, None
+        if view_groups is not None:
+            if resize is not None or int(filter) != FILTER_AREA or roi is not None or crops is not None or scale != 1 or _fit_struct(fit) is not None:
+                raise JbError(-9, "view groups bring their own targets and filters: not with resize, filter, roi, crops, a scale or a fit")
+            if views is None:
+                raise JbError(-7, "view groups want views")
+            self.groups, self.n_groups = _group_array(view_groups)
+            if view_outputs is not None:
+                self.outputs = _output_array(view_outputs, self.n_groups)
         self.scale = scale
         self.filter = int(filter)
         if self.filter != FILTER_AREA and resize is None:
@@ -230,9 +278,11 @@ class _Request:
                 raise JbError(-9, "views cannot be combined with a rectangle for every image (roi)")
             if crops is not None:
                 raise JbError(-9, "views cannot be combined with per-image rectangles (crops)")
-            if resize is None:
+            if resize is None and view_groups is None:
                 raise JbError(-7, "views want a target size (resize)")
             views = [list(r) for r in views]
+            if self.groups is not None and any(len(r) != sum(g.n_views for g in self.groups[:self.n_groups]) for r in views):
+                raise JbError(-2, "view groups: every image wants as many views as the groups count")
             self.views, self.views_per_image = _view_array(views)
             self.n_view_rows = len(views)
         self.fit = _fit_struct(fit)
@@ -252,6 +302,8 @@ class _Request:
         if self.fit is not None:
             rs = ctypes.byref(_resize_struct(self.target, self.filter))
             return "fit", (_ref(self.roi), rs, ctypes.byref(self.fit), _ref(self.spec))
+        if self.groups is not None:      # (every group brings its jb_resize)
+            return "view_groups", (self.views, self.groups, self.outputs, self.n_groups, _ref(self.spec))
         if self.views is not None:       # (takes a jb_resize: the filter needs no route of its own)
             rs = ctypes.byref(Resize(self.target[0], self.target[1], self.filter, 0))
             return "views", (self.views, self.views_per_image, rs, _ref(self.spec))
@@ -288,6 +340,8 @@ _ROUTES = {"plain": ("jb_decode_file", "jb_decode_memory", "jb_blocks_to_rgb_dev
            "crops_filtered": (None, None, "jb_blocks_to_rgb_device_crops_filtered"),
            # K views per image, each optionally mirrored, any filter
            "views": (None, None, "jb_blocks_to_rgb_device_views"),
+           # the views of an image in up to four groups, each with its own target size and filter
+           "view_groups": (None, None, "jb_blocks_to_rgb_device_view_groups"),
            # a fit other than FIT_STRETCH: letterbox or centred crop to the target, any filter
            "fit": ("jb_decode_file_fit", "jb_decode_memory_fit", "jb_blocks_to_rgb_device_fit")}
 
@@ -327,6 +381,27 @@ def views_check(desc, views, resize, filter=FILTER_AREA):
         raise JbError(rc, f"image {bad.value // k}, view {bad.value % k} cannot be had" if bad.value >= 0 else "bad target size, filter, count or descriptor")
 
 
+def view_groups_check(desc, views, view_groups):
+    """jb_view_groups_check: can the views ([[(x, y, w, h[, mirror]), ... K], ...], group-major within an image) be had in
+    the groups [(k, (w, h)[, filter]), ...]?  Raises JbError otherwise, the text naming the image and the view that is to
+    blame when one is."""
+    arr, k = _view_array(views)
+    groups, n_groups = _group_array(view_groups)
+    bad = ctypes.c_int(-1)
+    rc = lib().jb_view_groups_check(ctypes.byref(desc), arr, len(list(views)), groups, n_groups, ctypes.byref(bad))
+    if rc != JB_OK:
+        raise JbError(rc, f"image {bad.value // k}, view {bad.value % k} cannot be had" if bad.value >= 0 else "bad groups, target size, filter, count or descriptor")
+
+
+def view_groups_bytes(view_groups, fmt=FMT_RGB_U8_HWC):
+    """jb_view_groups_bytes: -> ([the byte offset of every group in a file's block], the block's bytes): group 0's outputs,
+    then group 1's, ..., tight, in format `fmt` (a format number or an OutputSpec)."""
+    groups, n_groups = _group_array(view_groups)
+    offsets, total = (ctypes.c_int64 * VIEW_GROUPS_MAX)(), ctypes.c_int64()
+    _check(lib().jb_view_groups_bytes(groups, n_groups, fmt.format if isinstance(fmt, OutputSpec) else int(fmt), offsets, ctypes.byref(total)))
+    return list(offsets[:n_groups]), total.value
+
+
 def _resize_struct(resize, filter):
     w, h = resize if resize is not None else (0, 0)
     return Resize(int(w), int(h), int(filter), 0)
@@ -358,6 +433,16 @@ def fit_geometry(width, height, resize, fit, roi=None, filter=FILTER_AREA):
     _check(lib().jb_fit_check(ctypes.byref(make_desc(int(width), int(height), 1, 1)), _ref(q.roi), ctypes.byref(_resize_struct(resize, filter)),
                               _ref(f), ctypes.byref(g)))
     return (g.src.x, g.src.y, g.src.width, g.src.height), (g.inner.x, g.inner.y, g.inner.width, g.inner.height)
+
+
+def _shape_groups(ptr, spec, shapes):
+    """"view groups": a file's block at `ptr` as a list of copy-free views, one per group: shapes = [(k, w, h), ...]."""
+    fmt = spec.format if spec is not None else FMT_RGB_U8_HWC
+    out, at = [], 0
+    for k, w, h in shapes:
+        out.append(_shape_output(ctypes.c_void_p(ptr + at), w, h, spec, k))
+        at += k * output_bytes(w, h, fmt)
+    return out
 
 
 def _shape_output(ptr, w, h, spec, k=0):
@@ -498,6 +583,12 @@ def lib():
     L.jb_blocks_to_rgb_device_views.argtypes = [vp, ctypes.POINTER(DeviceBatch), pv, ctypes.c_int, prs, ps, vp]
     L.jb_batch_decoder_run_views.argtypes = L.jb_batch_decoder_run.argtypes[:3] + [pv, ctypes.c_int] + L.jb_batch_decoder_run.argtypes[3:]
     L.jb_batch_decoder_submit_views.argtypes = L.jb_batch_decoder_submit.argtypes[:3] + [pv, ctypes.c_int] + L.jb_batch_decoder_submit.argtypes[3:]
+    pg = ctypes.POINTER(ViewGroup)
+    L.jb_view_groups_check.argtypes = [pd, pv, ctypes.c_int, pg, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    L.jb_view_groups_bytes.argtypes = [pg, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+    L.jb_blocks_to_rgb_device_view_groups.argtypes = [vp, ctypes.POINTER(DeviceBatch), pv, pg, ctypes.POINTER(ViewOutput), ctypes.c_int, ps, vp]
+    L.jb_batch_decoder_run_view_groups.argtypes = L.jb_batch_decoder_run.argtypes[:3] + [pv, pg, ctypes.c_int] + L.jb_batch_decoder_run.argtypes[3:]
+    L.jb_batch_decoder_submit_view_groups.argtypes = L.jb_batch_decoder_submit.argtypes[:3] + [pv, pg, ctypes.c_int] + L.jb_batch_decoder_submit.argtypes[3:]
     L.jb_filter_check.argtypes = [pd, pr, prs]
     L.jb_filter_window.argtypes = [pd, pr, prs, pr]
     L.jb_blocks_to_rgb_device_filtered.argtypes = [vp, ctypes.POINTER(DeviceBatch), pr, prs, ps, vp]
@@ -805,7 +896,7 @@ class Context:
 
     # -- the seam, device buffers ------------------------------------------------------------
     def blocks_to_rgb_device(self, batch, stream=None, scale=1, fmt=None, roi=None, resize=None, crops=None, filter=FILTER_AREA, views=None,
-                             fit=None):
+                             fit=None, view_groups=None, view_outputs=None):
         """scale 2, 4, 8: the batch's d_rgb and strides describe images of scaled_size(desc.width, desc.height, scale).
         fmt (an OutputSpec or a format number): planar output -- the batch's rgb_row_stride is then a plane's.
         roi=(x, y, w, h) (with any fmt, not with a scale): the batch's d_rgb and strides describe images of w x h, the
@@ -823,8 +914,14 @@ class Context:
         fit=Fit.pad(fill, anchor) / Fit.cover(anchor) / a mode number with resize=(w, h) (any fmt, roi and filter; not with crops
         or views): the source keeps its aspect ratio -- scaled to fit inside the target with the rest filled, or the largest
         centred rectangle of the target's aspect ratio resized (jb_blocks_to_rgb_device_fit).  None / FIT_STRETCH: as before.
+        view_groups=[(k, (w, h)[, filter]), ... G] with views= and view_outputs=[(d_out, image_stride, view_stride, row_stride[,
+        plane_stride]) or ViewOutput, ... G] (any fmt, whose plane_stride must be 0; not with resize, filter, roi, crops, fit or a
+        scale): the K = sum of k views of an image fall into G groups, group-major, each with its own target size and filter, all
+        from ONE pixel launch per image (jb_blocks_to_rgb_device_view_groups); batch.d_rgb and its strides are not read.
         Each is the entry point of that suffix (_ROUTES)."""
-        request = _Request(scale, fmt, roi, resize, crops, filter, views, fit)
+        request = _Request(scale, fmt, roi, resize, crops, filter, views, fit, view_groups, view_outputs)
+        if request.groups is not None and request.outputs is None:
+            raise JbError(-1, "view groups want view_outputs")
         if request.crops is not None and request.n_crops != batch.n_images:
             raise JbError(-2, f"{request.n_crops} rectangles (crops) for {batch.n_images} images")
         if request.views is not None and request.n_view_rows != batch.n_images:
@@ -865,7 +962,7 @@ def _batch_args(paths):
     """The argument arrays of one batch call over `paths`, as the ticket of BatchDecoder.submit holds them."""
     n = len(paths)
     return {"n": n, "paths": (ctypes.c_char_p * n)(*[os.fsencode(p) for p in paths]), "rgb": (ctypes.c_void_p * n)(),
-            "w": (ctypes.c_int32 * n)(), "h": (ctypes.c_int32 * n)(), "st": (ctypes.c_int * n)(), "id": ctypes.c_int(-1), "k": 0}
+            "w": (ctypes.c_int32 * n)(), "h": (ctypes.c_int32 * n)(), "st": (ctypes.c_int * n)(), "id": ctypes.c_int(-1), "k": 0, "groups": None}
 
 
 def _batch_times(times, rc):
@@ -874,11 +971,12 @@ def _batch_times(times, rc):
             "error": lib().jb_last_error(None).decode(errors="replace") if rc else ""}
 
 
-def _harvest(n, rgb, w, h, st, fmt, keep_pixels, on_image, arena, device_out, k=0):
+def _harvest(n, rgb, w, h, st, fmt, keep_pixels, on_image, arena, device_out, k=0, groups=None):
     """The results of a finished batch, without the times: (device pointers (int, 0 = failed), (width, height) per image,
     statuses) with device output, else (arrays / (width, height) without keep_pixels / None = failed, statuses).  Host
     images cost at most one view and one copy each; a malloc'ed one (no arena: arena images belong to the decoder) is
-    released here.  Afterwards rgb[] is all NULL: every pointer was released or handed out, none can be harvested twice."""
+    released here.  Afterwards rgb[] is all NULL: every pointer was released or handed out, none can be harvested twice.
+    groups ("view groups": [(k, w, h), ...]): a file's entry is a LIST of G arrays [k, ...], its block taken apart."""
     if device_out:
         out = ([int(rgb[i] or 0) for i in range(n)], [(w[i], h[i]) for i in range(n)])
     else:
@@ -886,10 +984,10 @@ def _harvest(n, rgb, w, h, st, fmt, keep_pixels, on_image, arena, device_out, k=
         for i in range(n):
             if rgb[i]:
                 if on_image is not None or keep_pixels:
-                    view = _shape_output(rgb[i], w[i], h[i], fmt, k)
+                    view = _shape_groups(rgb[i], fmt, groups) if groups else _shape_output(rgb[i], w[i], h[i], fmt, k)
                     if on_image is not None:
                         on_image(i, view)
-                imgs.append(view.copy() if keep_pixels else (w[i], h[i]))
+                imgs.append(([v.copy() for v in view] if groups else view.copy()) if keep_pixels else (w[i], h[i]))
                 if not arena:
                     lib().jb_free(rgb[i])
             else:
@@ -1020,10 +1118,27 @@ class BatchDecoder:
     def device_entropy_images(self):
         return lib().jb_batch_decoder_device_entropy_images(self._h)
 
-    def _run(self, paths, keep_pixels, on_image, crops=None, views=None):
+    @staticmethod
+    def _grouped(a, views, view_groups, crops):
+        """the arguments of a call with view groups: (views, groups, n_groups); a["k"], a["groups"] for the harvest"""
+        if crops is not None:
+            raise JbError(-9, "view groups cannot be combined with per-image rectangles (crops)")
+        if views is None:
+            raise JbError(-7, "view groups want views")
+        groups, n_groups = _group_array(view_groups)
+        arr, a["k"] = _view_array(views, a["n"])
+        if a["n"] and a["k"] != sum(g.n_views for g in groups[:n_groups]):
+            raise JbError(-2, "view groups: every file wants as many views as the groups count")
+        a["groups"] = [(g.n_views, g.rs.out_w, g.rs.out_h) for g in groups[:n_groups]]
+        return arr, groups, n_groups
+
+    def _run(self, paths, keep_pixels, on_image, crops=None, views=None, view_groups=None):
         a = _batch_args(paths)
         times = (ctypes.c_double * 4)()
-        if views is not None:
+        if view_groups is not None:
+            arr, groups, n_groups = self._grouped(a, views, view_groups, crops)
+            rc = lib().jb_batch_decoder_run_view_groups(self._h, a["paths"], a["n"], arr, groups, n_groups, a["rgb"], a["w"], a["h"], a["st"], times)
+        elif views is not None:
             if crops is not None:
                 raise JbError(-9, "views cannot be combined with per-image rectangles (crops)")
             arr, a["k"] = _view_array(views, a["n"])
@@ -1037,9 +1152,9 @@ class BatchDecoder:
 
     def _results(self, a, t, keep_pixels, on_image):
         return _harvest(a["n"], a["rgb"], a["w"], a["h"], a["st"], self._fmt, keep_pixels, on_image, self._arena, self._device_out,
-                        a.get("k", 0)) + (t,)
+                        a.get("k", 0), a.get("groups")) + (t,)
 
-    def run(self, paths, keep_pixels=True, on_image=None, crops=None, views=None):
+    def run(self, paths, keep_pixels=True, on_image=None, crops=None, views=None, view_groups=None):
         """-> what decode_batch returns, in the decoder's format.  crops=[(x, y, w, h), ...] (jb_batch_decoder_run_crops; a
         target size must be set, a rectangle for every image must not: rc -7 in the times): crops[i] is the rectangle of
         paths[i], in pixels of that file, and every image comes out as its rectangle at the target size; a file its
@@ -1047,9 +1162,13 @@ class BatchDecoder:
         views=[[(x, y, w, h[, mirror]), ... K], ...] (jb_batch_decoder_run_views; a target size must be set, rc -7, a scale or
         a rectangle for every image must not, rc -9): views[i] are the K views of paths[i], and the file's entry is ONE
         array [K, ...] in the decoder's format -- the file is decoded once.  A file one of whose views does not fit gets
-        status -2.  JbError(-2) for rows of unequal length or len(views) != len(paths)."""
+        status -2.  JbError(-2) for rows of unequal length or len(views) != len(paths).
+        view_groups=[(k, (w, h)[, filter]), ... G] with views= (jb_batch_decoder_run_view_groups; the decoder's own target size
+        and filter are not read; a scale, a rectangle for every image or a fit must not be set, rc -9): the K = sum of k views
+        of a file fall into G groups, group-major, each with its own target size and filter, and the file's entry is a LIST of
+        G arrays [k_g, ...] -- the file is still decoded once."""
         assert not self._device_out, "device output is set: use run_to_device"
-        return self._run(paths, keep_pixels, on_image, crops, views)
+        return self._run(paths, keep_pixels, on_image, crops, views, view_groups)
 
     def set_device_output(self, d_base, nbytes):
         """jb_batch_decoder_set_device_output: decoded images stay in the caller's DEVICE memory
@@ -1067,13 +1186,14 @@ class BatchDecoder:
         _check(lib().jb_batch_decoder_set_device_outputs(self._h, ptrs, sizes, n))
         self._arena = self._device_out = n > 0
 
-    def run_to_device(self, paths, crops=None, views=None):
+    def run_to_device(self, paths, crops=None, views=None, view_groups=None):
         """After set_device_output: -> (device pointers (int, 0 = failed), (width, height) per image, statuses, times).
-        crops: as for run().  views: as for run() -- a file's pointer is that of its K outputs, back to back, tight."""
+        crops: as for run().  views: as for run() -- a file's pointer is that of its K outputs, back to back, tight.
+        view_groups: as for run() -- a file's pointer is that of its block (view_groups_bytes has the layout)."""
         assert self._device_out, "call set_device_output first"
-        return self._run(paths, False, None, crops, views)
+        return self._run(paths, False, None, crops, views, view_groups)
 
-    def run_to_tensor(self, paths, out, crops=None, views=None):
+    def run_to_tensor(self, paths, out, crops=None, views=None, view_groups=None):
         """Decode files of ONE size (or, with a rectangle set, of any size the rectangle fits in: out is then
         [N, 3, h, w] of the rectangle; with a target size set, of any size: out is [N, 3, h, w] of the target) straight into a caller-supplied CUDA tensor through the device-output route:
         out is [N, 3, H, W] (planar formats; [N, H, W, 3] for format 0), contiguous, of the decoder's format's dtype, on
@@ -1081,8 +1201,12 @@ class BatchDecoder:
         that fails to decode) gets a non-zero status (JB_ERR_GEOMETRY = -2 for the size) and its slice of out is left
         as it was.  The decoder's device-output setting is replaced for the call and cleared afterwards.
         crops: as for run() -- the random-resized-crop of a batch straight into the model's input tensor.
-        views: as for run(); out is then [N, K, 3, h, w] ([N, K, h, w, 3] for format 0)."""
+        views: as for run(); out is then [N, K, 3, h, w] ([N, K, h, w, 3] for format 0).
+        view_groups: as for run(); out is then a LIST of G contiguous tensors [N, K_g, 3, h_g, w_g] ([N, K_g, h_g, w_g, 3] for
+        format 0), and is returned as it came."""
         import torch
+        if view_groups is not None:
+            return self._run_to_tensors(paths, out, views, view_groups)
         if views is not None:
             views = [list(r) for r in views]
             k = _view_array(views, len(paths))[1]
@@ -1092,6 +1216,43 @@ class BatchDecoder:
             flat, st, t = self._run_to_tensor(paths, out.view((-1,) + tuple(out.shape[2:])), None, views, k)
             return out, st, t
         return self._run_to_tensor(paths, out, crops, None, 1)
+
+    def _run_to_tensors(self, paths, outs, views, view_groups):
+        """run_to_tensor with view groups: the files' blocks land in a scratch region, one copy per file and group sorts them"""
+        import torch
+        spec = self._fmt
+        fmt = spec.format if spec is not None else FMT_RGB_U8_HWC
+        planar = fmt != FMT_RGB_U8_HWC
+        dt = {np.uint8: torch.uint8, np.float32: torch.float32, np.float16: torch.float16}[FMT_DTYPE[fmt]]
+        n = len(paths)
+        groups, n_groups = _group_array(view_groups)
+        offsets, per = view_groups_bytes(view_groups, fmt)
+        outs = list(outs)
+        if len(outs) != n_groups:
+            raise ValueError(f"{len(outs)} tensors for {n_groups} groups")
+        for g, out in zip(groups[:n_groups], outs):
+            want = (n, g.n_views, 3, g.rs.out_h, g.rs.out_w) if planar else (n, g.n_views, g.rs.out_h, g.rs.out_w, 3)
+            if not (out.is_cuda and out.is_contiguous() and out.dtype == dt and tuple(out.shape) == want):
+                raise ValueError(f"a group's tensor must be a contiguous CUDA tensor {list(want)} of {dt}")
+            if out.device.index != self._device:
+                raise ValueError(f"out is on {out.device}, the decoder on device {self._device}")
+        scratch = torch.empty(n * per + 256 * (n + 1), dtype=torch.uint8, device=outs[0].device)
+        torch.cuda.synchronize(outs[0].device)
+        self.set_device_output(scratch.data_ptr(), scratch.numel())
+        try:
+            ptrs, sizes, st, t = self.run_to_device(paths, None, views, view_groups)
+        finally:
+            self.set_device_output(0, 0)
+        st = list(st)
+        base = scratch.data_ptr()
+        for g, out in enumerate(outs):
+            flat = out.view(n, -1).view(torch.uint8) if out.dtype != torch.uint8 else out.view(n, -1)   # (a row per FILE)
+            for i in range(n):
+                if st[i] == JB_OK and ptrs[i]:
+                    off = ptrs[i] - base + offsets[g]
+                    flat[i].copy_(scratch[off:off + flat.shape[1]])
+        torch.cuda.synchronize(outs[0].device)
+        return outs, st, t
 
     def _run_to_tensor(self, paths, out, crops, views, k):
         """run_to_tensor over out = [N * k, ...]: file i's k outputs are out[i * k : (i + 1) * k]."""
@@ -1133,12 +1294,17 @@ class BatchDecoder:
         return out, st, t
 
     # -- batches in a stream (jb_batch_decoder_submit / _collect): two in flight -----------------
-    def submit(self, paths, crops=None, views=None):
+    def submit(self, paths, crops=None, views=None, view_groups=None):
         """-> a ticket (keeps the batch's arrays alive); the batch runs while the caller prepares the next one.
         crops: as for run() (jb_batch_decoder_submit_crops, which copies them; a refusal is a JbError here).
-        views: as for run() (jb_batch_decoder_submit_views, which copies them)."""
+        views: as for run() (jb_batch_decoder_submit_views, which copies them).
+        view_groups: as for run() (jb_batch_decoder_submit_view_groups, which copies views and groups)."""
         t = _batch_args(paths)
-        if views is not None:
+        if view_groups is not None:
+            arr, groups, n_groups = self._grouped(t, views, view_groups, crops)
+            _check(lib().jb_batch_decoder_submit_view_groups(self._h, t["paths"], t["n"], arr, groups, n_groups, t["rgb"], t["w"], t["h"], t["st"],
+                                                             ctypes.byref(t["id"])))
+        elif views is not None:
             if crops is not None:
                 raise JbError(-9, "views cannot be combined with per-image rectangles (crops)")
             arr, t["k"] = _view_array(views, t["n"])

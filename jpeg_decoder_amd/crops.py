@@ -49,3 +49,14 @@ def random_views(width, height, rng, k, p_mirror=0.5, scale=(0.08, 1.0), ratio=(
         x, y, w, h = random_resized_crop(width, height, rng, scale, ratio)
         views.append((x, y, w, h, bool(float(rng.random()) < p_mirror)))
     return views
+
+
+def random_multicrop(width, height, rng, groups=((2, (0.4, 1.0)), (8, (0.05, 0.4))), p_mirror=0.5, ratio=(3 / 4, 4 / 3)):
+    """One row of K views of a width x height image for views= with view_groups= -> [(x, y, w, h, mirror)] * K, group-major:
+    the multi-crop of DINO / DINOv2 / iBOT / SwAV -- groups = ((k, (scale_lo, scale_hi)), ...), by default 2 "global" and 8
+    "local" crops.  The draws are exactly random_views(width, height, rng, k, p_mirror, scale, ratio) per group, in group order,
+    on the same generator."""
+    views = []
+    for k, scale in groups:
+        views += random_views(width, height, rng, k, p_mirror, scale, ratio)
+    return views

@@ -603,7 +603,8 @@ int submit_launch(jb_ctx *ctx, const Submission &sub, const jb_image_desc *desc,
   b.qtab_image_stride = n_images > 1 ? 768 : 0;
   b.d_rgb = dst_device ? rgb : (uint8_t *)s.d_rgb;
   b.rgb_row_stride = plan.row_stride;
-  b.rgb_image_stride = plan.views ? plan.view_bytes : plan.image_bytes;  // ("views": an image's outputs back to back)
+  // ("views": an image's outputs back to back; "view groups": the images' blocks, which the seam takes apart)
+  b.rgb_image_stride = plan.views && plan.n_groups == 0 ? plan.view_bytes : plan.image_bytes;
   return seam_launch(ctx, &b, up, plan, "submit");
 }
 

@@ -64,6 +64,11 @@ struct PerFile {
   const jb_roi *rois = nullptr;
   const jb_view *views = nullptr;
   int k = 0;
+  // "view groups" (_run_view_groups): the k views of a file fall into n_groups groups, each with its own target and filter
+  // (by value: the same for every file, every part of a multi-device decoder and both sides of submit / collect); 0: none
+  jb_view_group groups[JB_VIEW_GROUPS_MAX] = {};
+  int n_groups = 0;
+  const jb_view_group *groups_ptr() const { return n_groups > 0 ? groups : nullptr; }
   const jb_roi *roi_of(int i) const { return rois ? &rois[i] : nullptr; }
   const jb_view *views_of(int i) const { return views ? &views[(size_t)i * (size_t)k] : nullptr; }
 };
@@ -252,7 +257,9 @@ constexpr size_t kHeadBytes[2] = {(size_t)4 << 10, (size_t)64 << 10};
 // (crop: this file's rectangle of a run with per-image rectangles, planned as the rectangle of a batch of one; else null)
 // (views: this file's k views of a run with views, planned as a batch of one -- plan.image_bytes is then that of the k
 // outputs, so the FILE stays the unit of every size downstream; the array is the run's and outlives the plan)
-void parse_one(Parsed &p, const OutputRequest &out, const jb_roi *crop = nullptr, const jb_view *views = nullptr, int k = 0) {
+// (groups: the views' groups of a run with view groups -- the plan's image_bytes is then the file's block)
+void parse_one(Parsed &p, const OutputRequest &out, const jb_roi *crop = nullptr, const jb_view *views = nullptr, int k = 0,
+               const jb_view_group *groups = nullptr, int n_groups = 0) {
   p.status = jb_entropy_decode(p.bytes.data(), p.bytes.size(), &p.desc, p.qtabs, nullptr, 0);
   if (p.status == JB_OK) p.status = jb_geometry_of(&p.desc, &p.geo);
   if (p.status != JB_OK) {
@@ -264,7 +271,9 @@ void parse_one(Parsed &p, const OutputRequest &out, const jb_roi *crop = nullptr
   int orient = out.orient;
   if (orient == JB_ORIENT_EXIF && jb_exif_orientation(p.bytes.data(), p.bytes.size(), &orient) != JB_OK) orient = JB_ORIENT_STORED;
   const jb_image_desc frame = jb_draft_desc_(&p.desc, out.draft);  // ("draft decode": every size downstream is the draft frame's)
-  if (views) {
+  if (views && groups) {
+    p.plan = jb_view_groups_plan_(&frame, &out.spec, views, 1, groups, n_groups, orient);
+  } else if (views) {
     const jb_resize rs = {out.target.w, out.target.h, out.target.filter, out.target.reserved};
     p.plan = jb_views_plan_(&frame, &out.spec, views, 1, k, &rs, orient);
   } else {
@@ -288,7 +297,7 @@ void parse_pass(const Run &r, int t, std::vector<Parsed> &parsed, size_t *max_co
       ok = level < 2 ? jb_read_prefix_(r.paths[i], kHeadBytes[level], p.bytes, &p.loaded) : jb_read_file_(r.paths[i], p.bytes);
       *t_read += jb_now_s_() - a;
       if (level == 2) p.loaded = ok;
-      if (ok) parse_one(p, r.out, r.per.roi_of(i), r.per.views_of(i), r.per.k);
+      if (ok) parse_one(p, r.out, r.per.roi_of(i), r.per.views_of(i), r.per.k, r.per.groups_ptr(), r.per.n_groups);
     }
     if (!ok) {
       p.status = JB_ERR_FORMAT;
@@ -404,7 +413,7 @@ struct LaneWorker {
       p.have = true;
       p.loaded = ok;
       if (ok) {
-        parse_one(p, r.out, r.per.roi_of(i), r.per.views_of(i), r.per.k);
+        parse_one(p, r.out, r.per.roi_of(i), r.per.views_of(i), r.per.k, r.per.groups_ptr(), r.per.n_groups);
       } else {
         p.status = JB_ERR_FORMAT;
         p.error = "cannot read file";
@@ -630,7 +639,8 @@ struct LaneWorker {
     if (r.per.views) {
       const jb_resize rs = {r.out.target.w, r.out.target.h, r.out.target.filter, r.out.target.reserved};
       for (int j = 0; j < f.n; j++) views.insert(views.end(), parsed[(size_t)(f.k + j)].plan.views, parsed[(size_t)(f.k + j)].plan.views + r.per.k);
-      plan = jb_views_plan_(&frame, &r.out.spec, views.data(), f.n, r.per.k, &rs, head.plan.orient);
+      plan = r.per.n_groups > 0 ? jb_view_groups_plan_(&frame, &r.out.spec, views.data(), f.n, r.per.groups, r.per.n_groups, head.plan.orient)
+                                : jb_views_plan_(&frame, &r.out.spec, views.data(), f.n, r.per.k, &rs, head.plan.orient);
     }
     if (r.per.rois) {
       for (int j = 0; j < f.n; j++) crops.push_back(parsed[(size_t)(f.k + j)].plan.roi);
@@ -1250,8 +1260,8 @@ int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, const P
     s.st.assign(n, JB_OK);
     th.emplace_back([&, k] {
       Share &m = sh[(size_t)k];
-      PerFile mine;
-      mine.rois = rois ? m.rois.data() : nullptr, mine.views = per.views ? m.views.data() : nullptr, mine.k = per.k;
+      PerFile mine = per;  // (k and the groups)
+      mine.rois = rois ? m.rois.data() : nullptr, mine.views = per.views ? m.views.data() : nullptr;
       m.rc = run_single(d->parts[(size_t)k], m.paths.data(), (int)m.paths.size(), mine, m.rgb.data(),
                         m.w.data(), m.h.data(), m.st.data(), m.times, false);
       if (m.rc != JB_OK) m.text = jb_last_error(nullptr);  // thread-local text: fetch it on this thread
@@ -1296,11 +1306,12 @@ int crops_state(const jb_batch_decoder *d, const char *fn) {
 }
 
 // "views": no scale, no decoder-wide rectangle (JB_ERR_UNSUPPORTED), a target size (JB_ERR_STATE), k in 1..16
-int views_state(const jb_batch_decoder *d, int k, const char *fn) {
+// (grouped: "view groups" bring their own targets; k is the groups' sum)
+int views_state(const jb_batch_decoder *d, int k, const char *fn, bool grouped = false) {
   const std::string name = fn;
   if (d->out.scale != 1) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, (name + ": views cannot be combined with a scale other than 1").c_str());
   if (d->out.has_roi) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, (name + ": views cannot be combined with a rectangle for every image").c_str());
-  if (!d->out.has_resize) return jb_fail_(nullptr, JB_ERR_STATE, (name + ": views want a target size").c_str());
+  if (!d->out.has_resize && !grouped) return jb_fail_(nullptr, JB_ERR_STATE, (name + ": views want a target size").c_str());
   if (k < 1 || k > JB_VIEWS_MAX) return jb_fail_(nullptr, JB_ERR_GEOMETRY, (name + ": views_per_image is outside 1..16").c_str());
   if (d->out.fit_ptr()) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, (name + ": a fit other than JB_FIT_STRETCH is set: views cannot be combined with it").c_str());
   return JB_OK;
@@ -1318,7 +1329,7 @@ int run_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, cons
     if (rc != JB_OK) return rc;
   }
   if (per.views) {
-    const int rc = views_state(d, per.k, fn);
+    const int rc = views_state(d, per.k, fn, per.n_groups > 0);
     if (rc != JB_OK) return rc;
   }
   if (d->split_for_sides) {
@@ -1354,6 +1365,35 @@ extern "C" int jb_batch_decoder_run_views(jb_batch_decoder *d, const char *const
 
 namespace {
 
+// "view groups": the counts of a grouped call into `per` (JB_ERR_GEOMETRY: what jb_view_groups_check refuses of them)
+int groups_into(PerFile &per, const jb_view *views, const jb_view_group *groups, int n_groups, const char *fn) {
+  const std::string name = fn;
+  if (!views || !groups) return jb_fail_(nullptr, JB_ERR_NULL, (name + ": NULL pointer").c_str());
+  if (n_groups < 1 || n_groups > JB_VIEW_GROUPS_MAX) return jb_fail_(nullptr, JB_ERR_GEOMETRY, (name + ": n_groups is outside 1..4").c_str());
+  int k = 0;
+  for (int g = 0; g < n_groups; g++) {
+    if (groups[g].n_views < 1 || groups[g].n_views > JB_VIEWS_MAX || groups[g].reserved != 0)
+      return jb_fail_(nullptr, JB_ERR_GEOMETRY, (name + ": a group's n_views is outside 1..16 (or its reserved is not 0)").c_str());
+    per.groups[g] = groups[g];
+    k += groups[g].n_views;
+  }
+  per.views = views, per.k = k, per.n_groups = n_groups;
+  return JB_OK;
+}
+
+}  // namespace
+
+extern "C" int jb_batch_decoder_run_view_groups(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_view *views,
+                                                const jb_view_group *groups, int n_groups, uint8_t **rgb, int32_t *widths, int32_t *heights,
+                                                int *statuses, double *times) {
+  PerFile per;
+  const int rc = groups_into(per, views, groups, n_groups, "jb_batch_decoder_run_view_groups");
+  if (rc != JB_OK) return rc;
+  return run_checked(d, paths, n_paths, per, rgb, widths, heights, statuses, times, "jb_batch_decoder_run_view_groups");
+}
+
+namespace {
+
 // jb_batch_decoder_submit, and (rois != null) jb_batch_decoder_submit_crops
 int submit_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, const PerFile &per, uint8_t **rgb, int32_t *widths,
                    int32_t *heights, int *statuses, int *ticket) {
@@ -1370,7 +1410,7 @@ int submit_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, c
     if (rc != JB_OK) return rc;
   }
   if (per.views) {
-    const int rc = views_state(d, per.k, "jb_batch_decoder_submit_views");
+    const int rc = views_state(d, per.k, per.n_groups > 0 ? "jb_batch_decoder_submit_view_groups" : "jb_batch_decoder_submit_views", per.n_groups > 0);
     if (rc != JB_OK) return rc;
   }
   const int side = d->tickets & 1;
@@ -1400,7 +1440,7 @@ int submit_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, c
   f.views.clear();
   if (per.views) f.views.assign(per.views, per.views + (size_t)n_paths * (size_t)per.k);
   const bool with_rois = rois != nullptr, with_views = per.views != nullptr;
-  const int views_k = per.k;
+  const PerFile asked = per;  // (k and the groups: by value into the thread)
   f.busy = true;
   f.ticket = d->tickets++;
   f.rc = JB_OK;
@@ -1409,8 +1449,8 @@ int submit_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, c
   jb_batch_decoder::Flight *const fp = &f;
   try {
     f.th = std::thread([=] {
-      PerFile mine;
-      mine.rois = with_rois ? fp->rois.data() : nullptr, mine.views = with_views ? fp->views.data() : nullptr, mine.k = views_k;
+      PerFile mine = asked;
+      mine.rois = with_rois ? fp->rois.data() : nullptr, mine.views = with_views ? fp->views.data() : nullptr;
       fp->rc = run_impl(target, fp->path_ptr.data(), n_paths, mine, rgb, widths, heights, statuses, fp->times);
       if (fp->rc != JB_OK) fp->text = jb_last_error(nullptr);  // thread-local text: fetch it on this thread
     });
@@ -1443,6 +1483,15 @@ extern "C" int jb_batch_decoder_submit_views(jb_batch_decoder *d, const char *co
   if (!views) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_submit_views: NULL pointer");
   PerFile per;
   per.views = views, per.k = views_per_image;
+  return submit_checked(d, paths, n_paths, per, rgb, widths, heights, statuses, ticket);
+}
+
+extern "C" int jb_batch_decoder_submit_view_groups(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_view *views,
+                                                   const jb_view_group *groups, int n_groups, uint8_t **rgb, int32_t *widths, int32_t *heights,
+                                                   int *statuses, int *ticket) {
+  PerFile per;
+  const int rc = groups_into(per, views, groups, n_groups, "jb_batch_decoder_submit_view_groups");
+  if (rc != JB_OK) return rc;
   return submit_checked(d, paths, n_paths, per, rgb, widths, heights, statuses, ticket);
 }
 

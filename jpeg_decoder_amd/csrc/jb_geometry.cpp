@@ -147,6 +147,39 @@ int jb_views_check(const jb_image_desc *d, const jb_view *views, int n_images, i
   return plan.status;
 }
 
+int jb_view_groups_check(const jb_image_desc *d, const jb_view *views, int n_images, const jb_view_group *groups, int n_groups, int *bad_index) {
+  if (bad_index) *bad_index = -1;
+  if (!d || !groups || (!views && n_images > 0)) return JB_ERR_NULL;
+  jb_geometry g;
+  const int rc = jb_geometry_of(d, &g);
+  if (rc != JB_OK) return rc;
+  const JbOutPlan plan = jb_view_groups_plan_(d, nullptr, views, n_images, groups, n_groups);
+  if (bad_index) *bad_index = plan.bad_crop;
+  return plan.status;
+}
+
+int jb_view_groups_bytes(const jb_view_group *groups, int n_groups, int format, int64_t *group_offsets, int64_t *image_bytes) {
+  if (!groups || !image_bytes) return JB_ERR_NULL;
+  if (n_groups < 1 || n_groups > JB_VIEW_GROUPS_MAX) return JB_ERR_GEOMETRY;
+  int64_t at = 0, k = 0;
+  for (int g = 0; g < n_groups; g++) {
+    if (groups[g].n_views < 1 || groups[g].reserved != 0) return JB_ERR_GEOMETRY;
+    k += groups[g].n_views;
+  }
+  if (k > JB_VIEWS_MAX) return JB_ERR_GEOMETRY;
+  int64_t offsets[JB_VIEW_GROUPS_MAX];
+  for (int g = 0; g < n_groups; g++) {
+    int64_t one = 0;
+    const int rc = jb_output_bytes(groups[g].rs.out_w, groups[g].rs.out_h, format, &one);
+    if (rc != JB_OK) return rc;
+    offsets[g] = at;
+    at += one * groups[g].n_views;
+  }
+  if (group_offsets) memcpy(group_offsets, offsets, sizeof(int64_t) * (size_t)n_groups);
+  *image_bytes = at;
+  return JB_OK;
+}
+
 int jb_filter_check(const jb_image_desc *d, const jb_roi *roi, const jb_resize *rs) {
   if (!d || !rs) return JB_ERR_NULL;
   jb_geometry g;
@@ -333,6 +366,68 @@ JbOutPlan jb_views_plan_(const jb_image_desc *d, const jb_output_spec *spec, con
   p.views = views, p.views_per_image = k, p.n_views = (int32_t)n;
   p.view_bytes = p.image_bytes;
   p.image_bytes = p.view_bytes * k;
+  return p;
+}
+
+JbOutPlan jb_view_groups_plan_(const jb_image_desc *d, const jb_output_spec *spec, const jb_view *views, int n_images, const jb_view_group *groups,
+                               int n_groups, int orientation) {
+  JbOutPlan p;
+  auto refuse = [&p](int status, const char *why, int bad = -1) {
+    memset(&p, 0, sizeof p);
+    p.orient = 1;
+    p.status = status, p.why = why, p.bad_crop = bad;
+    return p;
+  };
+  if (!d || !groups) return refuse(JB_ERR_NULL, "null descriptor or groups");
+  if (n_images < 0) return refuse(JB_ERR_GEOMETRY, "negative count");
+  if (n_groups < 1 || n_groups > JB_VIEW_GROUPS_MAX) return refuse(JB_ERR_GEOMETRY, "n_groups is outside 1..4");
+  int64_t k = 0;
+  for (int g = 0; g < n_groups; g++) {
+    if (groups[g].n_views < 1 || groups[g].reserved != 0) return refuse(JB_ERR_GEOMETRY, "a group's n_views is below 1 (or its reserved is not 0)");
+    k += groups[g].n_views;
+  }
+  if (k > JB_VIEWS_MAX) return refuse(JB_ERR_GEOMETRY, "the groups' views per image add up to more than 16");
+  // every view in flat order -- flags and reserved, then the rectangles: the views' plan under a target nothing refuses
+  const jb_resize any = {1, 1, JB_FILTER_AREA, 0};
+  p = jb_views_plan_(d, spec, views, n_images, (int)k, &any, orientation);
+  if (p.status != JB_OK) return p;
+  JbOutPlan out = p;
+  std::vector<jb_view> mine;
+  int32_t first = 0;
+  int64_t offset = 0;
+  for (int g = 0; g < n_groups; g++) {
+    const int kg = groups[g].n_views;
+    mine.resize((size_t)n_images * (size_t)kg);
+    for (int64_t i = 0; i < n_images; i++)
+      for (int v = 0; v < kg; v++) mine[(size_t)(i * kg + v)] = views[i * k + first + v];
+    p = jb_views_plan_(d, spec, mine.data(), n_images, kg, &groups[g].rs, orientation);
+    if (p.status != JB_OK) return refuse(p.status, p.why, p.bad_crop < 0 ? -1 : (int)((p.bad_crop / kg) * k + first + p.bad_crop % kg));
+    if (g == 0) {
+      out = p;
+      out.views = views, out.views_per_image = (int32_t)k, out.n_views = (int32_t)(n_images * k);
+    }
+    out.groups[g] = JbOutPlan::Group{first, kg, p.out_w, p.out_h, p.filter, p.row_stride, p.view_bytes, offset};
+    first += kg;
+    offset += p.view_bytes * kg;
+  }
+  out.n_groups = n_groups;
+  out.image_bytes = offset;
+  return out;
+}
+
+JbOutPlan jb_view_group_plan_(const JbOutPlan &plan, int g) {
+  JbOutPlan p = plan;
+  const JbOutPlan::Group &q = plan.groups[g];
+  p.n_groups = 0;
+  memset(p.groups, 0, sizeof p.groups);
+  p.views = nullptr;
+  p.views_per_image = q.n_views;
+  p.n_views = plan.views_per_image > 0 ? plan.n_views / plan.views_per_image * q.n_views : 0;
+  p.out_w = q.out_w, p.out_h = q.out_h, p.filter = q.filter;
+  p.inner = jb_roi{0, 0, q.out_w, q.out_h};
+  p.row_stride = q.row_stride;
+  p.view_bytes = q.view_bytes;
+  p.image_bytes = q.view_bytes * q.n_views;
   return p;
 }
 

@@ -180,6 +180,29 @@ struct JbViewFilterTable {
 };
 hipError_t jbk_filter_launch_views(const JbFilter &p, const JbViewFilterTable &table, int filter, int format, hipStream_t stream);
 
+// "View groups" (jb_resample.hip, MODE = kViewGroups): a view launch whose rows are not evenly spaced behind p.dst -- an
+// image's block interleaves groups of different sizes, and a launch's 32 rows may start in the middle of an image -- so
+// every row carries the place of its output: dst_offset bytes behind p.dst (p.dst_image_stride is not looked at).  Read by
+// blockIdx like the rest of the row: scalar loads, wave-uniform.  40 and 48 bytes a row: 1.4 and 1.7 KB with the arguments.
+struct JbViewGroupRow {
+  JbViewRow v;
+  int64_t dst_offset;  // >= 0
+};
+struct JbViewGroupTable {
+  JbViewGroupRow r[kJbCropsPerLaunch];
+};
+struct JbViewGroupFilterRow {
+  JbFilterRow f;
+  int64_t dst_offset;  // >= 0
+};
+struct JbViewGroupFilterTable {
+  JbViewGroupFilterRow r[kJbCropsPerLaunch];
+  uint32_t mirror;
+};
+// jbk_resample_launch_views / jbk_filter_launch_views with their validation, and dst_offset >= 0 of every row
+hipError_t jbk_resample_launch_view_groups(const JbResample &p, const JbViewGroupTable &table, int format, hipStream_t stream);
+hipError_t jbk_filter_launch_view_groups(const JbFilter &p, const JbViewGroupFilterTable &table, int filter, int format, hipStream_t stream);
+
 // "Fit" (jb_fit.hip jb_fit_fill_kernel): the border of n_images letterboxed outputs of ow x oh at dst, addressed as
 // JbResample addresses them (rows dst_row_stride bytes apart -- of a plane when planar --, planes dst_plane_stride, images
 // dst_image_stride).  A band is the rectangle bw x bh at (bx, by) of every output, in elements; bw or bh = 0: no such band.

@@ -61,6 +61,19 @@ struct JbOutPlan {
   int32_t views_per_image;  // 0: no views
   int32_t n_views;          // images * views_per_image
   int64_t view_bytes;       // 3 * out_w * out_h * esize
+  // "view groups" (include/jpegblk.h; jb_view_groups_plan_ alone sets these): the views_per_image = K views of an image
+  // fall into n_groups groups, group g the views [first, first + n_views) of every image under ITS target and filter.
+  // THE IMAGE STILL IS THE UNIT: image_bytes is the image's block -- group 0's outputs, then group 1's, ... tight, group g
+  // at `offset` -- and out_w, out_h, row_stride, view_bytes, filter and inner are group 0's.  n_groups 0: no groups.
+  struct Group {
+    int32_t first, n_views;  // s_g, K_g
+    int32_t out_w, out_h, filter;
+    int64_t row_stride;  // tight rows of one output (of a plane when planar)
+    int64_t view_bytes;  // 3 * out_w * out_h * esize
+    int64_t offset;      // bytes from the block's first byte to the group's first output
+  };
+  int32_t n_groups;
+  Group groups[JB_VIEW_GROUPS_MAX];
   // "orientation" (include/jpegblk.h): the plan was made for T_o of the frame -- every field above is in oriented
   // coordinates, of the frame with width and height swapped for 5..8.  1: none.  0 (JB_ORIENT_EXIF, which only a file
   // resolves): a plan of the stored frame that no launch takes (JB_ERR_STATE where the launch is asked for).
@@ -106,6 +119,15 @@ jb_fit_geometry jb_fit_geometry_of_(const jb_roi &source, int32_t w, int32_t h, 
 // checks per-image rectangles.  views may be null when there are none.
 JbOutPlan jb_views_plan_(const jb_image_desc *desc, const jb_output_spec *spec, const jb_view *views, int n_images, int views_per_image,
                          const jb_resize *rs, int orientation = 1);
+// "view groups": the ONE place that checks a grouped call, in the order jb_view_groups_check documents -- the counts, every
+// view's flags and reserved, then every rectangle (bad_crop: the flat index i * K + v), then group by group what
+// jb_views_plan_ answers for that group's views alone under groups[g].rs (the tap cap: bad_crop is still the caller's flat
+// index).  The plan is group 0's with `views` the caller's flat array, views_per_image = K, the groups filled in and
+// image_bytes the block.  groups is read before the call returns; views is BORROWED like jb_views_plan_'s.
+JbOutPlan jb_view_groups_plan_(const jb_image_desc *desc, const jb_output_spec *spec, const jb_view *views, int n_images,
+                               const jb_view_group *groups, int n_groups, int orientation = 1);
+// group g of a grouped plan as a plan of its own: what jb_views_plan_ gives for that group's views, without a `views` array
+JbOutPlan jb_view_group_plan_(const JbOutPlan &plan, int g);
 // "draft decode" (include/jpegblk.h): the descriptor a plan under draft `denom` (1, 2, 4, 8) is made from -- desc with
 // the DRAFT FRAME's width and height; everything that addresses coefficients keeps the true descriptor.  denom 1: desc.
 jb_image_desc jb_draft_desc_(const jb_image_desc *desc, int denom);

@@ -29,14 +29,18 @@
 
 #include "jb_kernels.h"
 
-// what a kernel's table argument is: none (one geometry for the launch), a rectangle per image, a view per output
-enum { kNoTable = 0, kCrops = 1, kViews = 2 };
+// what a kernel's table argument is: none (one geometry for the launch), a rectangle per image, a view per output, a
+// view and a destination per output ("view groups", jb_kernels.h)
+enum { kNoTable = 0, kCrops = 1, kViews = 2, kViewGroups = 3 };
 
 static constexpr int kResampleRows = 4;  // output rows (= waves) per workgroup
 
 // the rows of a kernel's by-value table argument
 static __device__ __forceinline__ const JbCrop *crops_of(const JbCropTable &table) { return table.c; }
-static __device__ __forceinline__ const JbViewRow *views_of(const JbViewTable &table) { return table.r; }
+static __device__ __forceinline__ const JbViewRow &view_of(const JbViewTable &table, uint32_t row) { return table.r[row]; }
+static __device__ __forceinline__ const JbViewRow &view_of(const JbViewGroupTable &table, uint32_t row) { return table.r[row].v; }
+static __device__ __forceinline__ int64_t dst_offset_of(const JbViewGroupTable &table, uint32_t row) { return table.r[row].dst_offset; }
+static __device__ __forceinline__ int64_t dst_offset_of(const JbViewGroupFilterTable &table, uint32_t row) { return table.r[row].dst_offset; }
 
 // floor(n / d) for n < 2^41, 1 <= d < 2^32 with a quotient of at most 255: a float estimate (a few units off at the
 // worst) and integer correction steps that make it exact whatever the estimate was
@@ -52,9 +56,10 @@ static __device__ __forceinline__ uint32_t div_to_u8(uint64_t n, uint32_t d, flo
 // img comes from blockIdx, so the table reads are scalar loads and everything derived from them stays wave-uniform.
 // VIEWS (TABLE is JbViewTable): `img` is the launch's row = the output's index behind p.dst; its source is the row's
 // w x h at (dx, dy) of the union at p.src + .src_offset, rows .src_row_bytes apart, and .mirror reverses the store.
+// VIEW GROUPS (TABLE is JbViewGroupTable): VIEWS, and the row's output lies at p.dst + .dst_offset.
 template <int FORMAT, int MODE = kNoTable, typename... TABLE>
 __global__ __launch_bounds__(64 * kResampleRows) void jb_resample_kernel(const JbResample p, const TABLE... table) {
-  constexpr bool CROPS = MODE == kCrops, VIEWS = MODE == kViews;
+  constexpr bool CROPS = MODE == kCrops, GROUPS = MODE == kViewGroups, VIEWS = MODE == kViews || GROUPS;
   static_assert(sizeof...(TABLE) == (MODE != kNoTable ? 1 : 0), "the table is the second argument of the CROPS and VIEWS instantiations alone");
   // (the wave id is wave-uniform, and only readfirstlane tells the compiler so)
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -76,7 +81,7 @@ __global__ __launch_bounds__(64 * kResampleRows) void jb_resample_kernel(const J
   // VIEWS: the union's row length, the view's first column in it, and the column this lane stores (else: constants)
   [[maybe_unused]] uint32_t union_row_bytes = 0, dx = 0, js = j;
   if constexpr (VIEWS) {
-    const JbViewRow &v = views_of(table...)[img];
+    const JbViewRow &v = view_of(table..., img);
     iw = (uint32_t)v.w, ih = (uint32_t)v.h;
     union_row_bytes = (uint32_t)v.src_row_bytes, dx = (uint32_t)v.dx;
     src_offset = v.src_offset + (int64_t)v.dy * v.src_row_bytes;
@@ -128,7 +133,9 @@ __global__ __launch_bounds__(64 * kResampleRows) void jb_resample_kernel(const J
 
   const uint32_t d = iw * ih;
   const float rcp_d = 1.0f / (float)d;
-  uint8_t *const dst = p.dst + (int64_t)img * p.dst_image_stride + (int64_t)k * p.dst_row_stride;
+  int64_t dst_offset = (int64_t)img * p.dst_image_stride;
+  if constexpr (GROUPS) dst_offset = dst_offset_of(table..., img);
+  uint8_t *const dst = p.dst + dst_offset + (int64_t)k * p.dst_row_stride;
 #pragma unroll
   for (int c = 0; c < 3; c++) {
     const uint32_t u = div_to_u8(acc[c] + (d >> 1), d, rcp_d);
@@ -176,6 +183,28 @@ hipError_t jbk_resample_launch_views(const JbResample &q, const JbViewTable &tab
     case 1: hipLaunchKernelGGL((jb_resample_kernel<1, kViews, JbViewTable>), grid, block, 0, stream, p, table); break;
     case 2: hipLaunchKernelGGL((jb_resample_kernel<2, kViews, JbViewTable>), grid, block, 0, stream, p, table); break;
     default: hipLaunchKernelGGL((jb_resample_kernel<3, kViews, JbViewTable>), grid, block, 0, stream, p, table); break;
+  }
+  return hipGetLastError();
+}
+
+hipError_t jbk_resample_launch_view_groups(const JbResample &q, const JbViewGroupTable &table, int format, hipStream_t stream) {
+  if (format < 0 || format > 3 || q.ow < 1 || q.oh < 1 || q.ow > 65535 || q.oh > 65535 || q.n_images < 1 || q.n_images > kJbCropsPerLaunch)
+    return hipErrorInvalidValue;
+  for (int i = 0; i < q.n_images; i++) {
+    const JbViewRow &v = table.r[i].v;
+    if (v.w < 1 || v.h < 1 || v.w > 65535 || v.h > 65535 || v.dx < 0 || v.dy < 0 || v.dy > 65535 || v.src_offset < 0 || v.src_row_bytes > 3 * 65535 ||
+        3 * ((int64_t)v.dx + v.w) > v.src_row_bytes || (v.mirror & ~1) || table.r[i].dst_offset < 0)
+      return hipErrorInvalidValue;
+  }
+  JbResample p = q;
+  dim3 grid;
+  if (!resample_grid(p, &grid)) return hipErrorInvalidValue;
+  const dim3 block(64 * kResampleRows);
+  switch (format) {
+    case 0: hipLaunchKernelGGL((jb_resample_kernel<0, kViewGroups, JbViewGroupTable>), grid, block, 0, stream, p, table); break;
+    case 1: hipLaunchKernelGGL((jb_resample_kernel<1, kViewGroups, JbViewGroupTable>), grid, block, 0, stream, p, table); break;
+    case 2: hipLaunchKernelGGL((jb_resample_kernel<2, kViewGroups, JbViewGroupTable>), grid, block, 0, stream, p, table); break;
+    default: hipLaunchKernelGGL((jb_resample_kernel<3, kViewGroups, JbViewGroupTable>), grid, block, 0, stream, p, table); break;
   }
   return hipGetLastError();
 }
@@ -242,6 +271,8 @@ static constexpr int kFilterLdsBytes = 64 << 10;  // what one workgroup may have
 static __device__ __forceinline__ const JbFilterRow *rows_of(const JbFilterTable &table) { return table.r; }
 static __device__ __forceinline__ const JbFilterRow *rows_of(const JbViewFilterTable &table) { return table.r; }
 static __device__ __forceinline__ bool mirror_of(const JbViewFilterTable &table, uint32_t row) { return (table.mirror >> row) & 1u; }
+static __device__ __forceinline__ bool mirror_of(const JbViewGroupFilterTable &table, uint32_t row) { return (table.mirror >> row) & 1u; }
+static __device__ __forceinline__ const JbFilterRow &group_row_of(const JbViewGroupFilterTable &table, uint32_t row) { return table.r[row].f; }
 static __device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
 
 // one lane's weights of output `i` of axis `a` (i < n: else none) into tab[t * stride], t < taps, zero behind its own
@@ -272,9 +303,10 @@ static __device__ __forceinline__ int filter_weights(const JbFilterAxis &a, int 
 
 // VIEWS (TABLE is JbViewFilterTable): `img` is the launch's row = the output's index behind p.dst; the row's window is its
 // image's union, which holds the rectangle's own window, and its bit of table.mirror reverses the store.
+// VIEW GROUPS (TABLE is JbViewGroupFilterTable): VIEWS, and the row's output lies at p.dst + its dst_offset.
 template <int FILTER, int FORMAT, int MODE = kNoTable, typename... TABLE>
 __global__ __launch_bounds__(256) void jb_filter_kernel(const JbFilter q, const TABLE... table) {
-  constexpr bool CROPS = MODE != kNoTable, VIEWS = MODE == kViews;
+  constexpr bool CROPS = MODE != kNoTable, GROUPS = MODE == kViewGroups, VIEWS = MODE == kViews || GROUPS;
   static_assert(sizeof...(TABLE) == (CROPS ? 1 : 0), "the table is the second argument of the CROPS and VIEWS instantiations alone");
   JB_DYNAMIC_LDS(filter_lds);
   const JbResample &p = q.base;
@@ -287,7 +319,8 @@ __global__ __launch_bounds__(256) void jb_filter_kernel(const JbFilter q, const 
   JbFilterRow g = q.one;
   int64_t src_offset = (int64_t)img * p.src_image_stride;
   if constexpr (CROPS) {  // this image's geometry: scalar loads, wave-uniform
-    g = rows_of(table...)[img];
+    if constexpr (GROUPS) g = group_row_of(table..., img);
+    else g = rows_of(table...)[img];
     src_offset = g.tmp_offset;
   }
   const int ow = p.ow, oh = p.oh;
@@ -377,7 +410,9 @@ __global__ __launch_bounds__(256) void jb_filter_kernel(const JbFilter q, const 
   for (int i = 0; i < kFilterRows / 4; i++) {
     const int s = wave + 4 * i;
     if (s >= n_rows) continue;
-    uint8_t *const dst = p.dst + (int64_t)img * p.dst_image_stride + (int64_t)(k0 + s) * p.dst_row_stride;
+    int64_t dst_offset = (int64_t)img * p.dst_image_stride;
+    if constexpr (GROUPS) dst_offset = dst_offset_of(table..., img);
+    uint8_t *const dst = p.dst + dst_offset + (int64_t)(k0 + s) * p.dst_row_stride;
 #pragma unroll
     for (int c = 0; c < 3; c++) {
       const uint32_t u = (uint32_t)clip8(acc[i][c] >> 22);
@@ -491,6 +526,27 @@ hipError_t jbk_filter_launch_views(const JbFilter &q, const JbViewFilterTable &t
     JB_FILTER_LAUNCH(1, kViews, p, table)
   } else {
     JB_FILTER_LAUNCH(2, kViews, p, table)
+  }
+#undef JB_FILTER_TABLE
+  return hipGetLastError();
+}
+
+hipError_t jbk_filter_launch_view_groups(const JbFilter &q, const JbViewGroupFilterTable &table, int filter, int format, hipStream_t stream) {
+  if (format < 0 || format > 3 || q.base.n_images < 1 || q.base.n_images > kJbCropsPerLaunch) return hipErrorInvalidValue;
+  JbFilter p = q;
+  JbFilterRow rows[kJbCropsPerLaunch];  // (filter_plan takes the rows without their offsets)
+  for (int i = 0; i < p.base.n_images; i++) {
+    if (table.r[i].dst_offset < 0) return hipErrorInvalidValue;
+    rows[i] = table.r[i].f;
+  }
+  dim3 grid;
+  const size_t lds = filter_plan(p, rows, p.base.n_images, filter, &grid, true);
+  if (!lds) return hipErrorInvalidValue;
+#define JB_FILTER_TABLE , JbViewGroupFilterTable
+  if (filter == 1) {
+    JB_FILTER_LAUNCH(1, kViewGroups, p, table)
+  } else {
+    JB_FILTER_LAUNCH(2, kViewGroups, p, table)
   }
 #undef JB_FILTER_TABLE
   return hipGetLastError();

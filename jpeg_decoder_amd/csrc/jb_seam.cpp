@@ -470,6 +470,98 @@ int seam_launch_views(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
   });
 }
 
+// 3g. "view groups" (plan.n_groups): 3f with a target and a filter per GROUP of an image's views.  The union of an image is
+// taken over all its K views, each under its own group's resize; the first half is 3c's, unchanged.  The tail makes, per
+// group, ceil(m * K_g / 32) launches of the kViewGroups mode: a group's outputs of consecutive images are not evenly
+// spaced (the other groups' may lie between them), so every row carries its place behind the group's d_out.
+int seam_launch_view_groups(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const jb_view_output *outs, const char *fn) {
+  if (!ctx) return fail(nullptr, JB_ERR_NULL, "%s: ctx is NULL", fn);
+  if (!b || !outs) return fail(ctx, JB_ERR_NULL, "%s: NULL pointer", fn);
+  jb_geometry g;
+  int64_t plane_strides[JB_VIEW_GROUPS_MAX] = {0, 0, 0, 0};
+  const int k = plan.views_per_image;
+  // every group's buffer against the group's plan, as a batch's d_rgb is checked: the images, then the views of one image
+  // (plan.n_groups is 0 for a plan that has failed: one round, which reports it)
+  for (int q = 0; q < (plan.n_groups > 0 ? plan.n_groups : 1); q++) {
+    JbOutPlan gp = plan.status == JB_OK ? jb_view_group_plan_(plan, q) : plan;
+    gp.spec.plane_stride = outs[q].plane_stride;
+    jb_device_batch ob = *b;
+    // (a failed plan is reported by the check behind the batch's own pointers and descriptor, whatever outs holds)
+    ob.d_rgb = plan.status == JB_OK ? (uint8_t *)outs[q].d_out : (uint8_t *)b->d_coef;
+    ob.rgb_row_stride = outs[q].row_stride, ob.rgb_image_stride = outs[q].image_stride;
+    int rc = seam_check(ctx, &ob, gp, fn, &g, &plane_strides[q]);
+    if (rc) return rc;
+    if (plan.n_views != (int64_t)b->n_images * k) return fail(ctx, JB_ERR_GEOMETRY, "%s: %d views for %d images", fn, plan.n_views, b->n_images);
+    const int kg = plan.groups[q].n_views;
+    if (kg > 1) {
+      ob.n_images = kg;
+      ob.coef_image_stride = g.coef_bytes;
+      ob.rgb_image_stride = outs[q].view_stride;
+      rc = seam_check(ctx, &ob, gp, fn, &g, &plane_strides[q]);
+      if (rc) return rc;
+    }
+    const int64_t one = gp.planar ? 2 * plane_strides[q] + outs[q].row_stride * (int64_t)gp.out_h : outs[q].row_stride * (int64_t)gp.out_h;
+    if (b->n_images > 1 && outs[q].image_stride < (kg - 1) * outs[q].view_stride + one)
+      return fail(ctx, JB_ERR_GEOMETRY, "%s: group %d: image_stride smaller than the image's %d outputs", fn, q, kg);
+  }
+  const jb_device_batch ob = oriented_batch(ctx, b, plan.orient);
+  const auto group_of = [&](int v) {
+    int q = 0;
+    while (v >= plan.groups[q].first + plan.groups[q].n_views) q++;
+    return q;
+  };
+  // every image's union of its views' sources -- a view's rectangle, with a filter its window at ITS group's target
+  std::vector<jb_roi> unions;
+  for (int64_t i = 0; i < b->n_images; i++) {
+    int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+    for (int v = 0; v < k; v++) {
+      const jb_view &w = plan.views[i * k + v];
+      const JbOutPlan::Group &gr = plan.groups[group_of(v)];
+      const jb_roi r = {w.x, w.y, w.width, w.height};
+      const jb_roi src = gr.filter ? jb_filter_window_of_(&ob.desc, &r, gr.out_w, gr.out_h, gr.filter) : r;
+      if (v == 0 || src.x < x0) x0 = src.x;
+      if (v == 0 || src.y < y0) y0 = src.y;
+      if (v == 0 || src.x + src.width > x1) x1 = src.x + src.width;
+      if (v == 0 || src.y + src.height > y1) y1 = src.y + src.height;
+    }
+    unions.push_back(jb_roi{x0, y0, x1 - x0, y1 - y0});
+  }
+  return rects_into_scratch(ctx, b, stream, plan.orient, unions.data(), g, [&](int64_t i0, int m, const JbCropTable &table, const void *src, hipStream_t s) {
+    for (int q = 0; q < plan.n_groups; q++) {
+      const JbOutPlan::Group &gr = plan.groups[q];
+      const JbOutPlan gp = jb_view_group_plan_(plan, q);
+      jb_device_batch vb = ob;  // (resample_args: dst is the group's buffer, every row brings its own offset)
+      vb.d_rgb = (uint8_t *)outs[q].d_out;
+      vb.rgb_row_stride = outs[q].row_stride;
+      vb.n_images = 1;
+      const int64_t n_rows = (int64_t)m * gr.n_views;
+      for (int64_t n0 = 0; n0 < n_rows; n0 += kJbCropsPerLaunch) {
+        const int n = (int)(n_rows - n0 < kJbCropsPerLaunch ? n_rows - n0 : kJbCropsPerLaunch);
+        JbViewGroupTable vt;
+        JbViewGroupFilterTable ft;
+        memset(&vt, 0, sizeof vt);
+        memset(&ft, 0, sizeof ft);
+        for (int t = 0; t < n; t++) {
+          const int j = (int)((n0 + t) / gr.n_views), v = (int)((n0 + t) % gr.n_views);  // the image of the sub-batch, the view of the group
+          const jb_view &w = plan.views[(i0 + j) * k + gr.first + v];
+          const jb_roi &u = unions[i0 + j];
+          const int mirror = (w.flags & JB_VIEW_MIRROR) ? 1 : 0;
+          const int64_t dst_offset = (i0 + j) * outs[q].image_stride + v * outs[q].view_stride;
+          if (gr.filter) {
+            ft.r[t] = JbViewGroupFilterRow{filter_row(jb_roi{w.x, w.y, w.width, w.height}, u, table.c[j].tmp_offset), dst_offset};
+            ft.mirror |= (uint32_t)mirror << t;
+          } else {
+            vt.r[t] = JbViewGroupRow{JbViewRow{table.c[j].tmp_offset, 3 * u.width, w.x - u.x, w.y - u.y, w.width, w.height, mirror}, dst_offset};
+          }
+        }
+        if (gr.filter) JB_HIP(ctx, jbk_filter_launch_view_groups(filter_args(&vb, gp, plane_strides[q], src, 0, n), ft, gr.filter, plan.format, s));
+        else JB_HIP(ctx, jbk_resample_launch_view_groups(resample_args(&vb, gp, plane_strides[q], src, 0, n), vt, plan.format, s));
+      }
+    }
+    return (int)JB_OK;
+  });
+}
+
 // 3b. a plan with a target size: two launches per sub-batch, in stream order -- the pixel kernel (full size or the
 // rectangle, interleaved uint8, tight) into the stream's scratch, jb_resample_kernel from there into the caller's buffer
 int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn) {
@@ -641,6 +733,13 @@ int seam_launch_lj(jb_ctx *ctx, const jb_device_batch *b, void *stream, const Jb
 
 // 3. the launch, on `stream` or (null) the context's primary stream; fn: the entry point's name, for the error text
 int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOutPlan &plan, const char *fn) {
+  if (plan.n_groups > 0 && plan.orient != JB_ORIENT_EXIF && ctx && b) {
+    // a submission's block buffer (b->d_rgb, images b->rgb_image_stride apart) as the groups' outputs: tight, group g at its offset
+    jb_view_output outs[JB_VIEW_GROUPS_MAX];
+    for (int q = 0; q < plan.n_groups; q++)
+      outs[q] = jb_view_output{b->d_rgb ? b->d_rgb + plan.groups[q].offset : nullptr, b->rgb_image_stride, plan.groups[q].view_bytes, plan.groups[q].row_stride, 0};
+    return seam_launch_view_groups(ctx, b, stream, plan, outs, fn);
+  }
   if (plan.views && plan.orient != JB_ORIENT_EXIF && ctx && b) return seam_launch_views(ctx, b, stream, plan, fn);
   if (plan.orient != JB_ORIENT_STORED && plan.orient != JB_ORIENT_EXIF && ctx && b) return seam_launch_oriented(ctx, b, stream, plan, fn);
   if (plan.has_resize && ctx && b) return seam_launch_resized(ctx, b, stream, plan, fn);
@@ -739,6 +838,19 @@ int jb_blocks_to_rgb_device_views(jb_ctx *ctx, const jb_device_batch *b, const j
   const jb_image_desc frame = jb_draft_desc_(&b->desc, ctx->draft);
   return seam_launch(ctx, b, stream, jb_views_plan_(&frame, spec, views, b->n_images < 0 ? 0 : b->n_images, views_per_image, rs, ctx->orientation),
                      "jb_blocks_to_rgb_device_views");
+}
+
+int jb_blocks_to_rgb_device_view_groups(jb_ctx *ctx, const jb_device_batch *b, const jb_view *views, const jb_view_group *groups,
+                                        const jb_view_output *outputs, int n_groups, const jb_output_spec *spec, void *stream) {
+  const char *const fn = "jb_blocks_to_rgb_device_view_groups";
+  if (!ctx) return fail(nullptr, JB_ERR_NULL, "%s: ctx is NULL", fn);
+  if (!b || !views || !groups || !outputs) return fail(ctx, JB_ERR_NULL, "%s: NULL pointer", fn);
+  if (spec && spec->plane_stride != 0) return fail(ctx, JB_ERR_GEOMETRY, "%s: spec->plane_stride must be 0 (every jb_view_output has its own)", fn);
+  const jb_image_desc frame = jb_draft_desc_(&b->desc, ctx->draft);
+  const JbOutPlan plan = jb_view_groups_plan_(&frame, spec, views, b->n_images < 0 ? 0 : b->n_images, groups, n_groups, ctx->orientation);
+  // (a plan that has failed has no groups: outputs[0] is then all the check reads, and n_groups < 1 has none to read)
+  static const jb_view_output none = {};
+  return seam_launch_view_groups(ctx, b, stream, plan, n_groups >= 1 ? outputs : &none, fn);
 }
 
 }  // extern "C"
