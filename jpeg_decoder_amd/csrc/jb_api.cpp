@@ -862,16 +862,25 @@ int jb_entropy_decode_device(jb_ctx *ctx, const uint8_t *jpeg, size_t jpeg_bytes
   if (rc) return rc;
   // The chunks fall into step within the launches of the first attempt on ordinary data; dense adversarial data
   // (hardly any EOB to meet at) can need a workgroup's state handed on more often -- kJbStatusNotInStep alone says "not
-  // yet": one retry with more launches, then the caller is told (JB_ERR_FORMAT) and the host decoder
-  // (jb_entropy_decode) is the authority.  Corrupt data (the other bits) is never retried.
+  // yet": a retry with kJbSyncLaunchesMax launches, and then one with as many as the image has workgroups -- a launch
+  // reads the exit states its left neighbours wrote in the launch BEFORE (the workgroups of a launch run side by side),
+  // so a correct state is sure to cross one workgroup boundary per launch and no more: codes on which lanes do not fall
+  // into step by themselves (every code of one length, say) need that many.  A launch in which nothing changes costs a
+  // workgroup two loads.  Then the caller is told (JB_ERR_FORMAT) and the host decoder (jb_entropy_decode) is the
+  // authority.  While kJbStatusNotInStep is set the other bits say nothing: a lane of the writing pass that started from
+  // a state that is not its left neighbour's decodes noise, and noise has impossible bits and overruns.  Corrupt data
+  // (the other bits WITHOUT "not in step") is never retried.
+  const int enough = lay.n_sync_wg + 1 < kJbSyncLaunchesCap ? lay.n_sync_wg + 1 : kJbSyncLaunchesCap;
   int launches = kJbSyncLaunches;
   for (;;) {
     rc = huff_stage(ctx, s, s.h_blob, lay, coef_bytes, d_coef, ctx->stream, launches);
     if (rc) return rc;
     JB_HIP(ctx, hipMemcpyAsync(s.h_status, s.d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
     JB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (s.h_status[0] != kJbStatusNotInStep || launches >= kJbSyncLaunchesMax) break;
-    launches = kJbSyncLaunchesMax;
+    if (!(s.h_status[0] & kJbStatusNotInStep)) break;
+    const int next = launches < kJbSyncLaunchesMax ? kJbSyncLaunchesMax : enough;
+    if (next <= launches) break;
+    launches = next;
   }
   s.n_status = 1;
   return check_status(ctx, s);

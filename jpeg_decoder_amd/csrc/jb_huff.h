@@ -77,7 +77,9 @@ constexpr int kJbSyncLaunches = 2;       // synchronisation launches before the 
                                          // of a workgroup fall into step with each other inside ONE launch (passes over
                                          // LDS, until nothing changes); a further launch carries the exit state of a
                                          // workgroup's last chunk into the next workgroup's first
-constexpr int kJbSyncLaunchesMax = 8;    // what a retry after "not in step" may ask for
+constexpr int kJbSyncLaunchesMax = 8;    // what the first retry after "not in step" asks for
+constexpr int kJbSyncLaunchesCap = 1024; // the second retry asks for one launch per workgroup of the image + 1 (a correct state
+                                         // crosses one workgroup boundary per launch for certain: that many always do), up to this
 
 // Chunks never straddle a restart boundary: interval i is cut into chunks from its own first byte
 // (an empty interval still has one chunk, so that its missing blocks are noticed).

@@ -3,7 +3,11 @@
 // with the host decoder (jb_entropy_decode, itself pinned to the reference's coefficient dumps).
 // Test infrastructure: checks the kernels' logic where there is no GPU, and counts what the
 // synchronisation costs (steps per pass) for design work.  Not part of the product.
-//   huff_emu [--launches N] [--quiet] [--strict] file.jpg [file.jpg ...]     (all files in ONE submission)
+//   huff_emu [--launches N] [--quiet] [--strict] [--side-by-side] file.jpg [file.jpg ...]     (all files in ONE submission)
+// --side-by-side: the workgroups of a launch run in DESCENDING order, so that none sees what its left neighbour writes in the
+// same launch.  On the device the workgroups of a launch run at the same time: a state is sure to cross a workgroup boundary
+// only from one launch to the next.  In ascending order (the default) it crosses all of them within one launch, and a stream
+// on which lanes do not fall into step by themselves looks cheaper here than it is there.
 // exit code 0: whatever the kernels accept (status 0) the host decoder accepts too, with the same coefficients.
 // An image the kernels flag goes back to the host decoder in the product, so a flag on a stream the host
 // accepts is allowed (damaged streams with bytes behind an interval's last block, say) -- unless --strict:
@@ -31,6 +35,7 @@ alignas(16) uint8_t lds[160 * 1024];
 // per launch (in order): lane-steps, and wave-steps = sum over the waves' passes of the longest lane (what a wave pays)
 static std::mutex g_mu;
 static int g_launch = -1;
+static bool g_side_by_side = false;
 static std::map<std::pair<int, int>, std::vector<uint32_t>> g_wave_max;  // (block, wave) -> per pass: max over lanes
 static std::vector<long long> g_lane_steps, g_wave_steps, g_wave_passes;
 struct PassStat {
@@ -63,7 +68,8 @@ void launch(dim3 grid, dim3 block, const std::function<void()> &body) {
         for (uint32_t m : kv.second) g_wave_steps[(size_t)g_launch] += m, g_wave_passes[(size_t)g_launch] += m ? 1 : 0;
     }
   } sum_at_exit;
-  for (unsigned b = 0; b < grid.x; b++) {
+  for (unsigned i = 0; i < grid.x; i++) {
+    const unsigned b = g_side_by_side ? grid.x - 1u - i : i;
     Group group((int)block.x);
     std::vector<std::thread> th;
     for (unsigned t = 0; t < block.x; t++)
@@ -104,10 +110,11 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[i], "--launches") && i + 1 < argc) launches = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--quiet")) quiet = true;
     else if (!strcmp(argv[i], "--strict")) strict = true;
+    else if (!strcmp(argv[i], "--side-by-side")) g_side_by_side = true;
     else paths.push_back(argv[i]);
   }
   if (paths.empty()) {
-    fprintf(stderr, "usage: huff_emu [--launches N] [--quiet] file.jpg ...\n");
+    fprintf(stderr, "usage: huff_emu [--launches N] [--quiet] [--strict] [--side-by-side] file.jpg ...\n");
     return 2;
   }
   std::vector<std::unique_ptr<JbHuffJob>> jobs;

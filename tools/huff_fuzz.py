@@ -22,6 +22,13 @@ def seeds():
         out.append(bytearray(synth.encode_jpeg(coef, w, h, hs, vs, q, restart_interval=ri)))
         if i % 2 == 0:  # the same without restart intervals: the self-synchronising decoder
             out.append(bytearray(synth.encode_jpeg(coef, w, h, hs, vs, q)))
+    # streams under Huffman tables of other shapes than Annex K's (tests/huff_tables.py: codes on both sides of the first
+    # lookup level, a second-level pool filled to its last table, 27-bit symbols, flat and reversed codes)
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import huff_tables
+    coef, q = synth.synth_blocks(200, 120, 2, 2, 66)
+    for k, name in enumerate(huff_tables.TAKEN):
+        out.append(bytearray(synth.encode_jpeg(coef, 200, 120, 2, 2, q, restart_interval=(0, 3)[k % 2], huffman=huff_tables.family(name))))
     try:
         import io
         from PIL import Image
