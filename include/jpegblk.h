@@ -539,6 +539,68 @@ int jb_view_groups_bytes(const jb_view_group *groups, int n_groups, int format, 
 int jb_blocks_to_rgb_device_view_groups(jb_ctx *ctx, const jb_device_batch *batch, const jb_view *views, const jb_view_group *groups,
                                         const jb_view_output *outputs, int n_groups, const jb_output_spec *spec, void *stream);
 
+/* ---- colour chains: per-view colour jitter, grayscale and solarize on the device, Pillow-exact ----
+ * What a self-supervised pipeline does behind the flip -- ColorJitter, RandomGrayscale, Solarize -- on the uint8 pixels of
+ * every view, in front of the output format (Normalize is the format's scale / bias).  The bits are those of torchvision's
+ * PIL backend: ImageEnhance.Brightness / Contrast / Color, the convert("HSV") hue shift, convert("L"), ImageOps.solarize.
+ * A CHAIN is 0..JB_COLOR_OPS_MAX operations applied in order, each (op, value) with a float32 value; an empty chain is the
+ * identity.  With u an [h, w, 3] uint8 view:
+ *   L(p) = (19595 R + 38470 G + 7471 B + 32768) >> 16.
+ *   blend(d, v, a), d and v integers in 0..255: t = (float)d + a * (float)(v - d) in float32, product and sum rounded
+ *     separately; 0 <= a <= 1: trunc(t); else 0 for t <= 0, 255 for t >= 255, else trunc(t).
+ *   JB_COLOR_BRIGHTNESS a: every channel blend(0, v, a).         JB_COLOR_SATURATION a: every channel blend(L(p), v, a).
+ *   JB_COLOR_CONTRAST a: S = the sum of L over the view AS IT STANDS when the op is reached, N = w * h,
+ *     m = (2 S + N) div (2 N) in 64-bit integers (Pillow's int(mean + 0.5)); every channel blend(m, v, a).
+ *   JB_COLOR_GRAYSCALE (value 0): R = G = B = L(p).              JB_COLOR_SOLARIZE t, t integral in 0..256: v < t ? v : 255 - v.
+ *   JB_COLOR_HUE d, d integral in 0..255: RGB -> HSV, H = (H + d) & 255, HSV -> RGB, Pillow's two conversions
+ *     (csrc/jb_color_core.h states them operation by operation: which steps are float32 and which double decides bits).
+ * A chain may hold ONE JB_COLOR_CONTRAST: each costs a reduction pass over the view. */
+enum { JB_COLOR_BRIGHTNESS = 1, JB_COLOR_CONTRAST, JB_COLOR_SATURATION, JB_COLOR_HUE, JB_COLOR_GRAYSCALE, JB_COLOR_SOLARIZE };
+enum { JB_COLOR_OPS_MAX = 8 };
+typedef struct jb_color_op {
+  int32_t op;  /* JB_COLOR_* */
+  float value; /* the factor, the hue shift, the threshold; 0 for JB_COLOR_GRAYSCALE */
+} jb_color_op;
+typedef struct jb_color_chain {
+  int32_t n_ops, reserved; /* 0..JB_COLOR_OPS_MAX; 0 */
+  jb_color_op ops[JB_COLOR_OPS_MAX];
+} jb_color_chain; /* 72 bytes */
+/* Can the n chains be had?  JB_ERR_NULL for a null array (n > 0); JB_ERR_GEOMETRY for n < 0 and for the first chain with
+ * n_ops outside 0..8, reserved != 0, an unknown op, a factor that is not finite or below 0, a hue outside 0..255 or not
+ * integral, a threshold outside 0..256 or not integral, or a JB_COLOR_GRAYSCALE value that is not 0; JB_ERR_UNSUPPORTED for
+ * the first chain with more than one JB_COLOR_CONTRAST.  Chains are looked at in order, and the first one that fails
+ * decides: *bad_index (may be NULL) is its index, -1 when no chain is to blame.  Pure host code. */
+int jb_color_check(const jb_color_chain *chains, int n, int *bad_index);
+/* The chain on a HOST image of w x h interleaved uint8 pixels (rows in_row_stride / out_row_stride bytes apart, each at
+ * least 3 * w; in == out is allowed): the CPU statement of the kernels' arithmetic, through the same csrc/jb_color_core.h.
+ * JB_ERR_NULL; JB_ERR_GEOMETRY for w or h outside 1..65535 or a stride below 3 * w; then jb_color_check's status. */
+int jb_color_host(const uint8_t *in, int64_t in_row_stride, int32_t w, int32_t h, const jb_color_chain *chain, uint8_t *out,
+                  int64_t out_row_stride);
+/* Chain i on DEVICE image i of n_images interleaved uint8 images of w x h (rows in_row_stride apart, images
+ * in_image_stride; decoded by this library or not), written in format `spec` (NULL: interleaved uint8) at d_out: rows
+ * out_row_stride apart (of a plane when planar), planes spec->plane_stride (0: tight), images out_image_stride, as a batch's
+ * d_rgb is described.  The outputs must not overlap the inputs.  chains: a HOST array of n_images, read before the call
+ * returns.  Launches on `stream` (NULL: the context's): jb_color_mean_kernel where a chain of the launch has a contrast
+ * -- integer sums, so the result does not depend on the order of the additions -- then jb_color_apply_kernel, 32 images a
+ * launch.  JB_ERR_NULL; JB_ERR_GEOMETRY for n_images < 1, w or h outside 1..65535, strides below one row / one image, a
+ * bad spec, or float output that is not aligned to its element size; then jb_color_check's status with the chain's index
+ * in jb_last_error.  In every refusal nothing is launched or written. */
+int jb_color_device(jb_ctx *ctx, const uint8_t *d_in, int64_t in_row_stride, int64_t in_image_stride, int32_t w, int32_t h,
+                    int32_t n_images, const jb_color_chain *chains, void *d_out, int64_t out_row_stride, int64_t out_image_stride,
+                    const jb_output_spec *spec, void *stream);
+/* The sibling entry point plus `colors`: n_images * K chains parallel to `views`, read before the call returns.
+ * DEFINITION: output (i, v) is format(chain[i * K + v](u)), u being what the sibling writes for the same call in
+ * JB_FMT_RGB_U8_HWC, mirror included, bit for bit -- under either arithmetic, any orientation, any draft and any filter.
+ * colors == NULL is exactly the sibling.  The sibling's refusals come first and are unchanged; then jb_color_check's status
+ * with the chain's flat index in jb_last_error; in every refusal nothing is launched or written.
+ * The resample and filter kernels then write interleaved uint8 into a staging region of the stream's scratch -- counted
+ * towards JPEGBLK_RESIZE_TMP_BYTES when images are packed into sub-batches -- and the two colour kernels read it. */
+int jb_blocks_to_rgb_device_views_color(jb_ctx *ctx, const jb_device_batch *batch, const jb_view *views, int views_per_image,
+                                        const jb_resize *rs, const jb_color_chain *colors, const jb_output_spec *spec, void *stream);
+int jb_blocks_to_rgb_device_view_groups_color(jb_ctx *ctx, const jb_device_batch *batch, const jb_view *views, const jb_view_group *groups,
+                                              const jb_view_output *outputs, int n_groups, const jb_color_chain *colors,
+                                              const jb_output_spec *spec, void *stream);
+
 /* ---- fit: aspect-preserving targets -- letterbox (pad) and centred crop (cover) ----
  * Every route above that gives a batch one output size STRETCHES its source to the target.  A jb_fit next to the
  * jb_resize says what else to do with a source whose aspect ratio is not the target's.  The SOURCE is the launch's
@@ -962,6 +1024,24 @@ int jb_batch_decoder_run_view_groups(jb_batch_decoder *dec, const char *const *p
 int jb_batch_decoder_submit_view_groups(jb_batch_decoder *dec, const char *const *paths, int n_paths, const jb_view *views,
                                         const jb_view_group *groups, int n_groups, uint8_t **rgb, int32_t *widths, int32_t *heights,
                                         int *statuses, int *ticket);
+/* "Colour chains": jb_batch_decoder_run_views / _submit_views / _run_view_groups / _submit_view_groups plus `colors`, n_paths * K
+ * chains parallel to `views` -- colors[i * K + v] is applied to view v of paths[i] as jb_blocks_to_rgb_device_views_color
+ * defines it; the layout of the outputs is the sibling's.  colors == NULL is exactly the sibling.  The sibling's call-wide
+ * refusals come first; then a bad chain refuses the WHOLE call with jb_color_check's status (the chain's flat index in
+ * jb_last_error) before a file is read; a file that fails for its own reasons gets its usual status.  The submit variants
+ * copy the chains. */
+int jb_batch_decoder_run_views_color(jb_batch_decoder *dec, const char *const *paths, int n_paths, const jb_view *views, int views_per_image,
+                                     const jb_color_chain *colors, uint8_t **rgb, int32_t *widths, int32_t *heights, int *statuses,
+                                     double *times);
+int jb_batch_decoder_submit_views_color(jb_batch_decoder *dec, const char *const *paths, int n_paths, const jb_view *views,
+                                        int views_per_image, const jb_color_chain *colors, uint8_t **rgb, int32_t *widths, int32_t *heights,
+                                        int *statuses, int *ticket);
+int jb_batch_decoder_run_view_groups_color(jb_batch_decoder *dec, const char *const *paths, int n_paths, const jb_view *views,
+                                           const jb_view_group *groups, int n_groups, const jb_color_chain *colors, uint8_t **rgb,
+                                           int32_t *widths, int32_t *heights, int *statuses, double *times);
+int jb_batch_decoder_submit_view_groups_color(jb_batch_decoder *dec, const char *const *paths, int n_paths, const jb_view *views,
+                                              const jb_view_group *groups, int n_groups, const jb_color_chain *colors, uint8_t **rgb,
+                                              int32_t *widths, int32_t *heights, int *statuses, int *ticket);
 /* The filter (JB_FILTER_*; see "resampling filters") of the batch decoder's later runs and submissions: it governs the
  * target size of jb_batch_decoder_set_resize and the per-image rectangles of _run_crops / _submit_crops alike, and is
  * kept while no target size is set (there is then nothing to resample).  A file whose reduction exceeds the tap cap gets

@@ -118,6 +118,70 @@ class ViewOutput(ctypes.Structure):
                 ("row_stride", ctypes.c_int64), ("plane_stride", ctypes.c_int64)]
 
 
+# jb_color_op.op (jpegblk.h, "colour chains")
+COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION, COLOR_HUE, COLOR_GRAYSCALE, COLOR_SOLARIZE = 1, 2, 3, 4, 5, 6
+COLOR_OPS_MAX = 8
+
+
+class ColorOp(ctypes.Structure):
+    """jb_color_op: one operation of a colour chain, (COLOR_*, a float32 value)."""
+    _fields_ = [("op", ctypes.c_int32), ("value", ctypes.c_float)]
+
+
+class ColorChain(ctypes.Structure):
+    """jb_color_chain ("colour chains"): 0..8 operations applied in order to the uint8 pixels of one view."""
+    _fields_ = [("n_ops", ctypes.c_int32), ("reserved", ctypes.c_int32), ("ops", ColorOp * COLOR_OPS_MAX)]
+
+    @classmethod
+    def make(cls, chain):
+        """None / [] (the identity) / [(op, value), ...] / a ColorChain -> a ColorChain.  More than 8 operations: n_ops says
+        so and holds the first 8 -- jb_color_check refuses it, as it refuses every other bad chain."""
+        if isinstance(chain, cls):
+            return chain
+        ops = [o if isinstance(o, ColorOp) else ColorOp(int(o[0]), float(o[1])) for o in (chain or [])]
+        c = cls()
+        c.n_ops = len(ops)
+        for i, o in enumerate(ops[:COLOR_OPS_MAX]):
+            c.ops[i] = o
+        return c
+
+
+def _chain_array(chains):
+    """a flat list of chains -> a ctypes array of jb_color_chain, at least one element long.  Chains of plain (op, value)
+    pairs -- what color.py draws -- are packed through numpy in bulk (a batch has thousands); anything else one by one."""
+    import numpy as np
+    chains = [c if c is not None else () for c in chains]
+    n = len(chains)
+    if any(isinstance(c, ColorChain) or any(isinstance(o, ColorOp) for o in c) for c in chains):
+        flat = [ColorChain.make(c) for c in chains]
+        return (ColorChain * max(n, 1))(*flat)
+    rec = np.zeros(max(n, 1), dtype=[("n_ops", "<i4"), ("reserved", "<i4"), ("op", "<i4", (COLOR_OPS_MAX,)), ("value", "<f4", (COLOR_OPS_MAX,))])
+    lens = np.array([len(c) for c in chains], dtype=np.int64).reshape(-1)
+    rec["n_ops"][:n] = lens                     # (more than 8: n_ops says so, jb_color_check refuses)
+    pairs = [(int(o[0]), float(o[1])) for c in chains for o in c[:COLOR_OPS_MAX]]
+    if pairs:
+        kept = np.minimum(lens, COLOR_OPS_MAX)
+        rows = np.repeat(np.arange(n), kept)
+        cols = np.arange(len(pairs)) - np.repeat(np.cumsum(kept) - kept, kept)
+        flat = np.array(pairs, dtype=np.float64)
+        rec["op"][rows, cols] = flat[:, 0].astype(np.int32)
+        rec["value"][rows, cols] = flat[:, 1].astype(np.float32)
+    # jb_color_op is (op, value) interleaved: weave the two columns into the ABI's layout
+    out = np.zeros(max(n, 1), dtype=[("n_ops", "<i4"), ("reserved", "<i4"), ("ops", [("op", "<i4"), ("value", "<f4")], (COLOR_OPS_MAX,))])
+    out["n_ops"], out["ops"]["op"], out["ops"]["value"] = rec["n_ops"], rec["op"], rec["value"]
+    assert out.dtype.itemsize == ctypes.sizeof(ColorChain)
+    return (ColorChain * max(n, 1)).from_buffer(out)   # (the array keeps `out` alive)
+
+
+def _color_array(colors, n, k):
+    """colors=[[chain, ... K], ... N] -> a ctypes array of N * K jb_color_chain parallel to the views; another shape than the
+    views': JbError(-2)"""
+    rows = [list(r) for r in colors]
+    if len(rows) != n or any(len(r) != k for r in rows):
+        raise JbError(-2, f"colors: {n} rows of {k} chains wanted, parallel to the views")
+    return _chain_array([c for r in rows for c in r])
+
+
 def _group_array(view_groups):
     """[(k, (w, h)[, filter]) or ViewGroup, ... G] -> (a ctypes array of G jb_view_group, at least one element long, G)."""
     gs = []
@@ -233,10 +297,14 @@ class _Request:
     crops or views JbError(-9), behind every refusal above.  view_groups ([(k, (w, h)[, filter]), ...]: "view groups") become
     .groups (a ctypes array of ViewGroup; .n_groups) and bring their own targets and filters: with resize, a filter other
     than FILTER_AREA, roi, crops, a scale or a fit JbError(-9), without views JbError(-7), a row of views whose length is
-    not the groups' K JbError(-2); view_outputs (the seam's jb_view_output per group) become .outputs."""
+    not the groups' K JbError(-2); view_outputs (the seam's jb_view_output per group) become .outputs.  colors ([[chain, ...
+    K], ... N], a chain being None / [(op, value), ...]: "colour chains") become .colors (a ctypes array of ColorChain parallel
+    to .views, or None): without views ValueError, another shape than the views' JbError(-2)."""
 
     def __init__(self, scale=1, fmt=None, roi=None, resize=None, crops=None, filter=FILTER_AREA, views=None, fit=None, view_groups=None,
-                 view_outputs=None):
+                 view_outputs=None, colors=None):
+        if colors is not None and views is None:
+            raise ValueError("colors want views (a K = 1 views= call covers a plain one)")
         self.groups, self.n_groups, self.outputs = None, 0, None
         if view_groups is not None:
             if resize is not None or int(filter) != FILTER_AREA or roi is not None or crops is not None or scale != 1 or _fit_struct(fit) is not None:
@@ -285,6 +353,9 @@ class _Request:
                 raise JbError(-2, "view groups: every image wants as many views as the groups count")
             self.views, self.views_per_image = _view_array(views)
             self.n_view_rows = len(views)
+        self.colors = None
+        if colors is not None:
+            self.colors = _color_array(colors, self.n_view_rows, self.views_per_image)
         self.fit = _fit_struct(fit)
         if self.fit is not None and self.fit.mode != FIT_STRETCH:
             if resize is None:
@@ -303,9 +374,13 @@ class _Request:
             rs = ctypes.byref(_resize_struct(self.target, self.filter))
             return "fit", (_ref(self.roi), rs, ctypes.byref(self.fit), _ref(self.spec))
         if self.groups is not None:      # (every group brings its jb_resize)
+            if self.colors is not None:
+                return "view_groups_color", (self.views, self.groups, self.outputs, self.n_groups, self.colors, _ref(self.spec))
             return "view_groups", (self.views, self.groups, self.outputs, self.n_groups, _ref(self.spec))
         if self.views is not None:       # (takes a jb_resize: the filter needs no route of its own)
             rs = ctypes.byref(Resize(self.target[0], self.target[1], self.filter, 0))
+            if self.colors is not None:
+                return "views_color", (self.views, self.views_per_image, rs, self.colors, _ref(self.spec))
             return "views", (self.views, self.views_per_image, rs, _ref(self.spec))
         if self.filter != FILTER_AREA:   # (always with a target size)
             rs = ctypes.byref(Resize(self.target[0], self.target[1], self.filter, 0))
@@ -342,6 +417,9 @@ _ROUTES = {"plain": ("jb_decode_file", "jb_decode_memory", "jb_blocks_to_rgb_dev
            "views": (None, None, "jb_blocks_to_rgb_device_views"),
            # the views of an image in up to four groups, each with its own target size and filter
            "view_groups": (None, None, "jb_blocks_to_rgb_device_view_groups"),
+           # views / view groups with colors=: a colour chain per view, between the resize and the output format
+           "views_color": (None, None, "jb_blocks_to_rgb_device_views_color"),
+           "view_groups_color": (None, None, "jb_blocks_to_rgb_device_view_groups_color"),
            # a fit other than FIT_STRETCH: letterbox or centred crop to the target, any filter
            "fit": ("jb_decode_file_fit", "jb_decode_memory_fit", "jb_blocks_to_rgb_device_fit")}
 
@@ -391,6 +469,31 @@ def view_groups_check(desc, views, view_groups):
     rc = lib().jb_view_groups_check(ctypes.byref(desc), arr, len(list(views)), groups, n_groups, ctypes.byref(bad))
     if rc != JB_OK:
         raise JbError(rc, f"image {bad.value // k}, view {bad.value % k} cannot be had" if bad.value >= 0 else "bad groups, target size, filter, count or descriptor")
+
+
+def color_check(chains):
+    """jb_color_check: can the chains ([chain, ...], a chain being None / [(op, value), ...] / a ColorChain) be had?  Raises
+    JbError otherwise (.bad_index: the first chain that fails, -1 when none is to blame)."""
+    chains = list(chains)
+    bad = ctypes.c_int(-1)
+    rc = lib().jb_color_check(_chain_array(chains), len(chains), ctypes.byref(bad))
+    if rc != JB_OK:
+        e = JbError(rc, lib().jb_last_error(None).decode(errors="replace"))
+        e.bad_index = bad.value
+        raise e
+
+
+def color_host(image, chain):
+    """jb_color_host: the chain on a host [h, w, 3] uint8 array -> a new array.  The CPU statement of the device kernels'
+    arithmetic (the same csrc/jb_color_core.h), for tests and for checking a pipeline without a GPU."""
+    import numpy as np
+    a = np.ascontiguousarray(image, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise JbError(-2, "color_host wants an [h, w, 3] uint8 image")
+    out = np.empty_like(a)
+    c = ColorChain.make(chain)
+    _check(lib().jb_color_host(_ptr(a), a.strides[0], a.shape[1], a.shape[0], ctypes.byref(c), _ptr(out), out.strides[0]))
+    return out
 
 
 def view_groups_bytes(view_groups, fmt=FMT_RGB_U8_HWC):
@@ -589,6 +692,16 @@ def lib():
     L.jb_blocks_to_rgb_device_view_groups.argtypes = [vp, ctypes.POINTER(DeviceBatch), pv, pg, ctypes.POINTER(ViewOutput), ctypes.c_int, ps, vp]
     L.jb_batch_decoder_run_view_groups.argtypes = L.jb_batch_decoder_run.argtypes[:3] + [pv, pg, ctypes.c_int] + L.jb_batch_decoder_run.argtypes[3:]
     L.jb_batch_decoder_submit_view_groups.argtypes = L.jb_batch_decoder_submit.argtypes[:3] + [pv, pg, ctypes.c_int] + L.jb_batch_decoder_submit.argtypes[3:]
+    pc = ctypes.POINTER(ColorChain)
+    L.jb_color_check.argtypes = [pc, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    L.jb_color_host.argtypes = [vp, i64, i32, i32, pc, vp, i64]
+    L.jb_color_device.argtypes = [vp, vp, i64, i64, i32, i32, i32, pc, vp, i64, i64, ps, vp]
+    L.jb_blocks_to_rgb_device_views_color.argtypes = [vp, ctypes.POINTER(DeviceBatch), pv, ctypes.c_int, prs, pc, ps, vp]
+    L.jb_blocks_to_rgb_device_view_groups_color.argtypes = [vp, ctypes.POINTER(DeviceBatch), pv, pg, ctypes.POINTER(ViewOutput), ctypes.c_int, pc, ps, vp]
+    L.jb_batch_decoder_run_views_color.argtypes = L.jb_batch_decoder_run.argtypes[:3] + [pv, ctypes.c_int, pc] + L.jb_batch_decoder_run.argtypes[3:]
+    L.jb_batch_decoder_submit_views_color.argtypes = L.jb_batch_decoder_submit.argtypes[:3] + [pv, ctypes.c_int, pc] + L.jb_batch_decoder_submit.argtypes[3:]
+    L.jb_batch_decoder_run_view_groups_color.argtypes = L.jb_batch_decoder_run.argtypes[:3] + [pv, pg, ctypes.c_int, pc] + L.jb_batch_decoder_run.argtypes[3:]
+    L.jb_batch_decoder_submit_view_groups_color.argtypes = L.jb_batch_decoder_submit.argtypes[:3] + [pv, pg, ctypes.c_int, pc] + L.jb_batch_decoder_submit.argtypes[3:]
     L.jb_filter_check.argtypes = [pd, pr, prs]
     L.jb_filter_window.argtypes = [pd, pr, prs, pr]
     L.jb_blocks_to_rgb_device_filtered.argtypes = [vp, ctypes.POINTER(DeviceBatch), pr, prs, ps, vp]
@@ -896,7 +1009,7 @@ class Context:
 
     # -- the seam, device buffers ------------------------------------------------------------
     def blocks_to_rgb_device(self, batch, stream=None, scale=1, fmt=None, roi=None, resize=None, crops=None, filter=FILTER_AREA, views=None,
-                             fit=None, view_groups=None, view_outputs=None):
+                             fit=None, view_groups=None, view_outputs=None, colors=None):
         """scale 2, 4, 8: the batch's d_rgb and strides describe images of scaled_size(desc.width, desc.height, scale).
         fmt (an OutputSpec or a format number): planar output -- the batch's rgb_row_stride is then a plane's.
         roi=(x, y, w, h) (with any fmt, not with a scale): the batch's d_rgb and strides describe images of w x h, the
@@ -918,8 +1031,12 @@ class Context:
         plane_stride]) or ViewOutput, ... G] (any fmt, whose plane_stride must be 0; not with resize, filter, roi, crops, fit or a
         scale): the K = sum of k views of an image fall into G groups, group-major, each with its own target size and filter, all
         from ONE pixel launch per image (jb_blocks_to_rgb_device_view_groups); batch.d_rgb and its strides are not read.
+        colors=[[chain, ... K], ... N] with views= (and with view_groups=): chain (i, v) -- None / [] (the identity) or [(COLOR_*,
+        value), ...], at most 8 operations and one COLOR_CONTRAST -- is applied to the uint8 pixels of view v of image i, mirror
+        included, in front of the output format: Pillow's ImageEnhance / convert / ImageOps.solarize bit for bit
+        (jb_blocks_to_rgb_device_views_color / _view_groups_color).  Without views ValueError.
         Each is the entry point of that suffix (_ROUTES)."""
-        request = _Request(scale, fmt, roi, resize, crops, filter, views, fit, view_groups, view_outputs)
+        request = _Request(scale, fmt, roi, resize, crops, filter, views, fit, view_groups, view_outputs, colors)
         if request.groups is not None and request.outputs is None:
             raise JbError(-1, "view groups want view_outputs")
         if request.crops is not None and request.n_crops != batch.n_images:
@@ -928,6 +1045,19 @@ class Context:
             raise JbError(-2, f"{request.n_view_rows} rows of views for {batch.n_images} images")
         route, tail = request.routed()
         _check(getattr(lib(), _ROUTES[route][_DEVICE])(self._h, ctypes.byref(batch), *tail, stream), self._h)
+
+    def color_device(self, d_in, in_row_stride, in_image_stride, width, height, n_images, chains, d_out, out_row_stride, out_image_stride,
+                     fmt=None, stream=None):
+        """jb_color_device: chain i ([chain, ...], n_images of them) on device image i of n_images interleaved uint8 images of
+        width x height at the device address d_in, written in format fmt (None: interleaved uint8) at d_out; the strides are
+        bytes, as a batch's d_rgb is described (out_row_stride: a plane's rows when planar).  Launches on `stream`."""
+        chains = list(chains)
+        if len(chains) != n_images:
+            raise JbError(-2, f"{len(chains)} chains for {n_images} images")
+        spec = fmt if fmt is None or isinstance(fmt, OutputSpec) else OutputSpec.make(fmt)
+        _check(lib().jb_color_device(self._h, ctypes.c_void_p(int(d_in)), in_row_stride, in_image_stride, width, height, n_images,
+                                     _chain_array(chains), ctypes.c_void_p(int(d_out)), out_row_stride, out_image_stride, _ref(spec), stream),
+               self._h)
 
     # -- decode(path) -> RGB -----------------------------------------------------------------
     def _decode(self, family, lead, request):
@@ -1132,17 +1262,31 @@ class BatchDecoder:
         a["groups"] = [(g.n_views, g.rs.out_w, g.rs.out_h) for g in groups[:n_groups]]
         return arr, groups, n_groups
 
-    def _run(self, paths, keep_pixels, on_image, crops=None, views=None, view_groups=None):
+    @staticmethod
+    def _no_colors_without_views(colors, views):
+        if colors is not None and views is None:
+            raise ValueError("colors want views (a K = 1 views= call covers a plain one)")
+
+    def _run(self, paths, keep_pixels, on_image, crops=None, views=None, view_groups=None, colors=None):
+        self._no_colors_without_views(colors, views)
         a = _batch_args(paths)
         times = (ctypes.c_double * 4)()
         if view_groups is not None:
             arr, groups, n_groups = self._grouped(a, views, view_groups, crops)
-            rc = lib().jb_batch_decoder_run_view_groups(self._h, a["paths"], a["n"], arr, groups, n_groups, a["rgb"], a["w"], a["h"], a["st"], times)
+            if colors is not None:
+                rc = lib().jb_batch_decoder_run_view_groups_color(self._h, a["paths"], a["n"], arr, groups, n_groups, _color_array(colors, a["n"], a["k"]),
+                                                                  a["rgb"], a["w"], a["h"], a["st"], times)
+            else:
+                rc = lib().jb_batch_decoder_run_view_groups(self._h, a["paths"], a["n"], arr, groups, n_groups, a["rgb"], a["w"], a["h"], a["st"], times)
         elif views is not None:
             if crops is not None:
                 raise JbError(-9, "views cannot be combined with per-image rectangles (crops)")
             arr, a["k"] = _view_array(views, a["n"])
-            rc = lib().jb_batch_decoder_run_views(self._h, a["paths"], a["n"], arr, a["k"], a["rgb"], a["w"], a["h"], a["st"], times)
+            if colors is not None:
+                rc = lib().jb_batch_decoder_run_views_color(self._h, a["paths"], a["n"], arr, a["k"], _color_array(colors, a["n"], a["k"]), a["rgb"],
+                                                            a["w"], a["h"], a["st"], times)
+            else:
+                rc = lib().jb_batch_decoder_run_views(self._h, a["paths"], a["n"], arr, a["k"], a["rgb"], a["w"], a["h"], a["st"], times)
         elif crops is not None:
             rc = lib().jb_batch_decoder_run_crops(self._h, a["paths"], a["n"], _crop_array(crops, a["n"]), a["rgb"], a["w"], a["h"],
                                                   a["st"], times)
@@ -1154,7 +1298,7 @@ class BatchDecoder:
         return _harvest(a["n"], a["rgb"], a["w"], a["h"], a["st"], self._fmt, keep_pixels, on_image, self._arena, self._device_out,
                         a.get("k", 0), a.get("groups")) + (t,)
 
-    def run(self, paths, keep_pixels=True, on_image=None, crops=None, views=None, view_groups=None):
+    def run(self, paths, keep_pixels=True, on_image=None, crops=None, views=None, view_groups=None, colors=None):
         """-> what decode_batch returns, in the decoder's format.  crops=[(x, y, w, h), ...] (jb_batch_decoder_run_crops; a
         target size must be set, a rectangle for every image must not: rc -7 in the times): crops[i] is the rectangle of
         paths[i], in pixels of that file, and every image comes out as its rectangle at the target size; a file its
@@ -1166,9 +1310,14 @@ class BatchDecoder:
         view_groups=[(k, (w, h)[, filter]), ... G] with views= (jb_batch_decoder_run_view_groups; the decoder's own target size
         and filter are not read; a scale, a rectangle for every image or a fit must not be set, rc -9): the K = sum of k views
         of a file fall into G groups, group-major, each with its own target size and filter, and the file's entry is a LIST of
-        G arrays [k_g, ...] -- the file is still decoded once."""
+        G arrays [k_g, ...] -- the file is still decoded once.
+        colors=[[chain, ... K], ...] with views= (jb_batch_decoder_run_views_color / _run_view_groups_color): colors[i][v] --
+        None / [] or [(COLOR_*, value), ...] -- is applied to view v of paths[i] on its uint8 pixels, mirror included, in front of
+        the decoder's format (Context.blocks_to_rgb_device has the definition).  A bad chain refuses the whole call (the
+        rc in the times); without views ValueError; another shape than the views' JbError(-2)."""
+        self._no_colors_without_views(colors, views)
         assert not self._device_out, "device output is set: use run_to_device"
-        return self._run(paths, keep_pixels, on_image, crops, views, view_groups)
+        return self._run(paths, keep_pixels, on_image, crops, views, view_groups, colors)
 
     def set_device_output(self, d_base, nbytes):
         """jb_batch_decoder_set_device_output: decoded images stay in the caller's DEVICE memory
@@ -1186,14 +1335,16 @@ class BatchDecoder:
         _check(lib().jb_batch_decoder_set_device_outputs(self._h, ptrs, sizes, n))
         self._arena = self._device_out = n > 0
 
-    def run_to_device(self, paths, crops=None, views=None, view_groups=None):
+    def run_to_device(self, paths, crops=None, views=None, view_groups=None, colors=None):
         """After set_device_output: -> (device pointers (int, 0 = failed), (width, height) per image, statuses, times).
         crops: as for run().  views: as for run() -- a file's pointer is that of its K outputs, back to back, tight.
-        view_groups: as for run() -- a file's pointer is that of its block (view_groups_bytes has the layout)."""
+        view_groups: as for run() -- a file's pointer is that of its block (view_groups_bytes has the layout).
+        colors: as for run()."""
+        self._no_colors_without_views(colors, views)
         assert self._device_out, "call set_device_output first"
-        return self._run(paths, False, None, crops, views, view_groups)
+        return self._run(paths, False, None, crops, views, view_groups, colors)
 
-    def run_to_tensor(self, paths, out, crops=None, views=None, view_groups=None):
+    def run_to_tensor(self, paths, out, crops=None, views=None, view_groups=None, colors=None):
         """Decode files of ONE size (or, with a rectangle set, of any size the rectangle fits in: out is then
         [N, 3, h, w] of the rectangle; with a target size set, of any size: out is [N, 3, h, w] of the target) straight into a caller-supplied CUDA tensor through the device-output route:
         out is [N, 3, H, W] (planar formats; [N, H, W, 3] for format 0), contiguous, of the decoder's format's dtype, on
@@ -1203,21 +1354,23 @@ class BatchDecoder:
         crops: as for run() -- the random-resized-crop of a batch straight into the model's input tensor.
         views: as for run(); out is then [N, K, 3, h, w] ([N, K, h, w, 3] for format 0).
         view_groups: as for run(); out is then a LIST of G contiguous tensors [N, K_g, 3, h_g, w_g] ([N, K_g, h_g, w_g, 3] for
-        format 0), and is returned as it came."""
+        format 0), and is returned as it came.
+        colors: as for run() -- the colour jitter of every view on the way into the model's input tensor."""
+        self._no_colors_without_views(colors, views)
         import torch
         if view_groups is not None:
-            return self._run_to_tensors(paths, out, views, view_groups)
+            return self._run_to_tensors(paths, out, views, view_groups, colors)
         if views is not None:
             views = [list(r) for r in views]
             k = _view_array(views, len(paths))[1]
             lead = (len(paths), k)
             if out.dim() != 5 or tuple(out.shape[:2]) != lead or not out.is_contiguous():
                 raise ValueError(f"out must be a contiguous CUDA tensor [{lead[0]}, {lead[1]}, 3, H, W] ([N, K, H, W, 3] for format 0)")
-            flat, st, t = self._run_to_tensor(paths, out.view((-1,) + tuple(out.shape[2:])), None, views, k)
+            flat, st, t = self._run_to_tensor(paths, out.view((-1,) + tuple(out.shape[2:])), None, views, k, colors)
             return out, st, t
         return self._run_to_tensor(paths, out, crops, None, 1)
 
-    def _run_to_tensors(self, paths, outs, views, view_groups):
+    def _run_to_tensors(self, paths, outs, views, view_groups, colors=None):
         """run_to_tensor with view groups: the files' blocks land in a scratch region, one copy per file and group sorts them"""
         import torch
         spec = self._fmt
@@ -1240,7 +1393,7 @@ class BatchDecoder:
         torch.cuda.synchronize(outs[0].device)
         self.set_device_output(scratch.data_ptr(), scratch.numel())
         try:
-            ptrs, sizes, st, t = self.run_to_device(paths, None, views, view_groups)
+            ptrs, sizes, st, t = self.run_to_device(paths, None, views, view_groups, colors)
         finally:
             self.set_device_output(0, 0)
         st = list(st)
@@ -1254,7 +1407,7 @@ class BatchDecoder:
         torch.cuda.synchronize(outs[0].device)
         return outs, st, t
 
-    def _run_to_tensor(self, paths, out, crops, views, k):
+    def _run_to_tensor(self, paths, out, crops, views, k, colors=None):
         """run_to_tensor over out = [N * k, ...]: file i's k outputs are out[i * k : (i + 1) * k]."""
         import torch
         spec = self._fmt
@@ -1276,7 +1429,7 @@ class BatchDecoder:
         torch.cuda.synchronize(out.device)
         self.set_device_output(scratch.data_ptr(), scratch.numel())
         try:
-            ptrs, sizes, st, t = self.run_to_device(paths, crops, views)
+            ptrs, sizes, st, t = self.run_to_device(paths, crops, views, None, colors)
         finally:
             self.set_device_output(0, 0)
         st = list(st)
@@ -1294,22 +1447,33 @@ class BatchDecoder:
         return out, st, t
 
     # -- batches in a stream (jb_batch_decoder_submit / _collect): two in flight -----------------
-    def submit(self, paths, crops=None, views=None, view_groups=None):
+    def submit(self, paths, crops=None, views=None, view_groups=None, colors=None):
         """-> a ticket (keeps the batch's arrays alive); the batch runs while the caller prepares the next one.
         crops: as for run() (jb_batch_decoder_submit_crops, which copies them; a refusal is a JbError here).
         views: as for run() (jb_batch_decoder_submit_views, which copies them).
-        view_groups: as for run() (jb_batch_decoder_submit_view_groups, which copies views and groups)."""
+        view_groups: as for run() (jb_batch_decoder_submit_view_groups, which copies views and groups).
+        colors: as for run() (the _color variants, which copy the chains too; a bad chain is a JbError here)."""
+        self._no_colors_without_views(colors, views)
         t = _batch_args(paths)
         if view_groups is not None:
             arr, groups, n_groups = self._grouped(t, views, view_groups, crops)
-            _check(lib().jb_batch_decoder_submit_view_groups(self._h, t["paths"], t["n"], arr, groups, n_groups, t["rgb"], t["w"], t["h"], t["st"],
-                                                             ctypes.byref(t["id"])))
+            if colors is not None:
+                _check(lib().jb_batch_decoder_submit_view_groups_color(self._h, t["paths"], t["n"], arr, groups, n_groups,
+                                                                       _color_array(colors, t["n"], t["k"]), t["rgb"], t["w"], t["h"], t["st"],
+                                                                       ctypes.byref(t["id"])))
+            else:
+                _check(lib().jb_batch_decoder_submit_view_groups(self._h, t["paths"], t["n"], arr, groups, n_groups, t["rgb"], t["w"], t["h"], t["st"],
+                                                                 ctypes.byref(t["id"])))
         elif views is not None:
             if crops is not None:
                 raise JbError(-9, "views cannot be combined with per-image rectangles (crops)")
             arr, t["k"] = _view_array(views, t["n"])
-            _check(lib().jb_batch_decoder_submit_views(self._h, t["paths"], t["n"], arr, t["k"], t["rgb"], t["w"], t["h"], t["st"],
-                                                       ctypes.byref(t["id"])))
+            if colors is not None:
+                _check(lib().jb_batch_decoder_submit_views_color(self._h, t["paths"], t["n"], arr, t["k"], _color_array(colors, t["n"], t["k"]),
+                                                                 t["rgb"], t["w"], t["h"], t["st"], ctypes.byref(t["id"])))
+            else:
+                _check(lib().jb_batch_decoder_submit_views(self._h, t["paths"], t["n"], arr, t["k"], t["rgb"], t["w"], t["h"], t["st"],
+                                                           ctypes.byref(t["id"])))
         elif crops is not None:
             _check(lib().jb_batch_decoder_submit_crops(self._h, t["paths"], t["n"], _crop_array(crops, t["n"]), t["rgb"], t["w"], t["h"],
                                                        t["st"], ctypes.byref(t["id"])))

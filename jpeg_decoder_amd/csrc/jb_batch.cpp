@@ -71,6 +71,9 @@ struct PerFile {
   const jb_view_group *groups_ptr() const { return n_groups > 0 ? groups : nullptr; }
   const jb_roi *roi_of(int i) const { return rois ? &rois[i] : nullptr; }
   const jb_view *views_of(int i) const { return views ? &views[(size_t)i * (size_t)k] : nullptr; }
+  // "colour chains" (the _color entry points): colors[i * k + v] goes with views[i * k + v]; null: none
+  const jb_color_chain *colors = nullptr;
+  const jb_color_chain *colors_of(int i) const { return colors ? &colors[(size_t)i * (size_t)k] : nullptr; }
 };
 
 struct Parsed {
@@ -635,12 +638,17 @@ struct LaneWorker {
     JbOutPlan plan = head.plan;
     std::vector<jb_roi> crops;
     std::vector<jb_view> views;  // "views": the members' views, k each, in the group's order
+    std::vector<jb_color_chain> colors;  // "colour chains": and their chains, parallel to them
     const jb_image_desc frame = jb_draft_desc_(&head.desc, r.out.draft);
     if (r.per.views) {
       const jb_resize rs = {r.out.target.w, r.out.target.h, r.out.target.filter, r.out.target.reserved};
       for (int j = 0; j < f.n; j++) views.insert(views.end(), parsed[(size_t)(f.k + j)].plan.views, parsed[(size_t)(f.k + j)].plan.views + r.per.k);
       plan = r.per.n_groups > 0 ? jb_view_groups_plan_(&frame, &r.out.spec, views.data(), f.n, r.per.groups, r.per.n_groups, head.plan.orient)
                                 : jb_views_plan_(&frame, &r.out.spec, views.data(), f.n, r.per.k, &rs, head.plan.orient);
+      if (r.per.colors) {
+        for (int j = 0; j < f.n; j++) colors.insert(colors.end(), r.per.colors_of(index_of(f.k + j)), r.per.colors_of(index_of(f.k + j)) + r.per.k);
+        plan.colors = colors.data();
+      }
     }
     if (r.per.rois) {
       for (int j = 0; j < f.n; j++) crops.push_back(parsed[(size_t)(f.k + j)].plan.roi);
@@ -763,6 +771,7 @@ struct jb_batch_decoder {
     std::vector<const char *> path_ptr;
     std::vector<jb_roi> rois;  // (jb_batch_decoder_submit_crops) the batch's rectangles, copied like the paths
     std::vector<jb_view> views;  // (jb_batch_decoder_submit_views) the batch's views, copied too
+    std::vector<jb_color_chain> colors;  // (the _color entry points) and their chains
   };
   Flight flights[2];
   int tickets = 0;
@@ -1237,6 +1246,7 @@ int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, const P
     std::vector<const char *> paths;
     std::vector<jb_roi> rois;  // (per-image rectangles: rectangle i goes where file i goes)
     std::vector<jb_view> views;  // (views: and so do file i's k views)
+    std::vector<jb_color_chain> colors;  // (colour chains: and their chains)
     std::vector<uint8_t *> rgb;
     std::vector<int32_t> w, h;
     std::vector<int> st;
@@ -1249,6 +1259,7 @@ int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, const P
     sh[(size_t)(i % np)].paths.push_back(paths[i]);
     if (rois) sh[(size_t)(i % np)].rois.push_back(rois[i]);
     if (per.views) sh[(size_t)(i % np)].views.insert(sh[(size_t)(i % np)].views.end(), per.views_of(i), per.views_of(i) + per.k);
+    if (per.colors) sh[(size_t)(i % np)].colors.insert(sh[(size_t)(i % np)].colors.end(), per.colors_of(i), per.colors_of(i) + per.k);
   }
   std::vector<std::thread> th;
   for (int k = 0; k < np; k++) {
@@ -1262,6 +1273,7 @@ int run_impl(jb_batch_decoder *d, const char *const *paths, int n_paths, const P
       Share &m = sh[(size_t)k];
       PerFile mine = per;  // (k and the groups)
       mine.rois = rois ? m.rois.data() : nullptr, mine.views = per.views ? m.views.data() : nullptr;
+      mine.colors = per.colors ? m.colors.data() : nullptr;
       m.rc = run_single(d->parts[(size_t)k], m.paths.data(), (int)m.paths.size(), mine, m.rgb.data(),
                         m.w.data(), m.h.data(), m.st.data(), m.times, false);
       if (m.rc != JB_OK) m.text = jb_last_error(nullptr);  // thread-local text: fetch it on this thread
@@ -1317,6 +1329,16 @@ int views_state(const jb_batch_decoder *d, int k, const char *fn, bool grouped =
   return JB_OK;
 }
 
+// "colour chains": a bad chain refuses the whole call, behind the call's own refusals (per.k has been checked)
+int colors_state(const PerFile &per, int n_paths, const char *fn) {
+  if (!per.colors) return JB_OK;
+  if ((int64_t)n_paths * per.k > 0x7fffffffLL) return jb_fail_(nullptr, JB_ERR_CAPACITY, (std::string(fn) + ": too many chains").c_str());
+  const int rc = jb_color_check(per.colors, n_paths * per.k, nullptr);
+  if (rc == JB_OK) return JB_OK;
+  const std::string why = jb_last_error(nullptr);
+  return jb_fail_(nullptr, rc, (std::string(fn) + ": " + why).c_str());
+}
+
 int run_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, const PerFile &per, uint8_t **rgb, int32_t *widths,
                 int32_t *heights, int *statuses, double *times, const char *fn) {
   const jb_roi *const rois = per.rois;
@@ -1329,7 +1351,8 @@ int run_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, cons
     if (rc != JB_OK) return rc;
   }
   if (per.views) {
-    const int rc = views_state(d, per.k, fn, per.n_groups > 0);
+    int rc = views_state(d, per.k, fn, per.n_groups > 0);
+    if (rc == JB_OK) rc = colors_state(per, n_paths, fn);
     if (rc != JB_OK) return rc;
   }
   if (d->split_for_sides) {
@@ -1363,6 +1386,15 @@ extern "C" int jb_batch_decoder_run_views(jb_batch_decoder *d, const char *const
   return run_checked(d, paths, n_paths, per, rgb, widths, heights, statuses, times, "jb_batch_decoder_run_views");
 }
 
+extern "C" int jb_batch_decoder_run_views_color(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_view *views, int views_per_image,
+                                                const jb_color_chain *colors, uint8_t **rgb, int32_t *widths, int32_t *heights, int *statuses,
+                                                double *times) {
+  if (!views) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_run_views_color: NULL pointer");
+  PerFile per;
+  per.views = views, per.k = views_per_image, per.colors = colors;
+  return run_checked(d, paths, n_paths, per, rgb, widths, heights, statuses, times, "jb_batch_decoder_run_views_color");
+}
+
 namespace {
 
 // "view groups": the counts of a grouped call into `per` (JB_ERR_GEOMETRY: what jb_view_groups_check refuses of them)
@@ -1382,6 +1414,16 @@ int groups_into(PerFile &per, const jb_view *views, const jb_view_group *groups,
 }
 
 }  // namespace
+
+extern "C" int jb_batch_decoder_run_view_groups_color(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_view *views,
+                                                      const jb_view_group *groups, int n_groups, const jb_color_chain *colors, uint8_t **rgb,
+                                                      int32_t *widths, int32_t *heights, int *statuses, double *times) {
+  PerFile per;
+  const int rc = groups_into(per, views, groups, n_groups, "jb_batch_decoder_run_view_groups_color");
+  if (rc != JB_OK) return rc;
+  per.colors = colors;
+  return run_checked(d, paths, n_paths, per, rgb, widths, heights, statuses, times, "jb_batch_decoder_run_view_groups_color");
+}
 
 extern "C" int jb_batch_decoder_run_view_groups(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_view *views,
                                                 const jb_view_group *groups, int n_groups, uint8_t **rgb, int32_t *widths, int32_t *heights,
@@ -1410,7 +1452,9 @@ int submit_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, c
     if (rc != JB_OK) return rc;
   }
   if (per.views) {
-    const int rc = views_state(d, per.k, per.n_groups > 0 ? "jb_batch_decoder_submit_view_groups" : "jb_batch_decoder_submit_views", per.n_groups > 0);
+    const char *const fn = per.n_groups > 0 ? "jb_batch_decoder_submit_view_groups" : "jb_batch_decoder_submit_views";
+    int rc = views_state(d, per.k, fn, per.n_groups > 0);
+    if (rc == JB_OK) rc = colors_state(per, n_paths, fn);
     if (rc != JB_OK) return rc;
   }
   const int side = d->tickets & 1;
@@ -1439,7 +1483,9 @@ int submit_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, c
   if (rois) f.rois.assign(rois, rois + n_paths);
   f.views.clear();
   if (per.views) f.views.assign(per.views, per.views + (size_t)n_paths * (size_t)per.k);
-  const bool with_rois = rois != nullptr, with_views = per.views != nullptr;
+  f.colors.clear();
+  if (per.colors) f.colors.assign(per.colors, per.colors + (size_t)n_paths * (size_t)per.k);
+  const bool with_rois = rois != nullptr, with_views = per.views != nullptr, with_colors = per.colors != nullptr;
   const PerFile asked = per;  // (k and the groups: by value into the thread)
   f.busy = true;
   f.ticket = d->tickets++;
@@ -1451,6 +1497,7 @@ int submit_checked(jb_batch_decoder *d, const char *const *paths, int n_paths, c
     f.th = std::thread([=] {
       PerFile mine = asked;
       mine.rois = with_rois ? fp->rois.data() : nullptr, mine.views = with_views ? fp->views.data() : nullptr;
+      mine.colors = with_colors ? fp->colors.data() : nullptr;
       fp->rc = run_impl(target, fp->path_ptr.data(), n_paths, mine, rgb, widths, heights, statuses, fp->times);
       if (fp->rc != JB_OK) fp->text = jb_last_error(nullptr);  // thread-local text: fetch it on this thread
     });
@@ -1492,6 +1539,25 @@ extern "C" int jb_batch_decoder_submit_view_groups(jb_batch_decoder *d, const ch
   PerFile per;
   const int rc = groups_into(per, views, groups, n_groups, "jb_batch_decoder_submit_view_groups");
   if (rc != JB_OK) return rc;
+  return submit_checked(d, paths, n_paths, per, rgb, widths, heights, statuses, ticket);
+}
+
+extern "C" int jb_batch_decoder_submit_views_color(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_view *views,
+                                                   int views_per_image, const jb_color_chain *colors, uint8_t **rgb, int32_t *widths,
+                                                   int32_t *heights, int *statuses, int *ticket) {
+  if (!views) return jb_fail_(nullptr, JB_ERR_NULL, "jb_batch_decoder_submit_views_color: NULL pointer");
+  PerFile per;
+  per.views = views, per.k = views_per_image, per.colors = colors;
+  return submit_checked(d, paths, n_paths, per, rgb, widths, heights, statuses, ticket);
+}
+
+extern "C" int jb_batch_decoder_submit_view_groups_color(jb_batch_decoder *d, const char *const *paths, int n_paths, const jb_view *views,
+                                                         const jb_view_group *groups, int n_groups, const jb_color_chain *colors, uint8_t **rgb,
+                                                         int32_t *widths, int32_t *heights, int *statuses, int *ticket) {
+  PerFile per;
+  const int rc = groups_into(per, views, groups, n_groups, "jb_batch_decoder_submit_view_groups_color");
+  if (rc != JB_OK) return rc;
+  per.colors = colors;
   return submit_checked(d, paths, n_paths, per, rgb, widths, heights, statuses, ticket);
 }
 

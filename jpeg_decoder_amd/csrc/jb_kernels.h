@@ -9,6 +9,7 @@ typedef void *hipStream_t;
 #include <hip/hip_runtime_api.h>
 #endif
 
+#include "../../include/jpegblk.h"  // (jb_color_chain: the colour launch takes the ABI's structure as it is)
 #include "jb_knobs.h"
 #include "jb_orient.h"
 
@@ -202,6 +203,32 @@ struct JbViewGroupFilterTable {
 // jbk_resample_launch_views / jbk_filter_launch_views with their validation, and dst_offset >= 0 of every row
 hipError_t jbk_resample_launch_view_groups(const JbResample &p, const JbViewGroupTable &table, int format, hipStream_t stream);
 hipError_t jbk_filter_launch_view_groups(const JbFilter &p, const JbViewGroupFilterTable &table, int filter, int format, hipStream_t stream);
+
+// "Colour chains" (jb_color.hip; the arithmetic is jb_color_core.h's): up to kJbCropsPerLaunch VIEWS a launch, each a tight
+// or strided interleaved uint8 image of w x h at src + src_offset (rows src_row_stride apart), its chain applied and the
+// result written in `format` at dst + dst_offset, addressed as JbResample addresses an output.  Chains and offsets travel
+// in the arguments: 88 bytes a row, 2.8 KB with JbColor, of the 4 KB argument segment.
+struct JbColorRow {
+  int64_t src_offset, dst_offset;  // >= 0
+  jb_color_chain chain;            // checked by the caller (jb_color_check)
+};
+struct JbColorTable {
+  JbColorRow r[kJbCropsPerLaunch];
+};
+struct JbColor {
+  const uint8_t *src;
+  uint8_t *dst;
+  int64_t src_row_stride, dst_row_stride, dst_plane_stride;
+  unsigned long long *sums;  // device, kJbCropsPerLaunch words, the launch's alone until it has run: the views' luma sums
+  int32_t w, h;              // each in 1..65535
+  int32_t n_views;
+  int32_t tiles_x;  // (set by the launch: workgroups per 4 rows)
+  float scale[3], bias[3];
+};
+// Where a chain of the launch has a JB_COLOR_CONTRAST: `sums` zeroed on the stream, then jb_color_mean_kernel (a workgroup
+// per 16 rows of a view; integer sums, one 64-bit atomic per workgroup).  Then jb_color_apply_kernel: one workgroup per 256
+// columns x 4 rows of a view, a lane per 4 pixels of a row.  An argument outside its range: hipErrorInvalidValue.
+hipError_t jbk_color_launch(const JbColor &p, const JbColorTable &table, int format, hipStream_t stream);
 
 // "Fit" (jb_fit.hip jb_fit_fill_kernel): the border of n_images letterboxed outputs of ow x oh at dst, addressed as
 // JbResample addresses them (rows dst_row_stride bytes apart -- of a plane when planar --, planes dst_plane_stride, images

@@ -88,6 +88,11 @@ struct JbOutPlan {
   int32_t fit_mode;  // JB_FIT_*
   jb_roi inner;
   uint8_t fill[3];
+  // "colour chains" (include/jpegblk.h; the _color entry points alone set it, on a plan with views): chain colors[i *
+  // views_per_image + v] is applied to output (i, v) between the resample or filter kernel and the output format.  BORROWED
+  // like views, parallel to it, and NOT checked by the plan: the launch reports jb_color_check's status behind the plan's
+  // own.  Null: none -- the launches are those of a plan without the field.
+  const jb_color_chain *colors;
 };
 
 // a target size for jb_out_plan_, and the filter that gets there (JB_FILTER_*; 0: the exact area resize).  w = h = 0 with

@@ -279,8 +279,17 @@ jb_roi stored_rect(const jb_device_batch *b, int orientation, const jb_roi &r) {
 // stream's scratch, sub-batch by sub-batch, under the context's arithmetic and the plan's orientation.  After the pixel
 // (and orient) launches of a sub-batch, tail(i0, m, table, src) makes the launches that read it: images i0 .. i0 + m - 1,
 // image i0 + j's shown[] rectangle as tight rows of table.c[j].w x .h at src + table.c[j].tmp_offset.
+// "Colour chains": stage_per_image > 0 asks for one more region of the same scratch -- that many bytes for every image of a
+// sub-batch, counted towards the cap when images are packed, and the 32 sum words of a colour launch in front of it --
+// which the tail gets as `stage`; 0: the scratch and the packing are what they are without the parameter.
+struct ColorStage {
+  uint8_t *bytes = nullptr;            // m * stage_per_image bytes (and the slack of the scratch behind them)
+  unsigned long long *sums = nullptr;  // kJbCropsPerLaunch words
+};
+constexpr int64_t kColorSumsBytes = 256;  // kJbCropsPerLaunch 64-bit words
 template <class Tail>
-int rects_into_scratch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int orient, const jb_roi *shown, const jb_geometry &g, Tail tail) {
+int rects_into_scratch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int orient, const jb_roi *shown, const jb_geometry &g,
+                       int64_t stage_per_image, Tail tail) {
   const int64_t cap = (int64_t)ctx->knobs.resize_tmp_bytes;
   // "orientation": the rectangles are the oriented frame's; the pixel kernel writes each one's rectangle of the STORED
   // frame, jb_orient_kernel turns it into a second region of the scratch
@@ -298,14 +307,18 @@ int rects_into_scratch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int 
   const auto pack = [&](int64_t i0, int64_t *bytes, int64_t *planes) {
     int m = 1;
     *bytes = bytes_of(i0), *planes = planes_of(i0);
-    while (i0 + m < b->n_images && m < kJbCropsPerLaunch && *bytes + bytes_of(i0 + m) <= cap && *planes + planes_of(i0 + m) <= cap)
+    while (i0 + m < b->n_images && m < kJbCropsPerLaunch && *bytes + bytes_of(i0 + m) + (m + 1) * stage_per_image <= cap &&
+           *planes + planes_of(i0 + m) <= cap)
       *bytes += bytes_of(i0 + m), *planes += planes_of(i0 + m), m++;
     return m;
   };
   int64_t most = 0, most_planes = 0;  // the largest sub-batch: what the scratches must hold
+  int most_images = 0;
   for (int64_t i0 = 0; i0 < b->n_images;) {
     int64_t bytes, planes;
-    i0 += pack(i0, &bytes, &planes);
+    const int m = pack(i0, &bytes, &planes);
+    i0 += m;
+    if (m > most_images) most_images = m;
     if (bytes > most) most = bytes;
     if (planes > most_planes) most_planes = planes;
   }
@@ -314,9 +327,14 @@ int rects_into_scratch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int 
   void *tmp = nullptr, *planes_d = nullptr;
   // (oriented: `most` counts both regions; the second one starts where the first one and its slack end)
   const int64_t region = oriented ? round_up(most / 2 + (int64_t)kTmpSlack, 256) : 0;
-  int rc = tmp_for_stream(ctx, s, oriented ? (size_t)(2 * region) : (size_t)most + kTmpSlack, &tmp);
+  const size_t sources = oriented ? (size_t)(2 * region) : (size_t)most + kTmpSlack;
+  // ("colour chains": the sums and the staged outputs behind the sources)
+  const int64_t stage_at = stage_per_image > 0 ? round_up((int64_t)sources, 256) : 0;
+  int rc = tmp_for_stream(ctx, s, stage_per_image > 0 ? (size_t)(stage_at + kColorSumsBytes + most_images * stage_per_image) + kTmpSlack : sources, &tmp);
   if (rc) return rc;
   const void *const resample_src = (const uint8_t *)tmp + region;
+  ColorStage stage;
+  if (stage_per_image > 0) stage.sums = (unsigned long long *)((uint8_t *)tmp + stage_at), stage.bytes = (uint8_t *)tmp + stage_at + kColorSumsBytes;
   if (lj) rc = scratch_for_stream(ctx, ctx->planes, s, (size_t)most_planes, &planes_d);
   if (rc) return rc;
   const int per_tile = jbk_mcus_per_tile(b->desc.hs, b->desc.vs), mw = 8 * b->desc.hs, mh = 8 * b->desc.vs;
@@ -374,7 +392,7 @@ int rects_into_scratch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int 
       }
       JB_HIP(ctx, jbk_orient_launch_table(q, turn, s));
     }
-    rc = tail(i0, m, table, resample_src, s);
+    rc = tail(i0, m, table, resample_src, s, stage);
     if (rc) return rc;
     i0 += m;
   }
@@ -391,7 +409,7 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
     for (int64_t i = 0; i < b->n_images; i++)
       windows.push_back(jb_filter_window_of_(&ob.desc, &plan.crops[i], plan.inner.width, plan.inner.height, plan.filter));
   const jb_roi *const shown = plan.filter ? windows.data() : plan.crops;
-  return rects_into_scratch(ctx, b, stream, plan.orient, shown, g, [&](int64_t i0, int m, const JbCropTable &table, const void *src, hipStream_t s) {
+  return rects_into_scratch(ctx, b, stream, plan.orient, shown, g, 0, [&](int64_t i0, int m, const JbCropTable &table, const void *src, hipStream_t s, const ColorStage &) {
     if (plan.filter) {
       JbFilterTable ftable;
       memset(&ftable, 0, sizeof ftable);
@@ -402,6 +420,45 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
     }
     return (int)JB_OK;
   });
+}
+
+// "Colour chains" (plan.colors): the resample and filter launches of a tail write format 0 into the stage -- `staged` is
+// the plan they take for that, `staged_batch` the batch whose d_rgb is the stage: tight outputs of the plan's size, one
+// behind the other -- and jbk_color_launch reads them: the chain, then the plan's format at the output's own place.
+JbOutPlan staged(const JbOutPlan &plan) {
+  JbOutPlan sp = plan;
+  sp.format = JB_FMT_RGB_U8_HWC, sp.planar = false, sp.esize = 1;
+  memset(&sp.spec, 0, sizeof sp.spec);
+  return sp;
+}
+jb_device_batch staged_batch(const jb_device_batch &ob, const JbOutPlan &plan, uint8_t *stage) {
+  jb_device_batch sb = ob;
+  sb.d_rgb = stage;
+  sb.rgb_row_stride = 3LL * plan.out_w;
+  sb.rgb_image_stride = 3LL * plan.out_w * plan.out_h;
+  sb.n_images = 2;  // (resample_args: the image stride counts)
+  return sb;
+}
+// the colour launch's arguments but the rows: n staged outputs of the plan's size at `src` -> the plan's format behind dst
+JbColor color_args(const JbOutPlan &plan, const uint8_t *src, uint8_t *dst, int64_t dst_row_stride, int64_t plane_stride, int n,
+                   const ColorStage &stage) {
+  JbColor c;
+  memset(&c, 0, sizeof c);
+  c.src = src, c.dst = dst;
+  c.src_row_stride = 3LL * plan.out_w;
+  c.dst_row_stride = dst_row_stride, c.dst_plane_stride = plane_stride;
+  c.sums = stage.sums;
+  c.w = plan.out_w, c.h = plan.out_h;
+  c.n_views = n;
+  for (int k = 0; k < 3; k++) c.scale[k] = plan.spec.scale[k], c.bias[k] = plan.spec.bias[k];
+  return c;
+}
+// jb_color_check's status for the n chains of a call, as the call's own refusal (the chain's flat index is in the text)
+int colors_check(jb_ctx *ctx, const jb_color_chain *colors, int64_t n, const char *fn) {
+  const int rc = jb_color_check(colors, (int)n, nullptr);
+  if (rc == JB_OK) return JB_OK;
+  const std::string why = jb_last_error(nullptr);
+  return fail(ctx, rc, "%s: %s", fn, why.c_str());
 }
 
 // 3f. "views" (plan.views): K outputs per image from ONE pixel launch.  Per image the UNION -- the bounding rectangle of
@@ -442,8 +499,15 @@ int seam_launch_views(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
   // the outputs are b's "images": one d_rgb index per view
   jb_device_batch vb = ob;
   vb.n_images = 2;  // (resample_args: the image stride counts)
-  return rects_into_scratch(ctx, b, stream, plan.orient, unions.data(), g, [&](int64_t i0, int m, const JbCropTable &table, const void *src, hipStream_t s) {
+  // "colour chains": every output goes through the stage, and the colour kernels write what the view kernels would have
+  const bool colored = plan.colors != nullptr;
+  if (colored && (rc = colors_check(ctx, plan.colors, plan.n_views, fn)) != JB_OK) return rc;
+  const JbOutPlan sp = staged(plan);
+  const int64_t staged_bytes = 3LL * plan.out_w * plan.out_h;
+  return rects_into_scratch(ctx, b, stream, plan.orient, unions.data(), g, colored ? k * staged_bytes : 0,
+                            [&](int64_t i0, int m, const JbCropTable &table, const void *src, hipStream_t s, const ColorStage &stage) {
     const int64_t n_rows = (int64_t)m * k;
+    const jb_device_batch sb = staged_batch(vb, plan, stage.bytes);
     for (int64_t n0 = 0; n0 < n_rows; n0 += kJbCropsPerLaunch) {
       const int n = (int)(n_rows - n0 < kJbCropsPerLaunch ? n_rows - n0 : kJbCropsPerLaunch);
       const int64_t first = i0 * k + n0;  // the launch's first output
@@ -462,6 +526,18 @@ int seam_launch_views(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
         } else {
           vt.r[t] = JbViewRow{table.c[j].tmp_offset, 3 * u.width, w.x - u.x, w.y - u.y, w.width, w.height, mirror};
         }
+      }
+      if (colored) {
+        // (the stage holds the sub-batch's outputs: output n0 + t of it at index n0 + t)
+        if (plan.filter) JB_HIP(ctx, jbk_filter_launch_views(filter_args(&sb, sp, 0, src, n0, n), ft, plan.filter, JB_FMT_RGB_U8_HWC, s));
+        else JB_HIP(ctx, jbk_resample_launch_views(resample_args(&sb, sp, 0, src, n0, n), vt, JB_FMT_RGB_U8_HWC, s));
+        JbColorTable ct;
+        memset(&ct, 0, sizeof ct);
+        for (int t = 0; t < n; t++) ct.r[t] = JbColorRow{t * staged_bytes, t * vb.rgb_image_stride, plan.colors[first + t]};
+        JB_HIP(ctx, jbk_color_launch(color_args(plan, stage.bytes + n0 * staged_bytes, vb.d_rgb + first * vb.rgb_image_stride,
+                                                vb.rgb_row_stride, plane_stride, n, stage),
+                                     ct, plan.format, s));
+        continue;
       }
       if (plan.filter) JB_HIP(ctx, jbk_filter_launch_views(filter_args(&vb, plan, plane_stride, src, first, n), ft, plan.filter, plan.format, s));
       else JB_HIP(ctx, jbk_resample_launch_views(resample_args(&vb, plan, plane_stride, src, first, n), vt, plan.format, s));
@@ -526,10 +602,23 @@ int seam_launch_view_groups(jb_ctx *ctx, const jb_device_batch *b, void *stream,
     }
     unions.push_back(jb_roi{x0, y0, x1 - x0, y1 - y0});
   }
-  return rects_into_scratch(ctx, b, stream, plan.orient, unions.data(), g, [&](int64_t i0, int m, const JbCropTable &table, const void *src, hipStream_t s) {
+  // "colour chains": as in 3f; the stage of a sub-batch holds group 0's outputs of its images, then group 1's, ...
+  const bool colored = plan.colors != nullptr;
+  if (colored) {
+    const int rc = colors_check(ctx, plan.colors, plan.n_views, fn);
+    if (rc != JB_OK) return rc;
+  }
+  int64_t staged_per_image = 0;
+  for (int q = 0; q < plan.n_groups; q++) staged_per_image += 3LL * plan.groups[q].out_w * plan.groups[q].out_h * plan.groups[q].n_views;
+  return rects_into_scratch(ctx, b, stream, plan.orient, unions.data(), g, colored ? staged_per_image : 0,
+                            [&](int64_t i0, int m, const JbCropTable &table, const void *src, hipStream_t s, const ColorStage &stage) {
+    int64_t group_at = 0;  // where the group's outputs start in the stage
     for (int q = 0; q < plan.n_groups; q++) {
       const JbOutPlan::Group &gr = plan.groups[q];
       const JbOutPlan gp = jb_view_group_plan_(plan, q);
+      const int64_t staged_bytes = 3LL * gr.out_w * gr.out_h;
+      uint8_t *const group_stage = stage.bytes + group_at;
+      group_at += (int64_t)m * gr.n_views * staged_bytes;
       jb_device_batch vb = ob;  // (resample_args: dst is the group's buffer, every row brings its own offset)
       vb.d_rgb = (uint8_t *)outs[q].d_out;
       vb.rgb_row_stride = outs[q].row_stride;
@@ -553,6 +642,25 @@ int seam_launch_view_groups(jb_ctx *ctx, const jb_device_batch *b, void *stream,
           } else {
             vt.r[t] = JbViewGroupRow{JbViewRow{table.c[j].tmp_offset, 3 * u.width, w.x - u.x, w.y - u.y, w.width, w.height, mirror}, dst_offset};
           }
+        }
+        if (colored) {
+          // the rows' outputs in the stage, tight and in the launch's order; the colour rows take them to their places
+          const JbOutPlan sp = staged(gp);
+          jb_device_batch sb = staged_batch(vb, gp, group_stage);
+          sb.n_images = 1;
+          JbColorTable ct;
+          memset(&ct, 0, sizeof ct);
+          for (int t = 0; t < n; t++) {
+            const int j = (int)((n0 + t) / gr.n_views), v = (int)((n0 + t) % gr.n_views);
+            int64_t &at = gr.filter ? ft.r[t].dst_offset : vt.r[t].dst_offset;
+            ct.r[t] = JbColorRow{(n0 + t) * staged_bytes, at, plan.colors[(i0 + j) * k + gr.first + v]};
+            at = (n0 + t) * staged_bytes;
+          }
+          if (gr.filter) JB_HIP(ctx, jbk_filter_launch_view_groups(filter_args(&sb, sp, 0, src, 0, n), ft, gr.filter, JB_FMT_RGB_U8_HWC, s));
+          else JB_HIP(ctx, jbk_resample_launch_view_groups(resample_args(&sb, sp, 0, src, 0, n), vt, JB_FMT_RGB_U8_HWC, s));
+          JB_HIP(ctx, jbk_color_launch(color_args(gp, group_stage, (uint8_t *)outs[q].d_out, outs[q].row_stride, plane_strides[q], n, stage), ct,
+                                       plan.format, s));
+          continue;
         }
         if (gr.filter) JB_HIP(ctx, jbk_filter_launch_view_groups(filter_args(&vb, gp, plane_strides[q], src, 0, n), ft, gr.filter, plan.format, s));
         else JB_HIP(ctx, jbk_resample_launch_view_groups(resample_args(&vb, gp, plane_strides[q], src, 0, n), vt, plan.format, s));
@@ -840,17 +948,87 @@ int jb_blocks_to_rgb_device_views(jb_ctx *ctx, const jb_device_batch *b, const j
                      "jb_blocks_to_rgb_device_views");
 }
 
+int jb_blocks_to_rgb_device_views_color(jb_ctx *ctx, const jb_device_batch *b, const jb_view *views, int views_per_image, const jb_resize *rs,
+                                        const jb_color_chain *colors, const jb_output_spec *spec, void *stream) {
+  const char *const fn = "jb_blocks_to_rgb_device_views_color";
+  if (ctx && (!views || !rs)) return fail(ctx, JB_ERR_NULL, "%s: NULL pointer", fn);
+  if (!ctx || !b) return seam_launch(ctx, b, stream, seam_plan(ctx, b, 1, spec), fn);  // (JB_ERR_NULL)
+  const jb_image_desc frame = jb_draft_desc_(&b->desc, ctx->draft);
+  JbOutPlan plan = jb_views_plan_(&frame, spec, views, b->n_images < 0 ? 0 : b->n_images, views_per_image, rs, ctx->orientation);
+  plan.colors = colors;
+  return seam_launch(ctx, b, stream, plan, fn);
+}
+
+static int view_groups_entry(jb_ctx *ctx, const jb_device_batch *b, const jb_view *views, const jb_view_group *groups, const jb_view_output *outputs,
+                             int n_groups, const jb_color_chain *colors, const jb_output_spec *spec, void *stream, const char *fn);
+
+int jb_blocks_to_rgb_device_view_groups_color(jb_ctx *ctx, const jb_device_batch *b, const jb_view *views, const jb_view_group *groups,
+                                              const jb_view_output *outputs, int n_groups, const jb_color_chain *colors,
+                                              const jb_output_spec *spec, void *stream) {
+  return view_groups_entry(ctx, b, views, groups, outputs, n_groups, colors, spec, stream, "jb_blocks_to_rgb_device_view_groups_color");
+}
+
 int jb_blocks_to_rgb_device_view_groups(jb_ctx *ctx, const jb_device_batch *b, const jb_view *views, const jb_view_group *groups,
                                         const jb_view_output *outputs, int n_groups, const jb_output_spec *spec, void *stream) {
-  const char *const fn = "jb_blocks_to_rgb_device_view_groups";
+  return view_groups_entry(ctx, b, views, groups, outputs, n_groups, nullptr, spec, stream, "jb_blocks_to_rgb_device_view_groups");
+}
+
+static int view_groups_entry(jb_ctx *ctx, const jb_device_batch *b, const jb_view *views, const jb_view_group *groups, const jb_view_output *outputs,
+                             int n_groups, const jb_color_chain *colors, const jb_output_spec *spec, void *stream, const char *fn) {
   if (!ctx) return fail(nullptr, JB_ERR_NULL, "%s: ctx is NULL", fn);
   if (!b || !views || !groups || !outputs) return fail(ctx, JB_ERR_NULL, "%s: NULL pointer", fn);
   if (spec && spec->plane_stride != 0) return fail(ctx, JB_ERR_GEOMETRY, "%s: spec->plane_stride must be 0 (every jb_view_output has its own)", fn);
   const jb_image_desc frame = jb_draft_desc_(&b->desc, ctx->draft);
-  const JbOutPlan plan = jb_view_groups_plan_(&frame, spec, views, b->n_images < 0 ? 0 : b->n_images, groups, n_groups, ctx->orientation);
+  JbOutPlan plan = jb_view_groups_plan_(&frame, spec, views, b->n_images < 0 ? 0 : b->n_images, groups, n_groups, ctx->orientation);
+  if (plan.status == JB_OK) plan.colors = colors;
   // (a plan that has failed has no groups: outputs[0] is then all the check reads, and n_groups < 1 has none to read)
   static const jb_view_output none = {};
   return seam_launch_view_groups(ctx, b, stream, plan, n_groups >= 1 ? outputs : &none, fn);
+}
+
+int jb_color_device(jb_ctx *ctx, const uint8_t *d_in, int64_t in_row_stride, int64_t in_image_stride, int32_t w, int32_t h, int32_t n_images,
+                    const jb_color_chain *chains, void *d_out, int64_t out_row_stride, int64_t out_image_stride, const jb_output_spec *spec,
+                    void *stream) {
+  const char *const fn = "jb_color_device";
+  if (!ctx) return fail(nullptr, JB_ERR_NULL, "%s: ctx is NULL", fn);
+  if (!d_in || !chains || !d_out) return fail(ctx, JB_ERR_NULL, "%s: NULL pointer", fn);
+  if (n_images < 1) return fail(ctx, JB_ERR_GEOMETRY, "%s: n_images = %d", fn, n_images);
+  // the output as a plan describes it: a w x h frame in the spec's format (sampling and tables are not looked at)
+  const jb_image_desc frame = {w, h, 1, 1, {0, 0, 0}, 0};
+  const JbOutPlan plan = jb_out_plan_(&frame, 1, spec);
+  if (plan.status != JB_OK) return fail(ctx, plan.status, "%s: %s", fn, plan.why);
+  int64_t plane_stride = 0;
+  if (plan.planar) {
+    if (jb_output_spec_check(&plan.spec, h, out_row_stride) != JB_OK)
+      return fail(ctx, JB_ERR_GEOMETRY, "%s: bad output spec (reserved, plane_stride < row stride * height, or scale / bias not finite)", fn);
+    plane_stride = plan.spec.plane_stride ? plan.spec.plane_stride : out_row_stride * (int64_t)h;
+    if (((uintptr_t)d_out | (uint64_t)out_row_stride | (uint64_t)plane_stride | (uint64_t)(n_images > 1 ? out_image_stride : 0)) & (uint64_t)(plan.esize - 1))
+      return fail(ctx, JB_ERR_GEOMETRY, "%s: f32 / f16 output wants the pointer and every stride to be multiples of the element size", fn);
+  }
+  const int64_t one_out = plan.planar ? 2 * plane_stride + out_row_stride * (int64_t)h : out_row_stride * (int64_t)h;
+  if (in_row_stride < 3LL * w || out_row_stride < plan.row_stride)
+    return fail(ctx, JB_ERR_GEOMETRY, "%s: a row stride is smaller than one row", fn);
+  if (n_images > 1 && (in_image_stride < in_row_stride * (int64_t)(h - 1) + 3LL * w || out_image_stride < one_out))
+    return fail(ctx, JB_ERR_GEOMETRY, "%s: image strides smaller than one image", fn);
+  int rc = colors_check(ctx, chains, n_images, fn);
+  if (rc != JB_OK) return rc;
+  DeviceGuard guard(ctx->device);
+  const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  void *tmp = nullptr;
+  rc = tmp_for_stream(ctx, s, (size_t)kColorSumsBytes, &tmp);  // (the launches of a stream are ordered: one set of sums)
+  if (rc) return rc;
+  ColorStage stage;
+  stage.sums = (unsigned long long *)tmp;
+  for (int64_t i0 = 0; i0 < n_images; i0 += kJbCropsPerLaunch) {
+    const int n = (int)(n_images - i0 < kJbCropsPerLaunch ? n_images - i0 : kJbCropsPerLaunch);
+    JbColorTable ct;
+    memset(&ct, 0, sizeof ct);
+    for (int t = 0; t < n; t++) ct.r[t] = JbColorRow{(i0 + t) * (n_images > 1 ? in_image_stride : 0), (i0 + t) * (n_images > 1 ? out_image_stride : 0), chains[i0 + t]};
+    JbColor c = color_args(plan, d_in, (uint8_t *)d_out, out_row_stride, plane_stride, n, stage);
+    c.src_row_stride = in_row_stride;
+    JB_HIP(ctx, jbk_color_launch(c, ct, plan.format, s));
+  }
+  return JB_OK;
 }
 
 }  // extern "C"
