@@ -11,11 +11,12 @@
 //   wave-uniform.  A lane's 4 pixels are three 4-byte loads at any byte address (gfx950 under ROCm runs with unaligned
 //   global access enabled) -- a ragged last group of a row falls back to bytes, nothing beyond the row is touched -- and
 //   its stores are 12 bytes interleaved, 4 bytes per plane for planar uint8, 8 for f16, 16 for f32.  The store expression
-//   of the float formats is jb_resample_kernel's, operation for operation.
+//   of the float formats is jb_store.h's, operation for operation.
 #include <hip/hip_runtime.h>
 
 #include "jb_color_core.h"
 #include "jb_kernels.h"
+#include "jb_launch.h"
 
 static constexpr int kColorRows = 4;  // rows (= waves) per workgroup of the apply kernel
 static constexpr int kMeanRows = 16;  // rows per workgroup of the mean kernel
@@ -173,11 +174,6 @@ hipError_t jbk_color_launch(const JbColor &q, const JbColorTable &table, int for
     if (e != hipSuccess) return e;
   }
   const dim3 grid((unsigned)(p.tiles_x * tiles_y), (unsigned)p.n_views), block(64 * kColorRows);
-  switch (format) {
-    case 0: hipLaunchKernelGGL(jb_color_apply_kernel<0>, grid, block, 0, stream, p, table); break;
-    case 1: hipLaunchKernelGGL(jb_color_apply_kernel<1>, grid, block, 0, stream, p, table); break;
-    case 2: hipLaunchKernelGGL(jb_color_apply_kernel<2>, grid, block, 0, stream, p, table); break;
-    default: hipLaunchKernelGGL(jb_color_apply_kernel<3>, grid, block, 0, stream, p, table); break;
-  }
+  jb_by_format(format, [&](auto F) { hipLaunchKernelGGL(jb_color_apply_kernel<decltype(F)::value>, grid, block, 0, stream, p, table); });
   return hipGetLastError();
 }

@@ -14,9 +14,12 @@
 // The body also compiles for the CPU (JB_KERNELS_HOST: tools/fuzz/fit_kernel_check.cpp).
 #ifndef JB_KERNELS_HOST
 #include <hip/hip_runtime.h>
+
+#include "jb_launch.h"
 #endif
 
 #include "jb_kernels.h"
+#include "jb_store.h"
 
 static constexpr int kFitFillLanes = 256;  // elements of a band per workgroup
 
@@ -38,20 +41,7 @@ __global__ __launch_bounds__(kFitFillLanes) void jb_fit_fill_kernel(const JbFitF
   const uint32_t x = bx + (n - row * bw), y = by + row;
   uint8_t *const dst = p.dst + (int64_t)img * p.dst_image_stride + (int64_t)y * p.dst_row_stride;
 #pragma unroll
-  for (int c = 0; c < 3; c++) {
-    const uint32_t u = p.fill[c];
-    // (jb_resample_kernel's store, operation for operation)
-    if constexpr (FORMAT == 0) {
-      dst[3 * (int64_t)x + c] = (uint8_t)u;
-    } else if constexpr (FORMAT == 1) {
-      dst[(int64_t)c * p.dst_plane_stride + x] = (uint8_t)u;
-    } else {
-      const float f = (float)u * p.scale[c] + p.bias[c];
-      uint8_t *const at = dst + (int64_t)c * p.dst_plane_stride;
-      if constexpr (FORMAT == 2) ((float *)at)[x] = f;
-      else ((_Float16 *)at)[x] = (_Float16)f;
-    }
-  }
+  for (int c = 0; c < 3; c++) jb_store_element<FORMAT>(dst, p.dst_plane_stride, x, c, p.fill[c], p.scale, p.bias);
 }
 
 // the grid of a launch (wgs into p); false: an argument outside its range, or more than 2^31 - 1 workgroups.  *n_wgs = 0:
@@ -78,12 +68,7 @@ hipError_t jbk_fit_fill_launch(const JbFitFill &q, int format, hipStream_t strea
   if (!fit_fill_grid(p, format, &n_wgs)) return hipErrorInvalidValue;
   if (n_wgs == 0) return hipSuccess;
   const dim3 grid((unsigned)n_wgs), block(kFitFillLanes);
-  switch (format) {
-    case 0: hipLaunchKernelGGL(jb_fit_fill_kernel<0>, grid, block, 0, stream, p); break;
-    case 1: hipLaunchKernelGGL(jb_fit_fill_kernel<1>, grid, block, 0, stream, p); break;
-    case 2: hipLaunchKernelGGL(jb_fit_fill_kernel<2>, grid, block, 0, stream, p); break;
-    default: hipLaunchKernelGGL(jb_fit_fill_kernel<3>, grid, block, 0, stream, p); break;
-  }
+  jb_by_format(format, [&](auto F) { hipLaunchKernelGGL(jb_fit_fill_kernel<decltype(F)::value>, grid, block, 0, stream, p); });
   return hipGetLastError();
 }
 #endif  // JB_KERNELS_HOST

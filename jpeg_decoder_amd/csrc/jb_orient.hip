@@ -17,8 +17,10 @@
 #include <hip/hip_runtime.h>
 
 #include "jb_kernels.h"
+#include "jb_launch.h"
 #endif
 #include "jb_orient.h"
+#include "jb_store.h"
 
 static constexpr int kOrientPitch = kJbOrientTile + 1;     // words per LDS row
 static constexpr int kOrientRowsPerWave = kJbOrientTile / 4;
@@ -97,21 +99,7 @@ static __device__ __forceinline__ void orient_store(const JbOrient &p, const Ori
     const uint32_t px = word[k];
     uint8_t *const row = t.dst + (int64_t)oy * t.dst_row_stride;
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const uint32_t s = (px >> (8 * c)) & 0xffu;
-      if constexpr (FORMAT == 0) {
-        row[3 * (int64_t)ox + c] = (uint8_t)s;
-      } else if constexpr (FORMAT == 1) {
-        row[(int64_t)c * p.dst_plane_stride + ox] = (uint8_t)s;
-      } else {
-        // the planar store stage's expression, operation for operation: u8 -> f32 (exact), one f32 multiply, one f32 add
-        // (separate instructions: built with -ffp-contract=off), for f16 one convert (round to nearest even)
-        const float f = (float)s * p.scale[c] + p.bias[c];
-        uint8_t *const at = row + (int64_t)c * p.dst_plane_stride;
-        if constexpr (FORMAT == 2) ((float *)at)[ox] = f;
-        else ((_Float16 *)at)[ox] = (_Float16)f;
-      }
-    }
+    for (int c = 0; c < 3; c++) jb_store_element<FORMAT>(row, p.dst_plane_stride, ox, c, (px >> (8 * c)) & 0xffu, p.scale, p.bias);
   }
 }
 
@@ -146,12 +134,7 @@ hipError_t jbk_orient_launch(const JbOrient &q, int format, hipStream_t stream) 
   JbOrient p = q;
   dim3 grid;
   if (!orient_grid(p, p.sw, p.sh, &grid)) return hipErrorInvalidValue;
-  switch (format) {
-    case 0: hipLaunchKernelGGL(jb_orient_kernel<0>, grid, dim3(256), 0, stream, p); break;
-    case 1: hipLaunchKernelGGL(jb_orient_kernel<1>, grid, dim3(256), 0, stream, p); break;
-    case 2: hipLaunchKernelGGL(jb_orient_kernel<2>, grid, dim3(256), 0, stream, p); break;
-    default: hipLaunchKernelGGL(jb_orient_kernel<3>, grid, dim3(256), 0, stream, p); break;
-  }
+  jb_by_format(format, [&](auto F) { hipLaunchKernelGGL(jb_orient_kernel<decltype(F)::value>, grid, dim3(256), 0, stream, p); });
   return hipGetLastError();
 }
 

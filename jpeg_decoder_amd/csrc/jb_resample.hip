@@ -28,6 +28,7 @@
 #endif
 
 #include "jb_kernels.h"
+#include "jb_store.h"
 
 // what a kernel's table argument is: none (one geometry for the launch), a rectangle per image, a view per output, a
 // view and a destination per output ("view groups", jb_kernels.h)
@@ -137,21 +138,8 @@ __global__ __launch_bounds__(64 * kResampleRows) void jb_resample_kernel(const J
   if constexpr (GROUPS) dst_offset = dst_offset_of(table..., img);
   uint8_t *const dst = p.dst + dst_offset + (int64_t)k * p.dst_row_stride;
 #pragma unroll
-  for (int c = 0; c < 3; c++) {
-    const uint32_t u = div_to_u8(acc[c] + (d >> 1), d, rcp_d);
-    if constexpr (FORMAT == 0) {
-      dst[3 * (int64_t)js + c] = (uint8_t)u;
-    } else if constexpr (FORMAT == 1) {
-      dst[(int64_t)c * p.dst_plane_stride + js] = (uint8_t)u;
-    } else {
-      // the planar store stage's expression, operation for operation: u8 -> f32 (exact), one f32 multiply, one f32 add
-      // (separate instructions: built with -ffp-contract=off), for f16 one v_cvt_f16_f32 (round to nearest even)
-      const float f = (float)u * p.scale[c] + p.bias[c];
-      uint8_t *const at = dst + (int64_t)c * p.dst_plane_stride;
-      if constexpr (FORMAT == 2) ((float *)at)[js] = f;
-      else ((_Float16 *)at)[js] = (_Float16)f;
-    }
-  }
+  for (int c = 0; c < 3; c++)
+    jb_store_element<FORMAT>(dst, p.dst_plane_stride, js, c, div_to_u8(acc[c] + (d >> 1), d, rcp_d), p.scale, p.bias);
 }
 
 // the grid of a launch (tiles_x, tiles_y into p); false: more than 2^31 - 1 workgroups
@@ -164,85 +152,76 @@ static bool resample_grid(JbResample &p, dim3 *grid) {
   return true;
 }
 
+// ---- the launchers' checks: host code that the CPU programs of tools/fuzz compile and run too -----------------------------
+constexpr int kAnyImages = 0x7fffffff;  // max_images of a launch without a table
+
+// the launch-wide ranges: the format, the target, and the images (a table's rows) of the launch
+static bool resample_args_ok(const JbResample &p, int format, int max_images) {
+  return format >= 0 && format <= 3 && p.ow >= 1 && p.oh >= 1 && p.ow <= 65535 && p.oh <= 65535 && p.n_images >= 1 && p.n_images <= max_images;
+}
+static bool crop_row_ok(const JbCrop &c) { return c.w >= 1 && c.h >= 1 && c.w <= 65535 && c.h <= 65535 && c.tmp_offset >= 0; }
+// (the view lies in its union's row; what the union's rows hold behind it is the seam's business)
+static bool view_row_ok(const JbViewRow &v) {
+  return v.w >= 1 && v.h >= 1 && v.w <= 65535 && v.h <= 65535 && v.dx >= 0 && v.dy >= 0 && v.dy <= 65535 && v.src_offset >= 0 &&
+         v.src_row_bytes <= 3 * 65535 && 3 * ((int64_t)v.dx + v.w) <= v.src_row_bytes && !(v.mirror & ~1);
+}
+// "view groups", either table: every row's output lies behind p.dst
+template <class TABLE>
+static bool dst_offsets_ok(const TABLE &table, int n) {
+  for (int i = 0; i < n; i++)
+    if (table.r[i].dst_offset < 0) return false;
+  return true;
+}
+// the first n rows of a resample launch's table
+static bool rows_ok(const JbCropTable &table, int n) {
+  for (int i = 0; i < n; i++)
+    if (!crop_row_ok(table.c[i])) return false;
+  return true;
+}
+static bool rows_ok(const JbViewTable &table, int n) {
+  for (int i = 0; i < n; i++)
+    if (!view_row_ok(table.r[i])) return false;
+  return true;
+}
+static bool rows_ok(const JbViewGroupTable &table, int n) {
+  for (int i = 0; i < n; i++)
+    if (!view_row_ok(table.r[i].v)) return false;
+  return dst_offsets_ok(table, n);
+}
+
 #ifndef JB_KERNELS_HOST
+#include "jb_launch.h"
+
+// grid, block and the dispatch by format of every resample launch
+template <int MODE, typename... TABLE>
+static hipError_t resample_dispatch(const JbResample &q, int format, hipStream_t stream, const TABLE &...table) {
+  JbResample p = q;
+  dim3 grid;
+  if (!resample_grid(p, &grid)) return hipErrorInvalidValue;
+  jb_by_format(format, [&](auto F) {
+    hipLaunchKernelGGL((jb_resample_kernel<decltype(F)::value, MODE, TABLE...>), grid, dim3(64 * kResampleRows), 0, stream, p, table...);
+  });
+  return hipGetLastError();
+}
+// a launch with a table: at most kJbCropsPerLaunch rows, each in its ranges
+template <int MODE, class TABLE>
+static hipError_t resample_table_launch(const JbResample &q, const TABLE &table, int format, hipStream_t stream) {
+  if (!resample_args_ok(q, format, kJbCropsPerLaunch) || !rows_ok(table, q.n_images)) return hipErrorInvalidValue;
+  return resample_dispatch<MODE>(q, format, stream, table);
+}
+
 hipError_t jbk_resample_launch_views(const JbResample &q, const JbViewTable &table, int format, hipStream_t stream) {
-  if (format < 0 || format > 3 || q.ow < 1 || q.oh < 1 || q.ow > 65535 || q.oh > 65535 || q.n_images < 1 || q.n_images > kJbCropsPerLaunch)
-    return hipErrorInvalidValue;
-  for (int i = 0; i < q.n_images; i++) {
-    const JbViewRow &v = table.r[i];
-    if (v.w < 1 || v.h < 1 || v.w > 65535 || v.h > 65535 || v.dx < 0 || v.dy < 0 || v.dy > 65535 || v.src_offset < 0 || v.src_row_bytes > 3 * 65535 ||
-        3 * ((int64_t)v.dx + v.w) > v.src_row_bytes || (v.mirror & ~1))
-      return hipErrorInvalidValue;
-  }
-  JbResample p = q;
-  dim3 grid;
-  if (!resample_grid(p, &grid)) return hipErrorInvalidValue;
-  const dim3 block(64 * kResampleRows);
-  switch (format) {
-    case 0: hipLaunchKernelGGL((jb_resample_kernel<0, kViews, JbViewTable>), grid, block, 0, stream, p, table); break;
-    case 1: hipLaunchKernelGGL((jb_resample_kernel<1, kViews, JbViewTable>), grid, block, 0, stream, p, table); break;
-    case 2: hipLaunchKernelGGL((jb_resample_kernel<2, kViews, JbViewTable>), grid, block, 0, stream, p, table); break;
-    default: hipLaunchKernelGGL((jb_resample_kernel<3, kViews, JbViewTable>), grid, block, 0, stream, p, table); break;
-  }
-  return hipGetLastError();
+  return resample_table_launch<kViews>(q, table, format, stream);
 }
-
 hipError_t jbk_resample_launch_view_groups(const JbResample &q, const JbViewGroupTable &table, int format, hipStream_t stream) {
-  if (format < 0 || format > 3 || q.ow < 1 || q.oh < 1 || q.ow > 65535 || q.oh > 65535 || q.n_images < 1 || q.n_images > kJbCropsPerLaunch)
-    return hipErrorInvalidValue;
-  for (int i = 0; i < q.n_images; i++) {
-    const JbViewRow &v = table.r[i].v;
-    if (v.w < 1 || v.h < 1 || v.w > 65535 || v.h > 65535 || v.dx < 0 || v.dy < 0 || v.dy > 65535 || v.src_offset < 0 || v.src_row_bytes > 3 * 65535 ||
-        3 * ((int64_t)v.dx + v.w) > v.src_row_bytes || (v.mirror & ~1) || table.r[i].dst_offset < 0)
-      return hipErrorInvalidValue;
-  }
-  JbResample p = q;
-  dim3 grid;
-  if (!resample_grid(p, &grid)) return hipErrorInvalidValue;
-  const dim3 block(64 * kResampleRows);
-  switch (format) {
-    case 0: hipLaunchKernelGGL((jb_resample_kernel<0, kViewGroups, JbViewGroupTable>), grid, block, 0, stream, p, table); break;
-    case 1: hipLaunchKernelGGL((jb_resample_kernel<1, kViewGroups, JbViewGroupTable>), grid, block, 0, stream, p, table); break;
-    case 2: hipLaunchKernelGGL((jb_resample_kernel<2, kViewGroups, JbViewGroupTable>), grid, block, 0, stream, p, table); break;
-    default: hipLaunchKernelGGL((jb_resample_kernel<3, kViewGroups, JbViewGroupTable>), grid, block, 0, stream, p, table); break;
-  }
-  return hipGetLastError();
+  return resample_table_launch<kViewGroups>(q, table, format, stream);
 }
-
 hipError_t jbk_resample_launch_crops(const JbResample &q, const JbCropTable &table, int format, hipStream_t stream) {
-  if (format < 0 || format > 3 || q.ow < 1 || q.oh < 1 || q.ow > 65535 || q.oh > 65535 || q.n_images < 1 || q.n_images > kJbCropsPerLaunch)
-    return hipErrorInvalidValue;
-  for (int i = 0; i < q.n_images; i++)
-    if (table.c[i].w < 1 || table.c[i].h < 1 || table.c[i].w > 65535 || table.c[i].h > 65535 || table.c[i].tmp_offset < 0)
-      return hipErrorInvalidValue;
-  JbResample p = q;
-  dim3 grid;
-  if (!resample_grid(p, &grid)) return hipErrorInvalidValue;
-  const dim3 block(64 * kResampleRows);
-  switch (format) {
-    case 0: hipLaunchKernelGGL((jb_resample_kernel<0, kCrops, JbCropTable>), grid, block, 0, stream, p, table); break;
-    case 1: hipLaunchKernelGGL((jb_resample_kernel<1, kCrops, JbCropTable>), grid, block, 0, stream, p, table); break;
-    case 2: hipLaunchKernelGGL((jb_resample_kernel<2, kCrops, JbCropTable>), grid, block, 0, stream, p, table); break;
-    default: hipLaunchKernelGGL((jb_resample_kernel<3, kCrops, JbCropTable>), grid, block, 0, stream, p, table); break;
-  }
-  return hipGetLastError();
+  return resample_table_launch<kCrops>(q, table, format, stream);
 }
-
 hipError_t jbk_resample_launch(const JbResample &q, int format, hipStream_t stream) {
-  if (format < 0 || format > 3 || q.iw < 1 || q.ih < 1 || q.ow < 1 || q.oh < 1 || q.iw > 65535 || q.ih > 65535 || q.ow > 65535 ||
-      q.oh > 65535 || q.n_images < 1)
-    return hipErrorInvalidValue;
-  JbResample p = q;
-  dim3 grid;
-  if (!resample_grid(p, &grid)) return hipErrorInvalidValue;
-  const dim3 block(64 * kResampleRows);
-  switch (format) {
-    case 0: hipLaunchKernelGGL(jb_resample_kernel<0>, grid, block, 0, stream, p); break;
-    case 1: hipLaunchKernelGGL(jb_resample_kernel<1>, grid, block, 0, stream, p); break;
-    case 2: hipLaunchKernelGGL(jb_resample_kernel<2>, grid, block, 0, stream, p); break;
-    default: hipLaunchKernelGGL(jb_resample_kernel<3>, grid, block, 0, stream, p); break;
-  }
-  return hipGetLastError();
+  if (!resample_args_ok(q, format, kAnyImages) || q.iw < 1 || q.ih < 1 || q.iw > 65535 || q.ih > 65535) return hipErrorInvalidValue;
+  return resample_dispatch<kNoTable>(q, format, stream);
 }
 #endif  // JB_KERNELS_HOST
 
@@ -257,7 +236,7 @@ hipError_t jbk_resample_launch(const JbResample &q, int format, hipStream_t stre
 //      a descriptor of the source row whose range keeps every load inside the scratch; T (rounded to uint8, as Pillow
 //      rounds between the passes) goes to LDS as one word per pixel, T[row][lane]: conflict-free again.
 //   3. one barrier, then the vertical pass out of LDS: a wave = output rows wave and wave + 4, so the row, its bounds and
-//      its weights stay wave-uniform; the store is jb_resample_kernel's.
+//      its weights stay wave-uniform; the store is jb_resample_kernel's (jb_store.h).
 // kFilterRows = 8: the span of source rows is (8 - 1) * scale + taps, so per output row 1080 -> 224 bilinear filters
 // 5.6 source rows where the ideal (infinitely many rows per workgroup) is 4.8 and 4 rows per workgroup would be 6.4; 16
 // rows would double T and the accumulators for the last 8 %.  When the span is longer than the T rows that fit LDS
@@ -416,17 +395,7 @@ __global__ __launch_bounds__(256) void jb_filter_kernel(const JbFilter q, const 
 #pragma unroll
     for (int c = 0; c < 3; c++) {
       const uint32_t u = (uint32_t)clip8(acc[i][c] >> 22);
-      // (jb_resample_kernel's store, operation for operation)
-      if constexpr (FORMAT == 0) {
-        dst[3 * (int64_t)js + c] = (uint8_t)u;
-      } else if constexpr (FORMAT == 1) {
-        dst[(int64_t)c * p.dst_plane_stride + js] = (uint8_t)u;
-      } else {
-        const float f = (float)u * p.scale[c] + p.bias[c];
-        uint8_t *const at = dst + (int64_t)c * p.dst_plane_stride;
-        if constexpr (FORMAT == 2) ((float *)at)[js] = f;
-        else ((_Float16 *)at)[js] = (_Float16)f;
-      }
+      jb_store_element<FORMAT>(dst, p.dst_plane_stride, js, c, u, p.scale, p.bias);
     }
   }
 }
@@ -475,81 +444,43 @@ static size_t filter_plan(JbFilter &p, const JbFilterRow *rows, int n, int filte
 }
 
 #ifndef JB_KERNELS_HOST
-#define JB_FILTER_LAUNCH(FILTER, CROPS, ...)                                                                                  \
-  switch (format) {                                                                                                           \
-    case 0: hipLaunchKernelGGL((jb_filter_kernel<FILTER, 0, CROPS JB_FILTER_TABLE>), grid, dim3(256), lds, stream, __VA_ARGS__); break; \
-    case 1: hipLaunchKernelGGL((jb_filter_kernel<FILTER, 1, CROPS JB_FILTER_TABLE>), grid, dim3(256), lds, stream, __VA_ARGS__); break; \
-    case 2: hipLaunchKernelGGL((jb_filter_kernel<FILTER, 2, CROPS JB_FILTER_TABLE>), grid, dim3(256), lds, stream, __VA_ARGS__); break; \
-    default: hipLaunchKernelGGL((jb_filter_kernel<FILTER, 3, CROPS JB_FILTER_TABLE>), grid, dim3(256), lds, stream, __VA_ARGS__); break; \
-  }
+// the filter 1 / 2 choice and the dispatch by format of every filtered launch (p, lds, grid: filter_plan's)
+template <int MODE, typename... TABLE>
+static hipError_t filter_dispatch(const JbFilter &p, int filter, int format, size_t lds, dim3 grid, hipStream_t stream, const TABLE &...table) {
+  const auto launch = [&](auto FILTER) {
+    jb_by_format(format, [&](auto F) {
+      hipLaunchKernelGGL((jb_filter_kernel<decltype(FILTER)::value, decltype(F)::value, MODE, TABLE...>), grid, dim3(256), lds, stream, p, table...);
+    });
+  };
+  if (filter == 1) launch(std::integral_constant<int, 1>{});
+  else launch(std::integral_constant<int, 2>{});
+  return hipGetLastError();
+}
+// a filtered launch: the launch-wide ranges, filter_plan over `rows` (null: the launch's one geometry, q.one), the dispatch
+template <int MODE, typename... TABLE>
+static hipError_t filter_launch(const JbFilter &q, const JbFilterRow *rows, bool contains, int filter, int format, hipStream_t stream,
+                                const TABLE &...table) {
+  if (!resample_args_ok(q.base, format, rows ? kJbCropsPerLaunch : kAnyImages)) return hipErrorInvalidValue;
+  JbFilter p = q;
+  dim3 grid;
+  const size_t lds = filter_plan(p, rows ? rows : &p.one, rows ? p.base.n_images : 1, filter, &grid, contains);
+  if (!lds) return hipErrorInvalidValue;
+  return filter_dispatch<MODE>(p, filter, format, lds, grid, stream, table...);
+}
 
 hipError_t jbk_filter_launch(const JbFilter &q, int filter, int format, hipStream_t stream) {
-  if (format < 0 || format > 3) return hipErrorInvalidValue;
-  JbFilter p = q;
-  dim3 grid;
-  const size_t lds = filter_plan(p, &p.one, 1, filter, &grid);
-  if (!lds) return hipErrorInvalidValue;
-#define JB_FILTER_TABLE
-  if (filter == 1) {
-    JB_FILTER_LAUNCH(1, kNoTable, p)
-  } else {
-    JB_FILTER_LAUNCH(2, kNoTable, p)
-  }
-#undef JB_FILTER_TABLE
-  return hipGetLastError();
+  return filter_launch<kNoTable>(q, nullptr, false, filter, format, stream);
 }
-
 hipError_t jbk_filter_launch_crops(const JbFilter &q, const JbFilterTable &table, int filter, int format, hipStream_t stream) {
-  if (format < 0 || format > 3 || q.base.n_images < 1 || q.base.n_images > kJbCropsPerLaunch) return hipErrorInvalidValue;
-  JbFilter p = q;
-  dim3 grid;
-  const size_t lds = filter_plan(p, table.r, p.base.n_images, filter, &grid);
-  if (!lds) return hipErrorInvalidValue;
-#define JB_FILTER_TABLE , JbFilterTable
-  if (filter == 1) {
-    JB_FILTER_LAUNCH(1, kCrops, p, table)
-  } else {
-    JB_FILTER_LAUNCH(2, kCrops, p, table)
-  }
-#undef JB_FILTER_TABLE
-  return hipGetLastError();
+  return filter_launch<kCrops>(q, table.r, false, filter, format, stream, table);
 }
-
 hipError_t jbk_filter_launch_views(const JbFilter &q, const JbViewFilterTable &table, int filter, int format, hipStream_t stream) {
-  if (format < 0 || format > 3 || q.base.n_images < 1 || q.base.n_images > kJbCropsPerLaunch) return hipErrorInvalidValue;
-  JbFilter p = q;
-  dim3 grid;
-  const size_t lds = filter_plan(p, table.r, p.base.n_images, filter, &grid, true);
-  if (!lds) return hipErrorInvalidValue;
-#define JB_FILTER_TABLE , JbViewFilterTable
-  if (filter == 1) {
-    JB_FILTER_LAUNCH(1, kViews, p, table)
-  } else {
-    JB_FILTER_LAUNCH(2, kViews, p, table)
-  }
-#undef JB_FILTER_TABLE
-  return hipGetLastError();
+  return filter_launch<kViews>(q, table.r, true, filter, format, stream, table);
 }
-
 hipError_t jbk_filter_launch_view_groups(const JbFilter &q, const JbViewGroupFilterTable &table, int filter, int format, hipStream_t stream) {
-  if (format < 0 || format > 3 || q.base.n_images < 1 || q.base.n_images > kJbCropsPerLaunch) return hipErrorInvalidValue;
-  JbFilter p = q;
+  if (q.base.n_images < 1 || q.base.n_images > kJbCropsPerLaunch || !dst_offsets_ok(table, q.base.n_images)) return hipErrorInvalidValue;
   JbFilterRow rows[kJbCropsPerLaunch];  // (filter_plan takes the rows without their offsets)
-  for (int i = 0; i < p.base.n_images; i++) {
-    if (table.r[i].dst_offset < 0) return hipErrorInvalidValue;
-    rows[i] = table.r[i].f;
-  }
-  dim3 grid;
-  const size_t lds = filter_plan(p, rows, p.base.n_images, filter, &grid, true);
-  if (!lds) return hipErrorInvalidValue;
-#define JB_FILTER_TABLE , JbViewGroupFilterTable
-  if (filter == 1) {
-    JB_FILTER_LAUNCH(1, kViewGroups, p, table)
-  } else {
-    JB_FILTER_LAUNCH(2, kViewGroups, p, table)
-  }
-#undef JB_FILTER_TABLE
-  return hipGetLastError();
+  for (int i = 0; i < q.base.n_images; i++) rows[i] = table.r[i].f;
+  return filter_launch<kViewGroups>(q, rows, true, filter, format, stream, table);
 }
-#undef JB_FILTER_LAUNCH
 #endif  // JB_KERNELS_HOST

@@ -253,6 +253,35 @@ JbFilterRow filter_row(const jb_roi &r, const jb_roi &win, int64_t tmp_offset) {
   return JbFilterRow{r.x, r.y, r.width, r.height, win.x, win.y, win.width, win.height, tmp_offset};
 }
 
+// images i0 .. i0 + m - 1 of b -- the coefficient and table pointers advanced -- written to d_rgb with the given strides
+// (the strides between b's images are checked, and meaningful, only when there is more than one)
+jb_device_batch sub_batch(const jb_device_batch *b, int64_t i0, int m, uint8_t *d_rgb, int64_t row_stride, int64_t image_stride) {
+  const int64_t coef_step = b->n_images > 1 ? b->coef_image_stride : 0;
+  jb_device_batch ib = *b;
+  ib.n_images = m;
+  ib.d_coef = (const int16_t *)((const uint8_t *)b->d_coef + i0 * coef_step);
+  ib.coef_image_stride = coef_step;
+  ib.d_qtabs = (const int32_t *)((const uint8_t *)b->d_qtabs + i0 * b->qtab_image_stride);
+  ib.d_rgb = d_rgb;
+  ib.rgb_row_stride = row_stride, ib.rgb_image_stride = image_stride;
+  return ib;
+}
+
+// 3b's and 3e's second half: the filter or resample launch of a sub-batch of whole images -- i0 .. i0 + m - 1 of fb, the
+// batch with the frame the plan was made for, their sources tight at src -- into the caller's buffer
+int whole_images_tail(jb_ctx *ctx, const jb_device_batch *fb, const JbOutPlan &plan, int64_t plane_stride, const void *src, int64_t i0, int m,
+                      hipStream_t s) {
+  if (plan.filter) {
+    JbFilter f = filter_args(fb, plan, plane_stride, src, i0, m);
+    const jb_roi whole = {0, 0, fb->desc.width, fb->desc.height};
+    f.one = filter_row(plan.has_roi ? plan.roi : whole, plan.window, 0);
+    JB_HIP(ctx, jbk_filter_launch(f, plan.filter, plan.format, s));
+  } else {
+    JB_HIP(ctx, jbk_resample_launch(resample_args(fb, plan, plane_stride, src, i0, m), plan.format, s));
+  }
+  return JB_OK;
+}
+
 // "orientation": the batch as the resample and filter launches see it -- the oriented frame (of the draft frame: the two
 // never come together, seam_check has refused); everything else is b's
 jb_device_batch oriented_batch(const jb_ctx *ctx, const jb_device_batch *b, int orientation) {
@@ -338,7 +367,7 @@ int rects_into_scratch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int 
   if (lj) rc = scratch_for_stream(ctx, ctx->planes, s, (size_t)most_planes, &planes_d);
   if (rc) return rc;
   const int per_tile = jbk_mcus_per_tile(b->desc.hs, b->desc.vs), mw = 8 * b->desc.hs, mh = 8 * b->desc.vs;
-  const int64_t coef_step = b->n_images > 1 ? b->coef_image_stride : 0;
+  const jb_device_batch fb = frame_batch(ctx, b);
   for (int64_t i0 = 0; i0 < b->n_images;) {
     int64_t bytes, planes;
     const int m = pack(i0, &bytes, &planes);
@@ -359,12 +388,7 @@ int rects_into_scratch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int 
       if (c.n_tiles > most_tiles) most_tiles = c.n_tiles;
       if (jbk_lj_tiles(c.w, c.h) > most_lj_tiles) most_lj_tiles = jbk_lj_tiles(c.w, c.h);
     }
-    jb_device_batch ib = frame_batch(ctx, b);
-    ib.d_coef = (const int16_t *)((const uint8_t *)b->d_coef + i0 * coef_step);
-    ib.coef_image_stride = coef_step;
-    ib.d_qtabs = (const int32_t *)((const uint8_t *)b->d_qtabs + i0 * b->qtab_image_stride);
-    ib.d_rgb = (uint8_t *)tmp;
-    ib.rgb_row_stride = ib.rgb_image_stride = 0;  // (per image: the table's)
+    const jb_device_batch ib = sub_batch(&fb, i0, m, (uint8_t *)tmp, 0, 0);  // (the strides are per image: the table's)
     JbLaunch p = launch_base(&ib, g);
     p.roi = 2;
     p.tiles_per_image = most_tiles;
@@ -423,21 +447,13 @@ int seam_launch_crops(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
 }
 
 // "Colour chains" (plan.colors): the resample and filter launches of a tail write format 0 into the stage -- `staged` is
-// the plan they take for that, `staged_batch` the batch whose d_rgb is the stage: tight outputs of the plan's size, one
-// behind the other -- and jbk_color_launch reads them: the chain, then the plan's format at the output's own place.
+// the plan they take for that: tight outputs of the plan's size, one behind the other -- and jbk_color_launch reads them:
+// the chain, then the plan's format at the output's own place.
 JbOutPlan staged(const JbOutPlan &plan) {
   JbOutPlan sp = plan;
   sp.format = JB_FMT_RGB_U8_HWC, sp.planar = false, sp.esize = 1;
   memset(&sp.spec, 0, sizeof sp.spec);
   return sp;
-}
-jb_device_batch staged_batch(const jb_device_batch &ob, const JbOutPlan &plan, uint8_t *stage) {
-  jb_device_batch sb = ob;
-  sb.d_rgb = stage;
-  sb.rgb_row_stride = 3LL * plan.out_w;
-  sb.rgb_image_stride = 3LL * plan.out_w * plan.out_h;
-  sb.n_images = 2;  // (resample_args: the image stride counts)
-  return sb;
 }
 // the colour launch's arguments but the rows: n staged outputs of the plan's size at `src` -> the plan's format behind dst
 JbColor color_args(const JbOutPlan &plan, const uint8_t *src, uint8_t *dst, int64_t dst_row_stride, int64_t plane_stride, int n,
@@ -461,6 +477,136 @@ int colors_check(jb_ctx *ctx, const jb_color_chain *colors, int64_t n, const cha
   return fail(ctx, rc, "%s: %s", fn, why.c_str());
 }
 
+// ---- what 3f ("views") and 3g ("view groups") share ------------------------------------------------------------------------
+// the union of image i's K sources: the bounding rectangle of its views' rectangles, with a filter of their windows.
+// target_of(v) -> JbTarget: the size and the filter view v of an image is resized under.
+template <class TargetOf>
+jb_roi views_union(const jb_device_batch &ob, const JbOutPlan &plan, int64_t i, TargetOf target_of) {
+  int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+  for (int v = 0; v < plan.views_per_image; v++) {
+    const jb_view &w = plan.views[i * plan.views_per_image + v];
+    const JbTarget t = target_of(v);
+    const jb_roi r = {w.x, w.y, w.width, w.height};
+    const jb_roi src = t.filter ? jb_filter_window_of_(&ob.desc, &r, t.w, t.h, t.filter) : r;
+    if (v == 0 || src.x < x0) x0 = src.x;
+    if (v == 0 || src.y < y0) y0 = src.y;
+    if (v == 0 || src.x + src.width > x1) x1 = src.x + src.width;
+    if (v == 0 || src.y + src.height > y1) y1 = src.y + src.height;
+  }
+  return jb_roi{x0, y0, x1 - x0, y1 - y0};
+}
+
+// A RUN: the views [first, first + n) of every image of the call, resized under one plan -- its target, filter and format --
+// into one buffer: output (i, v - first) lies at dst + i * image_stride + (v - first) * view_stride.  "Views" is one run
+// of all K views under the call's plan, "view groups" one run per group under jb_view_group_plan_.
+struct ViewRun {
+  JbOutPlan plan;
+  int first, n;
+  uint8_t *dst;
+  int64_t row_stride, plane_stride, image_stride, view_stride;
+};
+// the rows of one launch, area or filtered, every one with its output's place behind the launch's dst
+struct ViewRows {
+  JbViewGroupTable area;
+  JbViewGroupFilterTable filtered;
+};
+
+// n rows under `rp` (a run's plan, or `staged` of it) -> dst, rows row_stride and planes plane_stride apart.  The ONE place
+// that knows the two table flavours: under a call with groups every row travels with its place (the kViewGroups
+// launches); under one without, the rows lie `stride` apart from the first one's place on and travel without theirs (the
+// kViews launches).  The call's plan decides, not the spacing the rows happen to have.
+int launch_view_rows(jb_ctx *ctx, const jb_device_batch &ob, const JbOutPlan &rp, bool grouped, const ViewRows &rows, int n, uint8_t *dst,
+                     int64_t row_stride, int64_t plane_stride, int64_t stride, const void *src, hipStream_t s) {
+  jb_device_batch rb = ob;  // (resample_args: one "image" at dst -- where the others are is said below, or by the rows)
+  rb.d_rgb = dst, rb.rgb_row_stride = row_stride, rb.n_images = 1;
+  JbFilter f = filter_args(&rb, rp, plane_stride, src, 0, n);
+  if (grouped) {
+    if (rp.filter) JB_HIP(ctx, jbk_filter_launch_view_groups(f, rows.filtered, rp.filter, rp.format, s));
+    else JB_HIP(ctx, jbk_resample_launch_view_groups(f.base, rows.area, rp.format, s));
+    return JB_OK;
+  }
+  f.base.dst += rp.filter ? rows.filtered.r[0].dst_offset : rows.area.r[0].dst_offset;
+  f.base.dst_image_stride = stride;
+  if (rp.filter) {
+    JbViewFilterTable ft;
+    memset(&ft, 0, sizeof ft);
+    for (int t = 0; t < n; t++) ft.r[t] = rows.filtered.r[t].f;
+    ft.mirror = rows.filtered.mirror;
+    JB_HIP(ctx, jbk_filter_launch_views(f, ft, rp.filter, rp.format, s));
+  } else {
+    JbViewTable vt;
+    memset(&vt, 0, sizeof vt);
+    for (int t = 0; t < n; t++) vt.r[t] = rows.area.r[t].v;
+    JB_HIP(ctx, jbk_resample_launch_views(f.base, vt, rp.format, s));
+  }
+  return JB_OK;
+}
+
+// a run's outputs of a sub-batch -- images i0 .. i0 + m - 1, image i0 + j's union at src + table.c[j].tmp_offset -- cut into
+// launches of kJbCropsPerLaunch rows, so one pixel launch may be followed by several.  plan: the call's (its views, chains
+// and K).  "Colour chains": the rows go to run_stage instead -- the run's m * n outputs in format 0, tight, in the run's order
+// -- and a colour launch takes them from there to their places.
+int launch_run(jb_ctx *ctx, const jb_device_batch &ob, const JbOutPlan &plan, const ViewRun &run, const jb_roi *unions, const JbCropTable &table,
+               int64_t i0, int m, const void *src, hipStream_t s, const ColorStage &stage, uint8_t *run_stage) {
+  const bool grouped = plan.n_groups > 0, colored = plan.colors != nullptr;
+  const int64_t staged_bytes = 3LL * run.plan.out_w * run.plan.out_h;
+  const int64_t n_rows = (int64_t)m * run.n;
+  for (int64_t n0 = 0; n0 < n_rows; n0 += kJbCropsPerLaunch) {
+    const int n = (int)(n_rows - n0 < kJbCropsPerLaunch ? n_rows - n0 : kJbCropsPerLaunch);
+    ViewRows rows;
+    JbColorTable ct;
+    memset(&rows, 0, sizeof rows);
+    memset(&ct, 0, sizeof ct);
+    for (int t = 0; t < n; t++) {
+      const int j = (int)((n0 + t) / run.n), v = (int)((n0 + t) % run.n);    // the image of the sub-batch, the view of the run
+      const int64_t flat = (i0 + j) * plan.views_per_image + run.first + v;  // the caller's index of the view and of its chain
+      const jb_view &w = plan.views[flat];
+      const jb_roi &u = unions[i0 + j];
+      const int mirror = (w.flags & JB_VIEW_MIRROR) ? 1 : 0;
+      int64_t at = (i0 + j) * run.image_stride + v * run.view_stride;  // the output's place behind run.dst
+      if (colored) {
+        ct.r[t] = JbColorRow{(n0 + t) * staged_bytes, at, plan.colors[flat]};
+        at = (n0 + t) * staged_bytes;
+      }
+      if (run.plan.filter) {
+        rows.filtered.r[t] = JbViewGroupFilterRow{filter_row(jb_roi{w.x, w.y, w.width, w.height}, u, table.c[j].tmp_offset), at};
+        rows.filtered.mirror |= (uint32_t)mirror << t;
+      } else {
+        rows.area.r[t] = JbViewGroupRow{JbViewRow{table.c[j].tmp_offset, 3 * u.width, w.x - u.x, w.y - u.y, w.width, w.height, mirror}, at};
+      }
+    }
+    const int rc = colored ? launch_view_rows(ctx, ob, staged(run.plan), grouped, rows, n, run_stage, 3LL * run.plan.out_w, 0, staged_bytes, src, s)
+                           : launch_view_rows(ctx, ob, run.plan, grouped, rows, n, run.dst, run.row_stride, run.plane_stride, run.view_stride, src, s);
+    if (rc) return rc;
+    if (colored)
+      JB_HIP(ctx, jbk_color_launch(color_args(run.plan, run_stage, run.dst, run.row_stride, run.plane_stride, n, stage), ct, plan.format, s));
+  }
+  return JB_OK;
+}
+
+// the launches of a call with views, behind its checks: every image's union through 3c's first half, then run by run
+// the tail above.  "Colour chains": the chains are checked here, and the stage of a sub-batch holds run 0's outputs of its
+// images, then run 1's, ...
+int launch_view_runs(jb_ctx *ctx, const jb_device_batch *b, const jb_device_batch &ob, void *stream, const JbOutPlan &plan, const jb_geometry &g,
+                     const std::vector<jb_roi> &unions, const ViewRun *runs, int n_runs, const char *fn) {
+  const bool colored = plan.colors != nullptr;
+  if (colored)
+    if (const int rc = colors_check(ctx, plan.colors, plan.n_views, fn)) return rc;
+  const auto staged_bytes_of = [&](int q) { return 3LL * runs[q].plan.out_w * runs[q].plan.out_h * runs[q].n; };  // of a run, per image
+  int64_t staged_per_image = 0;
+  for (int q = 0; q < n_runs; q++) staged_per_image += staged_bytes_of(q);
+  return rects_into_scratch(ctx, b, stream, plan.orient, unions.data(), g, colored ? staged_per_image : 0,
+                            [&](int64_t i0, int m, const JbCropTable &table, const void *src, hipStream_t s, const ColorStage &stage) {
+    uint8_t *run_stage = stage.bytes;
+    for (int q = 0; q < n_runs; q++) {
+      const int rc = launch_run(ctx, ob, plan, runs[q], unions.data(), table, i0, m, src, s, stage, run_stage);
+      if (rc) return rc;
+      if (colored) run_stage += m * staged_bytes_of(q);
+    }
+    return (int)JB_OK;
+  });
+}
+
 // 3f. "views" (plan.views): K outputs per image from ONE pixel launch.  Per image the UNION -- the bounding rectangle of
 // its K rectangles, with a filter of their K windows -- goes through 3c's first half; the view kernels then read K
 // sub-rectangles of each union, kJbCropsPerLaunch outputs a launch, so one pixel launch may be followed by several.
@@ -481,69 +627,12 @@ int seam_launch_views(jb_ctx *ctx, const jb_device_batch *b, void *stream, const
     if (rc) return rc;
   }
   const jb_device_batch ob = oriented_batch(ctx, b, plan.orient);
-  // every image's union of its views' sources -- a view's rectangle, with a filter its window
   std::vector<jb_roi> unions;
-  for (int64_t i = 0; i < b->n_images; i++) {
-    int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
-    for (int v = 0; v < k; v++) {
-      const jb_view &w = plan.views[i * k + v];
-      const jb_roi r = {w.x, w.y, w.width, w.height};
-      const jb_roi src = plan.filter ? jb_filter_window_of_(&ob.desc, &r, plan.inner.width, plan.inner.height, plan.filter) : r;
-      if (v == 0 || src.x < x0) x0 = src.x;
-      if (v == 0 || src.y < y0) y0 = src.y;
-      if (v == 0 || src.x + src.width > x1) x1 = src.x + src.width;
-      if (v == 0 || src.y + src.height > y1) y1 = src.y + src.height;
-    }
-    unions.push_back(jb_roi{x0, y0, x1 - x0, y1 - y0});
-  }
-  // the outputs are b's "images": one d_rgb index per view
-  jb_device_batch vb = ob;
-  vb.n_images = 2;  // (resample_args: the image stride counts)
-  // "colour chains": every output goes through the stage, and the colour kernels write what the view kernels would have
-  const bool colored = plan.colors != nullptr;
-  if (colored && (rc = colors_check(ctx, plan.colors, plan.n_views, fn)) != JB_OK) return rc;
-  const JbOutPlan sp = staged(plan);
-  const int64_t staged_bytes = 3LL * plan.out_w * plan.out_h;
-  return rects_into_scratch(ctx, b, stream, plan.orient, unions.data(), g, colored ? k * staged_bytes : 0,
-                            [&](int64_t i0, int m, const JbCropTable &table, const void *src, hipStream_t s, const ColorStage &stage) {
-    const int64_t n_rows = (int64_t)m * k;
-    const jb_device_batch sb = staged_batch(vb, plan, stage.bytes);
-    for (int64_t n0 = 0; n0 < n_rows; n0 += kJbCropsPerLaunch) {
-      const int n = (int)(n_rows - n0 < kJbCropsPerLaunch ? n_rows - n0 : kJbCropsPerLaunch);
-      const int64_t first = i0 * k + n0;  // the launch's first output
-      JbViewTable vt;
-      JbViewFilterTable ft;
-      memset(&vt, 0, sizeof vt);
-      memset(&ft, 0, sizeof ft);
-      for (int t = 0; t < n; t++) {
-        const int j = (int)((n0 + t) / k);  // the image of the sub-batch
-        const jb_view &w = plan.views[first + t];
-        const jb_roi &u = unions[i0 + j];
-        const int mirror = (w.flags & JB_VIEW_MIRROR) ? 1 : 0;
-        if (plan.filter) {
-          ft.r[t] = filter_row(jb_roi{w.x, w.y, w.width, w.height}, u, table.c[j].tmp_offset);
-          ft.mirror |= (uint32_t)mirror << t;
-        } else {
-          vt.r[t] = JbViewRow{table.c[j].tmp_offset, 3 * u.width, w.x - u.x, w.y - u.y, w.width, w.height, mirror};
-        }
-      }
-      if (colored) {
-        // (the stage holds the sub-batch's outputs: output n0 + t of it at index n0 + t)
-        if (plan.filter) JB_HIP(ctx, jbk_filter_launch_views(filter_args(&sb, sp, 0, src, n0, n), ft, plan.filter, JB_FMT_RGB_U8_HWC, s));
-        else JB_HIP(ctx, jbk_resample_launch_views(resample_args(&sb, sp, 0, src, n0, n), vt, JB_FMT_RGB_U8_HWC, s));
-        JbColorTable ct;
-        memset(&ct, 0, sizeof ct);
-        for (int t = 0; t < n; t++) ct.r[t] = JbColorRow{t * staged_bytes, t * vb.rgb_image_stride, plan.colors[first + t]};
-        JB_HIP(ctx, jbk_color_launch(color_args(plan, stage.bytes + n0 * staged_bytes, vb.d_rgb + first * vb.rgb_image_stride,
-                                                vb.rgb_row_stride, plane_stride, n, stage),
-                                     ct, plan.format, s));
-        continue;
-      }
-      if (plan.filter) JB_HIP(ctx, jbk_filter_launch_views(filter_args(&vb, plan, plane_stride, src, first, n), ft, plan.filter, plan.format, s));
-      else JB_HIP(ctx, jbk_resample_launch_views(resample_args(&vb, plan, plane_stride, src, first, n), vt, plan.format, s));
-    }
-    return (int)JB_OK;
-  });
+  for (int64_t i = 0; i < b->n_images; i++)
+    unions.push_back(views_union(ob, plan, i, [&](int) { return JbTarget{plan.inner.width, plan.inner.height, plan.filter, 0}; }));
+  // one run: the outputs are b's "images", one d_rgb index per view, K of them per image
+  const ViewRun run = {plan, 0, k, b->d_rgb, b->rgb_row_stride, plane_stride, k * b->rgb_image_stride, b->rgb_image_stride};
+  return launch_view_runs(ctx, b, ob, stream, plan, g, unions, &run, 1, fn);
 }
 
 // 3g. "view groups" (plan.n_groups): 3f with a target and a filter per GROUP of an image's views.  The union of an image is
@@ -586,88 +675,18 @@ int seam_launch_view_groups(jb_ctx *ctx, const jb_device_batch *b, void *stream,
     while (v >= plan.groups[q].first + plan.groups[q].n_views) q++;
     return q;
   };
-  // every image's union of its views' sources -- a view's rectangle, with a filter its window at ITS group's target
+  // every view under ITS group's target and filter; one run per group, into the group's buffer
   std::vector<jb_roi> unions;
-  for (int64_t i = 0; i < b->n_images; i++) {
-    int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
-    for (int v = 0; v < k; v++) {
-      const jb_view &w = plan.views[i * k + v];
+  for (int64_t i = 0; i < b->n_images; i++)
+    unions.push_back(views_union(ob, plan, i, [&](int v) {
       const JbOutPlan::Group &gr = plan.groups[group_of(v)];
-      const jb_roi r = {w.x, w.y, w.width, w.height};
-      const jb_roi src = gr.filter ? jb_filter_window_of_(&ob.desc, &r, gr.out_w, gr.out_h, gr.filter) : r;
-      if (v == 0 || src.x < x0) x0 = src.x;
-      if (v == 0 || src.y < y0) y0 = src.y;
-      if (v == 0 || src.x + src.width > x1) x1 = src.x + src.width;
-      if (v == 0 || src.y + src.height > y1) y1 = src.y + src.height;
-    }
-    unions.push_back(jb_roi{x0, y0, x1 - x0, y1 - y0});
-  }
-  // "colour chains": as in 3f; the stage of a sub-batch holds group 0's outputs of its images, then group 1's, ...
-  const bool colored = plan.colors != nullptr;
-  if (colored) {
-    const int rc = colors_check(ctx, plan.colors, plan.n_views, fn);
-    if (rc != JB_OK) return rc;
-  }
-  int64_t staged_per_image = 0;
-  for (int q = 0; q < plan.n_groups; q++) staged_per_image += 3LL * plan.groups[q].out_w * plan.groups[q].out_h * plan.groups[q].n_views;
-  return rects_into_scratch(ctx, b, stream, plan.orient, unions.data(), g, colored ? staged_per_image : 0,
-                            [&](int64_t i0, int m, const JbCropTable &table, const void *src, hipStream_t s, const ColorStage &stage) {
-    int64_t group_at = 0;  // where the group's outputs start in the stage
-    for (int q = 0; q < plan.n_groups; q++) {
-      const JbOutPlan::Group &gr = plan.groups[q];
-      const JbOutPlan gp = jb_view_group_plan_(plan, q);
-      const int64_t staged_bytes = 3LL * gr.out_w * gr.out_h;
-      uint8_t *const group_stage = stage.bytes + group_at;
-      group_at += (int64_t)m * gr.n_views * staged_bytes;
-      jb_device_batch vb = ob;  // (resample_args: dst is the group's buffer, every row brings its own offset)
-      vb.d_rgb = (uint8_t *)outs[q].d_out;
-      vb.rgb_row_stride = outs[q].row_stride;
-      vb.n_images = 1;
-      const int64_t n_rows = (int64_t)m * gr.n_views;
-      for (int64_t n0 = 0; n0 < n_rows; n0 += kJbCropsPerLaunch) {
-        const int n = (int)(n_rows - n0 < kJbCropsPerLaunch ? n_rows - n0 : kJbCropsPerLaunch);
-        JbViewGroupTable vt;
-        JbViewGroupFilterTable ft;
-        memset(&vt, 0, sizeof vt);
-        memset(&ft, 0, sizeof ft);
-        for (int t = 0; t < n; t++) {
-          const int j = (int)((n0 + t) / gr.n_views), v = (int)((n0 + t) % gr.n_views);  // the image of the sub-batch, the view of the group
-          const jb_view &w = plan.views[(i0 + j) * k + gr.first + v];
-          const jb_roi &u = unions[i0 + j];
-          const int mirror = (w.flags & JB_VIEW_MIRROR) ? 1 : 0;
-          const int64_t dst_offset = (i0 + j) * outs[q].image_stride + v * outs[q].view_stride;
-          if (gr.filter) {
-            ft.r[t] = JbViewGroupFilterRow{filter_row(jb_roi{w.x, w.y, w.width, w.height}, u, table.c[j].tmp_offset), dst_offset};
-            ft.mirror |= (uint32_t)mirror << t;
-          } else {
-            vt.r[t] = JbViewGroupRow{JbViewRow{table.c[j].tmp_offset, 3 * u.width, w.x - u.x, w.y - u.y, w.width, w.height, mirror}, dst_offset};
-          }
-        }
-        if (colored) {
-          // the rows' outputs in the stage, tight and in the launch's order; the colour rows take them to their places
-          const JbOutPlan sp = staged(gp);
-          jb_device_batch sb = staged_batch(vb, gp, group_stage);
-          sb.n_images = 1;
-          JbColorTable ct;
-          memset(&ct, 0, sizeof ct);
-          for (int t = 0; t < n; t++) {
-            const int j = (int)((n0 + t) / gr.n_views), v = (int)((n0 + t) % gr.n_views);
-            int64_t &at = gr.filter ? ft.r[t].dst_offset : vt.r[t].dst_offset;
-            ct.r[t] = JbColorRow{(n0 + t) * staged_bytes, at, plan.colors[(i0 + j) * k + gr.first + v]};
-            at = (n0 + t) * staged_bytes;
-          }
-          if (gr.filter) JB_HIP(ctx, jbk_filter_launch_view_groups(filter_args(&sb, sp, 0, src, 0, n), ft, gr.filter, JB_FMT_RGB_U8_HWC, s));
-          else JB_HIP(ctx, jbk_resample_launch_view_groups(resample_args(&sb, sp, 0, src, 0, n), vt, JB_FMT_RGB_U8_HWC, s));
-          JB_HIP(ctx, jbk_color_launch(color_args(gp, group_stage, (uint8_t *)outs[q].d_out, outs[q].row_stride, plane_strides[q], n, stage), ct,
-                                       plan.format, s));
-          continue;
-        }
-        if (gr.filter) JB_HIP(ctx, jbk_filter_launch_view_groups(filter_args(&vb, gp, plane_strides[q], src, 0, n), ft, gr.filter, plan.format, s));
-        else JB_HIP(ctx, jbk_resample_launch_view_groups(resample_args(&vb, gp, plane_strides[q], src, 0, n), vt, plan.format, s));
-      }
-    }
-    return (int)JB_OK;
-  });
+      return JbTarget{gr.out_w, gr.out_h, gr.filter, 0};
+    }));
+  std::vector<ViewRun> runs;
+  for (int q = 0; q < plan.n_groups; q++)
+    runs.push_back(ViewRun{jb_view_group_plan_(plan, q), plan.groups[q].first, plan.groups[q].n_views, (uint8_t *)outs[q].d_out, outs[q].row_stride,
+                           plane_strides[q], outs[q].image_stride, outs[q].view_stride});
+  return launch_view_runs(ctx, b, ob, stream, plan, g, unions, runs.data(), plan.n_groups, fn);
 }
 
 // 3b. a plan with a target size: two launches per sub-batch, in stream order -- the pixel kernel (full size or the
@@ -694,28 +713,13 @@ int seam_launch_resized(jb_ctx *ctx, const jb_device_batch *b, void *stream, con
   void *tmp = nullptr;
   rc = tmp_for_stream(ctx, s, (size_t)(per * plan.tmp_image_bytes) + kTmpSlack, &tmp);
   if (rc) return rc;
-  // (the strides between images are checked, and meaningful, only when there is more than one)
-  const int64_t coef_step = b->n_images > 1 ? b->coef_image_stride : 0;
   for (int64_t i0 = 0; i0 < b->n_images; i0 += per) {
     const int m = (int)(b->n_images - i0 < per ? b->n_images - i0 : per);
-    jb_device_batch ib = *b;
-    ib.n_images = m;
-    ib.d_coef = (const int16_t *)((const uint8_t *)b->d_coef + i0 * coef_step);
-    ib.coef_image_stride = coef_step;
-    ib.d_qtabs = (const int32_t *)((const uint8_t *)b->d_qtabs + i0 * b->qtab_image_stride);
-    ib.d_rgb = (uint8_t *)tmp;
-    ib.rgb_row_stride = inner.row_stride;
-    ib.rgb_image_stride = plan.tmp_image_bytes;
+    const jb_device_batch ib = sub_batch(b, i0, m, (uint8_t *)tmp, inner.row_stride, plan.tmp_image_bytes);
     rc = seam_launch(ctx, &ib, s, inner, fn);
     if (rc) return rc;
-    if (plan.filter) {
-      JbFilter f = filter_args(&fb, plan, plane_stride, tmp, i0, m);
-      const jb_roi whole = {0, 0, fb.desc.width, fb.desc.height};
-      f.one = filter_row(plan.has_roi ? plan.roi : whole, plan.window, 0);
-      JB_HIP(ctx, jbk_filter_launch(f, plan.filter, plan.format, s));
-    } else {
-      JB_HIP(ctx, jbk_resample_launch(resample_args(b, plan, plane_stride, tmp, i0, m), plan.format, s));
-    }
+    rc = whole_images_tail(ctx, &fb, plan, plane_stride, tmp, i0, m, s);
+    if (rc) return rc;
   }
   // JB_FIT_PAD: the border of every image of the call in one launch.  Bands and inner rectangles are disjoint, so its place
   // on the stream is free: behind the last sub-batch, so that a sub-batch that fails leaves the bands alone
@@ -758,17 +762,10 @@ int seam_launch_oriented(jb_ctx *ctx, const jb_device_batch *b, void *stream, co
   rc = tmp_for_stream(ctx, s, (size_t)(n_regions * region), &tmp);
   if (rc) return rc;
   uint8_t *const turned = (uint8_t *)tmp + region;  // (the second region)
-  const int64_t coef_step = b->n_images > 1 ? b->coef_image_stride : 0, rgb_step = b->n_images > 1 ? b->rgb_image_stride : 0;
+  const int64_t rgb_step = b->n_images > 1 ? b->rgb_image_stride : 0;
   for (int64_t i0 = 0; i0 < b->n_images; i0 += per) {
     const int m = (int)(b->n_images - i0 < per ? b->n_images - i0 : per);
-    jb_device_batch ib = *b;
-    ib.n_images = m;
-    ib.d_coef = (const int16_t *)((const uint8_t *)b->d_coef + i0 * coef_step);
-    ib.coef_image_stride = coef_step;
-    ib.d_qtabs = (const int32_t *)((const uint8_t *)b->d_qtabs + i0 * b->qtab_image_stride);
-    ib.d_rgb = (uint8_t *)tmp;
-    ib.rgb_row_stride = inner.row_stride;
-    ib.rgb_image_stride = image_bytes;
+    const jb_device_batch ib = sub_batch(b, i0, m, (uint8_t *)tmp, inner.row_stride, image_bytes);
     rc = seam_launch(ctx, &ib, s, inner, fn);
     if (rc) return rc;
     JbOrient q;
@@ -791,13 +788,8 @@ int seam_launch_oriented(jb_ctx *ctx, const jb_device_batch *b, void *stream, co
     q.dst_image_stride = image_bytes;
     q.dst_row_stride = 3LL * shown.width;
     JB_HIP(ctx, jbk_orient_launch(q, JB_FMT_RGB_U8_HWC, s));
-    if (plan.filter) {
-      JbFilter f = filter_args(&ob, plan, plane_stride, turned, i0, m);
-      f.one = filter_row(plan.has_roi ? plan.roi : whole, plan.window, 0);
-      JB_HIP(ctx, jbk_filter_launch(f, plan.filter, plan.format, s));
-    } else {
-      JB_HIP(ctx, jbk_resample_launch(resample_args(&ob, plan, plane_stride, turned, i0, m), plan.format, s));
-    }
+    rc = whole_images_tail(ctx, &ob, plan, plane_stride, turned, i0, m, s);
+    if (rc) return rc;
   }
   if (plan.fit_mode == JB_FIT_PAD) JB_HIP(ctx, jbk_fit_fill_launch(fill_args(b, plan, plane_stride, 0, b->n_images), plan.format, s));  // (as in 3b: last)
   return JB_OK;
@@ -939,18 +931,21 @@ int jb_blocks_to_rgb_device_crops_filtered(jb_ctx *ctx, const jb_device_batch *b
                      "jb_blocks_to_rgb_device_crops_filtered");
 }
 
+static int views_entry(jb_ctx *ctx, const jb_device_batch *b, const jb_view *views, int views_per_image, const jb_resize *rs,
+                       const jb_color_chain *colors, const jb_output_spec *spec, void *stream, const char *fn);
+
 int jb_blocks_to_rgb_device_views(jb_ctx *ctx, const jb_device_batch *b, const jb_view *views, int views_per_image, const jb_resize *rs,
                                   const jb_output_spec *spec, void *stream) {
-  if (ctx && (!views || !rs)) return fail(ctx, JB_ERR_NULL, "jb_blocks_to_rgb_device_views: NULL pointer");
-  if (!ctx || !b) return seam_launch(ctx, b, stream, seam_plan(ctx, b, 1, spec), "jb_blocks_to_rgb_device_views");  // (JB_ERR_NULL)
-  const jb_image_desc frame = jb_draft_desc_(&b->desc, ctx->draft);
-  return seam_launch(ctx, b, stream, jb_views_plan_(&frame, spec, views, b->n_images < 0 ? 0 : b->n_images, views_per_image, rs, ctx->orientation),
-                     "jb_blocks_to_rgb_device_views");
+  return views_entry(ctx, b, views, views_per_image, rs, nullptr, spec, stream, "jb_blocks_to_rgb_device_views");
 }
 
 int jb_blocks_to_rgb_device_views_color(jb_ctx *ctx, const jb_device_batch *b, const jb_view *views, int views_per_image, const jb_resize *rs,
                                         const jb_color_chain *colors, const jb_output_spec *spec, void *stream) {
-  const char *const fn = "jb_blocks_to_rgb_device_views_color";
+  return views_entry(ctx, b, views, views_per_image, rs, colors, spec, stream, "jb_blocks_to_rgb_device_views_color");
+}
+
+static int views_entry(jb_ctx *ctx, const jb_device_batch *b, const jb_view *views, int views_per_image, const jb_resize *rs,
+                       const jb_color_chain *colors, const jb_output_spec *spec, void *stream, const char *fn) {
   if (ctx && (!views || !rs)) return fail(ctx, JB_ERR_NULL, "%s: NULL pointer", fn);
   if (!ctx || !b) return seam_launch(ctx, b, stream, seam_plan(ctx, b, 1, spec), fn);  // (JB_ERR_NULL)
   const jb_image_desc frame = jb_draft_desc_(&b->desc, ctx->draft);

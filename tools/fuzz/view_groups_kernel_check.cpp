@@ -275,6 +275,10 @@ static void one(int filter, int fmt, bool mirror, int pad_row, int pad_plane, in
                                   i * block + (n % gk[g]) * view[g]};
       }
       dim3 grid;
+      if (!resample_args_ok(a.p, fmt, kJbCropsPerLaunch) || !rows_ok(a.t, N * gk[g])) {
+        printf("FAIL: the launch validation refuses format %d group %d\n", fmt, g);
+        exit(1);
+      }
       if (!resample_grid(a.p, &grid)) exit(2);
       void (*const bodies[4])(const void *) = {area_body<0>, area_body<1>, area_body<2>, area_body<3>};
       run(Launch{bodies[fmt], &a, grid.x, 64u * kResampleRows, 0});
@@ -291,7 +295,8 @@ static void one(int filter, int fmt, bool mirror, int pad_row, int pad_plane, in
         if (flag(i, v)) a.t.mirror |= 1u << n;
       }
       dim3 grid;
-      const size_t lds = filter_plan(a.q, rows, N * gk[g], filter, &grid, true);
+      const bool args_ok = resample_args_ok(a.q.base, fmt, kJbCropsPerLaunch) && dst_offsets_ok(a.t, N * gk[g]);
+      const size_t lds = args_ok ? filter_plan(a.q, rows, N * gk[g], filter, &grid, true) : 0;
       if (!lds) {
         printf("FAIL: filter_plan refuses filter %d group %d\n", filter, g);
         exit(1);
@@ -335,6 +340,33 @@ static void one(int filter, int fmt, bool mirror, int pad_row, int pad_plane, in
   n_cases++;
 }
 
+// ---- the launchers' checks of a group row (jb_resample.hip: rows_ok of a JbViewGroupTable, dst_offsets_ok): from an accepted
+// table of two rows, a second row with dst_offset = -1 must be refused, in either kind of table ------------------------------
+static long n_validation = 0;
+static void expect(bool accepted, bool want, const char *what) {
+  if (accepted != want) {
+    printf("FAIL: the launch validation %s %s\n", accepted ? "accepts" : "refuses", what);
+    exit(1);
+  }
+  n_validation++;
+}
+static void validation() {
+  JbViewGroupTable at;
+  JbViewGroupFilterTable ft;
+  memset(&at, 0, sizeof at);
+  memset(&ft, 0, sizeof ft);
+  for (int i = 0; i < 2; i++) {
+    at.r[i] = JbViewGroupRow{JbViewRow{8100LL * i, 3 * 90, 3, 2, 20, 10, i}, 1890LL * i};
+    ft.r[i].dst_offset = 1890LL * i;  // (the filtered rows themselves are filter_plan's to check)
+  }
+  expect(rows_ok(at, 2) && dst_offsets_ok(ft, 2), true, "the tables the refused ones are made from");
+  at.r[1].dst_offset = -1, ft.r[1].dst_offset = -1;
+  expect(rows_ok(at, 2), false, "a group row with dst_offset = -1");
+  expect(dst_offsets_ok(ft, 2), false, "a filtered group row with dst_offset = -1");
+  at.r[1].dst_offset = 0, at.r[1].v.w = 0;
+  expect(rows_ok(at, 2), false, "a group row whose view has w = 0");
+}
+
 int main() {
   for (int filter = 0; filter <= 2; filter++)
     for (int fmt = 0; fmt < 4; fmt++)
@@ -343,5 +375,7 @@ int main() {
         one(filter, fmt, mirror != 0, 1, 5, 3, 7);  // padded: every gap keeps the sentinel
       }
   printf("%ld view group kernel cases ok\n", n_cases);
+  validation();
+  printf("%ld launch validation cases ok\n", n_validation);
   return 0;
 }

@@ -259,6 +259,10 @@ static void one(int filter, int fmt, int ow, int oh, bool mirror, int pad_row, i
       a.t.r[n] = JbViewRow{offset[i], 3 * uni[i].w, views[i][v].x - uni[i].x, views[i][v].y - uni[i].y, views[i][v].w, views[i][v].h, flag(n) ? 1 : 0};
     }
     dim3 grid;
+    if (!resample_args_ok(a.p, fmt, kJbCropsPerLaunch) || !rows_ok(a.t, n_out)) {
+      printf("FAIL: the launch validation refuses format %d target %dx%d\n", fmt, ow, oh);
+      exit(1);
+    }
     if (!resample_grid(a.p, &grid)) exit(2);
     void (*const bodies[4])(const void *) = {area_body<0>, area_body<1>, area_body<2>, area_body<3>};
     run(Launch{bodies[fmt], &a, grid.x, 64u * kResampleRows, 0});
@@ -273,7 +277,7 @@ static void one(int filter, int fmt, int ow, int oh, bool mirror, int pad_row, i
       if (flag(n)) a.t.mirror |= 1u << n;
     }
     dim3 grid;
-    const size_t lds = filter_plan(a.q, a.t.r, n_out, filter, &grid, true);
+    const size_t lds = resample_args_ok(a.q.base, fmt, kJbCropsPerLaunch) ? filter_plan(a.q, a.t.r, n_out, filter, &grid, true) : 0;
     if (!lds) {
       printf("FAIL: filter_plan refuses filter %d target %dx%d\n", filter, ow, oh);
       exit(1);
@@ -314,6 +318,68 @@ static void one(int filter, int fmt, int ow, int oh, bool mirror, int pad_row, i
   n_cases++;
 }
 
+// ---- the launchers' checks (jb_resample.hip: resample_args_ok, view_row_ok, crop_row_ok) -----------------------------------
+// From one accepted launch of two rows, every one of these changes alone -- to the SECOND row, so that the loops are seen
+// to reach it -- must be refused.
+static long n_validation = 0;
+static void expect(bool accepted, bool want, const char *what) {
+  if (accepted != want) {
+    printf("FAIL: the launch validation %s %s\n", accepted ? "accepts" : "refuses", what);
+    exit(1);
+  }
+  n_validation++;
+}
+static void validation() {
+  JbResample p;
+  JbViewTable vt;
+  JbCropTable ct;
+  memset(&p, 0, sizeof p);
+  memset(&vt, 0, sizeof vt);
+  memset(&ct, 0, sizeof ct);
+  p.ow = 70, p.oh = 9, p.n_images = 2;
+  for (int i = 0; i < 2; i++) {
+    vt.r[i] = JbViewRow{8100LL * i, 3 * 90, 3, 2, 20, 10, i};  // a 20 x 10 view at (3, 2) of a union 90 wide
+    ct.c[i].w = 20, ct.c[i].h = 10, ct.c[i].tmp_offset = 600LL * i;
+  }
+  expect(resample_args_ok(p, 0, kJbCropsPerLaunch) && resample_args_ok(p, 3, kJbCropsPerLaunch) && rows_ok(vt, 2) && rows_ok(ct, 2), true,
+         "the launch the refused ones are made from");
+  const auto view = [&](const char *what, auto change) {
+    JbViewTable t = vt;
+    change(t.r[1]);
+    expect(rows_ok(t, 2), false, what);
+  };
+  view("a view row with w = 0", [](JbViewRow &r) { r.w = 0; });
+  view("a view row with h = 0", [](JbViewRow &r) { r.h = 0; });
+  view("a view row with w = 65536", [](JbViewRow &r) { r.w = 65536; });
+  view("a view row with dx = -1", [](JbViewRow &r) { r.dx = -1; });
+  view("a view row with dy = -1", [](JbViewRow &r) { r.dy = -1; });
+  view("a view row with dy = 65536", [](JbViewRow &r) { r.dy = 65536; });
+  view("a view row with src_offset = -1", [](JbViewRow &r) { r.src_offset = -1; });
+  view("a view row with src_row_bytes = 3 * 65535 + 1", [](JbViewRow &r) { r.src_row_bytes = 3 * 65535 + 1; });
+  view("a view row with 3 * (dx + w) = src_row_bytes + 3", [](JbViewRow &r) { r.dx = r.src_row_bytes / 3 - r.w + 1; });
+  view("a view row with mirror = 2", [](JbViewRow &r) { r.mirror = 2; });
+  const auto crop = [&](const char *what, auto change) {
+    JbCropTable t = ct;
+    change(t.c[1]);
+    expect(rows_ok(t, 2), false, what);
+  };
+  crop("a crop row with w = 0", [](JbCrop &c) { c.w = 0; });
+  crop("a crop row with h = 0", [](JbCrop &c) { c.h = 0; });
+  crop("a crop row with w = 65536", [](JbCrop &c) { c.w = 65536; });
+  crop("a crop row with tmp_offset = -1", [](JbCrop &c) { c.tmp_offset = -1; });
+  const auto launch = [&](const char *what, int format, auto change) {
+    JbResample q = p;
+    change(q);
+    expect(resample_args_ok(q, format, kJbCropsPerLaunch), false, what);
+  };
+  launch("format = -1", -1, [](JbResample &) {});
+  launch("format = 4", 4, [](JbResample &) {});
+  launch("ow = 0", 0, [](JbResample &q) { q.ow = 0; });
+  launch("ow = 65536", 0, [](JbResample &q) { q.ow = 65536; });
+  launch("n_images = 0", 0, [](JbResample &q) { q.n_images = 0; });
+  launch("n_images = kJbCropsPerLaunch + 1", 0, [](JbResample &q) { q.n_images = kJbCropsPerLaunch + 1; });
+}
+
 int main() {
   const int targets[][2] = {{1, 1}, {1, 5}, {64, 3}, {65, 3}, {70, 9}};
   for (int filter = 0; filter <= 2; filter++)
@@ -324,5 +390,7 @@ int main() {
           if (t[0] == 70) one(filter, fmt, t[0], t[1], mirror != 0, 1, 5, 7);
         }
   printf("%ld view kernel cases ok\n", n_cases);
+  validation();
+  printf("%ld launch validation cases ok\n", n_validation);
   return 0;
 }
