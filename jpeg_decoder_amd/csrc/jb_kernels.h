@@ -10,6 +10,7 @@ typedef void *hipStream_t;
 #endif
 
 #include "../../include/jpegblk.h"  // (jb_color_chain: the colour launch takes the ABI's structure as it is)
+#include "jb_divmagic.h"
 #include "jb_knobs.h"
 #include "jb_orient.h"
 
@@ -45,6 +46,9 @@ struct JbLaunch {
   int32_t roi_x, roi_y;       // the rectangle, in pixels of the full-size image
   int32_t roi_w, roi_h;
   int32_t roi_mx, roi_my;     // the MCU that holds (roi_x, roi_y): roi_x / (8 * hs), roi_y / (8 * vs)
+  // the tile kernel's prologue divides by these three without a division (jb_divmagic.h).  Set by jbk_launch and
+  // jbk_launch_crops from the fields above, once per launch, on their own copy of the arguments: callers leave them alone.
+  JbDiv div_tiles_per_image, div_tiles_per_row, div_mcus_x;
 };
 
 // "Per-image rectangles" (jb_blocks_to_rgb_device_crops): what JbLaunch's roi_* fields say once for a launch, said per

@@ -18,6 +18,12 @@
 //         rows, so only the last tile of an image can be short; a colour segment may then
 //         straddle one row end and is stored in two parts (1920 px: +4.2 %).
 //     blockIdx -> tile is the identity (one compact advancing write window; XCD bands were slower).
+//   * the front of every tile is kept short, because the kernel runs at the knee where its instruction stream just
+//     stops hiding under the memory traffic (DESIGN_HISTORY.md section 4): tile -> (image, MCU row, first MCU) is two
+//     multiply-and-shift pairs the launch computes (jb_divmagic.h), not two integer divisions; a full 4:4:4 tile issues
+//     its eight LDS-DMA loads from two lane offsets and a scalar base that steps by 3072 bytes, with no vector
+//     instruction between them (only a ragged tile clamps block numbers per load); and the wave's quantisation table is
+//     fetched into SGPRs while the coefficients are on their way, not after they have arrived.
 //   * stage 1+2, one lane = one coded 8x8 block.  Lanes take the tile's blocks sorted by
 //     component, so the quantisation table is wave-uniform (scalar loads -> SGPRs) wherever
 //     possible (4:4:4: wave w = component w).  The lane's 128 coefficient bytes reach 32 VGPRs
@@ -59,6 +65,8 @@ namespace {
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void gbl_void_t;
 typedef __attribute__((address_space(4))) int32_t q_const_t;  // scalar-loadable (constant) memory
+typedef int32_t i32x16_t __attribute__((ext_vector_type(16)));
+typedef __attribute__((address_space(4))) i32x16_t q16_const_t __attribute__((aligned(4)));  // one s_load_dwordx16 of a table
 
 __device__ __forceinline__ float kf(uint32_t bits) { return __builtin_bit_cast(float, bits); }
 
@@ -432,8 +440,12 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
   // elsewhere -- nothing is re-read, so there is no L2 locality to win, and eight separate write
   // windows cost HBM page locality (tools/probe_store2.hip: the same 403 MB written by one
   // advancing window reach 6.4 TB/s, by many separate streams 5.2 TB/s).
+  // No division here: tile / tiles_per_image, rem / tiles_per_row and m0 / mcus_x are each one multiply-high and one
+  // shift by a pair the launch computed (jb_divmagic.h; exact for every tile < 2^31).  A 32-bit division is a float
+  // reciprocal, a trip through a VGPR and some 25 dependent scalar instructions, and two of them stood between the
+  // kernel arguments' arrival and every wave's first load.
   const int tile = blockIdx.x;
-  const int img = tile / tiles_per_image;
+  const int img = (int)jb_div_apply((uint32_t)tile, p.div_tiles_per_image);
   const int rem = tile - img * tiles_per_image;
   // Two tilings.  Linear (p.linear, the default): a tile is 192/NB consecutive MCUs of the image's
   // MCU stream, whatever MCU rows they fall in -- every tile but the image's last is full for any
@@ -459,11 +471,14 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
   int my, mx0, nvalid;
   if (LINEAR) {
     const int m0 = rem * MCUS;
-    my = m0 / p.mcus_x;
+    my = (int)jb_div_apply((uint32_t)m0, p.div_mcus_x);
     mx0 = m0 - my * p.mcus_x;
     nvalid = min(MCUS, p.mcus_x * p.mcus_y - m0);
   } else {
-    my = rem / tiles_per_row;
+    // (ROI = 2: the divisor is the image's own, read from its row of the table, which has no room for a pair: those
+    // instantiations keep this one division)
+    if constexpr (ROI == 2) my = rem / tiles_per_row;
+    else my = (int)jb_div_apply((uint32_t)rem, p.div_tiles_per_row);
     mx0 = (rem - my * tiles_per_row) * MCUS;
     // region of interest: the tile grid's origin is the MCU that holds the rectangle's first pixel; the coefficient
     // address below keeps the full image's mcus_x as its row pitch
@@ -487,6 +502,7 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
     // but the 8 instructions of the wave consume those 64 lines completely: measured 6.4-6.5 TB/s
     // on MI355X (tools/probe_load.hip), the same as perfectly coalesced loads.
     uint32_t raw[32];  // row k = dwords 4k..4k+3, two int16 (columns 2j, 2j+1) per dword
+    [[maybe_unused]] i32x16_t qw[4] = {};  // LDS-DMA path: the wave's table, 16 entries each
     if (kDirectLoad) {
       const int n = min(LM::block(tid), last_block);  // ragged tile: re-read its last block
       const u32x4_t *src = (const u32x4_t *)(tile_coef + (uint32_t)n * 128u);
@@ -508,21 +524,54 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
       // of lane l lands at chunk position j ^ ((l>>1)&7) (applied to the per-lane GLOBAL address,
       // LDS-DMA writes LDS linearly), which makes the 128-B-strided ds_read_b128 conflict free.
       char *const wave_lds = lds + wave * 8192;
-      if (JB_DO_LOAD(p))
+      if (JB_DO_LOAD(p)) {
+        if (nvalid == MCUS) {
+          // A full tile (wave-uniform; every tile of a 4096- or 8192-pixel row): nothing to clamp, and the block of
+          // lane l2 of wave w is 3 * l2 + w, so load i reads at i * 3072 + (lane >> 3) * 384 + w * 128 + its swizzled
+          // chunk.  The chunk's swizzle term f2 = (i & 1) * 4 + (lane >> 4) flips bit 2 from one load to the next:
+          // two lane offsets that differ by 64 bytes, and a scalar base that steps by 3072.
+          const uint8_t *const wave_coef = tile_coef + wave * 128;
+          // (opaque, so that hipcc keeps them as the loads' 32-bit lane offsets next to a scalar base, and does not fold
+          // each load's constant into a 64-bit lane address of its own)
+          uint32_t off_even = (uint32_t)(lane >> 3) * 384u + (uint32_t)(((lane & 7) ^ (lane >> 4)) << 4);
+          uint32_t off_odd = off_even ^ 64u;
+          asm volatile("" : "+v"(off_even), "+v"(off_odd));
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
-          const int l2 = i * 8 + (lane >> 3);  // the lane whose block this chunk belongs to
-          const int f2 = (l2 >> 1) & 7;
-          const int nsrc = min(LM::block(wave * 64 + l2), last_block);
-          const uint32_t off = (uint32_t)nsrc * 128u + (uint32_t)(((lane & 7) ^ f2) << 4);
-          __builtin_amdgcn_global_load_lds((gbl_void_t *)(tile_coef + off), (lds_void_t *)(wave_lds + i * 1024), 16, 0, JB_LOAD_AUX);
+          for (int i = 0; i < 8; i++) {
+            const uint8_t *step = wave_coef + i * 3072;
+            asm volatile("" : "+s"(step));
+            __builtin_amdgcn_global_load_lds((gbl_void_t *)(step + ((i & 1) ? off_odd : off_even)),
+                                             (lds_void_t *)(wave_lds + i * 1024), 16, 0, JB_LOAD_AUX);
+          }
+          // (ends this path with a statement the other one does not have: hipcc otherwise merges the two paths' eighth
+          // loads into one behind the join, addressed through a 64-bit lane pointer, behind the table's address arithmetic)
+          asm volatile("");
+        } else {
+          // the ragged tile (the last of a row whose MCUs are no multiple of 64): blocks past the last are re-reads of it
+#pragma unroll
+          for (int i = 0; i < 8; i++) {
+            const int l2 = i * 8 + (lane >> 3);  // the lane whose block this chunk belongs to
+            const int f2 = (l2 >> 1) & 7;
+            const int nsrc = min(LM::block(wave * 64 + l2), last_block);
+            const uint32_t off = (uint32_t)nsrc * 128u + (uint32_t)(((lane & 7) ^ f2) << 4);
+            __builtin_amdgcn_global_load_lds((gbl_void_t *)(tile_coef + off), (lds_void_t *)(wave_lds + i * 1024), 16, 0, JB_LOAD_AUX);
+          }
         }
+      }
+      // chunk j of this lane's block is at chunk position j ^ f: one lane address, and a constant under the XOR per read
       const int f = (lane >> 1) & 7;
-      const char *base = wave_lds + lane * 128;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const int lane_base = wave * 8192 + lane * 128 + (f << 4);
+      // The wave's table (4:4:4: one component per wave, so MIXQ and comp_b never matter here) is fetched while the
+      // coefficients are on their way, and is in SGPRs when the wait for the coefficients ends: the wait statement takes
+      // it as operands, so the four scalar loads cannot sink below it.  Left to itself hipcc issues them behind the
+      // ds_reads' wait and waits for them in full before the first multiply -- a scalar-memory round trip on every
+      // wave's critical path.
+#pragma unroll
+      for (int t = 0; t < 4; t++) qw[t] = *(const q16_const_t *)(qa + 16 * t);
+      asm volatile("s_waitcnt vmcnt(0)" : "+s"(qw[0]), "+s"(qw[1]), "+s"(qw[2]), "+s"(qw[3]) : : "memory");
 #pragma unroll
       for (int j = 0; j < 8; j++) {
-        const uint4 t = *(const uint4 *)(base + ((j ^ f) << 4));
+        const uint4 t = *(const uint4 *)(lds + (lane_base ^ (j << 4)));
         raw[j * 4 + 0] = t.x;
         raw[j * 4 + 1] = t.y;
         raw[j * 4 + 2] = t.z;
@@ -540,7 +589,9 @@ __global__ __launch_bounds__(tile_blocks(HS, VS), (HS == 1 && (SCALE == 1 || VS 
       for (int k = 0; k < 8; k++) {
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-          v[k * 8 + i] = dequant1(raw[k * 4 + (i >> 1)], i, qa[k * 8 + i]);
+          const int e = k * 8 + i;
+          const int q = kDirectLoad ? qa[e] : qw[e >> 4][e & 15];
+          v[e] = dequant1(raw[k * 4 + (i >> 1)], i, q);
         }
       }
     } else {
@@ -1216,11 +1267,22 @@ __global__ __launch_bounds__(64) void jb_small_kernel_16(const JbLaunch p) {
   jb_small_body<HS, VS>(p);
 }
 
+// the arguments with the prologue's division pairs (jb_divmagic.h) filled from the launch's own divisors: here, in front
+// of the two places that launch jb_tile_kernel, so that no caller can pass a pair that does not match its divisor
+static JbLaunch with_div(const JbLaunch &a) {
+  JbLaunch p = a;
+  p.div_tiles_per_image = jb_div_make(a.tiles_per_image);
+  p.div_tiles_per_row = jb_div_make(a.tiles_per_row);
+  p.div_mcus_x = jb_div_make(a.mcus_x);
+  return p;
+}
+
 // Launches jb_tile_kernel<HS, VS, MIXQ, LINEAR, STAGED, SCALE, FORMAT, ROI>: every launch of the 192-lane kernel goes through
 // here.  SCALE != 1 (the area-reduced store stage), FORMAT != 0 (the planar one) and ROI exist in the row-bound tiling only.
 // MIXQ is decided here, and MIXQ = true is only instantiated for a layout that can need it.
 template <int HS, int VS, int SCALE, int FORMAT, bool LINEAR = false, bool STAGED = false, int ROI = 0>
-static hipError_t launch_tile(const JbLaunch &p, hipStream_t stream) {
+static hipError_t launch_tile(const JbLaunch &a, hipStream_t stream) {
+  const JbLaunch p = with_div(a);
   using LM = LaneMap<HS, VS>;
   // does any wave hold two components whose tables may differ?  (never luma and chroma: jb_tile_kernel asserts it)
   constexpr bool kCbCrMixed = (LM::MCUS % 64 != 0);  // 4:2:0: Cb and Cr share the third wave
@@ -1274,7 +1336,8 @@ static hipError_t launch_layout(const JbLaunch &p, int scale, hipStream_t stream
 
 // the per-image rectangles: as launch_tile, with the table as the second kernel argument
 template <int HS, int VS>
-static hipError_t launch_crops(const JbLaunch &p, const JbCropTable &table, hipStream_t stream) {
+static hipError_t launch_crops(const JbLaunch &a, const JbCropTable &table, hipStream_t stream) {
+  const JbLaunch p = with_div(a);  // (tiles_per_row is the table's, per image: the ROI = 2 kernels divide by it)
   using LM = LaneMap<HS, VS>;
   constexpr bool kCbCrMixed = (LM::MCUS % 64 != 0);
   const dim3 grid(p.n_tiles), block(LM::TB);
