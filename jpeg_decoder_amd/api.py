@@ -1127,6 +1127,41 @@ def _harvest(n, rgb, w, h, st, fmt, keep_pixels, on_image, arena, device_out, k=
     return out + (list(st),)
 
 
+def _colors_want_views(colors, views):
+    if colors is not None and views is None:
+        raise ValueError("colors want views (a K = 1 views= call covers a plain one)")
+
+
+def _batch_route(a, crops, views, view_groups, colors):
+    """The batch counterpart of _ROUTES: what a run or a submission over the arrays `a` (_batch_args) is asked for per file ->
+    (the suffix of jb_batch_decoder_run / jb_batch_decoder_submit, its arguments between the count and the outputs); a["k"] and
+    a["groups"] become the harvest's hints.  JbError / ValueError for what cannot be combined."""
+    _colors_want_views(colors, views)
+    if view_groups is not None:
+        if crops is not None:
+            raise JbError(-9, "view groups cannot be combined with per-image rectangles (crops)")
+        if views is None:
+            raise JbError(-7, "view groups want views")
+        groups, n_groups = _group_array(view_groups)
+        arr, a["k"] = _view_array(views, a["n"])
+        if a["n"] and a["k"] != sum(g.n_views for g in groups[:n_groups]):
+            raise JbError(-2, "view groups: every file wants as many views as the groups count")
+        a["groups"] = [(g.n_views, g.rs.out_w, g.rs.out_h) for g in groups[:n_groups]]
+        suffix, extra = "_view_groups", [arr, groups, n_groups]
+    elif views is not None:
+        if crops is not None:
+            raise JbError(-9, "views cannot be combined with per-image rectangles (crops)")
+        arr, a["k"] = _view_array(views, a["n"])
+        suffix, extra = "_views", [arr, a["k"]]
+    elif crops is not None:
+        return "_crops", [_crop_array(crops, a["n"])]
+    else:
+        return "", []
+    if colors is not None:
+        return suffix + "_color", extra + [_color_array(colors, a["n"], a["k"])]
+    return suffix, extra
+
+
 class BatchDecoder:
     """jb_batch_decoder: n_threads host lanes (pinned buffers each) feeding one shared context per
     device, reusable.  devices=[...] (jb_batch_decoder_create_multi): one decoder over several
@@ -1248,50 +1283,11 @@ class BatchDecoder:
     def device_entropy_images(self):
         return lib().jb_batch_decoder_device_entropy_images(self._h)
 
-    @staticmethod
-    def _grouped(a, views, view_groups, crops):
-        """the arguments of a call with view groups: (views, groups, n_groups); a["k"], a["groups"] for the harvest"""
-        if crops is not None:
-            raise JbError(-9, "view groups cannot be combined with per-image rectangles (crops)")
-        if views is None:
-            raise JbError(-7, "view groups want views")
-        groups, n_groups = _group_array(view_groups)
-        arr, a["k"] = _view_array(views, a["n"])
-        if a["n"] and a["k"] != sum(g.n_views for g in groups[:n_groups]):
-            raise JbError(-2, "view groups: every file wants as many views as the groups count")
-        a["groups"] = [(g.n_views, g.rs.out_w, g.rs.out_h) for g in groups[:n_groups]]
-        return arr, groups, n_groups
-
-    @staticmethod
-    def _no_colors_without_views(colors, views):
-        if colors is not None and views is None:
-            raise ValueError("colors want views (a K = 1 views= call covers a plain one)")
-
     def _run(self, paths, keep_pixels, on_image, crops=None, views=None, view_groups=None, colors=None):
-        self._no_colors_without_views(colors, views)
         a = _batch_args(paths)
+        suffix, extra = _batch_route(a, crops, views, view_groups, colors)
         times = (ctypes.c_double * 4)()
-        if view_groups is not None:
-            arr, groups, n_groups = self._grouped(a, views, view_groups, crops)
-            if colors is not None:
-                rc = lib().jb_batch_decoder_run_view_groups_color(self._h, a["paths"], a["n"], arr, groups, n_groups, _color_array(colors, a["n"], a["k"]),
-                                                                  a["rgb"], a["w"], a["h"], a["st"], times)
-            else:
-                rc = lib().jb_batch_decoder_run_view_groups(self._h, a["paths"], a["n"], arr, groups, n_groups, a["rgb"], a["w"], a["h"], a["st"], times)
-        elif views is not None:
-            if crops is not None:
-                raise JbError(-9, "views cannot be combined with per-image rectangles (crops)")
-            arr, a["k"] = _view_array(views, a["n"])
-            if colors is not None:
-                rc = lib().jb_batch_decoder_run_views_color(self._h, a["paths"], a["n"], arr, a["k"], _color_array(colors, a["n"], a["k"]), a["rgb"],
-                                                            a["w"], a["h"], a["st"], times)
-            else:
-                rc = lib().jb_batch_decoder_run_views(self._h, a["paths"], a["n"], arr, a["k"], a["rgb"], a["w"], a["h"], a["st"], times)
-        elif crops is not None:
-            rc = lib().jb_batch_decoder_run_crops(self._h, a["paths"], a["n"], _crop_array(crops, a["n"]), a["rgb"], a["w"], a["h"],
-                                                  a["st"], times)
-        else:
-            rc = lib().jb_batch_decoder_run(self._h, a["paths"], a["n"], a["rgb"], a["w"], a["h"], a["st"], times)
+        rc = getattr(lib(), "jb_batch_decoder_run" + suffix)(self._h, a["paths"], a["n"], *extra, a["rgb"], a["w"], a["h"], a["st"], times)
         return self._results(a, _batch_times(times, rc), keep_pixels, on_image)
 
     def _results(self, a, t, keep_pixels, on_image):
@@ -1315,7 +1311,7 @@ class BatchDecoder:
         None / [] or [(COLOR_*, value), ...] -- is applied to view v of paths[i] on its uint8 pixels, mirror included, in front of
         the decoder's format (Context.blocks_to_rgb_device has the definition).  A bad chain refuses the whole call (the
         rc in the times); without views ValueError; another shape than the views' JbError(-2)."""
-        self._no_colors_without_views(colors, views)
+        _colors_want_views(colors, views)
         assert not self._device_out, "device output is set: use run_to_device"
         return self._run(paths, keep_pixels, on_image, crops, views, view_groups, colors)
 
@@ -1340,7 +1336,7 @@ class BatchDecoder:
         crops: as for run().  views: as for run() -- a file's pointer is that of its K outputs, back to back, tight.
         view_groups: as for run() -- a file's pointer is that of its block (view_groups_bytes has the layout).
         colors: as for run()."""
-        self._no_colors_without_views(colors, views)
+        _colors_want_views(colors, views)
         assert self._device_out, "call set_device_output first"
         return self._run(paths, False, None, crops, views, view_groups, colors)
 
@@ -1356,7 +1352,7 @@ class BatchDecoder:
         view_groups: as for run(); out is then a LIST of G contiguous tensors [N, K_g, 3, h_g, w_g] ([N, K_g, h_g, w_g, 3] for
         format 0), and is returned as it came.
         colors: as for run() -- the colour jitter of every view on the way into the model's input tensor."""
-        self._no_colors_without_views(colors, views)
+        _colors_want_views(colors, views)
         import torch
         if view_groups is not None:
             return self._run_to_tensors(paths, out, views, view_groups, colors)
@@ -1369,6 +1365,22 @@ class BatchDecoder:
             flat, st, t = self._run_to_tensor(paths, out.view((-1,) + tuple(out.shape[2:])), None, views, k, colors)
             return out, st, t
         return self._run_to_tensor(paths, out, crops, None, 1)
+
+    def _run_to_scratch(self, paths, per, device, crops, views, view_groups, colors):
+        """run_to_device into a scratch region of `per` bytes per file -> (scratch, its address, pointers, sizes, statuses, times).
+        The decoder places images group by group (a group of one thread's files back to back, groups on 256-byte steps of
+        the region, in the order the threads get there): they land here in their final format, and the caller's one
+        device-to-device copy per image puts them in order."""
+        import torch
+        n = len(paths)
+        scratch = torch.empty(n * per + 256 * (n + 1), dtype=torch.uint8, device=device)
+        torch.cuda.synchronize(device)
+        self.set_device_output(scratch.data_ptr(), scratch.numel())
+        try:
+            ptrs, sizes, st, t = self.run_to_device(paths, crops, views, view_groups, colors)
+        finally:
+            self.set_device_output(0, 0)
+        return scratch, scratch.data_ptr(), ptrs, sizes, list(st), t
 
     def _run_to_tensors(self, paths, outs, views, view_groups, colors=None):
         """run_to_tensor with view groups: the files' blocks land in a scratch region, one copy per file and group sorts them"""
@@ -1389,15 +1401,7 @@ class BatchDecoder:
                 raise ValueError(f"a group's tensor must be a contiguous CUDA tensor {list(want)} of {dt}")
             if out.device.index != self._device:
                 raise ValueError(f"out is on {out.device}, the decoder on device {self._device}")
-        scratch = torch.empty(n * per + 256 * (n + 1), dtype=torch.uint8, device=outs[0].device)
-        torch.cuda.synchronize(outs[0].device)
-        self.set_device_output(scratch.data_ptr(), scratch.numel())
-        try:
-            ptrs, sizes, st, t = self.run_to_device(paths, None, views, view_groups, colors)
-        finally:
-            self.set_device_output(0, 0)
-        st = list(st)
-        base = scratch.data_ptr()
+        scratch, base, ptrs, sizes, st, t = self._run_to_scratch(paths, per, outs[0].device, None, views, view_groups, colors)
         for g, out in enumerate(outs):
             flat = out.view(n, -1).view(torch.uint8) if out.dtype != torch.uint8 else out.view(n, -1)   # (a row per FILE)
             for i in range(n):
@@ -1422,19 +1426,8 @@ class BatchDecoder:
         H, W = (out.shape[2], out.shape[3]) if planar else (out.shape[1], out.shape[2])
         per = output_bytes(W, H, spec.format if spec is not None else FMT_RGB_U8_HWC) * k   # (a file's k outputs)
         assert per == out[0].numel() * out.element_size() * k
-        # the decoder places images group by group (a group of one thread's files back to back, groups on 256-byte
-        # steps of the region, in the order the threads get there): they land in a scratch region in their final
-        # format and one device-to-device copy per image puts them in order
-        scratch = torch.empty(n * per + 256 * (n + 1), dtype=torch.uint8, device=out.device)
-        torch.cuda.synchronize(out.device)
-        self.set_device_output(scratch.data_ptr(), scratch.numel())
-        try:
-            ptrs, sizes, st, t = self.run_to_device(paths, crops, views, None, colors)
-        finally:
-            self.set_device_output(0, 0)
-        st = list(st)
+        scratch, base, ptrs, sizes, st, t = self._run_to_scratch(paths, per, out.device, crops, views, None, colors)
         flat = out.view(n, -1).view(torch.uint8) if out.dtype != torch.uint8 else out.view(n, -1)   # (a row per FILE)
-        base = scratch.data_ptr()
         for i in range(n):
             if st[i] != JB_OK or not ptrs[i]:
                 continue
@@ -1453,32 +1446,10 @@ class BatchDecoder:
         views: as for run() (jb_batch_decoder_submit_views, which copies them).
         view_groups: as for run() (jb_batch_decoder_submit_view_groups, which copies views and groups).
         colors: as for run() (the _color variants, which copy the chains too; a bad chain is a JbError here)."""
-        self._no_colors_without_views(colors, views)
         t = _batch_args(paths)
-        if view_groups is not None:
-            arr, groups, n_groups = self._grouped(t, views, view_groups, crops)
-            if colors is not None:
-                _check(lib().jb_batch_decoder_submit_view_groups_color(self._h, t["paths"], t["n"], arr, groups, n_groups,
-                                                                       _color_array(colors, t["n"], t["k"]), t["rgb"], t["w"], t["h"], t["st"],
-                                                                       ctypes.byref(t["id"])))
-            else:
-                _check(lib().jb_batch_decoder_submit_view_groups(self._h, t["paths"], t["n"], arr, groups, n_groups, t["rgb"], t["w"], t["h"], t["st"],
+        suffix, extra = _batch_route(t, crops, views, view_groups, colors)
+        _check(getattr(lib(), "jb_batch_decoder_submit" + suffix)(self._h, t["paths"], t["n"], *extra, t["rgb"], t["w"], t["h"], t["st"],
                                                                  ctypes.byref(t["id"])))
-        elif views is not None:
-            if crops is not None:
-                raise JbError(-9, "views cannot be combined with per-image rectangles (crops)")
-            arr, t["k"] = _view_array(views, t["n"])
-            if colors is not None:
-                _check(lib().jb_batch_decoder_submit_views_color(self._h, t["paths"], t["n"], arr, t["k"], _color_array(colors, t["n"], t["k"]),
-                                                                 t["rgb"], t["w"], t["h"], t["st"], ctypes.byref(t["id"])))
-            else:
-                _check(lib().jb_batch_decoder_submit_views(self._h, t["paths"], t["n"], arr, t["k"], t["rgb"], t["w"], t["h"], t["st"],
-                                                           ctypes.byref(t["id"])))
-        elif crops is not None:
-            _check(lib().jb_batch_decoder_submit_crops(self._h, t["paths"], t["n"], _crop_array(crops, t["n"]), t["rgb"], t["w"], t["h"],
-                                                       t["st"], ctypes.byref(t["id"])))
-        else:
-            _check(lib().jb_batch_decoder_submit(self._h, t["paths"], t["n"], t["rgb"], t["w"], t["h"], t["st"], ctypes.byref(t["id"])))
         # the library writes into these arrays until the batch is collected (or the decoder destroyed): the decoder
         # object holds them as well, so a ticket the caller drops cannot free them under a running batch
         self._flights[t["id"].value] = t
