@@ -554,9 +554,29 @@ int jb_blocks_to_rgb_device_view_groups(jb_ctx *ctx, const jb_device_batch *batc
  *   JB_COLOR_GRAYSCALE (value 0): R = G = B = L(p).              JB_COLOR_SOLARIZE t, t integral in 0..256: v < t ? v : 255 - v.
  *   JB_COLOR_HUE d, d integral in 0..255: RGB -> HSV, H = (H + d) & 255, HSV -> RGB, Pillow's two conversions
  *     (csrc/jb_color_core.h states them operation by operation: which steps are float32 and which double decides bits).
- * A chain may hold ONE JB_COLOR_CONTRAST: each costs a reduction pass over the view. */
+ * A chain may hold ONE JB_COLOR_CONTRAST: each costs a reduction pass over the view.
+ *
+ * NEIGHBOURHOOD operations are numbered from 16 (1..15 are pointwise).  JB_COLOR_BLUR radius is Pillow's
+ * ImageFilter.GaussianBlur(radius) -- torchvision's PIL-backend GaussianBlur, DINO's own -- on the view AS IT STANDS when the
+ * op is reached: the blur's edges are the view's own edges, nothing from outside the view's rectangle enters.  Pillow does
+ * not convolve with a Gaussian: it runs an "extended box blur" three times along every row, then three times along every
+ * column, and rounds to uint8 after every pass.  With the float32 radius (jb_blur_params is the one text of this):
+ *   sigma2 = radius * radius / 3 (float32);  L = (float32)sqrt(12.0 * (double)sigma2 + 1.0);
+ *   l = (float32)floor(((double)L - 1.0) / 2.0);  a = (2 l + 1) * (l (l + 1) - 3 sigma2) / (6 (sigma2 - (l + 1)(l + 1))),
+ *   every operation a float32 one, rounded, none contracted;  fr = l + a.
+ *   r = (int)fr;  ww = (uint32)((float32)16777216 / (fr * 2 + 1));  fw = (16777216 - (2 r + 1) ww) / 2  (integers).
+ *   one pass along a line of n samples, per channel, c(i) = min(max(i, 0), n - 1):
+ *     out[x] = (ww * sum_{k = -r..r} in[c(x + k)] + fw * (in[c(x - r - 1)] + in[c(x + r + 1)]) + (1 << 23)) >> 24
+ *   in unsigned 32-bit integers (the bracket never exceeds 255 * 2^24 + 2^23).  The clamp c() applies to the input of EVERY
+ *   pass.  Radius 0 is the identity.
+ * A chain may hold ONE JB_COLOR_BLUR (each costs a tile pass), its box radius r at most JB_COLOR_BLUR_BOX_MAX (Gaussian radii
+ * up to about 8.4; the published pipelines draw from [0.1, 2.0]: r <= 1), and no JB_COLOR_CONTRAST BEHIND it (the mean would
+ * be that of the blurred view, which the reduction pass cannot see; a contrast in front of the blur is DINO's order).  A
+ * chain is thus: pointwise operations, at most one blur, pointwise operations without a contrast. */
 enum { JB_COLOR_BRIGHTNESS = 1, JB_COLOR_CONTRAST, JB_COLOR_SATURATION, JB_COLOR_HUE, JB_COLOR_GRAYSCALE, JB_COLOR_SOLARIZE };
+enum { JB_COLOR_BLUR = 16 };
 enum { JB_COLOR_OPS_MAX = 8 };
+enum { JB_COLOR_BLUR_BOX_MAX = 7 }; /* the largest box radius r the blur kernel's halo is built for */
 typedef struct jb_color_op {
   int32_t op;  /* JB_COLOR_* */
   float value; /* the factor, the hue shift, the threshold; 0 for JB_COLOR_GRAYSCALE */
@@ -569,8 +589,16 @@ typedef struct jb_color_chain {
  * n_ops outside 0..8, reserved != 0, an unknown op, a factor that is not finite or below 0, a hue outside 0..255 or not
  * integral, a threshold outside 0..256 or not integral, or a JB_COLOR_GRAYSCALE value that is not 0; JB_ERR_UNSUPPORTED for
  * the first chain with more than one JB_COLOR_CONTRAST.  Chains are looked at in order, and the first one that fails
- * decides: *bad_index (may be NULL) is its index, -1 when no chain is to blame.  Pure host code. */
+ * decides: *bad_index (may be NULL) is its index, -1 when no chain is to blame.  Pure host code.
+ * JB_COLOR_BLUR adds, under the same rules (a chain that is wrong both ways is JB_ERR_GEOMETRY): JB_ERR_GEOMETRY for a
+ * radius that is not finite or below 0; JB_ERR_UNSUPPORTED for a box radius above JB_COLOR_BLUR_BOX_MAX, for a second
+ * JB_COLOR_BLUR in a chain, and for a JB_COLOR_CONTRAST behind a JB_COLOR_BLUR. */
 int jb_color_check(const jb_color_chain *chains, int n, int *bad_index);
+/* Pillow's GaussianBlur radius -> the box radius and the two 8.24 fixed-point weights of one pass (above); the one text that
+ * turns a radius into weights: the kernels get the three integers.  JB_ERR_NULL for a null pointer; JB_ERR_GEOMETRY for a
+ * radius that is not finite or below 0; JB_ERR_UNSUPPORTED for r > JB_COLOR_BLUR_BOX_MAX; in a refusal nothing is written.
+ * Radius 0 gives r = 0, ww = 16777216, fw = 0: the identity.  Pure host code. */
+int jb_blur_params(float radius, int32_t *r, uint32_t *ww, uint32_t *fw);
 /* The chain on a HOST image of w x h interleaved uint8 pixels (rows in_row_stride / out_row_stride bytes apart, each at
  * least 3 * w; in == out is allowed): the CPU statement of the kernels' arithmetic, through the same csrc/jb_color_core.h.
  * JB_ERR_NULL; JB_ERR_GEOMETRY for w or h outside 1..65535 or a stride below 3 * w; then jb_color_check's status. */
@@ -581,7 +609,8 @@ int jb_color_host(const uint8_t *in, int64_t in_row_stride, int32_t w, int32_t h
  * out_row_stride apart (of a plane when planar), planes spec->plane_stride (0: tight), images out_image_stride, as a batch's
  * d_rgb is described.  The outputs must not overlap the inputs.  chains: a HOST array of n_images, read before the call
  * returns.  Launches on `stream` (NULL: the context's): jb_color_mean_kernel where a chain of the launch has a contrast
- * -- integer sums, so the result does not depend on the order of the additions -- then jb_color_apply_kernel, 32 images a
+ * -- integer sums, so the result does not depend on the order of the additions -- then jb_color_apply_kernel, and where a
+ * chain has a JB_COLOR_BLUR jb_color_blur_kernel for those views (a 64 x 32 tile with a halo, six passes in LDS), 32 images a
  * launch.  JB_ERR_NULL; JB_ERR_GEOMETRY for n_images < 1, w or h outside 1..65535, strides below one row / one image, a
  * bad spec, or float output that is not aligned to its element size; then jb_color_check's status with the chain's index
  * in jb_last_error.  In every refusal nothing is launched or written. */

@@ -17,10 +17,10 @@ from .api import (JbError, Context, ImageDesc, Geometry, DeviceBatch, lib, lib_p
                   View, VIEW_MIRROR, VIEWS_MAX, views_check, ViewGroup, ViewOutput, VIEW_GROUPS_MAX, view_groups_check, view_groups_bytes,
                   Fit, FitGeometry, fit_geometry, FIT_STRETCH, FIT_PAD, FIT_COVER, FIT_CENTER, FIT_START, FIT_END,
                   DraftGeometry, draft_geometry,
-                  ColorOp, ColorChain, color_check, color_host, COLOR_OPS_MAX,
+                  ColorOp, ColorChain, color_check, color_host, COLOR_OPS_MAX, blur_params, COLOR_BLUR, COLOR_BLUR_BOX_MAX,
                   COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION, COLOR_HUE, COLOR_GRAYSCALE, COLOR_SOLARIZE)
 from .crops import random_resized_crop, random_views, random_multicrop
-from .color import color_jitter, random_apply, random_grayscale, random_solarize, dino_color, hue_shift
+from .color import color_jitter, random_apply, random_grayscale, random_solarize, dino_color, hue_shift, random_blur, dino_augment
 
 __all__ = ["JbError", "Context", "ImageDesc", "Geometry", "DeviceBatch", "lib", "lib_path",
            "make_desc", "geometry_of", "resolve_qtabs", "entropy_decode", "decode_batch", "BatchDecoder", "build_library",
@@ -34,4 +34,5 @@ __all__ = ["JbError", "Context", "ImageDesc", "Geometry", "DeviceBatch", "lib", 
            "DraftGeometry", "draft_geometry",
            "ColorOp", "ColorChain", "color_check", "color_host", "COLOR_OPS_MAX", "COLOR_BRIGHTNESS", "COLOR_CONTRAST",
            "COLOR_SATURATION", "COLOR_HUE", "COLOR_GRAYSCALE", "COLOR_SOLARIZE",
-           "color_jitter", "random_apply", "random_grayscale", "random_solarize", "dino_color", "hue_shift"]
+           "color_jitter", "random_apply", "random_grayscale", "random_solarize", "dino_color", "hue_shift",
+           "blur_params", "COLOR_BLUR", "COLOR_BLUR_BOX_MAX", "random_blur", "dino_augment"]

@@ -120,7 +120,9 @@ class ViewOutput(ctypes.Structure):
 
 # jb_color_op.op (jpegblk.h, "colour chains")
 COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION, COLOR_HUE, COLOR_GRAYSCALE, COLOR_SOLARIZE = 1, 2, 3, 4, 5, 6
+COLOR_BLUR = 16               # (neighbourhood operations are numbered from 16); value: Pillow's GaussianBlur radius
 COLOR_OPS_MAX = 8
+COLOR_BLUR_BOX_MAX = 7        # the largest box radius of a COLOR_BLUR (Gaussian radii up to about 8.4)
 
 
 class ColorOp(ctypes.Structure):
@@ -483,6 +485,14 @@ def color_check(chains):
         raise e
 
 
+def blur_params(radius):
+    """jb_blur_params: Pillow's GaussianBlur radius -> (r, ww, fw), the box radius and the two 8.24 weights of one of its six
+    passes.  JbError for a radius that is negative or not finite (-2) or whose box radius is above COLOR_BLUR_BOX_MAX (-9)."""
+    r, ww, fw = ctypes.c_int32(), ctypes.c_uint32(), ctypes.c_uint32()
+    _check(lib().jb_blur_params(float(radius), ctypes.byref(r), ctypes.byref(ww), ctypes.byref(fw)))
+    return r.value, ww.value, fw.value
+
+
 def color_host(image, chain):
     """jb_color_host: the chain on a host [h, w, 3] uint8 array -> a new array.  The CPU statement of the device kernels'
     arithmetic (the same csrc/jb_color_core.h), for tests and for checking a pipeline without a GPU."""
@@ -695,6 +705,7 @@ def lib():
     pc = ctypes.POINTER(ColorChain)
     L.jb_color_check.argtypes = [pc, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     L.jb_color_host.argtypes = [vp, i64, i32, i32, pc, vp, i64]
+    L.jb_blur_params.argtypes = [ctypes.c_float, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
     L.jb_color_device.argtypes = [vp, vp, i64, i64, i32, i32, i32, pc, vp, i64, i64, ps, vp]
     L.jb_blocks_to_rgb_device_views_color.argtypes = [vp, ctypes.POINTER(DeviceBatch), pv, ctypes.c_int, prs, pc, ps, vp]
     L.jb_blocks_to_rgb_device_view_groups_color.argtypes = [vp, ctypes.POINTER(DeviceBatch), pv, pg, ctypes.POINTER(ViewOutput), ctypes.c_int, pc, ps, vp]
@@ -1032,8 +1043,9 @@ class Context:
         scale): the K = sum of k views of an image fall into G groups, group-major, each with its own target size and filter, all
         from ONE pixel launch per image (jb_blocks_to_rgb_device_view_groups); batch.d_rgb and its strides are not read.
         colors=[[chain, ... K], ... N] with views= (and with view_groups=): chain (i, v) -- None / [] (the identity) or [(COLOR_*,
-        value), ...], at most 8 operations and one COLOR_CONTRAST -- is applied to the uint8 pixels of view v of image i, mirror
-        included, in front of the output format: Pillow's ImageEnhance / convert / ImageOps.solarize bit for bit
+        value), ...], at most 8 operations, one COLOR_CONTRAST and one COLOR_BLUR with no contrast behind it -- is applied to
+        the uint8 pixels of view v of image i, mirror included, in front of the output format: Pillow's ImageEnhance /
+        convert / ImageOps.solarize / ImageFilter.GaussianBlur bit for bit
         (jb_blocks_to_rgb_device_views_color / _view_groups_color).  Without views ValueError.
         Each is the entry point of that suffix (_ROUTES)."""
         request = _Request(scale, fmt, roi, resize, crops, filter, views, fit, view_groups, view_outputs, colors)

@@ -2,10 +2,11 @@
 
 Pure Python over a numpy.random.Generator, like crops.py: the chains of a batch can be drawn before anything is decoded,
 and the same generator state gives the same chains.  A chain is a list of (op, value) with op one of the COLOR_* numbers;
-[] is the identity.  The procedures are torchvision's (ColorJitter, RandomApply, RandomGrayscale, RandomSolarize); the
-generator is numpy's, so the draws are not torch's.
+[] is the identity.  The procedures are torchvision's (ColorJitter, RandomApply, RandomGrayscale, RandomSolarize) and DINO's
+own GaussianBlur class; the generator is numpy's, so the draws are not torch's.
 """
 COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION, COLOR_HUE, COLOR_GRAYSCALE, COLOR_SOLARIZE = 1, 2, 3, 4, 5, 6
+COLOR_BLUR = 16
 
 
 def hue_shift(f):
@@ -56,6 +57,30 @@ def dino_color(rng, global_view_index=None):
     or not, so every view consumes the same draws but the solarize's."""
     jitter = color_jitter(rng, 0.4, 0.4, 0.2, 0.1)
     chain = random_apply(rng, 0.8, jitter) + random_grayscale(rng, 0.2)
+    if global_view_index == 1:
+        chain += random_solarize(rng, 0.2)
+    return chain
+
+
+def random_blur(rng, p, radius_min=0.1, radius_max=2.0):
+    """DINO's GaussianBlur(p, radius_min, radius_max) -- Pillow's ImageFilter.GaussianBlur with a uniform radius: one
+    rng.random() and one rng.uniform(radius_min, radius_max), BOTH always drawn, so every view consumes the same draws
+    -> [(COLOR_BLUR, radius)], or [] when the first draw is not below p."""
+    if not 0 <= radius_min <= radius_max:
+        raise ValueError("0 <= radius_min <= radius_max wanted")
+    apply = float(rng.random()) < p
+    radius = float(rng.uniform(radius_min, radius_max))
+    return [(COLOR_BLUR, radius)] if apply else []
+
+
+def dino_augment(rng, global_view_index=None):
+    """DINO's augmentation behind the crop and the flip for one view, blur included, in the paper's order:
+    ColorJitter(0.4, 0.4, 0.2, 0.1) with p = 0.8, RandomGrayscale(0.2), GaussianBlur with p = 1.0 for the first global view
+    (global_view_index == 0), 0.1 for the second (1) and 0.5 for a local one (None), and for the second global view Solarize
+    with p = 0.2.  The draws are dino_color's, with random_blur's two behind the grayscale's."""
+    jitter = color_jitter(rng, 0.4, 0.4, 0.2, 0.1)
+    chain = random_apply(rng, 0.8, jitter) + random_grayscale(rng, 0.2)
+    chain += random_blur(rng, {0: 1.0, 1: 0.1, None: 0.5}[global_view_index])
     if global_view_index == 1:
         chain += random_solarize(rng, 0.2)
     return chain

@@ -1,6 +1,7 @@
 // jb_color.hip -- "colour chains" (include/jpegblk.h): per-view brightness / contrast / saturation / hue / grayscale /
 // solarize on interleaved uint8 views, written in any of the four output formats.  The arithmetic is jb_color_core.h's,
-// the text the host statement (jb_color_host) compiles too.  Two kernels:
+// the text the host statement (jb_color_host) compiles too.  Three kernels (the third, jb_color_blur_kernel for the views
+// whose chain has a JB_COLOR_BLUR, is described where it stands):
 //
 // jb_color_mean_kernel -- only for launches with a JB_COLOR_CONTRAST: grid (slices of kMeanRows rows, views).  A lane
 //   applies the ops IN FRONT of the chain's contrast to its pixels and sums their luma in a 32-bit integer (at most
@@ -17,6 +18,12 @@
 #include "jb_color_core.h"
 #include "jb_kernels.h"
 #include "jb_launch.h"
+
+// the weights of the launch's blurs, beside JbColorTable in the arguments of jb_color_blur_kernel
+struct JbBlurTable {
+  JbBlurWeights k[kJbCropsPerLaunch];
+};
+static_assert(sizeof(JbColor) + sizeof(JbColorTable) + sizeof(JbBlurTable) <= 4096, "the colour kernels' arguments must fit the 4 KB segment");
 
 static constexpr int kColorRows = 4;  // rows (= waves) per workgroup of the apply kernel
 static constexpr int kMeanRows = 16;  // rows per workgroup of the mean kernel
@@ -74,27 +81,10 @@ __global__ __launch_bounds__(256) void jb_color_mean_kernel(const JbColor p, con
   if (threadIdx.x == 0) atomicAdd(&p.sums[view], (unsigned long long)part[0] + part[1] + part[2] + part[3]);
 }
 
+// n (1..4) pixels px of a row, behind the chain, to columns x.. of the output row at `dst` (of plane 0 when planar) in FORMAT:
+// the ONE store of the colour kernels
 template <int FORMAT>
-__global__ __launch_bounds__(64 * kColorRows) void jb_color_apply_kernel(const JbColor p, const JbColorTable table) {
-  const uint32_t view = blockIdx.y;
-  const JbColorRow &row = table.r[view];
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int lane = (int)(threadIdx.x & 63);
-  const uint32_t tx = blockIdx.x % (uint32_t)p.tiles_x, ty = blockIdx.x / (uint32_t)p.tiles_x;
-  const int y = (int)ty * kColorRows + wave;   // wave-uniform
-  const int x = ((int)tx * 64 + lane) * 4;
-  if (y >= p.h || x >= p.w) return;
-  const int n = min(4, p.w - x);
-  int mean = 0;
-  if (jbc_contrast_at(row.chain) >= 0) mean = jbc_contrast_mean(p.sums[view], (uint64_t)p.w * (uint64_t)p.h);
-  int px[4][3];
-  color_load(p.src + row.src_offset + (int64_t)y * p.src_row_stride + 3 * (int64_t)x, n, px);
-  const int n_ops = row.chain.n_ops;
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-    if (i < n) jbc_apply_ops(row.chain, 0, n_ops, mean, &px[i][0], &px[i][1], &px[i][2]);
-
-  uint8_t *const dst = p.dst + row.dst_offset + (int64_t)y * p.dst_row_stride;
+static __device__ __forceinline__ void color_store(const JbColor &p, uint8_t *const dst, const int x, const int n, const int px[4][3]) {
   if constexpr (FORMAT == 0) {
     uint8_t *const at = dst + 3 * (int64_t)x;
     if (n == 4) {
@@ -153,15 +143,148 @@ __global__ __launch_bounds__(64 * kColorRows) void jb_color_apply_kernel(const J
   }
 }
 
+template <int FORMAT>
+__global__ __launch_bounds__(64 * kColorRows) void jb_color_apply_kernel(const JbColor p, const JbColorTable table) {
+  const uint32_t view = blockIdx.y;
+  const JbColorRow &row = table.r[view];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = (int)(threadIdx.x & 63);
+  if (jbc_blur_at(row.chain) >= 0) return;  // (the whole workgroup: the view is jb_color_blur_kernel's)
+  const uint32_t tx = blockIdx.x % (uint32_t)p.tiles_x, ty = blockIdx.x / (uint32_t)p.tiles_x;
+  const int y = (int)ty * kColorRows + wave;   // wave-uniform
+  const int x = ((int)tx * 64 + lane) * 4;
+  if (y >= p.h || x >= p.w) return;
+  const int n = min(4, p.w - x);
+  int mean = 0;
+  if (jbc_contrast_at(row.chain) >= 0) mean = jbc_contrast_mean(p.sums[view], (uint64_t)p.w * (uint64_t)p.h);
+  int px[4][3];
+  color_load(p.src + row.src_offset + (int64_t)y * p.src_row_stride + 3 * (int64_t)x, n, px);
+  const int n_ops = row.chain.n_ops;
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+    if (i < n) jbc_apply_ops(row.chain, 0, n_ops, mean, &px[i][0], &px[i][1], &px[i][2]);
+
+  color_store<FORMAT>(p, p.dst + row.dst_offset + (int64_t)y * p.dst_row_stride, x, n, px);
+}
+
+// The tile of jb_color_blur_kernel<FORMAT, HALO>: kBlurW x kBlurH output pixels and HALO >= 3 (r + 1) samples around them,
+// three planes of bytes, twice (a pass reads one buffer and writes the other).  The pitch is an ODD number of 4-byte words:
+// in a row pass the lanes of a wave walk along rows one pitch apart, and an odd word pitch spreads 64 of them over the 64
+// banks; in a column pass the lanes walk down adjacent columns: adjacent bytes, the same or the next word.
+static constexpr int kBlurW = 64, kBlurH = 32;
+template <int HALO>
+struct BlurTile {
+  static constexpr int kW = kBlurW + 2 * HALO, kH = kBlurH + 2 * HALO;
+  static constexpr int kPitch = (((kW + 3) / 4) | 1) * 4;
+  static constexpr int kPlane = kPitch * kH;
+  static constexpr int kBytes = 2 * 3 * kPlane;  // HALO 6: 20,064 bytes; HALO 24: 55,680
+};
+static_assert(BlurTile<3 * (JB_COLOR_BLUR_BOX_MAX + 1)>::kBytes <= 64 * 1024, "the blur tile must fit a workgroup's LDS");
+
+// the lines [0, n_lines) of one pass, a thread each: line L is plane L / per_plane, row or column L % per_plane + first_line
+// (no division: three planes)
+template <int HALO>
+static __device__ __forceinline__ void blur_pass(const uint8_t *in, uint8_t *out, bool rows, int first_line, int per_plane, int first, int last,
+                                                 int lo, int hi, const JbBlurWeights &k) {
+  using T = BlurTile<HALO>;
+  for (int L = (int)threadIdx.x; L < 3 * per_plane; L += 256) {
+    const int c = L >= 2 * per_plane ? 2 : L >= per_plane ? 1 : 0;
+    const int line = L - c * per_plane + first_line;
+    const int at = c * T::kPlane + (rows ? line * T::kPitch : line);
+    jbc_blur_line(in + at, out + at, rows ? 1 : T::kPitch, first, last, lo, hi, k);
+  }
+}
+
+// jb_color_blur_kernel -- grid (tiles of 64 x 32 pixels, views); only the views whose chain has a JB_COLOR_BLUR.  The
+// workgroup loads its tile and 3 (r + 1) samples around it from the uint8 stage, positions clamped to the view, applies the
+// ops in front of the blur (with the contrast's mean) to every loaded pixel, runs three row passes and three column passes
+// between two LDS buffers -- each over the region the later passes still read: it shrinks by r + 1 a pass, and only
+// positions INSIDE the view are computed, because a read outside the view goes to the view's edge sample in EVERY pass
+// (jbc_blur_line's clamp) -- then applies the ops behind the blur and stores through color_store.  r, ww, fw and every
+// branch on an op are uniform over the workgroup.
+template <int FORMAT, int HALO>
+__global__ __launch_bounds__(256) void jb_color_blur_kernel(const JbColor p, const JbColorTable table, const JbBlurTable blur) {
+  using T = BlurTile<HALO>;
+  const uint32_t view = blockIdx.y;
+  const JbColorRow &row = table.r[view];
+  const int at = jbc_blur_at(row.chain);
+  if (at < 0) return;  // (the whole workgroup: the view is jb_color_apply_kernel's)
+  const JbBlurWeights k = blur.k[view];
+  const int step = k.r + 1, halo = 3 * step;
+  if (halo > HALO) return;  // (the launch picks HALO from the largest r: not reached)
+  __shared__ uint8_t lds[2][3 * T::kPlane];
+  const uint32_t tiles_x = (uint32_t)(p.w + kBlurW - 1) / (uint32_t)kBlurW;
+  const int x0 = (int)(blockIdx.x % tiles_x) * kBlurW, y0 = (int)(blockIdx.x / tiles_x) * kBlurH;
+  // local (0, 0) of the tile's buffers is the view's (bx, by); bw x bh samples are loaded
+  const int bx = x0 - halo, by = y0 - halo, bw = kBlurW + 2 * halo, bh = kBlurH + 2 * halo;
+  int mean = 0;
+  if (jbc_contrast_at(row.chain) >= 0) mean = jbc_contrast_mean(p.sums[view], (uint64_t)p.w * (uint64_t)p.h);
+  const uint8_t *const src = p.src + row.src_offset;
+  // a thread per loaded sample position, 256 adjacent ones a round (rows of bw = 70..112 positions: whole waves stay busy,
+  // which a wave per row would not: 76 = 64 + 12).  i / bw as a multiplication: exact while i * (inv * bw - 2^24) < 2^24,
+  // and i < 112 * 80, inv * bw - 2^24 < bw <= 112; i * inv < 2^32.
+  const uint32_t inv = ((1u << 24) + (uint32_t)bw - 1u) / (uint32_t)bw;
+#pragma unroll 4
+  for (int i = (int)threadIdx.x; i < bw * bh; i += 256) {
+    const int ly = (int)(((uint32_t)i * inv) >> 24), lx = i - ly * bw;
+    const int gy = min(max(by + ly, 0), p.h - 1), gx = min(max(bx + lx, 0), p.w - 1);
+    const uint8_t *const from = src + (int64_t)gy * p.src_row_stride + 3 * gx;
+    int r = from[0], g = from[1], b = from[2];
+    jbc_apply_ops(row.chain, 0, at, mean, &r, &g, &b);
+    uint8_t *const to = &lds[0][ly * T::kPitch + lx];
+    to[0] = (uint8_t)r, to[T::kPlane] = (uint8_t)g, to[2 * T::kPlane] = (uint8_t)b;
+  }
+  // the view's extent in local coordinates, and the part of the buffers inside the view
+  const int vx0 = -bx, vx1 = p.w - 1 - bx, vy0 = -by, vy1 = p.h - 1 - by;
+  const int rows0 = max(0, vy0), rows1 = min(bh, vy1 + 1);              // the rows the row passes run over
+  const int cols0 = halo, cols1 = min(halo + kBlurW, vx1 + 1);          // the columns the column passes run over
+#pragma unroll 1
+  for (int pass = 1; pass <= 3; pass++) {
+    __syncthreads();
+    blur_pass<HALO>(lds[(pass - 1) & 1], lds[pass & 1], true, rows0, rows1 - rows0, max(pass * step, vx0), min(bw - pass * step, vx1 + 1), vx0, vx1, k);
+  }
+#pragma unroll 1
+  for (int pass = 1; pass <= 3; pass++) {
+    __syncthreads();
+    blur_pass<HALO>(lds[pass & 1], lds[(pass - 1) & 1], false, cols0, cols1 - cols0, max(pass * step, vy0), min(bh - pass * step, vy1 + 1), vy0, vy1, k);
+  }
+  __syncthreads();
+  // the result is in lds[0]: 16 groups of 4 pixels a row, 32 rows
+  const int n_ops = row.chain.n_ops;
+  for (int item = (int)threadIdx.x; item < (kBlurW / 4) * kBlurH; item += 256) {
+    const int ry = item / (kBlurW / 4), x = x0 + 4 * (item % (kBlurW / 4)), y = y0 + ry;
+    if (y >= p.h || x >= p.w) continue;
+    const int n = min(4, p.w - x);
+    const uint8_t *const from = &lds[0][(halo + ry) * T::kPitch + halo + (x - x0)];
+    int px[4][3];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+#pragma unroll
+      for (int c = 0; c < 3; c++) px[i][c] = i < n ? from[c * T::kPlane + i] : 0;
+      if (i < n) jbc_apply_ops(row.chain, at + 1, n_ops, 0, &px[i][0], &px[i][1], &px[i][2]);
+    }
+    color_store<FORMAT>(p, p.dst + row.dst_offset + (int64_t)y * p.dst_row_stride, x, n, px);
+  }
+}
+
 hipError_t jbk_color_launch(const JbColor &q, const JbColorTable &table, int format, hipStream_t stream) {
   if (format < 0 || format > 3 || q.w < 1 || q.h < 1 || q.w > 65535 || q.h > 65535 || q.n_views < 1 || q.n_views > kJbCropsPerLaunch || !q.src ||
       !q.dst || !q.sums || q.src_row_stride < 3LL * q.w)
     return hipErrorInvalidValue;
   bool contrast = false;
+  int blur_r = -1;  // the largest box radius of the launch's blurs
+  JbBlurTable blurs = {};
   for (int i = 0; i < q.n_views; i++) {
     const JbColorRow &r = table.r[i];
     if (r.src_offset < 0 || r.dst_offset < 0 || r.chain.n_ops < 0 || r.chain.n_ops > JB_COLOR_OPS_MAX) return hipErrorInvalidValue;
-    if (jbc_contrast_at(r.chain) >= 0) contrast = true;
+    const int c_at = jbc_contrast_at(r.chain), b_at = jbc_blur_at(r.chain);
+    if (c_at >= 0) contrast = true;
+    if (b_at >= 0) {
+      // the mean kernel applies the ops in front of the contrast: never a blur (jb_color_check refuses a contrast behind one)
+      bool geometry;
+      if (c_at > b_at || !jbc_blur_weights(r.chain.ops[b_at].value, &blurs.k[i], &geometry)) return hipErrorInvalidValue;
+      blur_r = blurs.k[i].r > blur_r ? blurs.k[i].r : blur_r;
+    }
   }
   JbColor p = q;
   p.tiles_x = (p.w + 255) / 256;
@@ -175,5 +298,15 @@ hipError_t jbk_color_launch(const JbColor &q, const JbColorTable &table, int for
   }
   const dim3 grid((unsigned)(p.tiles_x * tiles_y), (unsigned)p.n_views), block(64 * kColorRows);
   jb_by_format(format, [&](auto F) { hipLaunchKernelGGL(jb_color_apply_kernel<decltype(F)::value>, grid, block, 0, stream, p, table); });
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || blur_r < 0) return e;
+  // the tile kernel, with the small halo (r <= 1: every published pipeline; 20 KB of LDS) or the one for r <= 7 (56 KB)
+  const dim3 blur_grid((unsigned)(((p.w + kBlurW - 1) / kBlurW) * ((p.h + kBlurH - 1) / kBlurH)), (unsigned)p.n_views);
+  jb_by_format(format, [&](auto F) {
+    if (blur_r <= 1)
+      hipLaunchKernelGGL((jb_color_blur_kernel<decltype(F)::value, 6>), blur_grid, dim3(256), 0, stream, p, table, blurs);
+    else
+      hipLaunchKernelGGL((jb_color_blur_kernel<decltype(F)::value, 3 * (JB_COLOR_BLUR_BOX_MAX + 1)>), blur_grid, dim3(256), 0, stream, p, table, blurs);
+  });
   return hipGetLastError();
 }

@@ -2,6 +2,7 @@
 // place: jb_color.hip compiles it for gfx950, jb_color_host (jb_color.hip's host half) and the CPU tests the same text for
 // the host.  It is Pillow's, operation for operation -- ImageEnhance.Brightness / Contrast / Color are Image.blend against
 // a degenerate image, the hue shift is convert("HSV") and back, grayscale is convert("L"), solarize is ImageOps.solarize.
+// JB_COLOR_BLUR is ImageFilter.GaussianBlur: BoxBlur.c's weights and its one pass along a line, at the end of this file.
 //
 // Every float step is written as ONE operation per statement and the file is built with -ffp-contract=off and without
 // fast-math: a product and the sum behind it stay two roundings, and f32 / f64 divisions are correctly rounded.
@@ -148,4 +149,97 @@ JBC_FN int jbc_contrast_at(const jb_color_chain &c) {
   for (int i = 0; i < c.n_ops && i < JB_COLOR_OPS_MAX; i++)
     if (c.ops[i].op == JB_COLOR_CONTRAST) return i;
   return -1;
+}
+
+// the index of the chain's JB_COLOR_BLUR (jb_color_check allows one, and no contrast behind it); -1: none
+JBC_FN int jbc_blur_at(const jb_color_chain &c) {
+  for (int i = 0; i < c.n_ops && i < JB_COLOR_OPS_MAX; i++)
+    if (c.ops[i].op == JB_COLOR_BLUR) return i;
+  return -1;
+}
+
+// ---- JB_COLOR_BLUR: Pillow's ImageFilter.GaussianBlur, three extended box blur passes along the rows, then three along
+// the columns, each rounded to uint8 (BoxBlur.c) ----
+// The weights of one pass: box radius r, 8.24 weights ww (the 2 r + 1 samples of the box) and fw (the two samples beside it).
+struct JbBlurWeights {
+  int32_t r;
+  uint32_t ww, fw;
+};
+
+// Pillow's _gaussian_blur_radius and ImagingLineBoxBlur's weights.  Only the HOST evaluates this (jb_blur_params): the double
+// sqrt and the float32 steps decide bits, and the weights travel to the kernel as three integers.  One operation per statement.
+// false: the radius is negative or not finite (*geometry = true), or r > JB_COLOR_BLUR_BOX_MAX (*geometry = false).
+JBC_FN bool jbc_blur_weights(float radius, JbBlurWeights *o, bool *geometry) {
+  *geometry = true;
+  if (!(radius >= 0.0f) || !(radius <= 3.402823466e38f)) return false;
+  *geometry = false;
+  const float rr = radius * radius;
+  const float sigma2 = rr / 3.0f;
+  const double l12 = 12.0 * (double)sigma2;
+  const double l121 = l12 + 1.0;
+  const float L = (float)sqrt(l121);
+  const double lm1 = (double)L - 1.0;
+  const float l = (float)floor(lm1 / 2.0);
+  if (!(l <= (float)JB_COLOR_BLUR_BOX_MAX)) return false;  // (a radius whose square is not finite too)
+  const float l2 = 2.0f * l;
+  const float l21 = l2 + 1.0f;
+  const float lp1 = l + 1.0f;
+  const float llp1 = l * lp1;
+  const float s3 = 3.0f * sigma2;
+  const float d1 = llp1 - s3;
+  const float num = l21 * d1;
+  const float sq = lp1 * lp1;
+  const float d2 = sigma2 - sq;
+  const float den = 6.0f * d2;
+  const float a = num / den;
+  const float fr = l + a;
+  if (!(fr < (float)(JB_COLOR_BLUR_BOX_MAX + 1))) return false;
+  const int32_t r = (int32_t)fr;
+  const float f2 = fr * 2.0f;
+  const float f21 = f2 + 1.0f;
+  const float wq = 16777216.0f / f21;
+  const uint32_t ww = (uint32_t)wq;
+  o->r = r;
+  o->ww = ww;
+  o->fw = (16777216u - (uint32_t)(2 * r + 1) * ww) / 2u;
+  return true;
+}
+
+// one sample of one pass: box = the sum of the 2 r + 1 samples of the box, sides = the sum of the two samples beside it.
+// Exact in uint32: ww (2 r + 1) + 2 fw <= 2^24.
+JBC_FN uint32_t jbc_blur_sample(uint32_t ww, uint32_t fw, uint32_t box, uint32_t sides) { return (ww * box + fw * sides + (1u << 23)) >> 24; }
+
+// one pass along one line: samples first..last-1 of `out` from `in`, both addressed in[i * stride]; a read of position i goes to
+// min(max(i, lo), hi), the view's two edge samples on this line.  The box sum runs along the line: two reads a sample, whatever r.
+// STRIDE: int for the kernel's tile, int64_t for the host's whole image.
+// in and out never overlap, and the reads of a sample do not depend on the sums in front of it: eight samples' reads are
+// issued together (on the device one wait for sixteen LDS loads, not eight waits for two), then the running sum goes along.
+template <typename STRIDE>
+JBC_FN void jbc_blur_line(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, STRIDE stride, int first, int last, int lo, int hi,
+                          const JbBlurWeights &k) {
+  if (first >= last) return;
+  const int r = k.r;
+#define JBC_AT(i) ((uint32_t)in[((i) < lo ? lo : (i) > hi ? hi : (i)) * stride])
+  uint32_t box = 0;
+  for (int j = -r; j <= r; j++) box += JBC_AT(first + j);
+  uint32_t left = JBC_AT(first - r - 1);
+  int x = first;
+  for (; x + 8 <= last; x += 8) {
+    uint32_t right[8], leave[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) right[j] = JBC_AT(x + j + r + 1), leave[j] = JBC_AT(x + j - r);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      out[(x + j) * stride] = (uint8_t)jbc_blur_sample(k.ww, k.fw, box, left + right[j]);
+      left = leave[j];
+      box = box + right[j] - left;
+    }
+  }
+  for (; x < last; x++) {
+    const uint32_t right = JBC_AT(x + r + 1);
+    out[x * stride] = (uint8_t)jbc_blur_sample(k.ww, k.fw, box, left + right);
+    left = JBC_AT(x - r);  // (the left neighbour of the box of x + 1: the sample that leaves the box)
+    box = box + right - left;
+  }
+#undef JBC_AT
 }

@@ -15,12 +15,14 @@ const char *chain_refusal(const jb_color_chain &c, int *status) {
   *status = JB_ERR_GEOMETRY;
   if (c.n_ops < 0 || c.n_ops > JB_COLOR_OPS_MAX) return "n_ops is outside 0..8";
   if (c.reserved != 0) return "reserved is not 0";
-  int contrasts = 0;
+  int contrasts = 0, blurs = 0;
+  bool box_too_large = false, contrast_behind_blur = false;
   for (int i = 0; i < c.n_ops; i++) {
     const float v = c.ops[i].value;
     switch (c.ops[i].op) {
       case JB_COLOR_CONTRAST:
         contrasts++;
+        if (blurs) contrast_behind_blur = true;
         [[fallthrough]];
       case JB_COLOR_BRIGHTNESS:
       case JB_COLOR_SATURATION:
@@ -35,11 +37,24 @@ const char *chain_refusal(const jb_color_chain &c, int *status) {
       case JB_COLOR_GRAYSCALE:
         if (v != 0.0f) return "the value of JB_COLOR_GRAYSCALE is not 0";
         break;
+      case JB_COLOR_BLUR: {
+        JbBlurWeights k;
+        bool geometry;
+        if (!jbc_blur_weights(v, &k, &geometry)) {
+          if (geometry) return "a blur radius is not finite or below 0";
+          box_too_large = true;
+        }
+        blurs++;
+        break;
+      }
       default: return "unknown op";
     }
   }
   *status = JB_ERR_UNSUPPORTED;
   if (contrasts > 1) return "more than one JB_COLOR_CONTRAST in a chain (each costs a reduction pass)";
+  if (box_too_large) return "a blur radius whose box radius is above JB_COLOR_BLUR_BOX_MAX (7: Gaussian radii up to about 8.4)";
+  if (blurs > 1) return "more than one JB_COLOR_BLUR in a chain (each costs a tile pass)";
+  if (contrast_behind_blur) return "a JB_COLOR_CONTRAST behind a JB_COLOR_BLUR (its mean would be the blurred view's)";
   *status = JB_OK;
   return nullptr;
 }
@@ -57,6 +72,17 @@ extern "C" int jb_color_check(const jb_color_chain *chains, int n, int *bad_inde
       return jb_fail_(nullptr, status, ("colour chain " + std::to_string(i) + ": " + why).c_str());
     }
   }
+  return JB_OK;
+}
+
+extern "C" int jb_blur_params(float radius, int32_t *r, uint32_t *ww, uint32_t *fw) {
+  if (!r || !ww || !fw) return jb_fail_(nullptr, JB_ERR_NULL, "jb_blur_params: NULL pointer");
+  JbBlurWeights k;
+  bool geometry;
+  if (!jbc_blur_weights(radius, &k, &geometry))
+    return geometry ? jb_fail_(nullptr, JB_ERR_GEOMETRY, "jb_blur_params: the radius is not finite or below 0")
+                    : jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_blur_params: the box radius is above JB_COLOR_BLUR_BOX_MAX (7)");
+  *r = k.r, *ww = k.ww, *fw = k.fw;
   return JB_OK;
 }
 
@@ -82,12 +108,56 @@ extern "C" int jb_color_host(const uint8_t *in, int64_t in_row_stride, int32_t w
     }
     mean = jbc_contrast_mean(sum, (uint64_t)w * (uint64_t)h);
   }
+  const int blur = jbc_blur_at(*chain);
+  if (blur < 0) {
+    for (int y = 0; y < h; y++) {
+      const uint8_t *p = in + y * in_row_stride;
+      uint8_t *q = out + y * out_row_stride;
+      for (int x = 0; x < w; x++, p += 3, q += 3) {
+        int r = p[0], g = p[1], b = p[2];
+        jbc_apply_ops(*chain, 0, chain->n_ops, mean, &r, &g, &b);
+        q[0] = (uint8_t)r, q[1] = (uint8_t)g, q[2] = (uint8_t)b;
+      }
+    }
+    return JB_OK;
+  }
+  // the blur kernel's order: the ops in front of the blur, six passes between two buffers of its own (in == out is
+  // allowed), the ops behind it
+  JbBlurWeights k;
+  bool geometry;
+  if (!jbc_blur_weights(chain->ops[blur].value, &k, &geometry)) return jb_fail_(nullptr, JB_ERR_UNSUPPORTED, "jb_color_host: blur radius");
+  const int64_t row = 3LL * w;
+  std::vector<uint8_t> a, b2;
+  try {
+    a.resize((size_t)(row * h)), b2.resize((size_t)(row * h));
+  } catch (const std::bad_alloc &) {
+    return jb_fail_(nullptr, JB_ERR_CAPACITY, "jb_color_host: no memory for the blur's two buffers");
+  }
   for (int y = 0; y < h; y++) {
     const uint8_t *p = in + y * in_row_stride;
+    uint8_t *q = a.data() + y * row;
+    for (int x = 0; x < w; x++, p += 3, q += 3) {
+      int r = p[0], g = p[1], b = p[2];
+      jbc_apply_ops(*chain, 0, blur, mean, &r, &g, &b);
+      q[0] = (uint8_t)r, q[1] = (uint8_t)g, q[2] = (uint8_t)b;
+    }
+  }
+  uint8_t *src = a.data(), *dst = b2.data();
+  for (int pass = 0; pass < 6; pass++) {
+    if (pass < 3) {
+      for (int y = 0; y < h; y++)
+        for (int c = 0; c < 3; c++) jbc_blur_line(src + y * row + c, dst + y * row + c, (int64_t)3, 0, w, 0, w - 1, k);
+    } else {
+      for (int64_t xc = 0; xc < row; xc++) jbc_blur_line(src + xc, dst + xc, row, 0, h, 0, h - 1, k);
+    }
+    std::swap(src, dst);
+  }
+  for (int y = 0; y < h; y++) {
+    const uint8_t *p = src + y * row;
     uint8_t *q = out + y * out_row_stride;
     for (int x = 0; x < w; x++, p += 3, q += 3) {
       int r = p[0], g = p[1], b = p[2];
-      jbc_apply_ops(*chain, 0, chain->n_ops, mean, &r, &g, &b);
+      jbc_apply_ops(*chain, blur + 1, chain->n_ops, 0, &r, &g, &b);
       q[0] = (uint8_t)r, q[1] = (uint8_t)g, q[2] = (uint8_t)b;
     }
   }

@@ -231,7 +231,12 @@ struct JbColor {
 };
 // Where a chain of the launch has a JB_COLOR_CONTRAST: `sums` zeroed on the stream, then jb_color_mean_kernel (a workgroup
 // per 16 rows of a view; integer sums, one 64-bit atomic per workgroup).  Then jb_color_apply_kernel: one workgroup per 256
-// columns x 4 rows of a view, a lane per 4 pixels of a row.  An argument outside its range: hipErrorInvalidValue.
+// columns x 4 rows of a view, a lane per 4 pixels of a row.  Where a chain of the launch has a JB_COLOR_BLUR, then
+// jb_color_blur_kernel too: one workgroup per 64 x 32 pixels of a view; the views with a blur are its, the others the apply
+// kernel's, and the workgroups of the other kernel's views return at once.  The launch turns each blur's radius into its
+// three integers on the host (jbc_blur_weights): 12 bytes a view beside the table, 3.3 KB of arguments in all.  A launch
+// without a blur issues what it issued before there was one.  An argument outside its range, a blur in front of a contrast
+// or a box radius above JB_COLOR_BLUR_BOX_MAX: hipErrorInvalidValue.
 hipError_t jbk_color_launch(const JbColor &p, const JbColorTable &table, int format, hipStream_t stream);
 
 // "Fit" (jb_fit.hip jb_fit_fill_kernel): the border of n_images letterboxed outputs of ow x oh at dst, addressed as
