@@ -61,6 +61,8 @@
  *                          staged, line-aligned store stage for every image that takes the linear tiling
  *   JPEGBLK_SMALL_GRID     1 = always the one-wave kernels (every layout has one), 0 = never (default: launches of
  *                          up to 8 workgroups per CU of the 192-lane kernel, e.g. one to four 1080p images, one 4096x4096 4:2:0)
+ *   JPEGBLK_FLAT_FRONT     0 = never the flat entry of the 4:4:4 pixel kernel (default: every launch whose tiles are all
+ *                          full and whose images' coefficients lie densely takes it; see jb_ctx_last_front)
  *   JPEGBLK_TIMING         1 | 2 | 3 = where one decode(bytes) / one device-entropy submission / one batch run spends its time (stderr)
  *   JPEGBLK_RESIZE_TMP_BYTES  bytes of full-size intermediates one launch pair of a decode to a fixed output size may
  *                          hold (default 128 MiB; more runs as sub-batches of whole images, one image at the least;
@@ -220,6 +222,21 @@ int jb_resolve_qtabs(const jb_image_desc *desc, const uint16_t *qtabs, int32_t *
  * 4:2:0) run as jb_small_kernel_444 / _420 / _16<2,1> / _16<1,2> instead (JPEGBLK_SMALL_GRID): four entry points
  * of one kernel body, one per layout. */
 const char *jb_kernel_name(const jb_image_desc *desc);
+/* Which front end the context's last launch of that kernel took, for tests and profilers: JB_FRONT_FLAT when every
+ * workgroup's coefficients start at d_coef + workgroup * tile bytes -- 4:4:4 at full size, the whole image, every tile
+ * full (64 MCUs) and the images coef_image_stride = their own length apart -- so that the kernel issues its loads before it
+ * has read anything else of its arguments; JB_FRONT_GENERAL otherwise; JB_FRONT_NONE before the first such launch.  The
+ * output's pitch, strides and width play no part, and the pixels are the same either way.  A profiler sees a flat launch
+ * as jb_tile_kernel_flat<LINEAR, FORMAT>: the body of jb_kernel_name's kernel behind a second entry.  *linear (may be NULL): 1 when
+ * that launch's tiles followed the MCU stream across MCU rows, 0 when each was a run of one MCU row. */
+#define JB_FRONT_NONE 0
+#define JB_FRONT_GENERAL 1
+#define JB_FRONT_FLAT 2
+int jb_ctx_last_front(const jb_ctx *ctx, int *linear);
+/* The geometry behind JB_FRONT_FLAT, a pure host function: would n_images images of mcus_x x mcus_y MCUs with luma
+ * sampling (hs, vs), coef_image_stride bytes apart, tiled along the MCU stream (linear = 1) or per MCU row (0), be such a
+ * launch?  1 or 0; 0 for arguments outside their range. */
+int jb_flat_front_geometry(int hs, int vs, int linear, int32_t mcus_x, int32_t mcus_y, int32_t n_images, int64_t coef_image_stride);
 
 /* ---- scaled output: decode at 1/2, 1/4 or 1/8 size ---------------------------------------
  * For denom K in {1, 2, 4, 8} an image of W x H decodes to ceil(W/K) x ceil(H/K) RGB pixels (interleaved

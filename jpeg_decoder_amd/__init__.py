@@ -9,7 +9,7 @@ There is no CPU fallback: if the library is missing, or no HIP device is usable,
 loudly (ImportError / JbError).
 """
 from .api import (JbError, Context, ImageDesc, Geometry, DeviceBatch, lib, lib_path, make_desc,
-                  geometry_of, resolve_qtabs, entropy_decode, decode_batch, BatchDecoder, build_library, scaled_size,
+                  geometry_of, flat_front_geometry, resolve_qtabs, entropy_decode, decode_batch, BatchDecoder, build_library, scaled_size,
                   OutputSpec, output_bytes, torch_batch, FMT_RGB_U8_HWC, FMT_RGB_U8_CHW, FMT_RGB_F32_CHW, FMT_RGB_F16_CHW,
                   FMT_DTYPE, Roi, roi_check, resize_check, crops_check, Resize, filter_check, filter_window,
                   FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC, ARITH_REFERENCE, ARITH_LIBJPEG,
@@ -23,7 +23,7 @@ from .crops import random_resized_crop, random_views, random_multicrop
 from .color import color_jitter, random_apply, random_grayscale, random_solarize, dino_color, hue_shift, random_blur, dino_augment
 
 __all__ = ["JbError", "Context", "ImageDesc", "Geometry", "DeviceBatch", "lib", "lib_path",
-           "make_desc", "geometry_of", "resolve_qtabs", "entropy_decode", "decode_batch", "BatchDecoder", "build_library",
+           "make_desc", "geometry_of", "flat_front_geometry", "resolve_qtabs", "entropy_decode", "decode_batch", "BatchDecoder", "build_library",
            "scaled_size", "OutputSpec", "output_bytes", "torch_batch", "FMT_RGB_U8_HWC", "FMT_RGB_U8_CHW", "FMT_RGB_F32_CHW",
            "FMT_RGB_F16_CHW", "FMT_DTYPE", "Roi", "roi_check", "resize_check", "crops_check",
            "random_resized_crop", "Resize", "filter_check", "filter_window", "FILTER_AREA", "FILTER_BILINEAR", "FILTER_BICUBIC",

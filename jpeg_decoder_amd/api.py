@@ -637,6 +637,8 @@ def lib():
     L.jb_resolve_qtabs.argtypes = [pd, vp, vp]
     L.jb_kernel_name.argtypes = [pd]
     L.jb_kernel_name.restype = ctypes.c_char_p
+    L.jb_ctx_last_front.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
+    L.jb_flat_front_geometry.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i64]
     L.jb_entropy_decode.argtypes = [vp, ctypes.c_size_t, pd, vp, vp, ctypes.c_size_t]
     L.jb_entropy_decode_mt.argtypes = [vp, ctypes.c_size_t, pd, vp, vp, ctypes.c_size_t, ctypes.c_int]
     L.jb_decode_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32)]
@@ -770,6 +772,11 @@ def geometry_of(desc):
     g = Geometry()
     _check(lib().jb_geometry_of(ctypes.byref(desc), ctypes.byref(g)))
     return g
+
+
+def flat_front_geometry(hs, vs, linear, mcus_x, mcus_y, n_images, coef_image_stride):
+    """jb_flat_front_geometry: may a launch of n_images such images take the 4:4:4 kernel's flat front end?  (no GPU needed)"""
+    return bool(lib().jb_flat_front_geometry(hs, vs, int(linear), mcus_x, mcus_y, n_images, coef_image_stride))
 
 
 def scaled_size(width, height, scale):
@@ -913,6 +920,13 @@ class Context:
     @property
     def device(self):
         return lib().jb_ctx_device(self._h)
+
+    def last_front(self):
+        """jb_ctx_last_front: (JB_FRONT_* of the context's last launch of the tile kernel -- 0 none yet, 1 general, 2 flat --,
+        1 if that launch's tiling was linear else 0)."""
+        linear = ctypes.c_int(0)
+        front = lib().jb_ctx_last_front(self._h, ctypes.byref(linear))
+        return front, linear.value
 
     @property
     def device_entropy_images(self):

@@ -104,6 +104,8 @@ struct jb_ctx {
   // "Draft decode" (include/jpegblk.h): 1, 2, 4, 8.  Not 1: the plans of this context's later calls are made for the
   // draft frame (jb_draft_desc_) and its pixel launches (JB_ARITH_LIBJPEG's alone) decode that frame.
   int draft = 1;
+  // which front end the last launch of the tile kernel took (JB_FRONT_*, jb_ctx_last_front) and whether its tiling was linear
+  int last_front = JB_FRONT_NONE, last_linear = 0;
 };
 
 // the error text of a failed call, formatted: into the context (ctx may be null) and the calling thread (jb_fail_)

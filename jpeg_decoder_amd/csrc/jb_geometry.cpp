@@ -35,6 +35,18 @@ int jb_geometry_of(const jb_image_desc *d, jb_geometry *g) {
   return JB_OK;
 }
 
+// "flat front end": workgroup t of a launch reads its tile at img * stride + (my * mcus_x + mx0) * 384, (img, my, mx0) its
+// image, MCU row and first MCU.  That is t * 24576 for every t exactly when no tile is short -- a row-bound tile ends with
+// its MCU row, a linear one with its image -- and the images are as far apart as their tiles are long; one image has no
+// distance to the next.  4:4:4 only: the layout whose tile is 64 MCUs of three blocks (jb_kernels.hip).
+int jb_flat_front_geometry(int hs, int vs, int linear, int32_t mcus_x, int32_t mcus_y, int32_t n_images, int64_t coef_image_stride) {
+  if (hs != 1 || vs != 1 || mcus_x < 1 || mcus_y < 1 || n_images < 1) return 0;
+  constexpr int64_t kTileMcus = 64, kTileBytes = kTileMcus * 3 * 128;
+  const int64_t mcus = (int64_t)mcus_x * mcus_y;
+  if (linear ? mcus % kTileMcus != 0 : mcus_x % kTileMcus != 0) return 0;
+  return n_images == 1 || coef_image_stride == mcus / kTileMcus * kTileBytes;
+}
+
 int jb_scaled_size(int32_t width, int32_t height, int denom, int32_t *out_w, int32_t *out_h) {
   if (!out_w || !out_h) return JB_ERR_NULL;
   if (denom != 1 && denom != 2 && denom != 4 && denom != 8) return JB_ERR_GEOMETRY;

@@ -79,7 +79,17 @@ int jbk_linear_ok(int hs, int vs, int mcus_x);
 // p.scale / p.bias the float formats' affine map.  Either exists in the row-bound tiling only (p.linear = p.small_grid
 // = 0) and not together: anything else is hipErrorInvalidValue.  p.roi = 1: the same kernel with the ROI store stage, for
 // scale 1 and any p.format, row-bound tiling only.
-hipError_t jbk_launch(const JbLaunch &p, int hs, int vs, int scale, hipStream_t stream);
+// flat = true: the flat entry of the 4:4:4 kernel -- its leading arguments are scalars, delivered in SGPRs at wave start,
+// and every wave issues its coefficient loads from p.coef + blockIdx * 24576 before it has read p.  Only for a launch of
+// which jbk_flat_front says 1: anything else is hipErrorInvalidValue.
+hipError_t jbk_launch(const JbLaunch &p, int hs, int vs, int scale, hipStream_t stream, bool flat = false);
+// May the launch jbk_launch(p, hs, vs, scale) take the flat entry?  The full-size store stages of the whole image (any
+// format, either tiling; not the small-grid kernels), and the geometry of jb_flat_front_geometry (include/jpegblk.h).
+// Nothing about the output enters it.  Host code only.
+inline int jbk_flat_front(const JbLaunch &p, int hs, int vs, int scale) {
+  if (scale != 1 || p.roi || p.small_grid || p.staged || p.tiles_per_image < 1) return 0;
+  return jb_flat_front_geometry(hs, vs, p.linear, p.mcus_x, p.mcus_y, p.n_tiles / p.tiles_per_image, p.coef_image_stride);
+}
 // p.roi = 2: the ROI store stage with a rectangle per image (format 0, scale 1, row-bound tiling; at most
 // kJbCropsPerLaunch images).  The grid is n_images x p.tiles_per_image, p.tiles_per_image the largest n_tiles of the
 // table; a workgroup beyond its image's n_tiles returns at once.  Image i is written as tight interleaved uint8 rows

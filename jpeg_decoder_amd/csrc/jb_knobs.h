@@ -17,6 +17,8 @@
 //                         line-aligned store stage for every image that takes the linear tiling
 //   JPEGBLK_SMALL_GRID    1 = always the one-wave kernels (every layout has one), 0 = never (default: for launches
 //                         of up to 8 workgroups per CU of the 192-lane kernel, e.g. one to four 1080p images, one 4096x4096 4:2:0)
+//   JPEGBLK_FLAT_FRONT    0: never the flat entry of the 4:4:4 tile kernel (default: every launch whose tiles are all
+//                         full and whose images lie densely takes it; jbk_flat_front of jb_kernels.h)
 //   JPEGBLK_PASS1         1: a batch run always reads every file's headers first (default: only a decoder whose
 //                         buffers do not exist yet does; otherwise files are parsed as their groups are formed)
 //   JPEGBLK_GROUP_RAMP    1: a thread's first two device groups are a quarter and a half of the full size (default: full)
@@ -51,6 +53,7 @@ struct JbKnobs {
   bool group_ramp = false;
   int small_grid = -1;       // -1: automatic
   int staged_store = 0;
+  bool flat_front = true;
   long group_mb = -1;        // -1: the default
   long dev_group_mb = -1;
   int numa = -1;             // -1: automatic, 0: off, 1: forced
@@ -77,6 +80,7 @@ inline JbKnobs jb_knobs_read() {
   k.group_ramp = flag("JPEGBLK_GROUP_RAMP");
   if (const char *e = getenv("JPEGBLK_STAGED_STORE")) k.staged_store = e[0] == '1' ? 1 : 0;
   if (const char *e = getenv("JPEGBLK_SMALL_GRID")) k.small_grid = e[0] == '0' ? 0 : e[0] == '1' ? 1 : -1;
+  if (const char *e = getenv("JPEGBLK_FLAT_FRONT")) k.flat_front = e[0] != '0';
   if (const char *e = getenv("JPEGBLK_GROUP_MB")) k.group_mb = atol(e) < 0 ? 0 : atol(e);
   if (const char *e = getenv("JPEGBLK_DEV_GROUP_MB")) k.dev_group_mb = atol(e) < 0 ? 0 : atol(e);
   if (const char *e = getenv("JPEGBLK_NUMA")) k.numa = e[0] == '0' ? 0 : e[0] == '1' ? 1 : -1;

@@ -857,8 +857,11 @@ int seam_launch(jb_ctx *ctx, const jb_device_batch *b, void *stream, const JbOut
   if (ctx->arithmetic == JB_ARITH_LIBJPEG) return seam_launch_lj(ctx, b, stream, plan, g, p);
   rc = seam_tiles(ctx, b, g, plan, p);
   if (rc) return rc;
+  // the flat front end (jb_kernels.h): wherever every workgroup's coefficients lie at d_coef + workgroup * tile bytes
+  const bool flat = ctx->knobs.flat_front && jbk_flat_front(p, b->desc.hs, b->desc.vs, plan.scale);
   DeviceGuard guard(ctx->device);
-  JB_HIP(ctx, jbk_launch(p, b->desc.hs, b->desc.vs, plan.scale, stream ? (hipStream_t)stream : ctx->stream));
+  JB_HIP(ctx, jbk_launch(p, b->desc.hs, b->desc.vs, plan.scale, stream ? (hipStream_t)stream : ctx->stream, flat));
+  ctx->last_front = flat ? JB_FRONT_FLAT : JB_FRONT_GENERAL, ctx->last_linear = p.linear;
   return JB_OK;
 }
 
@@ -876,6 +879,11 @@ extern "C" {
 const char *jb_kernel_name(const jb_image_desc *d) {
   if (!d) return "";
   return jbk_kernel_name(d->hs, d->vs);
+}
+
+int jb_ctx_last_front(const jb_ctx *ctx, int *linear) {
+  if (linear) *linear = ctx ? ctx->last_linear : 0;
+  return ctx ? ctx->last_front : JB_FRONT_NONE;
 }
 
 int jb_blocks_to_rgb_device(jb_ctx *ctx, const jb_device_batch *b, void *stream) {
