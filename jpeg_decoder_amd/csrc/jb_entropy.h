@@ -1,6 +1,7 @@
-// jb_entropy.h -- internal: the entropy-decoding primitives shared by the fast baseline front end
+// jb_entropy.h -- internal: the entropy-decoding primitives shared by the baseline scan decoder
 // (jb_frontend.cpp) and the general multi-scan / progressive one (jb_frontend_ext.cpp): zig-zag
 // order, canonical Huffman tables with lookahead, the MSB-first bit reader, one sequential block.
+// (The header the markers fill and the walk over them: jb_markers.h.)
 #ifndef JB_ENTROPY_H
 #define JB_ENTROPY_H
 

@@ -1,5 +1,7 @@
-// jb_frontend_ext.cpp -- the general host front end: what the fast baseline path
-// (jb_frontend.cpp) turns away but ITU-T T.81 allows and real files contain:
+// jb_frontend_ext.cpp -- the general rules of the host front end and the scan decoders behind them: what the baseline
+// rules (jb_frontend.cpp) answer JB_ERR_UNSUPPORTED to but ITU-T T.81 allows and real files contain.  The marker walk,
+// the header and the DQT / DHT / DRI segments are shared with them (jb_markers.h); the frame and scan rules (parse_sof,
+// parse_sos) are this file's own, and where they differ from the baseline ones on purpose is listed in jb_frontend.cpp.
 //   * progressive DCT frames (SOF2): spectral selection + successive approximation, Annex G;
 //   * grayscale frames (one component);
 //   * sequential frames coded in several scans (non-interleaved components).
@@ -18,52 +20,22 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 
 #include "../../include/jpegblk.h"
-#include "jb_entropy.h"
+#include "jb_markers.h"
 #include "jb_internal.h"
-
-namespace {
 
 using namespace jbe;
 
-struct Comp {
-  int id = 0, h = 1, v = 1, tq = 0;
-  int bw = 0, bh = 0;  // the component's own block grid (non-interleaved scans)
-};
+namespace {
 
 struct Scan {
   int ns = 0;
   int ci[3] = {0, 0, 0};          // frame component index of each scan component
   int td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
   int ss = 0, se = 63, ah = 0, al = 0;
-};
-
-struct Ext {
-  jb_image_desc desc;
-  jb_geometry g;
-  int ncomp = 0;
-  bool have_sof = false, progressive = false;
-  Comp comp[3];
-  uint16_t qtabs[4][64];
-  bool qset[4] = {false, false, false, false};
-  HuffTable dc[4], ac[4];
-  int restart_interval = 0;
-  int16_t *coef = nullptr;
-  int ny = 1, bpm = 3;
-
-  // block (by, bx) of frame component c -> its place in the MCU-interleaved array
-  inline int16_t *block(int c, int by, int bx) const {
-    int64_t idx;
-    if (c == 0) {
-      const int hs = desc.hs, vs = desc.vs;
-      idx = ((int64_t)(by / vs) * g.mcus_x + bx / hs) * bpm + (by % vs) * hs + bx % hs;
-    } else {
-      idx = ((int64_t)by * g.mcus_x + bx) * bpm + ny + c - 1;
-    }
-    return coef + idx * 64;
-  }
 };
 
 inline bool fits16(int v) { return v >= -32768 && v <= 32767; }
@@ -194,7 +166,7 @@ int decode_one_scan(Ext &x, const Scan &sc, const uint8_t *b, const uint8_t *e, 
   int until_restart = x.restart_interval;
   if (sc.ns == 1) {  // non-interleaved: the component's own block raster, one block per MCU
     const int c = sc.ci[0];
-    const Comp &cp = x.comp[c];
+    const Ext::Grid &cp = x.grid[c];
     for (int by = 0; by < cp.bh; by++) {
       // out of data: stop now rather than run the rest of a huge frame on padding zeros
       if (br.overran()) return set_err(err, JB_ERR_FORMAT, "entropy-coded data ends early");
@@ -257,7 +229,7 @@ int parse_sof(Ext &x, const uint8_t *s, size_t sl, Err &e) {
   if (sl < 6 + 3u * (unsigned)x.ncomp) return set_err(e, JB_ERR_FORMAT, "bad SOF segment");
   if (x.desc.width < 1 || x.desc.height < 1) return set_err(e, JB_ERR_GEOMETRY, "empty image");
   for (int c = 0; c < x.ncomp; c++) {
-    Comp &cp = x.comp[c];
+    Header::Comp &cp = x.comp[c];
     cp.id = s[6 + 3 * c];
     cp.h = s[7 + 3 * c] >> 4;
     cp.v = s[7 + 3 * c] & 15;
@@ -286,8 +258,8 @@ int parse_sof(Ext &x, const uint8_t *s, size_t sl, Err &e) {
   for (int c = 0; c < x.ncomp; c++) {  // component size = ceil(size * h / hmax), in blocks
     const int cw = c == 0 ? W : (W + x.desc.hs - 1) / x.desc.hs;
     const int ch = c == 0 ? H : (H + x.desc.vs - 1) / x.desc.vs;
-    x.comp[c].bw = (cw + 7) / 8;
-    x.comp[c].bh = (ch + 7) / 8;
+    x.grid[c].bw = (cw + 7) / 8;
+    x.grid[c].bh = (ch + 7) / 8;
   }
   x.have_sof = true;
   return JB_OK;
@@ -334,109 +306,88 @@ int parse_sos(Ext &x, const uint8_t *s, size_t sl, Scan &sc, Err &e) {
   return JB_OK;
 }
 
-int run(const uint8_t *d, size_t n, Ext &x, size_t coef_cap_bytes, bool headers_only, Err &e) {
-  if (!d || n < 4 || d[0] != 0xff || d[1] != 0xd8) return set_err(e, JB_ERR_FORMAT, "not a JPEG file (no SOI)");
-  memset(x.qtabs, 0, sizeof x.qtabs);
-  size_t pos = 2;
+// The walk from where `w` stands.  headers_only: up to the first SOS that passes the rules, which the walk is put back
+// in front of (x.first_sos); else every scan up to EOI or the end of the bytes.
+int run(Ext &x, MarkerWalk &w, size_t coef_cap_bytes, bool headers_only, Err &e) {
   int scans = 0;
   while (true) {
-    if (pos + 1 >= n) {
-      if (scans > 0) return JB_OK;  // no EOI: everything that was coded has been decoded
-      return set_err(e, JB_ERR_FORMAT, "truncated file (no SOS)");
-    }
-    if (d[pos] != 0xff) return set_err(e, JB_ERR_FORMAT, "marker expected");
-    while (pos < n && d[pos] == 0xff) pos++;
-    if (pos >= n) return scans > 0 ? JB_OK : set_err(e, JB_ERR_FORMAT, "truncated file");
-    const uint8_t m = d[pos++];
-    if (m == 0xd8 || m == 0x01 || (m >= 0xd0 && m <= 0xd7)) continue;  // no payload
-    if (m == 0xd9) {
-      if (scans == 0) return set_err(e, JB_ERR_FORMAT, "EOI before SOS");
-      return JB_OK;
-    }
-    if (pos + 2 > n) return set_err(e, JB_ERR_FORMAT, "truncated segment");
-    const size_t len = ((size_t)d[pos] << 8) | d[pos + 1];
-    if (len < 2 || pos + len > n) return set_err(e, JB_ERR_FORMAT, "bad segment length");
-    const uint8_t *s = d + pos + 2;
-    const size_t sl = len - 2;
-    pos += len;
-    if (m == 0xdb) {  // DQT
-      size_t i = 0;
-      while (i < sl) {
-        const int pq = s[i] >> 4, tq = s[i] & 15;
-        i++;
-        if (tq > 3) return set_err(e, JB_ERR_QTAB, "quantisation table id > 3");
-        const size_t need = pq ? 128 : 64;
-        if (pq > 1 || i + need > sl) return set_err(e, JB_ERR_FORMAT, "bad DQT segment");
-        for (int k = 0; k < 64; k++)
-          x.qtabs[tq][kZigZag[k]] = pq ? (uint16_t)((s[i + 2 * k] << 8) | s[i + 2 * k + 1]) : s[i + k];
-        x.qset[tq] = true;
-        i += need;
-      }
+    const int step = w.next(scans > 0, e);  // (no EOI: everything that was coded has been decoded)
+    if (step != MarkerWalk::kSegment) return step == MarkerWalk::kEnd ? (int)JB_OK : step;
+    const uint8_t m = w.marker;
+    int rc = JB_OK;
+    if (m == 0xdb) {
+      rc = parse_dqt(x, w.s, w.sl, e);
     } else if (m == 0xc0 || m == 0xc1 || m == 0xc2) {  // baseline / extended sequential / progressive, Huffman
       x.progressive = (m == 0xc2);
-      int rc = parse_sof(x, s, sl, e);
-      if (rc) return rc;
-      if (!headers_only) {
+      rc = parse_sof(x, w.s, w.sl, e);
+      if (rc == JB_OK && x.coef) {
         if ((size_t)x.g.coef_bytes > coef_cap_bytes) return set_err(e, JB_ERR_CAPACITY, "coefficient buffer too small");
         memset(x.coef, 0, (size_t)x.g.coef_bytes);  // scans add to it; grayscale leaves Cb, Cr at zero
       }
-    } else if (m >= 0xc3 && m <= 0xcf && m != 0xc4 && m != 0xc8 && m != 0xcc) {
-      return set_err(e, JB_ERR_UNSUPPORTED, "lossless, hierarchical and arithmetic-coded frames are not supported");
-    } else if (m == 0xc4) {  // DHT
-      size_t i = 0;
-      while (i < sl) {
-        if (i + 17 > sl) return set_err(e, JB_ERR_FORMAT, "bad DHT segment");
-        const int tc = s[i] >> 4, th = s[i] & 15;
-        if (th > 3 || tc > 1) return set_err(e, JB_ERR_FORMAT, "bad Huffman table id");
-        HuffTable &t = tc ? x.ac[th] : x.dc[th];
-        int total = 0;
-        t.counts[0] = 0;
-        for (int l = 1; l <= 16; l++) {
-          t.counts[l] = s[i + l];
-          total += s[i + l];
-        }
-        i += 17;
-        if (total > 256 || i + total > sl) return set_err(e, JB_ERR_FORMAT, "bad DHT segment");
-        memcpy(t.symbols, s + i, (size_t)total);
-        i += (size_t)total;
-        if (!t.build(tc != 0)) return set_err(e, JB_ERR_FORMAT, "over-subscribed Huffman table");
-      }
-    } else if (m == 0xdd) {  // DRI
-      if (sl != 2) return set_err(e, JB_ERR_FORMAT, "bad DRI segment");
-      x.restart_interval = (s[0] << 8) | s[1];
+    } else if (other_sof(m, 0xc3)) {
+      rc = set_err(e, JB_ERR_UNSUPPORTED, "lossless, hierarchical and arithmetic-coded frames are not supported");
+    } else if (m == 0xc4) {
+      rc = parse_dht(x, w.s, w.sl, false, e);
+    } else if (m == 0xdd) {
+      rc = parse_dri(x, w.s, w.sl, e);
     } else if (m == 0xda) {  // SOS + its entropy-coded segment
       Scan sc;
-      int rc = parse_sos(x, s, sl, sc, e);
+      rc = parse_sos(x, w.s, w.sl, sc, e);
       if (rc) return rc;
       for (int c = 0; c < x.ncomp; c++)
         if (!x.qset[x.comp[c].tq]) return set_err(e, JB_ERR_QTAB, "quantisation table not found");
-      if (headers_only) return JB_OK;
-      const size_t end = segment_end(d, pos, n);
-      rc = decode_one_scan(x, sc, d + pos, d + end, e);
-      if (rc) return rc;
+      if (headers_only) {
+        x.first_sos = w.at;
+        return JB_OK;
+      }
+      const size_t end = segment_end(w.d, w.pos, w.n);
+      rc = decode_one_scan(x, sc, w.d + w.pos, w.d + end, e);
       scans++;
-      pos = end;
+      w.pos = end;
     }
     // APPn, COM, anything else with a length: ignored
+    if (rc) return rc;
   }
 }
 
 }  // namespace
 
-// Entry point for jb_frontend.cpp.  coef == nullptr: headers only (desc and the tables seen before
-// the first scan).  Returns a jb_status; *err receives the message.
+// The general rules in two steps (jb_internal.h): the header up to the first scan ...
+int jb_ext_parse_(const uint8_t *jpeg, size_t n, Ext &x, Err &e) {
+  MarkerWalk w(jpeg, n);
+  x.bytes = jpeg;
+  x.n_bytes = n;
+  const int rc = w.soi(e);
+  return rc ? rc : run(x, w, 0, true, e);
+}
+
+// ... and its scans into `coef`
+int jb_ext_scans_(Ext &x, int16_t *coef, size_t coef_cap_bytes, Err &e) {
+  if ((size_t)x.g.coef_bytes > coef_cap_bytes) return set_err(e, JB_ERR_CAPACITY, "coefficient buffer too small");
+  memset(coef, 0, (size_t)x.g.coef_bytes);
+  x.coef = coef;
+  MarkerWalk w(x.bytes, x.n_bytes);
+  w.pos = x.first_sos;
+  const int rc = run(x, w, coef_cap_bytes, false, e);
+  x.coef = nullptr;
+  return rc;
+}
+
+// Both in one walk, as jb_entropy_decode has them: coef == nullptr: headers only (desc and the tables seen before the
+// first scan).  Returns a jb_status; *err receives the message.
 int jb_ext_decode_(const uint8_t *jpeg, size_t n, jb_image_desc *desc, uint16_t *qtabs, int16_t *coef,
                    size_t coef_cap_bytes, std::string *err) {
-  Ext *x = new Ext();
+  const std::unique_ptr<Ext> x(new Ext());
   x->coef = coef;
   Err e;
-  int rc = run(jpeg, n, *x, coef_cap_bytes, coef == nullptr, e);
+  MarkerWalk w(jpeg, n);
+  int rc = w.soi(e);
+  if (rc == JB_OK) rc = run(*x, w, coef_cap_bytes, coef == nullptr, e);
   if (rc == JB_OK) {
     *desc = x->desc;
     if (qtabs) memcpy(qtabs, x->qtabs, sizeof x->qtabs);
   } else if (err) {
     *err = e.msg;
   }
-  delete x;
   return rc;
 }

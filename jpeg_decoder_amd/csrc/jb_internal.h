@@ -56,8 +56,22 @@ int jb_decode_job_(jb_ctx *ctx, const JbHuffJob *job, uint8_t *rgb, const JbOutP
 int jb_blocks_to_rgb_plan_(jb_ctx *ctx, const jb_image_desc *desc, const int16_t *coef, const uint16_t *qtabs, uint8_t *rgb,
                            const JbOutPlan &plan);
 
-// ---- jb_frontend_ext.cpp -------------------------------------------------------------------------------------------
-// general front end: progressive, grayscale, multi-scan files
+// ---- jb_frontend.cpp, jb_frontend_ext.cpp: the front end in steps, on the shared header (jb_markers.h) --------------
+namespace jbe {
+struct Header;
+struct Ext;
+struct Err;
+}  // namespace jbe
+// the baseline rules: the header and where the one scan begins (gray: one-component frames too, for the device decoder) ...
+int jb_parse_baseline_(const uint8_t *jpeg, size_t n, jbe::Header &h, bool gray, jbe::Err &e);
+// ... the scan of such a header (three components) into `coef` on n_threads host threads ...
+int jb_decode_baseline_(const jbe::Header &h, int16_t *coef, size_t coef_cap_bytes, int n_threads, jbe::Err &e);
+// ... or a device job from it (jb_huff_prepare_(bytes, ...) of jb_huff.h is the two together); *why: a refusal's text
+int jb_huff_prepare_header_(const jbe::Header &h, JbHuffJob *job, uint32_t chunk_knob, const char **why);
+// the general rules (progressive, grayscale, multi-scan files): the header up to the first scan, and the scans into `coef`
+int jb_ext_parse_(const uint8_t *jpeg, size_t n, jbe::Ext &x, jbe::Err &e);
+int jb_ext_scans_(jbe::Ext &x, int16_t *coef, size_t coef_cap_bytes, jbe::Err &e);
+// both in one walk; coef == nullptr: the header only
 int jb_ext_decode_(const uint8_t *jpeg, size_t n, jb_image_desc *desc, uint16_t *qtabs, int16_t *coef, size_t coef_cap_bytes,
                    std::string *err);
 
