@@ -589,10 +589,33 @@ int jb_blocks_to_rgb_device_view_groups(jb_ctx *ctx, const jb_device_batch *batc
  * A chain may hold ONE JB_COLOR_BLUR (each costs a tile pass), its box radius r at most JB_COLOR_BLUR_BOX_MAX (Gaussian radii
  * up to about 8.4; the published pipelines draw from [0.1, 2.0]: r <= 1), and no JB_COLOR_CONTRAST BEHIND it (the mean would
  * be that of the blurred view, which the reduction pass cannot see; a contrast in front of the blur is DINO's order).  A
- * chain is thus: pointwise operations, at most one blur, pointwise operations without a contrast. */
+ * chain is thus: pointwise operations, at most one blur, pointwise operations without a contrast.
+ *
+ * The colour operations of RandAugment / AutoAugment / TrivialAugmentWide (torchvision's PIL backend: ImageOps.posterize /
+ * invert / autocontrast / equalize, ImageEnhance.Sharpness).  Numbers 0, 7, 9 and 99 stay unassigned.
+ *   JB_COLOR_POSTERIZE bits, bits integral in 0..8: every channel v & ~((1 << (8 - bits)) - 1).
+ *   JB_COLOR_INVERT (value 0): every channel 255 - v.
+ *   JB_COLOR_AUTOCONTRAST (value 0; cutoff 0): per channel, from the histogram of the view AS IT STANDS when the op is reached,
+ *     lo / hi = the first / last non-empty bin; hi <= lo: the channel is unchanged; else in fp64, one operation per statement,
+ *     scale = 255.0 / (hi - lo), offset = -lo * scale, t = ix * scale, t = t + offset; v becomes lut[v], lut[ix] = t truncated
+ *     toward zero and clamped to 0..255.
+ *   JB_COLOR_EQUALIZE (value 0): per channel, with counts h[0..255] of the view as it stands: fewer than two non-empty bins:
+ *     unchanged; step = (N - h[last non-empty bin]) div 255, step == 0: unchanged; else n = step div 2 and for i = 0..255:
+ *     lut[i] = min(n div step, 255), n += h[i].  Integers; counts fit uint32 (w, h <= 65535), n wants 64 bits.
+ *   JB_COLOR_SHARPNESS a, finite and >= 0 (a neighbourhood operation): every channel blend(S(p), v, a), S = ImageFilter.SMOOTH:
+ *     float32, k1 = 1.0f / 13.0f, k5 = 5.0f / 13.0f, acc = 0.5f, acc += (p[y+1][x-1] k1 + p[y+1][x] k1) + p[y+1][x+1] k1, then
+ *     row y with k1, k5, k1, then row y - 1, every product and every sum rounded separately;
+ *     S = acc <= 0 ? 0 : acc >= 255 ? 255 : (int)acc.  The view's outermost rows and columns are not filtered (S = p there:
+ *     the blend leaves them alone); a view narrower or lower than 3 is unchanged.
+ * STATISTICS operations are CONTRAST, AUTOCONTRAST and EQUALIZE (each costs a reduction pass): a chain may hold
+ * JB_COLOR_STATS_MAX of them, at most one of them a CONTRAST.  NEIGHBOURHOOD operations are BLUR and SHARPNESS (each costs a
+ * tile pass): a chain may hold one in all, and no statistics operation behind it.  jb_color_lut is the one text of the two
+ * tables. */
 enum { JB_COLOR_BRIGHTNESS = 1, JB_COLOR_CONTRAST, JB_COLOR_SATURATION, JB_COLOR_HUE, JB_COLOR_GRAYSCALE, JB_COLOR_SOLARIZE };
-enum { JB_COLOR_BLUR = 16 };
+enum { JB_COLOR_POSTERIZE = 10, JB_COLOR_INVERT, JB_COLOR_AUTOCONTRAST, JB_COLOR_EQUALIZE };
+enum { JB_COLOR_BLUR = 16, JB_COLOR_SHARPNESS };
 enum { JB_COLOR_OPS_MAX = 8 };
+enum { JB_COLOR_STATS_MAX = 2 }; /* statistics operations (contrast, autocontrast, equalize) a chain may hold */
 enum { JB_COLOR_BLUR_BOX_MAX = 7 }; /* the largest box radius r the blur kernel's halo is built for */
 typedef struct jb_color_op {
   int32_t op;  /* JB_COLOR_* */
@@ -609,8 +632,17 @@ typedef struct jb_color_chain {
  * decides: *bad_index (may be NULL) is its index, -1 when no chain is to blame.  Pure host code.
  * JB_COLOR_BLUR adds, under the same rules (a chain that is wrong both ways is JB_ERR_GEOMETRY): JB_ERR_GEOMETRY for a
  * radius that is not finite or below 0; JB_ERR_UNSUPPORTED for a box radius above JB_COLOR_BLUR_BOX_MAX, for a second
- * JB_COLOR_BLUR in a chain, and for a JB_COLOR_CONTRAST behind a JB_COLOR_BLUR. */
+ * JB_COLOR_BLUR in a chain, and for a JB_COLOR_CONTRAST behind a JB_COLOR_BLUR.
+ * The RandAugment operations add, under the same rules: JB_ERR_GEOMETRY for posterize bits outside 0..8 or not integral, a
+ * value other than 0 of JB_COLOR_INVERT / _AUTOCONTRAST / _EQUALIZE, a sharpness factor that is not finite or below 0;
+ * JB_ERR_UNSUPPORTED for more than JB_COLOR_STATS_MAX statistics operations in a chain, for a second neighbourhood operation
+ * (blur or sharpness), and for a statistics operation behind a neighbourhood operation. */
 int jb_color_check(const jb_color_chain *chains, int n, int *bad_index);
+/* The table of one channel from its 256 counts: op = JB_COLOR_AUTOCONTRAST or JB_COLOR_EQUALIZE as defined above (a channel
+ * that stays unchanged gets the identity); the one text of the two tables: the host statement and the device's table kernel
+ * compile it.  JB_ERR_NULL for a null pointer, JB_ERR_GEOMETRY for another op; in a refusal nothing is written.  The counts
+ * must add up to less than 2^32 (a view has at most 65535 x 65535 pixels).  Pure host code. */
+int jb_color_lut(int op, const uint32_t counts[256], uint8_t lut[256]);
 /* Pillow's GaussianBlur radius -> the box radius and the two 8.24 fixed-point weights of one pass (above); the one text that
  * turns a radius into weights: the kernels get the three integers.  JB_ERR_NULL for a null pointer; JB_ERR_GEOMETRY for a
  * radius that is not finite or below 0; JB_ERR_UNSUPPORTED for r > JB_COLOR_BLUR_BOX_MAX; in a refusal nothing is written.
@@ -628,9 +660,12 @@ int jb_color_host(const uint8_t *in, int64_t in_row_stride, int32_t w, int32_t h
  * returns.  Launches on `stream` (NULL: the context's): jb_color_mean_kernel where a chain of the launch has a contrast
  * -- integer sums, so the result does not depend on the order of the additions -- then jb_color_apply_kernel, and where a
  * chain has a JB_COLOR_BLUR jb_color_blur_kernel for those views (a 64 x 32 tile with a halo, six passes in LDS), 32 images a
- * launch.  JB_ERR_NULL; JB_ERR_GEOMETRY for n_images < 1, w or h outside 1..65535, strides below one row / one image, a
- * bad spec, or float output that is not aligned to its element size; then jb_color_check's status with the chain's index
- * in jb_last_error.  In every refusal nothing is launched or written. */
+ * launch.  Where a chain has a JB_COLOR_AUTOCONTRAST or _EQUALIZE: jb_color_hist_kernel (integer counts) and
+ * jb_color_table_kernel in front of them, one round per statistics operation of the longest chain; where one has a
+ * JB_COLOR_SHARPNESS: jb_color_sharp_kernel for those views.
+ * JB_ERR_NULL; JB_ERR_GEOMETRY for n_images < 1, w or h outside 1..65535, strides below one row / one image, a bad spec, or
+ * float output that is not aligned to its element size; then jb_color_check's status with the chain's index in
+ * jb_last_error.  In every refusal nothing is launched or written. */
 int jb_color_device(jb_ctx *ctx, const uint8_t *d_in, int64_t in_row_stride, int64_t in_image_stride, int32_t w, int32_t h,
                     int32_t n_images, const jb_color_chain *chains, void *d_out, int64_t out_row_stride, int64_t out_image_stride,
                     const jb_output_spec *spec, void *stream);

@@ -18,9 +18,11 @@ from .api import (JbError, Context, ImageDesc, Geometry, DeviceBatch, lib, lib_p
                   Fit, FitGeometry, fit_geometry, FIT_STRETCH, FIT_PAD, FIT_COVER, FIT_CENTER, FIT_START, FIT_END,
                   DraftGeometry, draft_geometry,
                   ColorOp, ColorChain, color_check, color_host, COLOR_OPS_MAX, blur_params, COLOR_BLUR, COLOR_BLUR_BOX_MAX,
-                  COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION, COLOR_HUE, COLOR_GRAYSCALE, COLOR_SOLARIZE)
+                  COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION, COLOR_HUE, COLOR_GRAYSCALE, COLOR_SOLARIZE,
+                  COLOR_POSTERIZE, COLOR_INVERT, COLOR_AUTOCONTRAST, COLOR_EQUALIZE, COLOR_SHARPNESS, COLOR_STATS_MAX, color_lut)
 from .crops import random_resized_crop, random_views, random_multicrop
-from .color import color_jitter, random_apply, random_grayscale, random_solarize, dino_color, hue_shift, random_blur, dino_augment
+from .color import (color_jitter, random_apply, random_grayscale, random_solarize, dino_color, hue_shift, random_blur, dino_augment,
+                    posterize, invert, autocontrast, equalize, sharpness, rand_augment_color, trivial_augment_wide_color)
 
 __all__ = ["JbError", "Context", "ImageDesc", "Geometry", "DeviceBatch", "lib", "lib_path",
            "make_desc", "geometry_of", "flat_front_geometry", "resolve_qtabs", "entropy_decode", "decode_batch", "BatchDecoder", "build_library",
@@ -35,4 +37,6 @@ __all__ = ["JbError", "Context", "ImageDesc", "Geometry", "DeviceBatch", "lib", 
            "ColorOp", "ColorChain", "color_check", "color_host", "COLOR_OPS_MAX", "COLOR_BRIGHTNESS", "COLOR_CONTRAST",
            "COLOR_SATURATION", "COLOR_HUE", "COLOR_GRAYSCALE", "COLOR_SOLARIZE",
            "color_jitter", "random_apply", "random_grayscale", "random_solarize", "dino_color", "hue_shift",
-           "blur_params", "COLOR_BLUR", "COLOR_BLUR_BOX_MAX", "random_blur", "dino_augment"]
+           "blur_params", "COLOR_BLUR", "COLOR_BLUR_BOX_MAX", "random_blur", "dino_augment",
+           "COLOR_POSTERIZE", "COLOR_INVERT", "COLOR_AUTOCONTRAST", "COLOR_EQUALIZE", "COLOR_SHARPNESS", "COLOR_STATS_MAX", "color_lut",
+           "posterize", "invert", "autocontrast", "equalize", "sharpness", "rand_augment_color", "trivial_augment_wide_color"]

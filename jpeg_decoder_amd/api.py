@@ -121,7 +121,10 @@ class ViewOutput(ctypes.Structure):
 # jb_color_op.op (jpegblk.h, "colour chains")
 COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION, COLOR_HUE, COLOR_GRAYSCALE, COLOR_SOLARIZE = 1, 2, 3, 4, 5, 6
 COLOR_BLUR = 16               # (neighbourhood operations are numbered from 16); value: Pillow's GaussianBlur radius
+COLOR_POSTERIZE, COLOR_INVERT, COLOR_AUTOCONTRAST, COLOR_EQUALIZE = 10, 11, 12, 13   # RandAugment's pointwise and table operations
+COLOR_SHARPNESS = 17          # a neighbourhood operation; value: ImageEnhance.Sharpness' factor
 COLOR_OPS_MAX = 8
+COLOR_STATS_MAX = 2           # statistics operations (contrast, autocontrast, equalize) a chain may hold, one of them a contrast
 COLOR_BLUR_BOX_MAX = 7        # the largest box radius of a COLOR_BLUR (Gaussian radii up to about 8.4)
 
 
@@ -493,6 +496,24 @@ def blur_params(radius):
     return r.value, ww.value, fw.value
 
 
+def color_lut(op, counts):
+    """jb_color_lut: the 256-entry table of one channel from its 256 counts (uint32, adding up to less than 2^32), for op =
+    COLOR_AUTOCONTRAST (ImageOps.autocontrast, cutoff 0) or COLOR_EQUALIZE (ImageOps.equalize) -> a uint8 array.  The one text
+    of the two tables: the device's table kernel compiles it too.  JbError(-2) for another op, another shape, a count that is
+    negative or not integral, or counts that add up to 2^32 or more."""
+    import numpy as np
+    given = np.asarray(counts)
+    if given.shape != (256,) or given.dtype.kind not in "iuf":
+        raise JbError(-2, "color_lut wants 256 counts")
+    exact = [int(c) for c in given.tolist()] if given.dtype.kind != "f" or bool(np.all(np.isfinite(given))) else None
+    if exact is None or any(c < 0 for c in exact) or exact != given.tolist() or sum(exact) >= 1 << 32:
+        raise JbError(-2, "color_lut wants non-negative integral counts that add up to less than 2^32")
+    h = np.array(exact, dtype=np.uint32)
+    lut = np.zeros(256, np.uint8)
+    _check(lib().jb_color_lut(int(op), _ptr(h), _ptr(lut)))
+    return lut
+
+
 def color_host(image, chain):
     """jb_color_host: the chain on a host [h, w, 3] uint8 array -> a new array.  The CPU statement of the device kernels'
     arithmetic (the same csrc/jb_color_core.h), for tests and for checking a pipeline without a GPU."""
@@ -708,6 +729,7 @@ def lib():
     L.jb_color_check.argtypes = [pc, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     L.jb_color_host.argtypes = [vp, i64, i32, i32, pc, vp, i64]
     L.jb_blur_params.argtypes = [ctypes.c_float, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+    L.jb_color_lut.argtypes = [ctypes.c_int, vp, vp]
     L.jb_color_device.argtypes = [vp, vp, i64, i64, i32, i32, i32, pc, vp, i64, i64, ps, vp]
     L.jb_blocks_to_rgb_device_views_color.argtypes = [vp, ctypes.POINTER(DeviceBatch), pv, ctypes.c_int, prs, pc, ps, vp]
     L.jb_blocks_to_rgb_device_view_groups_color.argtypes = [vp, ctypes.POINTER(DeviceBatch), pv, pg, ctypes.POINTER(ViewOutput), ctypes.c_int, pc, ps, vp]
@@ -1057,9 +1079,11 @@ class Context:
         scale): the K = sum of k views of an image fall into G groups, group-major, each with its own target size and filter, all
         from ONE pixel launch per image (jb_blocks_to_rgb_device_view_groups); batch.d_rgb and its strides are not read.
         colors=[[chain, ... K], ... N] with views= (and with view_groups=): chain (i, v) -- None / [] (the identity) or [(COLOR_*,
-        value), ...], at most 8 operations, one COLOR_CONTRAST and one COLOR_BLUR with no contrast behind it -- is applied to
-        the uint8 pixels of view v of image i, mirror included, in front of the output format: Pillow's ImageEnhance /
-        convert / ImageOps.solarize / ImageFilter.GaussianBlur bit for bit
+        value), ...], at most 8 operations; at most COLOR_STATS_MAX statistics operations (COLOR_CONTRAST, COLOR_AUTOCONTRAST,
+        COLOR_EQUALIZE), one of them a contrast; one neighbourhood operation (COLOR_BLUR or COLOR_SHARPNESS) with no statistics
+        operation behind it -- is applied to the uint8 pixels of view v of image i, mirror included, in front of the output
+        format: Pillow's ImageEnhance (Brightness, Contrast, Color, Sharpness: a blend against ImageFilter.SMOOTH) / convert /
+        ImageOps.solarize / posterize / invert / autocontrast / equalize / ImageFilter.GaussianBlur bit for bit
         (jb_blocks_to_rgb_device_views_color / _view_groups_color).  Without views ValueError.
         Each is the entry point of that suffix (_ROUTES)."""
         request = _Request(scale, fmt, roi, resize, crops, filter, views, fit, view_groups, view_outputs, colors)

@@ -3,10 +3,13 @@
 Pure Python over a numpy.random.Generator, like crops.py: the chains of a batch can be drawn before anything is decoded,
 and the same generator state gives the same chains.  A chain is a list of (op, value) with op one of the COLOR_* numbers;
 [] is the identity.  The procedures are torchvision's (ColorJitter, RandomApply, RandomGrayscale, RandomSolarize) and DINO's
-own GaussianBlur class; the generator is numpy's, so the draws are not torch's.
+own GaussianBlur class; the generator is numpy's, so the draws are not torch's.  rand_augment_color and
+trivial_augment_wide_color are torchvision's RandAugment and TrivialAugmentWide restricted to their colour operations.
 """
 COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION, COLOR_HUE, COLOR_GRAYSCALE, COLOR_SOLARIZE = 1, 2, 3, 4, 5, 6
-COLOR_BLUR = 16
+COLOR_POSTERIZE, COLOR_INVERT, COLOR_AUTOCONTRAST, COLOR_EQUALIZE = 10, 11, 12, 13
+COLOR_BLUR, COLOR_SHARPNESS = 16, 17
+COLOR_OPS_MAX, COLOR_STATS_MAX = 8, 2
 
 
 def hue_shift(f):
@@ -84,3 +87,130 @@ def dino_augment(rng, global_view_index=None):
     if global_view_index == 1:
         chain += random_solarize(rng, 0.2)
     return chain
+
+
+# ---- RandAugment / TrivialAugmentWide: the colour operations ----------------------------------------------------------------
+def posterize(bits):
+    """ImageOps.posterize(im, bits), bits in 0..8 -> a one-operation chain."""
+    if int(bits) != bits or not 0 <= bits <= 8:
+        raise ValueError("bits must be an integer in 0..8")
+    return [(COLOR_POSTERIZE, float(int(bits)))]
+
+
+def invert():
+    """ImageOps.invert(im) -> a one-operation chain."""
+    return [(COLOR_INVERT, 0.0)]
+
+
+def autocontrast():
+    """ImageOps.autocontrast(im) (cutoff 0) -> a one-operation chain."""
+    return [(COLOR_AUTOCONTRAST, 0.0)]
+
+
+def equalize():
+    """ImageOps.equalize(im) -> a one-operation chain."""
+    return [(COLOR_EQUALIZE, 0.0)]
+
+
+def sharpness(a):
+    """ImageEnhance.Sharpness(im).enhance(a), a finite and >= 0 -> a one-operation chain."""
+    if not 0 <= a < float("inf"):
+        raise ValueError("the sharpness factor must be finite and not negative")
+    return [(COLOR_SHARPNESS, float(a))]
+
+
+def _linspace32(start, end, steps):
+    """torch.linspace(start, end, steps) in float32, operation for operation: start + i * step in the lower half, end -
+    (steps - 1 - i) * step in the upper"""
+    import numpy as np
+    f = np.float32
+    if steps == 1:
+        return [float(f(start))]
+    step = f(f(end) - f(start)) / f(steps - 1)
+    return [float(f(start) + f(i) * step) if i < steps // 2 else float(f(end) - f(steps - 1 - i) * step) for i in range(steps)]
+
+
+def _posterize_bits(bins, span):
+    """8 - round(arange(bins) / ((bins - 1) / span)) in float32, round half to even (torch's): span 4 or 6"""
+    import numpy as np
+    if bins == 1:
+        return [8]
+    return [8 - int(np.round(np.float32(i) / np.float32((bins - 1) / span))) for i in range(bins)]
+
+
+# the nine colour entries of torchvision's operation tables, in the tables' order
+_IDENTITY, _BRIGHTNESS, _COLOR, _CONTRAST, _SHARPNESS, _POSTERIZE, _SOLARIZE, _AUTOCONTRAST, _EQUALIZE = range(9)
+_SIGNED = {_BRIGHTNESS: COLOR_BRIGHTNESS, _COLOR: COLOR_SATURATION, _CONTRAST: COLOR_CONTRAST, _SHARPNESS: COLOR_SHARPNESS}
+_STATS = (COLOR_CONTRAST, COLOR_AUTOCONTRAST, COLOR_EQUALIZE)
+
+
+def _takes(chain, op):
+    """can `chain` take one more `op` under jb_color_check's rules?"""
+    ops = [o for o, _ in chain]
+    if len(ops) >= COLOR_OPS_MAX:
+        return False
+    if op in _STATS:
+        if op == COLOR_CONTRAST and COLOR_CONTRAST in ops:
+            return False
+        return sum(o in _STATS for o in ops) < COLOR_STATS_MAX and COLOR_SHARPNESS not in ops and COLOR_BLUR not in ops
+    if op in (COLOR_SHARPNESS, COLOR_BLUR):
+        return COLOR_SHARPNESS not in ops and COLOR_BLUR not in ops
+    return True
+
+
+def _augment_entry(index, factor_mag, bits, threshold, negative):
+    """one entry of the operation table with its magnitude -> a chain of one operation, or [] for Identity"""
+    import math
+    if index == _IDENTITY:
+        return []
+    if index in _SIGNED:
+        return [(_SIGNED[index], 1.0 - factor_mag if negative else 1.0 + factor_mag)]
+    if index == _POSTERIZE:
+        return posterize(bits)
+    if index == _SOLARIZE:
+        return [(COLOR_SOLARIZE, float(math.ceil(threshold)))]      # v < 178.5 is v < 179
+    return autocontrast() if index == _AUTOCONTRAST else equalize()
+
+
+def rand_augment_color(rng, num_ops=2, magnitude=9, num_magnitude_bins=31):
+    """torchvision's RandAugment(num_ops, magnitude, num_magnitude_bins) restricted to the nine colour entries of its operation
+    table -- Identity, Brightness, Color, Contrast, Sharpness, Posterize, Solarize, AutoContrast, Equalize -> a chain of up to
+    num_ops operations (Identity adds none).  Per operation: the entry's index (rng.integers(9)), then for Brightness / Color /
+    Contrast / Sharpness the sign (rng.integers(2), 1: negative) of the factor 1 +- linspace(0, 0.9, bins)[magnitude].
+    Posterize keeps 8 - round(arange(bins) / ((bins - 1) / 4))[magnitude] bits, Solarize's threshold is
+    ceil(linspace(255, 0, bins)[magnitude]) (what v < t means for Pillow's float threshold).
+    ONE DEPARTURE from torchvision: an operation drawn that the chain so far cannot take -- a second Contrast, a second
+    Sharpness, a Contrast / AutoContrast / Equalize behind a Sharpness, a third statistics operation -- is drawn again, index
+    and sign.  At num_ops = 2 these are 5 of the 81 ordered pairs."""
+    bins = int(num_magnitude_bins)
+    if not 0 <= magnitude < bins:
+        raise ValueError("magnitude must lie in 0..num_magnitude_bins - 1")
+    if not 0 <= num_ops <= COLOR_OPS_MAX:
+        raise ValueError("num_ops must lie in 0..8")
+    m = int(magnitude)
+    factor_mag, bits, threshold = _linspace32(0.0, 0.9, bins)[m], _posterize_bits(bins, 4)[m], _linspace32(255.0, 0.0, bins)[m]
+    chain = []
+    for _ in range(int(num_ops)):
+        while True:
+            index = int(rng.integers(9))
+            negative = bool(int(rng.integers(2))) if index in _SIGNED else False
+            entry = _augment_entry(index, factor_mag, bits, threshold, negative)
+            if not entry or _takes(chain, entry[0][0]):
+                break
+        chain += entry
+    return chain
+
+
+def trivial_augment_wide_color(rng, num_magnitude_bins=31):
+    """torchvision's TrivialAugmentWide(num_magnitude_bins) restricted to the nine colour entries of its operation table -> a
+    chain of at most one operation.  The draws: the entry's index (rng.integers(9)); for an entry with magnitudes the bin
+    (rng.integers(bins)); for Brightness / Color / Contrast / Sharpness the sign (rng.integers(2), 1: negative) of the factor
+    1 +- linspace(0, 0.99, bins)[m].  Posterize keeps 8 - round(arange(bins) / ((bins - 1) / 6))[m] bits, Solarize's threshold
+    is ceil(linspace(255, 0, bins)[m]).  A chain of one operation can always be had: nothing is drawn again."""
+    bins = int(num_magnitude_bins)
+    if bins < 1:
+        raise ValueError("num_magnitude_bins must be at least 1")
+    index = int(rng.integers(9))
+    m = int(rng.integers(bins)) if index in _SIGNED or index in (_POSTERIZE, _SOLARIZE) else 0
+    negative = bool(int(rng.integers(2))) if index in _SIGNED else False
+    return _augment_entry(index, _linspace32(0.0, 0.99, bins)[m], _posterize_bits(bins, 6)[m], _linspace32(255.0, 0.0, bins)[m], negative)

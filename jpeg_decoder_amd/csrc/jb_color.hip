@@ -13,6 +13,10 @@
 //   global access enabled) -- a ragged last group of a row falls back to bytes, nothing beyond the row is touched -- and
 //   its stores are 12 bytes interleaved, 4 bytes per plane for planar uint8, 8 for f16, 16 for f32.  The store expression
 //   of the float formats is jb_store.h's, operation for operation.
+// jb_color_hist_kernel, jb_color_table_kernel -- only for launches with a JB_COLOR_AUTOCONTRAST / _EQUALIZE: three 256-bin
+//   histograms of a view in integers, and the 3 x 256 table bytes from them; ROUNDS of statistics are described in
+//   jb_kernels.h and where the two kernels stand.
+// jb_color_sharp_kernel -- only for the views whose chain has a JB_COLOR_SHARPNESS: a 64 x 32 tile with a halo of 1.
 #include <hip/hip_runtime.h>
 
 #include "jb_color_core.h"
@@ -27,6 +31,24 @@ static_assert(sizeof(JbColor) + sizeof(JbColorTable) + sizeof(JbBlurTable) <= 40
 
 static constexpr int kColorRows = 4;  // rows (= waves) per workgroup of the apply kernel
 static constexpr int kMeanRows = 16;  // rows per workgroup of the mean kernel
+static constexpr int kHistRows = 32;  // rows per workgroup of the histogram kernel
+
+// the scratch behind p.sums (jb_kernels.h): the 768 counters and the 768 table bytes of statistics operation k of a view
+static __device__ __forceinline__ uint32_t *color_counters(const JbColor &p, uint32_t view, int k) {
+  return (uint32_t *)(p.sums + kJbCropsPerLaunch) + (view * JB_COLOR_STATS_MAX + (uint32_t)k) * 768u;
+}
+static __device__ __forceinline__ uint8_t *color_table(const JbColor &p, uint32_t view, int k) {
+  return (uint8_t *)(p.sums + kJbCropsPerLaunch) + kJbCropsPerLaunch * JB_COLOR_STATS_MAX * kJbColorCounterBytes + (view * JB_COLOR_STATS_MAX + (uint32_t)k) * 768u;
+}
+// what a view's operations read beside the pixel.  The mean is read only where the chain has a contrast; a kernel of round k
+// applies the ops in front of statistics operation k alone, so it never reads an unfinished statistic.
+static __device__ __forceinline__ JbcCtx color_ctx(const JbColor &p, const JbcShape &shape, uint32_t view) {
+  JbcCtx s;
+  s.mean = shape.contrast >= 0 ? jbc_contrast_mean(p.sums[view], (uint64_t)p.w * (uint64_t)p.h) : 0;
+  s.at1 = shape.stat1;
+  s.lut[0] = color_table(p, view, 0), s.lut[1] = color_table(p, view, 1);
+  return s;
+}
 
 typedef uint32_t jb_u32_a1 __attribute__((aligned(1)));
 typedef uint32_t jb_u32_a2 __attribute__((aligned(2)));
@@ -47,11 +69,18 @@ static __device__ __forceinline__ void color_load(const uint8_t *at, int n, int 
   }
 }
 
-__global__ __launch_bounds__(256) void jb_color_mean_kernel(const JbColor p, const JbColorTable table) {
+// round: the contrast must be statistics operation `round` of its chain (0 or 1); with round 1 the table of round 0 is applied
+// in front of it.  NEW_OPS = false compiles the operations numbered from 10 out, for a launch without any: no such operation stands in front of a chain's
+// first statistics operation, and the kernel is then the one it was before there were tables.
+template <bool NEW_OPS>
+__global__ __launch_bounds__(256) void jb_color_mean_kernel(const JbColor p, const JbColorTable table, const int round) {
   const uint32_t view = blockIdx.y;
   const JbColorRow &row = table.r[view];
-  const int at = jbc_contrast_at(row.chain);
-  if (at < 0) return;  // (the whole workgroup: the chain is the view's)
+  const JbcShape shape = jbc_shape(row.chain);
+  const int at = shape.contrast;
+  if (at < 0 || jbc_stat_at(shape, round) != at) return;  // (the whole workgroup: the chain is the view's)
+  JbcCtx ctx;
+  ctx.mean = 0, ctx.at1 = shape.stat1, ctx.lut[0] = color_table(p, view, 0), ctx.lut[1] = nullptr;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = (int)(threadIdx.x & 63);
   const int y0 = (int)blockIdx.x * kMeanRows;
@@ -67,7 +96,7 @@ __global__ __launch_bounds__(256) void jb_color_mean_kernel(const JbColor p, con
 #pragma unroll
       for (int i = 0; i < 4; i++) {
         if (i < n) {
-          jbc_apply_ops(row.chain, 0, at, 0, &px[i][0], &px[i][1], &px[i][2]);
+          jbc_apply_ops<NEW_OPS>(row.chain, 0, at, ctx, &px[i][0], &px[i][1], &px[i][2]);
           sum += (uint32_t)jbc_luma(px[i][0], px[i][1], px[i][2]);
         }
       }
@@ -79,6 +108,108 @@ __global__ __launch_bounds__(256) void jb_color_mean_kernel(const JbColor p, con
   if (lane == 0) part[wave] = sum;
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(&p.sums[view], (unsigned long long)part[0] + part[1] + part[2] + part[3]);
+}
+
+// jb_color_hist_kernel -- grid (slices of kHistRows rows, views), for the views whose statistics operation `round` is a
+// JB_COLOR_AUTOCONTRAST or _EQUALIZE.  The mean kernel's walk: a lane applies the ops in front of that operation (with the
+// results of round 0 when round is 1) to its pixels and counts them in the workgroup's three 256-bin histograms in LDS with
+// LDS integer atomics (at most 32 x 65535 pixels a workgroup: far inside 32 bits); then the workgroup adds its non-empty bins
+// to the view's 768 counters with global integer atomics.  Integer sums: the result does not depend on the order.
+__global__ __launch_bounds__(256) void jb_color_hist_kernel(const JbColor p, const JbColorTable table, const int round) {
+  const uint32_t view = blockIdx.y;
+  const JbColorRow &row = table.r[view];
+  const JbcShape shape = jbc_shape(row.chain);
+  const int at = jbc_stat_at(shape, round);
+  if (at < 0 || !jbc_is_hist(row.chain.ops[at].op)) return;  // (the whole workgroup)
+  const JbcCtx ctx = color_ctx(p, shape, view);
+  __shared__ uint32_t hist[768];
+  for (int i = (int)threadIdx.x; i < 768; i += 256) hist[i] = 0;
+  __syncthreads();
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = (int)(threadIdx.x & 63);
+  const int y0 = (int)blockIdx.x * kHistRows;
+  const int y1 = min(y0 + kHistRows, p.h);
+  const uint8_t *const src = p.src + row.src_offset;
+  for (int y = y0 + wave; y < y1; y += 4) {
+    const uint8_t *const line = src + (int64_t)y * p.src_row_stride;
+    for (int x = 4 * lane; x < p.w; x += 256) {
+      const int n = min(4, p.w - x);
+      int px[4][3];
+      color_load(line + 3 * (int64_t)x, n, px);
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        if (i < n) {
+          jbc_apply_ops<true>(row.chain, 0, at, ctx, &px[i][0], &px[i][1], &px[i][2]);
+          atomicAdd(&hist[px[i][0]], 1u), atomicAdd(&hist[256 + px[i][1]], 1u), atomicAdd(&hist[512 + px[i][2]], 1u);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  uint32_t *const counters = color_counters(p, view, round);
+  for (int i = (int)threadIdx.x; i < 768; i += 256)
+    if (hist[i]) atomicAdd(&counters[i], hist[i]);
+}
+
+// jb_color_table_kernel -- grid (views), 256 threads: thread t makes entry t of the three tables of statistics operation
+// `round` from the view's 768 counters.  Per channel: the prefix sum of the counts in front of bin t (a wave scan with
+// __shfl_up, the four waves' totals through LDS), the first and last non-empty bins from the waves' ballots; then the entry is
+// jb_color_core.h's -- jbc_equalize_entry in integers, jbc_autocontrast_entry in fp64 (built with -ffp-contract=off; the
+// fp64 division is correctly rounded).  A kernel of its own, not a prologue of the consumers: 768 entries once a view, where
+// every workgroup of the apply, blur or sharpness kernel would repeat the scan.
+__global__ __launch_bounds__(256) void jb_color_table_kernel(const JbColor p, const JbColorTable table, const int round) {
+  const uint32_t view = blockIdx.y;
+  const JbColorRow &row = table.r[view];
+  const JbcShape shape = jbc_shape(row.chain);
+  const int at = jbc_stat_at(shape, round);
+  if (at < 0 || !jbc_is_hist(row.chain.ops[at].op)) return;  // (the whole workgroup)
+  const bool equalize = row.chain.ops[at].op == JB_COLOR_EQUALIZE;
+  const int t = (int)threadIdx.x, wave = t >> 6, lane = t & 63;
+  const uint32_t *const counters = color_counters(p, view, round);
+  __shared__ uint32_t counts[768], wave_sum[3][4];
+  __shared__ unsigned long long wave_mask[3][4];
+  uint32_t before[3];
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const uint32_t n = counters[256 * c + t];
+    counts[256 * c + t] = n;
+    uint32_t incl = n;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t v = (uint32_t)__shfl_up((int)incl, d, 64);
+      if (lane >= d) incl += v;
+    }
+    const unsigned long long mask = __ballot(n != 0);
+    if (lane == 63) wave_sum[c][wave] = incl;
+    if (lane == 0) wave_mask[c][wave] = mask;
+    before[c] = incl - n;
+  }
+  __syncthreads();
+  uint8_t *const lut = color_table(p, view, round);
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    uint32_t total = 0, front = before[c];
+    int lo = -1, hi = -1;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      const unsigned long long m = wave_mask[c][w];
+      if (w < wave) front += wave_sum[c][w];
+      total += wave_sum[c][w];
+      if (m) {
+        if (lo < 0) lo = 64 * w + (__ffsll((long long)m) - 1);
+        hi = 64 * w + 63 - __clzll((long long)m);
+      }
+    }
+    if (lo < 0) lo = hi = 0;  // (a view has pixels: not reached)
+    int e;
+    if (equalize) {
+      const uint32_t step = hi > lo ? (total - counts[256 * c + hi]) / 255u : 0u;
+      e = jbc_equalize_entry(step, front, t);
+    } else {
+      e = jbc_autocontrast_entry(lo, hi, t);
+    }
+    lut[256 * c + t] = (uint8_t)e;
+  }
 }
 
 // n (1..4) pixels px of a row, behind the chain, to columns x.. of the output row at `dst` (of plane 0 when planar) in FORMAT:
@@ -143,26 +274,27 @@ static __device__ __forceinline__ void color_store(const JbColor &p, uint8_t *co
   }
 }
 
-template <int FORMAT>
+// NEW_OPS: the launch has a chain with an operation numbered 10..13; false compiles those out, for the launches of the older kinds
+template <int FORMAT, bool NEW_OPS>
 __global__ __launch_bounds__(64 * kColorRows) void jb_color_apply_kernel(const JbColor p, const JbColorTable table) {
   const uint32_t view = blockIdx.y;
   const JbColorRow &row = table.r[view];
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = (int)(threadIdx.x & 63);
-  if (jbc_blur_at(row.chain) >= 0) return;  // (the whole workgroup: the view is jb_color_blur_kernel's)
+  const JbcShape shape = jbc_shape(row.chain);
+  if (shape.nbhd >= 0) return;  // (the whole workgroup: the view is jb_color_blur_kernel's or jb_color_sharp_kernel's)
   const uint32_t tx = blockIdx.x % (uint32_t)p.tiles_x, ty = blockIdx.x / (uint32_t)p.tiles_x;
   const int y = (int)ty * kColorRows + wave;   // wave-uniform
   const int x = ((int)tx * 64 + lane) * 4;
   if (y >= p.h || x >= p.w) return;
   const int n = min(4, p.w - x);
-  int mean = 0;
-  if (jbc_contrast_at(row.chain) >= 0) mean = jbc_contrast_mean(p.sums[view], (uint64_t)p.w * (uint64_t)p.h);
+  const JbcCtx ctx = color_ctx(p, shape, view);
   int px[4][3];
   color_load(p.src + row.src_offset + (int64_t)y * p.src_row_stride + 3 * (int64_t)x, n, px);
   const int n_ops = row.chain.n_ops;
 #pragma unroll
   for (int i = 0; i < 4; i++)
-    if (i < n) jbc_apply_ops(row.chain, 0, n_ops, mean, &px[i][0], &px[i][1], &px[i][2]);
+    if (i < n) jbc_apply_ops<NEW_OPS>(row.chain, 0, n_ops, ctx, &px[i][0], &px[i][1], &px[i][2]);
 
   color_store<FORMAT>(p, p.dst + row.dst_offset + (int64_t)y * p.dst_row_stride, x, n, px);
 }
@@ -202,13 +334,14 @@ static __device__ __forceinline__ void blur_pass(const uint8_t *in, uint8_t *out
 // positions INSIDE the view are computed, because a read outside the view goes to the view's edge sample in EVERY pass
 // (jbc_blur_line's clamp) -- then applies the ops behind the blur and stores through color_store.  r, ww, fw and every
 // branch on an op are uniform over the workgroup.
-template <int FORMAT, int HALO>
+template <int FORMAT, int HALO, bool NEW_OPS>
 __global__ __launch_bounds__(256) void jb_color_blur_kernel(const JbColor p, const JbColorTable table, const JbBlurTable blur) {
   using T = BlurTile<HALO>;
   const uint32_t view = blockIdx.y;
   const JbColorRow &row = table.r[view];
-  const int at = jbc_blur_at(row.chain);
-  if (at < 0) return;  // (the whole workgroup: the view is jb_color_apply_kernel's)
+  const JbcShape shape = jbc_shape(row.chain);
+  const int at = shape.nbhd;
+  if (at < 0 || row.chain.ops[at].op != JB_COLOR_BLUR) return;  // (the whole workgroup: the view is jb_color_apply_kernel's)
   const JbBlurWeights k = blur.k[view];
   const int step = k.r + 1, halo = 3 * step;
   if (halo > HALO) return;  // (the launch picks HALO from the largest r: not reached)
@@ -217,8 +350,7 @@ __global__ __launch_bounds__(256) void jb_color_blur_kernel(const JbColor p, con
   const int x0 = (int)(blockIdx.x % tiles_x) * kBlurW, y0 = (int)(blockIdx.x / tiles_x) * kBlurH;
   // local (0, 0) of the tile's buffers is the view's (bx, by); bw x bh samples are loaded
   const int bx = x0 - halo, by = y0 - halo, bw = kBlurW + 2 * halo, bh = kBlurH + 2 * halo;
-  int mean = 0;
-  if (jbc_contrast_at(row.chain) >= 0) mean = jbc_contrast_mean(p.sums[view], (uint64_t)p.w * (uint64_t)p.h);
+  const JbcCtx ctx = color_ctx(p, shape, view);
   const uint8_t *const src = p.src + row.src_offset;
   // a thread per loaded sample position, 256 adjacent ones a round (rows of bw = 70..112 positions: whole waves stay busy,
   // which a wave per row would not: 76 = 64 + 12).  i / bw as a multiplication: exact while i * (inv * bw - 2^24) < 2^24,
@@ -230,7 +362,7 @@ __global__ __launch_bounds__(256) void jb_color_blur_kernel(const JbColor p, con
     const int gy = min(max(by + ly, 0), p.h - 1), gx = min(max(bx + lx, 0), p.w - 1);
     const uint8_t *const from = src + (int64_t)gy * p.src_row_stride + 3 * gx;
     int r = from[0], g = from[1], b = from[2];
-    jbc_apply_ops(row.chain, 0, at, mean, &r, &g, &b);
+    jbc_apply_ops<NEW_OPS>(row.chain, 0, at, ctx, &r, &g, &b);
     uint8_t *const to = &lds[0][ly * T::kPitch + lx];
     to[0] = (uint8_t)r, to[T::kPlane] = (uint8_t)g, to[2 * T::kPlane] = (uint8_t)b;
   }
@@ -261,7 +393,68 @@ __global__ __launch_bounds__(256) void jb_color_blur_kernel(const JbColor p, con
     for (int i = 0; i < 4; i++) {
 #pragma unroll
       for (int c = 0; c < 3; c++) px[i][c] = i < n ? from[c * T::kPlane + i] : 0;
-      if (i < n) jbc_apply_ops(row.chain, at + 1, n_ops, 0, &px[i][0], &px[i][1], &px[i][2]);
+      if (i < n) jbc_apply_ops<NEW_OPS>(row.chain, at + 1, n_ops, ctx, &px[i][0], &px[i][1], &px[i][2]);
+    }
+    color_store<FORMAT>(p, p.dst + row.dst_offset + (int64_t)y * p.dst_row_stride, x, n, px);
+  }
+}
+
+// jb_color_sharp_kernel -- grid (tiles of 64 x 32 pixels, views); only the views whose chain has a JB_COLOR_SHARPNESS.  A
+// kernel of its own, not a mode of the blur kernel's tile: one pass, a halo of 1, 6.9 KB of LDS.  The blur kernel's order: the
+// workgroup loads its tile and one sample around it (positions clamped to the view; a clamped sample is never read, because
+// the view's outermost rows and columns are not filtered), the ops in front of the sharpness applied to every loaded pixel;
+// then a thread per 4 pixels of a row blends each sample with its SMOOTH (jbc_smooth), applies the ops behind and stores
+// through color_store.
+static constexpr int kSharpW = kBlurW + 2, kSharpH = kBlurH + 2, kSharpPitch = (((kSharpW + 3) / 4) | 1) * 4, kSharpPlane = kSharpPitch * kSharpH;
+template <int FORMAT>
+__global__ __launch_bounds__(256) void jb_color_sharp_kernel(const JbColor p, const JbColorTable table) {
+  const uint32_t view = blockIdx.y;
+  const JbColorRow &row = table.r[view];
+  const JbcShape shape = jbc_shape(row.chain);
+  const int at = shape.nbhd;
+  if (at < 0 || row.chain.ops[at].op != JB_COLOR_SHARPNESS) return;  // (the whole workgroup: the view is another kernel's)
+  __shared__ uint8_t lds[3 * kSharpPlane];
+  const uint32_t tiles_x = (uint32_t)(p.w + kBlurW - 1) / (uint32_t)kBlurW;
+  const int x0 = (int)(blockIdx.x % tiles_x) * kBlurW, y0 = (int)(blockIdx.x / tiles_x) * kBlurH;
+  const JbcCtx ctx = color_ctx(p, shape, view);
+  const uint8_t *const src = p.src + row.src_offset;
+  // local (lx, ly) is the view's (x0 - 1 + lx, y0 - 1 + ly); i / kSharpW as a multiplication: exact for i < 66 * 34 (the blur
+  // kernel's bound)
+  constexpr uint32_t inv = ((1u << 24) + (uint32_t)kSharpW - 1u) / (uint32_t)kSharpW;
+#pragma unroll 3
+  for (int i = (int)threadIdx.x; i < kSharpW * kSharpH; i += 256) {
+    const int ly = (int)(((uint32_t)i * inv) >> 24), lx = i - ly * kSharpW;
+    const int gy = min(max(y0 - 1 + ly, 0), p.h - 1), gx = min(max(x0 - 1 + lx, 0), p.w - 1);
+    const uint8_t *const from = src + (int64_t)gy * p.src_row_stride + 3 * gx;
+    int r = from[0], g = from[1], b = from[2];
+    jbc_apply_ops<true>(row.chain, 0, at, ctx, &r, &g, &b);
+    uint8_t *const to = &lds[ly * kSharpPitch + lx];
+    to[0] = (uint8_t)r, to[kSharpPlane] = (uint8_t)g, to[2 * kSharpPlane] = (uint8_t)b;
+  }
+  __syncthreads();
+  const float factor = row.chain.ops[at].value;
+  const int n_ops = row.chain.n_ops;
+  for (int item = (int)threadIdx.x; item < (kBlurW / 4) * kBlurH; item += 256) {
+    const int ry = item / (kBlurW / 4), x = x0 + 4 * (item % (kBlurW / 4)), y = y0 + ry;
+    if (y >= p.h || x >= p.w) continue;
+    const int n = min(4, p.w - x);
+    const bool edge_row = y == 0 || y == p.h - 1;
+    int px[4][3];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const uint8_t *const q = &lds[(1 + ry) * kSharpPitch + 1 + (x - x0) + i];  // (i < 4: inside the tile's 64 columns)
+      const bool plain = edge_row || x + i == 0 || x + i >= p.w - 1;
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        const uint8_t *const s = q + c * kSharpPlane;
+        const int v = s[0];
+        int sm = v;
+        if (!plain)
+          sm = jbc_smooth(s[kSharpPitch - 1], s[kSharpPitch], s[kSharpPitch + 1], s[-1], s[0], s[1], s[-kSharpPitch - 1], s[-kSharpPitch],
+                          s[-kSharpPitch + 1]);
+        px[i][c] = jbc_blend(sm, v, factor);
+      }
+      if (i < n) jbc_apply_ops<true>(row.chain, at + 1, n_ops, ctx, &px[i][0], &px[i][1], &px[i][2]);
     }
     color_store<FORMAT>(p, p.dst + row.dst_offset + (int64_t)y * p.dst_row_stride, x, n, px);
   }
@@ -271,42 +464,82 @@ hipError_t jbk_color_launch(const JbColor &q, const JbColorTable &table, int for
   if (format < 0 || format > 3 || q.w < 1 || q.h < 1 || q.w > 65535 || q.h > 65535 || q.n_views < 1 || q.n_views > kJbCropsPerLaunch || !q.src ||
       !q.dst || !q.sums || q.src_row_stride < 3LL * q.w)
     return hipErrorInvalidValue;
-  bool contrast = false;
+  bool contrast = false, hists = false, news = false, sharp = false, mean_in[JB_COLOR_STATS_MAX] = {}, hist_in[JB_COLOR_STATS_MAX] = {};
   int blur_r = -1;  // the largest box radius of the launch's blurs
   JbBlurTable blurs = {};
   for (int i = 0; i < q.n_views; i++) {
     const JbColorRow &r = table.r[i];
     if (r.src_offset < 0 || r.dst_offset < 0 || r.chain.n_ops < 0 || r.chain.n_ops > JB_COLOR_OPS_MAX) return hipErrorInvalidValue;
-    const int c_at = jbc_contrast_at(r.chain), b_at = jbc_blur_at(r.chain);
-    if (c_at >= 0) contrast = true;
-    if (b_at >= 0) {
-      // the mean kernel applies the ops in front of the contrast: never a blur (jb_color_check refuses a contrast behind one)
+    const JbcShape shape = jbc_shape(r.chain);
+    if (jbc_has_new_ops(r.chain)) news = true;
+    // the statistics kernels apply the ops in front of their operation: never a neighbourhood operation (jb_color_check refuses
+    // a statistics operation behind one), and the scratch holds JB_COLOR_STATS_MAX statistics a view
+    if (shape.n_stats > JB_COLOR_STATS_MAX || (shape.nbhd >= 0 && shape.n_stats > 0 && jbc_stat_at(shape, shape.n_stats - 1) > shape.nbhd))
+      return hipErrorInvalidValue;
+    for (int k = 0; k < shape.n_stats; k++) {
+      if (r.chain.ops[jbc_stat_at(shape, k)].op == JB_COLOR_CONTRAST)
+        contrast = mean_in[k] = true;
+      else
+        hists = hist_in[k] = true;
+    }
+    if (shape.nbhd >= 0 && r.chain.ops[shape.nbhd].op == JB_COLOR_BLUR) {
       bool geometry;
-      if (c_at > b_at || !jbc_blur_weights(r.chain.ops[b_at].value, &blurs.k[i], &geometry)) return hipErrorInvalidValue;
+      if (!jbc_blur_weights(r.chain.ops[shape.nbhd].value, &blurs.k[i], &geometry)) return hipErrorInvalidValue;
       blur_r = blurs.k[i].r > blur_r ? blurs.k[i].r : blur_r;
+    } else if (shape.nbhd >= 0) {
+      sharp = true;
     }
   }
   JbColor p = q;
   p.tiles_x = (p.w + 255) / 256;
   const int tiles_y = (p.h + kColorRows - 1) / kColorRows;  // (at most 256 x 16,384 workgroups a view)
-  if (contrast) {
-    hipError_t e = hipMemsetAsync(p.sums, 0, sizeof(unsigned long long) * kJbCropsPerLaunch, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(jb_color_mean_kernel, dim3((unsigned)((p.h + kMeanRows - 1) / kMeanRows), (unsigned)p.n_views), dim3(256), 0, stream, p, table);
-    e = hipGetLastError();
+  if (contrast || hists) {
+    // the sums, and in a launch with a histogram operation the counters of its views behind them
+    const size_t bytes = sizeof(unsigned long long) * kJbCropsPerLaunch + (hists ? (size_t)p.n_views * JB_COLOR_STATS_MAX * kJbColorCounterBytes : 0);
+    hipError_t e = hipMemsetAsync(p.sums, 0, bytes, stream);
     if (e != hipSuccess) return e;
   }
+  for (int k = 0; k < JB_COLOR_STATS_MAX; k++) {
+    if (mean_in[k]) {
+      if (!news)  // (then k is 0: a second statistics operation would be a table operation)
+        hipLaunchKernelGGL(jb_color_mean_kernel<false>, dim3((unsigned)((p.h + kMeanRows - 1) / kMeanRows), (unsigned)p.n_views), dim3(256), 0, stream, p, table, k);
+      else
+        hipLaunchKernelGGL(jb_color_mean_kernel<true>, dim3((unsigned)((p.h + kMeanRows - 1) / kMeanRows), (unsigned)p.n_views), dim3(256), 0, stream, p, table, k);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return e;
+    }
+    if (hist_in[k]) {
+      hipLaunchKernelGGL(jb_color_hist_kernel, dim3((unsigned)((p.h + kHistRows - 1) / kHistRows), (unsigned)p.n_views), dim3(256), 0, stream, p, table, k);
+      hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(jb_color_table_kernel, dim3(1, (unsigned)p.n_views), dim3(256), 0, stream, p, table, k);
+      e = hipGetLastError();
+      if (e != hipSuccess) return e;
+    }
+  }
   const dim3 grid((unsigned)(p.tiles_x * tiles_y), (unsigned)p.n_views), block(64 * kColorRows);
-  jb_by_format(format, [&](auto F) { hipLaunchKernelGGL(jb_color_apply_kernel<decltype(F)::value>, grid, block, 0, stream, p, table); });
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || blur_r < 0) return e;
-  // the tile kernel, with the small halo (r <= 1: every published pipeline; 20 KB of LDS) or the one for r <= 7 (56 KB)
-  const dim3 blur_grid((unsigned)(((p.w + kBlurW - 1) / kBlurW) * ((p.h + kBlurH - 1) / kBlurH)), (unsigned)p.n_views);
   jb_by_format(format, [&](auto F) {
-    if (blur_r <= 1)
-      hipLaunchKernelGGL((jb_color_blur_kernel<decltype(F)::value, 6>), blur_grid, dim3(256), 0, stream, p, table, blurs);
+    if (news)
+      hipLaunchKernelGGL((jb_color_apply_kernel<decltype(F)::value, true>), grid, block, 0, stream, p, table);
     else
-      hipLaunchKernelGGL((jb_color_blur_kernel<decltype(F)::value, 3 * (JB_COLOR_BLUR_BOX_MAX + 1)>), blur_grid, dim3(256), 0, stream, p, table, blurs);
+      hipLaunchKernelGGL((jb_color_apply_kernel<decltype(F)::value, false>), grid, block, 0, stream, p, table);
   });
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || (blur_r < 0 && !sharp)) return e;
+  // the tile kernels, the blur's with the small halo (r <= 1: every published pipeline; 20 KB of LDS) or the one for r <= 7 (56 KB)
+  const dim3 blur_grid((unsigned)(((p.w + kBlurW - 1) / kBlurW) * ((p.h + kBlurH - 1) / kBlurH)), (unsigned)p.n_views);
+  if (blur_r >= 0)
+    jb_by_format(format, [&](auto F) {
+      constexpr int kLarge = 3 * (JB_COLOR_BLUR_BOX_MAX + 1);
+      if (blur_r <= 1 && !news)
+        hipLaunchKernelGGL((jb_color_blur_kernel<decltype(F)::value, 6, false>), blur_grid, dim3(256), 0, stream, p, table, blurs);
+      else if (blur_r <= 1)
+        hipLaunchKernelGGL((jb_color_blur_kernel<decltype(F)::value, 6, true>), blur_grid, dim3(256), 0, stream, p, table, blurs);
+      else if (!news)
+        hipLaunchKernelGGL((jb_color_blur_kernel<decltype(F)::value, kLarge, false>), blur_grid, dim3(256), 0, stream, p, table, blurs);
+      else
+        hipLaunchKernelGGL((jb_color_blur_kernel<decltype(F)::value, kLarge, true>), blur_grid, dim3(256), 0, stream, p, table, blurs);
+    });
+  if (sharp) jb_by_format(format, [&](auto F) { hipLaunchKernelGGL(jb_color_sharp_kernel<decltype(F)::value>, blur_grid, dim3(256), 0, stream, p, table); });
   return hipGetLastError();
 }

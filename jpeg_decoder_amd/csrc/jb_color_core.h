@@ -3,6 +3,8 @@
 // the host.  It is Pillow's, operation for operation -- ImageEnhance.Brightness / Contrast / Color are Image.blend against
 // a degenerate image, the hue shift is convert("HSV") and back, grayscale is convert("L"), solarize is ImageOps.solarize.
 // JB_COLOR_BLUR is ImageFilter.GaussianBlur: BoxBlur.c's weights and its one pass along a line, at the end of this file.
+// Posterize / invert / autocontrast / equalize are ImageOps', JB_COLOR_SHARPNESS is ImageEnhance.Sharpness: a blend against
+// ImageFilter.SMOOTH.
 //
 // Every float step is written as ONE operation per statement and the file is built with -ffp-contract=off and without
 // fast-math: a product and the sum behind it stay two roundings, and f32 / f64 divisions are correctly rounded.
@@ -105,15 +107,115 @@ JBC_FN void jbc_hsv_to_rgb(int h, int s, int v, int *pr, int *pg, int *pb) {
   }
 }
 
-// one operation on one pixel; mean: the view's jbc_contrast_mean (JB_COLOR_CONTRAST alone reads it).  op is uniform over
-// a view -- on the device over a wave -- so the switch does not diverge.
-JBC_FN void jbc_apply_op(int op, float value, int mean, int *r, int *g, int *b) {
+// ---- statistics operations: JB_COLOR_CONTRAST (one number, the mean), JB_COLOR_AUTOCONTRAST and JB_COLOR_EQUALIZE (a table of
+// 256 bytes per channel from the channel's histogram) ----
+JBC_FN bool jbc_is_hist(int op) { return op == JB_COLOR_AUTOCONTRAST || op == JB_COLOR_EQUALIZE; }
+JBC_FN bool jbc_is_stat(int op) { return op == JB_COLOR_CONTRAST || jbc_is_hist(op); }
+JBC_FN bool jbc_is_nbhd(int op) { return op == JB_COLOR_BLUR || op == JB_COLOR_SHARPNESS; }
+
+// where a chain's statistics operations stand (in order; jb_color_check allows JB_COLOR_STATS_MAX, one of them a contrast) and
+// where its neighbourhood operation stands (one, no statistics operation behind it); -1: none
+// Two plain members, not an array: an index that is not a constant (a kernel's `round`) would make the compiler keep every
+// thread's JbcShape in LDS.
+struct JbcShape {
+  int stat0, stat1;  // the first and the second statistics operation (JB_COLOR_STATS_MAX = 2)
+  int n_stats, contrast, nbhd;
+};
+static_assert(JB_COLOR_STATS_MAX == 2, "JbcShape names its statistics operations");
+// the index of statistics operation k (0, 1) of the chain
+JBC_FN int jbc_stat_at(const JbcShape &s, int k) { return k == 0 ? s.stat0 : s.stat1; }
+JBC_FN JbcShape jbc_shape(const jb_color_chain &c) {
+  JbcShape s;
+  s.stat0 = s.stat1 = -1, s.n_stats = 0, s.contrast = -1, s.nbhd = -1;
+  for (int i = 0; i < c.n_ops && i < JB_COLOR_OPS_MAX; i++) {
+    const int op = c.ops[i].op;
+    if (jbc_is_stat(op)) {
+      if (s.n_stats == 0) s.stat0 = i;
+      if (s.n_stats == 1) s.stat1 = i;
+      s.n_stats++;
+      if (op == JB_COLOR_CONTRAST && s.contrast < 0) s.contrast = i;
+    } else if (jbc_is_nbhd(op) && s.nbhd < 0) {
+      s.nbhd = i;
+    }
+  }
+  return s;
+}
+
+// What the operations of a chain read beside the pixel: the contrast's mean, and the tables (3 x 256 bytes, R then G then B) of
+// the chain's histogram operations -- lut[0] is the table of the FIRST statistics operation (when it has one), lut[1] of the
+// second, which stands at index at1 (-1: the chain has no second one).  Only finished statistics are read: whoever applies
+// ops [first, last) has the results of every statistics operation in that range.
+struct JbcCtx {
+  int mean, at1;
+  const uint8_t *lut[JB_COLOR_STATS_MAX];
+};
+
+// ImageOps.autocontrast (cutoff 0): entry ix of a channel whose first / last non-empty bins are lo / hi.  fp64, one operation
+// per statement; Python's int() truncates toward zero, then the clamp.
+JBC_FN int jbc_autocontrast_entry(int lo, int hi, int ix) {
+  if (hi <= lo) return ix;
+  const double scale = 255.0 / (double)(hi - lo);
+  const double offset = (double)(-lo) * scale;
+  double t = (double)ix * scale;
+  t = t + offset;
+  return t <= 0.0 ? 0 : t >= 255.0 ? 255 : (int)t;
+}
+// ImageOps.equalize: entry i of a channel; before = h[0] + .. + h[i - 1], step = (N - h[last non-empty bin]) div 255, or 0 for
+// a channel with fewer than two non-empty bins.  step / 2 + before can pass 2^32: 64-bit.  The min is Pillow's.
+JBC_FN int jbc_equalize_entry(uint32_t step, uint32_t before, int i) {
+  if (step == 0) return i;
+  const uint64_t q = ((uint64_t)(step >> 1) + (uint64_t)before) / (uint64_t)step;
+  return q > 255 ? 255 : (int)q;
+}
+// the table of one channel from its 256 counts, one entry after the other (the host; the device's table kernel finds lo, hi
+// and the prefix sums in parallel and calls the two functions above)
+JBC_FN void jbc_lut_from_counts(int op, const uint32_t *h, uint8_t *lut) {
+  int lo = 256, hi = -1;
+  uint64_t n = 0;
+  for (int i = 0; i < 256; i++) {
+    if (h[i]) lo = lo == 256 ? i : lo, hi = i;
+    n += h[i];
+  }
+  if (hi < 0) lo = hi = 0;
+  const uint32_t step = hi > lo ? (uint32_t)((n - h[hi]) / 255u) : 0u;
+  uint32_t before = 0;
+  for (int i = 0; i < 256; i++) {
+    lut[i] = (uint8_t)(op == JB_COLOR_EQUALIZE ? jbc_equalize_entry(step, before, i) : jbc_autocontrast_entry(lo, hi, i));
+    before += h[i];
+  }
+}
+
+// ImageFilter.SMOOTH (Filter.c's 3 x 3, kernel (1 1 1, 1 5 1, 1 1 1) / 13) of one sample: a = the three samples of the row
+// below, b = of the sample's own row, c = of the row above.  float32; every product and every sum rounded separately.
+JBC_FN float jbc_smooth_row(int p0, int p1, int p2, float k0, float k1, float k2) {
+  const float m0 = (float)p0 * k0;
+  const float m1 = (float)p1 * k1;
+  const float m2 = (float)p2 * k2;
+  const float s = m0 + m1;
+  return s + m2;
+}
+JBC_FN int jbc_smooth(int a0, int a1, int a2, int b0, int b1, int b2, int c0, int c1, int c2) {
+  const float k1 = 1.0f / 13.0f, k5 = 5.0f / 13.0f;
+  float acc = 0.5f;
+  acc = acc + jbc_smooth_row(a0, a1, a2, k1, k1, k1);
+  acc = acc + jbc_smooth_row(b0, b1, b2, k1, k5, k1);
+  acc = acc + jbc_smooth_row(c0, c1, c2, k1, k1, k1);
+  return acc <= 0.0f ? 0 : acc >= 255.0f ? 255 : (int)acc;
+}
+
+// operation i of a chain on one pixel; s: the chain's context (JB_COLOR_CONTRAST reads the mean, the two table operations
+// their table).  op is uniform over a view -- on the device over a wave -- so the switch does not diverge.
+// NEW_OPS = false compiles the operations numbered from 10 out (their case labels fall into the default): the switch is then
+// the one over the six operations that it was before there were more, with no memory access in it.  The kernels run such
+// instantiations for the launches whose chains hold none of those operations.
+template <bool NEW_OPS>
+JBC_FN void jbc_apply_op(int op, float value, const JbcCtx &s, int i, int *r, int *g, int *b) {
   switch (op) {
     case JB_COLOR_BRIGHTNESS:
       *r = jbc_blend(0, *r, value), *g = jbc_blend(0, *g, value), *b = jbc_blend(0, *b, value);
       break;
     case JB_COLOR_CONTRAST:
-      *r = jbc_blend(mean, *r, value), *g = jbc_blend(mean, *g, value), *b = jbc_blend(mean, *b, value);
+      *r = jbc_blend(s.mean, *r, value), *g = jbc_blend(s.mean, *g, value), *b = jbc_blend(s.mean, *b, value);
       break;
     case JB_COLOR_SATURATION: {
       const int l = jbc_luma(*r, *g, *b);
@@ -121,10 +223,10 @@ JBC_FN void jbc_apply_op(int op, float value, int mean, int *r, int *g, int *b) 
       break;
     }
     case JB_COLOR_HUE: {
-      int h, s, v;
-      jbc_rgb_to_hsv(*r, *g, *b, &h, &s, &v);
+      int h, sat, v;
+      jbc_rgb_to_hsv(*r, *g, *b, &h, &sat, &v);
       h = (h + (int)value) & 255;
-      jbc_hsv_to_rgb(h, s, v, r, g, b);
+      jbc_hsv_to_rgb(h, sat, v, r, g, b);
       break;
     }
     case JB_COLOR_GRAYSCALE:
@@ -135,27 +237,36 @@ JBC_FN void jbc_apply_op(int op, float value, int mean, int *r, int *g, int *b) 
       *r = *r < t ? *r : 255 - *r, *g = *g < t ? *g : 255 - *g, *b = *b < t ? *b : 255 - *b;
       break;
     }
+    case JB_COLOR_POSTERIZE:
+      if constexpr (NEW_OPS) {
+        const int keep = ~((1 << (8 - (int)value)) - 1);
+        *r &= keep, *g &= keep, *b &= keep;
+      }
+      break;
+    case JB_COLOR_INVERT:
+      if constexpr (NEW_OPS) *r = 255 - *r, *g = 255 - *g, *b = 255 - *b;
+      break;
+    case JB_COLOR_AUTOCONTRAST:
+    case JB_COLOR_EQUALIZE:
+      if constexpr (NEW_OPS) {
+        const uint8_t *const t = i == s.at1 ? s.lut[1] : s.lut[0];
+        *r = t[*r], *g = t[256 + *g], *b = t[512 + *b];
+      }
+      break;
     default: break;
   }
 }
 
 // ops [first, last) of a chain on one pixel
-JBC_FN void jbc_apply_ops(const jb_color_chain &c, int first, int last, int mean, int *r, int *g, int *b) {
-  for (int i = first; i < last; i++) jbc_apply_op(c.ops[i].op, c.ops[i].value, mean, r, g, b);
+template <bool NEW_OPS>
+JBC_FN void jbc_apply_ops(const jb_color_chain &c, int first, int last, const JbcCtx &s, int *r, int *g, int *b) {
+  for (int i = first; i < last; i++) jbc_apply_op<NEW_OPS>(c.ops[i].op, c.ops[i].value, s, i, r, g, b);
 }
-
-// the index of the chain's JB_COLOR_CONTRAST (jb_color_check allows one); -1: none
-JBC_FN int jbc_contrast_at(const jb_color_chain &c) {
+// does the chain hold a pointwise or table operation numbered from 10?
+JBC_FN bool jbc_has_new_ops(const jb_color_chain &c) {
   for (int i = 0; i < c.n_ops && i < JB_COLOR_OPS_MAX; i++)
-    if (c.ops[i].op == JB_COLOR_CONTRAST) return i;
-  return -1;
-}
-
-// the index of the chain's JB_COLOR_BLUR (jb_color_check allows one, and no contrast behind it); -1: none
-JBC_FN int jbc_blur_at(const jb_color_chain &c) {
-  for (int i = 0; i < c.n_ops && i < JB_COLOR_OPS_MAX; i++)
-    if (c.ops[i].op == JB_COLOR_BLUR) return i;
-  return -1;
+    if (c.ops[i].op >= JB_COLOR_POSTERIZE && c.ops[i].op <= JB_COLOR_EQUALIZE) return true;
+  return false;
 }
 
 // ---- JB_COLOR_BLUR: Pillow's ImageFilter.GaussianBlur, three extended box blur passes along the rows, then three along

@@ -233,7 +233,8 @@ struct JbColor {
   const uint8_t *src;
   uint8_t *dst;
   int64_t src_row_stride, dst_row_stride, dst_plane_stride;
-  unsigned long long *sums;  // device, kJbCropsPerLaunch words, the launch's alone until it has run: the views' luma sums
+  unsigned long long *sums;  // device, kJbColorScratchBytes, the launch's alone until it has run: the views' luma sums
+                             // (kJbCropsPerLaunch words), then counters and tables (below)
   int32_t w, h;              // each in 1..65535
   int32_t n_views;
   int32_t tiles_x;  // (set by the launch: workgroups per 4 rows)
@@ -247,6 +248,19 @@ struct JbColor {
 // three integers on the host (jbc_blur_weights): 12 bytes a view beside the table, 3.3 KB of arguments in all.  A launch
 // without a blur issues what it issued before there was one.  An argument outside its range, a blur in front of a contrast
 // or a box radius above JB_COLOR_BLUR_BOX_MAX: hipErrorInvalidValue.
+//
+// Statistics that are not one number (JB_COLOR_AUTOCONTRAST, JB_COLOR_EQUALIZE): the scratch behind `sums` holds, for every
+// view of a launch and each of its JB_COLOR_STATS_MAX statistics operations, 768 uint32 counters (R, G, B histograms) and,
+// behind all counters, 768 table bytes: 256 + 32 * 2 * (3072 + 768) = 246,016 bytes.  ROUND k (0, 1) computes the k-th
+// statistics operation of every view that has one, with the results of round 0 applied in front of round 1's: the mean kernel
+// for a contrast, jb_color_hist_kernel (a workgroup per 32 rows of a view: LDS integer atomics, then one global integer
+// atomic per non-empty bin) and jb_color_table_kernel (a workgroup of 256 threads per view: counters -> table) for the two
+// table operations.  A round's kernels are launched only when a view of the launch needs them, and the counters are zeroed
+// (with the sums, one memset) only in a launch with a table operation.  Where a chain has a JB_COLOR_SHARPNESS,
+// jb_color_sharp_kernel (a 64 x 32 tile, halo 1) writes those views; the apply kernel skips them as it skips blur views.  A
+// launch whose chains have none of these issues what it issued before: memset, mean, apply, blur.
+constexpr int64_t kJbColorCounterBytes = 768 * 4, kJbColorTableBytes = 768;
+constexpr int64_t kJbColorScratchBytes = 8 * kJbCropsPerLaunch + kJbCropsPerLaunch * JB_COLOR_STATS_MAX * (kJbColorCounterBytes + kJbColorTableBytes);
 hipError_t jbk_color_launch(const JbColor &p, const JbColorTable &table, int format, hipStream_t stream);
 
 // "Fit" (jb_fit.hip jb_fit_fill_kernel): the border of n_images letterboxed outputs of ow x oh at dst, addressed as

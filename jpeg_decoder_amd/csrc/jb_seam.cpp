@@ -309,13 +309,15 @@ jb_roi stored_rect(const jb_device_batch *b, int orientation, const jb_roi &r) {
 // (and orient) launches of a sub-batch, tail(i0, m, table, src) makes the launches that read it: images i0 .. i0 + m - 1,
 // image i0 + j's shown[] rectangle as tight rows of table.c[j].w x .h at src + table.c[j].tmp_offset.
 // "Colour chains": stage_per_image > 0 asks for one more region of the same scratch -- that many bytes for every image of a
-// sub-batch, counted towards the cap when images are packed, and the 32 sum words of a colour launch in front of it --
+// sub-batch, counted towards the cap when images are packed, and the scratch of a colour launch (its 32 sum words, and the
+// counters and tables of its histogram operations: kJbColorScratchBytes, about 240 KB) in front of it --
 // which the tail gets as `stage`; 0: the scratch and the packing are what they are without the parameter.
 struct ColorStage {
   uint8_t *bytes = nullptr;            // m * stage_per_image bytes (and the slack of the scratch behind them)
-  unsigned long long *sums = nullptr;  // kJbCropsPerLaunch words
+  unsigned long long *sums = nullptr;  // kJbColorScratchBytes: kJbCropsPerLaunch words, then the counters and the tables
 };
-constexpr int64_t kColorSumsBytes = 256;  // kJbCropsPerLaunch 64-bit words
+constexpr int64_t kColorSumsBytes = kJbColorScratchBytes;
+static_assert(kColorSumsBytes % 256 == 0, "the staged outputs behind the colour scratch stay aligned");
 template <class Tail>
 int rects_into_scratch(jb_ctx *ctx, const jb_device_batch *b, void *stream, int orient, const jb_roi *shown, const jb_geometry &g,
                        int64_t stage_per_image, Tail tail) {
