@@ -610,10 +610,44 @@ int jb_blocks_to_rgb_device_view_groups(jb_ctx *ctx, const jb_device_batch *batc
  * STATISTICS operations are CONTRAST, AUTOCONTRAST and EQUALIZE (each costs a reduction pass): a chain may hold
  * JB_COLOR_STATS_MAX of them, at most one of them a CONTRAST.  NEIGHBOURHOOD operations are BLUR and SHARPNESS (each costs a
  * tile pass): a chain may hold one in all, and no statistics operation behind it.  jb_color_lut is the one text of the two
- * tables. */
+ * tables.
+ *
+ * GEOMETRIC operations are numbered from 32: the five affine entries of RandAugment / TrivialAugmentWide / AutoAugment at
+ * torchvision's default interpolation (NEAREST) and fill (None: black), with Pillow's bits.  Numbers 0, 7, 9, 14, 15, 18 and
+ * 99 stay unassigned.  The value is the float32 torchvision passes: a shear (the tangent), a translation in pixels
+ * (integral), a rotation in degrees.  The result has the view's size w x h.  jb_warp_params is the one text of what follows.
+ *   1. The inverse matrix a[0..5] in doubles, one operation per statement, nothing contracted.  torchvision's
+ *      _get_inverse_affine_matrix(center (cx, cy), angle 0, translate (tx, ty), scale 1, shear (sx, sy) in radians), rot = 0:
+ *        A = cos(rot - sy) / cos(sy);  B = -cos(rot - sy) * tan(sx) / cos(sy) - sin(rot);
+ *        C = sin(rot - sy) / cos(sy);  D = -sin(rot - sy) * tan(sx) / cos(sy) + cos(rot);
+ *        m = [D, -B, 0, -C, A, 0];  m[2] += m[0] * (-cx - tx) + m[1] * (-cy - ty);  m[5] += m[3] * (-cx - tx) + m[4] * (-cy - ty);
+ *        m[2] += cx;  m[5] += cy.
+ *      JB_COLOR_SHEAR_X v: sx = radians(degrees(atan((double)v))), sy = 0, centre and translate (0, 0); degrees(x) =
+ *        x * (180.0 / pi), radians(x) = x * (pi / 180.0).  JB_COLOR_SHEAR_Y v: sx and sy exchanged.
+ *      JB_COLOR_TRANSLATE_X t, t integral with |t| <= 65535: centre (w * 0.5, h * 0.5), translate (t, 0), no shear: exactly
+ *        [1, 0, -t, 0, 1, 0].  JB_COLOR_TRANSLATE_Y t: translate (0, t).
+ *      JB_COLOR_ROTATE deg: Pillow's Image.rotate(deg, NEAREST): g = -radians(deg mod 360.0) (Python's %: the divisor's sign),
+ *        m = [round15(cos g), round15(sin g), 0, round15(-sin g), round15(cos g), 0], round15 = Python's round(x, 15);
+ *        c = (w / 2.0, h / 2.0);  m[2] = m[0] * -c.x + m[1] * -c.y + 0, m[5] likewise;  m[2] += c.x, m[5] += c.y.
+ *   2. Pillow's two nearest-neighbour paths (Geometry.c).  JB_WARP_SHIFT, when a[1] == 0 and a[3] == 0: only a[0] == 1,
+ *      a[4] == 1 and integral a[2], a[5] are accepted (the translations, a zero shear, a rotation by a multiple of 360):
+ *      xin = x + (int)a[2], yin = y + (int)a[5]; every other such matrix -- a rotation by 180 is one -- is Pillow's scaling
+ *      path with a running double sum: JB_ERR_UNSUPPORTED.  JB_WARP_FIXED for everything else: FIX(v) = FLOOR(v * 65536.0 + 0.5),
+ *      FLOOR(v) = v < 0 ? (int)floor(v) : (int)v;  A0 = FIX(a[0]), A1 = FIX(a[1]), A3 = FIX(a[3]), A4 = FIX(a[4]),
+ *      A2 = FIX(a[2] + a[0] * 0.5 + a[1] * 0.5), A5 = FIX(a[5] + a[3] * 0.5 + a[4] * 0.5);  in int32, shifts arithmetic:
+ *      xin = (A2 + y * A1 + x * A0) >> 16, yin = (A5 + y * A4 + x * A3) >> 16.  The path is taken only when at the corners
+ *      (0, 0), (w, 0), (0, h), (w, h) |x * a[0] + y * a[1] + a[2]| < 32768.0 and the same for the second row; otherwise Pillow
+ *      goes to a float path: JB_ERR_UNSUPPORTED.
+ *   3. out[y][x] = 0 <= xin < w && 0 <= yin < h ? u[yin][xin] : (0, 0, 0), u the view AS IT STANDS when the op is reached.
+ * A chain may hold JB_COLOR_WARPS_MAX geometric operations, none of them BEHIND a neighbourhood operation (the filter would be
+ * wanted at a gathered position); in front of one, and in front of, behind or between statistics operations they are allowed:
+ * the statistics are those of the view as it stands, behind a warp of the warped view with its black pixels. */
 enum { JB_COLOR_BRIGHTNESS = 1, JB_COLOR_CONTRAST, JB_COLOR_SATURATION, JB_COLOR_HUE, JB_COLOR_GRAYSCALE, JB_COLOR_SOLARIZE };
 enum { JB_COLOR_POSTERIZE = 10, JB_COLOR_INVERT, JB_COLOR_AUTOCONTRAST, JB_COLOR_EQUALIZE };
 enum { JB_COLOR_BLUR = 16, JB_COLOR_SHARPNESS };
+enum { JB_COLOR_SHEAR_X = 32, JB_COLOR_SHEAR_Y, JB_COLOR_TRANSLATE_X, JB_COLOR_TRANSLATE_Y, JB_COLOR_ROTATE };
+enum { JB_COLOR_WARPS_MAX = 2 }; /* geometric operations a chain may hold */
+enum { JB_WARP_SHIFT = 0, JB_WARP_FIXED = 1 };
 enum { JB_COLOR_OPS_MAX = 8 };
 enum { JB_COLOR_STATS_MAX = 2 }; /* statistics operations (contrast, autocontrast, equalize) a chain may hold */
 enum { JB_COLOR_BLUR_BOX_MAX = 7 }; /* the largest box radius r the blur kernel's halo is built for */
@@ -636,8 +670,21 @@ typedef struct jb_color_chain {
  * The RandAugment operations add, under the same rules: JB_ERR_GEOMETRY for posterize bits outside 0..8 or not integral, a
  * value other than 0 of JB_COLOR_INVERT / _AUTOCONTRAST / _EQUALIZE, a sharpness factor that is not finite or below 0;
  * JB_ERR_UNSUPPORTED for more than JB_COLOR_STATS_MAX statistics operations in a chain, for a second neighbourhood operation
- * (blur or sharpness), and for a statistics operation behind a neighbourhood operation. */
+ * (blur or sharpness), and for a statistics operation behind a neighbourhood operation.
+ * The geometric operations add, under the same rules: JB_ERR_GEOMETRY for a value that is not finite and for a translation that
+ * is not integral or whose absolute value is above 65535; JB_ERR_UNSUPPORTED for more than JB_COLOR_WARPS_MAX geometric
+ * operations in a chain and for a geometric operation behind a neighbourhood operation.  jb_color_check does not know the
+ * view's size: the two refusals of jb_warp_params that depend on it (a matrix of Pillow's scaling path, one of its float
+ * path) come from the entry points, which know w x h (the target size), behind jb_color_check's status, JB_ERR_UNSUPPORTED
+ * with the chain's flat index in jb_last_error; in every refusal nothing is launched or written. */
 int jb_color_check(const jb_color_chain *chains, int n, int *bad_index);
+/* A geometric operation on a view of w x h -> Pillow's path (*mode: JB_WARP_SHIFT or JB_WARP_FIXED) and its six integers:
+ * for JB_WARP_SHIFT coef[2] and coef[5] are (int)a[2] and (int)a[5] and the others 0, for JB_WARP_FIXED coef[0..5] are A0..A5
+ * (above).  The one text of the coefficients: the host statement and every launch use it, the kernels get the integers and never
+ * see a double.  JB_ERR_NULL for a null pointer; JB_ERR_GEOMETRY for an op that is not geometric, for w or h outside 1..65535
+ * and for a value that jb_color_check refuses; JB_ERR_UNSUPPORTED for a matrix of Pillow's scaling path (a rotation by 180
+ * degrees) or of its float path; in a refusal nothing is written.  Pure host code. */
+int jb_warp_params(int op, float value, int32_t w, int32_t h, int32_t *mode, int32_t coef[6]);
 /* The table of one channel from its 256 counts: op = JB_COLOR_AUTOCONTRAST or JB_COLOR_EQUALIZE as defined above (a channel
  * that stays unchanged gets the identity); the one text of the two tables: the host statement and the device's table kernel
  * compile it.  JB_ERR_NULL for a null pointer, JB_ERR_GEOMETRY for another op; in a refusal nothing is written.  The counts
@@ -662,10 +709,14 @@ int jb_color_host(const uint8_t *in, int64_t in_row_stride, int32_t w, int32_t h
  * chain has a JB_COLOR_BLUR jb_color_blur_kernel for those views (a 64 x 32 tile with a halo, six passes in LDS), 32 images a
  * launch.  Where a chain has a JB_COLOR_AUTOCONTRAST or _EQUALIZE: jb_color_hist_kernel (integer counts) and
  * jb_color_table_kernel in front of them, one round per statistics operation of the longest chain; where one has a
- * JB_COLOR_SHARPNESS: jb_color_sharp_kernel for those views.
+ * JB_COLOR_SHARPNESS: jb_color_sharp_kernel for those views.  Where a chain of a launch has a geometric operation:
+ * jb_color_warp_table_kernel in front (the operations' integers into the stream's scratch), and the launch's kernels are
+ * their instantiations whose every pixel load is a gather through the geometric operations in front of the operation
+ * concerned; a launch without one runs the kernels without that text.
  * JB_ERR_NULL; JB_ERR_GEOMETRY for n_images < 1, w or h outside 1..65535, strides below one row / one image, a bad spec, or
  * float output that is not aligned to its element size; then jb_color_check's status with the chain's index in
- * jb_last_error.  In every refusal nothing is launched or written. */
+ * jb_last_error; then JB_ERR_UNSUPPORTED for a geometric operation that jb_warp_params refuses on w x h, with the chain's
+ * index.  In every refusal nothing is launched or written. */
 int jb_color_device(jb_ctx *ctx, const uint8_t *d_in, int64_t in_row_stride, int64_t in_image_stride, int32_t w, int32_t h,
                     int32_t n_images, const jb_color_chain *chains, void *d_out, int64_t out_row_stride, int64_t out_image_stride,
                     const jb_output_spec *spec, void *stream);
@@ -673,7 +724,8 @@ int jb_color_device(jb_ctx *ctx, const uint8_t *d_in, int64_t in_row_stride, int
  * DEFINITION: output (i, v) is format(chain[i * K + v](u)), u being what the sibling writes for the same call in
  * JB_FMT_RGB_U8_HWC, mirror included, bit for bit -- under either arithmetic, any orientation, any draft and any filter.
  * colors == NULL is exactly the sibling.  The sibling's refusals come first and are unchanged; then jb_color_check's status
- * with the chain's flat index in jb_last_error; in every refusal nothing is launched or written.
+ * with the chain's flat index in jb_last_error, then JB_ERR_UNSUPPORTED for a geometric operation that jb_warp_params refuses
+ * on its view's target size (with view groups: its group's), with the same index; in every refusal nothing is launched or written.
  * The resample and filter kernels then write interleaved uint8 into a staging region of the stream's scratch -- counted
  * towards JPEGBLK_RESIZE_TMP_BYTES when images are packed into sub-batches -- and the two colour kernels read it. */
 int jb_blocks_to_rgb_device_views_color(jb_ctx *ctx, const jb_device_batch *batch, const jb_view *views, int views_per_image,

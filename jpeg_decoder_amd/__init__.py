@@ -19,10 +19,13 @@ from .api import (JbError, Context, ImageDesc, Geometry, DeviceBatch, lib, lib_p
                   DraftGeometry, draft_geometry,
                   ColorOp, ColorChain, color_check, color_host, COLOR_OPS_MAX, blur_params, COLOR_BLUR, COLOR_BLUR_BOX_MAX,
                   COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION, COLOR_HUE, COLOR_GRAYSCALE, COLOR_SOLARIZE,
-                  COLOR_POSTERIZE, COLOR_INVERT, COLOR_AUTOCONTRAST, COLOR_EQUALIZE, COLOR_SHARPNESS, COLOR_STATS_MAX, color_lut)
+                  COLOR_POSTERIZE, COLOR_INVERT, COLOR_AUTOCONTRAST, COLOR_EQUALIZE, COLOR_SHARPNESS, COLOR_STATS_MAX, color_lut,
+                  COLOR_SHEAR_X, COLOR_SHEAR_Y, COLOR_TRANSLATE_X, COLOR_TRANSLATE_Y, COLOR_ROTATE, COLOR_WARPS_MAX, WARP_SHIFT, WARP_FIXED,
+                  warp_params)
 from .crops import random_resized_crop, random_views, random_multicrop
 from .color import (color_jitter, random_apply, random_grayscale, random_solarize, dino_color, hue_shift, random_blur, dino_augment,
-                    posterize, invert, autocontrast, equalize, sharpness, rand_augment_color, trivial_augment_wide_color)
+                    posterize, invert, autocontrast, equalize, sharpness, rand_augment_color, trivial_augment_wide_color,
+                    shear_x, shear_y, translate_x, translate_y, rotate, rand_augment, trivial_augment_wide)
 
 __all__ = ["JbError", "Context", "ImageDesc", "Geometry", "DeviceBatch", "lib", "lib_path",
            "make_desc", "geometry_of", "flat_front_geometry", "resolve_qtabs", "entropy_decode", "decode_batch", "BatchDecoder", "build_library",
@@ -39,4 +42,6 @@ __all__ = ["JbError", "Context", "ImageDesc", "Geometry", "DeviceBatch", "lib", 
            "color_jitter", "random_apply", "random_grayscale", "random_solarize", "dino_color", "hue_shift",
            "blur_params", "COLOR_BLUR", "COLOR_BLUR_BOX_MAX", "random_blur", "dino_augment",
            "COLOR_POSTERIZE", "COLOR_INVERT", "COLOR_AUTOCONTRAST", "COLOR_EQUALIZE", "COLOR_SHARPNESS", "COLOR_STATS_MAX", "color_lut",
-           "posterize", "invert", "autocontrast", "equalize", "sharpness", "rand_augment_color", "trivial_augment_wide_color"]
+           "posterize", "invert", "autocontrast", "equalize", "sharpness", "rand_augment_color", "trivial_augment_wide_color",
+           "COLOR_SHEAR_X", "COLOR_SHEAR_Y", "COLOR_TRANSLATE_X", "COLOR_TRANSLATE_Y", "COLOR_ROTATE", "COLOR_WARPS_MAX", "WARP_SHIFT",
+           "WARP_FIXED", "warp_params", "shear_x", "shear_y", "translate_x", "translate_y", "rotate", "rand_augment", "trivial_augment_wide"]

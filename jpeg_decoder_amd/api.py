@@ -123,6 +123,11 @@ COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION, COLOR_HUE, COLOR_GRAYSCALE, 
 COLOR_BLUR = 16               # (neighbourhood operations are numbered from 16); value: Pillow's GaussianBlur radius
 COLOR_POSTERIZE, COLOR_INVERT, COLOR_AUTOCONTRAST, COLOR_EQUALIZE = 10, 11, 12, 13   # RandAugment's pointwise and table operations
 COLOR_SHARPNESS = 17          # a neighbourhood operation; value: ImageEnhance.Sharpness' factor
+# geometric operations (numbered from 32): torchvision's affine entries at NEAREST with a black fill, Pillow's bits; value: the
+# shear (a tangent), the translation in pixels (integral), the rotation in degrees
+COLOR_SHEAR_X, COLOR_SHEAR_Y, COLOR_TRANSLATE_X, COLOR_TRANSLATE_Y, COLOR_ROTATE = 32, 33, 34, 35, 36
+COLOR_WARPS_MAX = 2           # geometric operations a chain may hold, none of them behind a COLOR_BLUR / COLOR_SHARPNESS
+WARP_SHIFT, WARP_FIXED = 0, 1  # warp_params' modes: Pillow's integer shift, its 16.16 fixed-point path
 COLOR_OPS_MAX = 8
 COLOR_STATS_MAX = 2           # statistics operations (contrast, autocontrast, equalize) a chain may hold, one of them a contrast
 COLOR_BLUR_BOX_MAX = 7        # the largest box radius of a COLOR_BLUR (Gaussian radii up to about 8.4)
@@ -496,6 +501,17 @@ def blur_params(radius):
     return r.value, ww.value, fw.value
 
 
+def warp_params(op, value, w, h):
+    """jb_warp_params: a geometric operation (COLOR_SHEAR_X .. COLOR_ROTATE) on a view of w x h -> (mode, [c0 .. c5]): Pillow's
+    path (WARP_SHIFT: xin = x + c2, yin = y + c5; WARP_FIXED: xin = (c2 + y c1 + x c0) >> 16, yin = (c5 + y c4 + x c3) >> 16 in
+    int32) and its six integers.  JbError(-2) for another op, a size outside 1..65535, a value that is not finite, a translation
+    that is not integral or beyond +-65535; JbError(-9) for a matrix of Pillow's scaling path (a rotation by 180 degrees) or of
+    its float path."""
+    mode, coef = ctypes.c_int32(), (ctypes.c_int32 * 6)()
+    _check(lib().jb_warp_params(int(op), float(value), int(w), int(h), ctypes.byref(mode), coef))
+    return mode.value, list(coef)
+
+
 def color_lut(op, counts):
     """jb_color_lut: the 256-entry table of one channel from its 256 counts (uint32, adding up to less than 2^32), for op =
     COLOR_AUTOCONTRAST (ImageOps.autocontrast, cutoff 0) or COLOR_EQUALIZE (ImageOps.equalize) -> a uint8 array.  The one text
@@ -730,6 +746,7 @@ def lib():
     L.jb_color_host.argtypes = [vp, i64, i32, i32, pc, vp, i64]
     L.jb_blur_params.argtypes = [ctypes.c_float, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
     L.jb_color_lut.argtypes = [ctypes.c_int, vp, vp]
+    L.jb_warp_params.argtypes = [ctypes.c_int, ctypes.c_float, i32, i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     L.jb_color_device.argtypes = [vp, vp, i64, i64, i32, i32, i32, pc, vp, i64, i64, ps, vp]
     L.jb_blocks_to_rgb_device_views_color.argtypes = [vp, ctypes.POINTER(DeviceBatch), pv, ctypes.c_int, prs, pc, ps, vp]
     L.jb_blocks_to_rgb_device_view_groups_color.argtypes = [vp, ctypes.POINTER(DeviceBatch), pv, pg, ctypes.POINTER(ViewOutput), ctypes.c_int, pc, ps, vp]

@@ -142,7 +142,23 @@ struct PerFile {
     if (!colors) return JB_OK;
     if ((int64_t)n_paths * k > 0x7fffffffLL) return fail(JB_ERR_CAPACITY, "too many chains");
     const int rc = jb_color_check(colors, n_paths * k, nullptr);
-    return rc == JB_OK ? JB_OK : fail(rc, std::string(jb_last_error(nullptr)));
+    if (rc != JB_OK) return fail(rc, std::string(jb_last_error(nullptr)));
+    // the refusals of the geometric operations that depend on the views' size: view v of a file has its group's target, or the decoder's
+    for (int i = 0; i < n_paths; i++) {
+      int v0 = 0;
+      for (int g = 0; g < (n_groups > 0 ? n_groups : 1); g++) {
+        const int n = n_groups > 0 ? groups[g].n_views : k;
+        const int32_t w = n_groups > 0 ? groups[g].rs.out_w : out.target.w, h = n_groups > 0 ? groups[g].rs.out_h : out.target.h;
+        int64_t bad = 0;
+        const char *why = nullptr;
+        // (a target outside 1..65535 is every file's own refusal, by its plan)
+        const bool sized = w >= 1 && h >= 1 && w <= 65535 && h <= 65535;
+        const int rs = sized ? jb_color_check_size_(colors + (size_t)i * (size_t)k + v0, n, w, h, &bad, &why) : JB_OK;
+        if (rs != JB_OK) return fail(rs, "colour chain " + std::to_string((int64_t)i * k + v0 + bad) + ": " + why);
+        v0 += n;
+      }
+    }
+    return JB_OK;
   }
 };
 

@@ -17,6 +17,9 @@
 //   histograms of a view in integers, and the 3 x 256 table bytes from them; ROUNDS of statistics are described in
 //   jb_kernels.h and where the two kernels stand.
 // jb_color_sharp_kernel -- only for the views whose chain has a JB_COLOR_SHARPNESS: a 64 x 32 tile with a halo of 1.
+// Geometric operations (JB_COLOR_SHEAR_X .. JB_COLOR_ROTATE): a launch with one runs the WARP instantiations of the kernels
+// above, whose every pixel load is jbc_gather (jb_color_core.h), behind jb_color_warp_table_kernel, which puts the operations'
+// integers into the scratch (jb_kernels.h); a launch without one runs the kernels with that text compiled out.
 #include <hip/hip_runtime.h>
 
 #include "jb_color_core.h"
@@ -28,6 +31,15 @@ struct JbBlurTable {
   JbBlurWeights k[kJbCropsPerLaunch];
 };
 static_assert(sizeof(JbColor) + sizeof(JbColorTable) + sizeof(JbBlurTable) <= 4096, "the colour kernels' arguments must fit the 4 KB segment");
+
+// the coefficients of the launch's geometric operations: the arguments of jb_color_warp_table_kernel alone, which copies them
+// into the scratch (jb_kernels.h says why they do not travel with the other kernels' arguments)
+struct JbWarpTable {
+  JbWarp k[kJbCropsPerLaunch][JB_COLOR_WARPS_MAX];
+};
+static_assert(sizeof(JbWarp) == 32 && sizeof(JbWarpTable) == kJbColorWarpBytes, "the warp table is the scratch's");
+static_assert(sizeof(JbColor) + sizeof(JbWarpTable) <= 4096, "the warp table kernel's arguments must fit the 4 KB segment");
+static_assert(kJbColorWarpOffset % 16 == 0, "the warp table in the scratch is aligned");
 
 static constexpr int kColorRows = 4;  // rows (= waves) per workgroup of the apply kernel
 static constexpr int kMeanRows = 16;  // rows per workgroup of the mean kernel
@@ -48,6 +60,19 @@ static __device__ __forceinline__ JbcCtx color_ctx(const JbColor &p, const JbcSh
   s.at1 = shape.stat1;
   s.lut[0] = color_table(p, view, 0), s.lut[1] = color_table(p, view, 1);
   return s;
+}
+
+// the two JbWarp of a view in the scratch (written by jb_color_warp_table_kernel in front of the launch's other kernels)
+static __device__ __forceinline__ const JbWarp *color_warps(const JbColor &p, uint32_t view) {
+  return (const JbWarp *)((const uint8_t *)p.sums + kJbColorWarpOffset) + view * JB_COLOR_WARPS_MAX;
+}
+// grid (1), 256 threads: the table's 512 words into the scratch, two a thread
+__global__ __launch_bounds__(256) void jb_color_warp_table_kernel(const JbColor p, const JbWarpTable t) {
+  static_assert(sizeof(JbWarpTable) == 2 * 256 * 4, "two words a thread");
+  uint32_t *const to = (uint32_t *)((uint8_t *)p.sums + kJbColorWarpOffset);
+  const uint32_t *const from = (const uint32_t *)&t;
+  to[threadIdx.x] = from[threadIdx.x];
+  to[256 + threadIdx.x] = from[256 + threadIdx.x];
 }
 
 typedef uint32_t jb_u32_a1 __attribute__((aligned(1)));
@@ -72,7 +97,9 @@ static __device__ __forceinline__ void color_load(const uint8_t *at, int n, int 
 // round: the contrast must be statistics operation `round` of its chain (0 or 1); with round 1 the table of round 0 is applied
 // in front of it.  NEW_OPS = false compiles the operations numbered from 10 out, for a launch without any: no such operation stands in front of a chain's
 // first statistics operation, and the kernel is then the one it was before there were tables.
-template <bool NEW_OPS>
+// WARP: the launch has a chain with a geometric operation: every pixel is jbc_gather's (the view as it stands in front of the
+// contrast, through the geometric operations in front of it); false compiles that out.
+template <bool NEW_OPS, bool WARP = false>
 __global__ __launch_bounds__(256) void jb_color_mean_kernel(const JbColor p, const JbColorTable table, const int round) {
   const uint32_t view = blockIdx.y;
   const JbColorRow &row = table.r[view];
@@ -92,6 +119,16 @@ __global__ __launch_bounds__(256) void jb_color_mean_kernel(const JbColor p, con
     for (int x = 4 * lane; x < p.w; x += 256) {
       const int n = min(4, p.w - x);
       int px[4][3];
+      if constexpr (WARP) {
+        const JbcWarpShape ws = jbc_warp_shape(row.chain);
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          if (i < n) {
+            jbc_gather<NEW_OPS>(row.chain, ws, at, ctx, color_warps(p, view), src, p.src_row_stride, p.w, p.h, x + i, y, &px[i][0], &px[i][1], &px[i][2]);
+            sum += (uint32_t)jbc_luma(px[i][0], px[i][1], px[i][2]);
+          }
+        continue;
+      }
       color_load(line + 3 * (int64_t)x, n, px);
 #pragma unroll
       for (int i = 0; i < 4; i++) {
@@ -115,6 +152,7 @@ __global__ __launch_bounds__(256) void jb_color_mean_kernel(const JbColor p, con
 // results of round 0 when round is 1) to its pixels and counts them in the workgroup's three 256-bin histograms in LDS with
 // LDS integer atomics (at most 32 x 65535 pixels a workgroup: far inside 32 bits); then the workgroup adds its non-empty bins
 // to the view's 768 counters with global integer atomics.  Integer sums: the result does not depend on the order.
+template <bool WARP>
 __global__ __launch_bounds__(256) void jb_color_hist_kernel(const JbColor p, const JbColorTable table, const int round) {
   const uint32_t view = blockIdx.y;
   const JbColorRow &row = table.r[view];
@@ -135,6 +173,16 @@ __global__ __launch_bounds__(256) void jb_color_hist_kernel(const JbColor p, con
     for (int x = 4 * lane; x < p.w; x += 256) {
       const int n = min(4, p.w - x);
       int px[4][3];
+      if constexpr (WARP) {
+        const JbcWarpShape ws = jbc_warp_shape(row.chain);
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          if (i < n) {
+            jbc_gather<true>(row.chain, ws, at, ctx, color_warps(p, view), src, p.src_row_stride, p.w, p.h, x + i, y, &px[i][0], &px[i][1], &px[i][2]);
+            atomicAdd(&hist[px[i][0]], 1u), atomicAdd(&hist[256 + px[i][1]], 1u), atomicAdd(&hist[512 + px[i][2]], 1u);
+          }
+        continue;
+      }
       color_load(line + 3 * (int64_t)x, n, px);
 #pragma unroll
       for (int i = 0; i < 4; i++) {
@@ -275,7 +323,9 @@ static __device__ __forceinline__ void color_store(const JbColor &p, uint8_t *co
 }
 
 // NEW_OPS: the launch has a chain with an operation numbered 10..13; false compiles those out, for the launches of the older kinds
-template <int FORMAT, bool NEW_OPS>
+// WARP: the launch has a chain with a geometric operation: a lane's pixels are jbc_gather's, three byte loads each at their own
+// positions; false compiles that out
+template <int FORMAT, bool NEW_OPS, bool WARP = false>
 __global__ __launch_bounds__(64 * kColorRows) void jb_color_apply_kernel(const JbColor p, const JbColorTable table) {
   const uint32_t view = blockIdx.y;
   const JbColorRow &row = table.r[view];
@@ -290,11 +340,22 @@ __global__ __launch_bounds__(64 * kColorRows) void jb_color_apply_kernel(const J
   const int n = min(4, p.w - x);
   const JbcCtx ctx = color_ctx(p, shape, view);
   int px[4][3];
-  color_load(p.src + row.src_offset + (int64_t)y * p.src_row_stride + 3 * (int64_t)x, n, px);
   const int n_ops = row.chain.n_ops;
+  if constexpr (WARP) {
+    const JbcWarpShape ws = jbc_warp_shape(row.chain);
 #pragma unroll
-  for (int i = 0; i < 4; i++)
-    if (i < n) jbc_apply_ops<NEW_OPS>(row.chain, 0, n_ops, ctx, &px[i][0], &px[i][1], &px[i][2]);
+    for (int i = 0; i < 4; i++) {
+      px[i][0] = px[i][1] = px[i][2] = 0;
+      if (i < n)
+        jbc_gather<NEW_OPS>(row.chain, ws, n_ops, ctx, color_warps(p, view), p.src + row.src_offset, p.src_row_stride, p.w, p.h, x + i, y, &px[i][0],
+                            &px[i][1], &px[i][2]);
+    }
+  } else {
+    color_load(p.src + row.src_offset + (int64_t)y * p.src_row_stride + 3 * (int64_t)x, n, px);
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+      if (i < n) jbc_apply_ops<NEW_OPS>(row.chain, 0, n_ops, ctx, &px[i][0], &px[i][1], &px[i][2]);
+  }
 
   color_store<FORMAT>(p, p.dst + row.dst_offset + (int64_t)y * p.dst_row_stride, x, n, px);
 }
@@ -334,7 +395,8 @@ static __device__ __forceinline__ void blur_pass(const uint8_t *in, uint8_t *out
 // positions INSIDE the view are computed, because a read outside the view goes to the view's edge sample in EVERY pass
 // (jbc_blur_line's clamp) -- then applies the ops behind the blur and stores through color_store.  r, ww, fw and every
 // branch on an op are uniform over the workgroup.
-template <int FORMAT, int HALO, bool NEW_OPS>
+// WARP: the launch has a chain with a geometric operation: every loaded sample is jbc_gather's at its clamped position
+template <int FORMAT, int HALO, bool NEW_OPS, bool WARP = false>
 __global__ __launch_bounds__(256) void jb_color_blur_kernel(const JbColor p, const JbColorTable table, const JbBlurTable blur) {
   using T = BlurTile<HALO>;
   const uint32_t view = blockIdx.y;
@@ -360,9 +422,14 @@ __global__ __launch_bounds__(256) void jb_color_blur_kernel(const JbColor p, con
   for (int i = (int)threadIdx.x; i < bw * bh; i += 256) {
     const int ly = (int)(((uint32_t)i * inv) >> 24), lx = i - ly * bw;
     const int gy = min(max(by + ly, 0), p.h - 1), gx = min(max(bx + lx, 0), p.w - 1);
-    const uint8_t *const from = src + (int64_t)gy * p.src_row_stride + 3 * gx;
-    int r = from[0], g = from[1], b = from[2];
-    jbc_apply_ops<NEW_OPS>(row.chain, 0, at, ctx, &r, &g, &b);
+    int r, g, b;
+    if constexpr (WARP) {
+      jbc_gather<NEW_OPS>(row.chain, jbc_warp_shape(row.chain), at, ctx, color_warps(p, view), src, p.src_row_stride, p.w, p.h, gx, gy, &r, &g, &b);
+    } else {
+      const uint8_t *const from = src + (int64_t)gy * p.src_row_stride + 3 * gx;
+      r = from[0], g = from[1], b = from[2];
+      jbc_apply_ops<NEW_OPS>(row.chain, 0, at, ctx, &r, &g, &b);
+    }
     uint8_t *const to = &lds[0][ly * T::kPitch + lx];
     to[0] = (uint8_t)r, to[T::kPlane] = (uint8_t)g, to[2 * T::kPlane] = (uint8_t)b;
   }
@@ -406,7 +473,7 @@ __global__ __launch_bounds__(256) void jb_color_blur_kernel(const JbColor p, con
 // then a thread per 4 pixels of a row blends each sample with its SMOOTH (jbc_smooth), applies the ops behind and stores
 // through color_store.
 static constexpr int kSharpW = kBlurW + 2, kSharpH = kBlurH + 2, kSharpPitch = (((kSharpW + 3) / 4) | 1) * 4, kSharpPlane = kSharpPitch * kSharpH;
-template <int FORMAT>
+template <int FORMAT, bool WARP = false>
 __global__ __launch_bounds__(256) void jb_color_sharp_kernel(const JbColor p, const JbColorTable table) {
   const uint32_t view = blockIdx.y;
   const JbColorRow &row = table.r[view];
@@ -425,9 +492,14 @@ __global__ __launch_bounds__(256) void jb_color_sharp_kernel(const JbColor p, co
   for (int i = (int)threadIdx.x; i < kSharpW * kSharpH; i += 256) {
     const int ly = (int)(((uint32_t)i * inv) >> 24), lx = i - ly * kSharpW;
     const int gy = min(max(y0 - 1 + ly, 0), p.h - 1), gx = min(max(x0 - 1 + lx, 0), p.w - 1);
-    const uint8_t *const from = src + (int64_t)gy * p.src_row_stride + 3 * gx;
-    int r = from[0], g = from[1], b = from[2];
-    jbc_apply_ops<true>(row.chain, 0, at, ctx, &r, &g, &b);
+    int r, g, b;
+    if constexpr (WARP) {
+      jbc_gather<true>(row.chain, jbc_warp_shape(row.chain), at, ctx, color_warps(p, view), src, p.src_row_stride, p.w, p.h, gx, gy, &r, &g, &b);
+    } else {
+      const uint8_t *const from = src + (int64_t)gy * p.src_row_stride + 3 * gx;
+      r = from[0], g = from[1], b = from[2];
+      jbc_apply_ops<true>(row.chain, 0, at, ctx, &r, &g, &b);
+    }
     uint8_t *const to = &lds[ly * kSharpPitch + lx];
     to[0] = (uint8_t)r, to[kSharpPlane] = (uint8_t)g, to[2 * kSharpPlane] = (uint8_t)b;
   }
@@ -467,11 +539,24 @@ hipError_t jbk_color_launch(const JbColor &q, const JbColorTable &table, int for
   bool contrast = false, hists = false, news = false, sharp = false, mean_in[JB_COLOR_STATS_MAX] = {}, hist_in[JB_COLOR_STATS_MAX] = {};
   int blur_r = -1;  // the largest box radius of the launch's blurs
   JbBlurTable blurs = {};
+  bool warp = false;  // a chain of the launch has a geometric operation: the WARP instantiations, behind the table's kernel
+  JbWarpTable warps = {};
   for (int i = 0; i < q.n_views; i++) {
     const JbColorRow &r = table.r[i];
     if (r.src_offset < 0 || r.dst_offset < 0 || r.chain.n_ops < 0 || r.chain.n_ops > JB_COLOR_OPS_MAX) return hipErrorInvalidValue;
     const JbcShape shape = jbc_shape(r.chain);
     if (jbc_has_new_ops(r.chain)) news = true;
+    const JbcWarpShape ws = jbc_warp_shape(r.chain);
+    for (int k = 0; k < JB_COLOR_WARPS_MAX; k++) {
+      const int at = k == 0 ? ws.warp0 : ws.warp1;
+      if (at < 0) continue;
+      const char *why;
+      // (the caller has checked the chains against the views' size; a geometric operation behind the neighbourhood operation
+      // would not be gathered by the tile kernels)
+      if (jbc_warp_params(r.chain.ops[at].op, r.chain.ops[at].value, q.w, q.h, &warps.k[i][k], &why) != JB_OK || (shape.nbhd >= 0 && at > shape.nbhd))
+        return hipErrorInvalidValue;
+      warp = true;
+    }
     // the statistics kernels apply the ops in front of their operation: never a neighbourhood operation (jb_color_check refuses
     // a statistics operation behind one), and the scratch holds JB_COLOR_STATS_MAX statistics a view
     if (shape.n_stats > JB_COLOR_STATS_MAX || (shape.nbhd >= 0 && shape.n_stats > 0 && jbc_stat_at(shape, shape.n_stats - 1) > shape.nbhd))
@@ -490,6 +575,7 @@ hipError_t jbk_color_launch(const JbColor &q, const JbColorTable &table, int for
       sharp = true;
     }
   }
+  if (warp) news = true;  // (the WARP instantiations are built with every operation)
   JbColor p = q;
   p.tiles_x = (p.w + 255) / 256;
   const int tiles_y = (p.h + kColorRows - 1) / kColorRows;  // (at most 256 x 16,384 workgroups a view)
@@ -499,9 +585,17 @@ hipError_t jbk_color_launch(const JbColor &q, const JbColorTable &table, int for
     hipError_t e = hipMemsetAsync(p.sums, 0, bytes, stream);
     if (e != hipSuccess) return e;
   }
+  if (warp) {
+    hipLaunchKernelGGL(jb_color_warp_table_kernel, dim3(1), dim3(256), 0, stream, p, warps);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
   for (int k = 0; k < JB_COLOR_STATS_MAX; k++) {
     if (mean_in[k]) {
-      if (!news)  // (then k is 0: a second statistics operation would be a table operation)
+      const dim3 mean_grid((unsigned)((p.h + kMeanRows - 1) / kMeanRows), (unsigned)p.n_views);
+      if (warp)
+        hipLaunchKernelGGL((jb_color_mean_kernel<true, true>), mean_grid, dim3(256), 0, stream, p, table, k);
+      else if (!news)  // (then k is 0: a second statistics operation would be a table operation)
         hipLaunchKernelGGL(jb_color_mean_kernel<false>, dim3((unsigned)((p.h + kMeanRows - 1) / kMeanRows), (unsigned)p.n_views), dim3(256), 0, stream, p, table, k);
       else
         hipLaunchKernelGGL(jb_color_mean_kernel<true>, dim3((unsigned)((p.h + kMeanRows - 1) / kMeanRows), (unsigned)p.n_views), dim3(256), 0, stream, p, table, k);
@@ -509,7 +603,11 @@ hipError_t jbk_color_launch(const JbColor &q, const JbColorTable &table, int for
       if (e != hipSuccess) return e;
     }
     if (hist_in[k]) {
-      hipLaunchKernelGGL(jb_color_hist_kernel, dim3((unsigned)((p.h + kHistRows - 1) / kHistRows), (unsigned)p.n_views), dim3(256), 0, stream, p, table, k);
+      const dim3 hist_grid((unsigned)((p.h + kHistRows - 1) / kHistRows), (unsigned)p.n_views);
+      if (warp)
+        hipLaunchKernelGGL(jb_color_hist_kernel<true>, hist_grid, dim3(256), 0, stream, p, table, k);
+      else
+        hipLaunchKernelGGL(jb_color_hist_kernel<false>, hist_grid, dim3(256), 0, stream, p, table, k);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return e;
       hipLaunchKernelGGL(jb_color_table_kernel, dim3(1, (unsigned)p.n_views), dim3(256), 0, stream, p, table, k);
@@ -519,7 +617,9 @@ hipError_t jbk_color_launch(const JbColor &q, const JbColorTable &table, int for
   }
   const dim3 grid((unsigned)(p.tiles_x * tiles_y), (unsigned)p.n_views), block(64 * kColorRows);
   jb_by_format(format, [&](auto F) {
-    if (news)
+    if (warp)
+      hipLaunchKernelGGL((jb_color_apply_kernel<decltype(F)::value, true, true>), grid, block, 0, stream, p, table);
+    else if (news)
       hipLaunchKernelGGL((jb_color_apply_kernel<decltype(F)::value, true>), grid, block, 0, stream, p, table);
     else
       hipLaunchKernelGGL((jb_color_apply_kernel<decltype(F)::value, false>), grid, block, 0, stream, p, table);
@@ -531,7 +631,11 @@ hipError_t jbk_color_launch(const JbColor &q, const JbColorTable &table, int for
   if (blur_r >= 0)
     jb_by_format(format, [&](auto F) {
       constexpr int kLarge = 3 * (JB_COLOR_BLUR_BOX_MAX + 1);
-      if (blur_r <= 1 && !news)
+      if (warp && blur_r <= 1)
+        hipLaunchKernelGGL((jb_color_blur_kernel<decltype(F)::value, 6, true, true>), blur_grid, dim3(256), 0, stream, p, table, blurs);
+      else if (warp)
+        hipLaunchKernelGGL((jb_color_blur_kernel<decltype(F)::value, kLarge, true, true>), blur_grid, dim3(256), 0, stream, p, table, blurs);
+      else if (blur_r <= 1 && !news)
         hipLaunchKernelGGL((jb_color_blur_kernel<decltype(F)::value, 6, false>), blur_grid, dim3(256), 0, stream, p, table, blurs);
       else if (blur_r <= 1)
         hipLaunchKernelGGL((jb_color_blur_kernel<decltype(F)::value, 6, true>), blur_grid, dim3(256), 0, stream, p, table, blurs);
@@ -540,6 +644,12 @@ hipError_t jbk_color_launch(const JbColor &q, const JbColorTable &table, int for
       else
         hipLaunchKernelGGL((jb_color_blur_kernel<decltype(F)::value, kLarge, true>), blur_grid, dim3(256), 0, stream, p, table, blurs);
     });
-  if (sharp) jb_by_format(format, [&](auto F) { hipLaunchKernelGGL(jb_color_sharp_kernel<decltype(F)::value>, blur_grid, dim3(256), 0, stream, p, table); });
+  if (sharp)
+    jb_by_format(format, [&](auto F) {
+      if (warp)
+        hipLaunchKernelGGL((jb_color_sharp_kernel<decltype(F)::value, true>), blur_grid, dim3(256), 0, stream, p, table);
+      else
+        hipLaunchKernelGGL((jb_color_sharp_kernel<decltype(F)::value, false>), blur_grid, dim3(256), 0, stream, p, table);
+    });
   return hipGetLastError();
 }

@@ -11,6 +11,8 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/jpegblk.h"
 
@@ -267,6 +269,199 @@ JBC_FN bool jbc_has_new_ops(const jb_color_chain &c) {
   for (int i = 0; i < c.n_ops && i < JB_COLOR_OPS_MAX; i++)
     if (c.ops[i].op >= JB_COLOR_POSTERIZE && c.ops[i].op <= JB_COLOR_EQUALIZE) return true;
   return false;
+}
+
+// ---- geometric operations (JB_COLOR_SHEAR_X .. JB_COLOR_ROTATE): Pillow's nearest-neighbour affine transform ----
+JBC_FN bool jbc_is_warp(int op) { return op >= JB_COLOR_SHEAR_X && op <= JB_COLOR_ROTATE; }
+
+// where a chain's geometric operations stand (in order; jb_color_check allows JB_COLOR_WARPS_MAX); -1: none.  Beside JbcShape,
+// not in it: the kernels of the launches without a geometric operation never ask.
+struct JbcWarpShape {
+  int warp0, warp1;
+};
+static_assert(JB_COLOR_WARPS_MAX == 2, "JbcWarpShape names its geometric operations");
+JBC_FN JbcWarpShape jbc_warp_shape(const jb_color_chain &c) {
+  JbcWarpShape s;
+  s.warp0 = s.warp1 = -1;
+  for (int i = 0; i < c.n_ops && i < JB_COLOR_OPS_MAX; i++)
+    if (jbc_is_warp(c.ops[i].op)) {
+      if (s.warp0 < 0) s.warp0 = i;
+      else if (s.warp1 < 0) s.warp1 = i;
+    }
+  return s;
+}
+
+// one geometric operation as the kernels get it: Pillow's path and its six integers (jb_warp_params); 32 bytes
+struct JbWarp {
+  int32_t mode, coef[6], pad;
+};
+
+// (x, y) of the view behind the operation -> the position it reads in the view in front; false: outside the view.  The sums
+// wrap like Pillow's int additions: jb_warp_params takes the fixed path only where the corners' positions fit 16.16.
+JBC_FN bool jbc_warp_back(const JbWarp &k, int w, int h, int *x, int *y) {
+  int xin, yin;
+  if (k.mode == JB_WARP_SHIFT) {
+    xin = *x + k.coef[2], yin = *y + k.coef[5];
+  } else {
+    const uint32_t ux = (uint32_t)*x, uy = (uint32_t)*y;
+    xin = (int32_t)((uint32_t)k.coef[2] + uy * (uint32_t)k.coef[1] + ux * (uint32_t)k.coef[0]) >> 16;
+    yin = (int32_t)((uint32_t)k.coef[5] + uy * (uint32_t)k.coef[4] + ux * (uint32_t)k.coef[3]) >> 16;
+  }
+  *x = xin, *y = yin;
+  return xin >= 0 && xin < w && yin >= 0 && yin < h;
+}
+
+// Pixel (x, y) of the view AS IT STANDS in front of op `last` of a chain with geometric operations, from the w x h source
+// at src (rows `stride` bytes apart): (x, y) backwards through the geometric operations in front of `last` -- wk[0] is
+// ws.warp0's, wk[1] ws.warp1's --, three byte loads there, then ops [0, last) forwards, a geometric operation setting the
+// pixel to black where ITS position fell outside.  A position outside is replaced by (0, 0): every load lies inside the view.
+// The chain is uniform over a view; only the two selects are per pixel.
+template <bool NEW_OPS>
+JBC_FN void jbc_gather(const jb_color_chain &c, const JbcWarpShape &ws, int last, const JbcCtx &s, const JbWarp *wk, const uint8_t *src,
+                       int64_t stride, int w, int h, int x, int y, int *r, int *g, int *b) {
+  bool out0 = false, out1 = false;
+  if (ws.warp1 >= 0 && ws.warp1 < last) {
+    out1 = !jbc_warp_back(wk[1], w, h, &x, &y);
+    if (out1) x = 0, y = 0;
+  }
+  if (ws.warp0 >= 0 && ws.warp0 < last) {
+    out0 = !jbc_warp_back(wk[0], w, h, &x, &y);
+    if (out0) x = 0, y = 0;
+  }
+  const uint8_t *const from = src + (int64_t)y * stride + 3 * (int64_t)x;
+  *r = from[0], *g = from[1], *b = from[2];
+  for (int i = 0; i < last; i++) {
+    if (i == ws.warp0) {
+      if (out0) *r = 0, *g = 0, *b = 0;
+    } else if (i == ws.warp1) {
+      if (out1) *r = 0, *g = 0, *b = 0;
+    } else {
+      jbc_apply_op<NEW_OPS>(c.ops[i].op, c.ops[i].value, s, i, r, g, b);
+    }
+  }
+}
+
+// Python's round(x, 15): the correctly rounded decimal with 15 places, read back (host only)
+inline double jbc_round15(double x) {
+  char text[64];
+  snprintf(text, sizeof text, "%.15f", x);
+  return strtod(text, nullptr);
+}
+
+// The ONE text of a geometric operation's coefficients (include/jpegblk.h states it): the inverse matrix in doubles, one
+// operation per statement (built with -ffp-contract=off), then Pillow's choice of path.  Host only: the kernels get the integers.
+// JB_OK, JB_ERR_GEOMETRY (the value, the size or the op) or JB_ERR_UNSUPPORTED (Pillow's scaling or float path); *why says which.
+inline int jbc_warp_params(int op, float value, int32_t w, int32_t h, JbWarp *o, const char **why) {
+  *why = "the op is not geometric";
+  if (!jbc_is_warp(op)) return JB_ERR_GEOMETRY;
+  *why = "the size is outside 1..65535";
+  if (w < 1 || h < 1 || w > 65535 || h > 65535) return JB_ERR_GEOMETRY;
+  *why = "the value of a geometric operation is not finite";
+  if (!(value >= -3.402823466e38f && value <= 3.402823466e38f)) return JB_ERR_GEOMETRY;
+  const double v = (double)value;
+  const double pi = 3.141592653589793;
+  double m[6];
+  if (op == JB_COLOR_ROTATE) {
+    double deg = fmod(v, 360.0);  // Python's %: the result takes the divisor's sign
+    if (deg != 0.0) {
+      if (deg < 0.0) deg = deg + 360.0;
+    } else {
+      deg = 0.0;
+    }
+    const double rad = deg * (pi / 180.0);
+    const double g = -rad;
+    const double cg = cos(g), sg = sin(g);
+    // (two conversions, not four: a correctly rounded conversion is odd, round15(-s) = -round15(s))
+    const double rc = jbc_round15(cg), rs = jbc_round15(sg);
+    m[0] = rc, m[1] = rs, m[2] = 0.0;
+    m[3] = -rs, m[4] = rc, m[5] = 0.0;
+    const double cx = (double)w / 2.0, cy = (double)h / 2.0;
+    const double nx = -cx, ny = -cy;
+    const double p0 = m[0] * nx, p1 = m[1] * ny;
+    const double s01 = p0 + p1;
+    const double q0 = m[3] * nx, q1 = m[4] * ny;
+    const double s34 = q0 + q1;
+    m[2] = s01 + m[2];
+    m[5] = s34 + m[5];
+    m[2] = m[2] + cx;
+    m[5] = m[5] + cy;
+  } else {
+    double sx = 0.0, sy = 0.0, cx = 0.0, cy = 0.0, tx = 0.0, ty = 0.0;
+    if (op == JB_COLOR_SHEAR_X || op == JB_COLOR_SHEAR_Y) {
+      const double at = atan(v);
+      const double deg = at * (180.0 / pi);
+      const double rad = deg * (pi / 180.0);
+      if (op == JB_COLOR_SHEAR_X) sx = rad;
+      else sy = rad;
+    } else {
+      *why = "a translation is not integral or its absolute value is above 65535";
+      if (v != floor(v) || v < -65535.0 || v > 65535.0) return JB_ERR_GEOMETRY;
+      cx = (double)w * 0.5, cy = (double)h * 0.5;
+      if (op == JB_COLOR_TRANSLATE_X) tx = v;
+      else ty = v;
+    }
+    const double rot = 0.0;
+    const double rs = rot - sy;
+    const double crs = cos(rs), srs = sin(rs), csy = cos(sy), tsx = tan(sx), srot = sin(rot), crot = cos(rot);
+    const double A = crs / csy;
+    const double b0 = -crs;
+    const double b1 = b0 * tsx;
+    const double b2 = b1 / csy;
+    const double B = b2 - srot;
+    const double C = srs / csy;
+    const double d0 = -srs;
+    const double d1 = d0 * tsx;
+    const double d2 = d1 / csy;
+    const double D = d2 + crot;
+    m[0] = D, m[1] = -B, m[2] = 0.0, m[3] = -C, m[4] = A, m[5] = 0.0;
+    const double ex = -cx - tx, ey = -cy - ty;
+    const double p0 = m[0] * ex, p1 = m[1] * ey;
+    const double s01 = p0 + p1;
+    const double q0 = m[3] * ex, q1 = m[4] * ey;
+    const double s34 = q0 + q1;
+    m[2] = m[2] + s01;
+    m[5] = m[5] + s34;
+    m[2] = m[2] + cx;
+    m[5] = m[5] + cy;
+  }
+  JbWarp k;
+  k.pad = 0;
+  if (m[1] == 0.0 && m[3] == 0.0) {
+    *why = "a matrix of Pillow's scaling path (a rotation by 180 degrees is one)";
+    if (m[0] != 1.0 || m[4] != 1.0 || m[2] != floor(m[2]) || m[5] != floor(m[5])) return JB_ERR_UNSUPPORTED;
+    k.mode = JB_WARP_SHIFT;
+    k.coef[0] = k.coef[1] = k.coef[3] = k.coef[4] = 0;
+    k.coef[2] = (int32_t)m[2], k.coef[5] = (int32_t)m[5];
+  } else {
+    *why = "a matrix of Pillow's float path (a corner's position does not fit 16.16 fixed point)";
+    const double xs[4] = {0.0, (double)w, 0.0, (double)w}, ys[4] = {0.0, 0.0, (double)h, (double)h};
+    for (int i = 0; i < 4; i++) {
+      const double a0 = xs[i] * m[0], a1 = ys[i] * m[1];
+      const double a01 = a0 + a1;
+      const double ax = a01 + m[2];
+      const double c0 = xs[i] * m[3], c1 = ys[i] * m[4];
+      const double c01 = c0 + c1;
+      const double ay = c01 + m[5];
+      if (!(fabs(ax) < 32768.0) || !(fabs(ay) < 32768.0)) return JB_ERR_UNSUPPORTED;
+    }
+    const auto fix = [](double t) {
+      const double s = t * 65536.0;
+      const double u = s + 0.5;
+      return u < 0.0 ? (int32_t)floor(u) : (int32_t)u;
+    };
+    const double h0 = m[0] * 0.5, h1 = m[1] * 0.5, h3 = m[3] * 0.5, h4 = m[4] * 0.5;
+    const double e2 = m[2] + h0, e5 = m[5] + h3;
+    const double f2 = e2 + h1, f5 = e5 + h4;
+    const double all[6] = {m[0], m[1], f2, m[3], m[4], f5};
+    // (FIX must fit int32; with the corners inside +-32768 the five operations' matrices always do: not reached)
+    for (int i = 0; i < 6; i++)
+      if (!(fabs(all[i]) * 65536.0 + 0.5 < 2147483648.0)) return JB_ERR_UNSUPPORTED;
+    k.mode = JB_WARP_FIXED;
+    for (int i = 0; i < 6; i++) k.coef[i] = fix(all[i]);
+  }
+  *o = k;
+  *why = nullptr;
+  return JB_OK;
 }
 
 // ---- JB_COLOR_BLUR: Pillow's ImageFilter.GaussianBlur, three extended box blur passes along the rows, then three along

@@ -75,6 +75,11 @@ int jb_ext_scans_(jbe::Ext &x, int16_t *coef, size_t coef_cap_bytes, jbe::Err &e
 int jb_ext_decode_(const uint8_t *jpeg, size_t n, jb_image_desc *desc, uint16_t *qtabs, int16_t *coef, size_t coef_cap_bytes,
                    std::string *err);
 
+// ---- jb_color_host.cpp: "colour chains" -----------------------------------------------------------------------------
+// What jb_color_check cannot know: the geometric operations of n CHECKED chains on views of w x h -- jb_warp_params' refusals
+// that depend on the size.  JB_OK, or the status with *bad (may be null) the first such chain's index and *why the reason.
+int jb_color_check_size_(const jb_color_chain *chains, int64_t n, int32_t w, int32_t h, int64_t *bad, const char **why);
+
 // ---- jb_hostutil.cpp: host helpers without HIP ---------------------------------------------------------------------
 // seconds on the steady clock
 double jb_now_s_();

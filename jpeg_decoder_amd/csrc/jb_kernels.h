@@ -259,8 +259,25 @@ struct JbColor {
 // (with the sums, one memset) only in a launch with a table operation.  Where a chain has a JB_COLOR_SHARPNESS,
 // jb_color_sharp_kernel (a 64 x 32 tile, halo 1) writes those views; the apply kernel skips them as it skips blur views.  A
 // launch whose chains have none of these issues what it issued before: memset, mean, apply, blur.
+//
+// Geometric operations (JB_COLOR_SHEAR_X .. JB_COLOR_ROTATE): the launch turns each into Pillow's path and six integers on the
+// host (jbc_warp_params; the kernels never see a double): 32 bytes an operation, JB_COLOR_WARPS_MAX a view, 2 KB a launch.
+// They do NOT travel in the arguments: JbColor + JbColorTable + JbBlurTable are 3.3 KB of the 4 KB segment, and the blur
+// kernel of a chain with a geometric operation in front of its blur wants all three.  Fewer views a launch would have kept
+// them in the arguments at the price of a second table type and twice the launches of every augmentation batch; instead the
+// coefficients lie in the colour scratch BEHIND the tables (kJbColorWarpOffset), written on the stream in front of the
+// launch's kernels by jb_color_warp_table_kernel, which gets them as ITS arguments (2 KB), and read from there by view
+// (scalar loads: the view is the workgroup's).  Only a launch with a geometric operation writes them, and only such a launch
+// runs the kernels' WARP instantiations, whose every pixel load is jbc_gather (jb_color_core.h); a launch without one
+// issues the kernels it issued before there were any, with the warp text compiled out.
+// A view WITHOUT a geometric operation in a launch WITH one pays for its neighbours: the WARP instantiations gather it with
+// byte loads at its own positions, NEW_OPS is forced on, and its blur runs the NEW_OPS variant; measured per 224 x 224 / 96 x 96
+// view with the empty chain, one rotation among the launch's 32: 0.18 / 0.27 us over the plain launch's 0.45 / 0.55
+// (DESIGN.md 5.25).  Splitting such a launch in two would cost a launch (about 0.3 us a view) for the same views: not done.
 constexpr int64_t kJbColorCounterBytes = 768 * 4, kJbColorTableBytes = 768;
-constexpr int64_t kJbColorScratchBytes = 8 * kJbCropsPerLaunch + kJbCropsPerLaunch * JB_COLOR_STATS_MAX * (kJbColorCounterBytes + kJbColorTableBytes);
+constexpr int64_t kJbColorWarpOffset = 8 * kJbCropsPerLaunch + kJbCropsPerLaunch * JB_COLOR_STATS_MAX * (kJbColorCounterBytes + kJbColorTableBytes);
+constexpr int64_t kJbColorWarpBytes = kJbCropsPerLaunch * JB_COLOR_WARPS_MAX * 32;
+constexpr int64_t kJbColorScratchBytes = kJbColorWarpOffset + kJbColorWarpBytes;
 hipError_t jbk_color_launch(const JbColor &p, const JbColorTable &table, int format, hipStream_t stream);
 
 // "Fit" (jb_fit.hip jb_fit_fill_kernel): the border of n_images letterboxed outputs of ow x oh at dst, addressed as

@@ -478,6 +478,15 @@ int colors_check(jb_ctx *ctx, const jb_color_chain *colors, int64_t n, const cha
   const std::string why = jb_last_error(nullptr);
   return fail(ctx, rc, "%s: %s", fn, why.c_str());
 }
+// behind colors_check: the refusals of the geometric operations that depend on the views' size w x h (jb_color_check_size_), for
+// the n checked chains from flat index `first` on
+int colors_check_size(jb_ctx *ctx, const jb_color_chain *colors, int64_t first, int64_t n, int32_t w, int32_t h, const char *fn) {
+  int64_t bad = 0;
+  const char *why = nullptr;
+  const int rc = jb_color_check_size_(colors + first, n, w, h, &bad, &why);
+  if (rc == JB_OK) return JB_OK;
+  return fail(ctx, rc, "%s: colour chain %lld: %s on a view of %d x %d", fn, (long long)(first + bad), why, w, h);
+}
 
 // ---- what 3f ("views") and 3g ("view groups") share ------------------------------------------------------------------------
 // the union of image i's K sources: the bounding rectangle of its views' rectangles, with a filter of their windows.
@@ -594,6 +603,11 @@ int launch_view_runs(jb_ctx *ctx, const jb_device_batch *b, const jb_device_batc
   const bool colored = plan.colors != nullptr;
   if (colored)
     if (const int rc = colors_check(ctx, plan.colors, plan.n_views, fn)) return rc;
+  if (colored)  // (a run's views have the run's size)
+    for (int64_t i = 0; i < plan.n_views / plan.views_per_image; i++)
+      for (int q = 0; q < n_runs; q++)
+        if (const int rc = colors_check_size(ctx, plan.colors, i * plan.views_per_image + runs[q].first, runs[q].n, runs[q].plan.out_w, runs[q].plan.out_h, fn))
+          return rc;
   const auto staged_bytes_of = [&](int q) { return 3LL * runs[q].plan.out_w * runs[q].plan.out_h * runs[q].n; };  // of a run, per image
   int64_t staged_per_image = 0;
   for (int q = 0; q < n_runs; q++) staged_per_image += staged_bytes_of(q);
@@ -1016,6 +1030,8 @@ int jb_color_device(jb_ctx *ctx, const uint8_t *d_in, int64_t in_row_stride, int
   if (n_images > 1 && (in_image_stride < in_row_stride * (int64_t)(h - 1) + 3LL * w || out_image_stride < one_out))
     return fail(ctx, JB_ERR_GEOMETRY, "%s: image strides smaller than one image", fn);
   int rc = colors_check(ctx, chains, n_images, fn);
+  if (rc != JB_OK) return rc;
+  rc = colors_check_size(ctx, chains, 0, n_images, w, h, fn);
   if (rc != JB_OK) return rc;
   DeviceGuard guard(ctx->device);
   const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
